@@ -26,6 +26,9 @@ the LAST line of stdout (`compact_line`; the driver keeps only a bounded tail of
                    runs on, on every 5th timed step
   cpu_baseline     the oracle (CPU restatement) timed on the host cores on a bounded sample (rank 0, N = 1 only)
   exchange         N > 1: what the gradient exchange saw (world, backend, RCCL version, bucket bytes, CUs left to RCCL)
+`--dump-outputs DIR` (rank 0) writes what the headline's LAST timed step returned to its caller - `loss`, `loss_scale`, the updated
+`params` and their `grads`, fp32 - as DIR/<name>.npy, at most 64 MB in all (`write_outputs`).  Weights, batches and RNG streams are
+seeded, so the same arguments give the same inputs on every run: two builds can be compared output for output.
 """
 import argparse
 import json
@@ -101,7 +104,7 @@ def kernel_hash():
     return h.hexdigest()[:16]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -119,7 +122,12 @@ def parse():
     ap.add_argument("--cpu_seconds", type=float, default=15.0)
     ap.add_argument("--no_cpu", action="store_true")
     ap.add_argument("--no_profile", action="store_true", help="skip the per-launch HIP events")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed train step returned to DIR/<name>.npy (fp32; see step_outputs)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def synthetic_batch(B, C, S, device, seed):
@@ -178,6 +186,43 @@ def cpu_baseline(seconds, S, in_channels):
             "sample": f"oracle (torch-CPU restatement) train step, B=32, {in_channels}x{S}x{S}, C=128, fp32, "
                       f"{n} steps in {t_total:.1f} s after 1 warm-up",
             "sampler_steps_per_sec": round(ns / ts, 2), "sampler_sample": f"oracle DDIM, guidance off, B=32, {ns} steps in {ts:.2f} s"}
+
+
+DUMP_LIMIT = 64 << 20    # bytes of all --dump-outputs files together
+DUMP_WHOLE = 1 << 16     # arrays of at most this many elements are always written whole
+
+
+def step_outputs(model, metrics):
+    """What a caller of `train_step` holds after the step: the metrics it returned, the updated parameters and their gradients (`p.grad`),
+    each parameter in the reference's shape (narrow widths without their zero padding), concatenated in sorted-name order; fp32 on the host."""
+    net = model.net
+    names = sorted(n for n, _ in net.named_parameters())
+    out = {k: v.detach().float().cpu() for k, v in metrics.items()}
+    out["params"] = torch.cat([net.param(n).detach().float().reshape(-1) for n in names]).cpu()
+    out["grads"] = torch.cat([net.grad(n).float().reshape(-1) for n in names]).cpu()
+    return out
+
+
+def write_outputs(d, arrays, limit=DUMP_LIMIT):
+    """name -> tensor  =>  d/<name>.npy in fp32.  If everything would exceed `limit` bytes, each array above DUMP_WHOLE elements is cut to
+    the same number of positions drawn by a fixed seed (arrays of one length share their positions), so the files stay comparable
+    between runs and builds.  -> {name: [shape, sampled]}"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    big = [k for k, t in arrays.items() if t.numel() > DUMP_WHOLE]
+    room = limit - 256 * len(arrays) - 4 * sum(t.numel() for k, t in arrays.items() if k not in big)    # (256: a .npy header's bound)
+    keep = room // (4 * len(big)) if big else 0
+    sampled = 4 * sum(arrays[k].numel() for k in big) > room
+    written = {}
+    for k, t in arrays.items():
+        a = t.detach().float().cpu()
+        cut = sampled and k in big
+        if cut:
+            pos = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(d, f"{k}.npy"), a.numpy().astype(np.float32))
+        written[k] = [list(a.shape), cut]
+    return written
 
 
 LINE_LIMIT = 4096        # bytes of the last stdout line (the driver keeps a bounded tail of stdout and parses its last line)
@@ -333,7 +378,7 @@ class Bench:
             # the weight gradients on the main stream (they run ~4 % slower than the other steps, which is inside `value`)
             ops.WGRAD_STREAM = side and ops.PROFILE is None
             x, y = batches[i % len(batches)]
-            model.train_step(x, y.clone())
+            self.last_metrics = model.train_step(x, y.clone())
         ops.WGRAD_STREAM = side
         self.barrier()
         elapsed = self.max_over_ranks(time.perf_counter() - t0)
@@ -448,6 +493,7 @@ class Bench:
                  attention=attention)
         hidden = a.hidden if key == "custom" else 128
         G.hidden_size = hidden
+        torch.manual_seed(G.seed)            # the net's default init draws from torch's global generator: the same weights every run
         model = Model(G).to(self.dev)
         model.size = S
         from generative_models_amd import parallel
@@ -462,6 +508,9 @@ class Bench:
             model.train_step(x, y.clone())
         prof = None if a.no_profile else []
         elapsed, nprof = self.timed_steps(model, batches, steps, prof)
+        if headline and a.dump_outputs and self.rank == 0:      # the last timed step's results, before anything else runs on the model
+            written = write_outputs(a.dump_outputs, step_outputs(model, self.last_metrics))
+            print(f"--dump-outputs: {written} -> {a.dump_outputs}", file=sys.stderr)
         ips = self.world * B * steps / elapsed
         out = {"workload": f"DDPM train step, {cin}x{S}x{S}, SimpleUnet C={hidden}{' + self-attention' + (' (fp8 QK^T / PV)' if attention == 2 else '') if attention else ''}, "
                            f"{B} images per GPU, T=1000 (BASELINE.json {what.split(':')[0]})", "baseline_entry": what,

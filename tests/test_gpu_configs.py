@@ -475,3 +475,31 @@ def test_sized_goldens_vs_reference(golden, name, cin, S, dtype, forced):
         lib.gmk_set_kernel_choice(-1, -1, -1)
         SIZED_REPORT[(name, str(dtype), forced)] = rep
         print("sized", name, dtype, "forced" if forced else "auto", {k: f"{v:.2e}" for k, v in rep.items()})
+
+
+def test_bench_dump_outputs_are_the_last_timed_step_and_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR`: the headline's last timed train step as a caller holds it (loss, loss_scale, updated parameters and their
+    gradients in the reference's shapes), fp32, and bit-identical between two runs with the same arguments (seeded weights, batches and RNG
+    streams; every kernel of the step is deterministic).  3x32x32 at a batch above the graphed-step limit: the kernel-by-kernel path of the headline."""
+    import json
+    from oracle import unet_ref as U
+    flags = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "custom", "--batch", "128", "--size", "32", "--in_channels", "3",
+             "--sampler_steps", "0", "--others", "0", "--no_cpu"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    runs = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + flags + ["--dump-outputs", str(d)], capture_output=True,
+                           text=True, timeout=900, cwd=ROOT, env=dict(env, OMP_NUM_THREADS="2", GMK_BENCH_STEADY_STEPS="4",
+                                                                      GMK_BENCH_DETAIL=str(tmp_path / f"detail_{name}.json")))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        runs.append({k: np.load(d / f"{k}.npy") for k in ("loss", "loss_scale", "params", "grads")})
+    a, b = runs
+    n = sum(v.numel() for v in U.reference_init_params(128, 3).values())
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].shape == () and np.isfinite(a["loss"]) and float(a["loss_scale"]) == 1.0
+    assert a["params"].shape == a["grads"].shape == (n,) and np.isfinite(a["grads"]).all() and np.abs(a["grads"]).max() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k

@@ -595,6 +595,37 @@ def test_bench_line_stays_inside_the_drivers_window():
     assert len(bench.compact_line(fat)) <= bench.LINE_LIMIT
 
 
+def test_bench_arguments_and_output_dump(tmp_path):
+    """`--steps` is the number of timed steps (at least one), `--dump-outputs DIR` writes fp32 .npy files: small arrays whole, and past the
+    64 MB limit the large ones cut to one seeded set of positions, the same on every call and for every array of one length."""
+    import bench
+    a = bench.parse(["--steps", "7", "--warmup", "0", "--dump-outputs", str(tmp_path / "d")])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == str(tmp_path / "d")
+    assert bench.parse([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+    g = torch.Generator().manual_seed(1)
+    arrays = {"loss": torch.tensor(0.25, dtype=torch.float64), "params": torch.randn(3000, 50, generator=g),
+              "grads": torch.randn(150000, generator=g).to(torch.bfloat16)}
+    w = bench.write_outputs(str(tmp_path / "whole"), arrays)
+    assert w == {"loss": [[], False], "params": [[3000, 50], False], "grads": [[150000], False]}
+    for k, t in arrays.items():
+        f = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert f.dtype == np.float32 and np.array_equal(f, t.float().numpy())
+    limit = 4 * 100000
+    for d in ("cut1", "cut2"):
+        w = bench.write_outputs(str(tmp_path / d), arrays, limit=limit)
+        assert w == {"loss": [[], False], "params": [[49903], True], "grads": [[49903], True]}
+        assert sum(os.path.getsize(tmp_path / d / f"{k}.npy") for k in arrays) <= limit
+    p1, g1 = (np.load(tmp_path / "cut1" / f"{k}.npy") for k in ("params", "grads"))
+    assert np.array_equal(p1, np.load(tmp_path / "cut2" / "params.npy")) and np.array_equal(g1, np.load(tmp_path / "cut2" / "grads.npy"))
+    flat = arrays["params"].reshape(-1).numpy()
+    idx = np.array([int(np.flatnonzero(flat == v)[0]) for v in p1[:200]])      # sampled values are entries of the array, in position order
+    assert np.all(np.diff(idx) > 0)
+    assert np.array_equal(g1[:200], arrays["grads"].float().numpy()[idx])  # the same positions in both arrays of one length
+
+
 def test_bench_launcher_branch_starts_ranks_without_touching_the_gpu():
     """Plain `python bench.py --gpus N` (no WORLD_SIZE: how the driver has called bench.py so far) must start its own N ranks as a child
     `torch.distributed.run`, from a process that has not initialised the GPU; with WORLD_SIZE set (the documented launcher form) or N = 1
@@ -616,32 +647,30 @@ def test_bench_launcher_branch_starts_ranks_without_touching_the_gpu():
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and int(cmd[cmd.index("--master-port") + 1]) > 0
     k = cmd.index(os.path.join(ROOT, "bench.py"))
     assert cmd[k + 1:] == ["--gpus", "4", "--steps", "7", "--warmup", "2"]
-    # the child's exit code is the parent's: a launcher that cannot start its ranks must not look like a finished bench
+    # the child's exit code is the parent's: a launcher that cannot start its ranks must not look like a finished bench (the ranks see no
+    # device, on a machine with a GPU too)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--no_cpu"],
-                       capture_output=True, text=True, timeout=600, env=dict(env, GMK_DIST_BACKEND="gloo", OMP_NUM_THREADS="1"))
-    assert r.returncode != 0 and "bench.py needs an MI355X" in r.stderr       # (no GPU here: both ranks refuse, loudly)
+                       capture_output=True, text=True, timeout=600, env=dict(env, GMK_DIST_BACKEND="gloo", OMP_NUM_THREADS="1",
+                                                                             HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1"))
+    assert r.returncode != 0 and "bench.py needs an MI355X" in r.stderr       # (no visible GPU: both ranks refuse, loudly)
 
 
 def _device_asm(src_name):
-    """gfx950 assembly of one kernel source (hipcc -S, device only), cached under /tmp by source hash: a few seconds per file."""
-    import hashlib
+    """gfx950 assembly of one kernel source (hipcc -S, device only), compiled from the tree into a temporary directory: a few seconds per file."""
     import shutil
+    import tempfile
     csrc = os.path.join(ROOT, "generative_models_amd", "csrc")
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not found")
-    h = hashlib.sha1()
-    for f in (src_name, "gmk_common.h", os.path.join(ROOT, "include", "gmk.h")):
-        h.update(open(os.path.join(csrc, f), "rb").read())
-    out = f"/tmp/gmk_isa_{src_name}_{h.hexdigest()[:12]}.s"
-    if not os.path.exists(out):
-        flags = re.search(r"^HIPFLAGS\s*[:+]?=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M)
+    flags = re.search(r"^HIPFLAGS\s*[:+]?=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M)
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, src_name + ".s")
         cmd = [hipcc] + (flags.group(1).split() if flags else ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off"])
-        cmd = [c for c in cmd if c != "-fPIC"] + ["--cuda-device-only", "-S", os.path.join(csrc, src_name), "-o", out + ".tmp"]
+        cmd = [c for c in cmd if c != "-fPIC"] + ["--cuda-device-only", "-S", os.path.join(csrc, src_name), "-o", out]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
-        os.replace(out + ".tmp", out)
-    return open(out).read().splitlines()
+        return open(out).read().splitlines()
 
 
 def _regs(operand_text):
@@ -757,9 +786,7 @@ def _check_register_loads_in_flight(src, name_regex, n_instances, vm_per_step, m
                     retired = True
                 ops = t.split(None, 1)[1] if " " in t and not t.endswith(":") else ""
                 if not t.endswith(":") and _regs(ops) & dest:
-                    if not retired:
-                        open("/tmp/gmk_isa_trace.txt", "w").write(trace(st).replace(" <- ", "\n"))
-                    assert retired, (name, ins[k0], "touched while possibly in flight by", t, "path in /tmp/gmk_isa_trace.txt")
+                    assert retired, (name, ins[k0], "touched while possibly in flight by", t, "path: " + trace(st))
                     # the consumers: the fp16 -> fp32 conversion of an activation chunk, the LDS write of a dY chunk (no conversion)
                     hit = hit or t.startswith("v_cvt_f32_f16") or t.startswith("ds_write_b128")
                     continue                                   # the value is consumed or dead behind this instruction
