@@ -2,7 +2,8 @@
 // Reference: gms/diffusion/gaussian_diffusion.py (training_losses :81-172, _run_model :61-77, _cf_guidance :174-187,
 // ddim_step :189-213, reverse_dpm_step :215-243, sample :292) and gms/diffusion/diffusion_utils.py
 // (diffusion_forward :65-73, diffusion_reverse :34-62, predict_* :76-105, _logsnr_schedule_cosine :198-201);
-// torch.optim.Adam as diffusion_model.py:56 constructs it.
+// torch.optim.Adam as diffusion_model.py:56 constructs it.  gmk_adam_ema_step's weight average has no reference call site (the
+// reference keeps no EMA): an extension, defined by torch.lerp.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -191,6 +192,25 @@ __global__ __launch_bounds__(256) void rng_kernel(float* __restrict__ out, int64
     }
 }
 
+// One Adam update of one element: the single definition behind adam_kernel and adam_ema_kernel, so the two produce the same bits for
+// p, m and v (the library builds with -ffp-contract=off; a second copy of these lines would still be a second place for them to drift).
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float step_size, float beta1, float beta2, float eps,
+                                          float inv_bc2_sqrt, float grad_scale) {
+    const float gg = g * grad_scale;
+    m = m + (gg - m) * (1.0f - beta1);             // exp_avg.lerp_(grad, 1 - beta1)
+    v = v * beta2 + (1.0f - beta2) * gg * gg;      // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
+    const float denom = sqrtf(v) * inv_bc2_sqrt + eps;
+    p = p - step_size * (m / denom);
+}
+
+// ema.lerp_(p, w) with torch.lerp's two forms: start + w (end - start) below w = 0.5, end - (end - start)(1 - w) from 0.5 up, so w = 1
+// gives end exactly and w = 0 gives start exactly.  Each form is one fused multiply-add (one rounding), as torch's device lerp is compiled;
+// w is uniform across the launch: no divergence.
+__device__ __forceinline__ float lerp_to(float start, float end, float w) {
+    const float diff = end - start;
+    return w < 0.5f ? fmaf(w, diff, start) : fmaf(-diff, 1.0f - w, end);
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                   float* __restrict__ v, int64_t n, float step_size, float beta1,
                                                   float beta2, float eps, float inv_bc2_sqrt, float grad_scale) {
@@ -199,23 +219,41 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         float pv[4], gv[4], mv[4], vv[4];
         load4(p + q * 4, pv); load4(g + q * 4, gv); load4(m + q * 4, mv); load4(v + q * 4, vv);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float gg = gv[k] * grad_scale;
-            mv[k] = mv[k] + (gg - mv[k]) * (1.0f - beta1);             // exp_avg.lerp_(grad, 1 - beta1)
-            vv[k] = vv[k] * beta2 + (1.0f - beta2) * gg * gg;          // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
-            const float denom = sqrtf(vv[k]) * inv_bc2_sqrt + eps;
-            pv[k] = pv[k] - step_size * (mv[k] / denom);
-        }
+        for (int k = 0; k < 4; ++k) adam_elem(pv[k], gv[k], mv[k], vv[k], step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
         store4(p + q * 4, pv); store4(m + q * 4, mv); store4(v + q * 4, vv);
     }
     // tail (n not a multiple of 4)
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const int64_t i = nq * 4 + threadIdx.x;
-        const float gg = g[i] * grad_scale;
-        const float mm = m[i] + (gg - m[i]) * (1.0f - beta1);
-        const float vv = v[i] * beta2 + (1.0f - beta2) * gg * gg;
-        m[i] = mm; v[i] = vv;
-        p[i] = p[i] - step_size * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps));
+        float pp = p[i], mm = m[i], vv = v[i];
+        adam_elem(pp, g[i], mm, vv, step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
+        m[i] = mm; v[i] = vv; p[i] = pp;
+    }
+}
+
+// Adam, then the EMA of the updated weights in the same pass: ema = lerp(ema, p_new, ema_w).  p is read once, so the EMA costs its own
+// read and write only (36 B / parameter against Adam's 28).
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, float* __restrict__ ema, int64_t n, float step_size,
+                                                      float beta1, float beta2, float eps, float inv_bc2_sqrt, float grad_scale,
+                                                      float ema_w) {
+    const int64_t nq = n / 4;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+        float pv[4], gv[4], mv[4], vv[4], ev[4];
+        load4(p + q * 4, pv); load4(g + q * 4, gv); load4(m + q * 4, mv); load4(v + q * 4, vv); load4(ema + q * 4, ev);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            adam_elem(pv[k], gv[k], mv[k], vv[k], step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
+            ev[k] = lerp_to(ev[k], pv[k], ema_w);
+        }
+        store4(p + q * 4, pv); store4(m + q * 4, mv); store4(v + q * 4, vv); store4(ema + q * 4, ev);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t i = nq * 4 + threadIdx.x;
+        float pp = p[i], mm = m[i], vv = v[i];
+        adam_elem(pp, g[i], mm, vv, step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
+        m[i] = mm; v[i] = vv; p[i] = pp;
+        ema[i] = lerp_to(ema[i], pp, ema_w);
     }
 }
 
@@ -352,15 +390,32 @@ extern "C" int gmk_distill_target(const float* z_teacher, const float* z_t, cons
     return gmk_check_launch("gmk_distill_target");
 }
 
+// scalar prologue in double, as torch.optim.adam._single_tensor_adam does on the host
+static void adam_scalars(float lr, float beta1, float beta2, int step, float* step_size, float* inv_bc2_sqrt) {
+    const double bc1 = 1.0 - pow((double)beta1, step);
+    const double bc2 = 1.0 - pow((double)beta2, step);
+    *step_size = (float)((double)lr / bc1);
+    *inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+}
+
 extern "C" int gmk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                              float eps, int step, float grad_scale, void* stream) {
     GMK_REQUIRE(p && g && m && v && n > 0 && step >= 1, "gmk_adam_step: bad arguments");
-    // scalar prologue in double, as torch.optim.adam._single_tensor_adam does on the host
-    const double bc1 = 1.0 - pow((double)beta1, step);
-    const double bc2 = 1.0 - pow((double)beta2, step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    float step_size, inv_bc2_sqrt;
+    adam_scalars(lr, beta1, beta2, step, &step_size, &inv_bc2_sqrt);
     adam_kernel<<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, n, step_size, beta1, beta2, eps,
                                                                         inv_bc2_sqrt, grad_scale);
     return gmk_check_launch("gmk_adam_step");
+}
+
+extern "C" int gmk_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1,
+                                 float beta2, float eps, int step, float grad_scale, float ema_w, void* stream) {
+    GMK_REQUIRE(p && g && m && v && n > 0 && step >= 1, "gmk_adam_ema_step: bad arguments");
+    GMK_REQUIRE(ema, "gmk_adam_ema_step: ema is null");
+    GMK_REQUIRE(ema_w >= 0.0f && ema_w <= 1.0f, "gmk_adam_ema_step: ema_w = %g outside [0, 1]", (double)ema_w);
+    float step_size, inv_bc2_sqrt;
+    adam_scalars(lr, beta1, beta2, step, &step_size, &inv_bc2_sqrt);
+    adam_ema_kernel<<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, ema, n, step_size, beta1, beta2, eps,
+                                                                            inv_bc2_sqrt, grad_scale, ema_w);
+    return gmk_check_launch("gmk_adam_ema_step");
 }

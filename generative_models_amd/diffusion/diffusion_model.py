@@ -53,6 +53,8 @@ def make_plugin(GMBase, AttrDict):
         DG.attention = 0               # 1: self-attention block behind `turn` (north_star / BASELINE config 5; not in the reference); 2: the same
                                        # with QK^T / PV on the fp8 matrix cores
         DG.seed = 0
+        DG.ema_decay = 0.0             # > 0: keep an exponential moving average of the weights (`ema_net`, updated inside the fused Adam launch)
+                                       # and sample / evaluate with it; not in the reference, off by default
 
         def __init__(self, G):
             super().__init__(G)
@@ -79,10 +81,49 @@ def make_plugin(GMBase, AttrDict):
                                                teacher_mode=get("teacher_mode"), sample_cond_w=get("sample_cond_w"),
                                                seed=seed)
             self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
-            self.optimizer = FusedAdam(self.net, lr=G.lr if "lr" in G else 3e-4)
+            # EMA of the weights (an extension): a second SimpleUnet of the same arena layout, so one fused launch updates both.  It is seeded
+            # from `net` at the first optimiser step (after a data-parallel broadcast of the initial weights) or by a checkpoint load.
+            self.ema_decay = float(get("ema_decay"))
+            self.ema_net = None
+            if self.ema_decay > 0:
+                self.ema_net = SimpleUnet(get("hidden_size"), get("dropout"), in_channels=get("in_channels"),
+                                          compute_dtype=cdt, attention=int(get("attention")), act_dtype=adt)
+                for param in self.ema_net.parameters():
+                    param.requires_grad = False
+                self.ema_net.eval()
+            self.optimizer = FusedAdam(self.net, lr=G.lr if "lr" in G else 3e-4, ema_net=self.ema_net, ema_decay=self.ema_decay)
             self.size = 32 if ("pad32" in G and G.pad32) else 28
             self._aux_rng = PhiloxStream(seed + 7919)
             self._sync = None
+
+        def train(self, mode=True):
+            super().train(mode)
+            if self.ema_net is not None:            # the average is never trained: no dropout in its forwards
+                self.ema_net.eval()
+            return self
+
+        def load_state_dict(self, state_dict, strict=True, assign=False):
+            if getattr(self, "ema_net", None) is None:          # EMA off (or the teacher load inside __init__, before the EMA net exists)
+                return super().load_state_dict(state_dict, strict=strict, assign=assign)
+            if not any(k.startswith("ema_net.") for k in state_dict):      # an ordinary checkpoint: the average restarts from the loaded weights
+                out = super().load_state_dict(state_dict, strict=False, assign=assign)
+                missing = [k for k in out.missing_keys if not k.startswith("ema_net.")]
+                if strict and (missing or out.unexpected_keys):
+                    raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing {missing}, "
+                                       f"unexpected {out.unexpected_keys}")
+                self.optimizer.seed_ema()
+                return type(out)(missing, out.unexpected_keys)
+            out = super().load_state_dict(state_dict, strict=strict, assign=assign)
+            self.optimizer.ema_seeded = True
+            return out
+
+        def _sampling_net(self):
+            """The network sample() and evaluate() run: the weight average when EMA is on."""
+            if self.ema_net is None:
+                return self.net
+            if not self.optimizer.ema_seeded:
+                self.optimizer.seed_ema()
+            return self.ema_net
 
         # -- training (diffusion_model.py:63-74)
         def train_step(self, x, y):
@@ -176,7 +217,7 @@ def make_plugin(GMBase, AttrDict):
             with torch.no_grad():
                 dev = self.net.flat_params.device
                 noise = self._aux_rng.normal((n, self.net.in_channels, self.size, self.size), dev)
-                net = partial(self.net, guide=y)
+                net = partial(self._sampling_net(), guide=y)
                 cond_w = 0.5 if y is not None else None
                 return self.diffusion.sample(net=net, init_x=noise, cond_w=cond_w, record=False)[0][-1]
 
@@ -191,7 +232,7 @@ def make_plugin(GMBase, AttrDict):
             stream = PhiloxStream(0)                                  # :99 torch.manual_seed(0)
             noise = stream.normal((25, self.net.in_channels, self.size, self.size), x.device)
             labels = torch.arange(25, dtype=torch.long, device=x.device) % 10   # :101
-            zs, xs, eps = self.diffusion.sample(net=partial(self.net, guide=labels), init_x=noise)
+            zs, xs, eps = self.diffusion.sample(net=partial(self._sampling_net(), guide=labels), init_x=noise)
             zs, xs, eps = proc(zs), proc(xs), proc(eps)
             self.last_eval = {"samples": zs[-1], "sampling_process": zs, "eps": eps, "x": xs}
             if writer is not None and self.net.in_channels == 1:        # :105-110, same tags

@@ -819,6 +819,16 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     check(lib.gmk_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, step, grad_scale, _s()), "adam_step")
 
 
+def adam_ema_step(p, g, m, v, ema, lr, beta1, beta2, eps, step, decay_t, grad_scale=1.0):
+    """adam_step, then ema.lerp_(p_new, 1 - decay_t) in the same pass over the arenas (gmk_adam_ema_step).  p, m, v come out the same bits as
+    adam_step's."""
+    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
+        _f32(t, nm)
+    assert p.numel() == g.numel() == m.numel() == v.numel() == ema.numel()
+    check(lib.gmk_adam_ema_step(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, step, grad_scale,
+                                1.0 - float(decay_t), _s()), "adam_ema_step")
+
+
 # ---- self-attention core (north_star extension; no reference call site) -----------------------------------------
 def bgemm_nt(A, B, out=None, alpha=1.0, out_dtype=None):
     """C[b] = alpha * A[b] @ B[b]^T for batches of K-contiguous matrices (row / batch strides free): A [batch, M, K],

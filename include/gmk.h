@@ -326,6 +326,12 @@ int gmk_distill_target(const float* z_teacher, const float* z_t, const float* x_
 /* ---- optimiser (torch.optim.Adam defaults as diffusion_model.py:56 uses it), flat fp32 arena ------------- */
 int gmk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, int step, float grad_scale, void* stream);
+/* Adam exactly as gmk_adam_step (the same p, m, v bits), then an exponential moving average of the updated weights in the same pass:
+ * ema = lerp(ema, p_new, ema_w), torch.lerp's formula (ema + ema_w (p_new - ema) for ema_w < 0.5, p_new - (p_new - ema)(1 - ema_w) above),
+ * ema_w = 1 - decay in [0, 1].  No reference call site: the reference keeps no EMA of its weights (an extension, off by default in
+ * DiffusionModel, DG.ema_decay).  ema: a second arena of n floats, same layout.  36 B / parameter against Adam's 28. */
+int gmk_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
+                      float eps, int step, float grad_scale, float ema_w, void* stream);
 
 #ifdef __cplusplus
 }
