@@ -3,7 +3,7 @@
 // ddim_step :189-213, reverse_dpm_step :215-243, sample :292) and gms/diffusion/diffusion_utils.py
 // (diffusion_forward :65-73, diffusion_reverse :34-62, predict_* :76-105, _logsnr_schedule_cosine :198-201);
 // torch.optim.Adam as diffusion_model.py:56 constructs it.  gmk_adam_ema_step's weight average has no reference call site (the
-// reference keeps no EMA): an extension, defined by torch.lerp.
+// reference keeps no EMA): an extension, defined by torch.lerp.  gmk_dpm_solver_step (DPM-Solver++(2M)) is an extension too.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -165,6 +165,47 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
     }
 }
 
+// grid (ceil(n/256), B): one DPM-Solver++(2M) step (Lu et al. 2022, Algorithm 2, data prediction) on the DDIM time grid.  x-hat / eps-hat
+// and the guidance exactly as sampler_step_kernel forms them; then D = (1 + k) x_hat - k x_prev (k = 1 / 2r, 0 on the first step: x_prev
+// is then not read) and z_s = c_z z + c_x D with c_z = sigma_s / sigma_t, c_x = -alpha_s expm1(-h), all three from the host.  x_hist
+// holds the previous step's x-hat on entry and this step's on exit (same element, same thread).  An extension: no reference call site.
+__global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __restrict__ v, const float* __restrict__ vu,
+                                                             const float* __restrict__ cond_w, const float* __restrict__ z,
+                                                             float* __restrict__ x_hist, float lt, float ls, float c_z, float c_x,
+                                                             float k_prev, int is_last, float* __restrict__ z_next,
+                                                             float* __restrict__ x_pred, float* __restrict__ eps_pred,
+                                                             float* __restrict__ z_dup, float* __restrict__ logsnr_next, int64_t n,
+                                                             int mt) {
+    const int b = blockIdx.y;
+    if (logsnr_next && blockIdx.x == 0 && threadIdx.x == 0) {
+        logsnr_next[b] = ls;
+        if (z_dup) logsnr_next[gridDim.y + b] = ls;
+    }
+    const LogsnrCoef c = logsnr_coef(lt);
+    const float w = cond_w ? cond_w[b] : 0.f;
+    const bool second_order = k_prev != 0.0f;            // uniform across the launch
+    const int64_t base = (int64_t)b * n;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float zz = z[base + i];
+        float xh = clip1(x_from_out(v[base + i], zz, c, mt));
+        float eh = c.c1 * (zz - xh * c.c2);
+        if (vu) {
+            const float xu = clip1(x_from_out(vu[base + i], zz, c, mt));
+            const float eu = c.c1 * (zz - xu * c.c2);
+            const float e = (1.0f + w) * eh + (-w) * eu;
+            xh = clip1(c.d1 * (zz - e * c.d2));
+            eh = c.c1 * (zz - xh * c.c2);
+        }
+        const float d = second_order ? (1.0f + k_prev) * xh - k_prev * x_hist[base + i] : xh;
+        const float zs = c_z * zz + c_x * d;
+        x_hist[base + i] = xh;
+        z_next[base + i] = is_last ? xh : zs;
+        if (z_dup) z_dup[base + i] = is_last ? xh : zs;
+        if (x_pred) x_pred[base + i] = xh;
+        if (eps_pred) eps_pred[base + i] = eh;
+    }
+}
+
 template <bool NORMAL>
 __global__ __launch_bounds__(256) void rng_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
     const int64_t nq = (n + 3) / 4;
@@ -312,6 +353,24 @@ extern "C" int gmk_sampler_step(const float* v, const float* v_uncond, const flo
                                                                      is_last, z_next, x_pred, eps_pred, n, nullptr, nullptr, mean_type,
                                                                      z_dup, logsnr_next);
     return gmk_check_launch("gmk_sampler_step");
+}
+
+extern "C" int gmk_dpm_solver_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float* x_hist,
+                                   float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last,
+                                   float* z_next, float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type,
+                                   int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && z && x_hist && z_next, "gmk_dpm_solver_step: null pointer");
+    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "gmk_dpm_solver_step: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_dpm_solver_step: v_uncond and cond_w go together");
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_dpm_solver_step: bad shape");
+    GMK_REQUIRE(isfinite(logsnr_t) && isfinite(logsnr_s) && isfinite(coef_z) && isfinite(coef_x) && isfinite(coef_prev),
+                "gmk_dpm_solver_step: non-finite time or coefficient");
+    int gx = (int)((n + 255) / 256);
+    if (gx > 64) gx = 64;
+    dpm_solver_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, x_hist, logsnr_t, logsnr_s, coef_z,
+                                                                        coef_x, coef_prev, is_last, z_next, x_pred, eps_pred, z_dup,
+                                                                        logsnr_next, n, mean_type);
+    return gmk_check_launch("gmk_dpm_solver_step");
 }
 
 extern "C" int gmk_ddim_step_vec(const float* v, const float* v_uncond, const float* cond_w, const float* z,

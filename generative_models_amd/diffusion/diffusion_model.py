@@ -33,10 +33,10 @@ def make_plugin(GMBase, AttrDict):
     class DiffusionModel(GMBase):
         DG = AttrDict()  # default G  (diffusion_model.py:15-29)
         DG.binarize = 0
-        DG.timesteps = 250
+        DG.timesteps = 250             # sampler steps (network evaluations per sample); also the distillation discretisation (teacher_path)
         DG.hidden_size = 128
         DG.dropout = 0.0
-        DG.sampler = "ddim"
+        DG.sampler = "ddim"            # 'ddim' | 'noisy' | 'teacher_test' (reference) | 'dpmpp_2m' (extension: DPM-Solver++(2M), second order, no training)
         DG.mean_type = "v"
         DG.eval_heavy = 1
         DG.class_cond = 1

@@ -7,6 +7,7 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
 * q_sample + log-SNR schedule          gmk_q_sample     (:94-100, diffusion_utils.py:65-73,198-201)
 * v -> x_hat/eps_hat, clip, loss, dL/dv gmk_v_loss       (:61-77,:165-169 and their backward)
 * DDIM / ancestral / guidance update   gmk_sampler_step (:174-243,:292)
+* DPM-Solver++(2M) update              gmk_dpm_solver_step (sampler='dpmpp_2m': an extension, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -14,8 +15,10 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
 distillation (:87-91,:105-154) is supported: `teacher_net` is a frozen HIP `SimpleUnet`; teacher DDIM
 steps run through gmk_ddim_step_vec / gmk_distill_target, the student is conditioned on the guidance weight.
 """
+from collections import namedtuple
 from functools import partial
 
+import math
 import os
 
 import numpy as np
@@ -37,6 +40,30 @@ def logsnr_schedule_cosine_host(u):
     """diffusion_utils.py:198-201 for a host scalar, all in fp32."""
     u = np.float32(u)
     return np.float32(-2.0) * np.log(np.tan(SCHED_A * u + SCHED_B, dtype=np.float32), dtype=np.float32)
+
+
+DpmCoef = namedtuple("DpmCoef", "i lt ls h coef_z coef_x coef_prev")
+
+
+def dpm_solver_coefs(num_steps):
+    """Per-step coefficients of sampler='dpmpp_2m' (DPM-Solver++(2M), Lu et al. 2022, Algorithm 2, data prediction; an extension with no
+    reference call site), one row per loop iteration i = T-1 ... 0 on DDIM's time grid.  lt / ls are the fp32 log-SNRs the DDIM path uses;
+    with lambda = logsnr / 2, alpha = sqrt(sigmoid(logsnr)), sigma = sqrt(sigmoid(-logsnr)) and h = lambda_s - lambda_t:
+      coef_z = sigma_s / sigma_t, coef_x = -alpha_s expm1(-h), coef_prev = 1 / (2 r), r = h_prev / h,
+    so that z_s = coef_z z_t + coef_x ((1 + coef_prev) x_hat - coef_prev x_hat_prev).  coef_prev is 0 on the first step (first order: DDIM's
+    update) and on the last (i == 0 returns x_hat itself, gaussian_diffusion.py:292), so T <= 2 is DDIM.  All in float64 from the fp32 log-SNRs."""
+    sigma = lambda l: math.sqrt(1.0 / (1.0 + math.exp(l)))
+    alpha = lambda l: math.sqrt(1.0 / (1.0 + math.exp(-l)))
+    rows, h_prev = [], None
+    for i in range(num_steps)[::-1]:
+        u_t, u_s = sampler_times(i, num_steps)
+        lt, ls = float(logsnr_schedule_cosine_host(u_t)), float(logsnr_schedule_cosine_host(u_s))
+        h = 0.5 * (ls - lt)
+        # a zero-length previous step (coincident fp32 log-SNRs, only at extreme T) leaves no slope to extrapolate: first order again
+        k = 0.0 if (not h_prev or i == 0) else h / (2.0 * h_prev)
+        rows.append(DpmCoef(i, lt, ls, h, sigma(ls) / sigma(lt), -alpha(ls) * math.expm1(-h), k))
+        h_prev = h
+    return rows
 
 
 class PhiloxStream:
@@ -270,7 +297,7 @@ class GaussianDiffusion:
         dev = init_x.device
         if cond_w is not None and net_cond_w is None:
             net_cond_w = 4.0 * self.rng.uniform((B,), dev)           # :247-251
-        if self.sampler not in ("ddim", "noisy", "teacher_test"):
+        if self.sampler not in ("ddim", "noisy", "teacher_test", "dpmpp_2m"):
             raise NotImplementedError(self.sampler)
         student_w, w, use_teacher = resolve_guidance(sample_cond_w=self.sample_cond_w, net_cond_w=net_cond_w, kw_cond_w=kw_cond_w,
                                                      has_teacher=self.teacher_net is not None, sampler=self.sampler)
@@ -370,6 +397,9 @@ class GaussianDiffusion:
         # small batches replay a captured forward (one static log-SNR buffer, safe by stream order); large ones launch it kernel by kernel
         graphed, lvecs = self._forward_runner(module, z2 if guided else z_t, guide2 if guided else guide, sw2 if guided else student_w)
         lvecs[0].fill_(float(first))
+        # dpmpp_2m: the previous step's x-hat, [B, ...] also when guided (the kernel reads and rewrites it in place; the first step does not read it)
+        dpm = dpm_solver_coefs(self.num_steps) if self.sampler == "dpmpp_2m" else None
+        x_hist = torch.empty_like(z_t) if dpm is not None else None
         for it, i in enumerate(range(self.num_steps)[::-1]):
             u_t, u_s = sampler_times(i, self.num_steps)
             lt, ls = logsnr_schedule_cosine_host(u_t), logsnr_schedule_cosine_host(u_s)
@@ -383,8 +413,13 @@ class GaussianDiffusion:
             noise = None
             if self.sampler == "noisy":
                 noise = ops.aligned(noises[i]) if noises is not None else ops.rng_normal(tuple(z_t.shape), self.rng.seed, offs[it] + q0, dev)   # :241
-            z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, i == 0, v_uncond=vu, cond_w=w, noise=noise, want_pred=record, mean_type=self.mean_type,
-                                           dup=guided, logsnr_next=lnext)
+            if dpm is not None:
+                c = dpm[it]
+                z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, c.coef_z, c.coef_x, c.coef_prev, i == 0, v_uncond=vu, cond_w=w,
+                                                  want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
+            else:
+                z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, i == 0, v_uncond=vu, cond_w=w, noise=noise, want_pred=record,
+                                               mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
             if guided:
                 z_t, z2 = z_t
             if record:

@@ -775,6 +775,30 @@ def sampler_step(v, z, logsnr_t, logsnr_s, is_last, v_uncond=None, cond_w=None, 
     return ((z_next, z2) if dup else z_next), xp, ep
 
 
+def dpm_solver_step(v, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x, coef_prev, is_last, v_uncond=None, cond_w=None, want_pred=False,
+                    mean_type="v", dup=False, logsnr_next=None):
+    """One DPM-Solver++(2M) step (gmk_dpm_solver_step).  x_hist: fp32 [B, ...], the previous x-hat, overwritten with this step's (not read
+    when coef_prev == 0).  Arguments and returns otherwise as `sampler_step` (no noise: the solver is deterministic)."""
+    _f32(v, "v"); _f32(z, "z"); _f32(x_hist, "x_hist")
+    B = z.shape[0]
+    n = z.numel() // B
+    assert v.shape == z.shape and x_hist.shape == z.shape
+    if v_uncond is not None:
+        _f32(v_uncond, "v_uncond"); assert v_uncond.shape == z.shape
+    if cond_w is not None:
+        _f32(cond_w, "cond_w"); assert cond_w.numel() == B
+    z2 = torch.empty((2 * B,) + tuple(z.shape[1:]), device=z.device, dtype=z.dtype) if dup else None
+    z_next = z2[:B] if dup else torch.empty_like(z)
+    xp = torch.empty_like(z) if want_pred else None
+    ep = torch.empty_like(z) if want_pred else None
+    if logsnr_next is not None:
+        _f32(logsnr_next, "logsnr_next"); assert logsnr_next.numel() == (2 * B if dup else B)
+    check(lib.gmk_dpm_solver_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(x_hist), float(logsnr_t), float(logsnr_s), float(coef_z),
+                                  float(coef_x), float(coef_prev), int(is_last), _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None,
+                                  _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()), "dpm_solver_step")
+    return ((z_next, z2) if dup else z_next), xp, ep
+
+
 def logsnr_schedule(B, device, u=None, i_times=None, num_steps=1, shift=0.0, want_u=False):
     """logsnr = schedule(u - shift), u given or (i_times + 1) / num_steps.  -> logsnr (, u_shifted)"""
     if u is not None:

@@ -281,6 +281,16 @@ int gmk_v_loss(const float* v, const float* z, const float* x, const float* eps,
 int gmk_sampler_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, const float* noise,
                      float logsnr_t, float logsnr_s, int is_last, float* z_next, float* x_pred, float* eps_pred,
                      float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+/* one DPM-Solver++(2M) step (Lu et al. 2022, Algorithm 2, data prediction) on the same time grid; an extension, no reference call site:
+ *   v, v_uncond, cond_w, mean_type: as gmk_sampler_step - x_hat is the clipped (guided) data prediction of that step, eps_hat = eps(x_hat, z).
+ *   x_hist: B x n, in place: the previous step's x_hat on entry (not read when coef_prev == 0), this step's x_hat on exit.
+ *   coef_z = sigma_s / sigma_t, coef_x = -alpha_s expm1(-h), coef_prev = 1 / (2 r) with h = (logsnr_s - logsnr_t) / 2 and r = h_prev / h
+ *   (0 on the first step: DDIM's update; the host passes 0 on the last step too); z_next = coef_z z + coef_x ((1 + coef_prev) x_hat - coef_prev x_prev), or x_hat when is_last.
+ *   logsnr_t: the network's time (x_hat, eps_hat); logsnr_s: written to logsnr_next.  x_pred / eps_pred (optional) receive x_hat and eps_hat;
+ *   z_dup / logsnr_next: gmk_sampler_step's conventions.  The host computes the coefficients in double from the fp32 log-SNRs. */
+int gmk_dpm_solver_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float* x_hist, float logsnr_t,
+                        float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last, float* z_next, float* x_pred,
+                        float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
 
 /* ---- self-attention core (north_star "optional self-attention block", BASELINE config 5) -------------
  * The reference SimpleUnet has no attention block: these have NO reference call site (parity unpinned; their definition is the

@@ -1,0 +1,127 @@
+"""CPU tests (no GPU) of sampler='dpmpp_2m' (DPM-Solver++(2M), an extension): the host coefficient table, the sampler name, the C ABI
+entry's argument checks, and the CPU restatement the GPU tests hold the kernel to."""
+import ctypes
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dpm_solver_ref  # noqa: E402
+
+
+def _sig(l):
+    """-> (alpha, sigma) in float64 of an fp32 log-SNR."""
+    return math.sqrt(1.0 / (1.0 + math.exp(-l))), math.sqrt(1.0 / (1.0 + math.exp(l)))
+
+
+@pytest.mark.parametrize("T", [1, 2])
+def test_one_and_two_steps_are_first_order(T):
+    from generative_models_amd.diffusion.gaussian_diffusion import dpm_solver_coefs
+    rows = dpm_solver_coefs(T)
+    assert [r.i for r in rows] == list(range(T))[::-1]
+    assert all(r.coef_prev == 0.0 for r in rows)
+
+
+@pytest.mark.parametrize("T", [3, 6, 20, 250, 1000])
+def test_coefficient_table(T):
+    from generative_models_amd.diffusion.gaussian_diffusion import dpm_solver_coefs, logsnr_schedule_cosine_host, sampler_times
+    rows = dpm_solver_coefs(T)
+    assert len(rows) == T and [r.i for r in rows] == list(range(T))[::-1]
+    assert rows[0].coef_prev == 0.0                                     # the first step is first order
+    assert rows[-1].coef_prev == 0.0                                    # the last returns x_hat: its update is never used
+    for j, r in enumerate(rows):
+        u_t, u_s = sampler_times(r.i, T)                                # the DDIM path's fp32 log-SNRs, exactly
+        assert r.lt == float(logsnr_schedule_cosine_host(u_t)) and r.ls == float(logsnr_schedule_cosine_host(u_s))
+        assert r.h == 0.5 * (r.ls - r.lt) and r.h > 0
+        (a_t, s_t), (a_s, s_s) = _sig(r.lt), _sig(r.ls)
+        assert r.coef_z == pytest.approx(s_s / s_t, rel=1e-12)
+        assert r.coef_x == pytest.approx(-a_s * math.expm1(-r.h), rel=1e-12)
+        if 0 < j < T - 1:                                               # 1 / (2 r), r = h_prev / h: the PREVIOUS step's h
+            assert r.coef_prev == pytest.approx(1.0 / (2.0 * (rows[j - 1].h / r.h)), rel=1e-12)
+    if T >= 6:                                                          # the grid's first step (from logsnr -20) is the longest in lambda:
+        assert rows[1].coef_prev < 0.5 - 1e-3                           # h shrinks, 1/(2r) < 1/2 (the step's own h would give 1/2)
+
+
+@pytest.mark.parametrize("T", [2, 10, 250])
+def test_first_order_update_is_ddim_on_random_data(T):
+    """(sigma_s / sigma_t) z + coef_x x = alpha_s x + sigma_s eps(x, z), eps(x, z) = (z - alpha_t x) / sigma_t: the first-order step is DDIM's
+    update rewritten - to fp32 rounding, with the coefficients rounded to fp32 as the kernel receives them."""
+    from generative_models_amd.diffusion.gaussian_diffusion import dpm_solver_coefs
+    g = torch.Generator().manual_seed(5)
+    x = torch.rand((4, 3, 8, 8), generator=g) * 2 - 1
+    z = torch.randn((4, 3, 8, 8), generator=g)
+    for r in dpm_solver_coefs(T):
+        (a_t, s_t), (a_s, s_s) = _sig(np.float32(r.lt)), _sig(np.float32(r.ls))
+        lhs = np.float32(r.coef_z) * z + np.float32(r.coef_x) * x
+        eps = (z.double() - a_t * x.double()) / s_t
+        rhs = a_s * x.double() + s_s * eps
+        scale = float(rhs.abs().max()) + float(z.abs().max()) * r.coef_z + float(x.abs().max()) * abs(r.coef_x)
+        assert float((lhs.double() - rhs).abs().max()) <= 4 * 2 ** -24 * scale, r
+
+
+def test_sampler_name():
+    from generative_models_amd.diffusion.gaussian_diffusion import GaussianDiffusion
+    d = GaussianDiffusion(mean_type="v", num_steps=4, sampler="dpmpp_2m")
+    assert d.sampler == "dpmpp_2m"
+    with pytest.raises(NotImplementedError):                             # an unknown name still raises, before any device work
+        GaussianDiffusion(mean_type="v", num_steps=4, sampler="dpmpp_3m").sample(net=lambda *a, **k: None, init_x=torch.zeros((1, 1, 8, 8)))
+
+
+def test_model_default_and_flag():
+    from generative_models_amd import common, main
+    Model = common.discover_models()["diffusion_model"]
+    assert Model.DG.sampler == "ddim"                                   # the default is unchanged
+    G, _ = main.FlagSpace(main.DG).resolve(["--model=diffusion", "--sampler", "dpmpp_2m", "--timesteps", "20"])
+    assert G.sampler == "dpmpp_2m" and G.timesteps == 20
+
+
+def test_header_declares_the_entry():
+    from generative_models_amd import _lib
+    protos = _lib.parse_header(os.path.join(ROOT, "include", "gmk.h"))
+    ret, argtypes, argnames = protos["gmk_dpm_solver_step"]
+    assert argnames == ["v", "v_uncond", "cond_w", "z", "x_hist", "logsnr_t", "logsnr_s", "coef_z", "coef_x", "coef_prev", "is_last",
+                        "z_next", "x_pred", "eps_pred", "z_dup", "logsnr_next", "mean_type", "B", "n", "stream"]
+    P, F, I = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
+    assert argtypes == [P] * 5 + [F] * 5 + [I] + [P] * 5 + [I, I, ctypes.c_int64, P]
+    assert ret is ctypes.c_int
+    # gmk_sampler_step's prototype is unchanged
+    assert protos["gmk_sampler_step"][2] == ["v", "v_uncond", "cond_w", "z", "noise", "logsnr_t", "logsnr_s", "is_last", "z_next", "x_pred",
+                                             "eps_pred", "z_dup", "logsnr_next", "mean_type", "B", "n", "stream"]
+
+
+def test_entry_rejects_bad_arguments_before_any_launch():
+    from generative_models_amd import _lib
+    lib = _lib.lib
+    buf = ctypes.c_void_p(16)        # never dereferenced: argument checks come first
+
+    def call(v=buf, vu=None, w=None, z=buf, hist=buf, zn=buf, mt=0, B=2, n=64, coef_prev=0.5):
+        return lib.gmk_dpm_solver_step(v, vu, w, z, hist, -1.0, 1.0, 0.5, 0.5, coef_prev, 0, zn, None, None, None, None, mt, B, n, None)
+    for kw in ({"v": None}, {"z": None}, {"hist": None}, {"zn": None}):
+        assert call(**kw) == -1 and b"null pointer" in lib.gmk_last_error()
+    for mt in (-1, 3):
+        assert call(mt=mt) == -1 and b"mean_type" in lib.gmk_last_error()
+    assert call(vu=buf) == -1 and b"together" in lib.gmk_last_error()
+    assert call(B=0) == -1 and b"shape" in lib.gmk_last_error()
+    assert call(coef_prev=float("nan")) == -1 and b"non-finite" in lib.gmk_last_error()
+
+
+def test_restatement_with_two_steps_is_ddim():
+    """The CPU restatement itself: with T <= 2 every step is first order or the final select, so the chain is the oracle's DDIM chain up to
+    rounding (C = 32 keeps the CPU U-Net fast)."""
+    from oracle import diffusion_ref as D
+    from oracle import unet_ref as U
+    params = U.reference_init_params(32, 1, zero_out_layers=False, seed=3)
+    g = torch.Generator().manual_seed(4)
+    init = torch.randn((2, 1, 8, 8), generator=g)
+    y = torch.tensor([2, 5])
+    with torch.no_grad():
+        for T in (1, 2):
+            a = dpm_solver_ref.sample(params, init, y, T)
+            b = D.sample(params, init, y, T, "ddim")
+            for p, q in zip(a, b):
+                assert float((p - q).abs().max()) <= 1e-5 * float(q.abs().max())
