@@ -3,7 +3,8 @@
 // ddim_step :189-213, reverse_dpm_step :215-243, sample :292) and gms/diffusion/diffusion_utils.py
 // (diffusion_forward :65-73, diffusion_reverse :34-62, predict_* :76-105, _logsnr_schedule_cosine :198-201);
 // torch.optim.Adam as diffusion_model.py:56 constructs it.  gmk_adam_ema_step's weight average has no reference call site (the
-// reference keeps no EMA): an extension, defined by torch.lerp.  gmk_dpm_solver_step (DPM-Solver++(2M)) is an extension too.
+// reference keeps no EMA): an extension, defined by torch.lerp.  gmk_dpm_solver_step (DPM-Solver++(2M)) is an extension too, and so are
+// the variational-bound kernels gmk_q_sample_logsnr / gmk_vlb_term / gmk_vlb_endpoints (Kingma et al. 2021, continuous-time VDM bound).
 #include <math.h>
 
 #include "gmk_common.h"
@@ -206,6 +207,129 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __res
     }
 }
 
+// ---- continuous-time variational bound (Kingma et al. 2021, VDM eq. 17 with lambda as the variable); an extension, no reference call site.
+// Every kernel below takes any n: 16-byte vector accesses when n % 4 == 0 (every row then starts 16-byte aligned), element by element otherwise.
+
+// grid (ceil(n/1024), B): z = alpha x + sigma eps at a given per-sample logsnr (q_sample_kernel draws its logsnr from u instead)
+__global__ __launch_bounds__(256) void q_sample_logsnr_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                             const float* __restrict__ logsnr, float* __restrict__ z, int64_t n) {
+    const int b = blockIdx.y;
+    const LogsnrCoef c = logsnr_coef(logsnr[b]);
+    const int64_t base = (int64_t)b * n;
+    if ((n & 3) == 0) {
+        for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+            float xv[4], ev[4], o[4];
+            load4(x + base + i, xv);
+            load4(eps + base + i, ev);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = __fadd_rn(__fmul_rn(xv[k], c.alpha), __fmul_rn(c.sigma, ev[k]));
+            store4(z + base + i, o);
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+            z[base + i] = __fadd_rn(__fmul_rn(x[base + i], c.alpha), __fmul_rn(c.sigma, eps[base + i]));
+    }
+}
+
+// the network's noise prediction, UNCLIPPED: 'v' sigma z + alpha out, 'eps' out, 'x' (z - alpha out) / sigma in predict_eps_from_x's form
+__device__ __forceinline__ float eps_from_out(float out, float zz, const LogsnrCoef& c, int mt) {
+    return mt == 0 ? c.sigma * zz + c.alpha * out : (mt == 1 ? out : c.c1 * (zz - out * c.c2));
+}
+
+// one block per sample: acc[b] += weight[b] * sum_i (eps - eps_hat)^2 (one read pass, v_loss_kernel's reduction: a fixed order, so
+// repeated calls give the same bits)
+__global__ __launch_bounds__(256) void vlb_term_kernel(const float* __restrict__ out, const float* __restrict__ z,
+                                                      const float* __restrict__ eps, const float* __restrict__ logsnr,
+                                                      const float* __restrict__ weight, float* __restrict__ acc, int64_t n, int mt) {
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const LogsnrCoef c = logsnr_coef(logsnr[b]);
+    const int64_t base = (int64_t)b * n;
+    float s = 0.f;
+    if ((n & 3) == 0) {
+        for (int64_t i = threadIdx.x * 4; i < n; i += 1024) {
+            float ov[4], zv[4], ev[4];
+            load4(out + base + i, ov);
+            load4(z + base + i, zv);
+            load4(eps + base + i, ev);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = ev[k] - eps_from_out(ov[k], zv[k], c, mt);
+                s = fmaf(d, d, s);
+            }
+        }
+    } else {
+        for (int64_t i = threadIdx.x; i < n; i += 256) {
+            const float d = eps[base + i] - eps_from_out(out[base + i], z[base + i], c, mt);
+            s = fmaf(d, d, s);
+        }
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) acc[b] += weight[b] * s;
+}
+
+// log(1 - Phi(t)) = log(erfc(t / sqrt 2) / 2): erfcf while it is representable, the asymptotic series (Abramowitz & Stegun 26.2.12, four terms:
+// the next is below 3e-7 relative from t = 9) beyond; -inf at t = +inf
+__device__ __forceinline__ float log_ndtr_upper(float t) {
+    if (t < 9.0f) return logf(0.5f * erfcf(t * 0.70710678118654752f));
+    const float r = 1.0f / (t * t);
+    return -0.5f * t * t - logf(t) - 0.91893853320467274f + log1pf(r * (-1.0f + r * (3.0f + r * (-15.0f + r * 105.0f))));
+}
+
+// log(Phi(a) - Phi(b)) for a > b (a may be +inf, b -inf): the bin's mass as a difference of the smaller tail probabilities, so that it never
+// rounds to log 0 when the bin lies far out in one tail, and as log1p of the two tails when it straddles 0
+__device__ __forceinline__ float log_bin_mass(float a, float b) {
+    if (b > 0.0f) {
+        const float la = log_ndtr_upper(a), lb = log_ndtr_upper(b);
+        return lb + log1pf(-expf(la - lb));
+    }
+    if (a < 0.0f) {
+        const float la = log_ndtr_upper(-a), lb = log_ndtr_upper(-b);
+        return la + log1pf(-expf(lb - la));
+    }
+    return log1pf(-0.5f * erfcf(a * 0.70710678118654752f) - 0.5f * erfcf(-b * 0.70710678118654752f));
+}
+
+// one block per sample: the prior term sum_i KL(N(alpha_1 x, sigma_1^2) || N(0, 1)) = half_a2 sum x^2 + n prior_c (the x-free part in double on
+// the host: it cancels in fp32), and the decoder term sum_i -log[Phi((x + delta - m) / s) - Phi((x - delta - m) / s)] with m = z_0 / alpha_0,
+// s = sigma_0 / alpha_0, z_0 = alpha_0 x + sigma_0 eps_0.  Then (x - m) / s = -eps_0 exactly, so the standardised edges are +-delta/s - eps_0
+// (dscale = delta / s): z_0 is never formed, whose rounding (ulp(x) / s) would swamp the edges.  The top bin (x > hi - delta) has upper edge +inf,
+// the bottom bin (x < lo + delta) lower edge -inf.
+__global__ __launch_bounds__(256) void vlb_endpoints_kernel(const float* __restrict__ x, const float* __restrict__ eps0, float delta,
+                                                           float dscale, float lo, float hi, float half_a2, float prior_c,
+                                                           float* __restrict__ out_prior, float* __restrict__ out_dec, int64_t n) {
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const int64_t base = (int64_t)b * n;
+    float sx = 0.f, sd = 0.f;
+    auto elem = [&](float xv, float e) {
+        sx = fmaf(xv, xv, sx);
+        const float a = xv > hi - delta ? INFINITY : dscale - e;
+        const float bb = xv < lo + delta ? -INFINITY : -dscale - e;
+        // both edges 12 standard deviations out: the bin's mass is 1 - O(1e-33), its -log 0 in fp32.  Every normal draw at lambda_max = 20
+        // takes this branch (the edges are +-delta e^10 = +-86 from -eps_0), which keeps the pass at memory speed instead of two erfcf
+        if (a >= 12.0f && bb <= -12.0f) return;
+        sd -= log_bin_mass(a, bb);
+    };
+    if ((n & 3) == 0) {
+        for (int64_t i = threadIdx.x * 4; i < n; i += 1024) {
+            float xv[4], ev[4];
+            load4(x + base + i, xv);
+            load4(eps0 + base + i, ev);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) elem(xv[k], ev[k]);
+        }
+    } else {
+        for (int64_t i = threadIdx.x; i < n; i += 256) elem(x[base + i], eps0[base + i]);
+    }
+    sx = block_sum(sx, red);
+    sd = block_sum(sd, red);
+    if (threadIdx.x == 0) {
+        out_prior[b] = half_a2 * sx + prior_c * (float)n;
+        out_dec[b] = sd;
+    }
+}
+
 template <bool NORMAL>
 __global__ __launch_bounds__(256) void rng_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
     const int64_t nq = (n + 3) / 4;
@@ -371,6 +495,41 @@ extern "C" int gmk_dpm_solver_step(const float* v, const float* v_uncond, const 
                                                                         coef_x, coef_prev, is_last, z_next, x_pred, eps_pred, z_dup,
                                                                         logsnr_next, n, mean_type);
     return gmk_check_launch("gmk_dpm_solver_step");
+}
+
+extern "C" int gmk_q_sample_logsnr(const float* x, const float* eps, const float* logsnr, float* z, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(x && eps && logsnr && z, "gmk_q_sample_logsnr: null pointer");
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_q_sample_logsnr: bad shape B=%d n=%lld", B, (long long)n);
+    int gx = (int)((n + 1023) / 1024);
+    if (gx > 64) gx = 64;
+    q_sample_logsnr_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(x, eps, logsnr, z, n);
+    return gmk_check_launch("gmk_q_sample_logsnr");
+}
+
+extern "C" int gmk_vlb_term(const float* out, const float* z, const float* eps, const float* logsnr, const float* weight, float* acc,
+                            int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(out && z && eps && logsnr && weight && acc, "gmk_vlb_term: null pointer");
+    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "gmk_vlb_term: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE(B > 0 && n > 0, "gmk_vlb_term: bad shape B=%d n=%lld", B, (long long)n);
+    vlb_term_kernel<<<B, 256, 0, gmk_stream(stream)>>>(out, z, eps, logsnr, weight, acc, n, mean_type);
+    return gmk_check_launch("gmk_vlb_term");
+}
+
+extern "C" int gmk_vlb_endpoints(const float* x, const float* eps0, float delta, float* out_prior, float* out_dec, int B, int64_t n,
+                                 void* stream) {
+    GMK_REQUIRE(x && eps0 && out_prior && out_dec, "gmk_vlb_endpoints: null pointer");
+    GMK_REQUIRE(B > 0 && n > 0, "gmk_vlb_endpoints: bad shape B=%d n=%lld", B, (long long)n);
+    GMK_REQUIRE(delta > 0.0f && delta <= 0.5f, "gmk_vlb_endpoints: delta = %g outside (0, 0.5]", (double)delta);
+    // the bound's end points lambda_min = -20 (prior) and lambda_max = 20 (decoder), in double: alpha_1^2 = sigmoid(-20) ~ 2.1e-9, and
+    // -a - log1p(-a) = a^2/2 + a^3/3 + ... (the x-free part of the prior KL) is formed by its series, which has no cancellation
+    const double a2 = 1.0 / (1.0 + exp(20.0));
+    const double prior_c = 0.5 * (a2 * a2 / 2.0 + a2 * a2 * a2 / 3.0);
+    const double dscale = (double)delta * exp(10.0);            // delta / s, s = sigma_0 / alpha_0 = exp(-lambda_max / 2)
+    // data range: binarised data (delta = 1/2) lie in {0, 1}, everything else in [-1, 1]
+    const float lo = delta == 0.5f ? 0.0f : -1.0f;
+    vlb_endpoints_kernel<<<B, 256, 0, gmk_stream(stream)>>>(x, eps0, delta, (float)dscale, lo, 1.0f, (float)(0.5 * a2), (float)prior_c,
+                                                            out_prior, out_dec, n);
+    return gmk_check_launch("gmk_vlb_endpoints");
 }
 
 extern "C" int gmk_ddim_step_vec(const float* v, const float* v_uncond, const float* cond_w, const float* z,

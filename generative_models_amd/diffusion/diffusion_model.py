@@ -13,6 +13,7 @@ optimiser; RNG from counter-based Philox streams on the device.  `make_plugin(ba
 the REFERENCE's `gms.common.GM`, which is what a `gms/` checkout needs for `discover_models()` to pick it up
 (INTEGRATION.md).
 """
+import math
 import random
 from functools import partial
 from pathlib import Path
@@ -55,6 +56,8 @@ def make_plugin(GMBase, AttrDict):
         DG.seed = 0
         DG.ema_decay = 0.0             # > 0: keep an exponential moving average of the weights (`ema_net`, updated inside the fused Adam launch)
                                        # and sample / evaluate with it; not in the reference, off by default
+        DG.nlogp_samples = 0           # > 0: loss() also reports the variational bound (`nlogp`, logged as eval/nlogp, and `bpd`) of the sampling
+                                       # net with that many log-SNR draws per image; not in the reference, off by default
 
         def __init__(self, G):
             super().__init__(G)
@@ -75,6 +78,13 @@ def make_plugin(GMBase, AttrDict):
                     param.requires_grad = False
             else:
                 self.teacher_net = None
+            self.nlogp_samples = int(get("nlogp_samples"))
+            if self.nlogp_samples < 0:
+                raise ValueError(f"nlogp_samples = {self.nlogp_samples}: 0 (off) or the number of draws per image")
+            if self.nlogp_samples > 0 and self.teacher_net is not None:
+                raise ValueError("nlogp_samples > 0 with teacher_path: a distilled student is conditioned on cond_w; its variational bound "
+                                 "is not defined")
+            self.binarize = int(get("binarize"))
             seed = int(get("seed")) * 1000 + parallel.rank()
             self.diffusion = GaussianDiffusion(mean_type=get("mean_type"), num_steps=int(get("timesteps")),
                                                sampler=get("sampler"), teacher_net=self.teacher_net,
@@ -210,7 +220,23 @@ def make_plugin(GMBase, AttrDict):
         def loss(self, x, y):
             metrics = self.diffusion.training_losses(net=partial(self.net, guide=y), x=x)
             metrics = {key: val.mean() for key, val in metrics.items()}
+            if self.nlogp_samples > 0:              # the unconditional bound, nats/dim; the driver logs `nlogp` as eval/nlogp (gms/main.py:170-174)
+                nlogp = self.nlogp(x)["nlogp"].mean()
+                metrics["nlogp"] = nlogp
+                metrics["bpd"] = nlogp / math.log(2.0)
             return metrics["loss"], metrics
+
+        # -- likelihood (an extension): the variational bound of `GaussianDiffusion.nll` on the net sample() and evaluate() use
+        NLOGP_SAMPLES = 16                          # draws per image when neither the call nor `nlogp_samples` gives a number
+
+        def nlogp(self, x, y=None, num_samples=None, seed=0):
+            """Per-image bound on -log p(x) (y None: unconditional, guide -1, the classifier-free branch the net is trained on) or on
+            -log p(x | y) for labels y, in nats per dimension; bin half-width 1/2 for binarised data, 1/255 otherwise.  -> the dict of
+            `GaussianDiffusion.nll` (nlogp, se, diffusion, prior, decoder: fp32 [B])."""
+            K = num_samples or self.nlogp_samples or self.NLOGP_SAMPLES
+            guide = y if y is not None else torch.full((x.shape[0],), -1, dtype=torch.long, device=x.device)
+            delta = 0.5 if self.binarize else 1.0 / 255
+            return self.diffusion.nll(net=partial(self._sampling_net(), guide=guide), x=x, num_samples=K, seed=seed, delta=delta)
 
         # -- sampling (:82-87)
         def sample(self, n, y=None):

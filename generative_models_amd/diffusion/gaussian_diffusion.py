@@ -8,6 +8,7 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
 * v -> x_hat/eps_hat, clip, loss, dL/dv gmk_v_loss       (:61-77,:165-169 and their backward)
 * DDIM / ancestral / guidance update   gmk_sampler_step (:174-243,:292)
 * DPM-Solver++(2M) update              gmk_dpm_solver_step (sampler='dpmpp_2m': an extension, no reference call site)
+* variational bound (`nll`)            gmk_q_sample_logsnr, gmk_vlb_term, gmk_vlb_endpoints (an extension, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -64,6 +65,34 @@ def dpm_solver_coefs(num_steps):
         rows.append(DpmCoef(i, lt, ls, h, sigma(ls) / sigma(lt), -alpha(ls) * math.expm1(-h), k))
         h_prev = h
     return rows
+
+
+# the variational bound's log-SNR range: the schedule's truncation (diffusion_utils.py:199-200)
+VLB_LOGSNR_MAX, VLB_LOGSNR_MIN = 20.0, -20.0
+
+
+def stratified_logsnr(u0, K):
+    """fp32 [K, B] log-SNRs lambda_{b,k} = lambda_max - Delta frac(u0_b + k / K) of `GaussianDiffusion.nll`: uniform in lambda, one draw of
+    each image in each of the K equal strata of [lambda_min, lambda_max].  Formed in float64 (an fp32 sum u0 + k / K can round onto the
+    next stratum's edge), then rounded to fp32."""
+    k = torch.arange(K, device=u0.device, dtype=torch.float64)[:, None] / K
+    frac = torch.remainder(u0.double()[None, :] + k, 1.0)
+    return (VLB_LOGSNR_MAX - (VLB_LOGSNR_MAX - VLB_LOGSNR_MIN) * frac).float()
+
+
+class _EvalForward:
+    """`module` without dropout for the duration of a with-block, whatever its training flag (its forward reads the flag)."""
+
+    def __init__(self, module):
+        self.module = module
+
+    def __enter__(self):
+        self.was = self.module.training
+        self.module.training = False
+        return self.module
+
+    def __exit__(self, *exc):
+        self.module.training = self.was
 
 
 class PhiloxStream:
@@ -284,6 +313,53 @@ class GaussianDiffusion:
         loss_b, x_mse, eps_mse, dv = ops.v_loss(v, z_t, x_t, eps_t, logsnr, grad_scale=grad_scale, loss_type=loss_type, mean_type=self.mean_type)
         module.backward_hip(ctx, dv, on_grads_ready=on_grads_ready, join_side_before_ready=join_side_before_ready)
         return {"loss": loss_b, "x_mse": x_mse, "eps_mse": eps_mse, "logsnr": logsnr}
+
+    # ---- likelihood: the continuous-time variational bound (an extension, no reference call site) ------------------------------------------
+    @torch.no_grad()
+    def nll(self, *, net, x, num_samples, seed=0, delta=1.0 / 255):
+        """Per-image variational bound on -log p(x) of Kingma et al. 2021 (VDM) for this schedule (cosine log-SNR truncated to [-20, 20]), in nats
+        per dimension.  x [B, C, H, W], D = C H W, lambda = logsnr, alpha^2 = sigmoid(lambda), sigma^2 = sigmoid(-lambda), Delta = 40:
+          diffusion  1/2 int_{-20}^{20} E_eps |eps - eps_hat(z_lambda, lambda)|^2 d lambda  (VDM eq. 17 with lambda as the variable), estimated with
+                     K = num_samples stratified draws per image, lambda_{b,k} = 20 - Delta frac(u0_b + k / K): mean_k 1/2 Delta |eps_k - eps_hat_k|^2
+          prior      sum_i KL(N(alpha_1 x_i, sigma_1^2) || N(0, 1)) at lambda = -20
+          decoder    the discretised Gaussian at lambda = 20 with mean z_0 / alpha_0 and scale sigma_0 / alpha_0, bins of half-width `delta`
+                     centred on the value (1/255 for [-1, 1] data, 1/2 for binarised {0, 1} data), outermost edges +-inf.
+        eps_hat is the network's noise prediction UNCLIPPED ('v': sigma z + alpha out, 'eps': out, 'x': (z - alpha out) / sigma), not the clipped
+        x-hat that training and the samplers use: clipping could only tighten the bound, and it would break its closed form for a known network.
+        The draws come from a fresh PhiloxStream(seed) in the order u0 [B], eps_k for k = 0 ... K-1, eps_0, so repeated calls (two checkpoints,
+        EMA against raw weights) share their random numbers.  The forward runs without dropout, whatever `module.training` is.
+        -> dict of fp32 [B]: nlogp = (prior + decoder + diffusion) / D, se (the standard error of the diffusion estimate from the spread of
+        the K draws - conservative under stratification; NaN for K = 1), diffusion, prior, decoder, all per dimension."""
+        module, guide, kw_cond_w = _unwrap(net)
+        if self.teacher_net is not None or kw_cond_w is not None:
+            raise ValueError("nll: a distilled student is conditioned on cond_w; its variational bound is not defined")
+        K = int(num_samples)
+        if K < 1:
+            raise ValueError(f"nll: num_samples = {num_samples}, need at least 1")
+        x = ops.aligned(x.float())
+        B, dev = x.shape[0], x.device
+        D = x.numel() // B
+        Bp = (B + 3) // 4 * 4                      # rows of [K, Bp] buffers start 16-byte aligned
+        rng = PhiloxStream(seed)
+        u0 = rng.uniform((B,), dev)
+        logsnr = torch.empty((K, Bp), device=dev)
+        logsnr[:, :B] = stratified_logsnr(u0, K)
+        acc = torch.zeros((K, Bp), device=dev)
+        weight = torch.full((B,), 0.5 * (VLB_LOGSNR_MAX - VLB_LOGSNR_MIN), device=dev)
+        with _EvalForward(module):
+            for k in range(K):
+                eps = rng.normal(x.shape, dev)
+                lk = logsnr[k, :B]
+                z = ops.q_sample_logsnr(x, eps, lk)
+                out = module.forward_hip(z, lk, guide, None)
+                ops.vlb_term(out, z, eps, lk, weight, acc[k, :B], mean_type=self.mean_type)
+                ops.throttle()                     # at most two draws queued on the GPU (see ops.throttle)
+        eps0 = rng.normal(x.shape, dev)
+        prior, dec = ops.vlb_endpoints(x, eps0, delta)
+        vals = acc[:, :B]
+        diff = vals.mean(0)
+        se = vals.std(0) / math.sqrt(K) if K > 1 else torch.full_like(diff, float("nan"))
+        return {"nlogp": (prior + dec + diff) / D, "se": se / D, "diffusion": diff / D, "prior": prior / D, "decoder": dec / D}
 
     # ---- sampling ----------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -799,6 +799,58 @@ def dpm_solver_step(v, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x, coef_prev,
     return ((z_next, z2) if dup else z_next), xp, ep
 
 
+# ---- continuous-time variational bound (an extension; gaussian_diffusion.GaussianDiffusion.nll) ----------------------------------------
+# Shapes, dtypes and the mean type are checked before `_f32` asks for a device tensor, so that a bad call is named for what is wrong with it.
+def _vlb_check(tensors, vectors=()):
+    """tensors: (tensor, name) pairs of one image shape [B, ...]; vectors: (tensor, name) pairs of B floats each.  -> (B, floats per image)"""
+    for t, nm in tuple(tensors) + tuple(vectors):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{nm}: dtype {t.dtype}, expected torch.float32")
+    shape = tuple(tensors[0][0].shape)
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f"{tensors[0][1]}: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
+    for t, nm in tensors:
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{nm}: shape {tuple(t.shape)}, expected {shape}")
+    for t, nm in vectors:
+        if t.dim() != 1 or t.numel() != shape[0]:
+            raise ValueError(f"{nm}: shape {tuple(t.shape)}, expected ({shape[0]},)")
+    for t, nm in tuple(tensors) + tuple(vectors):
+        _f32(t, nm)
+    return shape[0], math.prod(shape[1:])
+
+
+def q_sample_logsnr(x, eps, logsnr):
+    """z = alpha x + sigma eps at the per-sample log-SNR `logsnr` (fp32 [B]).  -> z"""
+    B, n = _vlb_check(((x, "x"), (eps, "eps")), vectors=((logsnr, "logsnr"),))
+    z = torch.empty_like(x)
+    check(lib.gmk_q_sample_logsnr(_p(x), _p(eps), _p(logsnr), _p(z), B, n, _s()), "q_sample_logsnr")
+    return z
+
+
+def vlb_term(out, z, eps, logsnr, weight, acc, mean_type="v"):
+    """acc += weight * sum over each image of (eps - eps_hat)^2, eps_hat the unclipped noise prediction of the net output `out` (gmk_vlb_term).
+    logsnr, weight, acc: fp32 [B]; acc is updated in place and returned."""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    B, n = _vlb_check(((out, "out"), (z, "z"), (eps, "eps")), vectors=((logsnr, "logsnr"), (weight, "weight"), (acc, "acc")))
+    check(lib.gmk_vlb_term(_p(out), _p(z), _p(eps), _p(logsnr), _p(weight), _p(acc), MEAN_TYPES[mean_type], B, n, _s()), "vlb_term")
+    return acc
+
+
+def vlb_endpoints(x, eps0, delta):
+    """Prior (KL at logsnr -20) and decoder (discretised Gaussian at logsnr 20, bin half-width `delta`) terms per image, in nats.
+    -> (prior, decoder), fp32 [B] each."""
+    delta = float(delta)
+    if not 0.0 < delta <= 0.5:
+        raise ValueError(f"delta = {delta}: the bin half-width must lie in (0, 0.5]")
+    B, n = _vlb_check(((x, "x"), (eps0, "eps0")))
+    prior = torch.empty((B,), device=x.device, dtype=torch.float32)
+    dec = torch.empty_like(prior)
+    check(lib.gmk_vlb_endpoints(_p(x), _p(eps0), delta, _p(prior), _p(dec), B, n, _s()), "vlb_endpoints")
+    return prior, dec
+
+
 def logsnr_schedule(B, device, u=None, i_times=None, num_steps=1, shift=0.0, want_u=False):
     """logsnr = schedule(u - shift), u given or (i_times + 1) / num_steps.  -> logsnr (, u_shifted)"""
     if u is not None:

@@ -291,6 +291,20 @@ int gmk_sampler_step(const float* v, const float* v_uncond, const float* cond_w,
 int gmk_dpm_solver_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float* x_hist, float logsnr_t,
                         float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last, float* z_next, float* x_pred,
                         float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+/* continuous-time variational bound (Kingma et al. 2021, VDM eq. 17 in lambda = logsnr, lambda in [-20, 20]); an extension, no reference
+ * call site.  Any n (rows of 4k floats take the vector path).
+ *   gmk_q_sample_logsnr: z = alpha x + sigma eps at the given per-sample logsnr[B] (alpha^2 = sigmoid(l), sigma^2 = sigmoid(-l)).
+ *   gmk_vlb_term: acc[b] += weight[b] * sum_i (eps - eps_hat)^2, eps_hat the UNCLIPPED noise prediction of the net output `out` at z, logsnr:
+ *     mean_type 0 'v' sigma z + alpha out, 1 'eps' out, 2 'x' (z - alpha out) / sigma.  acc is read and written (accumulates).
+ *   gmk_vlb_endpoints: per image, out_prior[b] = sum_i KL(N(alpha_1 x, sigma_1^2) || N(0, 1)) at lambda = -20 and
+ *     out_dec[b] = sum_i -log[Phi((x + delta - m) / s) - Phi((x - delta - m) / s)], the discretised Gaussian at lambda = 20 with
+ *     m = z_0 / alpha_0, s = sigma_0 / alpha_0, z_0 = alpha_0 x + sigma_0 eps0 (nats).  Bins are centred on x; the top bin's upper edge
+ *     (x > 1 - delta) is +inf, the bottom bin's lower edge (x < lo + delta) -inf, lo = 0 for binarised data (delta = 1/2, values {0, 1}),
+ *     else -1 (delta = 1/255 for [-1, 1] data).  0 < delta <= 1/2. */
+int gmk_q_sample_logsnr(const float* x, const float* eps, const float* logsnr, float* z, int B, int64_t n, void* stream);
+int gmk_vlb_term(const float* out, const float* z, const float* eps, const float* logsnr, const float* weight, float* acc, int mean_type,
+                 int B, int64_t n, void* stream);
+int gmk_vlb_endpoints(const float* x, const float* eps0, float delta, float* out_prior, float* out_dec, int B, int64_t n, void* stream);
 
 /* ---- self-attention core (north_star "optional self-attention block", BASELINE config 5) -------------
  * The reference SimpleUnet has no attention block: these have NO reference call site (parity unpinned; their definition is the
