@@ -4,7 +4,8 @@
 // (diffusion_forward :65-73, diffusion_reverse :34-62, predict_* :76-105, _logsnr_schedule_cosine :198-201);
 // torch.optim.Adam as diffusion_model.py:56 constructs it.  gmk_adam_ema_step's weight average has no reference call site (the
 // reference keeps no EMA): an extension, defined by torch.lerp.  gmk_dpm_solver_step (DPM-Solver++(2M)) is an extension too, and so are
-// the variational-bound kernels gmk_q_sample_logsnr / gmk_vlb_term / gmk_vlb_endpoints (Kingma et al. 2021, continuous-time VDM bound).
+// the variational-bound kernels gmk_q_sample_logsnr / gmk_vlb_term / gmk_vlb_endpoints (Kingma et al. 2021, continuous-time VDM bound) and
+// the inpainting merge gmk_inpaint_merge (RePaint, Lugmayr et al. 2022).
 #include <math.h>
 
 #include "gmk_common.h"
@@ -204,6 +205,73 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __res
         if (z_dup) z_dup[base + i] = is_last ? xh : zs;
         if (x_pred) x_pred[base + i] = xh;
         if (eps_pred) eps_pred[base + i] = eh;
+    }
+}
+
+// ---- RePaint inpainting (Lugmayr et al. 2022, Algorithm 1, jump length 1); an extension, no reference call site.
+// The four normals gmk_rng_normal(seed, .) writes at Philox counter `ctr`: rng_kernel<true>'s Box-Muller, the same operations in the same
+// order (the library builds with -ffp-contract=off), so a draw made here equals the one a separate gmk_rng_normal launch would store.
+__device__ __forceinline__ void philox_normal4(uint64_t ctr, uint64_t seed, float (&o)[4]) {
+    uint32_t rnd[4];
+    philox4x32(ctr, seed, rnd);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float u1 = 1.0f - u01(rnd[2 * k]);
+        const float u2 = u01(rnd[2 * k + 1]);
+        const float rad = sqrtf(-2.0f * logf(u1));
+        float s, cs;
+        sincosf(6.283185307179586f * u2, &s, &cs);
+        o[2 * k] = rad * cs; o[2 * k + 1] = rad * s;
+    }
+}
+
+// grid (ceil(n/1024), B), in place after the sampler update of step t -> s has written z (RePaint Algorithm 1):
+//   known = is_last ? x0 : alpha_s x0 + sigma_s eps1;  z = m ? known : z   (a select: where m == 0, z keeps its bits)
+//   renoise: z = a z + b eps2, a = alpha_t / alpha_s, b = sqrt(1 - alpha_t^2 / alpha_s^2)   (q(z_t | z_s): back to time t)
+// eps1 / eps2 are Philox normals drawn here and never stored: element j of this chunk (j = b n + i) takes counter ctr1 + j / 4 (eps1) and
+// ctr2 + j / 4 (eps2), component j % 4.  eps1 is only formed for groups of four with a known pixel (and never when is_last), eps2 only when
+// renoise; x0 is only read where a group has a known pixel.  n % 4 == 0: every group of four lies in one row and starts 16-byte aligned.
+__global__ __launch_bounds__(256) void inpaint_merge_kernel(float* __restrict__ z, const float* __restrict__ x0,
+                                                           const uint8_t* __restrict__ mask, float alpha_s, float sigma_s, float a,
+                                                           float b, int is_last, int renoise, float l_next, uint64_t seed,
+                                                           uint64_t ctr1, uint64_t ctr2, float* __restrict__ z_dup,
+                                                           float* __restrict__ logsnr_next, int64_t n) {
+    const int row = blockIdx.y;
+    if (logsnr_next && blockIdx.x == 0 && threadIdx.x == 0) {
+        logsnr_next[row] = l_next;
+        if (z_dup) logsnr_next[gridDim.y + row] = l_next;
+    }
+    const int64_t base = (int64_t)row * n;
+    for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+        const int64_t j = base + i;
+        const uint64_t q = (uint64_t)(j >> 2);
+        float zv[4];
+        load4(z + j, zv);
+        const uchar4 m4 = *reinterpret_cast<const uchar4*>(mask + j);
+        const uint8_t m[4] = {m4.x, m4.y, m4.z, m4.w};
+        if (m4.x | m4.y | m4.z | m4.w) {
+            float xv[4], known[4];
+            load4(x0 + j, xv);
+            if (is_last) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) known[k] = xv[k];
+            } else {
+                float e[4];
+                philox_normal4(ctr1 + q, seed, e);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) known[k] = alpha_s * xv[k] + sigma_s * e[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zv[k] = m[k] ? known[k] : zv[k];
+        }
+        if (renoise) {
+            float e[4];
+            philox_normal4(ctr2 + q, seed, e);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zv[k] = a * zv[k] + b * e[k];
+        }
+        store4(z + j, zv);
+        if (z_dup) store4(z_dup + j, zv);
     }
 }
 
@@ -495,6 +563,27 @@ extern "C" int gmk_dpm_solver_step(const float* v, const float* v_uncond, const 
                                                                         coef_x, coef_prev, is_last, z_next, x_pred, eps_pred, z_dup,
                                                                         logsnr_next, n, mean_type);
     return gmk_check_launch("gmk_dpm_solver_step");
+}
+
+extern "C" int gmk_inpaint_merge(float* z, const float* x0, const uint8_t* mask, float alpha_s, float sigma_s, float a, float b,
+                                 int is_last, int renoise, float logsnr_t, float logsnr_s, uint64_t seed, uint64_t offset, uint64_t q0,
+                                 int B_total, float* z_dup, float* logsnr_next, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(z && x0 && mask, "gmk_inpaint_merge: null pointer");
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0 && n % 4 == 0, "gmk_inpaint_merge: bad shape B=%d n=%lld (n %% 4 == 0 required)", B,
+                (long long)n);
+    // the chunk's counters lie inside the whole batch's: q0 + B n / 4 <= B_total n / 4
+    GMK_REQUIRE(B_total >= B && B_total < 65536 && q0 <= (uint64_t)(B_total - B) * (uint64_t)(n / 4),
+                "gmk_inpaint_merge: chunk (B=%d, q0=%llu) outside the batch of B_total=%d", B, (unsigned long long)q0, B_total);
+    GMK_REQUIRE(!(is_last && renoise), "gmk_inpaint_merge: the last step does not re-noise");
+    GMK_REQUIRE(isfinite(alpha_s) && isfinite(sigma_s) && isfinite(a) && isfinite(b) && isfinite(logsnr_t) && isfinite(logsnr_s),
+                "gmk_inpaint_merge: non-finite time or coefficient");
+    int gx = (int)((n + 1023) / 1024);
+    if (gx > 64) gx = 64;
+    const uint64_t ctr1 = offset + q0;
+    const uint64_t ctr2 = offset + (uint64_t)B_total * (uint64_t)(n / 4) + q0;
+    inpaint_merge_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(z, x0, mask, alpha_s, sigma_s, a, b, is_last, renoise,
+                                                                     renoise ? logsnr_t : logsnr_s, seed, ctr1, ctr2, z_dup, logsnr_next, n);
+    return gmk_check_launch("gmk_inpaint_merge");
 }
 
 extern "C" int gmk_q_sample_logsnr(const float* x, const float* eps, const float* logsnr, float* z, int B, int64_t n, void* stream) {

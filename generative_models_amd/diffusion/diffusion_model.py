@@ -58,6 +58,8 @@ def make_plugin(GMBase, AttrDict):
                                        # and sample / evaluate with it; not in the reference, off by default
         DG.nlogp_samples = 0           # > 0: loss() also reports the variational bound (`nlogp`, logged as eval/nlogp, and `bpd`) of the sampling
                                        # net with that many log-SNR draws per image; not in the reference, off by default
+        DG.inpaint_eval = 0            # r >= 1: evaluate() also fills in the bottom half of the first 25 test images (RePaint, resample = r) as
+                                       # last_eval['inpaint'] / grid 'inpaint'; not in the reference, off by default
 
         def __init__(self, G):
             super().__init__(G)
@@ -84,6 +86,9 @@ def make_plugin(GMBase, AttrDict):
             if self.nlogp_samples > 0 and self.teacher_net is not None:
                 raise ValueError("nlogp_samples > 0 with teacher_path: a distilled student is conditioned on cond_w; its variational bound "
                                  "is not defined")
+            self.inpaint_eval = int(get("inpaint_eval"))
+            if self.inpaint_eval < 0:
+                raise ValueError(f"inpaint_eval = {self.inpaint_eval}: 0 (off) or the resample count r >= 1")
             self.binarize = int(get("binarize"))
             seed = int(get("seed")) * 1000 + parallel.rank()
             self.diffusion = GaussianDiffusion(mean_type=get("mean_type"), num_steps=int(get("timesteps")),
@@ -247,6 +252,19 @@ def make_plugin(GMBase, AttrDict):
                 cond_w = 0.5 if y is not None else None
                 return self.diffusion.sample(net=net, init_x=noise, cond_w=cond_w, record=False)[0][-1]
 
+        # -- inpainting (an extension): RePaint with this model's sampler on the net sample() uses
+        def inpaint(self, x, mask, y=None, resample=1, seed=0):
+            """Fill in the pixels of x ([B, C, S, S] in [-1, 1], the shape sample() returns) where `mask` (broadcastable to x, {0, 1}) is 0,
+            keeping those where it is 1, with `GaussianDiffusion.inpaint`.  y: labels, as in sample() (then guided with cond_w = 0.5).  The
+            initial noise comes from the sampler's auxiliary stream, the known-region noise from PhiloxStream(seed).  -> [B, C, S, S]"""
+            with torch.no_grad():
+                noise = self._aux_rng.normal(tuple(x.shape), x.device)
+                net = partial(self._sampling_net(), guide=y)
+                cond_w = 0.5 if y is not None else None
+                return self.diffusion.inpaint(net=net, x0=x, mask=mask, init_x=noise, cond_w=cond_w, resample=resample, seed=seed)[0][-1]
+
+        INPAINT_EVAL_SEED = 104723                  # evaluate()'s inpainting: initial noise from PhiloxStream(this), known-region noise from this + 1
+
         # -- evaluate (:89-111): 25 class-conditional samples without guidance, trajectories as uint8
         def evaluate(self, writer, x, y, epoch):
             def proc(t):
@@ -266,6 +284,17 @@ def make_plugin(GMBase, AttrDict):
                 common.write_gridvid(writer, "sampling_process", zs, epoch)
                 common.write_gridvid(writer, "diffusion_model/eps", eps, epoch)
                 common.write_gridvid(writer, "diffusion_model/x", xs, epoch)
+            if self.inpaint_eval > 0:                                 # an extension: after everything above, on Philox streams of its own
+                k = min(25, x.shape[0])
+                x0 = x[:k].float()
+                mask = torch.ones((1, 1, x0.shape[2], 1), dtype=torch.uint8, device=x.device)
+                mask[:, :, x0.shape[2] // 2:] = 0                     # the bottom half (rows >= S / 2) is filled in
+                init = PhiloxStream(self.INPAINT_EVAL_SEED).normal(tuple(x0.shape), x.device)
+                z = self.diffusion.inpaint(net=partial(self._sampling_net(), guide=None if y is None else y[:k]), x0=x0, mask=mask, init_x=init,
+                                           resample=self.inpaint_eval, seed=self.INPAINT_EVAL_SEED + 1)[0][-1]
+                self.last_eval["inpaint"] = proc(z)
+                if writer is not None and self.net.in_channels == 1 and k == 25:
+                    common.write_grid(writer, "inpaint", self.last_eval["inpaint"], epoch)
             random.randint(0, 2 ** 32)                                # :111 keeps the host RNG consumption
 
     return DiffusionModel

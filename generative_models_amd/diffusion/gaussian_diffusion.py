@@ -9,6 +9,7 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
 * DDIM / ancestral / guidance update   gmk_sampler_step (:174-243,:292)
 * DPM-Solver++(2M) update              gmk_dpm_solver_step (sampler='dpmpp_2m': an extension, no reference call site)
 * variational bound (`nll`)            gmk_q_sample_logsnr, gmk_vlb_term, gmk_vlb_endpoints (an extension, no reference call site)
+* RePaint inpainting (`inpaint`)       gmk_inpaint_merge after the update (an extension, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -65,6 +66,34 @@ def dpm_solver_coefs(num_steps):
         rows.append(DpmCoef(i, lt, ls, h, sigma(ls) / sigma(lt), -alpha(ls) * math.expm1(-h), k))
         h_prev = h
     return rows
+
+
+InpaintCoef = namedtuple("InpaintCoef", "i lt ls alpha_s sigma_s a b is_last")
+
+
+def inpaint_coefs(num_steps):
+    """Per-step coefficients of `GaussianDiffusion.inpaint` (RePaint, Lugmayr et al. 2022, Algorithm 1), one row per loop iteration
+    i = T-1 ... 0 on DDIM's time grid; lt / ls are the fp32 log-SNRs the sampler uses.  With alpha^2 = sigmoid(l), sigma^2 = sigmoid(-l):
+      alpha_s, sigma_s  the known region's noisy copy alpha_s x0 + sigma_s eps at time s
+      a, b              the forward transition q(z_t | z_s) = N(a z_s, b^2), a = alpha_t / alpha_s, b^2 = 1 - alpha_t^2 / alpha_s^2,
+                        formed as b^2 = -expm1(lt - ls) sigma_t^2 (no cancellation), so that a^2 sigma_s^2 + b^2 = sigma_t^2
+      is_last           i == 0: the known region is x0 itself and the step never re-noises.
+    All in float64 from the fp32 log-SNRs."""
+    sig = lambda l: 1.0 / (1.0 + math.exp(-l))
+    rows = []
+    for i in range(num_steps)[::-1]:
+        u_t, u_s = sampler_times(i, num_steps)
+        lt, ls = float(logsnr_schedule_cosine_host(u_t)), float(logsnr_schedule_cosine_host(u_s))
+        a = math.sqrt(sig(lt) / sig(ls))
+        b = math.sqrt(-math.expm1(lt - ls) * sig(-lt))
+        rows.append(InpaintCoef(i, lt, ls, math.sqrt(sig(ls)), math.sqrt(sig(-ls)), a, b, i == 0))
+    return rows
+
+
+def inpaint_passes(i, resample):
+    """Network evaluations of inpainting step i: `resample`, the last step (i == 0) one - it never re-noises.  A call of T steps costs
+    T r - (r - 1) forwards."""
+    return 1 if i == 0 else int(resample)
 
 
 # the variational bound's log-SNR range: the schedule's truncation (diffusion_utils.py:199-200)
@@ -368,6 +397,57 @@ class GaussianDiffusion:
         with record=False only the final z is produced and returned as a 1-tuple-compatible triple
         (z[None], None, None) — the 3*T*B*C*H*W*4-byte trajectory is the dominant cost at large T*B otherwise.
         `noises` ([T, ...], indexed by step i) / `net_cond_w` inject the random draws (tests)."""
+        return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, noises=noises, net_cond_w=net_cond_w)
+
+    # ---- inpainting (RePaint, Lugmayr et al. 2022, Algorithm 1; an extension, no reference call site) -------------------------------------
+    @torch.no_grad()
+    def inpaint(self, *, net, x0, mask, init_x, cond_w=None, resample=1, seed=0, record=False):
+        """Fill in the unknown part of x0 with this sampler: after every step t -> s the known pixels (mask 1) of z are replaced by a fresh noisy
+        copy alpha_s x0 + sigma_s eps of x0 (by x0 itself at the last step), the others keep the sampler's value.  With resample = r > 1 every
+        step except the last runs r network evaluations, each but the final one followed by a jump back to time t through q(z_t | z_s) (jump
+        length 1), so a call costs T r - (r - 1) forwards.  mask: bool / uint8 / float with values in {0, 1}, broadcastable to x0's shape
+        ([B, C, H, W]); x0: init_x's shape.  Samplers 'ddim', 'noisy', 'teacher_test' take any r >= 1; 'dpmpp_2m' only r = 1 (its x-hat
+        history has no meaning across a jump back).  `net` / `cond_w` (guidance) as in `sample`, and so is the noise of 'noisy' (one draw from
+        self.rng per network evaluation).  The known-region noise comes from a PhiloxStream(seed) of its own, advanced by 2 B n values per
+        merge, so calls with the same seed see the same numbers.  -> sample()'s triple; with `record` the (z, x_hat, eps_hat) of the last pass
+        of each step, [T, B, C, H, W] each."""
+        r = resample
+        if isinstance(r, bool) or int(r) != r or r < 1:
+            raise ValueError(f"inpaint: resample = {resample}, need an integer >= 1")
+        r = int(r)
+        if self.sampler == "dpmpp_2m" and r > 1:
+            raise ValueError("inpaint: sampler 'dpmpp_2m' takes resample = 1 only (its x-hat history has no meaning across a jump back)")
+        shape = tuple(init_x.shape)
+        if tuple(x0.shape) != shape:
+            raise ValueError(f"inpaint: x0 shape {tuple(x0.shape)} differs from init_x shape {shape}")
+        if len(shape) < 2 or 0 in shape:
+            raise ValueError(f"inpaint: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
+        n1 = math.prod(shape[1:])
+        if n1 % 4:
+            raise ValueError(f"inpaint: {n1} values per image, a multiple of 4 is required")
+        m = self._inpaint_mask(mask, shape, init_x.device)
+        inp = (ops.aligned(x0.to(init_x.device).float()), m, PhiloxStream(seed), r)
+        return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, inp=inp)
+
+    @staticmethod
+    def _inpaint_mask(mask, shape, device):
+        """bool / integer / float mask with values in {0, 1}, broadcastable to `shape` -> uint8 [B, n] on `device` (1 = known)."""
+        if not isinstance(mask, torch.Tensor):
+            raise ValueError(f"inpaint: mask must be a tensor, got {type(mask).__name__}")
+        try:
+            ok = tuple(torch.broadcast_shapes(tuple(mask.shape), shape)) == shape
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError(f"inpaint: mask shape {tuple(mask.shape)} does not broadcast to {shape}")
+        if mask.dtype != torch.bool:
+            if mask.is_complex() or not bool(((mask == 0) | (mask == 1)).all()):
+                raise ValueError("inpaint: mask values must be 0 or 1")
+        m = mask.to(device=device).to(torch.uint8).expand(shape).reshape(shape[0], -1)
+        return ops.aligned(m.contiguous())
+
+    def _sample(self, *, net, init_x, cond_w=None, record=True, noises=None, net_cond_w=None, inp=None):
+        """The loop behind `sample` and `inpaint` (inp: None, or (x0, uint8 mask [B, n], the known-region PhiloxStream, resample))."""
         module, guide, kw_cond_w = _unwrap(net)
         B = init_x.shape[0]
         dev = init_x.device
@@ -402,14 +482,17 @@ class GaussianDiffusion:
             K = 2
         bounds = [(k * B // K, (k + 1) * B // K) for k in range(K)]
         cut = lambda t, a, b_: None if t is None else ops.aligned(t[a:b_])
-        offs = []                      # Philox counter of each step's noise draw for the WHOLE batch (ancestral sampler): chunks take their slice of it
+        # Philox counter of each network evaluation's noise draw for the WHOLE batch (ancestral sampler), and of each inpainting merge's
+        # known-region draws: chunks take their slice of them
+        offs, moffs = [], []
         need_rng = self.sampler == "noisy" and noises is None
         cur = torch.cuda.current_stream() if dev.type == "cuda" else None
         streams = [cur] if K == 1 else self._chunk_streams(dev, K)
         gens = []
         for k, (a, b_) in enumerate(bounds):
+            inp_k = None if inp is None else (cut(inp[0], a, b_), cut(inp[1], a, b_), inp[2].seed, moffs, B, inp[3])
             args = (module, cut(guide, a, b_), cut(student_w, a, b_), cut(w, a, b_), cut(z_all, a, b_),
-                    noises if (noises is None or K == 1) else torch.as_tensor(noises)[:, a:b_], record, offs, a * n1 // 4)
+                    noises if (noises is None or K == 1) else torch.as_tensor(noises)[:, a:b_], record, offs, a * n1 // 4, inp_k)
             gens.append(self._sample_chunk(*args))
         if K > 1:
             # what a forward builds lazily after a weight update (packed weights, frequency tables) is enqueued HERE, on the stream both chunk
@@ -428,9 +511,12 @@ class GaussianDiffusion:
                 else:
                     outs.append(next(gens[k]))
             return outs
-        for _ in range(self.num_steps):
-            if need_rng:
-                offs.append(self.rng._take(B * n1))
+        for i in range(self.num_steps)[::-1]:
+            for _ in range(1 if inp is None else inpaint_passes(i, inp[3])):
+                if need_rng:
+                    offs.append(self.rng._take(B * n1))
+                if inp is not None:
+                    moffs.append(inp[2]._take(2 * B * n1))      # eps1 and eps2 of one merge, used or not
             advance()
             if K > 1:                                   # the throttle's event has to cover both halves
                 for st in streams:
@@ -455,9 +541,11 @@ class GaussianDiffusion:
             self._streams = [torch.cuda.Stream(device=dev) for _ in range(K)]
         return self._streams[:K]
 
-    def _sample_chunk(self, module, guide, student_w, w, z_t, noises, record, offs, q0):
+    def _sample_chunk(self, module, guide, student_w, w, z_t, noises, record, offs, q0, inp=None):
         """The sampler loop over one (chunk of a) batch as a generator: one `next` per step (everything it launches goes to the stream current at
-        that call), then one more for the result.  offs[it] / q0: Philox counter of step `it`'s whole-batch noise draw / this chunk's offset in it."""
+        that call), then one more for the result.  offs[f] / q0: Philox counter of network evaluation `f`'s whole-batch noise draw / this chunk's
+        offset in it.  inp (inpainting): None, or (x0, uint8 mask [B, n] of this chunk, seed, moffs, B_total, resample) - moffs[f] is the
+        whole-batch Philox counter of evaluation f's merge."""
         B = z_t.shape[0]
         dev = z_t.device
         zs, xs, es = [], [], []
@@ -476,28 +564,37 @@ class GaussianDiffusion:
         # dpmpp_2m: the previous step's x-hat, [B, ...] also when guided (the kernel reads and rewrites it in place; the first step does not read it)
         dpm = dpm_solver_coefs(self.num_steps) if self.sampler == "dpmpp_2m" else None
         x_hist = torch.empty_like(z_t) if dpm is not None else None
+        inp_c = inpaint_coefs(self.num_steps) if inp is not None else None
+        f = 0                                   # network evaluations so far (one per step unless inpainting resamples)
         for it, i in enumerate(range(self.num_steps)[::-1]):
             u_t, u_s = sampler_times(i, self.num_steps)
             lt, ls = logsnr_schedule_cosine_host(u_t), logsnr_schedule_cosine_host(u_s)
-            lvec, lnext = lvecs[it & 1], lvecs[(it + 1) & 1]
-            if not guided:
-                v = graphed(z_t) if graphed else module.forward_hip(z_t, lvec, guide, student_w)
-                vu = None
-            else:
-                v2 = graphed(z2) if graphed else module.forward_hip(z2, lvec, guide2, sw2)
-                v, vu = v2[:B], v2[B:]
-            noise = None
-            if self.sampler == "noisy":
-                noise = ops.aligned(noises[i]) if noises is not None else ops.rng_normal(tuple(z_t.shape), self.rng.seed, offs[it] + q0, dev)   # :241
-            if dpm is not None:
-                c = dpm[it]
-                z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, c.coef_z, c.coef_x, c.coef_prev, i == 0, v_uncond=vu, cond_w=w,
-                                                  want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
-            else:
-                z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, i == 0, v_uncond=vu, cond_w=w, noise=noise, want_pred=record,
-                                               mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
-            if guided:
-                z_t, z2 = z_t
+            npass = 1 if inp is None else inpaint_passes(i, inp[5])
+            for p in range(npass):
+                lvec, lnext = lvecs[f & 1], lvecs[(f + 1) & 1]
+                if not guided:
+                    v = graphed(z_t) if graphed else module.forward_hip(z_t, lvec, guide, student_w)
+                    vu = None
+                else:
+                    v2 = graphed(z2) if graphed else module.forward_hip(z2, lvec, guide2, sw2)
+                    v, vu = v2[:B], v2[B:]
+                noise = None
+                if self.sampler == "noisy":
+                    noise = ops.aligned(noises[i]) if noises is not None else ops.rng_normal(tuple(z_t.shape), self.rng.seed, offs[f] + q0, dev)   # :241
+                if dpm is not None:
+                    c = dpm[it]
+                    z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, c.coef_z, c.coef_x, c.coef_prev, i == 0, v_uncond=vu, cond_w=w,
+                                                      want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
+                else:
+                    z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, i == 0, v_uncond=vu, cond_w=w, noise=noise, want_pred=record,
+                                                   mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
+                if guided:
+                    z_t, z2 = z_t
+                if inp is not None:             # the known region, then (all passes but the step's last) the jump back to time t
+                    c = inp_c[it]
+                    ops.inpaint_merge(z_t, inp[0], inp[1], c.alpha_s, c.sigma_s, c.a, c.b, c.is_last, p < npass - 1, lt, ls, inp[2], inp[3][f],
+                                      q0=q0, B_total=inp[4], z_dup=z2[B:] if guided else None, logsnr_next=lnext)
+                f += 1
             if record:
                 zs.append(z_t); xs.append(xp); es.append(ep)
             yield None

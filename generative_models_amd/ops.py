@@ -799,6 +799,55 @@ def dpm_solver_step(v, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x, coef_prev,
     return ((z_next, z2) if dup else z_next), xp, ep
 
 
+def inpaint_merge(z, x0, mask, alpha_s, sigma_s, a, b, is_last, renoise, logsnr_t, logsnr_s, seed, offset, q0=0, B_total=None, z_dup=None,
+                  logsnr_next=None):
+    """RePaint's merge of the known region (gmk_inpaint_merge), in place on z (fp32 [B, ...], the sampler update's output):
+    z = mask ? (is_last ? x0 : alpha_s x0 + sigma_s eps1) : z, then z = a z + b eps2 when `renoise`.  mask: uint8 with B x n elements in z's
+    element order (nonzero = known); x0: z's shape.  eps1 / eps2 are the Philox normals of gmk_rng_normal(seed, offset + q0) and
+    gmk_rng_normal(seed, offset + B_total n / 4 + q0): q0 places this chunk's rows inside a batch of B_total rows (default: the chunk is
+    the batch).  z_dup: a second tensor of z's shape that receives the same values; logsnr_next: fp32 [B] ([2B] with z_dup), filled with
+    logsnr_t when renoise, else logsnr_s.  -> z"""
+    for t, nm in ((z, "z"), (x0, "x0"), (z_dup, "z_dup"), (logsnr_next, "logsnr_next")):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"{nm}: dtype {t.dtype}, expected torch.float32")
+    if mask.dtype != torch.uint8:
+        raise ValueError(f"mask: dtype {mask.dtype}, expected torch.uint8")
+    shape = tuple(z.shape)
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f"z: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
+    B, n = shape[0], math.prod(shape[1:])
+    if n % 4:
+        raise ValueError(f"z: {n} values per image, a multiple of 4 is required")
+    if tuple(x0.shape) != shape:
+        raise ValueError(f"x0: shape {tuple(x0.shape)}, expected {shape}")
+    if mask.dim() < 1 or mask.shape[0] != B or mask.numel() != B * n:
+        raise ValueError(f"mask: shape {tuple(mask.shape)}, expected {B} rows of {n} values")
+    if z_dup is not None and tuple(z_dup.shape) != shape:
+        raise ValueError(f"z_dup: shape {tuple(z_dup.shape)}, expected {shape}")
+    if logsnr_next is not None and (logsnr_next.dim() != 1 or logsnr_next.numel() != (2 * B if z_dup is not None else B)):
+        raise ValueError(f"logsnr_next: shape {tuple(logsnr_next.shape)}, expected ({2 * B if z_dup is not None else B},)")
+    B_total = B if B_total is None else int(B_total)
+    q0, offset, seed = int(q0), int(offset), int(seed)
+    if B_total < B or q0 < 0 or q0 > (B_total - B) * (n // 4):
+        raise ValueError(f"q0 = {q0}, B_total = {B_total}: a chunk of {B} rows must lie inside the batch")
+    if offset < 0 or not 0 <= seed < 1 << 64:
+        raise ValueError(f"offset = {offset}, seed = {seed}: Philox counters and seeds are unsigned 64-bit")
+    if is_last and renoise:
+        raise ValueError("inpaint_merge: the last step does not re-noise")
+    coefs = (alpha_s, sigma_s, a, b, logsnr_t, logsnr_s)
+    if not all(math.isfinite(float(c)) for c in coefs):
+        raise ValueError(f"inpaint_merge: non-finite time or coefficient {coefs}")
+    _f32(z, "z"); _f32(x0, "x0"); _chk(mask, torch.uint8, "mask")
+    if z_dup is not None:
+        _f32(z_dup, "z_dup")
+    if logsnr_next is not None:
+        _f32(logsnr_next, "logsnr_next")
+    check(lib.gmk_inpaint_merge(_p(z), _p(x0), _p(mask), float(alpha_s), float(sigma_s), float(a), float(b), int(bool(is_last)),
+                                int(bool(renoise)), float(logsnr_t), float(logsnr_s), seed, offset, q0, B_total, _p(z_dup), _p(logsnr_next),
+                                B, n, _s()), "inpaint_merge")
+    return z
+
+
 # ---- continuous-time variational bound (an extension; gaussian_diffusion.GaussianDiffusion.nll) ----------------------------------------
 # Shapes, dtypes and the mean type are checked before `_f32` asks for a device tensor, so that a bad call is named for what is wrong with it.
 def _vlb_check(tensors, vectors=()):

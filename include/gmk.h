@@ -291,6 +291,19 @@ int gmk_sampler_step(const float* v, const float* v_uncond, const float* cond_w,
 int gmk_dpm_solver_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float* x_hist, float logsnr_t,
                         float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last, float* z_next, float* x_pred,
                         float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+/* RePaint inpainting merge (Lugmayr et al. 2022, Algorithm 1, jump length 1); an extension, no reference call site.  In place on z (B x n,
+ * fp32), after the sampler update of a step t -> s has written it.  mask: uint8 B x n in x's element order, nonzero = known pixel; x0: the
+ * known image (B x n fp32).  n % 4 == 0.
+ *   known = is_last ? x0 : alpha_s x0 + sigma_s eps1;  z = mask ? known : z  (a select: unknown pixels keep their bits)
+ *   renoise (never with is_last): z = a z + b eps2, a = alpha_t / alpha_s, b = sqrt(1 - alpha_t^2 / alpha_s^2): back to time t.
+ * alpha^2 = sigmoid(logsnr), sigma^2 = sigmoid(-logsnr); the host computes the four coefficients in double from the fp32 log-SNRs.
+ * eps1 / eps2 are Philox normals drawn in the kernel and never stored: with N = B_total n / 4, element j of this chunk is element j of
+ * gmk_rng_normal(seed, offset + q0) (eps1) and of gmk_rng_normal(seed, offset + N + q0) (eps2) - so a chunk of rows at counter offset q0
+ * inside a batch of B_total rows draws exactly what the whole batch would.  z_dup (optional): a second copy of z (the guided 2B batch's
+ * other half); logsnr_next (optional, B floats, 2B with z_dup): filled with logsnr_t when renoise, else logsnr_s. */
+int gmk_inpaint_merge(float* z, const float* x0, const uint8_t* mask, float alpha_s, float sigma_s, float a, float b, int is_last,
+                      int renoise, float logsnr_t, float logsnr_s, uint64_t seed, uint64_t offset, uint64_t q0, int B_total, float* z_dup,
+                      float* logsnr_next, int B, int64_t n, void* stream);
 /* continuous-time variational bound (Kingma et al. 2021, VDM eq. 17 in lambda = logsnr, lambda in [-20, 20]); an extension, no reference
  * call site.  Any n (rows of 4k floats take the vector path).
  *   gmk_q_sample_logsnr: z = alpha x + sigma eps at the given per-sample logsnr[B] (alpha^2 = sigmoid(l), sigma^2 = sigmoid(-l)).

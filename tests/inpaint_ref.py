@@ -1,0 +1,141 @@
+"""CPU restatement of `GaussianDiffusion.inpaint` (RePaint, Lugmayr et al. 2022, Algorithm 1, jump length 1) - test infrastructure.
+
+Built on the oracle's reference pieces: every network evaluation is the oracle's DDIM step (`ddim_step`) or ancestral step
+(`reverse_dpm_step`), or a DPM-Solver++(2M) step formed from `run_model` (+ `cf_guidance`) as tests/dpm_solver_ref.py does, on DDIM's time
+grid (`sampler_times`, `logsnr_schedule_cosine`).  The merge's coefficients are computed here in float64 from the fp32 log-SNRs,
+independently of the package's `inpaint_coefs`.  With alpha^2 = sigmoid(logsnr), sigma^2 = sigmoid(-logsnr), after the update of step t -> s:
+    known = x0 (last step) or alpha_s x0 + sigma_s eps1;   z = where(mask, known, z_s)
+    all passes of a step but its last:  z = (alpha_t / alpha_s) z + sqrt(1 - alpha_t^2 / alpha_s^2) eps2, and the step runs again from z
+The last step (i == 0) runs once.  The random draws are inputs, one entry per network evaluation f: eps1[f], eps2[f] (the merge) and
+noises[f] (sampler 'noisy').  The recorded trajectory is (z, x_hat, eps_hat) of the last pass of each step."""
+import math
+
+import torch
+
+from oracle import diffusion_ref as D
+
+
+def _alpha_sigma(l):
+    l = float(l)
+    return math.sqrt(1.0 / (1.0 + math.exp(-l))), math.sqrt(1.0 / (1.0 + math.exp(l)))
+
+
+def forwards(num_steps, resample):
+    """Network evaluations of one inpainting call."""
+    return sum(1 if i == 0 else resample for i in range(num_steps))
+
+
+def sample(params, init_x, x0, mask, guide, num_steps, sampler="ddim", cond_w=None, resample=1, eps1=None, eps2=None, noises=None,
+           mean_type="v", record=True):
+    """-> (zs, xs, es) stacked [T, B, ...] when `record`, else the final z.  mask: bool, broadcastable to x0; `cond_w`: the resolved
+    per-sample guidance weights or None."""
+    z_t = init_x
+    known_px = torch.broadcast_to(mask.bool(), x0.shape)
+    zs, xs, es = [], [], []
+    x_prev, h_prev = None, None
+    B = init_x.shape[0]
+    f = 0
+    for i in range(num_steps)[::-1]:
+        u_t, u_s = D.sampler_times(i, num_steps)
+        logsnr_t = D.logsnr_schedule_cosine(torch.tensor(u_t))
+        logsnr_s = D.logsnr_schedule_cosine(torch.tensor(u_s))
+        (a_t, s_t), (a_s, s_s) = _alpha_sigma(logsnr_t), _alpha_sigma(logsnr_s)
+        npass = 1 if i == 0 else resample
+        for p in range(npass):
+            if sampler == "ddim":
+                z_s, x_pred, eps_pred = D.ddim_step(params, logsnr_t, logsnr_s, z_t, guide, cond_w, mean_type)
+            elif sampler == "noisy":
+                z_s, x_pred, eps_pred = D.reverse_dpm_step(params, logsnr_t, logsnr_s, z_t, noises[f], guide, cond_w, mean_type)
+            elif sampler == "dpmpp_2m":
+                lt = torch.broadcast_to(logsnr_t.reshape(()), (B,))
+                out = D.run_model(params, z_t, lt, guide=guide, mean_type=mean_type)
+                x_pred, eps_pred = out["model_x"], out["model_eps"]
+                if cond_w is not None:
+                    x_pred, eps_pred = D.cf_guidance(params, z_t, eps_pred, lt, cond_w, guide, mean_type)
+                h = 0.5 * (float(logsnr_s) - float(logsnr_t))
+                if x_prev is None:
+                    d = x_pred
+                else:
+                    k = 1.0 / (2.0 * (h_prev / h))
+                    d = (1.0 + k) * x_pred - k * x_prev
+                z_s = (s_s / s_t) * z_t + (-a_s * math.expm1(-h)) * d
+                x_prev, h_prev = x_pred, h
+            else:
+                raise NotImplementedError(sampler)
+            z_gen = x_pred if i == 0 else z_s
+            known = x0 if i == 0 else a_s * x0 + s_s * eps1[f]
+            z = torch.where(known_px, known, z_gen)
+            if p < npass - 1:
+                a = a_t / a_s
+                z = a * z + math.sqrt(1.0 - a * a) * eps2[f]
+            z_t = z
+            f += 1
+        if record:
+            zs.append(z_t); xs.append(x_pred); es.append(eps_pred)
+    if record:
+        return torch.stack(zs), torch.stack(xs), torch.stack(es)
+    return z_t
+
+
+# ---- the learning check (tests/test_gpu_inpaint.py G7, tools/inpaint_probe.py (c)) -------------------------------------------------------
+# Two fixed 1x28x28 images whose top halves differ and whose bottom halves differ; a net trained on them alone has to complete a top half
+# with the bottom half of the same image.  Both carry label 0, so the label tells the modes apart no more than the unconditional branch does.
+def two_modes():
+    """-> fp32 [2, 1, 28, 28] in [-1, 1]: mode 0 has a bright left / dark right top half over a bright bottom bar, mode 1 the mirror
+    image on top over a dark bottom bar."""
+    x = torch.empty((2, 1, 28, 28))
+    x[0, 0, :14, :14], x[0, 0, :14, 14:], x[0, 0, 14:] = 1.0, -1.0, 0.8
+    x[1, 0, :14, :14], x[1, 0, :14, 14:], x[1, 0, 14:] = -1.0, 1.0, -0.8
+    return x
+
+
+def top_half_mask(S=28):
+    """uint8 [1, 1, S, 1]: 1 (known) on rows < S / 2."""
+    m = torch.zeros((1, 1, S, 1), dtype=torch.uint8)
+    m[:, :, : S // 2] = 1
+    return m
+
+
+def closer_to(samples, modes):
+    """Index of the mode whose bottom half is nearer (L2) to each sample's bottom half.  -> int64 [N]"""
+    h = samples.shape[-2] // 2
+    d = ((samples[:, None, :, h:] - modes[None, :, :, h:]) ** 2).flatten(2).sum(-1)
+    return d.argmin(1)
+
+
+LEARNING_CHECK_STEPS, LEARNING_CHECK_BS, LEARNING_CHECK_T = 300, 64, 50
+LEARNING_CHECK_R = 5                  # the resample count the check runs at (tools/inpaint_probe.py (c))
+
+
+def train_two_mode(make_model, steps=LEARNING_CHECK_STEPS, bs=LEARNING_CHECK_BS, seed=0):
+    """A default plugin model (16-bit mode, hidden 128, DDIM with T = LEARNING_CHECK_T) trained `steps` steps at batch `bs` on the two modes,
+    drawn with equal probability (torch.Generator(seed)), all with label 0.  `make_model(**flags)` builds it on the GPU.  -> the model, eval"""
+    torch.manual_seed(seed)                                       # the initial weights
+    model = make_model(timesteps=LEARNING_CHECK_T, bs=bs, lr=1e-3, in_channels=1, seed=seed)
+    modes = two_modes().cuda()
+    g = torch.Generator().manual_seed(seed)
+    model.train()
+    for _ in range(steps):
+        idx = torch.randint(0, 2, (bs,), generator=g).cuda()
+        model.train_step(modes[idx], torch.zeros((bs,), dtype=torch.long, device="cuda"))
+    torch.cuda.synchronize()
+    return model.eval()
+
+
+def completion_accuracy(model, r, per_mode=32, seed=0):
+    """Inpaint the bottom half of `per_mode` copies of each mode given its top half (resample r, label 0, known-region seed `seed`), and
+    draw as many unconditional samples from the same initial noise.  -> (fraction of completions nearer their own mode's bottom half,
+    fraction of the unconditional samples nearer mode 0)"""
+    from functools import partial
+
+    from generative_models_amd.diffusion.gaussian_diffusion import PhiloxStream
+    modes = two_modes().cuda()
+    x0 = modes.repeat_interleave(per_mode, 0)
+    truth = torch.arange(2, device="cuda").repeat_interleave(per_mode)
+    init = PhiloxStream(1000 + seed).normal(tuple(x0.shape), "cuda")
+    net = partial(model._sampling_net(), guide=torch.zeros((x0.shape[0],), dtype=torch.long, device="cuda"))
+    out = model.diffusion.inpaint(net=net, x0=x0, mask=top_half_mask().cuda(), init_x=init, resample=r, seed=seed)[0][-1]
+    free = model.diffusion.sample(net=net, init_x=init, record=False)[0][-1]
+    right = float((closer_to(out, modes) == truth).float().mean())
+    uncond = float((closer_to(free, modes) == 0).float().mean())
+    return right, uncond

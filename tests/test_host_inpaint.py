@@ -1,0 +1,235 @@
+"""CPU tests (no GPU) of RePaint inpainting (`GaussianDiffusion.inpaint`, `ops.inpaint_merge`, `DiffusionModel.inpaint`, DG.inpaint_eval; an
+extension): the host coefficient table, the pass schedule, every argument check before any launch, the flag, and the CPU restatement the GPU
+tests hold the kernel to."""
+import ctypes
+import math
+import os
+import sys
+
+import pytest
+import torch
+import yaml
+
+ROOT = os.path.dirname(os.path.abspath(os.path.dirname(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import inpaint_ref  # noqa: E402
+
+
+def _sig(l):
+    return 1.0 / (1.0 + math.exp(-l))
+
+
+@pytest.mark.parametrize("T", [2, 4, 250, 1000])
+def test_coefficient_table(T):
+    from generative_models_amd.diffusion.gaussian_diffusion import inpaint_coefs, logsnr_schedule_cosine_host, sampler_times
+    rows = inpaint_coefs(T)
+    assert len(rows) == T and [r.i for r in rows] == list(range(T))[::-1]
+    for r in rows:
+        u_t, u_s = sampler_times(r.i, T)                                 # the sampler's fp32 log-SNRs, exactly
+        assert r.lt == float(logsnr_schedule_cosine_host(u_t)) and r.ls == float(logsnr_schedule_cosine_host(u_s))
+        assert r.alpha_s == pytest.approx(math.sqrt(_sig(r.ls)), rel=1e-14)
+        assert r.sigma_s == pytest.approx(math.sqrt(_sig(-r.ls)), rel=1e-14)
+        assert r.alpha_s ** 2 + r.sigma_s ** 2 == pytest.approx(1.0, abs=1e-14)
+        assert 0.0 < r.a < 1.0                                           # the jump back shrinks the signal ...
+        sigma_t2 = _sig(-r.lt)
+        assert abs(r.a ** 2 * r.sigma_s ** 2 + r.b ** 2 - sigma_t2) < 1e-12    # ... and q(z_t | z_s) lands on the marginal at t
+        assert r.a == pytest.approx(math.sqrt(_sig(r.lt)) / math.sqrt(_sig(r.ls)), rel=1e-12)
+    assert [r.is_last for r in rows] == [False] * (T - 1) + [True]       # only the last row, and it never re-noises
+
+
+@pytest.mark.parametrize("T", [1, 2, 4, 20])
+@pytest.mark.parametrize("r", [1, 2, 3, 10])
+def test_forward_count(T, r):
+    from generative_models_amd.diffusion.gaussian_diffusion import inpaint_passes
+    n = sum(inpaint_passes(i, r) for i in range(T))
+    assert n == T * r - (r - 1) == inpaint_ref.forwards(T, r)
+    assert inpaint_passes(0, r) == 1
+
+
+def test_inpaint_rejects_bad_arguments_before_any_launch():
+    from generative_models_amd.diffusion.gaussian_diffusion import GaussianDiffusion
+    from generative_models_amd.diffusion.simple_unet import SimpleUnet
+    x = torch.zeros((2, 1, 8, 8))
+    ok = torch.ones((2, 1, 8, 8), dtype=torch.uint8)
+    d = GaussianDiffusion(mean_type="v", num_steps=4)
+    net = SimpleUnet(32, 0.0)
+    call = lambda **kw: d.inpaint(**{"net": net, "x0": x, "mask": ok, "init_x": x, **kw})
+    for bad in (torch.full((2, 1, 8, 8), 2, dtype=torch.uint8), torch.full((1, 1, 8, 8), 0.5), torch.full((2, 1, 1, 1), -1.0),
+                torch.full((1,), float("nan"))):
+        with pytest.raises(ValueError, match="0 or 1"):
+            call(mask=bad)
+    for bad in (torch.ones((3, 1, 8, 8)), torch.ones((2, 1, 8, 7)), torch.ones((1, 2, 1, 1)), torch.ones((1, 2, 1, 8, 8))):
+        with pytest.raises(ValueError, match="broadcast"):
+            call(mask=bad)
+    with pytest.raises(ValueError, match="x0 shape"):
+        call(x0=torch.zeros((2, 1, 8, 4)))
+    with pytest.raises(ValueError, match="x0 shape"):
+        call(x0=torch.zeros((1, 1, 8, 8)))
+    odd = torch.zeros((2, 1, 3, 3))
+    with pytest.raises(ValueError, match="multiple of 4"):
+        call(x0=odd, init_x=odd, mask=torch.ones((1,)))
+    for r in (0, -1, 1.5):
+        with pytest.raises(ValueError, match="resample"):
+            call(resample=r)
+    d.sampler = "dpmpp_2m"
+    with pytest.raises(ValueError, match="dpmpp_2m"):
+        call(resample=2)
+
+
+def test_mask_is_materialised_as_uint8_rows():
+    from generative_models_amd.diffusion.gaussian_diffusion import GaussianDiffusion
+    m = GaussianDiffusion._inpaint_mask(torch.tensor([True, False, True, True]).reshape(1, 1, 1, 4), (3, 2, 2, 4), "cpu")
+    assert m.dtype == torch.uint8 and tuple(m.shape) == (3, 16) and m.is_contiguous()
+    assert m.tolist() == [[1, 0, 1, 1] * 4] * 3
+    m = GaussianDiffusion._inpaint_mask(torch.tensor([0.0, 1.0]).reshape(2, 1, 1, 1), (2, 1, 2, 2), "cpu")
+    assert m.tolist() == [[0] * 4, [1] * 4]
+
+
+def test_merge_wrapper_rejects_bad_arguments():
+    from generative_models_amd import ops
+    z = torch.zeros((3, 1, 4, 4))
+    m = torch.ones((3, 16), dtype=torch.uint8)
+    c = dict(alpha_s=0.8, sigma_s=0.6, a=0.5, b=0.7, is_last=False, renoise=False, logsnr_t=-1.0, logsnr_s=1.0, seed=1, offset=0)
+    call = lambda z=z, x0=z, mask=m, **kw: ops.inpaint_merge(z, x0, mask, **{**c, **kw})
+    with pytest.raises(ValueError, match="dtype"):
+        call(z=z.double())
+    with pytest.raises(ValueError, match="dtype"):
+        call(x0=z.half())
+    with pytest.raises(ValueError, match="dtype"):
+        call(mask=m.bool())
+    with pytest.raises(ValueError, match="dtype"):
+        call(z_dup=z.bfloat16())
+    with pytest.raises(ValueError, match="dtype"):
+        call(logsnr_next=torch.zeros((3,), dtype=torch.float64))
+    odd = torch.zeros((3, 1, 3, 3))
+    with pytest.raises(ValueError, match="multiple of 4"):
+        call(z=odd, x0=odd, mask=torch.ones((3, 9), dtype=torch.uint8))
+    with pytest.raises(ValueError, match="shape"):
+        call(z=torch.zeros((3,)))
+    with pytest.raises(ValueError, match="shape"):
+        call(x0=torch.zeros((3, 1, 4, 8)))
+    for bad in (torch.ones((3, 12), dtype=torch.uint8), torch.ones((1, 48), dtype=torch.uint8), torch.ones((48,), dtype=torch.uint8)):
+        with pytest.raises(ValueError, match="mask"):
+            call(mask=bad)
+    with pytest.raises(ValueError, match="z_dup"):
+        call(z_dup=torch.zeros((6, 1, 4, 4)))
+    with pytest.raises(ValueError, match="logsnr_next"):
+        call(logsnr_next=torch.zeros((6,)))
+    with pytest.raises(ValueError, match="logsnr_next"):
+        call(logsnr_next=torch.zeros((3,)), z_dup=z)
+    with pytest.raises(ValueError, match="batch"):
+        call(B_total=2)
+    with pytest.raises(ValueError, match="batch"):
+        call(B_total=4, q0=4 * 1 + 1)                                  # (B_total - B) n / 4 = 4 counters of room
+    with pytest.raises(ValueError, match="unsigned"):
+        call(offset=-1)
+    with pytest.raises(ValueError, match="last step"):
+        call(is_last=True, renoise=True)
+    with pytest.raises(ValueError, match="non-finite"):
+        call(b=float("nan"))
+    with pytest.raises(ValueError, match="device tensor"):           # the mask may have any shape with B rows of n values
+        call(mask=torch.ones((3, 1, 4, 4), dtype=torch.uint8), z_dup=z, logsnr_next=torch.zeros((6,)), B_total=4, q0=4)
+
+
+def test_header_declares_the_entry():
+    from generative_models_amd import _lib
+    protos = _lib.parse_header(os.path.join(ROOT, "include", "gmk.h"))
+    ret, argtypes, argnames = protos["gmk_inpaint_merge"]
+    assert argnames == ["z", "x0", "mask", "alpha_s", "sigma_s", "a", "b", "is_last", "renoise", "logsnr_t", "logsnr_s", "seed", "offset",
+                        "q0", "B_total", "z_dup", "logsnr_next", "B", "n", "stream"]
+    P, F, I, U = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint64
+    assert argtypes == [P] * 3 + [F] * 4 + [I, I, F, F, U, U, U, I, P, P, I, ctypes.c_int64, P]
+    assert ret is ctypes.c_int
+
+
+def test_entry_rejects_bad_arguments_before_any_launch():
+    from generative_models_amd import _lib
+    lib = _lib.lib
+    buf = ctypes.c_void_p(16)        # never dereferenced: argument checks come first
+
+    def call(z=buf, x0=buf, mask=buf, b=0.5, is_last=0, renoise=0, q0=0, B_total=2, B=2, n=64):
+        return lib.gmk_inpaint_merge(z, x0, mask, 0.8, 0.6, 0.5, b, is_last, renoise, -1.0, 1.0, 1, 0, q0, B_total, None, None, B, n, None)
+    for kw in ({"z": None}, {"x0": None}, {"mask": None}):
+        assert call(**kw) == -1 and b"null pointer" in lib.gmk_last_error()
+    for kw in ({"B": 0}, {"B": 70000, "B_total": 70000}, {"n": 0}, {"n": 62}):
+        assert call(**kw) == -1 and b"shape" in lib.gmk_last_error()
+    for kw in ({"B_total": 1}, {"B_total": 3, "q0": 17}):
+        assert call(**kw) == -1 and b"outside the batch" in lib.gmk_last_error()
+    assert call(is_last=1, renoise=1) == -1 and b"re-noise" in lib.gmk_last_error()
+    assert call(b=float("inf")) == -1 and b"non-finite" in lib.gmk_last_error()
+
+
+def test_flag_default_cli_and_hps(tmp_path):
+    from generative_models_amd import common, main
+    Model = common.discover_models()["diffusion_model"]
+    assert Model.DG.inpaint_eval == 0 and isinstance(Model.DG.inpaint_eval, int)
+    G, _ = main.FlagSpace(main.DG).resolve(["--model=diffusion"])
+    assert G.inpaint_eval == 0
+    G, _ = main.FlagSpace(main.DG).resolve(["--model=diffusion", "--inpaint_eval", "3"])
+    assert G.inpaint_eval == 3
+    G.logdir = str(tmp_path)
+
+    class Writer:
+        def add_scalar(self, *a):
+            pass
+
+        def flush(self):
+            pass
+    common.dump_logger({"loss": [1.0]}, Writer(), 0, G)
+    with open(tmp_path / "hps.yaml") as f:
+        assert yaml.load(f, Loader=yaml.Loader)["inpaint_eval"] == 3
+
+
+def test_model_flag_check():
+    from generative_models_amd import common
+    Model = common.discover_models()["diffusion_model"]
+    G = common.AttrDict(dict(Model.DG))
+    G.update(hidden_size=32, inpaint_eval=-1)
+    with pytest.raises(ValueError, match="inpaint_eval"):
+        Model(G)
+
+
+def _restatement_case(sampler, guided, resample=1, T=3, mean_type="v"):
+    from oracle import unet_ref as U
+    params = U.reference_init_params(32, 1, zero_out_layers=False, seed=3)
+    g = torch.Generator().manual_seed(4)
+    B, S = 2, 8
+    init = torch.randn((B, 1, S, S), generator=g)
+    x0 = torch.rand((B, 1, S, S), generator=g) * 2 - 1
+    F = inpaint_ref.forwards(T, resample)
+    draws = {k: torch.randn((F, B, 1, S, S), generator=g) for k in ("eps1", "eps2", "noises")}
+    y = torch.tensor([2, 5])
+    w = torch.tensor([0.4, 2.0]) if guided else None
+    return params, init, x0, y, w, draws
+
+
+@pytest.mark.parametrize("sampler,guided", [("ddim", False), ("ddim", True), ("noisy", False), ("dpmpp_2m", False)])
+def test_restatement_with_an_empty_mask_is_the_sampler(sampler, guided):
+    """With nothing known and r = 1 the merge leaves every value alone: the chain is the oracle's (or the DPM-Solver restatement's), exactly."""
+    import dpm_solver_ref
+    from oracle import diffusion_ref as D
+    params, init, x0, y, w, dr = _restatement_case(sampler, guided)
+    with torch.no_grad():
+        a = inpaint_ref.sample(params, init, x0, torch.zeros((1,), dtype=torch.bool), y, 3, sampler, cond_w=w, noises=dr["noises"], **{
+            k: dr[k] for k in ("eps1", "eps2")})
+        if sampler == "dpmpp_2m":
+            b = dpm_solver_ref.sample(params, init, y, 3, cond_w=w)
+        else:
+            b = D.sample(params, init, y, 3, sampler, cond_w=w, noises=dr["noises"].flip(0))      # the oracle indexes noises by step i
+    for p, q in zip(a, b):
+        assert torch.equal(p, q)
+
+
+@pytest.mark.parametrize("resample", [1, 3])
+def test_restatement_with_a_full_mask_ends_on_x0(resample):
+    params, init, x0, y, w, dr = _restatement_case("ddim", False, resample)
+    with torch.no_grad():
+        zs, xs, _ = inpaint_ref.sample(params, init, x0, torch.ones((1,), dtype=torch.bool), y, 3, "ddim", resample=resample,
+                                       eps1=dr["eps1"], eps2=dr["eps2"])
+    assert torch.equal(zs[-1], x0)
+    # a known pixel at step s is a draw of q(z_s | x0): alpha_s x0 + sigma_s eps1 of that step's last merge
+    from oracle import diffusion_ref as D
+    u_t, u_s = D.sampler_times(2, 3)
+    l = float(D.logsnr_schedule_cosine(torch.tensor(u_s)))
+    a_s, s_s = math.sqrt(_sig(l)), math.sqrt(_sig(-l))
+    assert torch.allclose(zs[0], a_s * x0 + s_s * dr["eps1"][resample - 1], atol=1e-6)
