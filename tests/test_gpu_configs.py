@@ -503,3 +503,20 @@ def test_bench_dump_outputs_are_the_last_timed_step_and_reproducible(tmp_path):
     assert a["params"].shape == a["grads"].shape == (n,) and np.isfinite(a["grads"]).all() and np.abs(a["grads"]).max() > 0
     for k in a:
         assert np.array_equal(a[k], b[k]), k
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain `bench.py` run (no `--full`) times the headline's steps and prints its line: the sampler, steady-state, other-config and CPU
+    flags keep their defaults here, and none of those runs happens."""
+    import json
+    flags = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "custom", "--batch", "64"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GMK_FORCE_EXCHANGE", "GMK_BENCH_STEADY_STEPS")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + flags, capture_output=True, text=True, timeout=600, cwd=ROOT,
+                       env=dict(env, OMP_NUM_THREADS="2", GMK_BENCH_DETAIL=str(tmp_path / "detail.json")))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "ddpm_train_images_per_sec" and line["value"] > 0 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0 and line["roofline"]["kernel"].startswith("conv")      # (from the timed steps' own events)
+    full = json.load(open(tmp_path / "detail.json"))
+    for d in (line, full):
+        assert not {"steady_state", "sampler", "other_configs", "cpu_baseline", "exchange"} & {k for k, v in d.items() if v is not None}, sorted(d)

@@ -89,7 +89,7 @@ def test_bench_two_ranks_rehearsal(form):
     from rank 0 with the whole-job rate."""
     import json
     flags = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "custom", "--batch", "64", "--sampler_steps", "2",
-             "--sampler_steps_other", "2", "--no_cpu"]
+             "--sampler_steps_other", "2", "--no_cpu", "--full"]
     if form == "plain":
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + flags
     else:
@@ -199,7 +199,7 @@ def test_bench_forced_exchange_on_one_gpu():
     """`GMK_FORCE_EXCHANGE=1 python bench.py --gpus 1`: the N = 1 line with an `exchange` block measured over RCCL (one rank) - both carve-out
     settings, `exposed_ms`, the RCCL version - so that the overlap machinery of the N > 1 line has run on hardware before a node is available."""
     import json
-    flags = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "custom", "--batch", "256", "--sampler_steps", "0", "--no_cpu"]
+    flags = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "custom", "--batch", "256", "--sampler_steps", "0", "--no_cpu", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + flags, capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(env, GMK_FORCE_EXCHANGE="1", OMP_NUM_THREADS="2", GMK_BENCH_STEADY_STEPS="6", GMK_BENCH_AB_STEPS="4"))

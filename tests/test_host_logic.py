@@ -626,6 +626,46 @@ def test_bench_arguments_and_output_dump(tmp_path):
     assert np.array_equal(g1[:200], arrays["grads"].float().numpy()[idx])  # the same positions in both arrays of one length
 
 
+def test_bench_plain_run_measures_the_headline_alone(tmp_path, monkeypatch, capsys):
+    """`bench.py --steps K --warmup W` runs the headline config and prints its line; the other configs, the fp32 modes and the CPU baseline
+    run with `--full` only, after the headline, and the headline's own run is the same call in both modes."""
+    import json
+    import bench
+    from generative_models_amd._lib import lib
+    calls = []
+
+    def run_config(self, key, spec, steps, warmup, headline, dtype=None, sampler=True):
+        calls.append((key, steps, warmup, headline, dtype))
+        return {"value": 100.0, "ms_per_step": 20.0, "workload": key, "baseline_entry": spec[4], "global_batch": spec[2]}
+
+    def cpu(seconds, S, cin):
+        calls.append(("cpu", S, cin))
+        return {"value": 1.0, "sampler_steps_per_sec": 1.0, "sample": "s", "sampler_sample": "s"}
+
+    monkeypatch.setattr(bench.Bench, "run_config", run_config)
+    monkeypatch.setattr(bench, "cpu_baseline", cpu)
+    monkeypatch.setattr(bench, "fp32_mode", lambda: ("fp32 storage, exact-fp32 MFMA", bench.MFMA_F32_PEAK_TFLOPS))
+    monkeypatch.setattr(lib, "gmk_set_fp32_exact", lambda exact: 0)
+    monkeypatch.setenv("GMK_BENCH_DETAIL", str(tmp_path / "detail.json"))
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full"])):
+        b = object.__new__(bench.Bench)          # (no device: run_config is the stand-in above)
+        b.a, b.world, b.rank = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"] + extra), 1, 0
+        calls.clear()
+        b.main()
+        lines[mode] = (json.loads(capsys.readouterr().out.strip().splitlines()[-1]), list(calls))
+    line, ran = lines["plain"]
+    assert ran == [("cfg2", 7, 2, True, None)]
+    assert (line["metric"], line["value"], line["unit"], line["higher_is_better"], line["ms_per_step"]) == ("ddpm_train_images_per_sec", 100.0, "images/s", True, 20.0)
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["dtype"] == "fp16_fwd+bf16_bwd"
+    assert not {"other_configs", "cpu_baseline", "steady_state", "sampler"} & set(line)
+    line, ran = lines["full"]
+    assert ran[0] == ("cfg2", 7, 2, True, None) and ran[1:4] == [(k, 50, 10, False, None) for k in ("cfg1", "cfg3", "cfg4")]
+    assert ran[4:6] == [("cfg2", 10, 3, False, "fp32")] * 2 and ran[6:] == [("cpu", 32, 3), ("cpu", 28, 1)]
+    assert line["value"] == 100.0 and set(line["other_configs"]) == {"cfg1", "cfg3", "cfg4", "cfg2_fp32", "cfg2_fp32_split"}
+    assert line["cpu_baseline"]["cfg0_shape"]["value"] == 1.0
+
+
 def test_bench_launcher_branch_starts_ranks_without_touching_the_gpu():
     """Plain `python bench.py --gpus N` (no WORLD_SIZE: how the driver has called bench.py so far) must start its own N ranks as a child
     `torch.distributed.run`, from a process that has not initialised the GPU; with WORLD_SIZE set (the documented launcher form) or N = 1

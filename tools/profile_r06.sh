@@ -5,7 +5,7 @@
 # PARTS=reports (bench line + parity / trajectory reports) run in separate calls)
 #   r06_<cfg>_train_serial_kernel_stats.csv   rocprofv3 --kernel-trace --stats of the train steps with non-overlapping launches
 #                                             (GMK_WGRAD_STREAM=0): the averages that compare with the bench line's HIP events
-#   r06_bench_kernel_stats.csv                the default `python bench.py` command (all configs, samplers, overlapping streams)
+#   r06_bench_kernel_stats.csv                the `python bench.py --full` command (all configs, samplers, overlapping streams)
 #   r06_<cfg>_sampler_serial_kernel_stats.csv  the DDIM loop on ONE stream (shares are read from this one); ..._two_stream_...: the shipped form
 #   r06_traffic.json                          HBM bytes per launch of every kernel of the headline config, separate --pmc passes,
 #                                             stamped with the kernel-source hash (bench.py quotes it only for the same sources)
@@ -34,7 +34,7 @@ for cfg in cfg2 cfg1; do
   cp $(find $OUT/sampler2_$cfg -name "*kernel_stats.csv" | head -1) profiles/r06_${cfg}_sampler_two_stream_kernel_stats.csv
   echo "sampler $cfg done"
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python bench.py --no_cpu --sampler_steps 100 > $OUT/prof_bench.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python bench.py --full --no_cpu --sampler_steps 100 > $OUT/prof_bench.log 2>&1 || exit 1
 cp $(find $OUT/bench -name "*kernel_stats.csv" | head -1) profiles/r06_bench_kernel_stats.csv
 echo "bench stats done"
 fi
@@ -66,7 +66,7 @@ echo "traffic done"
 cp profiles/r06_traffic.json $KEEP/
 fi
 [[ " $PARTS " == *" reports "* ]] || exit 0
-python bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 cp $OUT/bench.json profiles/r06_bench.json                     # the compact line (what the driver parses)
 cp gpurun_out/bench_detail.json profiles/r06_bench_detail.json   # the full record of the same run
 python tools/wgrad_s2_ab.py 2>/dev/null > profiles/r06_wgrad_stride2_ab.txt || exit 1      # stride-2 weight gradient: four-plane slot form vs im2col, per launch
