@@ -490,6 +490,101 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, co
     }
 }
 
+// ---- probability-flow ODE (Song et al. 2021, section 4.3 and App. D.2, in lambda = logsnr); an extension, no reference call site.
+// Probes and dequantisation noise use gmk_rng_uniform's counters: element i is component i % 4 of Philox counter offset + i / 4, so the
+// host can replay them with a plain uniform draw.
+__global__ __launch_bounds__(256) void rng_rademacher_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
+    const int64_t nq = (n + 3) / 4;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t rnd[4];
+        philox4x32(offset + (uint64_t)q, seed, rnd);
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = u01(rnd[k]) >= 0.5f ? 1.0f : -1.0f;
+        const int64_t i = q * 4;
+        if (i + 3 < n) store4(out + i, o);
+        else for (int k = 0; i + k < n; ++k) out[i + k] = o[k];
+    }
+}
+
+// y = x + delta (2 u - 1): uniform dequantisation inside the bin of half-width delta; u is never stored
+__global__ __launch_bounds__(256) void dequantize_kernel(const float* __restrict__ x, float* __restrict__ y, float delta, int64_t n,
+                                                        uint64_t seed, uint64_t offset) {
+    const int64_t nq = (n + 3) / 4;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t rnd[4];
+        philox4x32(offset + (uint64_t)q, seed, rnd);
+        const int64_t i = q * 4;
+        if (i + 3 < n) {
+            float xv[4], o[4];
+            load4(x + i, xv);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = xv[k] + delta * (2.0f * u01(rnd[k]) - 1.0f);
+            store4(y + i, o);
+        } else {
+            for (int k = 0; i + k < n; ++k) y[i + k] = x[i + k] + delta * (2.0f * u01(rnd[k]) - 1.0f);
+        }
+    }
+}
+
+// grid (gx, B); gx = 1 whenever acc or prior is given (one workgroup per image, vlb_term_kernel's fixed-order reduction).  Per element:
+// x_hat / eps_hat of the network output at (z, logsnr_i), both unclipped; z = alpha_j x_hat + sigma_j eps_hat in place when `update`;
+// x_hat to x_out when given.  Per image: acc += div_a + div_b sum r g (the weighted divergence) and prior = 1/2 sum z^2 + prior_c.
+// z is read and written by the same thread (no __restrict__ on it: the prior reads the values the update overwrites - never both in one launch).
+__global__ __launch_bounds__(256) void pf_ode_step_kernel(const float* __restrict__ out, float* z, const float* __restrict__ r,
+                                                         const float* __restrict__ g, float* __restrict__ acc, float* __restrict__ prior,
+                                                         float* __restrict__ x_out, float li, float lj, int update, float div_a,
+                                                         float div_b, float prior_c, int64_t n, int mt) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const LogsnrCoef c = logsnr_coef(li);
+    const LogsnrCoef cj = logsnr_coef(lj);
+    const bool div = acc != nullptr, pri = prior != nullptr;
+    const int64_t base = (int64_t)b * n;
+    float srg = 0.f, szz = 0.f;
+    if ((n & 3) == 0) {
+        for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+            float ov[4], zv[4], xh[4];
+            load4(out + base + i, ov);
+            load4(z + base + i, zv);
+            if (div) {
+                float rv[4], gv[4];
+                load4(r + base + i, rv);
+                load4(g + base + i, gv);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) srg = fmaf(rv[k], gv[k], srg);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (pri) szz = fmaf(zv[k], zv[k], szz);
+                xh[k] = x_from_out(ov[k], zv[k], c, mt);
+                const float eh = eps_from_out(ov[k], zv[k], c, mt);
+                zv[k] = cj.alpha * xh[k] + cj.sigma * eh;
+            }
+            if (update) store4(z + base + i, zv);
+            if (x_out) store4(x_out + base + i, xh);
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+            const float o = out[base + i], zz = z[base + i];
+            if (div) srg = fmaf(r[base + i], g[base + i], srg);
+            if (pri) szz = fmaf(zz, zz, szz);
+            const float xh = x_from_out(o, zz, c, mt);
+            const float eh = eps_from_out(o, zz, c, mt);
+            if (update) z[base + i] = cj.alpha * xh + cj.sigma * eh;
+            if (x_out) x_out[base + i] = xh;
+        }
+    }
+    if (div) {
+        srg = block_sum(srg, red);
+        if (threadIdx.x == 0) acc[b] += div_a + div_b * srg;
+    }
+    if (pri) {
+        szz = block_sum(szz, red);
+        if (threadIdx.x == 0) prior[b] = 0.5f * szz + prior_c;
+    }
+}
+
 int stream_grid(int64_t work_items) {
     int64_t g = (work_items + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
@@ -725,4 +820,37 @@ extern "C" int gmk_adam_ema_step(float* p, const float* g, float* m, float* v, f
     adam_ema_kernel<<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, ema, n, step_size, beta1, beta2, eps,
                                                                             inv_bc2_sqrt, grad_scale, ema_w);
     return gmk_check_launch("gmk_adam_ema_step");
+}
+
+extern "C" int gmk_rng_rademacher(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
+    GMK_REQUIRE(out && n > 0, "gmk_rng_rademacher: bad arguments");
+    rng_rademacher_kernel<<<stream_grid((n + 3) / 4), 256, 0, gmk_stream(stream)>>>(out, n, seed, offset);
+    return gmk_check_launch("gmk_rng_rademacher");
+}
+
+extern "C" int gmk_dequantize(const float* x, float* y, float delta, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
+    GMK_REQUIRE(x && y && n > 0, "gmk_dequantize: bad arguments");
+    GMK_REQUIRE(delta > 0.0f && delta <= 0.5f, "gmk_dequantize: delta = %g outside (0, 0.5]", (double)delta);
+    dequantize_kernel<<<stream_grid((n + 3) / 4), 256, 0, gmk_stream(stream)>>>(x, y, delta, n, seed, offset);
+    return gmk_check_launch("gmk_dequantize");
+}
+
+extern "C" int gmk_pf_ode_step(const float* out, float* z, const float* r, const float* g, float* acc, float* prior, float* x_out,
+                               float logsnr_i, float logsnr_j, int update, float div_a, float div_b, float prior_c, int mean_type, int B,
+                               int64_t n, void* stream) {
+    GMK_REQUIRE(out && z, "gmk_pf_ode_step: null pointer");
+    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "gmk_pf_ode_step: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_pf_ode_step: bad shape B=%d n=%lld", B, (long long)n);
+    GMK_REQUIRE(!acc || (r && g), "gmk_pf_ode_step: the divergence needs the probe r and the VJP g");
+    GMK_REQUIRE(!(prior && update), "gmk_pf_ode_step: the prior is taken at the last point, which has no update");
+    GMK_REQUIRE(isfinite(logsnr_i) && isfinite(logsnr_j) && isfinite(div_a) && isfinite(div_b) && isfinite(prior_c),
+                "gmk_pf_ode_step: non-finite time or coefficient");
+    int gx = 1;
+    if (!acc && !prior) {
+        const int64_t g64 = (n + 1023) / 1024;
+        gx = (int)(g64 > 64 ? 64 : g64);
+    }
+    pf_ode_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(out, z, r, g, acc, prior, x_out, logsnr_i, logsnr_j, update, div_a,
+                                                                     div_b, prior_c, n, mean_type);
+    return gmk_check_launch("gmk_pf_ode_step");
 }

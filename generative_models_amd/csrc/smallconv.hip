@@ -682,11 +682,13 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_tile16_kernel(const float* __
 // One workgroup = one band of image rows.  Pass 1 reads every activation vector of the band (+1 row above/below) once and
 // leaves its 9 per-tap channel sums in LDS (tap[t][q] = sum_c a[q,c] w[s][c][t], reduced over the pixel's lanes with DPP);
 // pass 2 adds the 9 shifted planes per output pixel.  (A gather would read each activation 9 times through L1.)
-template <typename T>
-__global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a, const float* __restrict__ w,
-                                                      const float* __restrict__ bias, float* __restrict__ out, int cs,
-                                                      int H, int W, int C, float inv_w, int band, int nbands) {
-    extern __shared__ __attribute__((aligned(16))) float tapl[];   // [9][(band+2)*W]
+// STEM_DGRAD: the same contraction is the stem's data gradient (transposed 3x3 convolution, C -> cs):
+//   dx[b,s,p] = sum_{t,c} dy[b,p - off(t),c] * w[c][s][t] = sum_{t,c} dy[b,p + off(t),c] * w[c][s][8 - t]      w: [C][cs][3][3]
+// i.e. the head forward with the weight transposed and flipped (read in place) and no bias.
+template <typename T, bool STEM_DGRAD>
+__device__ __forceinline__ void head_fwd_body(const T* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias,
+                                              float* __restrict__ out, int cs, int H, int W, int C, float inv_w, int band, int nbands,
+                                              float* tapl) {                      // [9][(band+2)*W]
     const int tid = threadIdx.x;
     const int nvec = C >> 3, planes = 256 / nvec;
     const int vec = tid % nvec, pl = tid / nvec;
@@ -700,7 +702,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a, 
 #pragma unroll
         for (int t = 0; t < 9; ++t)
 #pragma unroll
-            for (int i = 0; i < 8; ++i) wr[t][i] = w[((size_t)s * C + vec * 8 + i) * 9 + t];
+            for (int i = 0; i < 8; ++i)
+                wr[t][i] = STEM_DGRAD ? w[((size_t)(vec * 8 + i) * cs + s) * 9 + (8 - t)] : w[((size_t)s * C + vec * 8 + i) * 9 + t];
         if (s) __syncthreads();
         for (int q0 = 0; q0 < next; q0 += planes) {      // every lane of a wave runs the same trip count (DPP below)
             const int q = q0 + pl;
@@ -723,7 +726,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a, 
             if (vec < 9 && q < next) tapl[vec * plane + q] = mine;
         }
         __syncthreads();
-        const float bv = bias[s];
+        const float bv = STEM_DGRAD ? 0.f : bias[s];
         for (int o = tid; o < rows * W; o += 256) {
             const int oyl = div_small(o, inv_w), ox = o - oyl * W;
             const int oy = r0 + oyl;
@@ -744,20 +747,34 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a, 
 }
 
 
+template <typename T>
+__global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, float* __restrict__ out, int cs,
+                                                      int H, int W, int C, float inv_w, int band, int nbands) {
+    extern __shared__ __attribute__((aligned(16))) float tapl[];
+    head_fwd_body<T, false>(a, w, bias, out, cs, H, W, C, inv_w, band, nbands, tapl);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const T* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dx,
+                                                        int cs, int H, int W, int C, float inv_w, int band, int nbands) {
+    extern __shared__ __attribute__((aligned(16))) float tapl[];
+    head_fwd_body<T, true>(dy, w, nullptr, dx, cs, H, W, C, inv_w, band, nbands, tapl);
+}
+
 // ---- head forward on the 16-bit matrix cores (bf16 or fp16 activations) ------------------------------------------------------
 // Pass 1 of the kernel above is a GEMM: Tap[j][q] = sum_c w[j][c] a[q][c], j = (image channel, tap) <= 27 rows, 128-deep.  Here it IS
 // one: v_mfma_f32_32x32x16_bf16 with the fp32 weights split into bf16 hi + lo parts (two MFMAs per k-step, the weight error drops to
 // 2^-17; the activations are bf16 already), the weights resident in registers as A operands, a lane's B operand = the 16 bytes of
 // its pixel's k-slice straight from HBM.  All image channels come out of ONE read of the activations (the VALU kernel re-read the band
 // once per image channel), D[j][q] lands a lane's 16 tap sums for its own pixel, which go to the LDS planes; pass 2 is unchanged.
-// One workgroup of 8 waves = one band of rows (+1 row above / below) of one image.
-template <typename T>
-__global__ __launch_bounds__(512) void head_fwd_mfma_kernel(const T* __restrict__ a, const float* __restrict__ w,
-                                                           const float* __restrict__ bias, float* __restrict__ out, int cs, int H,
-                                                           int W, int band, int nbands, unsigned a_bytes) {
+// One workgroup of 8 waves = one band of rows (+1 row above / below) of one image.  STEM_DGRAD: the stem's data gradient, as in head_fwd_body.
+template <typename T, bool STEM_DGRAD>
+__device__ __forceinline__ void head_fwd_mfma_body(const T* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias,
+                                                   float* __restrict__ out, int cs, int H, int W, int band, int nbands, unsigned a_bytes,
+                                                   float* tapl) {                 // [9 cs][(band+2)*W]
     constexpr int C = 128;
     constexpr unsigned kBadOff = 0xFFFFFF00u;
-    extern __shared__ __attribute__((aligned(16))) float tapl[];   // [9 cs][(band+2)*W]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int b = blockIdx.x / nbands, r0 = (blockIdx.x % nbands) * band;
@@ -775,7 +792,8 @@ __global__ __launch_bounds__(512) void head_fwd_mfma_kernel(const T* __restrict_
         for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float wv = r < K ? w[((size_t)sj * C + 16 * ks + 8 * h + e) * 9 + tj] : 0.f;
+                const int c = 16 * ks + 8 * h + e;
+                const float wv = r >= K ? 0.f : (STEM_DGRAD ? w[((size_t)c * cs + sj) * 9 + (8 - tj)] : w[((size_t)sj * C + c) * 9 + tj]);
                 const T hi = (T)wv;
                 whi[ks][e] = hi;
                 wlo[ks][e] = (T)(wv - (float)hi);
@@ -820,7 +838,7 @@ __global__ __launch_bounds__(512) void head_fwd_mfma_kernel(const T* __restrict_
     for (int o = tid; o < cs * per; o += 512) {
         const int sc = o / per, rem = o - sc * per;
         const int oyl = rem / W, ox = rem - oyl * W, oy = r0 + oyl;
-        float sum = bias[sc];
+        float sum = STEM_DGRAD ? 0.f : bias[sc];
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
             const int iy = oy + ky - 1;
@@ -833,6 +851,21 @@ __global__ __launch_bounds__(512) void head_fwd_mfma_kernel(const T* __restrict_
         }
         out[((size_t)(b * cs + sc) * H + oy) * W + ox] = sum;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void head_fwd_mfma_kernel(const T* __restrict__ a, const float* __restrict__ w,
+                                                           const float* __restrict__ bias, float* __restrict__ out, int cs, int H,
+                                                           int W, int band, int nbands, unsigned a_bytes) {
+    extern __shared__ __attribute__((aligned(16))) float tapl[];
+    head_fwd_mfma_body<T, false>(a, w, bias, out, cs, H, W, band, nbands, a_bytes, tapl);
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void stem_dgrad_mfma_kernel(const T* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dx,
+                                                             int cs, int H, int W, int band, int nbands, unsigned dy_bytes) {
+    extern __shared__ __attribute__((aligned(16))) float tapl[];
+    head_fwd_mfma_body<T, true>(dy, w, nullptr, dx, cs, H, W, band, nbands, dy_bytes, tapl);
 }
 
 int small_ppb(int64_t npix) {          // pixels per workgroup of the streaming kernels
@@ -982,14 +1015,39 @@ extern "C" int gmk_head_wgrad(const float* dout, const void* a, float* dw_part, 
     return gmk_check_launch("gmk_head_wgrad");
 }
 
-extern "C" int gmk_head_fwd(const void* a, const float* w, const float* bias, float* out, int B, int cout, int H, int W,
-                            int C, int dtype, void* stream) {
-    GMK_REQUIRE(a && w && bias && out, "gmk_head_fwd: null pointer");
-    GMK_REQUIRE(small_shape_ok(B, cout, H, W, C), "gmk_head_fwd: unsupported shape");
+// The head forward and the stem data gradient: one C -> cs contraction over 3x3 taps (head_fwd_body / head_fwd_mfma_body)
+template <typename T, bool STEM_DGRAD>
+static void launch_mfma_band(const T* a, const float* w, const float* bias, float* out, int B, int cs, int H, int W, int mb, int nb2,
+                             size_t lds, unsigned a_bytes, hipStream_t stream) {
+    if constexpr (STEM_DGRAD) {
+        static const hipError_t attr = hipFuncSetAttribute((const void*)stem_dgrad_mfma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                           131072);
+        (void)attr;
+        stem_dgrad_mfma_kernel<T><<<B * nb2, 512, lds, stream>>>(a, w, out, cs, H, W, mb, nb2, a_bytes);
+    } else {
+        static const hipError_t attr = hipFuncSetAttribute((const void*)head_fwd_mfma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                           131072);
+        (void)attr;
+        head_fwd_mfma_kernel<T><<<B * nb2, 512, lds, stream>>>(a, w, bias, out, cs, H, W, mb, nb2, a_bytes);
+    }
+}
+
+template <typename T, bool STEM_DGRAD>
+static void launch_valu_band(const T* a, const float* w, const float* bias, float* out, int B, int cs, int H, int W, int C, float inv_w,
+                             int band, int nbands, size_t lds, hipStream_t stream) {
+    if constexpr (STEM_DGRAD)
+        stem_dgrad_kernel<T><<<B * nbands, 256, lds, stream>>>(a, w, out, cs, H, W, C, inv_w, band, nbands);
+    else
+        head_fwd_kernel<T><<<B * nbands, 256, lds, stream>>>(a, w, bias, out, cs, H, W, C, inv_w, band, nbands);
+}
+
+template <bool STEM_DGRAD>
+static int launch_head_contraction(const void* a, const float* w, const float* bias, float* out, int B, int cs, int H, int W, int C,
+                                   int dtype, hipStream_t stream, const char* name) {
     const size_t a_bytes = (size_t)B * H * W * C * 2;
-    if (gmk_is16(dtype) && C == 128 && cout <= 3 && a_bytes < 0xFFFFFF00ull && gmk_kernel_choice(3, "GMK_DEV_VARIANT") != 41) {
-        // matrix-core kernel: all image channels from one read; 9 * cout fp32 planes of (band + 2) rows in <= 124 KiB of LDS
-        int mb = (int)(126976 / ((size_t)36 * cout * W)) - 2;
+    if (gmk_is16(dtype) && C == 128 && cs <= 3 && a_bytes < 0xFFFFFF00ull && gmk_kernel_choice(3, "GMK_DEV_VARIANT") != 41) {
+        // matrix-core kernel: all image channels from one read; 9 * cs fp32 planes of (band + 2) rows in <= 124 KiB of LDS
+        int mb = (int)(126976 / ((size_t)36 * cs * W)) - 2;
         if (mb >= 1) {
             if (mb >= H) mb = H;
             else {                       // equal bands
@@ -997,38 +1055,41 @@ extern "C" int gmk_head_fwd(const void* a, const float* w, const float* bias, fl
                 mb = (H + n - 1) / n;
             }
             const int nb2 = (H + mb - 1) / mb;
-            const size_t lds2 = (size_t)9 * cout * (mb + 2) * W * 4;
-            static const hipError_t attr = hipFuncSetAttribute((const void*)head_fwd_mfma_kernel<bf16_t>,
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-            static const hipError_t attr16 = hipFuncSetAttribute((const void*)head_fwd_mfma_kernel<f16_t>,
-                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-            (void)attr; (void)attr16;
+            const size_t lds2 = (size_t)9 * cs * (mb + 2) * W * 4;
             if (dtype == GMK_F16)
-                head_fwd_mfma_kernel<f16_t><<<B * nb2, 512, lds2, gmk_stream(stream)>>>((const f16_t*)a, w, bias, out, cout, H, W, mb, nb2,
-                                                                                       (unsigned)a_bytes);
+                launch_mfma_band<f16_t, STEM_DGRAD>((const f16_t*)a, w, bias, out, B, cs, H, W, mb, nb2, lds2, (unsigned)a_bytes, stream);
             else
-                head_fwd_mfma_kernel<bf16_t><<<B * nb2, 512, lds2, gmk_stream(stream)>>>((const bf16_t*)a, w, bias, out, cout, H, W, mb, nb2,
-                                                                                        (unsigned)a_bytes);
-            return gmk_check_launch("gmk_head_fwd");
+                launch_mfma_band<bf16_t, STEM_DGRAD>((const bf16_t*)a, w, bias, out, B, cs, H, W, mb, nb2, lds2, (unsigned)a_bytes, stream);
+            return gmk_check_launch(name);
         }
     }
     // band of rows per workgroup: 9 fp32 planes of (band + 2) rows within 48 KiB of LDS, at least 4 workgroups per CU's worth of bands
     int band = 49152 / (36 * W) - 2;
-    GMK_REQUIRE(band >= 1, "gmk_head_fwd: image too wide (W=%d)", W);
+    GMK_REQUIRE(band >= 1, "%s: image too wide (W=%d)", name, W);
     if (band > H) band = H;
     const int nbands = (H + band - 1) / band;
     const size_t lds = (size_t)9 * (band + 2) * W * 4;
     const float inv_w = 1.0f / (float)W;
     if (dtype == GMK_BF16)
-        head_fwd_kernel<bf16_t><<<B * nbands, 256, lds, gmk_stream(stream)>>>((const bf16_t*)a, w, bias, out, cout, H, W, C, inv_w,
-                                                                              band, nbands);
+        launch_valu_band<bf16_t, STEM_DGRAD>((const bf16_t*)a, w, bias, out, B, cs, H, W, C, inv_w, band, nbands, lds, stream);
     else if (dtype == GMK_F16)
-        head_fwd_kernel<f16_t><<<B * nbands, 256, lds, gmk_stream(stream)>>>((const f16_t*)a, w, bias, out, cout, H, W, C, inv_w,
-                                                                             band, nbands);
+        launch_valu_band<f16_t, STEM_DGRAD>((const f16_t*)a, w, bias, out, B, cs, H, W, C, inv_w, band, nbands, lds, stream);
     else if (dtype == GMK_F32)
-        head_fwd_kernel<float><<<B * nbands, 256, lds, gmk_stream(stream)>>>((const float*)a, w, bias, out, cout, H, W, C, inv_w,
-                                                                             band, nbands);
+        launch_valu_band<float, STEM_DGRAD>((const float*)a, w, bias, out, B, cs, H, W, C, inv_w, band, nbands, lds, stream);
     else
-        GMK_REQUIRE(false, "gmk_head_fwd: bad dtype %d", dtype);
-    return gmk_check_launch("gmk_head_fwd");
+        GMK_REQUIRE(false, "%s: bad dtype %d", name, dtype);
+    return gmk_check_launch(name);
+}
+
+extern "C" int gmk_head_fwd(const void* a, const float* w, const float* bias, float* out, int B, int cout, int H, int W,
+                            int C, int dtype, void* stream) {
+    GMK_REQUIRE(a && w && bias && out, "gmk_head_fwd: null pointer");
+    GMK_REQUIRE(small_shape_ok(B, cout, H, W, C), "gmk_head_fwd: unsupported shape");
+    return launch_head_contraction<false>(a, w, bias, out, B, cout, H, W, C, dtype, gmk_stream(stream), "gmk_head_fwd");
+}
+
+extern "C" int gmk_stem_dgrad(const void* dy, const float* w, float* dx, int B, int cin, int H, int W, int C, int dtype, void* stream) {
+    GMK_REQUIRE(dy && w && dx, "gmk_stem_dgrad: null pointer");
+    GMK_REQUIRE(small_shape_ok(B, cin, H, W, C), "gmk_stem_dgrad: unsupported shape B=%d cin=%d %dx%d C=%d", B, cin, H, W, C);
+    return launch_head_contraction<true>(dy, w, nullptr, dx, B, cin, H, W, C, dtype, gmk_stream(stream), "gmk_stem_dgrad");
 }

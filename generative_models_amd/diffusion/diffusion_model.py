@@ -58,6 +58,8 @@ def make_plugin(GMBase, AttrDict):
                                        # and sample / evaluate with it; not in the reference, off by default
         DG.nlogp_samples = 0           # > 0: loss() also reports the variational bound (`nlogp`, logged as eval/nlogp, and `bpd`) of the sampling
                                        # net with that many log-SNR draws per image; not in the reference, off by default
+        DG.ode_nlogp_steps = 0         # N > 0: loss() also reports the probability-flow ODE likelihood (`ode_nlogp`, logged as
+                                       # <model>/test/ode_nlogp) of the sampling net on N steps; not in the reference, off by default
         DG.inpaint_eval = 0            # r >= 1: evaluate() also fills in the bottom half of the first 25 test images (RePaint, resample = r) as
                                        # last_eval['inpaint'] / grid 'inpaint'; not in the reference, off by default
 
@@ -86,6 +88,12 @@ def make_plugin(GMBase, AttrDict):
             if self.nlogp_samples > 0 and self.teacher_net is not None:
                 raise ValueError("nlogp_samples > 0 with teacher_path: a distilled student is conditioned on cond_w; its variational bound "
                                  "is not defined")
+            self.ode_nlogp_steps = int(get("ode_nlogp_steps"))
+            if self.ode_nlogp_steps < 0:
+                raise ValueError(f"ode_nlogp_steps = {self.ode_nlogp_steps}: 0 (off) or the number of ODE steps")
+            if self.ode_nlogp_steps > 0 and self.teacher_net is not None:
+                raise ValueError("ode_nlogp_steps > 0 with teacher_path: a distilled student is conditioned on cond_w; its probability-flow "
+                                 "ODE has no density")
             self.inpaint_eval = int(get("inpaint_eval"))
             if self.inpaint_eval < 0:
                 raise ValueError(f"inpaint_eval = {self.inpaint_eval}: 0 (off) or the resample count r >= 1")
@@ -229,6 +237,8 @@ def make_plugin(GMBase, AttrDict):
                 nlogp = self.nlogp(x)["nlogp"].mean()
                 metrics["nlogp"] = nlogp
                 metrics["bpd"] = nlogp / math.log(2.0)
+            if self.ode_nlogp_steps > 0:            # the unconditional ODE likelihood, nats/dim; logged as <model>/test/ode_nlogp
+                metrics["ode_nlogp"] = self.ode_nlogp(x)["nlogp"].mean()
             return metrics["loss"], metrics
 
         # -- likelihood (an extension): the variational bound of `GaussianDiffusion.nll` on the net sample() and evaluate() use
@@ -242,6 +252,32 @@ def make_plugin(GMBase, AttrDict):
             guide = y if y is not None else torch.full((x.shape[0],), -1, dtype=torch.long, device=x.device)
             delta = 0.5 if self.binarize else 1.0 / 255
             return self.diffusion.nll(net=partial(self._sampling_net(), guide=guide), x=x, num_samples=K, seed=seed, delta=delta)
+
+        # -- probability-flow ODE (an extension): encode / decode / exact likelihood of `GaussianDiffusion` on the net sample() uses
+        ODE_NLOGP_STEPS = 512                       # ODE steps of ode_nlogp() when neither the call nor `ode_nlogp_steps` gives a number
+
+        def _ode_guide(self, x, y):
+            return y if y is not None else torch.full((x.shape[0],), -1, dtype=torch.long, device=x.device)
+
+        def encode(self, x, y=None, steps=None):
+            """The latent code of x ([B, C, S, S]) under the probability-flow ODE (DDIM inversion) on `steps` steps (default `timesteps`);
+            y: labels (the conditional ODE), None: unconditional (guide -1).  -> z, x's shape"""
+            return self.diffusion.encode(net=partial(self._sampling_net(), guide=self._ode_guide(x, y)), x=x,
+                                         num_steps=steps or self.diffusion.num_steps)
+
+        def decode(self, z, y=None, steps=None):
+            """The inverse of encode(): the image of the latent code z.  -> x, z's shape"""
+            return self.diffusion.decode(net=partial(self._sampling_net(), guide=self._ode_guide(z, y)), z=z,
+                                         num_steps=steps or self.diffusion.num_steps)
+
+        def ode_nlogp(self, x, y=None, steps=None, seed=0):
+            """Per-image -log p(x) (or -log p(x | y)) of the probability-flow ODE model, in nats per dimension, on `steps` ODE steps (default
+            `ode_nlogp_steps`, else ODE_NLOGP_STEPS); bin half-width 1/2 for binarised data, 1/255 otherwise.  -> the dict of
+            `GaussianDiffusion.ode_nll` (nlogp, prior, divergence: fp32 [B])."""
+            N = steps or self.ode_nlogp_steps or self.ODE_NLOGP_STEPS
+            delta = 0.5 if self.binarize else 1.0 / 255
+            return self.diffusion.ode_nll(net=partial(self._sampling_net(), guide=self._ode_guide(x, y)), x=x, num_steps=N, seed=seed,
+                                          delta=delta)
 
         # -- sampling (:82-87)
         def sample(self, n, y=None):

@@ -10,6 +10,8 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
 * DPM-Solver++(2M) update              gmk_dpm_solver_step (sampler='dpmpp_2m': an extension, no reference call site)
 * variational bound (`nll`)            gmk_q_sample_logsnr, gmk_vlb_term, gmk_vlb_endpoints (an extension, no reference call site)
 * RePaint inpainting (`inpaint`)       gmk_inpaint_merge after the update (an extension, no reference call site)
+* probability-flow ODE (`encode`, `decode`, `ode_nll`)  gmk_pf_ode_step, gmk_rng_rademacher, gmk_dequantize and the network's input gradient
+                                        (SimpleUnet.input_vjp_hip, gmk_stem_dgrad) (an extension, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -107,6 +109,36 @@ def stratified_logsnr(u0, K):
     k = torch.arange(K, device=u0.device, dtype=torch.float64)[:, None] / K
     frac = torch.remainder(u0.double()[None, :] + k, 1.0)
     return (VLB_LOGSNR_MAX - (VLB_LOGSNR_MAX - VLB_LOGSNR_MIN) * frac).float()
+
+
+def ode_logsnr_grid(num_steps):
+    """The probability-flow ODE's time grid, the samplers' own: lambda_i = logsnr_schedule_cosine(i / N) in fp32 for i = 0 ... N (lambda_0 = 20,
+    the data end; lambda_N = -20, the prior end), as Python floats."""
+    N = int(num_steps)
+    return [float(logsnr_schedule_cosine_host(np.float32(np.float32(i) / np.float32(N)))) for i in range(N + 1)]
+
+
+def ode_trapezoid_weights(lam):
+    """w_i of the trapezoid rule over the grid `lam` (decreasing): sum_{i<N} 1/2 (lambda_i - lambda_{i+1}) (d_i + d_{i+1}) = sum_i w_i d_i."""
+    N = len(lam) - 1
+    return [0.5 * ((lam[i - 1] - lam[i] if i > 0 else 0.0) + (lam[i] - lam[i + 1] if i < N else 0.0)) for i in range(N + 1)]
+
+
+def ode_divergence_coefs(logsnr, D, mean_type):
+    """(a, b) with d = a + b r.g the Hutchinson estimate of the divergence of the probability-flow drift f(z, lambda) = 1/2 sigma^2 z -
+    1/2 sigma eps_hat(z, lambda) (dz / d lambda) at one point: d = 1/2 sigma^2 D - 1/2 sigma (c_z D + c_o r.g), g = (d out / d z)^T r,
+    (c_z, c_o) = (sigma, alpha) 'v', (0, 1) 'eps', (1 / sigma, -alpha / sigma) 'x'.  In float64; the constant a is formed without
+    cancellation ('v': 0, 'x': -1/2 alpha^2 D)."""
+    a2 = 1.0 / (1.0 + math.exp(-logsnr))
+    s2 = 1.0 / (1.0 + math.exp(logsnr))
+    alpha, sigma = math.sqrt(a2), math.sqrt(s2)
+    if mean_type == "v":
+        return 0.0, -0.5 * sigma * alpha
+    if mean_type == "eps":
+        return 0.5 * s2 * D, -0.5 * sigma
+    if mean_type == "x":
+        return -0.5 * a2 * D, 0.5 * alpha
+    raise ValueError(f"mean_type {mean_type!r}")
 
 
 class _EvalForward:
@@ -389,6 +421,113 @@ class GaussianDiffusion:
         diff = vals.mean(0)
         se = vals.std(0) / math.sqrt(K) if K > 1 else torch.full_like(diff, float("nan"))
         return {"nlogp": (prior + dec + diff) / D, "se": se / D, "diffusion": diff / D, "prior": prior / D, "decoder": dec / D}
+
+    # ---- probability-flow ODE: encode, decode, exact likelihood (an extension, no reference call site) -----------------------------------
+    # dz / d lambda = f(z, lambda) = 1/2 sigma^2 z - 1/2 sigma eps_hat(z, lambda) (Song et al. 2021, section 4.3 and App. D.2, in lambda = logsnr),
+    # discretised on the samplers' grid lambda_i = lambda(i / N) by DDIM's update without the clip: z_j = alpha_j x_hat_i + sigma_j eps_hat_i
+    # (j = i + 1 encoding, i - 1 decoding), x_hat / eps_hat the UNCLIPPED predictions of the net output at (z_i, lambda_i).
+    def _ode_net(self, net, what):
+        module, guide, kw_cond_w = _unwrap(net)
+        if self.teacher_net is not None or kw_cond_w is not None:
+            raise ValueError(f"{what}: a distilled student is conditioned on cond_w (a guided ODE): its probability-flow ODE has no density")
+        return module, guide
+
+    @staticmethod
+    def _ode_check(what, x, num_steps, module):
+        N = int(num_steps)
+        if N < 1 or N != num_steps:
+            raise ValueError(f"{what}: num_steps = {num_steps}, need an integer >= 1")
+        if x.dim() != 4 or x.shape[0] == 0 or x.shape[1] != getattr(module, "in_channels", x.shape[1]):
+            raise ValueError(f"{what}: x has shape {tuple(x.shape)}, expected [B, {getattr(module, 'in_channels', 'C')}, H, W] with B > 0")
+        return N
+
+    @staticmethod
+    def _ode_times(lam, B, dev):
+        """fp32 [N + 1, Bp] device table of the grid's log-SNRs: row i is the network time of evaluation i (rows start 16-byte aligned)."""
+        Bp = (B + 3) // 4 * 4
+        return torch.tensor(lam, dtype=torch.float32)[:, None].expand(len(lam), Bp).contiguous().to(dev)
+
+    @torch.no_grad()
+    def encode(self, *, net, x, num_steps):
+        """DDIM inversion: the latent code z_N of x under the probability-flow ODE on N = num_steps steps.  z_0 = x, then N updates
+        i = 0 ... N-1 (N forwards).  Deterministic: decode(encode(x)) -> x as N grows.  Runs without dropout.  -> z_N, fp32, x's shape."""
+        module, guide = self._ode_net(net, "encode")
+        N = self._ode_check("encode", x, num_steps, module)
+        z = x.float().clone(memory_format=torch.contiguous_format)
+        B, dev = z.shape[0], z.device
+        lam = ode_logsnr_grid(N)
+        times = self._ode_times(lam, B, dev)
+        with _EvalForward(module):
+            for i in range(N):
+                out = module.forward_hip(z, times[i, :B], guide, None)
+                ops.pf_ode_step(out, z, lam[i], lam[i + 1], mean_type=self.mean_type)
+                ops.throttle()
+        return z
+
+    @torch.no_grad()
+    def decode(self, *, net, z, num_steps):
+        """The inverse of `encode`: from z at lambda_N = -20, N updates i = N ... 1 (N forwards); returns the x_hat of the last evaluation
+        (at lambda_1), as the sampler does at its last step.  Runs without dropout.  -> fp32, z's shape."""
+        module, guide = self._ode_net(net, "decode")
+        N = self._ode_check("decode", z, num_steps, module)
+        z = z.float().clone(memory_format=torch.contiguous_format)
+        B, dev = z.shape[0], z.device
+        lam = ode_logsnr_grid(N)
+        times = self._ode_times(lam, B, dev)
+        x_hat = torch.empty_like(z)
+        with _EvalForward(module):
+            for i in range(N, 0, -1):
+                out = module.forward_hip(z, times[i, :B], guide, None)
+                ops.pf_ode_step(out, z, lam[i], lam[i - 1] if i > 1 else None, mean_type=self.mean_type, x_out=x_hat if i == 1 else None)
+                ops.throttle()
+        return x_hat
+
+    @staticmethod
+    def ode_draw_counters(B, D, num_steps):
+        """Philox counters of `ode_nll`'s draws from PhiloxStream(seed), in draw order: the dequantisation u [B, D] (gmk_rng_uniform's
+        element order), then the probe of each evaluation i = 0 ... N (r = +1 where the uniform at its counters is >= 1/2, else -1).
+        -> [u, r_0, ..., r_N]"""
+        q = (B * D + 3) // 4
+        return [k * q for k in range(int(num_steps) + 2)]
+
+    @torch.no_grad()
+    def ode_nll(self, *, net, x, num_steps, seed=0, delta=1.0 / 255):
+        """Per-image negative log-likelihood of the probability-flow ODE model (the deterministic model the samplers draw from), in nats per
+        dimension, by the instantaneous change of variables with one Rademacher (Hutchinson) probe per evaluation.  x [B, C, H, W], D = C H W:
+          y = x + u, u ~ U(-delta, delta)^D (dequantisation: 1/255 for [-1, 1] data, 1/2 for binarised data)
+          z_0 = y, z_{i+1} = the ODE update, N = num_steps;  d_i = 1/2 sigma_i^2 D - 1/2 sigma_i (c_z D + c_o r_i . g_i), g_i = (d out / d z)^T r_i
+          log p(y) = log N(z_N; 0, I) - sum_{i<N} 1/2 (lambda_i - lambda_{i+1}) (d_i + d_{i+1})
+        N + 1 evaluations (a forward, an input VJP and one gmk_pf_ode_step each).  Draws: a fresh PhiloxStream(seed), u then one probe per
+        evaluation (ode_draw_counters).  Runs without dropout.
+        -> dict of fp32 [B]: nlogp = -log p(y) / D - log(2 delta) (by Jensen an upper bound on -log P(x's bin) / D, up to the estimator's
+        noise), prior = -log N(z_N; 0, I) / D, divergence = the trapezoid sum / D."""
+        module, guide = self._ode_net(net, "ode_nll")
+        N = self._ode_check("ode_nll", x, num_steps, module)
+        delta = float(delta)
+        if not 0.0 < delta <= 0.5:
+            raise ValueError(f"ode_nll: delta = {delta}, the bin half-width must lie in (0, 0.5]")
+        x = ops.aligned(x.float())
+        B, dev = x.shape[0], x.device
+        D = x.numel() // B
+        rng = PhiloxStream(seed)
+        z = ops.dequantize(x, delta, rng.seed, rng._take(B * D))
+        lam = ode_logsnr_grid(N)
+        wts = ode_trapezoid_weights(lam)
+        times = self._ode_times(lam, B, dev)
+        acc = torch.zeros((B,), device=dev)
+        prior = torch.empty((B,), device=dev)
+        with _EvalForward(module):
+            for i in range(N + 1):
+                store = {}
+                out = module.forward_hip(z, times[i, :B], guide, None, ctx=store)
+                r = ops.rng_rademacher(tuple(z.shape), rng.seed, rng._take(B * D), dev)
+                g = module.input_vjp_hip(store, r)
+                a, b = ode_divergence_coefs(lam[i], D, self.mean_type)
+                last = i == N
+                ops.pf_ode_step(out, z, lam[i], None if last else lam[i + 1], mean_type=self.mean_type, r=r, g=g, acc=acc,
+                                div_a=wts[i] * a, div_b=wts[i] * b, prior=prior if last else None)
+                ops.throttle()
+        return {"nlogp": (prior + acc) / D - math.log(2.0 * delta), "prior": prior / D, "divergence": acc / D}
 
     # ---- sampling ----------------------------------------------------------------------------------------
     @torch.no_grad()

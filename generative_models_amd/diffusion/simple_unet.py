@@ -559,8 +559,9 @@ class SimpleUnet(nn.Module):
         out = self._conv([o], self._packs["attn.proj"][0], C, 1, ops.NORMAL, (H, W), bias=P["attn.proj.bias"], residual=residual)
         return out, (a, qkv, Pm, o)
 
-    def _attn_core_bwd(self, saved, dout):
-        """Backward of `_attn_core_fwd` for the gradient `dout` of its output: fills the gradients of attn.proj / attn.qkv, -> gradient of `a`."""
+    def _attn_core_bwd(self, saved, dout, grads=True):
+        """Backward of `_attn_core_fwd` for the gradient `dout` of its output: fills the gradients of attn.proj / attn.qkv (not when
+        grads=False: the data gradient only), -> gradient of `a`."""
         P, G, C = self._pv, self._gv, self.channels
         a, qkv, Pm, o = saved
         B, H, W, _ = a.shape
@@ -568,8 +569,9 @@ class SimpleUnet(nn.Module):
         scale = C ** -0.5
         t = qkv.view(B, N, 3 * C)
         q, k, v = t[:, :, :C], t[:, :, C:2 * C], t[:, :, 2 * C:]
-        ops.colsum(ops.chansum(dout), G["attn.proj.bias"], defer=True)
-        self._wgrad(dout, [o], 1, ops.NORMAL, G["attn.proj.weight"])
+        if grads:
+            ops.colsum(ops.chansum(dout), G["attn.proj.bias"], defer=True)
+            self._wgrad(dout, [o], 1, ops.NORMAL, G["attn.proj.weight"])
         do = self._conv([dout], self._packs["attn.proj"][1], C, 1, ops.NORMAL, (H, W)).view(B, N, C)
         # o = P v,  P = softmax(scale * q k^T)
         if Pm is None:          # fused backward: P recomputed block by block in registers (gmk_attention_bwd), no [B, N, N] tensor anywhere
@@ -583,8 +585,9 @@ class SimpleUnet(nn.Module):
             ops.bgemm_nt(dS, ops.transpose_last2(k), out=d3[:, :, :C])                               # dq = dS k
             ops.bgemm_nt(ops.transpose_last2(dS), ops.transpose_last2(q), out=d3[:, :, C:2 * C])     # dk = dS^T q
         # (q, k, v) = conv1x1(a)
-        G["attn.qkv.bias"].copy_(dqkv.float().sum((0, 1, 2)))        # 3C-channel bias gradient: tiny, off the hot path
-        self._wgrad(dqkv, [a], 1, ops.NORMAL, G["attn.qkv.weight"])
+        if grads:
+            G["attn.qkv.bias"].copy_(dqkv.float().sum((0, 1, 2)))        # 3C-channel bias gradient: tiny, off the hot path
+            self._wgrad(dqkv, [a], 1, ops.NORMAL, G["attn.qkv.weight"])
         return self._conv([dqkv], self._packs["attn.qkv"][1], C, 1, ops.NORMAL, (H, W))
 
     def _attn_fwd(self, x, ctx):
@@ -597,15 +600,16 @@ class SimpleUnet(nn.Module):
             ctx["attn"] = (x, mean, rstd, saved)
         return ops.cast16(out, self.act_dtype) if self.act_dtype != T else out
 
-    def _attn_bwd(self, ctx, dout):
-        """-> (dx, per-sample channel sums of dx)."""
+    def _attn_bwd(self, ctx, dout, grads=True):
+        """-> (dx, per-sample channel sums of dx (None when grads=False: the data gradient only))."""
         P, G, C = self._pv, self._gv, self.channels
         x, mean, rstd, saved = ctx.pop("attn")
         B = x.shape[0]
-        da = self._attn_core_bwd(saved, dout)            # out = x + core(a)
-        s = torch.empty((B, C), device=x.device, dtype=torch.float32)
+        da = self._attn_core_bwd(saved, dout, grads)     # out = x + core(a)
+        s = torch.empty((B, C), device=x.device, dtype=torch.float32) if grads else None
         dx, dgp, dbp = ops.gn_silu_bwd(da, x, P["attn.norm.weight"], P["attn.norm.bias"], mean, rstd, dadd1=dout, dxsum=s)
-        ops.colsum(dgp, G["attn.norm.weight"], defer=True); ops.colsum(dbp, G["attn.norm.bias"], defer=True)
+        if grads:
+            ops.colsum(dgp, G["attn.norm.weight"], defer=True); ops.colsum(dbp, G["attn.norm.bias"], defer=True)
         return dx, s
 
     def _wgrad(self, dy, srcs, ksize, mode, dw):
@@ -646,30 +650,35 @@ class SimpleUnet(nn.Module):
         if self._side is not None:
             torch.cuda.current_stream().wait_stream(self._side)
 
-    def _res_bwd(self, name, ctx, dout, dout_sum, demb_all, blk, extra_add=None):
+    def _res_bwd(self, name, ctx, dout, dout_sum, demb_all, blk, extra_add=None, grads=True):
         """dout: gradient of the block output (NHWC); dout_sum: its per-sample channel sums [B, C].
         extra_add: per-source optional extra gradient tensors added into the returned source gradients.
+        grads=False: the data gradient only (input_vjp_hip) - no weight, bias or embedding gradient, no channel sums (dout_sum / demb_all
+        unused, None returned for dsrc_sum).
         Returns [(dsrc, dsrc_sum)] per source."""
         P, G, C = self._pv, self._gv, self.channels
         srcs, a, stats1, h, a2, (mean2, rstd2) = ctx.pop(name)
         B, H, W, _ = dout.shape
         two = len(srcs) == 2
         # conv2 (out_layers.3)
-        ops.colsum(dout_sum, G[f"{name}.out_layers.3.bias"], defer=True)
-        self._wgrad(dout, [a2], 3, ops.NORMAL, G[f"{name}.out_layers.3.weight"])
+        if grads:
+            ops.colsum(dout_sum, G[f"{name}.out_layers.3.bias"], defer=True)
+            self._wgrad(dout, [a2], 3, ops.NORMAL, G[f"{name}.out_layers.3.weight"])
         _, wd2 = self._packs[f"{name}.out_layers.3"]
         da2 = self._conv([dout], wd2, C, 3, ops.NORMAL, (H, W))
         dh, dgp, dbp = ops.gn_silu_bwd(da2, h, P[f"{name}.out_layers.0.weight"], P[f"{name}.out_layers.0.bias"], mean2,
-                                       rstd2, dxsum=demb_all[:, blk * C:(blk + 1) * C], dropout=ctx.pop(name + ".dropout", None),
-                                       xadd=ctx["emb_all"][:, blk * C:(blk + 1) * C])
-        ops.colsum(dgp, G[f"{name}.out_layers.0.weight"], defer=True); ops.colsum(dbp, G[f"{name}.out_layers.0.bias"], defer=True)
-        # conv1 (in_layers.2): bias gradient = column sum of the embedding gradient slice (both are sum_hw dh)
-        ops.colsum(demb_all[:, blk * C:(blk + 1) * C], G[f"{name}.in_layers.2.bias"], defer=True)
-        self._wgrad(dh, a, 3, ops.NORMAL, G[f"{name}.in_layers.2.weight"])
+                                       rstd2, dxsum=demb_all[:, blk * C:(blk + 1) * C] if grads else None,
+                                       dropout=ctx.pop(name + ".dropout", None), xadd=ctx["emb_all"][:, blk * C:(blk + 1) * C])
+        if grads:
+            ops.colsum(dgp, G[f"{name}.out_layers.0.weight"], defer=True); ops.colsum(dbp, G[f"{name}.out_layers.0.bias"], defer=True)
+            # conv1 (in_layers.2): bias gradient = column sum of the embedding gradient slice (both are sum_hw dh)
+            ops.colsum(demb_all[:, blk * C:(blk + 1) * C], G[f"{name}.in_layers.2.bias"], defer=True)
+            self._wgrad(dh, a, 3, ops.NORMAL, G[f"{name}.in_layers.2.weight"])
         _, wd1 = self._packs[f"{name}.in_layers.2"]
         if two:
-            ops.colsum(dout_sum, G[f"{name}.skip_connection.bias"], defer=True)
-            self._wgrad(dout, srcs, 1, ops.NORMAL, G[f"{name}.skip_connection.weight"])
+            if grads:
+                ops.colsum(dout_sum, G[f"{name}.skip_connection.bias"], defer=True)
+                self._wgrad(dout, srcs, 1, ops.NORMAL, G[f"{name}.skip_connection.weight"])
             _, wds = self._packs[f"{name}.skip_connection"]
         outs = []
         gw, gb = G[f"{name}.in_layers.0.weight"], G[f"{name}.in_layers.0.bias"]
@@ -683,11 +692,12 @@ class SimpleUnet(nn.Module):
             da = self._conv([dh], wd1, len(srcs) * C, 3, ops.NORMAL, (H, W), n0=i * C)
             dskip = dskips[i]
             add2 = extra_add[i] if extra_add is not None else None
-            ssum = torch.empty((B, C), device=dout.device, dtype=torch.float32)
+            ssum = torch.empty((B, C), device=dout.device, dtype=torch.float32) if grads else None
             ds, dgp, dbp = ops.gn_silu_bwd(da, s, P[f"{name}.in_layers.0.weight"][i * C:(i + 1) * C],
                                            P[f"{name}.in_layers.0.bias"][i * C:(i + 1) * C], stats1[i][0], stats1[i][1],
                                            dadd1=dskip, dadd2=add2, dxsum=ssum)
-            ops.colsum(dgp, gw[i * C:(i + 1) * C], defer=True); ops.colsum(dbp, gb[i * C:(i + 1) * C], defer=True)
+            if grads:
+                ops.colsum(dgp, gw[i * C:(i + 1) * C], defer=True); ops.colsum(dbp, gb[i * C:(i + 1) * C], defer=True)
             outs.append((ds, ssum))
         return outs
 
@@ -771,8 +781,9 @@ class SimpleUnet(nn.Module):
         assert all(srt[i][1] == srt[i + 1][0] for i in range(3)), "gradient buckets must tile the arena"
         return buckets
 
-    def backward_hip(self, ctx, dout, on_grads_ready=None, join_side_before_ready=True):
-        """dout: NCHW fp32 gradient of the network output.  Fills `flat_grads` (overwrites every touched slice).
+    def backward_hip(self, ctx, dout, on_grads_ready=None, join_side_before_ready=True, want_dx=False):
+        """dout: NCHW fp32 gradient of the network output.  Fills `flat_grads` (overwrites every touched slice); want_dx: also returns the
+        gradient of the input x (NCHW fp32, the stem's data gradient gmk_stem_dgrad), else None.
         on_grads_ready(k): called as soon as every kernel that writes bucket k of grad_buckets() has been ENQUEUED (overlapped gradient
         all-reduce).  A bucket is final only when the side stream's weight gradients are: with join_side_before_ready the current stream
         joins the side stream in front of every callback (a callback may then read the bucket in current-stream order); a consumer
@@ -784,7 +795,7 @@ class SimpleUnet(nn.Module):
             self._cu_part = (full, min(ops.WGRAD_CUS, full - 8))
             ops.set_cu_limit(full - self._cu_part[1])
             try:
-                return self.backward_hip(ctx, dout, on_grads_ready, join_side_before_ready)
+                return self.backward_hip(ctx, dout, on_grads_ready, join_side_before_ready, want_dx)
             finally:
                 ops.set_cu_limit(full)
                 self._cu_part = None
@@ -852,20 +863,59 @@ class SimpleUnet(nn.Module):
         ops.flush_colsums()
         ready(3)
         self._join_side()          # the caller (optimiser step, next forward) continues on the current stream
+        return ops.stem_dgrad(dt0, P["down.seq.0.conv.weight"]) if want_dx else None
+
+    def input_vjp_hip(self, ctx, r):
+        """The input gradient alone: (d out / d x)^T r for the forward that filled `ctx` (forward_hip(..., ctx=)), r NCHW fp32 of the output's
+        shape -> dx NCHW fp32 of the input's shape.  backward_hip's data-gradient chain from the head down to the stem, then the stem's data
+        gradient (gmk_stem_dgrad): no weight, bias or embedding gradient, no channel sums, no side stream, no CU partition - `flat_grads` is
+        not touched.  Consumes `ctx` like backward_hip.  (An extension: the reference never differentiates with respect to its input.)"""
+        P, C, T = self._pv, self.channels, self.compute_dtype
+        B, H, W = ctx["dims"]
+        H2, W2 = H // 2, W // 2
+        x, t2, t5, u0r, u3r, u6, ao, mo, ro = ctx["net"]
+        if tuple(r.shape) != tuple(x.shape):
+            raise ValueError(f"input_vjp_hip: r has shape {tuple(r.shape)}, the network output {tuple(x.shape)}")
+        r = ops.aligned(r.float())
+        dao = ops.head_dgrad(r, P["out.2.weight"], T)
+        du6, _, _ = ops.gn_silu_bwd(dao, u6, P["out.0.weight"], P["out.0.bias"], mo, ro)
+        res = lambda name, d, blk, extra=None: self._res_bwd(name, ctx, d, None, None, blk, extra_add=extra, grads=False)
+        (du5, _), (dt0a, _) = res("up.seq.6", du6, 11)
+        (du4, _), (dt1a, _) = res("up.seq.5", du5, 10)
+        (du3, _), (dt2a, _) = res("up.seq.4", du4, 9)
+        du3r = self._upsample_dgrad("up.seq.3.1.conv", du3)
+        (du2, _), (dt3a, _) = res("up.seq.3.0", du3r, 8)
+        (du1, _), (dt4a, _) = res("up.seq.2", du2, 7)
+        (du0, _), (dt5a, _) = res("up.seq.1", du1, 6)
+        du0r = self._upsample_dgrad("up.seq.0.1.conv", du0)
+        (dt7, _), (dt6a, _) = res("up.seq.0.0", du0r, 5)
+        if self.attention:
+            dt7, _ = self._attn_bwd(ctx, dt7, grads=False)
+        ((dt6, _),) = res("turn", dt7, 4, [dt6a])
+        dt5 = self._conv([dt6], self._packs["down.seq.6.conv"][1], C, 3, ops.TRANSPOSED2, (H2, W2), residual=dt5a)
+        ((dt4, _),) = res("down.seq.5", dt5, 3, [dt4a])
+        ((dt3, _),) = res("down.seq.4", dt4, 2, [dt3a])
+        dt2 = self._conv([dt3], self._packs["down.seq.3.conv"][1], C, 3, ops.TRANSPOSED2, (H, W), residual=dt2a)
+        ((dt1, _),) = res("down.seq.2", dt2, 1, [dt1a])
+        ((dt0, _),) = res("down.seq.1", dt1, 0, [dt0a])
+        return ops.stem_dgrad(dt0, P["down.seq.0.conv.weight"])
 
     def zero_grad_arena(self):
         self.flat_grads.zero_()
 
     def forward(self, x, timesteps, guide=None, cond_w=None):
-        """Reference signature (simple_unet.py:44).  Differentiable through SimpleUnetFunction when grad is enabled."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        """Reference signature (simple_unet.py:44).  Differentiable through SimpleUnetFunction when grad is enabled and the parameters or
+        x require it (x: torch.autograd.grad(net(x, ...).sum(), x) works with frozen parameters too)."""
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             return SimpleUnetFunction.apply(self, x, timesteps, guide, cond_w, *self.parameters())
         return self.forward_hip(x, timesteps, guide, cond_w)
 
 
 class SimpleUnetFunction(torch.autograd.Function):
     """torch.autograd bridge: forward = forward_hip, backward = backward_hip.  Parameter gradients are ACCUMULATED
-    into `p.grad` (the arena views) like autograd would; there is no gradient w.r.t. x (the reference never needs it)."""
+    into `p.grad` (the arena views) like autograd would.  The gradient w.r.t. x (an extension: the reference never needs it) is returned
+    when x requires grad; with no parameter requiring grad it comes from input_vjp_hip, which leaves the arena alone.  No gradient w.r.t.
+    the time, the labels or cond_w."""
 
     @staticmethod
     def forward(ctx, net, x, timesteps, guide, cond_w, *params):
@@ -877,8 +927,13 @@ class SimpleUnetFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         net = ctx.net
-        prev = net.flat_grads.clone()
-        net.backward_hip(ctx.store, dout)
-        net.flat_grads.add_(prev)
-        # gradients were written in place into p.grad (views of the arena): return None for every input
-        return (None,) * (5 + len(list(net.parameters())))
+        want_dx = ctx.needs_input_grad[1]
+        dx = None
+        if any(ctx.needs_input_grad[5:]):
+            prev = net.flat_grads.clone()
+            dx = net.backward_hip(ctx.store, dout, want_dx=want_dx)
+            net.flat_grads.add_(prev)
+        elif want_dx:
+            dx = net.input_vjp_hip(ctx.store, dout)
+        # parameter gradients were written in place into p.grad (views of the arena): None for every parameter
+        return (None, dx) + (None,) * (3 + len(list(net.parameters())))

@@ -631,6 +631,23 @@ def head_wgrad(dout, a, dwb):
     return colsum(part, dwb)
 
 
+def stem_dgrad(dy, w):
+    """The network's input gradient through the stem: dy NHWC [B, H, W, C] (compute dtype) -> dx NCHW fp32 [B, cin, H, W], the transposed 3x3
+    convolution with the stem weight w [C, cin, 3, 3] (gmk_stem_dgrad; an extension)."""
+    if dy.dim() != 4 or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[0] != dy.shape[3]:
+        raise ValueError(f"stem_dgrad: bad shapes dy {tuple(dy.shape)} and w {tuple(w.shape)}: expected [B, H, W, C] and [C, cin, 3, 3]")
+    if dy.dtype not in _DT:
+        raise ValueError(f"stem_dgrad: dy dtype {dy.dtype}")
+    _f32(w, "w"); _chk(dy, name="dy")
+    B, H, W, C = dy.shape
+    cin = w.shape[1]
+    dx = torch.empty((B, cin, H, W), device=dy.device, dtype=torch.float32)
+    name = "stem_dgrad_mfma_kernel" if dy.dtype in _HALF and C == 128 and cin <= 3 else "stem_dgrad_kernel"
+    with _Timed(name, 2.0 * B * H * W * C * cin * 9, _nbytes(dy, dx), fixed=True):
+        check(lib.gmk_stem_dgrad(_p(dy), _p(w), _p(dx), B, cin, H, W, C, _DT[dy.dtype], _s()), "stem_dgrad")
+    return dx
+
+
 # ---- embedding path --------------------------------------------------------------------------------------
 def timestep_freqs(max_period, device):
     """simple_unet.py:215-219 evaluated with the same torch fp32 ops (host), as a 32-entry table."""
@@ -898,6 +915,56 @@ def vlb_endpoints(x, eps0, delta):
     dec = torch.empty_like(prior)
     check(lib.gmk_vlb_endpoints(_p(x), _p(eps0), delta, _p(prior), _p(dec), B, n, _s()), "vlb_endpoints")
     return prior, dec
+
+
+# ---- probability-flow ODE (an extension; gaussian_diffusion.GaussianDiffusion.encode / decode / ode_nll) ----------------------------------
+def rng_rademacher(shape, seed, offset, device):
+    """+1 where rng_uniform(shape, seed, offset) >= 1/2, else -1 (Hutchinson probes)."""
+    out = torch.empty(shape, device=device, dtype=torch.float32)
+    with _Timed("rng_rademacher_kernel", 0.0, _nbytes(out), fixed=True):
+        check(lib.gmk_rng_rademacher(_p(out), out.numel(), int(seed), int(offset), _s()), "rng_rademacher")
+    return out
+
+
+def dequantize(x, delta, seed, offset):
+    """y = x + delta (2 u - 1), u = rng_uniform(x.shape, seed, offset) (drawn in the kernel).  -> y"""
+    delta = float(delta)
+    if not 0.0 < delta <= 0.5:
+        raise ValueError(f"delta = {delta}: the bin half-width must lie in (0, 0.5]")
+    if x.dtype != torch.float32:
+        raise ValueError(f"x: dtype {x.dtype}, expected torch.float32")
+    if x.numel() == 0:
+        raise ValueError("x: empty")
+    _f32(x, "x")
+    y = torch.empty_like(x)
+    with _Timed("dequantize_kernel", 0.0, _nbytes(x, y), fixed=True):
+        check(lib.gmk_dequantize(_p(x), _p(y), delta, x.numel(), int(seed), int(offset), _s()), "dequantize")
+    return y
+
+
+def pf_ode_step(out, z, logsnr_i, logsnr_j=None, mean_type="v", r=None, g=None, acc=None, div_a=0.0, div_b=0.0, prior=None, x_out=None):
+    """One probability-flow ODE step after the network evaluation `out` at (z, logsnr_i) (gmk_pf_ode_step), fp32 [B, ...] tensors:
+    logsnr_j given: z = alpha_j x_hat + sigma_j eps_hat in place (x_hat, eps_hat unclipped); x_out: receives x_hat;
+    acc (fp32 [B]): acc += div_a + div_b sum r g per image (needs the probe r and its input VJP g); prior (fp32 [B], only without an
+    update): -log N(z; 0, I) per image.  -> z"""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    if acc is not None and (r is None or g is None):
+        raise ValueError("pf_ode_step: the divergence needs the probe r and the VJP g")
+    if prior is not None and logsnr_j is not None:
+        raise ValueError("pf_ode_step: the prior is taken at the last point, which has no update")
+    coefs = (logsnr_i, 0.0 if logsnr_j is None else logsnr_j, div_a, div_b)
+    if not all(math.isfinite(float(c)) for c in coefs):
+        raise ValueError(f"pf_ode_step: non-finite time or coefficient {coefs}")
+    tensors = [(out, "out"), (z, "z")] + [(t, nm) for t, nm in ((r, "r"), (g, "g"), (x_out, "x_out")) if t is not None]
+    vectors = [(t, nm) for t, nm in ((acc, "acc"), (prior, "prior")) if t is not None]
+    B, n = _vlb_check(tensors, vectors=vectors)
+    prior_c = 0.5 * n * math.log(2.0 * math.pi)
+    with _Timed("pf_ode_step_kernel", 0.0, _nbytes(out, z, r, g, x_out) + (_nbytes(z) if logsnr_j is not None else 0.0), fixed=True):
+        check(lib.gmk_pf_ode_step(_p(out), _p(z), _p(r), _p(g), _p(acc), _p(prior), _p(x_out), float(logsnr_i),
+                                  float(0.0 if logsnr_j is None else logsnr_j), int(logsnr_j is not None), float(div_a), float(div_b),
+                                  float(prior_c), MEAN_TYPES[mean_type], B, n, _s()), "pf_ode_step")
+    return z
 
 
 def logsnr_schedule(B, device, u=None, i_times=None, num_steps=1, shift=0.0, want_u=False):

@@ -225,6 +225,10 @@ int gmk_head_dgrad(const float* dout, const float* w, void* da, int B, int cout,
 int gmk_head_wgrad_blocks(int64_t n_pixels);
 int gmk_head_wgrad(const float* dout, const void* a, float* dw_part, int B, int cout, int H, int W, int C, int dtype,
                    void* stream);
+/* stem data gradient (the network's input gradient; an extension, the reference never forms it): dy NHWC [B][H][W][C] (dtype: the
+ * compute type, bf16 or fp32; fp16 accepted) -> dx NCHW fp32 [B][cin][H][W] (cin <= 4), the transposed 3x3 / stride-1 / pad-1 convolution
+ * with the stem weight w [C][cin][3][3]: dx[b,s,p] = sum_{c,t} dy[b, p - off(t), c] w[c][s][t].  No bias. */
+int gmk_stem_dgrad(const void* dy, const float* w, float* dx, int B, int cin, int H, int W, int C, int dtype, void* stream);
 
 /* ---- embedding path (simple_unet.py:20-34,45-64,166,205-224), fp32 -------------------------------------- */
 /* out[b][0:32] = cos(t[b]*f_k), out[b][32:64] = sin(t[b]*f_k); freqs: fp32 [32] table computed by the host
@@ -318,6 +322,21 @@ int gmk_q_sample_logsnr(const float* x, const float* eps, const float* logsnr, f
 int gmk_vlb_term(const float* out, const float* z, const float* eps, const float* logsnr, const float* weight, float* acc, int mean_type,
                  int B, int64_t n, void* stream);
 int gmk_vlb_endpoints(const float* x, const float* eps0, float delta, float* out_prior, float* out_dec, int B, int64_t n, void* stream);
+/* probability-flow ODE (Song et al. 2021, section 4.3 / App. D.2) in lambda = logsnr; an extension, no reference call site.
+ *   gmk_rng_rademacher: out[i] = +1 where u >= 1/2, -1 elsewhere, u = element i of gmk_rng_uniform(seed, offset) (Hutchinson probes).
+ *   gmk_dequantize: y = x + delta (2 u - 1), u = element i of gmk_rng_uniform(seed, offset) (drawn in the kernel, never stored).
+ *   gmk_pf_ode_step: one network evaluation `out` at (z, logsnr_i), B x n fp32.  eps_hat = the UNCLIPPED noise prediction of gmk_vlb_term,
+ *     x_hat = 'v' alpha z - sigma out, 'eps' (z - sigma out) / alpha, 'x' out (= (z - sigma eps_hat) / alpha).
+ *     update != 0: z = alpha_j x_hat + sigma_j eps_hat in place (alpha_j, sigma_j at logsnr_j: DDIM's update without the clip).
+ *     x_out (optional): receives x_hat.
+ *     acc (optional, B floats): acc[b] += div_a + div_b sum_i r g, the trapezoid-weighted divergence of the ODE's drift (host coefficients:
+ *       w_i (1/2 sigma_i^2 n - 1/2 sigma_i c_z n) and -w_i 1/2 sigma_i c_o); needs r (the probe) and g (the input VJP of `out` along r).
+ *     prior (optional, B floats, never with update): prior[b] = 1/2 sum_i z^2 + prior_c, i.e. -log N(z; 0, I) with prior_c = n/2 log(2 pi).
+ *   With acc or prior the grid is one workgroup per image (a fixed-order reduction: repeated calls give the same bits).  Any n. */
+int gmk_rng_rademacher(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
+int gmk_dequantize(const float* x, float* y, float delta, int64_t n, uint64_t seed, uint64_t offset, void* stream);
+int gmk_pf_ode_step(const float* out, float* z, const float* r, const float* g, float* acc, float* prior, float* x_out, float logsnr_i,
+                    float logsnr_j, int update, float div_a, float div_b, float prior_c, int mean_type, int B, int64_t n, void* stream);
 
 /* ---- self-attention core (north_star "optional self-attention block", BASELINE config 5) -------------
  * The reference SimpleUnet has no attention block: these have NO reference call site (parity unpinned; their definition is the
