@@ -5,7 +5,8 @@
 // torch.optim.Adam as diffusion_model.py:56 constructs it.  gmk_adam_ema_step's weight average has no reference call site (the
 // reference keeps no EMA): an extension, defined by torch.lerp.  gmk_dpm_solver_step (DPM-Solver++(2M)) is an extension too, and so are
 // the variational-bound kernels gmk_q_sample_logsnr / gmk_vlb_term / gmk_vlb_endpoints (Kingma et al. 2021, continuous-time VDM bound) and
-// the inpainting merge gmk_inpaint_merge (RePaint, Lugmayr et al. 2022).
+// the inpainting merge gmk_inpaint_merge (RePaint, Lugmayr et al. 2022).  gmk_grad_norm / gmk_adam_step_ctl (global-norm clipping by
+// torch.nn.utils.clip_grad_norm_'s rule, and the non-finite guard GradScaler.step gives the reference at diffusion_model.py:71) are extensions.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -490,6 +491,91 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, co
     }
 }
 
+// ---- steered optimiser step: global gradient norm, clipping and the non-finite guard without a host sync; an extension (the reference's
+// guard is GradScaler.step's, diffusion_model.py:71; it has no clipping).
+// Stage 1: workgroup b owns float4s [b * kNormQuads, (b + 1) * kNormQuads) of g and writes their sum of squares to part[b]: kNormLoads 16-byte
+// loads per thread, all issued before the first is used.  The grid follows from n alone (never from the CU limit) and every sum has a fixed
+// order, so the bits are the same on every call and on every rank.  Longest chain of fp32 additions behind part[b]: kNormLoads per component
+// accumulator, 2 to join the four, 1 for the n & 3 tail (workgroup 0), 6 + 2 in block_sum.
+constexpr int kNormLoads = 8;
+constexpr int kNormQuads = 256 * kNormLoads;
+
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, float* __restrict__ part, int64_t n) {
+    __shared__ float red[4];
+    const int64_t nq = n / 4;
+    const int64_t q0 = (int64_t)blockIdx.x * kNormQuads + threadIdx.x;
+    float gv[kNormLoads][4];
+#pragma unroll
+    for (int k = 0; k < kNormLoads; ++k) {
+        const int64_t q = q0 + k * 256;
+        if (q < nq) load4(g + q * 4, gv[k]);
+        else gv[k][0] = gv[k][1] = gv[k][2] = gv[k][3] = 0.f;
+    }
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < kNormLoads; ++k)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = fmaf(gv[k][c], gv[k][c], acc[c]);
+    float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const float t = g[nq * 4 + threadIdx.x];
+        s = fmaf(t, t, s);
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// Stage 2, one workgroup: thread t adds part[t], part[t + 256], ... in that order (ceil(nparts / 256) additions), then block_sum (6 + 2).
+// state: [0] total_norm = grad_scale sqrt(sum), [1] coef = min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; 1 when
+// max_norm <= 0), [2] apply = 1 if total_norm is finite (a NaN or inf gradient, or a sum of squares beyond fp32, gives 0), [3] skipped, the
+// running count of apply == 0.
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* __restrict__ part, int nparts, float grad_scale, float max_norm,
+                                                             float* __restrict__ state) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) {
+        const float total = grad_scale * sqrtf(s);
+        const bool finite = isfinite(total);
+        state[0] = total;
+        state[1] = max_norm > 0.0f ? fminf(1.0f, max_norm / (total + 1e-6f)) : 1.0f;
+        state[2] = finite ? 1.0f : 0.0f;
+        state[3] = state[3] + (finite ? 0.0f : 1.0f);
+    }
+}
+
+// adam_kernel / adam_ema_kernel steered by gmk_grad_norm's state: gg = (g grad_scale) coef (adam_elem then multiplies by 1: exact), and no
+// memory is touched when apply == 0.  Both values are uniform across the launch.
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_ctl_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, float* __restrict__ ema, const float* __restrict__ state,
+                                                      int64_t n, float step_size, float beta1, float beta2, float eps, float inv_bc2_sqrt,
+                                                      float grad_scale, float ema_w) {
+    if (state[2] == 0.0f) return;
+    const float coef = state[1];
+    const int64_t nq = n / 4;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+        float pv[4], gv[4], mv[4], vv[4], ev[4];
+        load4(p + q * 4, pv); load4(g + q * 4, gv); load4(m + q * 4, mv); load4(v + q * 4, vv);
+        if (EMA) load4(ema + q * 4, ev);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            adam_elem(pv[k], (gv[k] * grad_scale) * coef, mv[k], vv[k], step_size, beta1, beta2, eps, inv_bc2_sqrt, 1.0f);
+            if (EMA) ev[k] = lerp_to(ev[k], pv[k], ema_w);
+        }
+        store4(p + q * 4, pv); store4(m + q * 4, mv); store4(v + q * 4, vv);
+        if (EMA) store4(ema + q * 4, ev);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t i = nq * 4 + threadIdx.x;
+        float pp = p[i], mm = m[i], vv = v[i];
+        adam_elem(pp, (g[i] * grad_scale) * coef, mm, vv, step_size, beta1, beta2, eps, inv_bc2_sqrt, 1.0f);
+        m[i] = mm; v[i] = vv; p[i] = pp;
+        if (EMA) ema[i] = lerp_to(ema[i], pp, ema_w);
+    }
+}
+
 // ---- probability-flow ODE (Song et al. 2021, section 4.3 and App. D.2, in lambda = logsnr); an extension, no reference call site.
 // Probes and dequantisation noise use gmk_rng_uniform's counters: element i is component i % 4 of Philox counter offset + i / 4, so the
 // host can replay them with a plain uniform draw.
@@ -820,6 +906,43 @@ extern "C" int gmk_adam_ema_step(float* p, const float* g, float* m, float* v, f
     adam_ema_kernel<<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, ema, n, step_size, beta1, beta2, eps,
                                                                             inv_bc2_sqrt, grad_scale, ema_w);
     return gmk_check_launch("gmk_adam_ema_step");
+}
+
+static int64_t grad_norm_parts(int64_t n) {
+    const int64_t nq = n / 4;
+    return nq <= kNormQuads ? 1 : (nq + kNormQuads - 1) / kNormQuads;
+}
+
+extern "C" int64_t gmk_grad_norm_workspace_bytes(int64_t n) { return n > 0 ? grad_norm_parts(n) * (int64_t)sizeof(float) : 0; }
+
+extern "C" int gmk_grad_norm(const float* g, int64_t n, float grad_scale, float max_norm, float* workspace, int64_t workspace_bytes,
+                             float* state, void* stream) {
+    GMK_REQUIRE(g && workspace && state && n > 0, "gmk_grad_norm: bad arguments");
+    GMK_REQUIRE(isfinite(grad_scale) && grad_scale > 0.0f, "gmk_grad_norm: grad_scale = %g must be finite and positive", (double)grad_scale);
+    GMK_REQUIRE(!isnan(max_norm), "gmk_grad_norm: max_norm is NaN");
+    const int64_t parts = grad_norm_parts(n);
+    GMK_REQUIRE(parts < (int64_t)1 << 31, "gmk_grad_norm: n = %lld too large", (long long)n);
+    GMK_REQUIRE(workspace_bytes >= parts * (int64_t)sizeof(float), "gmk_grad_norm: workspace of %lld bytes, %lld needed",
+                (long long)workspace_bytes, (long long)(parts * (int64_t)sizeof(float)));
+    grad_norm_partial_kernel<<<(int)parts, 256, 0, gmk_stream(stream)>>>(g, workspace, n);
+    grad_norm_final_kernel<<<1, 256, 0, gmk_stream(stream)>>>(workspace, (int)parts, grad_scale, max_norm, state);
+    return gmk_check_launch("gmk_grad_norm");
+}
+
+extern "C" int gmk_adam_step_ctl(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
+                                 float eps, int step, float grad_scale, float ema_w, const float* state, void* stream) {
+    GMK_REQUIRE(p && g && m && v && n > 0 && step >= 1, "gmk_adam_step_ctl: bad arguments");
+    GMK_REQUIRE(state, "gmk_adam_step_ctl: state is null");
+    GMK_REQUIRE(!ema || (ema_w >= 0.0f && ema_w <= 1.0f), "gmk_adam_step_ctl: ema_w = %g outside [0, 1]", (double)ema_w);
+    float step_size, inv_bc2_sqrt;
+    adam_scalars(lr, beta1, beta2, step, &step_size, &inv_bc2_sqrt);
+    if (ema)
+        adam_ctl_kernel<true><<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, ema, state, n, step_size, beta1, beta2, eps,
+                                                                                      inv_bc2_sqrt, grad_scale, ema_w);
+    else
+        adam_ctl_kernel<false><<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, nullptr, state, n, step_size, beta1, beta2,
+                                                                                       eps, inv_bc2_sqrt, grad_scale, 0.0f);
+    return gmk_check_launch("gmk_adam_step_ctl");
 }
 
 extern "C" int gmk_rng_rademacher(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {

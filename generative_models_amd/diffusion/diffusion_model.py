@@ -45,7 +45,7 @@ def make_plugin(GMBase, AttrDict):
         DG.cf_drop_prob = 0.1
         DG.teacher_path = Path(".")
         DG.teacher_mode = "step1"
-        DG.lr_scheduler = "none"
+        DG.lr_scheduler = "none"         # 'none' (reference: nothing reads it there) | 'cosine' (extension: FusedAdam.lr_at)
         # additions of the HIP path
         DG.compute_dtype = "bf16"      # 'bf16' (16-bit MFMA mode: bf16 gradients) or 'fp32' (exact-fp32 MFMA, 1e-3 parity mode)
         DG.act_dtype = os.environ.get("GMK_ACT_DTYPE", "fp16")      # 16-bit mode only: storage of forward activations / forward weight packs, 'fp16' (the precision of the
@@ -62,6 +62,12 @@ def make_plugin(GMBase, AttrDict):
                                        # <model>/test/ode_nlogp) of the sampling net on N steps; not in the reference, off by default
         DG.inpaint_eval = 0            # r >= 1: evaluate() also fills in the bottom half of the first 25 test images (RePaint, resample = r) as
                                        # last_eval['inpaint'] / grid 'inpaint'; not in the reference, off by default
+        DG.grad_clip = 0.0             # c > 0: clip the global gradient norm to c inside the optimiser step (torch.nn.utils.clip_grad_norm_'s rule) and
+                                       # report train/grad_norm, train/skipped_steps; implies skip_nonfinite; not in the reference, off by default
+        DG.skip_nonfinite = 0          # 1: a step whose gradients hold an inf or a NaN changes nothing (the guard of the reference's GradScaler.step)
+        DG.lr_warmup = 0               # W > 0: lr times min(1, (t + 1) / W) after t steps, under either lr_scheduler
+        DG.lr_decay_steps = 0          # 'cosine': steps from lr down to lr_min_ratio * lr, counted from the end of the warm-up
+        DG.lr_min_ratio = 0.1
 
         def __init__(self, G):
             super().__init__(G)
@@ -114,7 +120,23 @@ def make_plugin(GMBase, AttrDict):
                 for param in self.ema_net.parameters():
                     param.requires_grad = False
                 self.ema_net.eval()
-            self.optimizer = FusedAdam(self.net, lr=G.lr if "lr" in G else 3e-4, ema_net=self.ema_net, ema_decay=self.ema_decay)
+            grad_clip, lr_min_ratio = float(get("grad_clip")), float(get("lr_min_ratio"))
+            lr_warmup, lr_decay_steps = int(get("lr_warmup")), int(get("lr_decay_steps"))
+            if not grad_clip >= 0.0:
+                raise ValueError(f"grad_clip = {grad_clip}: 0 (off) or the largest global gradient norm")
+            if int(get("skip_nonfinite")) not in (0, 1):
+                raise ValueError(f"skip_nonfinite = {get('skip_nonfinite')}: 0 (off) or 1")
+            if get("lr_scheduler") not in ("none", "cosine"):
+                raise ValueError(f"lr_scheduler = {get('lr_scheduler')!r}: 'none' or 'cosine'")
+            if lr_warmup < 0 or lr_decay_steps < 0:
+                raise ValueError(f"lr_warmup = {lr_warmup}, lr_decay_steps = {lr_decay_steps}: 0 (off) or a number of steps")
+            if not 0.0 <= lr_min_ratio <= 1.0:
+                raise ValueError(f"lr_min_ratio = {lr_min_ratio}: the final fraction of lr, in [0, 1]")
+            if get("lr_scheduler") == "cosine" and lr_decay_steps == 0:
+                raise ValueError("lr_scheduler = 'cosine' with lr_decay_steps = 0: give the number of steps of the decay")
+            self.optimizer = FusedAdam(self.net, lr=G.lr if "lr" in G else 3e-4, ema_net=self.ema_net, ema_decay=self.ema_decay,
+                                       grad_clip=grad_clip, skip_nonfinite=bool(int(get("skip_nonfinite"))), lr_scheduler=get("lr_scheduler"),
+                                       lr_warmup=lr_warmup, lr_decay_steps=lr_decay_steps, lr_min_ratio=lr_min_ratio)
             self.size = 32 if ("pad32" in G and G.pad32) else 28
             self._aux_rng = PhiloxStream(seed + 7919)
             self._sync = None
@@ -148,6 +170,18 @@ def make_plugin(GMBase, AttrDict):
                 self.optimizer.seed_ema()
             return self.ema_net
 
+        def _step_metrics(self, loss):
+            """What train_step returns: the reference's two keys; with clipping or the guard on also `grad_norm` and `skipped_steps` (device
+            scalars copied from the optimiser's state: no host sync), with a schedule on also `lr`."""
+            metrics = {"loss": loss, "loss_scale": torch.tensor(1.0)}
+            opt = self.optimizer
+            if opt.steered:
+                metrics["grad_norm"] = opt.ctl_state[ops.GRAD_NORM].clone()
+                metrics["skipped_steps"] = opt.ctl_state[ops.SKIPPED].clone()
+            if opt.scheduled:
+                metrics["lr"] = torch.tensor(opt.last_lr, dtype=torch.float64)
+            return metrics
+
         # -- training (diffusion_model.py:63-74)
         def train_step(self, x, y):
             B = x.shape[0]
@@ -171,16 +205,15 @@ def make_plugin(GMBase, AttrDict):
                 raise
             self._sync.finish()
             self.optimizer.step(grad_scale=1.0 / world)
-            metrics = {"loss": ops.mean(out["loss"])}
+            metrics = self._step_metrics(ops.mean(out["loss"]))
             ops.throttle()                          # at most two steps queued on the GPU (see ops.throttle)
-            metrics["loss_scale"] = torch.tensor(1.0)
             return metrics
 
         # -- small batches: the step as a replayed HIP graph ------------------------------------------------------------------
         # The reference's default invocation trains at bs = 32 (BASELINE configs[0]).  At that size a step is ~ 350 kernel launches whose host
         # side (ctypes + torch allocations, 4.6 - 5.0 ms) exceeds the GPU's work (3.5 ms): forward, loss, backward and the loss mean are captured once
         # per input shape and replayed; the random draws (same Philox streams, same order), the label drop on the CALLER's y, the copies into
-        # the static inputs and the fused Adam (its step count changes every step) stay outside.  Same kernels, same arguments: the
+        # the static inputs and the fused Adam (its step count changes every step; with it the gradient-norm launches of grad_clip / skip_nonfinite) stay outside.  Same kernels, same arguments: the
         # parameters after k steps equal the kernel-by-kernel path's bit for bit (tests/test_gpu_unet.py).  The weight gradients run on the main
         # stream inside the capture (the side stream pays at sizes that fill the chip).  Measured, same box: bs = 32 5.00 -> 3.46 ms per step,
         # bs = 64 4.69 -> 4.14, bs = 128 5.11 -> 5.23 (hence the 64 Ki-pixel limit).  GMK_TRAIN_GRAPH_PIXELS=0 turns it off.
@@ -225,7 +258,7 @@ def make_plugin(GMBase, AttrDict):
             xs.copy_(x); ys.copy_(y); es.copy_(eps); us.copy_(u)
             graph.replay()
             self.optimizer.step(grad_scale=1.0)
-            metrics = {"loss": loss.clone(), "loss_scale": torch.tensor(1.0)}
+            metrics = self._step_metrics(loss.clone())
             ops.throttle()
             return metrics
 

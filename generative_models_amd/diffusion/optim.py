@@ -6,7 +6,19 @@ leaves them unchanged exactly as torch's skip of `grad is None` does.
 
 With `ema_net` and `ema_decay > 0` (an extension: the reference keeps no weight average) the same launch also updates an exponential
 moving average of the weights in `ema_net.flat_params` (same arena layout): ema.lerp_(p_new, 1 - decay_t) with the warm-up of
-`ema_decay_at`.  The EMA starts as a copy of the weights at the first step, or at `seed_ema()`."""
+`ema_decay_at`.  The EMA starts as a copy of the weights at the first step, or at `seed_ema()`.
+
+Three more extensions, all off by default (step() then makes exactly the calls above):
+  * `grad_clip = c > 0`: the gradient is scaled by min(1, c / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s rule, with `norm` the global L2
+    norm of the gradient Adam consumes (after `grad_scale`);
+  * `skip_nonfinite`: a step whose gradient norm is inf or NaN changes nothing - p, m, v and the EMA keep their bits - which is what the
+    reference's GradScaler.step does.  `grad_clip > 0` implies this guard: a non-finite norm has no clipping coefficient worth applying;
+  * a learning-rate schedule on the host, `lr_at`.
+The norm and the decision are formed on the device (ops.grad_norm) and read by the Adam launch (ops.adam_step_ctl): no host sync.  A skipped
+step therefore STILL advances `step_count`, and with it the bias correction, the schedule and the EMA warm-up; GradScaler does not advance the
+optimiser on a skipped step.  The count of skipped steps lives on the device (`ctl_state[ops.SKIPPED]`)."""
+import math
+
 import torch
 
 from .. import ops
@@ -19,7 +31,8 @@ def ema_decay_at(decay, t):
 
 
 class FusedAdam:
-    def __init__(self, net, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, ema_net=None, ema_decay=0.0):
+    def __init__(self, net, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, ema_net=None, ema_decay=0.0, grad_clip=0.0, skip_nonfinite=False,
+                 lr_scheduler="none", lr_warmup=0, lr_decay_steps=0, lr_min_ratio=0.1):
         self.net, self.lr, self.betas, self.eps = net, float(lr), betas, float(eps)
         self.step_count = 0
         self.m = self.v = None
@@ -30,6 +43,37 @@ class FusedAdam:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
         self.ema_net = ema_net if self.ema_decay > 0 else None
         self.ema_seeded = False
+        self.grad_clip, self.skip_nonfinite = float(grad_clip), bool(skip_nonfinite)
+        if not self.grad_clip >= 0.0:
+            raise ValueError(f"grad_clip must be >= 0 (0: off), got {grad_clip}")
+        self.lr_scheduler, self.lr_warmup, self.lr_decay_steps = lr_scheduler, int(lr_warmup), int(lr_decay_steps)
+        self.lr_min_ratio = float(lr_min_ratio)
+        if self.lr_scheduler not in ("none", "cosine"):
+            raise ValueError(f"lr_scheduler must be 'none' or 'cosine', got {lr_scheduler!r}")
+        if self.lr_warmup < 0 or self.lr_decay_steps < 0:
+            raise ValueError(f"lr_warmup and lr_decay_steps must be >= 0, got {lr_warmup} and {lr_decay_steps}")
+        if not 0.0 <= self.lr_min_ratio <= 1.0:
+            raise ValueError(f"lr_min_ratio must be in [0, 1], got {lr_min_ratio}")
+        if self.lr_scheduler == "cosine" and self.lr_decay_steps == 0:
+            raise ValueError("lr_scheduler 'cosine' needs lr_decay_steps > 0")
+        self.steered = self.grad_clip > 0 or self.skip_nonfinite          # step() goes through ops.grad_norm / ops.adam_step_ctl
+        self.scheduled = self.lr_scheduler != "none" or self.lr_warmup > 0
+        self.ctl_state = self._ctl_ws = None                              # device: [grad_norm, clip coefficient, apply, skipped steps]
+        self._skipped0 = 0.0                                              # the count a loaded state dict carries, until ctl_state exists
+        self.last_lr = self.lr
+
+    def lr_at(self, t):
+        """Learning rate of the step taken after `t` earlier ones, in double.  Warm-up: times min(1, (t + 1) / lr_warmup).  'cosine': from lr
+        down to lr_min_ratio * lr over the lr_decay_steps steps that follow the warm-up, constant from there on."""
+        if not self.scheduled:
+            return self.lr
+        f = 1.0
+        if self.lr_warmup > 0:
+            f = min(1.0, (t + 1.0) / self.lr_warmup)
+        if self.lr_scheduler == "cosine":
+            x = min(max(t - self.lr_warmup, 0), self.lr_decay_steps) / self.lr_decay_steps
+            f *= self.lr_min_ratio + (1.0 - self.lr_min_ratio) * 0.5 * (1.0 + math.cos(math.pi * x))
+        return self.lr * f
 
     def zero_grad(self):
         self.net.flat_grads.zero_()
@@ -45,9 +89,12 @@ class FusedAdam:
         if self.m is None or self.m.device != p.device:
             self.m = torch.zeros_like(p)
             self.v = torch.zeros_like(p)
+        lr = self.last_lr = self.lr_at(self.step_count) if self.scheduled else self.lr
+        if self.steered:
+            return self._step_steered(p, lr, grad_scale)
         if self.ema_net is None:
             self.step_count += 1
-            ops.adam_step(p, self.net.flat_grads, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
+            ops.adam_step(p, self.net.flat_grads, self.m, self.v, lr, self.betas[0], self.betas[1], self.eps,
                           self.step_count, grad_scale)
             self.net.mark_params_changed()
             return
@@ -55,13 +102,38 @@ class FusedAdam:
             self.seed_ema()
         decay_t = ema_decay_at(self.ema_decay, self.step_count)
         self.step_count += 1
-        ops.adam_ema_step(p, self.net.flat_grads, self.m, self.v, self.ema_net.flat_params, self.lr, self.betas[0], self.betas[1],
+        ops.adam_ema_step(p, self.net.flat_grads, self.m, self.v, self.ema_net.flat_params, lr, self.betas[0], self.betas[1],
                           self.eps, self.step_count, decay_t, grad_scale)
         self.net.mark_params_changed()
         self.ema_net.mark_params_changed()
 
+    def _step_steered(self, p, lr, grad_scale):
+        g = self.net.flat_grads
+        if self.ctl_state is None or self.ctl_state.device != p.device:
+            self.ctl_state = torch.tensor([0.0, 1.0, 1.0, self._skipped0], dtype=torch.float32, device=p.device)
+            self._ctl_ws = ops.grad_norm_workspace(p.numel(), p.device)
+        ops.grad_norm(g, self.ctl_state, grad_scale, self.grad_clip, self._ctl_ws)
+        ema, decay_t = None, 0.0
+        if self.ema_net is not None:
+            if not self.ema_seeded:
+                self.seed_ema()
+            ema, decay_t = self.ema_net.flat_params, ema_decay_at(self.ema_decay, self.step_count)
+        self.step_count += 1                        # also when the device skips the step: the host never learns of it
+        ops.adam_step_ctl(p, g, self.m, self.v, self.ctl_state, lr, self.betas[0], self.betas[1], self.eps, self.step_count, grad_scale,
+                          ema=ema, decay_t=decay_t)
+        self.net.mark_params_changed()
+        if ema is not None:
+            self.ema_net.mark_params_changed()
+
+    def skipped_steps(self):
+        """Steps the non-finite guard has dropped so far (reads the device: a host sync)."""
+        return int(self._skipped0 if self.ctl_state is None else self.ctl_state[ops.SKIPPED].item())
+
     def state_dict(self):
-        return {"step": self.step_count, "m": self.m, "v": self.v, "lr": self.lr}
+        return {"step": self.step_count, "m": self.m, "v": self.v, "lr": self.lr, "skipped": self.skipped_steps()}
 
     def load_state_dict(self, sd):
         self.step_count, self.m, self.v, self.lr = sd["step"], sd["m"], sd["v"], sd["lr"]
+        self._skipped0 = float(sd.get("skipped", 0))
+        if self.ctl_state is not None:
+            self.ctl_state[ops.SKIPPED] = self._skipped0

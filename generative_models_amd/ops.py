@@ -1021,6 +1021,38 @@ def adam_ema_step(p, g, m, v, ema, lr, beta1, beta2, eps, step, decay_t, grad_sc
                                 1.0 - float(decay_t), _s()), "adam_ema_step")
 
 
+GRAD_NORM, CLIP_COEF, APPLY, SKIPPED = 0, 1, 2, 3       # slots of the 4-float state gmk_grad_norm writes
+
+
+def grad_norm_workspace(n, device):
+    """The workspace gmk_grad_norm needs for an arena of n floats (one partial sum of squares per workgroup)."""
+    return torch.empty((max(1, lib.gmk_grad_norm_workspace_bytes(int(n)) // 4),), dtype=torch.float32, device=device)
+
+
+def grad_norm(g, state, grad_scale=1.0, max_norm=0.0, workspace=None):
+    """state[GRAD_NORM] = grad_scale * ||g||_2, state[CLIP_COEF] = clip_grad_norm_'s coefficient for max_norm (1 when max_norm <= 0),
+    state[APPLY] = 1 if the norm is finite else 0, state[SKIPPED] += 1 - apply; no host sync (gmk_grad_norm).  `state`: 4 fp32 on the device,
+    zeroed by the caller before the first call; `workspace`: grad_norm_workspace(g.numel()), allocated here if not given.  -> state"""
+    _f32(g, "g")
+    _f32(state, "state")
+    assert state.numel() == 4
+    if workspace is None:
+        workspace = grad_norm_workspace(g.numel(), g.device)
+    _f32(workspace, "workspace")
+    check(lib.gmk_grad_norm(_p(g), g.numel(), grad_scale, max_norm, _p(workspace), workspace.numel() * 4, _p(state), _s()), "grad_norm")
+    return state
+
+
+def adam_step_ctl(p, g, m, v, state, lr, beta1, beta2, eps, step, grad_scale=1.0, ema=None, decay_t=0.0):
+    """adam_step (ema None) or adam_ema_step on the gradient (g * grad_scale) * state[CLIP_COEF]; does nothing at all when state[APPLY] is 0
+    (gmk_adam_step_ctl).  With a coefficient of 1 the bits of those two ops."""
+    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (state, "state")) + (() if ema is None else ((ema, "ema"),)):
+        _f32(t, nm)
+    assert p.numel() == g.numel() == m.numel() == v.numel() and state.numel() == 4 and (ema is None or ema.numel() == p.numel())
+    check(lib.gmk_adam_step_ctl(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, step, grad_scale,
+                                1.0 - float(decay_t), _p(state), _s()), "adam_step_ctl")
+
+
 # ---- self-attention core (north_star extension; no reference call site) -----------------------------------------
 def bgemm_nt(A, B, out=None, alpha=1.0, out_dtype=None):
     """C[b] = alpha * A[b] @ B[b]^T for batches of K-contiguous matrices (row / batch strides free): A [batch, M, K],

@@ -388,6 +388,22 @@ int gmk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
  * DiffusionModel, DG.ema_decay).  ema: a second arena of n floats, same layout.  36 B / parameter against Adam's 28. */
 int gmk_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
                       float eps, int step, float grad_scale, float ema_w, void* stream);
+/* Global L2 norm of the gradient arena and this step's decision, on the device (no host sync).  No reference call site for the clipping; the
+ * guard is what GradScaler.step does in the reference's train step (diffusion_model.py:71).  Writes state[0..3]:
+ *   [0] total_norm = grad_scale sqrt(sum g^2)                       the norm of the gradient Adam consumes
+ *   [1] coef       = min(1, max_norm / (total_norm + 1e-6))         torch.nn.utils.clip_grad_norm_; max_norm <= 0: no clipping, 1
+ *   [2] apply      = 1 if total_norm is finite, else 0              (an overflowing sum of squares counts as non-finite)
+ *   [3] skipped    += 1 - apply                                     a running count: zero it once, before the first call
+ * Two launches: one partial sum of squares per workgroup into `workspace` (gmk_grad_norm_workspace_bytes(n) bytes; the grid depends on n
+ * alone, not on gmk_set_cu_limit), then one workgroup adds the partials in a fixed order.  No atomics: the same bits on every call. */
+int64_t gmk_grad_norm_workspace_bytes(int64_t n);
+int gmk_grad_norm(const float* g, int64_t n, float grad_scale, float max_norm, float* workspace, int64_t workspace_bytes, float* state,
+                  void* stream);
+/* gmk_adam_step (ema NULL) or gmk_adam_ema_step steered by gmk_grad_norm's `state`: the gradient is (g grad_scale) coef - with coef = 1 the
+ * bits of those two, with coef < 1 the bits of gmk_adam_step(grad_scale = 1) on a gradient pre-scaled the same way - and when apply is 0 the
+ * launch returns before it touches p, m, v or ema. */
+int gmk_adam_step_ctl(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2, float eps,
+                      int step, float grad_scale, float ema_w, const float* state, void* stream);
 
 #ifdef __cplusplus
 }
