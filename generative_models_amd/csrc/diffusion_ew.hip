@@ -11,6 +11,8 @@
 
 #include "gmk_common.h"
 
+#define GMK_REQUIRE_MEAN_TYPE(mt, who) GMK_REQUIRE((mt) >= 0 && (mt) <= 2, who ": mean_type must be 0 (v), 1 (eps) or 2 (x)")
+
 namespace {
 
 // cosine log-SNR schedule constants for logsnr in [-20, 20] (diffusion_utils.py:199-200), rounded to fp32 the way
@@ -285,18 +287,19 @@ __global__ __launch_bounds__(256) void q_sample_logsnr_kernel(const float* __res
     const int b = blockIdx.y;
     const LogsnrCoef c = logsnr_coef(logsnr[b]);
     const int64_t base = (int64_t)b * n;
+    auto elem = [&](float xv, float ev) { return __fadd_rn(__fmul_rn(xv, c.alpha), __fmul_rn(c.sigma, ev)); };
     if ((n & 3) == 0) {
         for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
             float xv[4], ev[4], o[4];
             load4(x + base + i, xv);
             load4(eps + base + i, ev);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = __fadd_rn(__fmul_rn(xv[k], c.alpha), __fmul_rn(c.sigma, ev[k]));
+            for (int k = 0; k < 4; ++k) o[k] = elem(xv[k], ev[k]);
             store4(z + base + i, o);
         }
     } else {
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-            z[base + i] = __fadd_rn(__fmul_rn(x[base + i], c.alpha), __fmul_rn(c.sigma, eps[base + i]));
+            z[base + i] = elem(x[base + i], eps[base + i]);
     }
 }
 
@@ -315,6 +318,10 @@ __global__ __launch_bounds__(256) void vlb_term_kernel(const float* __restrict__
     const LogsnrCoef c = logsnr_coef(logsnr[b]);
     const int64_t base = (int64_t)b * n;
     float s = 0.f;
+    auto elem = [&](float o, float zz, float e) {
+        const float d = e - eps_from_out(o, zz, c, mt);
+        s = fmaf(d, d, s);
+    };
     if ((n & 3) == 0) {
         for (int64_t i = threadIdx.x * 4; i < n; i += 1024) {
             float ov[4], zv[4], ev[4];
@@ -322,16 +329,10 @@ __global__ __launch_bounds__(256) void vlb_term_kernel(const float* __restrict__
             load4(z + base + i, zv);
             load4(eps + base + i, ev);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float d = ev[k] - eps_from_out(ov[k], zv[k], c, mt);
-                s = fmaf(d, d, s);
-            }
+            for (int k = 0; k < 4; ++k) elem(ov[k], zv[k], ev[k]);
         }
     } else {
-        for (int64_t i = threadIdx.x; i < n; i += 256) {
-            const float d = eps[base + i] - eps_from_out(out[base + i], z[base + i], c, mt);
-            s = fmaf(d, d, s);
-        }
+        for (int64_t i = threadIdx.x; i < n; i += 256) elem(out[base + i], z[base + i], eps[base + i]);
     }
     s = block_sum(s, red);
     if (threadIdx.x == 0) acc[b] += weight[b] * s;
@@ -426,7 +427,7 @@ __global__ __launch_bounds__(256) void rng_kernel(float* __restrict__ out, int64
     }
 }
 
-// One Adam update of one element: the single definition behind adam_kernel and adam_ema_kernel, so the two produce the same bits for
+// One Adam update of one element: the single definition behind every adam_kernel instantiation, so they produce the same bits for
 // p, m and v (the library builds with -ffp-contract=off; a second copy of these lines would still be a second place for them to drift).
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float step_size, float beta1, float beta2, float eps,
                                           float inv_bc2_sqrt, float grad_scale) {
@@ -445,49 +446,41 @@ __device__ __forceinline__ float lerp_to(float start, float end, float w) {
     return w < 0.5f ? fmaf(w, diff, start) : fmaf(-diff, 1.0f - w, end);
 }
 
+// The Adam step behind gmk_adam_step, gmk_adam_ema_step and gmk_adam_step_ctl.
+// EMA: Adam, then the EMA of the updated weights in the same pass: ema = lerp(ema, p_new, ema_w).  p is read once, so the EMA costs its own
+// read and write only (36 B / parameter against Adam's 28).
+// CTL: steered by gmk_grad_norm's state (below): gg = (g grad_scale) coef (adam_elem then multiplies by 1: exact), and no memory is touched
+// when apply == 0.  Both values are uniform across the launch.  Without CTL adam_elem forms g grad_scale itself and `state` is not read.
+template <bool EMA, bool CTL>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, int64_t n, float step_size, float beta1,
-                                                  float beta2, float eps, float inv_bc2_sqrt, float grad_scale) {
+                                                  float* __restrict__ v, float* __restrict__ ema, const float* __restrict__ state,
+                                                  int64_t n, float step_size, float beta1, float beta2, float eps, float inv_bc2_sqrt,
+                                                  float grad_scale, float ema_w) {
+    if (CTL && state[2] == 0.0f) return;
+    const float coef = CTL ? state[1] : 1.0f;
+    auto elem = [&](float& pp, float gk, float& mm, float& vv) {
+        adam_elem(pp, CTL ? (gk * grad_scale) * coef : gk, mm, vv, step_size, beta1, beta2, eps, inv_bc2_sqrt, CTL ? 1.0f : grad_scale);
+    };
     const int64_t nq = n / 4;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
-        float pv[4], gv[4], mv[4], vv[4];
+        float pv[4], gv[4], mv[4], vv[4], ev[4];
         load4(p + q * 4, pv); load4(g + q * 4, gv); load4(m + q * 4, mv); load4(v + q * 4, vv);
+        if (EMA) load4(ema + q * 4, ev);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) adam_elem(pv[k], gv[k], mv[k], vv[k], step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
+        for (int k = 0; k < 4; ++k) {
+            elem(pv[k], gv[k], mv[k], vv[k]);
+            if (EMA) ev[k] = lerp_to(ev[k], pv[k], ema_w);
+        }
         store4(p + q * 4, pv); store4(m + q * 4, mv); store4(v + q * 4, vv);
+        if (EMA) store4(ema + q * 4, ev);
     }
     // tail (n not a multiple of 4)
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const int64_t i = nq * 4 + threadIdx.x;
         float pp = p[i], mm = m[i], vv = v[i];
-        adam_elem(pp, g[i], mm, vv, step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
+        elem(pp, g[i], mm, vv);
         m[i] = mm; v[i] = vv; p[i] = pp;
-    }
-}
-
-// Adam, then the EMA of the updated weights in the same pass: ema = lerp(ema, p_new, ema_w).  p is read once, so the EMA costs its own
-// read and write only (36 B / parameter against Adam's 28).
-__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                      float* __restrict__ v, float* __restrict__ ema, int64_t n, float step_size,
-                                                      float beta1, float beta2, float eps, float inv_bc2_sqrt, float grad_scale,
-                                                      float ema_w) {
-    const int64_t nq = n / 4;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
-        float pv[4], gv[4], mv[4], vv[4], ev[4];
-        load4(p + q * 4, pv); load4(g + q * 4, gv); load4(m + q * 4, mv); load4(v + q * 4, vv); load4(ema + q * 4, ev);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            adam_elem(pv[k], gv[k], mv[k], vv[k], step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
-            ev[k] = lerp_to(ev[k], pv[k], ema_w);
-        }
-        store4(p + q * 4, pv); store4(m + q * 4, mv); store4(v + q * 4, vv); store4(ema + q * 4, ev);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = nq * 4 + threadIdx.x;
-        float pp = p[i], mm = m[i], vv = v[i];
-        adam_elem(pp, g[i], mm, vv, step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
-        m[i] = mm; v[i] = vv; p[i] = pp;
-        ema[i] = lerp_to(ema[i], pp, ema_w);
+        if (EMA) ema[i] = lerp_to(ema[i], pp, ema_w);
     }
 }
 
@@ -545,37 +538,6 @@ __global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* __res
     }
 }
 
-// adam_kernel / adam_ema_kernel steered by gmk_grad_norm's state: gg = (g grad_scale) coef (adam_elem then multiplies by 1: exact), and no
-// memory is touched when apply == 0.  Both values are uniform across the launch.
-template <bool EMA>
-__global__ __launch_bounds__(256) void adam_ctl_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                      float* __restrict__ v, float* __restrict__ ema, const float* __restrict__ state,
-                                                      int64_t n, float step_size, float beta1, float beta2, float eps, float inv_bc2_sqrt,
-                                                      float grad_scale, float ema_w) {
-    if (state[2] == 0.0f) return;
-    const float coef = state[1];
-    const int64_t nq = n / 4;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
-        float pv[4], gv[4], mv[4], vv[4], ev[4];
-        load4(p + q * 4, pv); load4(g + q * 4, gv); load4(m + q * 4, mv); load4(v + q * 4, vv);
-        if (EMA) load4(ema + q * 4, ev);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            adam_elem(pv[k], (gv[k] * grad_scale) * coef, mv[k], vv[k], step_size, beta1, beta2, eps, inv_bc2_sqrt, 1.0f);
-            if (EMA) ev[k] = lerp_to(ev[k], pv[k], ema_w);
-        }
-        store4(p + q * 4, pv); store4(m + q * 4, mv); store4(v + q * 4, vv);
-        if (EMA) store4(ema + q * 4, ev);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = nq * 4 + threadIdx.x;
-        float pp = p[i], mm = m[i], vv = v[i];
-        adam_elem(pp, (g[i] * grad_scale) * coef, mm, vv, step_size, beta1, beta2, eps, inv_bc2_sqrt, 1.0f);
-        m[i] = mm; v[i] = vv; p[i] = pp;
-        if (EMA) ema[i] = lerp_to(ema[i], pp, ema_w);
-    }
-}
-
 // ---- probability-flow ODE (Song et al. 2021, section 4.3 and App. D.2, in lambda = logsnr); an extension, no reference call site.
 // Probes and dequantisation noise use gmk_rng_uniform's counters: element i is component i % 4 of Philox counter offset + i / 4, so the
 // host can replay them with a plain uniform draw.
@@ -628,6 +590,12 @@ __global__ __launch_bounds__(256) void pf_ode_step_kernel(const float* __restric
     const bool div = acc != nullptr, pri = prior != nullptr;
     const int64_t base = (int64_t)b * n;
     float srg = 0.f, szz = 0.f;
+    auto elem = [&](float o, float zz, float& xh, float& zj) {      // -> x_hat and the updated z
+        if (pri) szz = fmaf(zz, zz, szz);
+        xh = x_from_out(o, zz, c, mt);
+        const float eh = eps_from_out(o, zz, c, mt);
+        zj = cj.alpha * xh + cj.sigma * eh;
+    };
     if ((n & 3) == 0) {
         for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
             float ov[4], zv[4], xh[4];
@@ -641,23 +609,16 @@ __global__ __launch_bounds__(256) void pf_ode_step_kernel(const float* __restric
                 for (int k = 0; k < 4; ++k) srg = fmaf(rv[k], gv[k], srg);
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (pri) szz = fmaf(zv[k], zv[k], szz);
-                xh[k] = x_from_out(ov[k], zv[k], c, mt);
-                const float eh = eps_from_out(ov[k], zv[k], c, mt);
-                zv[k] = cj.alpha * xh[k] + cj.sigma * eh;
-            }
+            for (int k = 0; k < 4; ++k) elem(ov[k], zv[k], xh[k], zv[k]);
             if (update) store4(z + base + i, zv);
             if (x_out) store4(x_out + base + i, xh);
         }
     } else {
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-            const float o = out[base + i], zz = z[base + i];
             if (div) srg = fmaf(r[base + i], g[base + i], srg);
-            if (pri) szz = fmaf(zz, zz, szz);
-            const float xh = x_from_out(o, zz, c, mt);
-            const float eh = eps_from_out(o, zz, c, mt);
-            if (update) z[base + i] = cj.alpha * xh + cj.sigma * eh;
+            float xh, zj;
+            elem(out[base + i], z[base + i], xh, zj);
+            if (update) z[base + i] = zj;
             if (x_out) x_out[base + i] = xh;
         }
     }
@@ -669,6 +630,12 @@ __global__ __launch_bounds__(256) void pf_ode_step_kernel(const float* __restric
         szz = block_sum(szz, red);
         if (threadIdx.x == 0) prior[b] = 0.5f * szz + prior_c;
     }
+}
+
+// blocks per row of a (gx, B) grid whose blocks take `per_block` elements per pass: enough for the row, at most 64
+int row_grid(int64_t n, int per_block) {
+    const int64_t g = (n + per_block - 1) / per_block;
+    return (int)(g > 64 ? 64 : g);
 }
 
 int stream_grid(int64_t work_items) {
@@ -695,8 +662,7 @@ extern "C" int gmk_q_sample(const float* x, const float* eps, const float* u, fl
     GMK_REQUIRE(x && eps && u && logsnr && z, "gmk_q_sample: null pointer");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0 && n % 4 == 0, "gmk_q_sample: bad shape B=%d n=%lld (n %% 4 == 0 required)", B,
                 (long long)n);
-    int gx = (int)((n + 1023) / 1024);
-    if (gx > 64) gx = 64;
+    const int gx = row_grid(n, 1024);
     q_sample_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(x, eps, u, logsnr, z, n);
     return gmk_check_launch("gmk_q_sample");
 }
@@ -707,7 +673,7 @@ extern "C" int gmk_v_loss(const float* v, const float* z, const float* x, const 
     GMK_REQUIRE(v && z && x && eps && logsnr && loss_b, "gmk_v_loss: null pointer");
     GMK_REQUIRE(B > 0 && n > 0, "gmk_v_loss: bad shape");
     GMK_REQUIRE(loss_type == 0 || loss_type == 1, "gmk_v_loss: loss_type must be 0 (snr_trunc) or 1 (snr)");
-    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "gmk_v_loss: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_v_loss");
     v_loss_kernel<<<B, 256, 0, gmk_stream(stream)>>>(v, z, x, eps, logsnr, loss_b, x_mse, eps_mse, dv, grad_scale, n, loss_type, mean_type);
     return gmk_check_launch("gmk_v_loss");
 }
@@ -717,11 +683,10 @@ extern "C" int gmk_sampler_step(const float* v, const float* v_uncond, const flo
                                 float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n,
                                 void* stream) {
     GMK_REQUIRE(v && z && z_next, "gmk_sampler_step: null pointer");
-    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "gmk_sampler_step: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_sampler_step");
     GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_sampler_step: v_uncond and cond_w go together");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_sampler_step: bad shape");
-    int gx = (int)((n + 255) / 256);
-    if (gx > 64) gx = 64;
+    const int gx = row_grid(n, 256);
     sampler_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, noise, logsnr_t, logsnr_s,
                                                                      is_last, z_next, x_pred, eps_pred, n, nullptr, nullptr, mean_type,
                                                                      z_dup, logsnr_next);
@@ -733,13 +698,12 @@ extern "C" int gmk_dpm_solver_step(const float* v, const float* v_uncond, const 
                                    float* z_next, float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type,
                                    int B, int64_t n, void* stream) {
     GMK_REQUIRE(v && z && x_hist && z_next, "gmk_dpm_solver_step: null pointer");
-    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "gmk_dpm_solver_step: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_dpm_solver_step");
     GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_dpm_solver_step: v_uncond and cond_w go together");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_dpm_solver_step: bad shape");
     GMK_REQUIRE(isfinite(logsnr_t) && isfinite(logsnr_s) && isfinite(coef_z) && isfinite(coef_x) && isfinite(coef_prev),
                 "gmk_dpm_solver_step: non-finite time or coefficient");
-    int gx = (int)((n + 255) / 256);
-    if (gx > 64) gx = 64;
+    const int gx = row_grid(n, 256);
     dpm_solver_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, x_hist, logsnr_t, logsnr_s, coef_z,
                                                                         coef_x, coef_prev, is_last, z_next, x_pred, eps_pred, z_dup,
                                                                         logsnr_next, n, mean_type);
@@ -758,8 +722,7 @@ extern "C" int gmk_inpaint_merge(float* z, const float* x0, const uint8_t* mask,
     GMK_REQUIRE(!(is_last && renoise), "gmk_inpaint_merge: the last step does not re-noise");
     GMK_REQUIRE(isfinite(alpha_s) && isfinite(sigma_s) && isfinite(a) && isfinite(b) && isfinite(logsnr_t) && isfinite(logsnr_s),
                 "gmk_inpaint_merge: non-finite time or coefficient");
-    int gx = (int)((n + 1023) / 1024);
-    if (gx > 64) gx = 64;
+    const int gx = row_grid(n, 1024);
     const uint64_t ctr1 = offset + q0;
     const uint64_t ctr2 = offset + (uint64_t)B_total * (uint64_t)(n / 4) + q0;
     inpaint_merge_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(z, x0, mask, alpha_s, sigma_s, a, b, is_last, renoise,
@@ -770,8 +733,7 @@ extern "C" int gmk_inpaint_merge(float* z, const float* x0, const uint8_t* mask,
 extern "C" int gmk_q_sample_logsnr(const float* x, const float* eps, const float* logsnr, float* z, int B, int64_t n, void* stream) {
     GMK_REQUIRE(x && eps && logsnr && z, "gmk_q_sample_logsnr: null pointer");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_q_sample_logsnr: bad shape B=%d n=%lld", B, (long long)n);
-    int gx = (int)((n + 1023) / 1024);
-    if (gx > 64) gx = 64;
+    const int gx = row_grid(n, 1024);
     q_sample_logsnr_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(x, eps, logsnr, z, n);
     return gmk_check_launch("gmk_q_sample_logsnr");
 }
@@ -779,7 +741,7 @@ extern "C" int gmk_q_sample_logsnr(const float* x, const float* eps, const float
 extern "C" int gmk_vlb_term(const float* out, const float* z, const float* eps, const float* logsnr, const float* weight, float* acc,
                             int mean_type, int B, int64_t n, void* stream) {
     GMK_REQUIRE(out && z && eps && logsnr && weight && acc, "gmk_vlb_term: null pointer");
-    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "gmk_vlb_term: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_vlb_term");
     GMK_REQUIRE(B > 0 && n > 0, "gmk_vlb_term: bad shape B=%d n=%lld", B, (long long)n);
     vlb_term_kernel<<<B, 256, 0, gmk_stream(stream)>>>(out, z, eps, logsnr, weight, acc, n, mean_type);
     return gmk_check_launch("gmk_vlb_term");
@@ -806,11 +768,10 @@ extern "C" int gmk_ddim_step_vec(const float* v, const float* v_uncond, const fl
                                  const float* logsnr_t, const float* logsnr_s, float* z_next, float* x_pred, float* eps_pred,
                                  int mean_type, int B, int64_t n, void* stream) {
     GMK_REQUIRE(v && z && z_next && logsnr_t && logsnr_s, "gmk_ddim_step_vec: null pointer");
-    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "gmk_ddim_step_vec: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_ddim_step_vec");
     GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_ddim_step_vec: v_uncond and cond_w go together");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_ddim_step_vec: bad shape");
-    int gx = (int)((n + 255) / 256);
-    if (gx > 64) gx = 64;
+    const int gx = row_grid(n, 256);
     sampler_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, nullptr, 0.f, 0.f, 0, z_next, x_pred,
                                                                      eps_pred, n, logsnr_t, logsnr_s, mean_type);
     return gmk_check_launch("gmk_ddim_step_vec");
@@ -818,12 +779,11 @@ extern "C" int gmk_ddim_step_vec(const float* v, const float* v_uncond, const fl
 
 namespace {
 // u -> logsnr (diffusion_utils.py:198-201); optionally u = (i + 1) / T - shift from integer times (gaussian_diffusion.py:90-91)
-__global__ void schedule_kernel(const float* __restrict__ u, const int64_t* __restrict__ ti, float inv_T_num, float T,
-                                float shift, float* __restrict__ u_out, float* __restrict__ logsnr, int B) {
+__global__ void schedule_kernel(const float* __restrict__ u, const int64_t* __restrict__ ti, float T, float shift,
+                                float* __restrict__ u_out, float* __restrict__ logsnr, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     float uu = ti ? __fdiv_rn((float)(ti[b] + 1), T) : u[b];
-    (void)inv_T_num;
     uu = __fsub_rn(uu, shift);
     if (u_out) u_out[b] = uu;
     const float t = __fadd_rn(__fmul_rn(kSchedA, uu), kSchedB);
@@ -861,7 +821,7 @@ extern "C" int gmk_logsnr_schedule(const float* u, const int64_t* i_times, int n
                                    float* logsnr, int B, void* stream) {
     GMK_REQUIRE((u != nullptr) != (i_times != nullptr) && logsnr && B > 0, "gmk_logsnr_schedule: give exactly one of u / i_times");
     GMK_REQUIRE(!i_times || num_steps >= 1, "gmk_logsnr_schedule: num_steps");
-    schedule_kernel<<<(B + 255) / 256, 256, 0, gmk_stream(stream)>>>(u, i_times, 0.f, (float)num_steps, shift, u_out, logsnr, B);
+    schedule_kernel<<<(B + 255) / 256, 256, 0, gmk_stream(stream)>>>(u, i_times, (float)num_steps, shift, u_out, logsnr, B);
     return gmk_check_launch("gmk_logsnr_schedule");
 }
 
@@ -871,29 +831,29 @@ extern "C" int gmk_distill_target(const float* z_teacher, const float* z_t, cons
     GMK_REQUIRE(z_teacher && z_t && x_pred_teacher && logsnr && logsnr_s && i_times && x_target && eps_target,
                 "gmk_distill_target: null pointer");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_distill_target: bad shape");
-    int gx = (int)((n + 255) / 256);
-    if (gx > 64) gx = 64;
+    const int gx = row_grid(n, 256);
     distill_target_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(z_teacher, z_t, x_pred_teacher, logsnr, logsnr_s, i_times,
                                                                        x_target, eps_target, n);
     return gmk_check_launch("gmk_distill_target");
 }
 
-// scalar prologue in double, as torch.optim.adam._single_tensor_adam does on the host
-static void adam_scalars(float lr, float beta1, float beta2, int step, float* step_size, float* inv_bc2_sqrt) {
+// scalar prologue in double, as torch.optim.adam._single_tensor_adam does on the host, then the one launch of an Adam step
+template <bool EMA, bool CTL>
+static int adam_launch(const char* who, float* p, const float* g, float* m, float* v, float* ema, const float* state, int64_t n, float lr,
+                       float beta1, float beta2, float eps, int step, float grad_scale, float ema_w, void* stream) {
     const double bc1 = 1.0 - pow((double)beta1, step);
     const double bc2 = 1.0 - pow((double)beta2, step);
-    *step_size = (float)((double)lr / bc1);
-    *inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    const float step_size = (float)((double)lr / bc1);
+    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    adam_kernel<EMA, CTL><<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, ema, state, n, step_size, beta1, beta2, eps,
+                                                                                  inv_bc2_sqrt, grad_scale, ema_w);
+    return gmk_check_launch(who);
 }
 
 extern "C" int gmk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                              float eps, int step, float grad_scale, void* stream) {
     GMK_REQUIRE(p && g && m && v && n > 0 && step >= 1, "gmk_adam_step: bad arguments");
-    float step_size, inv_bc2_sqrt;
-    adam_scalars(lr, beta1, beta2, step, &step_size, &inv_bc2_sqrt);
-    adam_kernel<<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, n, step_size, beta1, beta2, eps,
-                                                                        inv_bc2_sqrt, grad_scale);
-    return gmk_check_launch("gmk_adam_step");
+    return adam_launch<false, false>("gmk_adam_step", p, g, m, v, nullptr, nullptr, n, lr, beta1, beta2, eps, step, grad_scale, 0.0f, stream);
 }
 
 extern "C" int gmk_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1,
@@ -901,11 +861,7 @@ extern "C" int gmk_adam_ema_step(float* p, const float* g, float* m, float* v, f
     GMK_REQUIRE(p && g && m && v && n > 0 && step >= 1, "gmk_adam_ema_step: bad arguments");
     GMK_REQUIRE(ema, "gmk_adam_ema_step: ema is null");
     GMK_REQUIRE(ema_w >= 0.0f && ema_w <= 1.0f, "gmk_adam_ema_step: ema_w = %g outside [0, 1]", (double)ema_w);
-    float step_size, inv_bc2_sqrt;
-    adam_scalars(lr, beta1, beta2, step, &step_size, &inv_bc2_sqrt);
-    adam_ema_kernel<<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, ema, n, step_size, beta1, beta2, eps,
-                                                                            inv_bc2_sqrt, grad_scale, ema_w);
-    return gmk_check_launch("gmk_adam_ema_step");
+    return adam_launch<true, false>("gmk_adam_ema_step", p, g, m, v, ema, nullptr, n, lr, beta1, beta2, eps, step, grad_scale, ema_w, stream);
 }
 
 static int64_t grad_norm_parts(int64_t n) {
@@ -934,15 +890,8 @@ extern "C" int gmk_adam_step_ctl(float* p, const float* g, float* m, float* v, f
     GMK_REQUIRE(p && g && m && v && n > 0 && step >= 1, "gmk_adam_step_ctl: bad arguments");
     GMK_REQUIRE(state, "gmk_adam_step_ctl: state is null");
     GMK_REQUIRE(!ema || (ema_w >= 0.0f && ema_w <= 1.0f), "gmk_adam_step_ctl: ema_w = %g outside [0, 1]", (double)ema_w);
-    float step_size, inv_bc2_sqrt;
-    adam_scalars(lr, beta1, beta2, step, &step_size, &inv_bc2_sqrt);
-    if (ema)
-        adam_ctl_kernel<true><<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, ema, state, n, step_size, beta1, beta2, eps,
-                                                                                      inv_bc2_sqrt, grad_scale, ema_w);
-    else
-        adam_ctl_kernel<false><<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, nullptr, state, n, step_size, beta1, beta2,
-                                                                                       eps, inv_bc2_sqrt, grad_scale, 0.0f);
-    return gmk_check_launch("gmk_adam_step_ctl");
+    return (ema ? adam_launch<true, true> : adam_launch<false, true>)("gmk_adam_step_ctl", p, g, m, v, ema, state, n, lr, beta1, beta2, eps, step,
+                                                                      grad_scale, ema ? ema_w : 0.0f, stream);
 }
 
 extern "C" int gmk_rng_rademacher(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
@@ -962,17 +911,13 @@ extern "C" int gmk_pf_ode_step(const float* out, float* z, const float* r, const
                                float logsnr_i, float logsnr_j, int update, float div_a, float div_b, float prior_c, int mean_type, int B,
                                int64_t n, void* stream) {
     GMK_REQUIRE(out && z, "gmk_pf_ode_step: null pointer");
-    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "gmk_pf_ode_step: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_pf_ode_step");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_pf_ode_step: bad shape B=%d n=%lld", B, (long long)n);
     GMK_REQUIRE(!acc || (r && g), "gmk_pf_ode_step: the divergence needs the probe r and the VJP g");
     GMK_REQUIRE(!(prior && update), "gmk_pf_ode_step: the prior is taken at the last point, which has no update");
     GMK_REQUIRE(isfinite(logsnr_i) && isfinite(logsnr_j) && isfinite(div_a) && isfinite(div_b) && isfinite(prior_c),
                 "gmk_pf_ode_step: non-finite time or coefficient");
-    int gx = 1;
-    if (!acc && !prior) {
-        const int64_t g64 = (n + 1023) / 1024;
-        gx = (int)(g64 > 64 ? 64 : g64);
-    }
+    const int gx = (acc || prior) ? 1 : row_grid(n, 1024);
     pf_ode_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(out, z, r, g, acc, prior, x_out, logsnr_i, logsnr_j, update, div_a,
                                                                      div_b, prior_c, n, mean_type);
     return gmk_check_launch("gmk_pf_ode_step");

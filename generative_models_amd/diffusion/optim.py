@@ -85,42 +85,29 @@ class FusedAdam:
         self.ema_seeded = True
 
     def step(self, grad_scale=1.0):
-        p = self.net.flat_params
+        p, g = self.net.flat_params, self.net.flat_grads
         if self.m is None or self.m.device != p.device:
             self.m = torch.zeros_like(p)
             self.v = torch.zeros_like(p)
         lr = self.last_lr = self.lr_at(self.step_count) if self.scheduled else self.lr
         if self.steered:
-            return self._step_steered(p, lr, grad_scale)
-        if self.ema_net is None:
-            self.step_count += 1
-            ops.adam_step(p, self.net.flat_grads, self.m, self.v, lr, self.betas[0], self.betas[1], self.eps,
-                          self.step_count, grad_scale)
-            self.net.mark_params_changed()
-            return
-        if not self.ema_seeded:
-            self.seed_ema()
-        decay_t = ema_decay_at(self.ema_decay, self.step_count)
-        self.step_count += 1
-        ops.adam_ema_step(p, self.net.flat_grads, self.m, self.v, self.ema_net.flat_params, lr, self.betas[0], self.betas[1],
-                          self.eps, self.step_count, decay_t, grad_scale)
-        self.net.mark_params_changed()
-        self.ema_net.mark_params_changed()
-
-    def _step_steered(self, p, lr, grad_scale):
-        g = self.net.flat_grads
-        if self.ctl_state is None or self.ctl_state.device != p.device:
-            self.ctl_state = torch.tensor([0.0, 1.0, 1.0, self._skipped0], dtype=torch.float32, device=p.device)
-            self._ctl_ws = ops.grad_norm_workspace(p.numel(), p.device)
-        ops.grad_norm(g, self.ctl_state, grad_scale, self.grad_clip, self._ctl_ws)
+            if self.ctl_state is None or self.ctl_state.device != p.device:
+                self.ctl_state = torch.tensor([0.0, 1.0, 1.0, self._skipped0], dtype=torch.float32, device=p.device)
+                self._ctl_ws = ops.grad_norm_workspace(p.numel(), p.device)
+            ops.grad_norm(g, self.ctl_state, grad_scale, self.grad_clip, self._ctl_ws)
         ema, decay_t = None, 0.0
         if self.ema_net is not None:
             if not self.ema_seeded:
                 self.seed_ema()
             ema, decay_t = self.ema_net.flat_params, ema_decay_at(self.ema_decay, self.step_count)
-        self.step_count += 1                        # also when the device skips the step: the host never learns of it
-        ops.adam_step_ctl(p, g, self.m, self.v, self.ctl_state, lr, self.betas[0], self.betas[1], self.eps, self.step_count, grad_scale,
-                          ema=ema, decay_t=decay_t)
+        self.step_count += 1                        # also when the device skips a steered step: the host never learns of it
+        adam = (lr, self.betas[0], self.betas[1], self.eps, self.step_count)
+        if self.steered:
+            ops.adam_step_ctl(p, g, self.m, self.v, self.ctl_state, *adam, grad_scale, ema=ema, decay_t=decay_t)
+        elif ema is not None:
+            ops.adam_ema_step(p, g, self.m, self.v, ema, *adam, decay_t, grad_scale)
+        else:
+            ops.adam_step(p, g, self.m, self.v, *adam, grad_scale)
         self.net.mark_params_changed()
         if ema is not None:
             self.ema_net.mark_params_changed()

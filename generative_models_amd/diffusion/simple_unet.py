@@ -801,104 +801,93 @@ class SimpleUnet(nn.Module):
                 self._cu_part = None
         ready = on_grads_ready if on_grads_ready is not None else (lambda k: None)
         join = self._join_side if (on_grads_ready is not None and join_side_before_ready) else (lambda: None)
-        P, G, C, T = self._pv, self._gv, self.channels, self.compute_dtype
-        B, H, W = ctx["dims"]
-        H2, W2, H4, W4 = H // 2, W // 2, H // 4, W // 4
-        x, t2, t5, u0r, u3r, u6, ao, mo, ro = ctx["net"]
-        dev = dout.device
-        dout = ops.aligned(dout.float())
-        demb_all = torch.empty((B, 12 * C), device=dev, dtype=torch.float32)
-
-        # head: out.2 conv + out.0 GroupNorm/SiLU
-        o = self._offsets["out.2.weight"]
-        nhead = self.in_channels * C * 9
-        assert self._offsets["out.2.bias"] == o + (nhead + 3) // 4 * 4 == o + nhead
-        self._on_side(lambda: ops.head_wgrad(dout, ao, self.flat_grads[o:o + nhead + self.in_channels]), (dout, ao))
-        dao = ops.head_dgrad(dout, P["out.2.weight"], T)
-        s6 = torch.empty((B, C), device=dev, dtype=torch.float32)
-        du6, dgp, dbp = ops.gn_silu_bwd(dao, u6, P["out.0.weight"], P["out.0.bias"], mo, ro, dxsum=s6)
-        ops.colsum(dgp, G["out.0.weight"], defer=True); ops.colsum(dbp, G["out.0.bias"], defer=True)
-
-        (du5, s5), (dt0a, _) = self._res_bwd("up.seq.6", ctx, du6, s6, demb_all, 11)
-        (du4, s4), (dt1a, _) = self._res_bwd("up.seq.5", ctx, du5, s5, demb_all, 10)
-        (du3, s3), (dt2a, _) = self._res_bwd("up.seq.4", ctx, du4, s4, demb_all, 9)
-        ops.flush_colsums(); join()
-        ready(0)
-        # up.seq.3.1: nearest x2 + conv
-        ops.colsum(s3, G["up.seq.3.1.conv.bias"], defer=True)
-        self._upsample_wgrad("up.seq.3.1.conv", du3, u3r)
-        du3r = self._upsample_dgrad("up.seq.3.1.conv", du3)
-        s3r = ops.chansum(du3r)
-        (du2, s2), (dt3a, _) = self._res_bwd("up.seq.3.0", ctx, du3r, s3r, demb_all, 8)
-        (du1, s1), (dt4a, _) = self._res_bwd("up.seq.2", ctx, du2, s2, demb_all, 7)
-        (du0, s0), (dt5a, _) = self._res_bwd("up.seq.1", ctx, du1, s1, demb_all, 6)
-        ops.colsum(s0, G["up.seq.0.1.conv.bias"], defer=True)
-        self._upsample_wgrad("up.seq.0.1.conv", du0, u0r)
-        du0r = self._upsample_dgrad("up.seq.0.1.conv", du0)
-        s0r = ops.chansum(du0r)
-        (dt7, s7), (dt6a, _) = self._res_bwd("up.seq.0.0", ctx, du0r, s0r, demb_all, 5)
-        if self.attention:
-            dt7, s7 = self._attn_bwd(ctx, dt7)
-        ops.flush_colsums(); join()
-        ready(1)
-        ((dt6, s6t),) = self._res_bwd("turn", ctx, dt7, s7, demb_all, 4, extra_add=[dt6a])
-        # down.seq.6: stride-2 conv; its data gradient is the transposed gather
-        ops.colsum(s6t, G["down.seq.6.conv.bias"], defer=True)
-        self._wgrad(dt6, [t5], 3, ops.STRIDE2, G["down.seq.6.conv.weight"])
-        dt5 = self._conv([dt6], self._packs["down.seq.6.conv"][1], C, 3, ops.TRANSPOSED2, (H2, W2), residual=dt5a)
-        s5t = ops.chansum(dt5)
-        ((dt4, s4t),) = self._res_bwd("down.seq.5", ctx, dt5, s5t, demb_all, 3, extra_add=[dt4a])
-        ((dt3, s3t),) = self._res_bwd("down.seq.4", ctx, dt4, s4t, demb_all, 2, extra_add=[dt3a])
-        ops.colsum(s3t, G["down.seq.3.conv.bias"], defer=True)
-        self._wgrad(dt3, [t2], 3, ops.STRIDE2, G["down.seq.3.conv.weight"])
-        dt2 = self._conv([dt3], self._packs["down.seq.3.conv"][1], C, 3, ops.TRANSPOSED2, (H, W), residual=dt2a)
-        s2t = ops.chansum(dt2)
-        ((dt1, s1t),) = self._res_bwd("down.seq.2", ctx, dt2, s2t, demb_all, 1, extra_add=[dt1a])
-        ((dt0, s0t),) = self._res_bwd("down.seq.1", ctx, dt1, s1t, demb_all, 0, extra_add=[dt0a])
-        ops.colsum(s0t, G["down.seq.0.conv.bias"], defer=True)
-        self._on_side(lambda: ops.stem_wgrad(x, dt0, G["down.seq.0.conv.weight"]), (x, dt0))
-        ops.flush_colsums(); join()
-        ready(2)
-        self._embed_bwd(ctx, demb_all)
-        ops.flush_colsums()
-        ready(3)
-        self._join_side()          # the caller (optimiser step, next forward) continues on the current stream
-        return ops.stem_dgrad(dt0, P["down.seq.0.conv.weight"]) if want_dx else None
+        dt0 = self._backward_schedule(ctx, ops.aligned(dout.float()), True, ready, join)
+        return ops.stem_dgrad(dt0, self._pv["down.seq.0.conv.weight"]) if want_dx else None
 
     def input_vjp_hip(self, ctx, r):
         """The input gradient alone: (d out / d x)^T r for the forward that filled `ctx` (forward_hip(..., ctx=)), r NCHW fp32 of the output's
         shape -> dx NCHW fp32 of the input's shape.  backward_hip's data-gradient chain from the head down to the stem, then the stem's data
         gradient (gmk_stem_dgrad): no weight, bias or embedding gradient, no channel sums, no side stream, no CU partition - `flat_grads` is
         not touched.  Consumes `ctx` like backward_hip.  (An extension: the reference never differentiates with respect to its input.)"""
-        P, C, T = self._pv, self.channels, self.compute_dtype
+        x = ctx["net"][0]
+        if tuple(r.shape) != tuple(x.shape):
+            raise ValueError(f"input_vjp_hip: r has shape {tuple(r.shape)}, the network output {tuple(x.shape)}")
+        dt0 = self._backward_schedule(ctx, ops.aligned(r.float()), False)
+        return ops.stem_dgrad(dt0, self._pv["down.seq.0.conv.weight"])
+
+    def _backward_schedule(self, ctx, dout, grads, ready=None, join=None):
+        """The one backward schedule: the order of the blocks and the wiring of the seven skip gradients.  dout: aligned NCHW fp32.
+        grads=True (backward_hip): the data-gradient chain plus every weight, bias and embedding gradient into `flat_grads`, with join() /
+        ready(k) once bucket k of grad_buckets() is enqueued.  grads=False (input_vjp_hip): the data-gradient chain alone.
+        -> dt0, the gradient of the stem's output."""
+        P, G, C, T = self._pv, self._gv, self.channels, self.compute_dtype
         B, H, W = ctx["dims"]
         H2, W2 = H // 2, W // 2
         x, t2, t5, u0r, u3r, u6, ao, mo, ro = ctx["net"]
-        if tuple(r.shape) != tuple(x.shape):
-            raise ValueError(f"input_vjp_hip: r has shape {tuple(r.shape)}, the network output {tuple(x.shape)}")
-        r = ops.aligned(r.float())
-        dao = ops.head_dgrad(r, P["out.2.weight"], T)
-        du6, _, _ = ops.gn_silu_bwd(dao, u6, P["out.0.weight"], P["out.0.bias"], mo, ro)
-        res = lambda name, d, blk, extra=None: self._res_bwd(name, ctx, d, None, None, blk, extra_add=extra, grads=False)
-        (du5, _), (dt0a, _) = res("up.seq.6", du6, 11)
-        (du4, _), (dt1a, _) = res("up.seq.5", du5, 10)
-        (du3, _), (dt2a, _) = res("up.seq.4", du4, 9)
-        du3r = self._upsample_dgrad("up.seq.3.1.conv", du3)
-        (du2, _), (dt3a, _) = res("up.seq.3.0", du3r, 8)
-        (du1, _), (dt4a, _) = res("up.seq.2", du2, 7)
-        (du0, _), (dt5a, _) = res("up.seq.1", du1, 6)
-        du0r = self._upsample_dgrad("up.seq.0.1.conv", du0)
-        (dt7, _), (dt6a, _) = res("up.seq.0.0", du0r, 5)
+        dev = dout.device
+        demb_all = torch.empty((B, 12 * C), device=dev, dtype=torch.float32) if grads else None
+        res = lambda name, d, dsum, blk, extra=None: self._res_bwd(name, ctx, d, dsum, demb_all, blk, extra_add=extra, grads=grads)
+
+        def bucket_done(k):
+            if grads:
+                ops.flush_colsums(); join()
+                ready(k)
+
+        def up(name, d, dsum, src):                  # nearest x2 + conv
+            if grads:
+                ops.colsum(dsum, G[name + ".bias"], defer=True)
+                self._upsample_wgrad(name, d, src)
+            dsrc = self._upsample_dgrad(name, d)
+            return dsrc, (ops.chansum(dsrc) if grads else None)
+
+        def down(name, d, dsum, src, hw, skip):      # stride-2 conv; its data gradient is the transposed gather
+            if grads:
+                ops.colsum(dsum, G[name + ".bias"], defer=True)
+                self._wgrad(d, [src], 3, ops.STRIDE2, G[name + ".weight"])
+            dsrc = self._conv([d], self._packs[name][1], C, 3, ops.TRANSPOSED2, hw, residual=skip)
+            return dsrc, (ops.chansum(dsrc) if grads else None)
+
+        # head: out.2 conv + out.0 GroupNorm/SiLU
+        if grads:
+            o = self._offsets["out.2.weight"]
+            nhead = self.in_channels * C * 9
+            assert self._offsets["out.2.bias"] == o + (nhead + 3) // 4 * 4 == o + nhead
+            self._on_side(lambda: ops.head_wgrad(dout, ao, self.flat_grads[o:o + nhead + self.in_channels]), (dout, ao))
+        dao = ops.head_dgrad(dout, P["out.2.weight"], T)
+        s6 = torch.empty((B, C), device=dev, dtype=torch.float32) if grads else None
+        du6, dgp, dbp = ops.gn_silu_bwd(dao, u6, P["out.0.weight"], P["out.0.bias"], mo, ro, dxsum=s6)
+        if grads:
+            ops.colsum(dgp, G["out.0.weight"], defer=True); ops.colsum(dbp, G["out.0.bias"], defer=True)
+
+        (du5, s5), (dt0a, _) = res("up.seq.6", du6, s6, 11)
+        (du4, s4), (dt1a, _) = res("up.seq.5", du5, s5, 10)
+        (du3, s3), (dt2a, _) = res("up.seq.4", du4, s4, 9)
+        bucket_done(0)
+        du3r, s3r = up("up.seq.3.1.conv", du3, s3, u3r)
+        (du2, s2), (dt3a, _) = res("up.seq.3.0", du3r, s3r, 8)
+        (du1, s1), (dt4a, _) = res("up.seq.2", du2, s2, 7)
+        (du0, s0), (dt5a, _) = res("up.seq.1", du1, s1, 6)
+        du0r, s0r = up("up.seq.0.1.conv", du0, s0, u0r)
+        (dt7, s7), (dt6a, _) = res("up.seq.0.0", du0r, s0r, 5)
         if self.attention:
-            dt7, _ = self._attn_bwd(ctx, dt7, grads=False)
-        ((dt6, _),) = res("turn", dt7, 4, [dt6a])
-        dt5 = self._conv([dt6], self._packs["down.seq.6.conv"][1], C, 3, ops.TRANSPOSED2, (H2, W2), residual=dt5a)
-        ((dt4, _),) = res("down.seq.5", dt5, 3, [dt4a])
-        ((dt3, _),) = res("down.seq.4", dt4, 2, [dt3a])
-        dt2 = self._conv([dt3], self._packs["down.seq.3.conv"][1], C, 3, ops.TRANSPOSED2, (H, W), residual=dt2a)
-        ((dt1, _),) = res("down.seq.2", dt2, 1, [dt1a])
-        ((dt0, _),) = res("down.seq.1", dt1, 0, [dt0a])
-        return ops.stem_dgrad(dt0, P["down.seq.0.conv.weight"])
+            dt7, s7 = self._attn_bwd(ctx, dt7, grads=grads)
+        bucket_done(1)
+        ((dt6, s6t),) = res("turn", dt7, s7, 4, [dt6a])
+        dt5, s5t = down("down.seq.6.conv", dt6, s6t, t5, (H2, W2), dt5a)
+        ((dt4, s4t),) = res("down.seq.5", dt5, s5t, 3, [dt4a])
+        ((dt3, s3t),) = res("down.seq.4", dt4, s4t, 2, [dt3a])
+        dt2, s2t = down("down.seq.3.conv", dt3, s3t, t2, (H, W), dt2a)
+        ((dt1, s1t),) = res("down.seq.2", dt2, s2t, 1, [dt1a])
+        ((dt0, s0t),) = res("down.seq.1", dt1, s1t, 0, [dt0a])
+        if grads:
+            ops.colsum(s0t, G["down.seq.0.conv.bias"], defer=True)
+            self._on_side(lambda: ops.stem_wgrad(x, dt0, G["down.seq.0.conv.weight"]), (x, dt0))
+            bucket_done(2)
+            self._embed_bwd(ctx, demb_all)
+            ops.flush_colsums()
+            ready(3)
+            self._join_side()          # the caller (optimiser step, next forward) continues on the current stream
+        return dt0
 
     def zero_grad_arena(self):
         self.flat_grads.zero_()

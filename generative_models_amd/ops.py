@@ -767,17 +767,16 @@ def v_loss(v, z, x, eps, logsnr, grad_scale=None, loss_type=0, mean_type="v"):
     return loss_b, xm, em, dv
 
 
-def sampler_step(v, z, logsnr_t, logsnr_s, is_last, v_uncond=None, cond_w=None, noise=None, want_pred=False, mean_type="v",
-                 dup=False, logsnr_next=None):
-    """dup: z_next is returned as the first half of a [2B, ...] tensor whose second half holds the same values (z2 = returned[1]);
-    logsnr_next: fp32 [B] (or [2B] with dup) filled with logsnr_s."""
+def _sampler_io(v, z, same_shape, cond_w, want_pred, dup, logsnr_next):
+    """The checks and outputs `sampler_step` and `dpm_solver_step` share.  same_shape: (tensor or None, name) pairs of z's shape.
+    -> (B, n, z_next, z2 (None without dup), x_pred, eps_pred)"""
     _f32(v, "v"); _f32(z, "z")
     B = z.shape[0]
     n = z.numel() // B
     assert v.shape == z.shape
-    for t in (v_uncond, noise):
+    for t, nm in same_shape:
         if t is not None:
-            _f32(t, "aux"); assert t.shape == z.shape
+            _f32(t, nm); assert t.shape == z.shape
     if cond_w is not None:
         _f32(cond_w, "cond_w"); assert cond_w.numel() == B
     z2 = torch.empty((2 * B,) + tuple(z.shape[1:]), device=z.device, dtype=z.dtype) if dup else None
@@ -786,6 +785,14 @@ def sampler_step(v, z, logsnr_t, logsnr_s, is_last, v_uncond=None, cond_w=None, 
     ep = torch.empty_like(z) if want_pred else None
     if logsnr_next is not None:
         _f32(logsnr_next, "logsnr_next"); assert logsnr_next.numel() == (2 * B if dup else B)
+    return B, n, z_next, z2, xp, ep
+
+
+def sampler_step(v, z, logsnr_t, logsnr_s, is_last, v_uncond=None, cond_w=None, noise=None, want_pred=False, mean_type="v",
+                 dup=False, logsnr_next=None):
+    """dup: z_next is returned as the first half of a [2B, ...] tensor whose second half holds the same values (z2 = returned[1]);
+    logsnr_next: fp32 [B] (or [2B] with dup) filled with logsnr_s."""
+    B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((v_uncond, "v_uncond"), (noise, "noise")), cond_w, want_pred, dup, logsnr_next)
     check(lib.gmk_sampler_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(noise), float(logsnr_t), float(logsnr_s),
                                int(is_last), _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next),
                                MEAN_TYPES[mean_type], B, n, _s()), "sampler_step")
@@ -796,20 +803,7 @@ def dpm_solver_step(v, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x, coef_prev,
                     mean_type="v", dup=False, logsnr_next=None):
     """One DPM-Solver++(2M) step (gmk_dpm_solver_step).  x_hist: fp32 [B, ...], the previous x-hat, overwritten with this step's (not read
     when coef_prev == 0).  Arguments and returns otherwise as `sampler_step` (no noise: the solver is deterministic)."""
-    _f32(v, "v"); _f32(z, "z"); _f32(x_hist, "x_hist")
-    B = z.shape[0]
-    n = z.numel() // B
-    assert v.shape == z.shape and x_hist.shape == z.shape
-    if v_uncond is not None:
-        _f32(v_uncond, "v_uncond"); assert v_uncond.shape == z.shape
-    if cond_w is not None:
-        _f32(cond_w, "cond_w"); assert cond_w.numel() == B
-    z2 = torch.empty((2 * B,) + tuple(z.shape[1:]), device=z.device, dtype=z.dtype) if dup else None
-    z_next = z2[:B] if dup else torch.empty_like(z)
-    xp = torch.empty_like(z) if want_pred else None
-    ep = torch.empty_like(z) if want_pred else None
-    if logsnr_next is not None:
-        _f32(logsnr_next, "logsnr_next"); assert logsnr_next.numel() == (2 * B if dup else B)
+    B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((x_hist, "x_hist"), (v_uncond, "v_uncond")), cond_w, want_pred, dup, logsnr_next)
     check(lib.gmk_dpm_solver_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(x_hist), float(logsnr_t), float(logsnr_s), float(coef_z),
                                   float(coef_x), float(coef_prev), int(is_last), _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None,
                                   _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()), "dpm_solver_step")
@@ -1004,19 +998,23 @@ def distill_target(z_teacher, z_t, x_pred_teacher, logsnr, logsnr_s, i_times):
     return xt, et
 
 
-def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
-    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+def _adam_arenas(p, g, m, v, ema=None):
+    """The tensor checks of the three Adam ops: fp32 device arenas of one size (ema when given)."""
+    arenas = ((p, "p"), (g, "g"), (m, "m"), (v, "v")) + (() if ema is None else ((ema, "ema"),))
+    for t, nm in arenas:
         _f32(t, nm)
-    assert p.numel() == g.numel() == m.numel() == v.numel()
+    assert all(t.numel() == p.numel() for t, _ in arenas)
+
+
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
+    _adam_arenas(p, g, m, v)
     check(lib.gmk_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, step, grad_scale, _s()), "adam_step")
 
 
 def adam_ema_step(p, g, m, v, ema, lr, beta1, beta2, eps, step, decay_t, grad_scale=1.0):
     """adam_step, then ema.lerp_(p_new, 1 - decay_t) in the same pass over the arenas (gmk_adam_ema_step).  p, m, v come out the same bits as
     adam_step's."""
-    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
-        _f32(t, nm)
-    assert p.numel() == g.numel() == m.numel() == v.numel() == ema.numel()
+    _adam_arenas(p, g, m, v, ema)
     check(lib.gmk_adam_ema_step(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, step, grad_scale,
                                 1.0 - float(decay_t), _s()), "adam_ema_step")
 
@@ -1046,9 +1044,9 @@ def grad_norm(g, state, grad_scale=1.0, max_norm=0.0, workspace=None):
 def adam_step_ctl(p, g, m, v, state, lr, beta1, beta2, eps, step, grad_scale=1.0, ema=None, decay_t=0.0):
     """adam_step (ema None) or adam_ema_step on the gradient (g * grad_scale) * state[CLIP_COEF]; does nothing at all when state[APPLY] is 0
     (gmk_adam_step_ctl).  With a coefficient of 1 the bits of those two ops."""
-    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (state, "state")) + (() if ema is None else ((ema, "ema"),)):
-        _f32(t, nm)
-    assert p.numel() == g.numel() == m.numel() == v.numel() and state.numel() == 4 and (ema is None or ema.numel() == p.numel())
+    _adam_arenas(p, g, m, v, ema)
+    _f32(state, "state")
+    assert state.numel() == 4
     check(lib.gmk_adam_step_ctl(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, step, grad_scale,
                                 1.0 - float(decay_t), _p(state), _s()), "adam_step_ctl")
 

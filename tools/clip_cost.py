@@ -4,8 +4,9 @@ Adam alone, in the whole train step.
     python tools/clip_cost.py ab    [cfg2|bs32] [rounds=6] [steps=10]   same-process, interleaved step times, flags off vs
                                                                            --grad_clip 1.0 --skip_nonfinite 1
     python tools/clip_cost.py trace [cfg2|bs32] [steps=50]              `steps` train steps with the flags off, then `steps` with them on (to
-                                                                           run under rocprofv3 --kernel-trace --stats: adam_kernel next to
-                                                                           grad_norm_partial_kernel, grad_norm_final_kernel, adam_ctl_kernel)
+                                                                           run under rocprofv3 --kernel-trace --stats: adam_kernel<false, false>
+                                                                           next to grad_norm_partial_kernel, grad_norm_final_kernel and
+                                                                           adam_kernel<false, true> (<EMA, CTL>))
 cfg2: BASELINE configs[2] (3x32x32, bs = 2048, kernel-by-kernel step); bs32: 1x28x28, bs = 32 (the replayed-graph step).  Both print the
 arena size and the bytes each launch moves (4 B per parameter for the norm, 28 for either Adam), to turn kernel times into bandwidth.  The
 flags-off arm is the step as it was before the flags existed: no new kernel is launched in it."""
@@ -53,7 +54,7 @@ def main():
     x, y = batch(cfg)
     models = {arm: model(cfg, flags) for arm, flags in ARMS.items()}
     n = models["off"].net.flat_params.numel()
-    print(f"{cfg}: arena {n} floats; grad_norm_partial_kernel {4 * n / 1e6:.1f} MB, adam_kernel / adam_ctl_kernel {28 * n / 1e6:.1f} MB per launch",
+    print(f"{cfg}: arena {n} floats; grad_norm_partial_kernel {4 * n / 1e6:.1f} MB, adam_kernel<false, false> / adam_kernel<false, true> {28 * n / 1e6:.1f} MB per launch",
           flush=True)
     if mode == "trace":
         k = int(sys.argv[3]) if len(sys.argv) > 3 else 50

@@ -2,8 +2,8 @@
 
     python tools/ema_cost.py ab    [cfg2|bs32] [rounds=6] [steps=10]   same-process, interleaved step times, ema_decay 0 vs 0.9999
     python tools/ema_cost.py trace [cfg2|bs32] [steps=50]              `steps` train steps with EMA off, then `steps` with it on (to run
-                                                                          under rocprofv3 --kernel-trace --stats: adam_kernel and
-                                                                          adam_ema_kernel side by side)
+                                                                          under rocprofv3 --kernel-trace --stats: adam_kernel<false, false>
+                                                                          and adam_kernel<true, false> (<EMA, CTL>) side by side)
 cfg2: BASELINE configs[2] (3x32x32, bs = 2048, kernel-by-kernel step); bs32: 1x28x28, bs = 32 (the replayed-graph step).  Both print the
 arena size and the bytes each optimiser launch moves (28 / 36 B per parameter), to turn kernel times into bandwidth."""
 import statistics
@@ -48,7 +48,7 @@ def main():
     x, y = batch(cfg)
     models = {d: model(cfg, d) for d in (0.0, 0.9999)}
     n = models[0.0].net.flat_params.numel()
-    print(f"{cfg}: arena {n} floats; adam_kernel {28 * n / 1e6:.1f} MB, adam_ema_kernel {36 * n / 1e6:.1f} MB per launch", flush=True)
+    print(f"{cfg}: arena {n} floats; adam_kernel<false, false> {28 * n / 1e6:.1f} MB, adam_kernel<true, false> {36 * n / 1e6:.1f} MB per launch", flush=True)
     if mode == "trace":
         k = int(sys.argv[3]) if len(sys.argv) > 3 else 50
         for d, m in models.items():
