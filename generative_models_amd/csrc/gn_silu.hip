@@ -721,6 +721,343 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(XREG > 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Paired backward.  A down-path tensor t_k of the U-Net is normalised twice: as the input of a down ResBlock (GroupNorm(32, C)) and, with other
+// gamma / beta and other groups, as the skip half of an up ResBlock's input (GroupNorm(32, 2C)).  The paired kernel differentiates both from ONE
+// copy of x in LDS: the arithmetic and every reduction order are those of gn_silu_bwd_hybrid_kernel, so each output has the bits two launches give it.
+// ------------------------------------------------------------------------------------------------------
+struct GnFwdSide {          // one consumer of the shared x in the paired forward
+    void* y; const float* gamma; const float* beta; float* mean; float* rstd; int G;
+};
+
+// gn_silu_fwd_reg_kernel for the same two consumers: x is loaded once, its (s0, q0, s1, q1) partial sums are reduced once (they do not depend
+// on the group layout), then the group statistics and the apply sweep run once per consumer from the registers, in the single kernel's order:
+// y, mean and rstd of each consumer are the bits of its own gmk_gn_silu_fwd call.  HBM: 1 read + 2 writes instead of 2 + 2.
+// HW == ITER * planes and blockDim.x == planes * NVEC (the host checks): no pixel masks.  Only ITER = 4 (16 x 16) is instantiated: at ITER = 16
+// (32 x 32) the 64 resident registers plus a second consumer's sweep do not fit the 128 registers two workgroups per CU allow.
+template <typename T, int ITER, int NVEC>
+__global__ __launch_bounds__(1024) void gn_silu_fwd_pair_kernel(const T* __restrict__ x, const GnFwdSide sa, const GnFwdSide sb, int HW, int C,
+                                                              float eps, int B, int planes, const float* __restrict__ xadd, int xadd_stride) {
+    __shared__ float red[16][NVEC][4];      // [wave][vec][s0, q0, s1, q1]
+    __shared__ float smean[2][16], srstd[2][16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    constexpr int CS = NVEC * 8, LOGV = NVEC == 8 ? 3 : 2;
+    const int vec = tid & (NVEC - 1), pl = tid >> LOGV;
+    int b, slab;
+    slab_of_block(blockIdx.x, C / CS, B, b, slab);
+    const int c0 = slab * CS;
+    const size_t base = (size_t)b * HW * C + c0 + vec * 8;
+    const size_t estride = (size_t)planes * C;
+    u32x4_t raw[ITER];
+    {
+        size_t eoff = base + (size_t)pl * C;
+#pragma unroll
+        for (int i = 0; i < ITER; ++i, eoff += estride) {
+            asm volatile("" : "+v"(eoff));
+            raw[i] = *reinterpret_cast<const u32x4_t*>(x + eoff);
+        }
+    }
+    float ea[8];           // per-(sample, channel) addend applied to x on load, the same for both consumers
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ea[k] = xadd ? xadd[(size_t)b * xadd_stride + c0 + vec * 8 + k] : 0.f;
+    float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < ITER; ++i) {
+        float v[8];
+        unpack8<T>(raw[i], v);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = v[k] + ea[k];
+        s0 += (v[0] + v[1]) + (v[2] + v[3]);
+        q0 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+        s1 += (v[4] + v[5]) + (v[6] + v[7]);
+        q1 += (v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7]);
+    }
+#pragma unroll
+    for (int i = 0; i < ITER; ++i) asm volatile("" : "+v"(raw[i]));       // stay packed across the reduction (see gn_silu_fwd_reg_kernel)
+    s0 = vec_lane_sum<NVEC>(s0); q0 = vec_lane_sum<NVEC>(q0); s1 = vec_lane_sum<NVEC>(s1); q1 = vec_lane_sum<NVEC>(q1);
+    if (lane < NVEC) { red[wave][lane][0] = s0; red[wave][lane][1] = q0; red[wave][lane][2] = s1; red[wave][lane][3] = q1; }
+    __syncthreads();
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+        const GnFwdSide& sd = side ? sb : sa;
+        const int cpg = C / sd.G, g0 = c0 / cpg, gps = CS / cpg;
+        if (tid < gps) {
+            const int hv_per_g = cpg >> 2;          // 4-channel half-vectors per group
+            float s = 0.f, q = 0.f;
+            for (int j = 0; j < hv_per_g; ++j) {
+                const int hv = tid * hv_per_g + j, vv = hv >> 1, hf = hv & 1;
+                for (int w = 0; w < nwaves; ++w) { s += red[w][vv][hf * 2]; q += red[w][vv][hf * 2 + 1]; }
+            }
+            const float n = (float)cpg * (float)HW;
+            const float m = s / n;
+            const float var = fmaxf(q / n - m * m, 0.f);
+            const float r = 1.0f / sqrtf(var + eps);
+            smean[side][tid] = m; srstd[side][tid] = r;
+            sd.mean[b * sd.G + g0 + tid] = m; sd.rstd[b * sd.G + g0 + tid] = r;
+        }
+    }
+    __syncthreads();
+    // one apply sweep per consumer, not interleaved: one (scale, shift) set live at a time
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+        const GnFwdSide& sd = side ? sb : sa;
+        const int cpg = C / sd.G;
+        T* y = (T*)sd.y;
+#pragma unroll
+        for (int i = 0; i < ITER; ++i) asm volatile("" : "+v"(raw[i]));       // (or the first consumer's unpacked floats are kept for the second: 8 * ITER registers)
+        float sc[8], sh[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int cl = vec * 8 + i, g = cl / cpg, c = c0 + cl;
+            sc[i] = srstd[side][g] * sd.gamma[c];
+            sh[i] = sd.beta[c] - (smean[side][g] - ea[i]) * sc[i];          // (x + ea - mean) * sc + beta
+        }
+        size_t eoff = base + (size_t)pl * C;
+#pragma unroll
+        for (int i = 0; i < ITER; ++i, eoff += estride) {
+            asm volatile("" : "+v"(eoff));
+            float v[8];
+            unpack8<T>(raw[i], v);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = siluf_(fmaf(v[k], sc[k], sh[k]));
+            store8(y + eoff, v);
+        }
+    }
+}
+
+struct GnBwdSide {          // one consumer of the shared x in the paired backward: its output gradient, its gradient addend, its GroupNorm
+    const bf16_t* dy; const bf16_t* dadd; const float* gamma; const float* beta; const float* mean; const float* rstd;
+    float* dgp; float* dbp; int G;
+};
+
+// gn_silu_bwd_hybrid_kernel for both consumers of x, one workgroup = one (sample, 32-channel slab), x parked in LDS ONCE:
+//   phase A (the up block's GroupNorm over the skip half): ds = bf16(GNbwd_up(dy_up) + dadd_up) - the tensor the two-launch form writes to
+//           HBM and reads back - takes the place of dy_up in the registers, rounded where the stored one is rounded;
+//   phase B (the down block's GroupNorm): dx = GNbwd_dn(dy_dn) + dadd_dn + ds, today's kernel with its second addend in registers.
+// Same thread -> pixel mapping, accumulation and reduction order as the single kernel at this (ITER, THREADS), so dx, both dgamma / dbeta
+// partials and dxsum are the bits of the two launches.  HW == ITER * THREADS / 4 exactly (no pixel masks); both sweeps of both phases are
+// software-pipelined like the EXACT form above.  KEEPB: iterations of dy_dn that stay in registers between phase B's sweeps (the rest is
+// read again in its second sweep).
+template <typename TX, int ITER, int THREADS, int KEEPB, int WMIN, int WMAX>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WMIN, WMAX))) void gn_silu_bwd_pair_kernel(
+    const TX* __restrict__ x, const GnBwdSide up, const GnBwdSide dn, bf16_t* __restrict__ dx, float* __restrict__ dxsum, int dxsum_stride,
+    int HW, int C, int B, const float* __restrict__ xadd, int xadd_stride) {
+    static_assert(ITER % 2 == 0 && KEEPB <= ITER, "pixel pairs");
+    constexpr int NVEC = 4, CS = NVEC * 8, NW = THREADS / 64, PL = THREADS / NVEC, N2 = ITER / 2;
+    extern __shared__ __attribute__((aligned(16))) char xs_lds[];        // [HW][NVEC] x 16 B
+    __shared__ float red[NW][NVEC][16];
+    __shared__ float chg[CS], chb[CS];
+    __shared__ float sA[8], sB[8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int vec = tid & (NVEC - 1), pl = tid / NVEC;
+    int b, slab;
+    slab_of_block(blockIdx.x, C / CS, B, b, slab);
+    const int c0 = slab * CS;
+    const size_t base = (size_t)b * HW * C + c0 + vec * 8;
+    const size_t estride = (size_t)PL * C;
+    constexpr float kNegLog2e = -1.4426950408889634f;
+    u32x4_t dr[ITER];                       // phase A: dy_up, then ds (packed bf16)
+    u32x4_t dk[KEEPB > 0 ? KEEPB : 1];      // phase B: the kept part of dy_dn
+    float xs[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) xs[k] = 0.f;
+#pragma unroll
+    for (int ph = 0; ph < 2; ++ph) {
+        const GnBwdSide& sd = ph ? dn : up;
+        // (opaque per phase: otherwise phase B's per-channel constants are loaded at the top of the kernel and held through phase A - 24 registers)
+        int bq = b;
+        asm volatile("" : "+s"(bq));
+        const int G = sd.G, cpg = C / G, g0 = c0 / cpg, gps = CS / cpg;
+        const int glo = (vec * 8) / cpg, ghi = (vec * 8 + 4) / cpg;
+        const float rs0 = sd.rstd[bq * G + g0 + glo], rs1 = sd.rstd[bq * G + g0 + ghi];
+        f32x2_t sv[4], tv[4], muv[4];           // the per-channel constants of gn_silu_bwd_hybrid_kernel
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int k = 2 * jj + e, c = c0 + vec * 8 + k;
+                const float m = sd.mean[bq * G + g0 + (k < 4 ? glo : ghi)] - (xadd ? xadd[(size_t)bq * xadd_stride + c] : 0.f);
+                const float sc = (k < 4 ? rs0 : rs1) * sd.gamma[c];
+                muv[jj][e] = m; sv[jj][e] = sc; tv[jj][e] = sd.beta[c] - m * sc;
+            }
+        }
+        f32x2_t ax[4], ab[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) { ax[jj] = f32x2_t{0.f, 0.f}; ab[jj] = f32x2_t{0.f, 0.f}; }
+        size_t eoff = base + (size_t)pl * C;
+        uint32_t loff = ((uint32_t)pl * NVEC + vec) * 16;
+        {
+            // first sweep: the loads of pixel pair c + 1 in flight under the arithmetic of pair c.  Phase A brings x in and parks it.
+            u32x4_t xr[2][2], dq[2][2];
+#pragma unroll
+            for (int c = 0; c < N2 + 1; ++c) {
+                if (c < N2) {
+                    asm volatile("" : "+v"(eoff));
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        if (ph == 0) xr[c & 1][u] = *reinterpret_cast<const u32x4_t*>(x + eoff + u * estride);
+                        dq[c & 1][u] = *reinterpret_cast<const u32x4_t*>(sd.dy + eoff + u * estride);
+                    }
+                    eoff += 2 * estride;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (c >= 1) {
+                    const int cc = c - 1;
+                    asm volatile("" : "+v"(loff));
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const int i = cc * 2 + u;
+                        u32x4_t xq;
+                        if (ph == 0) {
+                            xq = xr[cc & 1][u];
+                            *reinterpret_cast<u32x4_t*>(xs_lds + loff + u * (PL * NVEC * 16)) = xq;
+                        } else {
+                            xq = *reinterpret_cast<const u32x4_t*>(xs_lds + loff + u * (PL * NVEC * 16));
+                        }
+                        const u32x4_t dv4 = dq[cc & 1][u];
+                        if (ph == 0) dr[i] = dv4;
+                        else if (i < KEEPB) dk[i < KEEPB ? i : 0] = dv4;
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj) {
+                            const f32x2_t xv = unpack2<TX>(xq[jj]), dv = unpack2<bf16_t>(dv4[jj]);
+                            const f32x2_t dg = silu_grad2(xv, dv, sv[jj], tv[jj], kNegLog2e);
+                            ax[jj] = __builtin_elementwise_fma(dg, xv, ax[jj]);
+                            ab[jj] += dg;
+                        }
+                    }
+                    loff += 2 * PL * NVEC * 16;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < ITER; ++i) asm volatile("" : "+v"(dr[i]));          // stay packed across the reduction
+        if (ph == 1) {
+#pragma unroll
+            for (int i = 0; i < KEEPB; ++i) asm volatile("" : "+v"(dk[i]));
+        }
+        float ag[8], abk[8];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int k = 2 * jj + e;
+                abk[k] = ab[jj][e];
+                ag[k] = (ax[jj][e] - muv[jj][e] * ab[jj][e]) * (k < 4 ? rs0 : rs1);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { ag[k] = vec_lane_sum<NVEC>(ag[k]); abk[k] = vec_lane_sum<NVEC>(abk[k]); }
+        if (lane < NVEC) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { red[wave][lane][k] = ag[k]; red[wave][lane][8 + k] = abk[k]; }
+        }
+        __syncthreads();
+        if (tid < CS) {
+            const int vv = tid >> 3, k = tid & 7;
+            float a = 0.f, bb = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) { a += red[w][vv][k]; bb += red[w][vv][8 + k]; }
+            chg[tid] = a; chb[tid] = bb;
+            sd.dgp[(size_t)b * C + c0 + tid] = a;
+            sd.dbp[(size_t)b * C + c0 + tid] = bb;
+        }
+        __syncthreads();
+        if (tid < gps) {
+            float A = 0.f, Bq = 0.f;
+            for (int j = 0; j < cpg; ++j) {
+                const int cl = tid * cpg + j;
+                A = fmaf(sd.gamma[c0 + cl], chb[cl], A);
+                Bq = fmaf(sd.gamma[c0 + cl], chg[cl], Bq);
+            }
+            const float inv_n = 1.f / ((float)cpg * (float)HW);
+            sA[tid] = A * inv_n; sB[tid] = Bq * inv_n;
+        }
+        __syncthreads();
+        f32x2_t npv[4], qv[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const float rsk = jj < 2 ? rs0 : rs1, cA = jj < 2 ? sA[glo] : sA[ghi], cB = jj < 2 ? sB[glo] : sB[ghi];
+            const float r2b = rsk * rsk * cB;
+            npv[jj] = f32x2_t{-r2b, -r2b};
+            qv[jj] = muv[jj] * r2b - rsk * cA;
+        }
+        eoff = base + (size_t)pl * C;
+        loff = ((uint32_t)pl * NVEC + vec) * 16;
+        {
+            // second sweep: phase A turns dr from dy_up into ds; phase B writes dx
+            u32x4_t a1[2][2], dq2[2][2];
+            size_t lo = eoff;
+#pragma unroll
+            for (int c = 0; c < N2 + 1; ++c) {
+                if (c < N2) {
+                    asm volatile("" : "+v"(lo));
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const int i = 2 * c + u;
+                        if (ph == 1 && i >= KEEPB) dq2[c & 1][u] = *reinterpret_cast<const u32x4_t*>(sd.dy + lo + u * estride);
+                        a1[c & 1][u] = *reinterpret_cast<const u32x4_t*>(sd.dadd + lo + u * estride);
+                    }
+                    lo += 2 * estride;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (c >= 1) {
+                    const int cc = c - 1;
+                    asm volatile("" : "+v"(eoff), "+v"(loff));
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const int i = 2 * cc + u;
+                        const u32x4_t xq = *reinterpret_cast<const u32x4_t*>(xs_lds + loff + u * (PL * NVEC * 16));
+                        const u32x4_t dv4 = ph == 0 ? dr[i] : i < KEEPB ? dk[i < KEEPB ? i : 0] : dq2[cc & 1][u];
+                        u32x4_t ow;
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj) {
+                            const f32x2_t xv = unpack2<TX>(xq[jj]), dv = unpack2<bf16_t>(dv4[jj]);
+                            const f32x2_t dg = silu_grad2(xv, dv, sv[jj], tv[jj], kNegLog2e);
+                            f32x2_t ov = __builtin_elementwise_fma(dg, sv[jj], __builtin_elementwise_fma(xv, npv[jj], qv[jj]));
+                            ov += unpack2<bf16_t>(a1[cc & 1][u][jj]);
+                            if (ph == 1) {
+                                ov += unpack2<bf16_t>(dr[i][jj]);
+                                xs[2 * jj] += ov[0]; xs[2 * jj + 1] += ov[1];
+                            }
+                            ow[jj] = pack_pair<bf16_t>(ov[0], ov[1]);
+                        }
+                        if (ph == 0) {
+                            dr[i] = ow;
+                            asm volatile("" : "+v"(dr[i]));      // pins the arithmetic here, as the store does in phase B (nothing else orders it before phase B's second sweep)
+                        } else {
+                            *reinterpret_cast<u32x4_t*>(dx + eoff + u * estride) = ow;
+                        }
+                    }
+                    if (ph == 1) {
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) asm volatile("" : "+v"(xs[k]));    // (or the adds are sunk into the `if (dxsum)` below)
+                    }
+                    eoff += 2 * estride; loff += 2 * PL * NVEC * 16;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    }
+    if (dxsum) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) xs[k] = vec_lane_sum<NVEC>(xs[k]);
+        __syncthreads();   // red is re-used
+        if (lane < NVEC) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) red[wave][lane][k] = xs[k];
+        }
+        __syncthreads();
+        if (tid < CS) {
+            const int vv = tid >> 3, k = tid & 7;
+            float a = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) a += red[w][vv][k];
+            dxsum[(size_t)b * dxsum_stride + c0 + tid] = a;
+        }
+    }
+}
+
 // pixels per thread of the register-resident kernels: the smallest of 1, 2, 4, 8 that fits the slab into <= 512 threads
 int gn_reg_iter(int HW, int nvec) {
     // 28 x 28 (784 pixels; round 4): 16 pixels per thread leave 49 planes x 8 = 392 of 448 threads busy (4.05 TB/s against 4.65 at 32 x 32, same batch);
@@ -1120,6 +1457,74 @@ extern "C" int gmk_gn_silu_bwd(const void* dy, const void* x, const float* gamma
     else
         GMK_REQUIRE(false, "gmk_gn_silu_bwd: bad dtype %d", dtype);
     return gmk_check_launch("gmk_gn_silu_bwd");
+}
+
+// The shapes the paired backward takes: those where gmk_gn_silu_bwd runs the hybrid kernel without pixel masks (32 x 32 and 16 x 16), bf16
+// gradients beside 16-bit activations, groups of 4, 8 or 16 channels.
+extern "C" int gmk_gn_pair_ok(int HW, int C, int groups_a, int groups_b, int x_dtype, int grad_dtype) {
+    if (!gmk_is16(x_dtype) || grad_dtype != GMK_BF16 || gmk_kernel_choice(2, "GMK_GN_KERNEL") != 0) return 0;
+    if (C <= 0 || C > 256 || C % 32 || (HW != 1024 && HW != 256)) return 0;
+    for (int G : {groups_a, groups_b})
+        if (!gn_shape_ok(C, G) || gn_narrow(C, G) || 32 % (C / G)) return 0;
+    return 1;
+}
+
+// The paired forward: where gmk_gn_silu_fwd runs the register kernel on 64-channel slabs at 4 pixels per thread (16 x 16).
+extern "C" int gmk_gn_pair_fwd_ok(int HW, int C, int groups_a, int groups_b, int dtype) {
+    if (!gmk_is16(dtype) || gmk_kernel_choice(2, "GMK_GN_KERNEL") != 0) return 0;
+    if (C <= 0 || C > 256 || C % 64 || HW != 256) return 0;
+    for (int G : {groups_a, groups_b})
+        if (!gn_shape_ok(C, G) || gn_narrow(C, G) || 32 % (C / G)) return 0;
+    return 1;
+}
+
+extern "C" int gmk_gn_silu_fwd_pair(const void* x, void* y_a, void* y_b, const float* gamma_a, const float* beta_a, const float* gamma_b,
+                                    const float* beta_b, float* mean_a, float* rstd_a, float* mean_b, float* rstd_b, int B, int HW, int C,
+                                    int groups_a, int groups_b, float eps, const float* xadd, int xadd_stride, int dtype, void* stream) {
+    GMK_REQUIRE(x && y_a && y_b && gamma_a && beta_a && gamma_b && beta_b && mean_a && rstd_a && mean_b && rstd_b,
+                "gmk_gn_silu_fwd_pair: null pointer");
+    GMK_REQUIRE(!xadd || xadd_stride >= C, "gmk_gn_silu_fwd_pair: xadd_stride %d < C %d", xadd_stride, C);
+    GMK_REQUIRE(B > 0 && gmk_gn_pair_fwd_ok(HW, C, groups_a, groups_b, dtype),
+                "gmk_gn_silu_fwd_pair: unsupported shape B=%d HW=%d C=%d G=%d,%d dtype=%d (gmk_gn_pair_fwd_ok)", B, HW, C, groups_a, groups_b, dtype);
+    const int it = gn_reg_iter(HW, 8), planes = HW / it, threads = planes * 8, nblk = B * (C / 64);      // as gmk_gn_silu_fwd chooses: 4, 64, 512
+    GMK_REQUIRE(it == 4 && threads == 512, "gmk_gn_silu_fwd_pair: internal: %d pixels per thread, %d threads", it, threads);
+    const GnFwdSide sa = {y_a, gamma_a, beta_a, mean_a, rstd_a, groups_a}, sb = {y_b, gamma_b, beta_b, mean_b, rstd_b, groups_b};
+    gmk_note_kernel(26);
+    if (dtype == GMK_F16)
+        gn_silu_fwd_pair_kernel<f16_t, 4, 8><<<nblk, threads, 0, gmk_stream(stream)>>>((const f16_t*)x, sa, sb, HW, C, eps, B, planes, xadd, xadd_stride);
+    else
+        gn_silu_fwd_pair_kernel<bf16_t, 4, 8><<<nblk, threads, 0, gmk_stream(stream)>>>((const bf16_t*)x, sa, sb, HW, C, eps, B, planes, xadd, xadd_stride);
+    return gmk_check_launch("gmk_gn_silu_fwd_pair");
+}
+
+extern "C" int gmk_gn_silu_bwd_pair(const void* x, const void* dy_up, const void* dadd_up, const float* gamma_up, const float* beta_up,
+                                    const float* mean_up, const float* rstd_up, float* dgamma_part_up, float* dbeta_part_up, int groups_up,
+                                    const void* dy_dn, const void* dadd_dn, const float* gamma_dn, const float* beta_dn, const float* mean_dn,
+                                    const float* rstd_dn, float* dgamma_part_dn, float* dbeta_part_dn, int groups_dn, void* dx, float* dxsum,
+                                    int dxsum_stride, int B, int HW, int C, const float* xadd, int xadd_stride, int x_dtype, void* stream) {
+    GMK_REQUIRE(x && dy_up && dadd_up && dadd_dn && gamma_up && beta_up && mean_up && rstd_up && dgamma_part_up && dbeta_part_up && dy_dn && gamma_dn && beta_dn &&
+                    mean_dn && rstd_dn && dgamma_part_dn && dbeta_part_dn && dx,
+                "gmk_gn_silu_bwd_pair: null pointer");
+    GMK_REQUIRE(!xadd || xadd_stride >= C, "gmk_gn_silu_bwd_pair: xadd_stride %d < C %d", xadd_stride, C);
+    GMK_REQUIRE(!dxsum || dxsum_stride >= C, "gmk_gn_silu_bwd_pair: dxsum_stride %d < C %d", dxsum_stride, C);
+    GMK_REQUIRE(B > 0 && gmk_gn_pair_ok(HW, C, groups_up, groups_dn, x_dtype, GMK_BF16),
+                "gmk_gn_silu_bwd_pair: unsupported shape B=%d HW=%d C=%d G=%d,%d x_dtype=%d (gmk_gn_pair_ok)", B, HW, C, groups_up, groups_dn,
+                x_dtype);
+    const GnBwdSide up = {(const bf16_t*)dy_up, (const bf16_t*)dadd_up, gamma_up, beta_up, mean_up, rstd_up, dgamma_part_up, dbeta_part_up, groups_up};
+    const GnBwdSide dn = {(const bf16_t*)dy_dn, (const bf16_t*)dadd_dn, gamma_dn, beta_dn, mean_dn, rstd_dn, dgamma_part_dn, dbeta_part_dn, groups_dn};
+    const size_t lds = (size_t)HW * 64;
+    const int nblk = B * (C / 32);
+    const bool xf16 = x_dtype == GMK_F16;
+    gmk_note_kernel(25);
+#define GMK_GN_BWD_PAIR(TT, IT, TH, KB, W0, W1)                                                                                          \
+    gn_silu_bwd_pair_kernel<TT, IT, TH, KB, W0, W1><<<nblk, TH, lds, gmk_stream(stream)>>>((const TT*)x, up, dn, (bf16_t*)dx, dxsum,        \
+                                                                                       dxsum_stride, HW, C, B, xadd, xadd_stride)
+    // 32 x 32: dy_dn is read again in phase B's second sweep (7 tensor passes) so that ds + the pipeline buffers fit 128 registers and two
+    // workgroups share a CU like the single kernel's; keeping it resident (6 passes, 141 registers, one workgroup per CU) measured 9 % slower.
+    if (HW == 1024) { if (xf16) GMK_GN_BWD_PAIR(f16_t, 8, 512, 0, 4, 4); else GMK_GN_BWD_PAIR(bf16_t, 8, 512, 0, 4, 4); }
+    else { if (xf16) GMK_GN_BWD_PAIR(f16_t, 4, 256, 4, 3, 4); else GMK_GN_BWD_PAIR(bf16_t, 4, 256, 4, 3, 4); }
+#undef GMK_GN_BWD_PAIR
+    return gmk_check_launch("gmk_gn_silu_bwd_pair");
 }
 
 extern "C" int gmk_cast16(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream) {

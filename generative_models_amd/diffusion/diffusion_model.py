@@ -199,7 +199,7 @@ def make_plugin(GMBase, AttrDict):
                 return self._train_step_graphed(x, y)
             try:
                 out = self.diffusion.train_forward_backward(net=partial(self.net, guide=y), x=x, grad_scale=1.0 / B,
-                                                            on_grads_ready=self._sync.hook, join_side_before_ready=False)
+                                                            on_grads_ready=self._sync.hook if parallel.exchanging() else None, join_side_before_ready=False)
             except BaseException:
                 self._sync.abort()                  # a raise between hook() and finish() must not leave the process on the carved CU limit
                 raise
@@ -239,7 +239,7 @@ def make_plugin(GMBase, AttrDict):
                 ops.WGRAD_STREAM, self.net._side = side_was and os.environ.get("GMK_TRAIN_GRAPH_SIDE", "0") == "1", None
                 try:
                     run = lambda: self.diffusion.train_forward_backward(net=partial(self.net, guide=ys), x=xs, grad_scale=1.0 / B, u=us, eps=es,
-                                                                        on_grads_ready=self._sync.hook, join_side_before_ready=False)
+                                                                        on_grads_ready=self._sync.hook if parallel.exchanging() else None, join_side_before_ready=False)
                     warm = torch.cuda.Stream(device=dev)        # warm-up off the capture: packs, workspaces, allocator pools (gradients only)
                     warm.wait_stream(torch.cuda.current_stream())
                     with torch.cuda.stream(warm):

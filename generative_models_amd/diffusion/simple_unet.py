@@ -114,6 +114,19 @@ def _attach(root, dotted, param):
     mod.register_parameter(parts[-1], param)
 
 
+# down ResBlock -> the up ResBlock whose skip half normalises the same input tensor (t0, t1, t3, t4 of forward_hip)
+_SKIP_CONSUMER = {"down.seq.1": "up.seq.6", "down.seq.2": "up.seq.5", "down.seq.4": "up.seq.3.0", "down.seq.5": "up.seq.2"}
+
+
+class _DeferredGN:
+    """The GroupNorm backward of an up block's skip half, not yet run: x (the shared down-path tensor), gn = (dy, dadd, gamma, beta, mean, rstd),
+    and the gradient slices (gw, gb) its dgamma / dbeta partials reduce into (SimpleUnet._res_bwd)."""
+    __slots__ = ("x", "gn", "gw", "gb")
+
+    def __init__(self, x, gn, gw, gb):
+        self.x, self.gn, self.gw, self.gb = x, gn, gw, gb
+
+
 class SimpleUnet(nn.Module):
     def __init__(self, channels, dropout=0.0, in_channels=1, compute_dtype=torch.bfloat16, attention=False, act_dtype=None):
         super().__init__()
@@ -502,10 +515,20 @@ class SimpleUnet(nn.Module):
                 res = srcs[0]
             return self._conv([h], wf2, C, 3, ops.NORMAL, (H, W), bias=P[f"{name}.out_layers.3.bias"], residual=res, gn=(t2c, t2h))
         a, stats1 = [], []
+        ahead = ctx.setdefault("gn_fwd_pair", {}) if ctx is not None else {}      # up block name -> (x, y, mean, rstd) its skip half got from the down block
         for i, s in enumerate(srcs):
             g = P[f"{name}.in_layers.0.weight"][i * C:(i + 1) * C]
             b = P[f"{name}.in_layers.0.bias"][i * C:(i + 1) * C]
-            y, mean, rstd = ops.gn_silu_fwd(s, g, b, gpc)
+            up = _SKIP_CONSUMER.get(name)
+            if i == 1 and name in ahead and ahead[name][0] is s:
+                _, y, mean, rstd = ahead.pop(name)
+            elif ctx is not None and up is not None and C == 128 and not self._narrow and ops.gn_pair_fwd_ok(s, gpc, self._g2):
+                # this tensor is also the skip half of `up`'s input: both GroupNorms from one read of it (bit-identical to the two launches)
+                (y, mean, rstd), second = ops.gn_silu_fwd_pair(s, (g, b, gpc), (P[f"{up}.in_layers.0.weight"][C:2 * C],
+                                                                                P[f"{up}.in_layers.0.bias"][C:2 * C], self._g2))
+                ahead[up] = (s,) + second
+            else:
+                y, mean, rstd = ops.gn_silu_fwd(s, g, b, gpc)
             a.append(y); stats1.append((mean, rstd))
         h = self._conv(a, wf1, C, 3, ops.NORMAL, (H, W))      # bias + embedding enter through `xadd` below
         drop = None
@@ -650,11 +673,16 @@ class SimpleUnet(nn.Module):
         if self._side is not None:
             torch.cuda.current_stream().wait_stream(self._side)
 
-    def _res_bwd(self, name, ctx, dout, dout_sum, demb_all, blk, extra_add=None, grads=True):
+    def _res_bwd(self, name, ctx, dout, dout_sum, demb_all, blk, extra_add=None, grads=True, defer_skip=False):
         """dout: gradient of the block output (NHWC); dout_sum: its per-sample channel sums [B, C].
         extra_add: per-source optional extra gradient tensors added into the returned source gradients.
         grads=False: the data gradient only (input_vjp_hip) - no weight, bias or embedding gradient, no channel sums (dout_sum / demb_all
         unused, None returned for dsrc_sum).
+        defer_skip (an up block whose skip source is a down ResBlock's input): where ops.gn_pair_ok takes the shape, the GroupNorm backward of
+        the skip half is NOT run; its operands are returned as a _DeferredGN in place of the gradient tensor, and the down block that receives it as
+        extra_add runs both GroupNorm backward passes over the shared tensor as one launch (ops.gn_silu_bwd_pair, bit-identical).
+        Until then the record keeps this block's (da, dskip) alive instead of the one tensor ds (dskip may pin conv1x1_pair's second output): about
+        + 1.3 GB of peak memory at B = 2048, 32 x 32 over the four paired tensors.
         Returns [(dsrc, dsrc_sum)] per source."""
         P, G, C = self._pv, self._gv, self.channels
         srcs, a, stats1, h, a2, (mean2, rstd2) = ctx.pop(name)
@@ -692,10 +720,18 @@ class SimpleUnet(nn.Module):
             da = self._conv([dh], wd1, len(srcs) * C, 3, ops.NORMAL, (H, W), n0=i * C)
             dskip = dskips[i]
             add2 = extra_add[i] if extra_add is not None else None
+            gn = (da, dskip, P[f"{name}.in_layers.0.weight"][i * C:(i + 1) * C], P[f"{name}.in_layers.0.bias"][i * C:(i + 1) * C],
+                  stats1[i][0], stats1[i][1])
+            if defer_skip and i == 1 and grads and C == 128 and not self._narrow and ops.gn_pair_ok(s, self._g2, self._g1, da.dtype):
+                outs.append((_DeferredGN(s, gn, gw[C:2 * C], gb[C:2 * C]), None))
+                continue
             ssum = torch.empty((B, C), device=dout.device, dtype=torch.float32) if grads else None
-            ds, dgp, dbp = ops.gn_silu_bwd(da, s, P[f"{name}.in_layers.0.weight"][i * C:(i + 1) * C],
-                                           P[f"{name}.in_layers.0.bias"][i * C:(i + 1) * C], stats1[i][0], stats1[i][1],
-                                           dadd1=dskip, dadd2=add2, dxsum=ssum)
+            if isinstance(add2, _DeferredGN):
+                assert add2.x is s
+                ds, (ugp, ubp), (dgp, dbp) = ops.gn_silu_bwd_pair(s, add2.gn, gn, dxsum=ssum)
+                ops.colsum(ugp, add2.gw, defer=True); ops.colsum(ubp, add2.gb, defer=True)
+            else:
+                ds, dgp, dbp = ops.gn_silu_bwd(da, s, *gn[2:], dadd1=dskip, dadd2=add2, dxsum=ssum)
             if grads:
                 ops.colsum(dgp, gw[i * C:(i + 1) * C], defer=True); ops.colsum(dbp, gb[i * C:(i + 1) * C], defer=True)
             outs.append((ds, ssum))
@@ -788,7 +824,11 @@ class SimpleUnet(nn.Module):
         all-reduce).  A bucket is final only when the side stream's weight gradients are: with join_side_before_ready the current stream
         joins the side stream in front of every callback (a callback may then read the bucket in current-stream order); a consumer
         that orders its own stream behind BOTH streams (parallel.GradSync: the all-reduce runs on a third stream) passes False, and
-        the data-gradient chain on the current stream never waits for the weight gradients."""
+        the data-gradient chain on the current stream never waits for the weight gradients.
+        The callback also decides which GroupNorm backward kernels run: WITHOUT one, the up blocks over t0, t1, t3, t4 defer their skip half's
+        GroupNorm backward to the matching down block (one paired launch, ops.gn_silu_bwd_pair; same bits), which writes those in_layers.0
+        gradient slices only at the end of the pass - later than ready(0) / ready(1) promise.  WITH one, even a no-op, every block keeps its two
+        launches."""
         if ops.WGRAD_CUS > 0 and ops.WGRAD_STREAM and dout.is_cuda and self._cu_part is None and not (
                 torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1):
             full = ops.get_cu_limit()
@@ -799,9 +839,8 @@ class SimpleUnet(nn.Module):
             finally:
                 ops.set_cu_limit(full)
                 self._cu_part = None
-        ready = on_grads_ready if on_grads_ready is not None else (lambda k: None)
-        join = self._join_side if (on_grads_ready is not None and join_side_before_ready) else (lambda: None)
-        dt0 = self._backward_schedule(ctx, ops.aligned(dout.float()), True, ready, join)
+        join = self._join_side if (on_grads_ready is not None and join_side_before_ready) else None
+        dt0 = self._backward_schedule(ctx, ops.aligned(dout.float()), True, on_grads_ready, join)
         return ops.stem_dgrad(dt0, self._pv["down.seq.0.conv.weight"]) if want_dx else None
 
     def input_vjp_hip(self, ctx, r):
@@ -826,7 +865,14 @@ class SimpleUnet(nn.Module):
         x, t2, t5, u0r, u3r, u6, ao, mo, ro = ctx["net"]
         dev = dout.device
         demb_all = torch.empty((B, 12 * C), device=dev, dtype=torch.float32) if grads else None
-        res = lambda name, d, dsum, blk, extra=None: self._res_bwd(name, ctx, d, dsum, demb_all, blk, extra_add=extra, grads=grads)
+        # The up blocks whose skip source feeds a down ResBlock (t0, t1, t3, t4) leave their skip half's GroupNorm backward to that block (one
+        # launch for both, _res_bwd defer_skip).  That moves their in_layers.0 gradients [C:2C] to the end of the pass, behind ready(0) / ready(1):
+        # only without a gradient exchange (no on_grads_ready).
+        pair = grads and ready is None
+        ready = ready if ready is not None else (lambda k: None)
+        join = join if join is not None else (lambda: None)
+        res = lambda name, d, dsum, blk, extra=None, defer=False: self._res_bwd(name, ctx, d, dsum, demb_all, blk, extra_add=extra, grads=grads,
+                                                                               defer_skip=defer and pair)
 
         def bucket_done(k):
             if grads:
@@ -859,13 +905,13 @@ class SimpleUnet(nn.Module):
         if grads:
             ops.colsum(dgp, G["out.0.weight"], defer=True); ops.colsum(dbp, G["out.0.bias"], defer=True)
 
-        (du5, s5), (dt0a, _) = res("up.seq.6", du6, s6, 11)
-        (du4, s4), (dt1a, _) = res("up.seq.5", du5, s5, 10)
+        (du5, s5), (dt0a, _) = res("up.seq.6", du6, s6, 11, defer=True)
+        (du4, s4), (dt1a, _) = res("up.seq.5", du5, s5, 10, defer=True)
         (du3, s3), (dt2a, _) = res("up.seq.4", du4, s4, 9)
         bucket_done(0)
         du3r, s3r = up("up.seq.3.1.conv", du3, s3, u3r)
-        (du2, s2), (dt3a, _) = res("up.seq.3.0", du3r, s3r, 8)
-        (du1, s1), (dt4a, _) = res("up.seq.2", du2, s2, 7)
+        (du2, s2), (dt3a, _) = res("up.seq.3.0", du3r, s3r, 8, defer=True)
+        (du1, s1), (dt4a, _) = res("up.seq.2", du2, s2, 7, defer=True)
         (du0, s0), (dt5a, _) = res("up.seq.1", du1, s1, 6)
         du0r, s0r = up("up.seq.0.1.conv", du0, s0, u0r)
         (dt7, s7), (dt6a, _) = res("up.seq.0.0", du0r, s0r, 5)

@@ -38,7 +38,8 @@ KERNEL_NAMES = {1: "conv_igemm_kernel", 2: "conv_igemm_dma_kernel", 3: "conv3x3_
                 # the slot weight-gradient kernel on the four parity planes of a stride-2 convolution's input (round 6): its own line (4 - 16 MFMAs per step, not 36)
                 17: "conv_wgrad_slots_ws_kernel[stride-2 planes]",
                 8: "conv_subpixel_ws_kernel[upsample]", 9: "conv_subpixel_ws_kernel[transposed]", 10: "conv_subpixel_ws_kernel[upsample dgrad]",
-                21: "gn_silu_fwd_reg_kernel", 22: "gn_silu_fwd_kernel", 23: "gn_silu_bwd_hybrid_kernel", 24: "gn_silu_bwd_kernel"}
+                21: "gn_silu_fwd_reg_kernel", 22: "gn_silu_fwd_kernel", 23: "gn_silu_bwd_hybrid_kernel", 24: "gn_silu_bwd_kernel",
+                25: "gn_silu_bwd_pair_kernel", 26: "gn_silu_fwd_pair_kernel"}
 
 
 def instantiation_key(name, dtype):
@@ -210,6 +211,10 @@ EMB_SIDE = os.environ.get("GMK_EMB_SIDE", "1") == "1"          # the embedding p
 FWD_SIDE = os.environ.get("GMK_FWD_SIDE", "0") == "1"          # forward 1x1 skip convolutions on the side stream (simple_unet._res_fwd)
 WGRAD_CUS = int(os.environ.get("GMK_WGRAD_CUS", "0"))           # > 0: the side stream's persistent grids take this many CUs, the data-gradient chain's the rest
 WGRAD_STREAM = os.environ.get("GMK_WGRAD_STREAM", "1") != "0"    # weight gradients on a side stream beside the data-gradient chain (simple_unet._wgrad)
+# GMK_GN_PAIR also gates the paired forward (gmk_gn_silu_fwd_pair, 16 x 16 only; simple_unet._res_fwd).
+# The two GroupNorm backward passes over a down-path tensor (the down ResBlock's and the skip half of the matching up ResBlock's) as ONE launch
+# (gmk_gn_silu_bwd_pair; simple_unet._res_bwd).  GMK_GN_PAIR=0: the two launches with the up block's input gradient handed over through HBM (A/B).
+GN_PAIR = os.environ.get("GMK_GN_PAIR", "1") != "0"
 
 
 def _xadd_stride(xadd, B, C):
@@ -294,6 +299,75 @@ def gn_silu_bwd(dy, x, gamma, beta, mean, rstd, dadd1=None, dadd2=None, dxsum=No
                                   _p(dgp), _p(dbp), _p(dxsum), stride, B, H * W, C, G, float(dp), int(dseed), int(doff),
                                   _p(xadd), xs, _DT[dy.dtype], _DT[x.dtype], _s()), "gn_silu_bwd")
     return dx, dgp, dbp
+
+
+def gn_pair_fwd_ok(x, groups_a, groups_b):
+    """True if the GroupNorm + SiLU forward of x's two consumers runs as one launch (gn_silu_fwd_pair)."""
+    if not GN_PAIR or groups_a <= 0 or groups_b <= 0 or x.dtype not in _HALF or getattr(x, "_gn_stats", None) is not None:
+        return False
+    B, H, W, C = x.shape
+    return bool(lib.gmk_gn_pair_fwd_ok(H * W, C, groups_a, groups_b, _DT[x.dtype]))
+
+
+def gn_silu_fwd_pair(x, a, b, eps=1e-5, xadd=None):
+    """GroupNorm + SiLU of one x for two consumers, a / b = (gamma, beta, groups): -> ((y_a, mean_a, rstd_a), (y_b, mean_b, rstd_b)), each
+    bit-identical to gn_silu_fwd(x, gamma, beta, groups, xadd=xadd) of its own, with x read once.  Shapes: gn_pair_fwd_ok."""
+    _chk(x, name="x")
+    B, H, W, C = x.shape
+    outs, args = [], []
+    for gamma, beta, groups in (a, b):
+        _f32(gamma, "gamma"); _f32(beta, "beta")
+        assert gamma.numel() == C and beta.numel() == C and groups > 0
+        y = torch.empty_like(x)
+        mean = torch.empty((B, groups), device=x.device, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+        mean._gn_groups = groups
+        outs.append((y, mean, rstd))
+    xs = _xadd_stride(xadd, B, C)
+    (ya, ma, ra), (yb, mb, rb) = outs
+    with _Timed("gn_silu_fwd_pair", 0.0, _nbytes(x, ya, yb)):
+        check(lib.gmk_gn_silu_fwd_pair(_p(x), _p(ya), _p(yb), _p(a[0]), _p(a[1]), _p(b[0]), _p(b[1]), _p(ma), _p(ra), _p(mb), _p(rb), B, H * W, C,
+                                       a[2], b[2], eps, _p(xadd), xs, _DT[x.dtype], _s()), "gn_silu_fwd_pair")
+    return outs[0], outs[1]
+
+
+def gn_pair_ok(x, groups_up, groups_dn, grad_dtype=torch.bfloat16):
+    """True if the GroupNorm backward of x's two consumers (groups_up / groups_dn groups) runs as one launch (gn_silu_bwd_pair)."""
+    if not GN_PAIR or groups_up <= 0 or groups_dn <= 0 or x.dtype not in _HALF or grad_dtype not in _DT:
+        return False
+    B, H, W, C = x.shape
+    return bool(lib.gmk_gn_pair_ok(H * W, C, groups_up, groups_dn, _DT[x.dtype], _DT[grad_dtype]))
+
+
+def gn_silu_bwd_pair(x, up, dn, dxsum=None, xadd=None):
+    """The backward of x's two GroupNorm + SiLU consumers in one launch.  up / dn = (dy, dadd, gamma, beta, mean, rstd) of the up block's skip
+    half and of the down block; -> (dx, (dgp_up, dbp_up), (dgp_dn, dbp_dn)), bit-identical to
+        ds, dgp_up, dbp_up = gn_silu_bwd(dy_up, x, ..., dadd1=dadd_up)
+        dx, dgp_dn, dbp_dn = gn_silu_bwd(dy_dn, x, ..., dadd1=dadd_dn, dadd2=ds, dxsum=dxsum)
+    without ds in HBM and with x read once.  Shapes: gn_pair_ok."""
+    _chk(x, name="x")
+    B, H, W, C = x.shape
+    sides = []
+    for dy, dadd, gamma, beta, mean, rstd in (up, dn):
+        _chk(dy, torch.bfloat16, "dy"); _chk(dadd, torch.bfloat16, "dadd"); _f32(gamma, "gamma"); _f32(beta, "beta")
+        assert dy.shape == x.shape and dadd.shape == x.shape and gamma.numel() == C and beta.numel() == C
+        G = getattr(mean, "_gn_groups", mean.shape[1])
+        dgp = torch.empty((B, C), device=x.device, dtype=torch.float32)
+        sides.append((dy, dadd, gamma, beta, mean, rstd, dgp, torch.empty_like(dgp), G))
+    dx = torch.empty_like(sides[1][0])
+    stride = 0
+    if dxsum is not None:
+        assert dxsum.dtype == torch.float32 and dxsum.shape == (B, C) and dxsum.stride(1) == 1
+        stride = dxsum.stride(0)
+    xs = _xadd_stride(xadd, B, C)
+    args = []
+    for dy, dadd, gamma, beta, mean, rstd, dgp, dbp, G in sides:
+        args += [_p(dy), _p(dadd), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dgp), _p(dbp), G]
+    # (the 32 x 32 instantiation reads dy_dn twice: 7 tensor passes; 6 at 16 x 16)
+    with _Timed("gn_silu_bwd_pair", 0.0, _nbytes(x, sides[0][0], sides[0][1], sides[1][0], sides[1][1], dx, sides[1][0] if H * W == 1024 else None)):
+        check(lib.gmk_gn_silu_bwd_pair(_p(x), *args, _p(dx), _p(dxsum), stride, B, H * W, C, _p(xadd), xs, _DT[x.dtype], _s()),
+              "gn_silu_bwd_pair")
+    return dx, (sides[0][6], sides[0][7]), (sides[1][6], sides[1][7])
 
 
 def cast16(x, dtype):

@@ -36,7 +36,7 @@ int gmk_version(void);
 const char* gmk_last_error(void);
 /* profiling aid: which kernel the calling thread's last gmk_conv_igemm / gmk_conv_wgrad / gmk_gn_* call launched
  * (1 conv_igemm_kernel, 2 conv_igemm_dma_kernel, 3 conv3x3_halo_kernel, 4 conv3x3_halo_ws_kernel, 7 conv3x3_halo_ws_kernel with the folded 1x1 skip convolution, 8 / 9 / 10 conv_subpixel_ws_kernel (upsample / transposed / upsample data gradient), 5 a halo kernel on the zero-stuffed source of GMK_CONV_TRANSPOSED2 (GMK_CONV_KERNEL=3), 6 the four parity-phase launches of the LDS-DMA kernel for GMK_CONV_TRANSPOSED2, 11 conv_wgrad_kernel,
- * 12 conv_wgrad_slots_kernel, 13 conv_wgrad_slots_ws_kernel, 17 its four-plane form for GMK_CONV_STRIDE2, 16 conv_wgrad_subpixel_ws_kernel, 14 conv1x1_pair_stream_kernel, 15 conv1x1_wgrad_stream_kernel, 21 gn_silu_fwd_reg_kernel, 22 gn_silu_fwd_kernel, 23 gn_silu_bwd_hybrid_kernel, 24 gn_silu_bwd_kernel) */
+ * 12 conv_wgrad_slots_kernel, 13 conv_wgrad_slots_ws_kernel, 17 its four-plane form for GMK_CONV_STRIDE2, 16 conv_wgrad_subpixel_ws_kernel, 14 conv1x1_pair_stream_kernel, 15 conv1x1_wgrad_stream_kernel, 21 gn_silu_fwd_reg_kernel, 22 gn_silu_fwd_kernel, 23 gn_silu_bwd_hybrid_kernel, 24 gn_silu_bwd_kernel, 25 gn_silu_bwd_pair_kernel, 26 gn_silu_fwd_pair_kernel) */
 int gmk_last_kernel(void);
 /* development aid: force kernel variants (0 = automatic; see GMK_CONV_KERNEL / GMK_WGRAD_KERNEL / GMK_GN_KERNEL); -1 = unset */
 int gmk_set_kernel_choice(int conv, int wgrad, int gn);
@@ -103,6 +103,25 @@ int gmk_gn_silu_bwd(const void* dy, const void* x, const float* gamma, const flo
                     float* dbeta_part, float* dxsum, int dxsum_stride, int B, int HW, int C, int groups,
                     float drop_p, uint64_t drop_seed, uint64_t drop_offset, const float* xadd, int xadd_stride, int dtype,
                     int x_dtype, void* stream);
+/* Paired backward: ONE tensor x with TWO GroupNorm + SiLU consumers (a down-path tensor of the U-Net: the down ResBlock's GroupNorm(32, C) and the
+ * skip half of an up ResBlock's GroupNorm(32, 2C), other gamma / beta / groups).  x is read once; every output is bit-identical to the two
+ * gmk_gn_silu_bwd calls it replaces.  gmk_gn_pair_ok: 1 if the paired kernel takes the shape (HW = 32 x 32 or 16 x 16, C a multiple of 32,
+ * groups of 4 / 8 / 16 channels, 16-bit x, bf16 gradients), else 0 - the caller then makes the two calls. */
+int gmk_gn_pair_ok(int HW, int C, int groups_a, int groups_b, int x_dtype, int grad_dtype);
+/* Paired forward of the same two consumers: x read once, (y, mean, rstd) of each bit-identical to its own gmk_gn_silu_fwd call (no dropout, no
+ * producer statistics).  gmk_gn_pair_fwd_ok: 1 where it runs (HW = 16 x 16, C a multiple of 64, groups of 4 / 8 / 16 channels, 16-bit x). */
+int gmk_gn_pair_fwd_ok(int HW, int C, int groups_a, int groups_b, int dtype);
+int gmk_gn_silu_fwd_pair(const void* x, void* y_a, void* y_b, const float* gamma_a, const float* beta_a, const float* gamma_b,
+                         const float* beta_b, float* mean_a, float* rstd_a, float* mean_b, float* rstd_b, int B, int HW, int C,
+                         int groups_a, int groups_b, float eps, const float* xadd, int xadd_stride, int dtype, void* stream);
+/* dx = GNbwd_dn(dy_dn) + dadd_dn + bf16(GNbwd_up(dy_up) + dadd_up): the up consumer's input gradient (the tensor the two-call form hands over
+ * through HBM as the second call's dadd2) stays in registers, rounded to bf16 where the stored one is.  Both addends are required.
+ * dgamma / dbeta partials of both consumers are written; dxsum (optional): per-sample channel sums of dx.  Gradients are bf16. */
+int gmk_gn_silu_bwd_pair(const void* x, const void* dy_up, const void* dadd_up, const float* gamma_up, const float* beta_up,
+                         const float* mean_up, const float* rstd_up, float* dgamma_part_up, float* dbeta_part_up, int groups_up,
+                         const void* dy_dn, const void* dadd_dn, const float* gamma_dn, const float* beta_dn, const float* mean_dn,
+                         const float* rstd_dn, float* dgamma_part_dn, float* dbeta_part_dn, int groups_dn, void* dx, float* dxsum,
+                         int dxsum_stride, int B, int HW, int C, const float* xadd, int xadd_stride, int x_dtype, void* stream);
 /* dst[i] = (dst type) src[i], n a multiple of 8: fp16 <-> bf16 storage conversion (fp16 results saturate at the largest finite value).
  * No reference call site: the self-attention extension (north_star, BASELINE configs[4]) keeps bf16 internals and converts the fp16
  * forward stream at its boundary. */
