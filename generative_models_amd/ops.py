@@ -163,6 +163,15 @@ def _f32(t, name):
     return _chk(t, torch.float32, name)
 
 
+def check_stream(seed, offset):
+    """-> (seed, offset) as ints.  A Philox stream is named by an unsigned 64-bit seed and counter; ctypes would wrap any other int into
+    c_uint64 silently, which selects a different stream from the one asked for."""
+    seed, offset = int(seed), int(offset)
+    if not (0 <= seed < 1 << 64 and 0 <= offset < 1 << 64):
+        raise ValueError(f"offset = {offset}, seed = {seed}: Philox counters and seeds are unsigned 64-bit")
+    return seed, offset
+
+
 # ---- packing ---------------------------------------------------------------------------------------------
 def pack_conv_weight(w, w_fwd, w_dgrad):
     _f32(w, "w")
@@ -748,8 +757,9 @@ def guide_onehot(guide):
 
 def label_drop(y, p, seed, offset):
     """In place: y[b] = -1 where rng_uniform((B,), seed, offset)[b] < p (diffusion_model.py:67)."""
+    seed, offset = check_stream(seed, offset)
     _chk(y, torch.int64, "y")
-    check(lib.gmk_label_drop(_p(y), y.numel(), float(p), int(seed), int(offset), _s()), "label_drop")
+    check(lib.gmk_label_drop(_p(y), y.numel(), float(p), seed, offset, _s()), "label_drop")
     return y
 
 
@@ -801,12 +811,14 @@ def scale_rows(x, rowscale):
 
 # ---- diffusion algebra -----------------------------------------------------------------------------------
 def rng_normal(shape, seed, offset, device):
+    seed, offset = check_stream(seed, offset)
     out = torch.empty(shape, device=device, dtype=torch.float32)
     check(lib.gmk_rng_normal(_p(out), out.numel(), seed, offset, _s()), "rng_normal")
     return out
 
 
 def rng_uniform(shape, seed, offset, device):
+    seed, offset = check_stream(seed, offset)
     out = torch.empty(shape, device=device, dtype=torch.float32)
     check(lib.gmk_rng_uniform(_p(out), out.numel(), seed, offset, _s()), "rng_uniform")
     return out
@@ -912,11 +924,10 @@ def inpaint_merge(z, x0, mask, alpha_s, sigma_s, a, b, is_last, renoise, logsnr_
     if logsnr_next is not None and (logsnr_next.dim() != 1 or logsnr_next.numel() != (2 * B if z_dup is not None else B)):
         raise ValueError(f"logsnr_next: shape {tuple(logsnr_next.shape)}, expected ({2 * B if z_dup is not None else B},)")
     B_total = B if B_total is None else int(B_total)
-    q0, offset, seed = int(q0), int(offset), int(seed)
+    q0 = int(q0)
     if B_total < B or q0 < 0 or q0 > (B_total - B) * (n // 4):
         raise ValueError(f"q0 = {q0}, B_total = {B_total}: a chunk of {B} rows must lie inside the batch")
-    if offset < 0 or not 0 <= seed < 1 << 64:
-        raise ValueError(f"offset = {offset}, seed = {seed}: Philox counters and seeds are unsigned 64-bit")
+    seed, offset = check_stream(seed, offset)
     if is_last and renoise:
         raise ValueError("inpaint_merge: the last step does not re-noise")
     coefs = (alpha_s, sigma_s, a, b, logsnr_t, logsnr_s)
@@ -988,9 +999,10 @@ def vlb_endpoints(x, eps0, delta):
 # ---- probability-flow ODE (an extension; gaussian_diffusion.GaussianDiffusion.encode / decode / ode_nll) ----------------------------------
 def rng_rademacher(shape, seed, offset, device):
     """+1 where rng_uniform(shape, seed, offset) >= 1/2, else -1 (Hutchinson probes)."""
+    seed, offset = check_stream(seed, offset)
     out = torch.empty(shape, device=device, dtype=torch.float32)
     with _Timed("rng_rademacher_kernel", 0.0, _nbytes(out), fixed=True):
-        check(lib.gmk_rng_rademacher(_p(out), out.numel(), int(seed), int(offset), _s()), "rng_rademacher")
+        check(lib.gmk_rng_rademacher(_p(out), out.numel(), seed, offset, _s()), "rng_rademacher")
     return out
 
 
@@ -999,6 +1011,7 @@ def dequantize(x, delta, seed, offset):
     delta = float(delta)
     if not 0.0 < delta <= 0.5:
         raise ValueError(f"delta = {delta}: the bin half-width must lie in (0, 0.5]")
+    seed, offset = check_stream(seed, offset)
     if x.dtype != torch.float32:
         raise ValueError(f"x: dtype {x.dtype}, expected torch.float32")
     if x.numel() == 0:
@@ -1006,7 +1019,7 @@ def dequantize(x, delta, seed, offset):
     _f32(x, "x")
     y = torch.empty_like(x)
     with _Timed("dequantize_kernel", 0.0, _nbytes(x, y), fixed=True):
-        check(lib.gmk_dequantize(_p(x), _p(y), delta, x.numel(), int(seed), int(offset), _s()), "dequantize")
+        check(lib.gmk_dequantize(_p(x), _p(y), delta, x.numel(), seed, offset, _s()), "dequantize")
     return y
 
 

@@ -1,0 +1,222 @@
+"""GPU tests that pin the random streams to Random123 Philox4x32-10 with the documented element mapping (element i of stream (seed, offset)
+is component i % 4 of counter offset + i // 4): gmk_rng_uniform / gmk_rng_normal and every kernel that draws for itself - Rademacher probes,
+dequantisation noise, the classifier-free label drop, both RePaint draws and the GroupNorm dropout mask, forward and backward - against the
+host restatement tests/philox_ref.py (itself checked against the published known-answer vectors in tests/test_host_philox.py), never against
+ops.rng_*.  Seeds and counters reach past 2^32: the key's high word, the counter's high word, the carry into it inside one launch and the wrap
+at 2^64 are all exercised."""
+import os
+import sys
+from functools import lru_cache
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import philox_ref  # noqa: E402
+from test_gpu_ops import TOL, rel_err  # noqa: E402
+
+SEEDS = [0, 1, 1234, 1 << 32, (1 << 63) + 12345, (1 << 64) - 1]
+OFFSETS = [0, 5, (1 << 32) - 3, 1 << 32, (1 << 40) + 7, (1 << 64) - 2]      # 2^32 - 3: the carry inside a launch; 2^64 - 2: the wrap
+SIZES = [1, 2, 3, 4, 5, 1023, 4099]                                         # scalar tails of 1, 2, 3 values, and whole vectors
+# |device fp32 normal - float64 reference| <= NORMAL_TOL, absolute.  The radius is at most sqrt(2 * 24 ln 2) = 5.77; the fp32 product
+# 2 pi u2 is off by up to half an ulp at 6.28 (2.4e-7 in the angle, times the radius); sincosf, logf and sqrtf add a few ulp each: below
+# about 5e-6 in all.  A sin / cos swap, a wrong pairing or a wrong radius misses by order 1.
+NORMAL_TOL = 1e-5
+BIG = ((1 << 63) + 12345, (1 << 40) + 7)                                     # (seed >= 2^32, offset with a non-zero high word)
+CARRY = ((1 << 32) + 99, (1 << 32) - 20)                                     # the counter crosses 2^32 inside the draw
+SMALL = (99, 1000)
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    from generative_models_amd import ops as o
+    return o
+
+
+@lru_cache(maxsize=None)
+def ref_uniform(seed, offset, n):
+    u = philox_ref.uniform(seed, offset, n)
+    u.setflags(write=False)
+    return u
+
+
+@lru_cache(maxsize=None)
+def ref_normal(seed, offset, n):
+    z = philox_ref.normal(seed, offset, n)
+    z.setflags(write=False)
+    return z
+
+
+def t(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+# ---- raw streams -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", SEEDS)
+def test_rng_uniform_is_philox4x32_10_bit_for_bit(ops, seed):
+    """(seed 0, offset 0) is the first Random123 known-answer vector seen through u01."""
+    got = torch.cat([ops.rng_uniform((n,), seed, off, "cuda") for off in OFFSETS for n in SIZES]).cpu()
+    want = t(np.concatenate([ref_uniform(seed, off, n) for off in OFFSETS for n in SIZES]))
+    assert got.dtype == torch.float32
+    if not torch.equal(got, want):
+        bad = int((got != want).nonzero()[0])
+        pos, case = 0, None
+        for off in OFFSETS:
+            for n in SIZES:
+                if case is None and bad < pos + n:
+                    case = (off, n, bad - pos)
+                pos += n
+        raise AssertionError(f"seed {seed}: first mismatch at (offset, n, element) = {case}: got {float(got[bad])!r}, expected {float(want[bad])!r}")
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_rng_normal_is_box_muller_on_philox4x32_10(ops, seed):
+    """Largest deviation from the float64 reference seen on the MI355X: 1.30e-6 over this grid, 1.58e-6 in the 2^20 + 1 case below (bound 1e-5)."""
+    got = torch.cat([ops.rng_normal((n,), seed, off, "cuda") for off in OFFSETS for n in SIZES]).cpu()
+    want = t(np.concatenate([ref_normal(seed, off, n) for off in OFFSETS for n in SIZES]))
+    assert got.dtype == torch.float32
+    dev = (got.double() - want).abs()
+    print(f"rng_normal seed {seed}: max |got - ref| = {float(dev.max()):.3e}")
+    assert float(dev.max()) <= NORMAL_TOL, f"seed {seed}: element {int(dev.argmax())} of the concatenated grid is off by {float(dev.max()):.3e}"
+
+
+def test_streams_past_one_million_values(ops):
+    """n = 2^20 + 1 (a one-value tail behind 2^18 whole vectors, 1025 workgroups) across the carry into the high counter word.  The launch caps
+    its grid at 4096 workgroups, which takes more than 2^22 values to reach: the grid-stride loop does not wrap at this size."""
+    n = (1 << 20) + 1
+    seed, off = (1 << 63) + 12345, (1 << 32) - 3
+    u = ops.rng_uniform((n,), seed, off, "cuda").cpu()
+    assert torch.equal(u, t(ref_uniform(seed, off, n)))
+    z = ops.rng_normal((n,), seed, off, "cuda").cpu()
+    dev = (z.double() - t(ref_normal(seed, off, n))).abs()
+    print(f"rng_normal n = 2^20 + 1: max |got - ref| = {float(dev.max()):.3e}")
+    assert float(dev.max()) <= NORMAL_TOL
+
+
+# ---- in-kernel consumers -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed,off", [SMALL, BIG, CARRY, ((1 << 64) - 1, (1 << 64) - 2)])
+def test_rademacher_probes(ops, seed, off):
+    n = 4099
+    got = ops.rng_rademacher((n,), seed, off, "cuda").cpu()
+    assert torch.equal(got, t(philox_ref.rademacher(seed, off, n)))
+
+
+@pytest.mark.parametrize("n", [4096, 4099])                      # whole vectors only; a three-value scalar tail
+@pytest.mark.parametrize("seed,off", [SMALL, BIG, CARRY])
+def test_dequantisation_noise(ops, seed, off, n):
+    """y = x + delta (2 u - 1) in fp32 in the kernel's operation order.  2 u and 2 u - 1 are exact (u lies on the 2^-24 grid), the product and
+    the sum round once each, and the library builds with -ffp-contract=off: NumPy's fp32 arithmetic gives the same bits."""
+    delta = 1.0 / 255.0
+    x = (torch.randint(0, 256, (n,), generator=torch.Generator().manual_seed(n)).float() / 127.5 - 1.0)
+    got = ops.dequantize(x.cuda(), delta, seed, off).cpu()
+    u = ref_uniform(seed, off, n)
+    want = x.numpy() + np.float32(delta) * (np.float32(2.0) * u - np.float32(1.0))
+    assert want.dtype == np.float32
+    assert torch.equal(got, t(want))
+
+
+@pytest.mark.parametrize("B", [1, 6, 7, 1024])
+@pytest.mark.parametrize("seed,off", [SMALL, BIG, CARRY])
+def test_label_drop_rows(ops, seed, off, B):
+    """Row b is dropped iff component b & 3 of counter offset + (b >> 2) is below p."""
+    p = 0.1
+    y0 = torch.arange(B, dtype=torch.int64) % 10
+    y = ops.label_drop(y0.clone().cuda(), p, seed, off).cpu()
+    drop = t(philox_ref.label_drop_mask(seed, off, B, p))
+    assert torch.equal(y != y0, drop)
+    assert bool((y[drop] == -1).all()) and torch.equal(y[~drop], y0[~drop])
+    if B == 1024:
+        assert 60 < int(drop.sum()) < 150                        # both kinds of row are present (binomial(1024, 0.1): 102 +- 10)
+
+
+@pytest.mark.parametrize("seed,off", [SMALL, BIG, CARRY])
+def test_inpaint_merge_draws(ops, seed, off):
+    """The two degenerate settings of test_merge_kernel_draws_match_rng_normal_exactly, on a chunk of 3 rows placed at row 1 of a batch of 5:
+    all pixels known with alpha_s = 0, sigma_s = 1 leaves eps1, a re-noising jump with a = 0, b = 1 leaves eps2 - the normals of counters
+    offset + q0 and offset + N + q0, N = B_total n / 4."""
+    B, n, B_total = 3, 64, 5
+    q0, N = 1 * n // 4, B_total * n // 4
+    x0 = torch.zeros((B, 1, 8, 8), device="cuda")
+    z = torch.zeros_like(x0)
+    ones = torch.ones((B, n), dtype=torch.uint8, device="cuda")
+    ops.inpaint_merge(z, x0, ones, 0.0, 1.0, 1.0, 0.0, False, False, -1.0, 1.0, seed, off, q0=q0, B_total=B_total)
+    eps1 = z.cpu().reshape(-1).double()
+    ops.inpaint_merge(z, x0, torch.zeros_like(ones), 0.0, 1.0, 0.0, 1.0, False, True, -1.0, 1.0, seed, off, q0=q0, B_total=B_total)
+    eps2 = z.cpu().reshape(-1).double()
+    m64 = (1 << 64) - 1
+    d1 = float((eps1 - t(ref_normal(seed, (off + q0) & m64, B * n))).abs().max())
+    d2 = float((eps2 - t(ref_normal(seed, (off + N + q0) & m64, B * n))).abs().max())
+    print(f"inpaint_merge: max |eps1 - ref| = {d1:.3e}, max |eps2 - ref| = {d2:.3e}")
+    assert d1 <= NORMAL_TOL and d2 <= NORMAL_TOL
+
+
+# GroupNorm dropout: one shape per forward kernel that can apply the mask.  (H = W, dtype, groups, kernel id of gmk_last_kernel)
+GN_CASES = [(8, torch.bfloat16, 32, 22),       # streaming gn_silu_fwd_kernel
+            (16, torch.bfloat16, 32, 21),      # gn_silu_fwd_reg_kernel, 64-channel slabs
+            (64, torch.bfloat16, 32, 21),      # the 1024-thread 32-channel-slab form
+            (8, torch.float32, 32, 22),
+            (12, torch.bfloat16, 64, 22)]      # the narrow branch (2 channels per group)
+GN_SEED, GN_OFF = (1 << 63) + 12345, (1 << 33) - 4096      # the 8 x 8 case ends on a multiple of 2^32, the larger ones cross it
+GN_P = 0.25
+
+
+def _gn_inputs(S, dtype, B=2, C=128):
+    g = torch.Generator().manual_seed(S)
+    x = (torch.randn((B, S, S, C), generator=g) * 1.5 + 0.3).to(dtype)
+    gamma = 1 + 0.1 * torch.randn((C,), generator=g)
+    beta = 0.1 * torch.randn((C,), generator=g)
+    return x, gamma, beta
+
+
+def test_groupnorm_dropout_mask_forward(ops):
+    """Dropped elements are exactly zero; kept ones are the undropped output over 1 - p: within 2^-7 relative for bf16 (two half-ulp roundings
+    of 2^-9 each - the undropped output's and the scaled one's - doubled for margin), 2^-22 for fp32 in the same way.  One loop over the
+    shapes, so that the kernels that ran can be counted: the three bf16 shapes with 32 groups cover both forward kernels."""
+    from generative_models_amd._lib import lib
+    ran = []
+    for S, dtype, G, kernel in GN_CASES:
+        case = f"{S}x{S} {dtype} groups {G}"
+        x, gamma, beta = _gn_inputs(S, dtype)
+        xd, gd, bd = x.cuda(), gamma.cuda(), beta.cuda()
+        y0, _, _ = ops.gn_silu_fwd(xd, gd, bd, G)
+        y, _, _ = ops.gn_silu_fwd(xd, gd, bd, G, dropout=(GN_P, GN_SEED, GN_OFF))
+        ran.append(lib.gmk_last_kernel())
+        assert ran[-1] == kernel, f"{case}: kernel {ran[-1]} ran, expected {kernel}"
+        y0, y = y0.cpu().double(), y.cpu().double()
+        keep = t(philox_ref.keep_mask(GN_SEED, GN_OFF, x.numel(), GN_P)).reshape(x.shape)      # NHWC element order
+        assert 0.70 < float(keep.double().mean()) < 0.80
+        assert bool((y[~keep] == 0).all()), f"{case}: {int((y[~keep] != 0).sum())} dropped elements are not zero"
+        want = y0[keep] / (1.0 - GN_P)
+        tol = 2.0 ** -7 if dtype == torch.bfloat16 else 2.0 ** -22
+        excess = (y[keep] - want).abs() - tol * want.abs()
+        assert float(excess.max()) <= 0, f"{case}: {int((excess > 0).sum())} kept elements differ from y0 / (1 - p)"
+        assert int((y[keep] != 0).sum()) > 0.99 * int(keep.sum()), case                         # kept elements are not zeroed
+    assert set(ran[:3]) == {21, 22}
+
+
+@pytest.mark.parametrize("S", [8, 16])
+def test_groupnorm_dropout_mask_backward(ops, S):
+    """dx, dgamma and dbeta against float64 autograd through silu(group_norm(x)) * keep / (1 - p) with the host mask: the backward kernel
+    regenerates the forward's mask from (seed, offset).  A mask wrong at a few elements misses by order 0.1."""
+    dtype, G = torch.bfloat16, 32
+    x, gamma, beta = _gn_inputs(S, dtype)
+    B, _, _, C = x.shape
+    dy = torch.randn(x.shape, generator=torch.Generator().manual_seed(100 + S)).to(dtype)
+    keep = t(philox_ref.keep_mask(GN_SEED, GN_OFF, x.numel(), GN_P)).reshape(x.shape)
+    xr = x.double().permute(0, 3, 1, 2).requires_grad_(True)                                # NCHW view of the NHWC values
+    gr, br = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    yr = F.silu(F.group_norm(xr, G, gr, br, 1e-5)) * keep.permute(0, 3, 1, 2).double() / (1.0 - GN_P)
+    yr.backward(dy.double().permute(0, 3, 1, 2))
+    xd, gd, bd = x.cuda(), gamma.cuda(), beta.cuda()
+    drop = (GN_P, GN_SEED, GN_OFF)
+    y, mean, rstd = ops.gn_silu_fwd(xd, gd, bd, G, dropout=drop)
+    assert rel_err(y, yr.detach().permute(0, 2, 3, 1)) < TOL[dtype]
+    dx, dgp, dbp = ops.gn_silu_bwd(dy.cuda(), xd, gd, bd, mean, rstd, dropout=drop)
+    assert rel_err(dx, xr.grad.permute(0, 2, 3, 1)) < TOL[dtype]
+    assert rel_err(dgp.sum(0), gr.grad) < TOL[dtype]
+    assert rel_err(dbp.sum(0), br.grad) < TOL[dtype]
