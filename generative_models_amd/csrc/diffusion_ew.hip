@@ -5,7 +5,8 @@
 // torch.optim.Adam as diffusion_model.py:56 constructs it.  gmk_adam_ema_step's weight average has no reference call site (the
 // reference keeps no EMA): an extension, defined by torch.lerp.  gmk_dpm_solver_step (DPM-Solver++(2M)) is an extension too, and so are
 // the variational-bound kernels gmk_q_sample_logsnr / gmk_vlb_term / gmk_vlb_endpoints (Kingma et al. 2021, continuous-time VDM bound) and
-// the inpainting merge gmk_inpaint_merge (RePaint, Lugmayr et al. 2022).  gmk_grad_norm / gmk_adam_step_ctl (global-norm clipping by
+// the inpainting merge gmk_inpaint_merge (RePaint, Lugmayr et al. 2022) and dynamic thresholding (gmk_dyn_threshold, gmk_sampler_step_dt,
+// gmk_dpm_solver_step_dt; Saharia et al. 2022).  gmk_grad_norm / gmk_adam_step_ctl (global-norm clipping by
 // torch.nn.utils.clip_grad_norm_'s rule, and the non-finite guard GradScaler.step gives the reference at diffusion_model.py:71) are extensions.
 #include <math.h>
 
@@ -124,14 +125,32 @@ __global__ __launch_bounds__(256) void v_loss_kernel(const float* __restrict__ v
     }
 }
 
-// grid (ceil(n/256), B)
+// ---- dynamic thresholding (Saharia et al. 2022, Imagen, section 2.3); an extension, no reference call site.
+// The UNCLIPPED data prediction of one element: x_from_out of the conditional output, and when guided the extrapolation of sampler_step_kernel
+// without its three clips (a prediction clipped at +-1 before the extrapolation would defeat the threshold).  Guidance is defined in eps space,
+// e = (1 + w) e_c + (-w) e_u and x_raw = x_from_eps(z, e); eps_from_x and x_from_eps are affine in x and inverse to each other and the weights sum
+// to 1, so that is x_raw = (1 + w) x_c + (-w) x_u, which is what is evaluated.  The round trip itself cancels in fp32 at low SNR: at logsnr -20
+// it forms z - e d2 with e d2 = z - O(4e-5) and multiplies by d1 = 2e4, a relative error of 1e-3 in x_raw against 1e-7 here (float64 restatement).
+// The one definition behind dyn_threshold_kernel's keys and the DT instantiations of the two update kernels: the same bits in both.
+__device__ __forceinline__ float x_raw_from_out(float out, float out_u, bool guided, float w, float zz, const LogsnrCoef& c, int mt) {
+    float xr = x_from_out(out, zz, c, mt);
+    if (guided) xr = (1.0f + w) * xr + (-w) * x_from_out(out_u, zz, c, mt);
+    return xr;
+}
+// x-hat = clamp(x_raw, -s, s) / s, a true division: with s = 1 this is clip1's bits
+__device__ __forceinline__ float threshold_x(float xr, float s) { return fminf(fmaxf(xr, -s), s) / s; }
+
+// grid (ceil(n/256), B).  DT (gmk_sampler_step_dt): x-hat is the raw prediction clamped to thr[b] and divided by it instead of the static clip;
+// everything after x-hat is shared.  The DT = false instantiation is the kernel gmk_sampler_step and gmk_ddim_step_vec have always launched.
+template <bool DT>
 __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restrict__ v, const float* __restrict__ vu,
                                                           const float* __restrict__ cond_w, const float* __restrict__ z,
                                                           const float* __restrict__ noise, float lt, float ls, int is_last,
                                                           float* __restrict__ z_next, float* __restrict__ x_pred,
                                                           float* __restrict__ eps_pred, int64_t n,
                                                           const float* __restrict__ lt_vec, const float* __restrict__ ls_vec, int mt,
-                                                          float* __restrict__ z_dup = nullptr, float* __restrict__ logsnr_next = nullptr) {
+                                                          float* __restrict__ z_dup = nullptr, float* __restrict__ logsnr_next = nullptr,
+                                                          const float* __restrict__ thr = nullptr) {
     const int b = blockIdx.y;
     if (lt_vec) { lt = lt_vec[b]; ls = ls_vec[b]; }      // per-sample times (teacher steps of the distillation loss)
     // the next iteration's network time: u_t(i - 1) = u_s(i) (gaussian_diffusion.py:288-290), so logsnr_s IS the next logsnr_t
@@ -151,14 +170,20 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
     const int64_t base = (int64_t)b * n;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float zz = z[base + i];
-        float xh = clip1(x_from_out(v[base + i], zz, c, mt));
-        float eh = c.c1 * (zz - xh * c.c2);
-        if (vu) {   // classifier-free guidance in eps space (:176-186)
-            const float xu = clip1(x_from_out(vu[base + i], zz, c, mt));
-            const float eu = c.c1 * (zz - xu * c.c2);
-            const float e = (1.0f + w) * eh + (-w) * eu;
-            xh = clip1(c.d1 * (zz - e * c.d2));
+        float xh, eh;
+        if (DT) {
+            xh = threshold_x(x_raw_from_out(v[base + i], vu ? vu[base + i] : 0.f, vu != nullptr, w, zz, c, mt), thr[b]);
             eh = c.c1 * (zz - xh * c.c2);
+        } else {
+            xh = clip1(x_from_out(v[base + i], zz, c, mt));
+            eh = c.c1 * (zz - xh * c.c2);
+            if (vu) {   // classifier-free guidance in eps space (:176-186)
+                const float xu = clip1(x_from_out(vu[base + i], zz, c, mt));
+                const float eu = c.c1 * (zz - xu * c.c2);
+                const float e = (1.0f + w) * eh + (-w) * eu;
+                xh = clip1(c.d1 * (zz - e * c.d2));
+                eh = c.c1 * (zz - xh * c.c2);
+            }
         }
         float zs;
         if (noise) zs = (r * alpha_st * zz + omr * alpha_s * xh) + stdv * noise[base + i];   // :242
@@ -174,13 +199,15 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
 // and the guidance exactly as sampler_step_kernel forms them; then D = (1 + k) x_hat - k x_prev (k = 1 / 2r, 0 on the first step: x_prev
 // is then not read) and z_s = c_z z + c_x D with c_z = sigma_s / sigma_t, c_x = -alpha_s expm1(-h), all three from the host.  x_hist
 // holds the previous step's x-hat on entry and this step's on exit (same element, same thread).  An extension: no reference call site.
+// DT (gmk_dpm_solver_step_dt): x-hat by the dynamic threshold thr[b], as in sampler_step_kernel<true>.
+template <bool DT>
 __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __restrict__ v, const float* __restrict__ vu,
                                                              const float* __restrict__ cond_w, const float* __restrict__ z,
                                                              float* __restrict__ x_hist, float lt, float ls, float c_z, float c_x,
                                                              float k_prev, int is_last, float* __restrict__ z_next,
                                                              float* __restrict__ x_pred, float* __restrict__ eps_pred,
                                                              float* __restrict__ z_dup, float* __restrict__ logsnr_next, int64_t n,
-                                                             int mt) {
+                                                             int mt, const float* __restrict__ thr) {
     const int b = blockIdx.y;
     if (logsnr_next && blockIdx.x == 0 && threadIdx.x == 0) {
         logsnr_next[b] = ls;
@@ -192,14 +219,20 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __res
     const int64_t base = (int64_t)b * n;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float zz = z[base + i];
-        float xh = clip1(x_from_out(v[base + i], zz, c, mt));
-        float eh = c.c1 * (zz - xh * c.c2);
-        if (vu) {
-            const float xu = clip1(x_from_out(vu[base + i], zz, c, mt));
-            const float eu = c.c1 * (zz - xu * c.c2);
-            const float e = (1.0f + w) * eh + (-w) * eu;
-            xh = clip1(c.d1 * (zz - e * c.d2));
+        float xh, eh;
+        if (DT) {
+            xh = threshold_x(x_raw_from_out(v[base + i], vu ? vu[base + i] : 0.f, vu != nullptr, w, zz, c, mt), thr[b]);
             eh = c.c1 * (zz - xh * c.c2);
+        } else {
+            xh = clip1(x_from_out(v[base + i], zz, c, mt));
+            eh = c.c1 * (zz - xh * c.c2);
+            if (vu) {
+                const float xu = clip1(x_from_out(vu[base + i], zz, c, mt));
+                const float eu = c.c1 * (zz - xu * c.c2);
+                const float e = (1.0f + w) * eh + (-w) * eu;
+                xh = clip1(c.d1 * (zz - e * c.d2));
+                eh = c.c1 * (zz - xh * c.c2);
+            }
         }
         const float d = second_order ? (1.0f + k_prev) * xh - k_prev * x_hist[base + i] : xh;
         const float zs = c_z * zz + c_x * d;
@@ -208,6 +241,131 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __res
         if (z_dup) z_dup[base + i] = is_last ? xh : zs;
         if (x_pred) x_pred[base + i] = xh;
         if (eps_pred) eps_pred[base + i] = eh;
+    }
+}
+
+// ---- the per-image threshold of dynamic thresholding: an exact order-statistic selection in LDS.
+// s[b] = max(1, q), q the p-quantile of |x_raw[b]| by torch.quantile's linear rule: q = a[lo] + frac (a[hi] - a[lo]) in fp32, a = |x_raw[b]| sorted
+// ascending, lo = k_lo, hi = min(lo + 1, n - 1) (k_lo and frac from the host, in double).  a[lo] and a[hi] are exact order statistics.
+//
+// One workgroup of 256 threads per image.  key = bits(x_raw) & 0x7fffffff: non-negative floats order as unsigned integers, so the k-th
+// smallest key is the k-th smallest |x_raw|.  The keys of an image of n <= kDynKeys values are formed once (one read of v, v_uncond and z)
+// and stay in LDS; a larger image re-forms them from global memory in every pass.  Selection is an MSB-first radix select, four 8-bit
+// digits: each pass counts, among the keys that share the digits decided so far, the next digit's 256 values (integer LDS atomics into one
+// histogram per wave: integer adds commute, so the counts do not depend on timing), scans the counts and narrows to the bin that holds rank
+// k_lo.  After the last pass the prefix IS a[lo], and the workgroup knows how many keys lie below it and how many equal it; a[hi] = a[lo]
+// when hi == lo or at least k_lo + 2 keys are <= a[lo], else the smallest key above a[lo] (one more pass, an integer LDS min).  No floating-
+// point atomics; every loop's trip count depends on n alone, whatever the values (NaNs and infinities are keys like any other).
+// LDS: 48 KiB of keys + 4 KiB of histograms + 84 B = 53,332 B per workgroup, so three workgroups (12 waves) share a CU's 160 KiB.
+constexpr int kDynKeys = 12288;      // LDS-resident keys per image: covers 3 x 64 x 64
+
+// inclusive sum over the 16 lanes of a DPP row (row_shr:1, 2, 4, 8; a lane the shift leaves without a source adds 0)
+__device__ __forceinline__ uint32_t row_scan16(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void dyn_threshold_kernel(const float* __restrict__ v, const float* __restrict__ vu,
+                                                           const float* __restrict__ cond_w, const float* __restrict__ z, float lt,
+                                                           uint32_t k_lo, float frac, float* __restrict__ s_out, float* __restrict__ q_out,
+                                                           uint32_t n, int mt) {
+    __shared__ __attribute__((aligned(16))) uint32_t keys[kDynKeys];
+    __shared__ uint32_t hist[4][256];
+    __shared__ uint32_t rowtot[16];
+    __shared__ uint32_t sel[4];          // the chosen bin: digit, rank inside it, keys below it, keys in it
+    __shared__ uint32_t min_above;
+    const int b = blockIdx.x;
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+    const LogsnrCoef c = logsnr_coef(lt);
+    const float w = cond_w ? cond_w[b] : 0.f;
+    const bool guided = vu != nullptr;
+    const bool in_lds = n <= (uint32_t)kDynKeys;
+    const bool vec = (n & 3) == 0;       // every row then starts 16-byte aligned
+    const int64_t base = (int64_t)b * n;
+    auto key_of = [&](float o, float ou, float zz) {
+        return __builtin_bit_cast(uint32_t, x_raw_from_out(o, ou, guided, w, zz, c, mt)) & 0x7fffffffu;
+    };
+    auto key1 = [&](uint32_t i) { return key_of(v[base + i], guided ? vu[base + i] : 0.f, z[base + i]); };
+    auto key4 = [&](uint32_t i, uint32_t (&k)[4]) {
+        float ov[4], uv[4] = {0.f, 0.f, 0.f, 0.f}, zv[4];
+        load4(v + base + i, ov);
+        load4(z + base + i, zv);
+        if (guided) load4(vu + base + i, uv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) k[j] = key_of(ov[j], uv[j], zv[j]);
+    };
+    // f(key) for every key of the image, from LDS or re-formed from global memory
+    auto for_keys = [&](auto&& f) {
+        if (in_lds) {
+            for (uint32_t i = tid; i < n; i += 256) f(keys[i]);
+        } else if (vec) {
+            for (uint32_t i = tid * 4; i < n; i += 1024) {
+                uint32_t k[4];
+                key4(i, k);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) f(k[j]);
+            }
+        } else {
+            for (uint32_t i = tid; i < n; i += 256) f(key1(i));
+        }
+    };
+    if (tid == 0) min_above = 0xffffffffu;
+    if (in_lds) {
+        if (vec) {
+            for (uint32_t i = tid * 4; i < n; i += 1024) {
+                uint32_t k[4];
+                key4(i, k);
+                *reinterpret_cast<uint4*>(&keys[i]) = make_uint4(k[0], k[1], k[2], k[3]);
+            }
+        } else {
+            for (uint32_t i = tid; i < n; i += 256) keys[i] = key1(i);
+        }
+    }
+    uint32_t prefix = 0;                 // the digits of a[lo] decided so far
+    uint32_t rank = k_lo;                // a[lo]'s rank among the keys that share them
+    uint32_t below = 0, equal = 0;       // keys below the prefix's range / inside the last chosen bin
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int shift = 24 - 8 * p;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) hist[k][tid] = 0;
+        __syncthreads();                 // also: the keys are in LDS (p == 0), the last pass's `sel` has been read
+        for_keys([&](uint32_t key) {
+            if ((uint32_t)((uint64_t)key >> (shift + 8)) == prefix) atomicAdd(&hist[wave][(key >> shift) & 255u], 1u);
+        });
+        __syncthreads();
+        const uint32_t cnt = (hist[0][tid] + hist[1][tid]) + (hist[2][tid] + hist[3][tid]);      // thread t owns digit value t
+        const uint32_t inc = row_scan16(cnt);
+        if ((tid & 15) == 15) rowtot[tid >> 4] = inc;
+        __syncthreads();
+        uint32_t before = 0;             // keys in the rows of bins before this thread's
+#pragma unroll
+        for (uint32_t r = 0; r < 16; ++r) before += r < (tid >> 4) ? rowtot[r] : 0u;
+        const uint32_t excl = before + inc - cnt;
+        if (excl <= rank && rank < excl + cnt) {      // exactly one thread: the counts sum to the keys that share the prefix, rank is below that
+            sel[0] = tid; sel[1] = rank - excl; sel[2] = excl; sel[3] = cnt;
+        }
+        __syncthreads();
+        prefix = (prefix << 8) | sel[0];
+        rank = sel[1];
+        below += sel[2];
+        equal = sel[3];
+    }
+    // the smallest key above a[lo] (0xffffffff when there is none: then it is not used)
+    uint32_t m = 0xffffffffu;
+    for_keys([&](uint32_t key) { m = (key > prefix && key < m) ? key : m; });
+    atomicMin(&min_above, m);
+    __syncthreads();
+    if (tid == 0) {
+        const bool hi_is_lo = k_lo == n - 1 || below + equal >= k_lo + 2;
+        const float a_lo = __builtin_bit_cast(float, prefix);
+        const float a_hi = __builtin_bit_cast(float, hi_is_lo ? prefix : min_above);
+        const float q = __fadd_rn(a_lo, __fmul_rn(frac, __fsub_rn(a_hi, a_lo)));
+        s_out[b] = fmaxf(1.0f, q);
+        if (q_out) q_out[b] = q;
     }
 }
 
@@ -678,36 +836,83 @@ extern "C" int gmk_v_loss(const float* v, const float* z, const float* x, const 
     return gmk_check_launch("gmk_v_loss");
 }
 
+// The argument checks and the launch behind gmk_sampler_step / gmk_sampler_step_dt (DT: thr is required)
+template <bool DT>
+static int sampler_step_launch(const char* who, const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z,
+                               const float* noise, float logsnr_t, float logsnr_s, int is_last, float* z_next, float* x_pred,
+                               float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && z && z_next && (!DT || thr), "%s: null pointer", who);
+    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "%s: mean_type must be 0 (v), 1 (eps) or 2 (x)", who);
+    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "%s: v_uncond and cond_w go together", who);
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "%s: bad shape", who);
+    const int gx = row_grid(n, 256);
+    sampler_step_kernel<DT><<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, noise, logsnr_t, logsnr_s, is_last, z_next,
+                                                                         x_pred, eps_pred, n, nullptr, nullptr, mean_type, z_dup,
+                                                                         logsnr_next, thr);
+    return gmk_check_launch(who);
+}
+
 extern "C" int gmk_sampler_step(const float* v, const float* v_uncond, const float* cond_w, const float* z,
                                 const float* noise, float logsnr_t, float logsnr_s, int is_last, float* z_next,
                                 float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n,
                                 void* stream) {
-    GMK_REQUIRE(v && z && z_next, "gmk_sampler_step: null pointer");
-    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_sampler_step");
-    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_sampler_step: v_uncond and cond_w go together");
-    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_sampler_step: bad shape");
+    return sampler_step_launch<false>("gmk_sampler_step", v, v_uncond, cond_w, nullptr, z, noise, logsnr_t, logsnr_s, is_last, z_next, x_pred,
+                                      eps_pred, z_dup, logsnr_next, mean_type, B, n, stream);
+}
+
+extern "C" int gmk_sampler_step_dt(const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z,
+                                   const float* noise, float logsnr_t, float logsnr_s, int is_last, float* z_next, float* x_pred,
+                                   float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
+    return sampler_step_launch<true>("gmk_sampler_step_dt", v, v_uncond, cond_w, thr, z, noise, logsnr_t, logsnr_s, is_last, z_next, x_pred,
+                                     eps_pred, z_dup, logsnr_next, mean_type, B, n, stream);
+}
+
+template <bool DT>
+static int dpm_solver_step_launch(const char* who, const float* v, const float* v_uncond, const float* cond_w, const float* thr,
+                                  const float* z, float* x_hist, float logsnr_t, float logsnr_s, float coef_z, float coef_x,
+                                  float coef_prev, int is_last, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
+                                  float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && z && x_hist && z_next && (!DT || thr), "%s: null pointer", who);
+    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "%s: mean_type must be 0 (v), 1 (eps) or 2 (x)", who);
+    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "%s: v_uncond and cond_w go together", who);
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "%s: bad shape", who);
+    GMK_REQUIRE(isfinite(logsnr_t) && isfinite(logsnr_s) && isfinite(coef_z) && isfinite(coef_x) && isfinite(coef_prev),
+                "%s: non-finite time or coefficient", who);
     const int gx = row_grid(n, 256);
-    sampler_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, noise, logsnr_t, logsnr_s,
-                                                                     is_last, z_next, x_pred, eps_pred, n, nullptr, nullptr, mean_type,
-                                                                     z_dup, logsnr_next);
-    return gmk_check_launch("gmk_sampler_step");
+    dpm_solver_step_kernel<DT><<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x,
+                                                                            coef_prev, is_last, z_next, x_pred, eps_pred, z_dup, logsnr_next,
+                                                                            n, mean_type, thr);
+    return gmk_check_launch(who);
 }
 
 extern "C" int gmk_dpm_solver_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float* x_hist,
                                    float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last,
                                    float* z_next, float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type,
                                    int B, int64_t n, void* stream) {
-    GMK_REQUIRE(v && z && x_hist && z_next, "gmk_dpm_solver_step: null pointer");
-    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_dpm_solver_step");
-    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_dpm_solver_step: v_uncond and cond_w go together");
-    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_dpm_solver_step: bad shape");
-    GMK_REQUIRE(isfinite(logsnr_t) && isfinite(logsnr_s) && isfinite(coef_z) && isfinite(coef_x) && isfinite(coef_prev),
-                "gmk_dpm_solver_step: non-finite time or coefficient");
-    const int gx = row_grid(n, 256);
-    dpm_solver_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, x_hist, logsnr_t, logsnr_s, coef_z,
-                                                                        coef_x, coef_prev, is_last, z_next, x_pred, eps_pred, z_dup,
-                                                                        logsnr_next, n, mean_type);
-    return gmk_check_launch("gmk_dpm_solver_step");
+    return dpm_solver_step_launch<false>("gmk_dpm_solver_step", v, v_uncond, cond_w, nullptr, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x,
+                                         coef_prev, is_last, z_next, x_pred, eps_pred, z_dup, logsnr_next, mean_type, B, n, stream);
+}
+
+extern "C" int gmk_dpm_solver_step_dt(const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z,
+                                      float* x_hist, float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_prev,
+                                      int is_last, float* z_next, float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next,
+                                      int mean_type, int B, int64_t n, void* stream) {
+    return dpm_solver_step_launch<true>("gmk_dpm_solver_step_dt", v, v_uncond, cond_w, thr, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x,
+                                        coef_prev, is_last, z_next, x_pred, eps_pred, z_dup, logsnr_next, mean_type, B, n, stream);
+}
+
+extern "C" int gmk_dyn_threshold(const float* v, const float* v_uncond, const float* cond_w, const float* z, float logsnr_t, int k_lo,
+                                 float frac, float* s_out, float* q_out, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && z && s_out, "gmk_dyn_threshold: null pointer");
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_dyn_threshold");
+    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_dyn_threshold: v_uncond and cond_w go together");
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0 && n < ((int64_t)1 << 31), "gmk_dyn_threshold: bad shape B=%d n=%lld (n < 2^31)", B, (long long)n);
+    GMK_REQUIRE(k_lo >= 0 && k_lo < n, "gmk_dyn_threshold: rank k_lo = %d outside [0, n = %lld)", k_lo, (long long)n);
+    GMK_REQUIRE(frac >= 0.0f && frac < 1.0f, "gmk_dyn_threshold: frac = %g outside [0, 1)", (double)frac);
+    GMK_REQUIRE(isfinite(logsnr_t), "gmk_dyn_threshold: non-finite time");
+    dyn_threshold_kernel<<<B, 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, logsnr_t, (uint32_t)k_lo, frac, s_out, q_out, (uint32_t)n,
+                                                            mean_type);
+    return gmk_check_launch("gmk_dyn_threshold");
 }
 
 extern "C" int gmk_inpaint_merge(float* z, const float* x0, const uint8_t* mask, float alpha_s, float sigma_s, float a, float b,
@@ -772,8 +977,8 @@ extern "C" int gmk_ddim_step_vec(const float* v, const float* v_uncond, const fl
     GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_ddim_step_vec: v_uncond and cond_w go together");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_ddim_step_vec: bad shape");
     const int gx = row_grid(n, 256);
-    sampler_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, nullptr, 0.f, 0.f, 0, z_next, x_pred,
-                                                                     eps_pred, n, logsnr_t, logsnr_s, mean_type);
+    sampler_step_kernel<false><<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, nullptr, 0.f, 0.f, 0, z_next, x_pred,
+                                                                            eps_pred, n, logsnr_t, logsnr_s, mean_type);
     return gmk_check_launch("gmk_ddim_step_vec");
 }
 

@@ -23,7 +23,7 @@ import os
 import torch
 
 from .. import common, ops, parallel
-from .gaussian_diffusion import GaussianDiffusion, PhiloxStream
+from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -62,6 +62,8 @@ def make_plugin(GMBase, AttrDict):
                                        # <model>/test/ode_nlogp) of the sampling net on N steps; not in the reference, off by default
         DG.inpaint_eval = 0            # r >= 1: evaluate() also fills in the bottom half of the first 25 test images (RePaint, resample = r) as
                                        # last_eval['inpaint'] / grid 'inpaint'; not in the reference, off by default
+        DG.dyn_threshold = 0.0         # p in (0, 1]: sample() / evaluate() / inpaint() clamp each image's x-hat to its own p-th percentile of |x| and rescale
+                                       # (dynamic thresholding, Saharia et al. 2022; e.g. 0.995) instead of the clip at 1; not in the reference, off by default
         DG.grad_clip = 0.0             # c > 0: clip the global gradient norm to c inside the optimiser step (torch.nn.utils.clip_grad_norm_'s rule) and
                                        # report train/grad_norm, train/skipped_steps; implies skip_nonfinite; not in the reference, off by default
         DG.skip_nonfinite = 0          # 1: a step whose gradients hold an inf or a NaN changes nothing (the guard of the reference's GradScaler.step)
@@ -104,11 +106,12 @@ def make_plugin(GMBase, AttrDict):
             if self.inpaint_eval < 0:
                 raise ValueError(f"inpaint_eval = {self.inpaint_eval}: 0 (off) or the resample count r >= 1")
             self.binarize = int(get("binarize"))
+            dyn_threshold = dyn_threshold_check(get("dyn_threshold"))
             seed = int(get("seed")) * 1000 + parallel.rank()
             self.diffusion = GaussianDiffusion(mean_type=get("mean_type"), num_steps=int(get("timesteps")),
                                                sampler=get("sampler"), teacher_net=self.teacher_net,
                                                teacher_mode=get("teacher_mode"), sample_cond_w=get("sample_cond_w"),
-                                               seed=seed)
+                                               seed=seed, dyn_threshold=dyn_threshold)
             self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
             # EMA of the weights (an extension): a second SimpleUnet of the same arena layout, so one fused launch updates both.  It is seeded
             # from `net` at the first optimiser step (after a data-parallel broadcast of the initial weights) or by a checkpoint load.

@@ -10,6 +10,8 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
 * DPM-Solver++(2M) update              gmk_dpm_solver_step (sampler='dpmpp_2m': an extension, no reference call site)
 * variational bound (`nll`)            gmk_q_sample_logsnr, gmk_vlb_term, gmk_vlb_endpoints (an extension, no reference call site)
 * RePaint inpainting (`inpaint`)       gmk_inpaint_merge after the update (an extension, no reference call site)
+* dynamic thresholding (`dyn_threshold=p`)  gmk_dyn_threshold, then gmk_sampler_step_dt / gmk_dpm_solver_step_dt (Saharia et al. 2022, section 2.3;
+                                        an extension, no reference call site)
 * probability-flow ODE (`encode`, `decode`, `ode_nll`)  gmk_pf_ode_step, gmk_rng_rademacher, gmk_dequantize and the network's input gradient
                                         (SimpleUnet.input_vjp_hip, gmk_stem_dgrad) (an extension, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
@@ -68,6 +70,37 @@ def dpm_solver_coefs(num_steps):
         rows.append(DpmCoef(i, lt, ls, h, sigma(ls) / sigma(lt), -alpha(ls) * math.expm1(-h), k))
         h_prev = h
     return rows
+
+
+def dyn_threshold_check(p):
+    """The dynamic-thresholding option: 0 is off, else the percentile p in (0, 1].  -> float(p), or ValueError (NaN included)."""
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise ValueError(f"dyn_threshold = {p!r}: 0 (off) or a percentile in (0, 1]") from None
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dyn_threshold = {p}: 0 (off) or a percentile in (0, 1]")
+    return p
+
+
+def dyn_threshold_rank(p, n):
+    """Where the p-quantile (0 < p <= 1) of n sorted values lies, by torch.quantile's linear rule: pos = p (n - 1) in double, k_lo = floor(pos),
+    frac = fp32(pos - k_lo); the quantile is a[k_lo] + frac (a[min(k_lo + 1, n - 1)] - a[k_lo]).  The arguments of gmk_dyn_threshold, which asks
+    for 0 <= frac < 1: a remainder within half an fp32 ulp below 1 (it would round to 1.0f) names the next rank itself, (k_lo + 1, 0).
+    p = 1 gives (n - 1, 0), n = 1 gives (0, 0).  -> (k_lo, frac) as Python int and float."""
+    p, n = float(p), int(n)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"dyn_threshold_rank: p = {p} outside (0, 1]")
+    if n < 1 or n >= 1 << 31:
+        raise ValueError(f"dyn_threshold_rank: n = {n} outside [1, 2^31)")
+    pos = p * (n - 1)
+    k_lo = min(int(math.floor(pos)), n - 1)
+    frac = float(np.float32(pos - k_lo))
+    if frac >= 1.0:
+        k_lo, frac = k_lo + 1, 0.0
+    if k_lo >= n - 1:                       # the top rank has no neighbour above it
+        k_lo, frac = n - 1, 0.0
+    return k_lo, frac
 
 
 InpaintCoef = namedtuple("InpaintCoef", "i lt ls alpha_s sigma_s a b is_last")
@@ -230,9 +263,14 @@ class _VLoss(torch.autograd.Function):
 
 class GaussianDiffusion:
     def __init__(self, *, mean_type, num_steps, teacher_net=None, teacher_mode=None, sampler="ddim", sample_cond_w=None,
-                 seed=0):
+                 seed=0, dyn_threshold=0.0):
         if mean_type not in ops.MEAN_TYPES:                     # :70-71
             raise NotImplementedError(mean_type)
+        # dynamic thresholding of the samplers' x-hat (Saharia et al. 2022, section 2.3; an extension, no reference call site): 0 is off (the
+        # reference's static clip, the same launches as ever), else each image's x-hat is the unclipped (guided) prediction clamped to its own
+        # p-th percentile s of |x| (s >= 1) and divided by s.  sample() and inpaint() only: the ODE is unclipped by definition and the
+        # training loss keeps the reference's clip.
+        self.dyn_threshold = dyn_threshold_check(dyn_threshold)
         self.mean_type = mean_type
         self.num_steps = num_steps
         self.teacher_net = teacher_net
@@ -720,13 +758,17 @@ class GaussianDiffusion:
                 noise = None
                 if self.sampler == "noisy":
                     noise = ops.aligned(noises[i]) if noises is not None else ops.rng_normal(tuple(z_t.shape), self.rng.seed, offs[f] + q0, dev)   # :241
+                # dynamic thresholding: one select launch per network evaluation (per image, so a half-batch gives the whole batch's bits)
+                thr = None
+                if self.dyn_threshold:
+                    thr = ops.dyn_threshold(v, z_t, lt, self.dyn_threshold, v_uncond=vu, cond_w=w, mean_type=self.mean_type)
                 if dpm is not None:
                     c = dpm[it]
                     z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, c.coef_z, c.coef_x, c.coef_prev, i == 0, v_uncond=vu, cond_w=w,
-                                                      want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
+                                                      want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr)
                 else:
                     z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, i == 0, v_uncond=vu, cond_w=w, noise=noise, want_pred=record,
-                                                   mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
+                                                   mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr)
                 if guided:
                     z_t, z2 = z_t
                 if inp is not None:             # the known region, then (all passes but the step's last) the jump back to time t

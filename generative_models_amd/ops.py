@@ -853,9 +853,9 @@ def v_loss(v, z, x, eps, logsnr, grad_scale=None, loss_type=0, mean_type="v"):
     return loss_b, xm, em, dv
 
 
-def _sampler_io(v, z, same_shape, cond_w, want_pred, dup, logsnr_next):
-    """The checks and outputs `sampler_step` and `dpm_solver_step` share.  same_shape: (tensor or None, name) pairs of z's shape.
-    -> (B, n, z_next, z2 (None without dup), x_pred, eps_pred)"""
+def _sampler_check(v, z, same_shape, cond_w):
+    """The input checks `sampler_step`, `dpm_solver_step` and `dyn_threshold` share.  same_shape: (tensor or None, name) pairs of z's shape.
+    -> (B, n)"""
     _f32(v, "v"); _f32(z, "z")
     B = z.shape[0]
     n = z.numel() // B
@@ -865,6 +865,13 @@ def _sampler_io(v, z, same_shape, cond_w, want_pred, dup, logsnr_next):
             _f32(t, nm); assert t.shape == z.shape
     if cond_w is not None:
         _f32(cond_w, "cond_w"); assert cond_w.numel() == B
+    return B, n
+
+
+def _sampler_io(v, z, same_shape, cond_w, want_pred, dup, logsnr_next):
+    """The checks and outputs `sampler_step` and `dpm_solver_step` share.  same_shape: as in `_sampler_check`.
+    -> (B, n, z_next, z2 (None without dup), x_pred, eps_pred)"""
+    B, n = _sampler_check(v, z, same_shape, cond_w)
     z2 = torch.empty((2 * B,) + tuple(z.shape[1:]), device=z.device, dtype=z.dtype) if dup else None
     z_next = z2[:B] if dup else torch.empty_like(z)
     xp = torch.empty_like(z) if want_pred else None
@@ -874,26 +881,60 @@ def _sampler_io(v, z, same_shape, cond_w, want_pred, dup, logsnr_next):
     return B, n, z_next, z2, xp, ep
 
 
+def _thr_check(thr, B):
+    """`thr` of the *_dt entries: fp32 [B], the per-image threshold `dyn_threshold` returns."""
+    _f32(thr, "thr")
+    if thr.dim() != 1 or thr.numel() != B:
+        raise ValueError(f"thr: shape {tuple(thr.shape)}, expected ({B},)")
+    return thr
+
+
 def sampler_step(v, z, logsnr_t, logsnr_s, is_last, v_uncond=None, cond_w=None, noise=None, want_pred=False, mean_type="v",
-                 dup=False, logsnr_next=None):
+                 dup=False, logsnr_next=None, thr=None):
     """dup: z_next is returned as the first half of a [2B, ...] tensor whose second half holds the same values (z2 = returned[1]);
-    logsnr_next: fp32 [B] (or [2B] with dup) filled with logsnr_s."""
+    logsnr_next: fp32 [B] (or [2B] with dup) filled with logsnr_s.  thr: None, or fp32 [B] - dynamic thresholding (gmk_sampler_step_dt):
+    x-hat is the unclipped (guided) prediction clamped to +-thr[b] and divided by thr[b] (`dyn_threshold` gives thr)."""
     B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((v_uncond, "v_uncond"), (noise, "noise")), cond_w, want_pred, dup, logsnr_next)
-    check(lib.gmk_sampler_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(noise), float(logsnr_t), float(logsnr_s),
-                               int(is_last), _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next),
-                               MEAN_TYPES[mean_type], B, n, _s()), "sampler_step")
+    tail = (float(logsnr_t), float(logsnr_s), int(is_last), _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next),
+            MEAN_TYPES[mean_type], B, n, _s())
+    if thr is None:
+        check(lib.gmk_sampler_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(noise), *tail), "sampler_step")
+    else:
+        check(lib.gmk_sampler_step_dt(_p(v), _p(v_uncond), _p(cond_w), _p(_thr_check(thr, B)), _p(z), _p(noise), *tail), "sampler_step_dt")
     return ((z_next, z2) if dup else z_next), xp, ep
 
 
 def dpm_solver_step(v, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x, coef_prev, is_last, v_uncond=None, cond_w=None, want_pred=False,
-                    mean_type="v", dup=False, logsnr_next=None):
+                    mean_type="v", dup=False, logsnr_next=None, thr=None):
     """One DPM-Solver++(2M) step (gmk_dpm_solver_step).  x_hist: fp32 [B, ...], the previous x-hat, overwritten with this step's (not read
-    when coef_prev == 0).  Arguments and returns otherwise as `sampler_step` (no noise: the solver is deterministic)."""
+    when coef_prev == 0).  Arguments and returns otherwise as `sampler_step` (no noise: the solver is deterministic); thr as there
+    (gmk_dpm_solver_step_dt)."""
     B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((x_hist, "x_hist"), (v_uncond, "v_uncond")), cond_w, want_pred, dup, logsnr_next)
-    check(lib.gmk_dpm_solver_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(x_hist), float(logsnr_t), float(logsnr_s), float(coef_z),
-                                  float(coef_x), float(coef_prev), int(is_last), _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None,
-                                  _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()), "dpm_solver_step")
+    tail = (_p(x_hist), float(logsnr_t), float(logsnr_s), float(coef_z), float(coef_x), float(coef_prev), int(is_last), _p(z_next), _p(xp),
+            _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s())
+    if thr is None:
+        check(lib.gmk_dpm_solver_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), *tail), "dpm_solver_step")
+    else:
+        check(lib.gmk_dpm_solver_step_dt(_p(v), _p(v_uncond), _p(cond_w), _p(_thr_check(thr, B)), _p(z), *tail), "dpm_solver_step_dt")
     return ((z_next, z2) if dup else z_next), xp, ep
+
+
+DYN_THRESHOLD_KEYS = 12288      # kDynKeys of csrc/diffusion_ew.hip: images of up to this many values are selected from LDS, larger ones re-read
+
+
+def dyn_threshold(v, z, logsnr_t, p, v_uncond=None, cond_w=None, mean_type="v", want_q=False):
+    """The per-image threshold of dynamic thresholding (Saharia et al. 2022, section 2.3; gmk_dyn_threshold; an extension): s[b] = max(1, q[b]),
+    q[b] the p-quantile (0 < p <= 1, torch.quantile's linear rule, exact order statistics) of |x_raw[b]|, x_raw the UNCLIPPED (guided, when
+    v_uncond / cond_w are given) data prediction of the network output v at (z, logsnr_t).  v, z, v_uncond: fp32 [B, ...]; cond_w: fp32 [B].
+    -> s (fp32 [B]: the `thr=` of `sampler_step` / `dpm_solver_step`), or (s, q) with want_q."""
+    from .diffusion.gaussian_diffusion import dyn_threshold_rank
+    B, n = _sampler_check(v, z, ((v_uncond, "v_uncond"),), cond_w)
+    k_lo, frac = dyn_threshold_rank(p, n)
+    s = torch.empty((B,), device=z.device, dtype=torch.float32)
+    q = torch.empty_like(s) if want_q else None
+    check(lib.gmk_dyn_threshold(_p(v), _p(v_uncond), _p(cond_w), _p(z), float(logsnr_t), k_lo, frac, _p(s), _p(q), MEAN_TYPES[mean_type],
+                                B, n, _s()), "dyn_threshold")
+    return (s, q) if want_q else s
 
 
 def inpaint_merge(z, x0, mask, alpha_s, sigma_s, a, b, is_last, renoise, logsnr_t, logsnr_s, seed, offset, q0=0, B_total=None, z_dup=None,

@@ -314,6 +314,29 @@ int gmk_sampler_step(const float* v, const float* v_uncond, const float* cond_w,
 int gmk_dpm_solver_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float* x_hist, float logsnr_t,
                         float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last, float* z_next, float* x_pred,
                         float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+/* dynamic thresholding of the data prediction (Saharia et al. 2022, Imagen, section 2.3); an extension, no reference call site.
+ *   x_raw: the UNCLIPPED prediction of one network evaluation at (z, logsnr_t): x_c = x(v) by mean_type (gmk_v_loss's formulas); unguided
+ *     x_raw = x_c; guided e_c = eps(z, x_c), e_u = eps(z, x(v_uncond)), e = (1 + w_b) e_c + (-w_b) e_u, x_raw = x(z, e) - gmk_sampler_step's
+ *     guidance without its three clips (a prediction clipped at +-1 before the extrapolation would defeat the threshold).  eps(z, .) and x(z, .)
+ *     are affine and inverse to each other, so this is (1 + w_b) x_c + (-w_b) x(v_uncond), the form the kernels evaluate: the round trip through
+ *     eps space cancels in fp32 at low SNR (1e-3 relative in x_raw at logsnr -20).
+ *   gmk_dyn_threshold: per image b, q_b = a[k_lo] + frac (a[hi] - a[k_lo]) in fp32, a = |x_raw[b]| sorted ascending, hi = min(k_lo + 1, n - 1):
+ *     torch.quantile's linear rule for p with p (n - 1) = k_lo + frac (the host splits it in double).  a[k_lo] and a[hi] are exact order
+ *     statistics (a radix select over the values' bits in LDS, one workgroup per image; no floating-point atomics: the same call gives the same
+ *     bits).  s_out[b] = max(1, q_b); q_out (optional, B floats) receives q_b itself.  0 <= k_lo < n < 2^31, 0 <= frac < 1; any n >= 1 (images of up
+ *     to 12,288 values are read once and selected in LDS, larger ones are re-read per pass).  Non-finite inputs give unspecified values, nothing else.
+ *   gmk_sampler_step_dt / gmk_dpm_solver_step_dt: gmk_sampler_step / gmk_dpm_solver_step with x_hat = min(max(x_raw, -thr_b), thr_b) / thr_b (a true
+ *     division) in place of the clipped prediction; eps_hat = eps(z, x_hat) and everything after it (the update, x_hist, the is_last select, z_dup,
+ *     logsnr_next) unchanged.  thr: B floats, required (gmk_dyn_threshold's s_out).  With thr = 1 and no guidance they give the bits of the entries
+ *     without _dt: the same kernels, instantiated a second time. */
+int gmk_dyn_threshold(const float* v, const float* v_uncond, const float* cond_w, const float* z, float logsnr_t, int k_lo, float frac,
+                      float* s_out, float* q_out, int mean_type, int B, int64_t n, void* stream);
+int gmk_sampler_step_dt(const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z, const float* noise,
+                        float logsnr_t, float logsnr_s, int is_last, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
+                        float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+int gmk_dpm_solver_step_dt(const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z, float* x_hist,
+                           float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last, float* z_next,
+                           float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
 /* RePaint inpainting merge (Lugmayr et al. 2022, Algorithm 1, jump length 1); an extension, no reference call site.  In place on z (B x n,
  * fp32), after the sampler update of a step t -> s has written it.  mask: uint8 B x n in x's element order, nonzero = known pixel; x0: the
  * known image (B x n fp32).  n % 4 == 0.
