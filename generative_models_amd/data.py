@@ -7,6 +7,9 @@ Transform chain, in the reference's order (gms/common.py:104-111):
     ToTensor()               uint8 HxW -> float32 [1, H, W] / 255
     binarize:  (x > 0.5).float()          else:  x.float(); 2 * x - 1
     pad32:     F.pad(x, (2, 2, 2, 2))     (zeros — also for the [-1, 1] data, whose background is -1)
+
+`DeviceDataset` (an extension, `--data_device 1`) keeps a split on the GPU as uint8 and runs the same chain inside the one HIP launch that
+assembles a batch; `load_cifar10` / `load_npy` read its other two sources.
 """
 import gzip
 import os
@@ -138,3 +141,101 @@ class SyntheticMNIST:
             if self.pad32:
                 x = torch.nn.functional.pad(x, (2, 2, 2, 2))       # :110-111 (zeros)
             yield x, labels
+
+
+# ---- device-resident datasets (an extension: the reference's DataLoader has no counterpart) -------------------------------------------
+CIFAR10_FILES = {True: tuple(f"data_batch_{i}.bin" for i in range(1, 6)), False: ("test_batch.bin",)}
+
+
+def load_cifar10(root):
+    """-> ((train_images, train_labels), (test_images, test_labels)): uint8 [N, 3, 32, 32] and uint8 [N], from the binary version of CIFAR-10
+    under <root>/cifar-10-batches-bin/ - records of 1 label byte + 3072 pixel bytes, the R, G and B planes of a 32 x 32 image in that order."""
+    folder = os.path.join(root, "cifar-10-batches-bin")
+    out = []
+    for train in (True, False):
+        parts = []
+        for name in CIFAR10_FILES[train]:
+            path = os.path.join(folder, name)
+            if not os.path.exists(path):
+                raise FileNotFoundError(f"{name} not found under {folder} (CIFAR-10 cannot be downloaded here: no network); place the six "
+                                        f"files of the binary version (cifar-10-binary.tar.gz, unpacked) there, or use --data npy")
+            raw = np.fromfile(path, dtype=np.uint8)
+            if raw.size == 0 or raw.size % 3073:
+                raise ValueError(f"{path}: {raw.size} bytes is not a whole number of 3073-byte CIFAR-10 records")
+            parts.append(raw.reshape(-1, 3073))
+        rec = np.concatenate(parts)
+        out.append((np.ascontiguousarray(rec[:, 1:]).reshape(-1, 3, 32, 32), np.ascontiguousarray(rec[:, 0])))
+    return tuple(out)
+
+
+def load_npy(root):
+    """-> ((train_images, train_labels), (test_images, test_labels)) from <root>/{train,test}_images.npy (uint8 [N, H, W] or [N, C, H, W])
+    and <root>/{train,test}_labels.npy (integers in 0..255, [N])."""
+    out = []
+    for split in ("train", "test"):
+        arrays = []
+        for kind in ("images", "labels"):
+            path = os.path.join(root, f"{split}_{kind}.npy")
+            if not os.path.exists(path):
+                raise FileNotFoundError(f"{split}_{kind}.npy not found under {root}; --data npy reads {{train,test}}_images.npy (uint8 "
+                                        f"[N, H, W] or [N, C, H, W]) and {{train,test}}_labels.npy there")
+            arrays.append(np.load(path, allow_pickle=False))
+        images, labels = arrays
+        if images.dtype != np.uint8 or images.ndim not in (3, 4):
+            raise ValueError(f"{root}/{split}_images.npy: {images.dtype} {images.shape}, expected uint8 [N, H, W] or [N, C, H, W]")
+        out.append((images, labels))
+    return tuple(out)
+
+
+class DeviceDataset:
+    """One split held on the GPU as the uint8 bytes it came as; every batch is ONE launch of ops.batch_gather (gather by a device-side
+    permutation, the transform chain of `transform`, zero border, random horizontal flip) - no host gather, no host-to-device copy and no
+    host sync per step, where `MnistLoader` indexes an fp32 host tensor and copies the result every step.  Same batch stream shape as
+    `MnistLoader`: shuffled every epoch, last partial batch dropped, `len` = (N // world) // bs.
+
+    The shuffle has a host restatement (tests/loader_ref.py).  Epoch e (`epoch`: counts __iter__ calls from 0, settable) sorts the keys
+    rng_uniform((N,), seed, e * ((N + 3) // 4)) with a STABLE sort (24-bit keys tie at N = 60 000); this rank takes perm[rank::world] and
+    batch i its slice [i bs, (i + 1) bs).  Every rank derives the same permutation from the shared seed: nothing is broadcast.  The flips
+    of the k-th batch this loader yields (k runs across epochs) come from the stream (seed + 1, k * ((bs + 3) // 4))."""
+
+    def __init__(self, images_u8, labels, bs, *, binarize, pad, flip_p=0.0, device, seed=0, rank=0, world=1):
+        images = np.asarray(images_u8)
+        labels = np.asarray(labels)
+        if images.dtype != np.uint8 or images.ndim not in (3, 4):
+            raise ValueError(f"images: {images.dtype} {images.shape}, expected uint8 [N, H, W] or [N, C, H, W]")
+        if images.ndim == 3:
+            images = images[:, None]
+        if labels.ndim != 1 or labels.shape[0] != images.shape[0] or labels.dtype.kind not in "iu":
+            raise ValueError(f"labels: {labels.dtype} {labels.shape}, expected integers [{images.shape[0]}]")
+        if labels.size and (labels.min() < 0 or labels.max() > 255):
+            raise ValueError(f"labels span [{labels.min()}, {labels.max()}]: they are kept as uint8")
+        if not 0.0 <= float(flip_p) <= 1.0:
+            raise ValueError(f"flip_p = {flip_p}: a probability")
+        if not str(device).startswith("cuda"):
+            raise ValueError(f"DeviceDataset on {device!r}: the dataset lives on a GPU (use MnistLoader for host batches)")
+        self.bs, self.rank, self.world = int(bs), int(rank), int(world)
+        self.binarize, self.pad, self.flip_p = int(bool(binarize)), int(pad), float(flip_p)
+        self.seed, self.epoch, self._k = int(seed), 0, 0
+        self.images = torch.from_numpy(np.array(images, dtype=np.uint8, copy=True)).to(device)      # uploaded once, as uint8 (a copy: IDX arrays are read-only views)
+        self.labels = torch.from_numpy(labels.astype(np.uint8)).to(device)
+        if len(self) < 1:
+            raise ValueError(f"{images.shape[0]} images over {self.world} ranks give no batch of {self.bs}")
+
+    def __len__(self):
+        return (self.images.shape[0] // self.world) // self.bs
+
+    def __iter__(self):
+        from . import ops
+        N = self.images.shape[0]
+        keys = ops.rng_uniform((N,), self.seed, self.epoch * ((N + 3) // 4), self.images.device)
+        self.epoch += 1
+        perm = torch.sort(keys, stable=True).indices[self.rank::self.world].contiguous()      # built once per epoch
+        return self._batches(perm)
+
+    def _batches(self, perm):
+        from . import ops
+        quads = (self.bs + 3) // 4
+        for i in range(len(self)):
+            k, self._k = self._k, self._k + 1
+            yield ops.batch_gather(self.images, self.labels, perm[i * self.bs:(i + 1) * self.bs], pad=self.pad, binarize=self.binarize,
+                                   flip_p=self.flip_p, seed=self.seed + 1, offset=k * quads, trusted=True)

@@ -70,6 +70,7 @@ def make_plugin(GMBase, AttrDict):
         DG.lr_warmup = 0               # W > 0: lr times min(1, (t + 1) / W) after t steps, under either lr_scheduler
         DG.lr_decay_steps = 0          # 'cosine': steps from lr down to lr_min_ratio * lr, counted from the end of the warm-up
         DG.lr_min_ratio = 0.1
+        DG.image_size = 0              # S > 0: images are S x S (CIFAR-10: 32 with in_channels 3); 0: the reference's 28, or 32 with pad32
 
         def __init__(self, G):
             super().__init__(G)
@@ -141,6 +142,11 @@ def make_plugin(GMBase, AttrDict):
                                        grad_clip=grad_clip, skip_nonfinite=bool(int(get("skip_nonfinite"))), lr_scheduler=get("lr_scheduler"),
                                        lr_warmup=lr_warmup, lr_decay_steps=lr_decay_steps, lr_min_ratio=lr_min_ratio)
             self.size = 32 if ("pad32" in G and G.pad32) else 28
+            if int(get("image_size")) < 0:
+                raise ValueError(f"image_size = {get('image_size')}: 0 (28, or 32 with pad32) or the side of the square images")
+            self._size_declared = int(get("image_size")) > 0
+            if self._size_declared:
+                self.size = int(get("image_size"))
             self._aux_rng = PhiloxStream(seed + 7919)
             self._sync = None
 
@@ -185,8 +191,18 @@ def make_plugin(GMBase, AttrDict):
                 metrics["lr"] = torch.tensor(opt.last_lr, dtype=torch.float64)
             return metrics
 
+        def _check_image(self, x):
+            """A batch that cannot be this model's fails here, by name, instead of deep inside a kernel wrapper: the channel count always, the
+            spatial size once `image_size` declares it (with image_size = 0 callers keep training at sizes of their own, as before; `size`
+            then only shapes sample() and evaluate())."""
+            C, S = self.net.in_channels, self.size
+            if x.dim() != 4 or x.shape[1] != C or (self._size_declared and tuple(x.shape[2:]) != (S, S)):
+                raise ValueError(f"batch of shape {tuple(x.shape)}: this model takes [B, {C}, {S}, {S}] (in_channels = {C}, image size {S}: set "
+                                 f"--in_channels / --image_size / --pad32 to match the data)")
+
         # -- training (diffusion_model.py:63-74)
         def train_step(self, x, y):
+            self._check_image(x)
             B = x.shape[0]
             # classifier-free label drop (:67): mutates the caller's y in place like the reference, but the mask comes from the
             # device RNG inside one small kernel (the reference's CPU-generated mask forces a host sync every step)
@@ -267,6 +283,7 @@ def make_plugin(GMBase, AttrDict):
 
         # -- loss (:76-80): differentiable through torch.autograd; used by the driver's test-set pass
         def loss(self, x, y):
+            self._check_image(x)
             metrics = self.diffusion.training_losses(net=partial(self.net, guide=y), x=x)
             metrics = {key: val.mean() for key, val in metrics.items()}
             if self.nlogp_samples > 0:              # the unconditional bound, nats/dim; the driver logs `nlogp` as eval/nlogp (gms/main.py:170-174)

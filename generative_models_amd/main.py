@@ -9,7 +9,8 @@ an `EpochLog` that keeps device tensors on the device until the epoch ends (the 
 serialise host and GPU every step), rank-aware logging and checkpointing for one-process-per-GPU runs.
 
 Environment differences (no network, no tensorboard / ignite in the image): `--data synthetic` (default) is an MNIST-shaped
-generator, `--data mnist` reads the IDX files if they are present; the writer is `common.NullWriter`.
+generator, `--data mnist` reads the IDX files if they are present; the writer is `common.NullWriter`.  `--data_device 1` keeps
+`mnist`, `cifar10` or an `npy` array on the GPU and assembles every batch there (data.DeviceDataset).
 
     python -m generative_models_amd.main --model=diffusion --epochs=1 --bs 32
     torchrun --nproc-per-node 8 -m generative_models_amd.main --model=diffusion      (one process per GPU, RCCL)
@@ -47,10 +48,13 @@ DG.classifier = Path("./weights/classifier.pt")
 DG.eval_heavy = 0
 DG.skip_training = 0
 # additions
-DG.data = "synthetic"      # 'synthetic' | 'mnist' (IDX files under <data_root>/MNIST/raw)
+DG.data = "synthetic"      # 'synthetic' | 'mnist' (IDX files under <data_root>/MNIST/raw) | with data_device 1 also 'cifar10'
+                           # (<data_root>/cifar-10-batches-bin) and 'npy' (<data_root>/{train,test}_{images,labels}.npy)
 DG.data_root = Path("data")
 DG.train_batches = 8       # synthetic batches per epoch (per rank)
 DG.test_batches = 2
+DG.data_device = 0         # 1: the dataset stays on the GPU as uint8 and one HIP kernel assembles each batch (data.DeviceDataset)
+DG.flip_p = 0.0            # probability of a horizontal flip per train image (data_device 1 only)
 
 SyntheticMNIST = datasets.SyntheticMNIST       # kept importable from here
 
@@ -244,8 +248,42 @@ def _feature_extractors(G, device, test_ds=None):
     return autoencoder, classifier
 
 
+DEVICE_DATA = ("mnist", "cifar10", "npy")
+
+
+def _check_data_flags(G):
+    """Flag combinations the data path does not serve, named before any model or file is touched."""
+    if G.data not in DEVICE_DATA + ("synthetic",):
+        raise ValueError(f"--data {G.data!r}: 'synthetic', 'mnist', or with --data_device 1 'cifar10' / 'npy'")
+    if G.data_device not in (0, 1):
+        raise ValueError(f"--data_device {G.data_device}: 0 (host loader) or 1 (dataset on the GPU)")
+    if not 0.0 <= G.flip_p <= 1.0:
+        raise ValueError(f"--flip_p {G.flip_p}: a probability")
+    if G.data_device and G.data not in DEVICE_DATA:
+        raise ValueError(f"--data_device 1 serves --data {' / '.join(DEVICE_DATA)}; --data {G.data} already draws on the device")
+    if not G.data_device and G.data in ("cifar10", "npy"):
+        raise ValueError(f"--data {G.data} needs --data_device 1 (there is no host loader for it)")
+    if G.flip_p > 0 and not G.data_device:
+        raise ValueError(f"--flip_p {G.flip_p} needs --data_device 1 (the flip is part of the device batch kernel)")
+
+
+def _device_datasets(G, device, rank, world):
+    root = str(G.data_root)
+    if G.data == "mnist":
+        train, test = ((datasets.read_idx(datasets._find(root, img)), datasets.read_idx(datasets._find(root, lab)))
+                       for img, lab in (datasets.FILES[True], datasets.FILES[False]))
+    else:
+        train, test = (datasets.load_cifar10 if G.data == "cifar10" else datasets.load_npy)(root)
+    common_kw = dict(binarize=G.binarize, pad=2 if G.pad32 else 0, device=device, rank=rank, world=world)
+    return (datasets.DeviceDataset(*train, G.bs, flip_p=G.flip_p, seed=1000, **common_kw),      # seeds as load_mnist's; flips on the train split only
+            datasets.DeviceDataset(*test, G.bs, flip_p=0.0, seed=1001, **common_kw))
+
+
 def _datasets(G, device):
     rank, world = parallel.rank(), parallel.world()
+    _check_data_flags(G)
+    if G.data_device:
+        return _device_datasets(G, device, rank, world)
     if G.data == "mnist":          # gms/main.py:84 `load_mnist`
         return datasets.load_mnist(G.bs, G.binarize, G.pad32, root=str(G.data_root), device=device, seed=1000, rank=rank, world=world)
     if G.data == "synthetic":
@@ -257,6 +295,7 @@ def _datasets(G, device):
 def load_model_and_data(argv=None):
     """-> (model, train_ds, test_ds, autoencoder, classifier, G), the reference's call shape (gms/main.py:43-92)."""
     G, Model = FlagSpace(DG).resolve(argv)
+    _check_data_flags(G)
     init_distributed()
     device = _run_device(G.device)
     model = Model(G=G).to(device)

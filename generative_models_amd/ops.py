@@ -763,6 +763,41 @@ def label_drop(y, p, seed, offset):
     return y
 
 
+def batch_gather(images, labels, index, *, pad, binarize, flip_p=0.0, seed=0, offset=0, trusted=False):
+    """-> (x fp32 [B, C, H + 2 pad, W + 2 pad], y int64 [B]), both FRESH on every call (train_step overwrites y in place): the transform chain
+    of data.transform on images[index] (uint8 [N, C, H, W] on the device), a zero border of `pad` pixels, and a mirror along W of the images
+    whose element of rng_uniform((B,), seed, offset) is below flip_p; y = labels[index] (uint8 [N]).  Unless `trusted`, 0 <= index < N is
+    checked with one host sync and a violation raises before anything is launched."""
+    seed, offset = check_stream(seed, offset)
+    for t, dtype, name in ((images, torch.uint8, "images"), (labels, torch.uint8, "labels"), (index, torch.int64, "index")):
+        if not t.is_cuda:
+            raise ValueError(f"{name}: expected a device tensor (the HIP path has no CPU fallback)")
+        if t.dtype != dtype:
+            raise ValueError(f"{name}: dtype {t.dtype}, expected {dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+        if t.device != images.device:
+            raise ValueError(f"{name}: on {t.device}, images on {images.device}")
+    if images.dim() != 4 or labels.dim() != 1 or index.dim() != 1 or labels.shape[0] != images.shape[0] or index.numel() == 0 or images.numel() == 0:
+        raise ValueError(f"batch_gather: images {tuple(images.shape)} (want [N, C, H, W]), labels {tuple(labels.shape)} (want [N]), "
+                         f"index {tuple(index.shape)} (want [B], B > 0)")
+    pad, binarize, flip_p = int(pad), int(binarize), float(flip_p)
+    if pad < 0 or binarize not in (0, 1) or not 0.0 <= flip_p <= 1.0:
+        raise ValueError(f"batch_gather: pad = {pad} (>= 0), binarize = {binarize} (0 or 1), flip_p = {flip_p} (in [0, 1])")
+    N, C, H, W = images.shape
+    B = index.numel()
+    if not trusted:
+        lo, hi = (int(v) for v in torch.stack((index.min(), index.max())).tolist())      # one sync
+        if lo < 0 or hi >= N:
+            raise ValueError(f"batch_gather: index values span [{lo}, {hi}], the dataset has {N} images")
+    x = torch.empty((B, C, H + 2 * pad, W + 2 * pad), device=images.device, dtype=torch.float32)
+    y = torch.empty((B,), device=images.device, dtype=torch.int64)
+    with _Timed("batch_gather_kernel", 0.0, _nbytes(x, y) + float(B * C * H * W + B), fixed=True):
+        check(lib.gmk_batch_gather(_p(images), _p(labels), _p(index), B, N, C, H, W, pad, binarize, flip_p, seed, offset, _p(x), _p(y), _s()),
+              "batch_gather")
+    return x, y
+
+
 def mean(x):
     """0-dim fp32 mean of a contiguous fp32 vector (fixed summation order)."""
     _f32(x, "x")

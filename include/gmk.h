@@ -258,6 +258,18 @@ int gmk_guide_onehot(const int64_t* guide, float* onehot, float* keep, int B, vo
 /* classifier-free label drop of DiffusionModel.train_step (diffusion_model.py:67 `y[torch.rand(B) < cf_drop_prob] = -1`), in
  * place on the caller's labels like the reference: y[b] = -1 where gmk_rng_uniform(seed, offset)[b] < p */
 int gmk_label_drop(int64_t* y, int B, float p, uint64_t seed, uint64_t offset, void* stream);
+/* one training batch from a dataset that lives on the device as the bytes it came as: the reference's transform chain
+ * (gms/common.py:104-111: ToTensor, then the threshold or 2 x - 1, then F.pad) applied to images[index], in one launch - what the
+ * reference's DataLoader workers do on the host (:116-131).  An extension (data.DeviceDataset), off by default.
+ *   images [N][C][H][W] uint8, labels [N] uint8, index [B] int64 with values in [0, N) - the caller guarantees it (ops.batch_gather checks)
+ *   x [B][C][H + 2 pad][W + 2 pad] fp32 (16-byte aligned; images / labels / index need their natural alignment only), y [B] int64
+ *   x = the bits of the CPU chain: float32(u8) / 255 (correctly rounded), binarize 1: > 0.5 ? 1 : 0, binarize 0: 2 x - 1; then a border of
+ *     `pad` ZEROS on each side (F.pad(x, (p, p, p, p)): 0 also for the [-1, 1] data, as in the reference)
+ *   flip: image b is mirrored along W (inside its border) where element b of gmk_rng_uniform(seed, offset) over B values is < flip_p -
+ *     gmk_label_drop's convention; flip_p = 0 draws nothing, flip_p = 1 mirrors every image
+ *   y[b] = labels[index[b]].  Any C H W: rows of whole 16-byte groups ((W + 2 pad) % 4 == 0) take the vector path, others a per-element one. */
+int gmk_batch_gather(const uint8_t* images, const uint8_t* labels, const int64_t* index, int B, int64_t N, int C, int H, int W, int pad,
+                     int binarize, float flip_p, uint64_t seed, uint64_t offset, float* x, int64_t* y, void* stream);
 /* out[0] = mean(x[0..n)), fixed summation order: the batch mean of the per-sample losses (diffusion_model.py:78) */
 int gmk_mean(const float* x, int n, float* out, void* stream);
 /* C[i][j] = (accumulate ? C[i][j] : 0) + rowscale[i] * (bias[j] + bias2[j] + sum_k fa(A[i*sa0 + k*sa1]) * fb(B[k*sb0 + j*sb1]))
