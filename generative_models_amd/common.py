@@ -149,6 +149,66 @@ class NullWriter:
         pass
 
 
+def frame_indices(T, max_frames):
+    """The frames of a T-frame trajectory an animation of at most `max_frames` (>= 2) keeps: all of them when they fit, else
+    idx_k = k (T - 1) // (F - 1), k = 0 .. F - 1 - evenly spread, strictly increasing, the first and the last always among them."""
+    F = int(max_frames)
+    if F < 2:
+        raise ValueError(f"max_frames = {max_frames}: at least 2 (the first and the last frame)")
+    if T <= F:
+        return list(range(T))
+    return [k * (T - 1) // (F - 1) for k in range(F)]
+
+
+class ImageWriter(NullWriter):
+    """NullWriter that also writes pictures: PNG for images, animated PNG for videos, under <logdir>/images/<tag with '/' as '_'>_<step:04d>.png
+    (an extension; the reference hands both to tensorboard).  `add_image` / `add_video` keep tensorboard's call surface for uint8 pictures on
+    either side; `write_frames` is the device path the models use: float samples in, one tiling kernel, one copy to the host, zlib."""
+
+    def __init__(self, logdir, max_frames=60):
+        super().__init__(logdir)
+        if int(max_frames) < 2:
+            raise ValueError(f"max_frames = {max_frames}: at least 2 (the first and the last frame)")
+        self.max_frames = int(max_frames)
+
+    def path_for(self, tag, step):
+        return Path(self.logdir) / "images" / f"{tag.replace('/', '_')}_{int(step):04d}.png"
+
+    def _write(self, tag, step, blob):
+        path = self.path_for(tag, step)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_bytes(blob)
+        return path
+
+    def add_image(self, tag, img, step):
+        """img: uint8 [C, H, W], C 1 or 3."""
+        from . import pngio
+        return self._write(tag, step, pngio.encode_png(*pngio.from_chw(img)))
+
+    def add_video(self, tag, vid, step, fps=4):
+        """vid: uint8 [1, T, C, H, W], C 1 or 3 (tensorboard's batch of videos, one video)."""
+        from . import pngio
+        if vid.ndim != 5 or vid.shape[0] != 1 or vid.shape[1] < 1:
+            raise ValueError(f"a video of shape {tuple(vid.shape)}: want uint8 [1, T, C, H, W]")
+        frames = [pngio.from_chw(frame) for frame in vid[0]]
+        _, W, H, C = frames[0]
+        return self._write(tag, step, pngio.encode_apng([f[0] for f in frames], W, H, C, fps))
+
+    def write_frames(self, tag, x, step, *, ncol=5, crop=0, fps=None):
+        """x: fp32 device tensor in [-1, 1], [N, C, H, W] -> a PNG of the images tiled `ncol` to a line, or [T, N, C, H, W] -> an APNG of such
+        frames (at most `max_frames` of them: frame_indices), at `fps` (default: the reference's min(frames // 3, 60), at least 1)."""
+        from . import ops, pngio
+        if x.dim() == 5 and x.shape[0] > self.max_frames:
+            x = x[torch.tensor(frame_indices(x.shape[0], self.max_frames), device=x.device)]
+        lines = ops.image_grid(x, ncol=ncol, crop=crop, row_prefix=1).cpu().numpy()
+        C = x.shape[-3]
+        height, width = lines.shape[-2], (lines.shape[-1] - 1) // C
+        if lines.ndim == 2:
+            return self._write(tag, step, pngio.encode_png(lines, width, height, C))
+        fps = max(1, min(lines.shape[0] // 3, 60)) if fps is None else fps
+        return self._write(tag, step, pngio.encode_apng(lines, width, height, C, fps))
+
+
 def write_grid(writer, tag, x, epoch):
     """25 samples as one 5x5 image (gms/common.py:177-180: '(n1 n2) c h w -> c (n1 h) (n2 w)')."""
     assert tuple(x.shape) == (25, 1, 28, 28)

@@ -341,6 +341,15 @@ def make_plugin(GMBase, AttrDict):
                 cond_w = 0.5 if y is not None else None
                 return self.diffusion.sample(net=net, init_x=noise, cond_w=cond_w, record=False)[0][-1]
 
+        def _crop(self):
+            """Pixels evaluate() and sample_uint8() cut from every side: the pad32 border (:93-94 `x[..., 2:-2, 2:-2]`)."""
+            return 2 if ("pad32" in self.G and self.G.pad32) else 0
+
+        def sample_uint8(self, n, y=None):
+            """sample(n, y) as bytes (an extension): uint8 [n, C, S', S'] on the device, quantised by evaluate()'s rule with the pad32 border cut -
+            the images of a dataset file (data.load_npy's layout)."""
+            return ops.to_uint8(self.sample(n, y), crop=self._crop())
+
         # -- inpainting (an extension): RePaint with this model's sampler on the net sample() uses
         def inpaint(self, x, mask, y=None, resample=1, seed=0):
             """Fill in the pixels of x ([B, C, S, S] in [-1, 1], the shape sample() returns) where `mask` (broadcastable to x, {0, 1}) is 0,
@@ -356,19 +365,24 @@ def make_plugin(GMBase, AttrDict):
 
         # -- evaluate (:89-111): 25 class-conditional samples without guidance, trajectories as uint8
         def evaluate(self, writer, x, y, epoch):
-            def proc(t):
-                t = ((t + 1) * 127.5).clamp(0, 255).to(torch.uint8).cpu()
-                if "pad32" in self.G and self.G.pad32:
-                    t = t[..., 2:-2, 2:-2]
-                return t
+            crop = self._crop()
+
+            def proc(t):                                              # :92's chain and the pad32 crop in one pass on the device, then the bytes move
+                return ops.to_uint8(t, crop=crop).cpu()
 
             stream = PhiloxStream(0)                                  # :99 torch.manual_seed(0)
             noise = stream.normal((25, self.net.in_channels, self.size, self.size), x.device)
             labels = torch.arange(25, dtype=torch.long, device=x.device) % 10   # :101
             zs, xs, eps = self.diffusion.sample(net=partial(self._sampling_net(), guide=labels), init_x=noise)
+            pictures = writer is not None and hasattr(writer, "write_frames")
+            if pictures:                                              # an extension (common.ImageWriter): files, from the float trajectories, any shape
+                writer.write_frames("samples", zs[-1], epoch, crop=crop)
+                writer.write_frames("sampling_process", zs, epoch, crop=crop)
+                writer.write_frames("diffusion_model/eps", eps, epoch, crop=crop)
+                writer.write_frames("diffusion_model/x", xs, epoch, crop=crop)
             zs, xs, eps = proc(zs), proc(xs), proc(eps)
             self.last_eval = {"samples": zs[-1], "sampling_process": zs, "eps": eps, "x": xs}
-            if writer is not None and self.net.in_channels == 1:        # :105-110, same tags
+            if not pictures and writer is not None and self.net.in_channels == 1:        # :105-110, same tags
                 common.write_grid(writer, "samples", zs[-1], epoch)
                 common.write_gridvid(writer, "sampling_process", zs, epoch)
                 common.write_gridvid(writer, "diffusion_model/eps", eps, epoch)
@@ -382,7 +396,9 @@ def make_plugin(GMBase, AttrDict):
                 z = self.diffusion.inpaint(net=partial(self._sampling_net(), guide=None if y is None else y[:k]), x0=x0, mask=mask, init_x=init,
                                            resample=self.inpaint_eval, seed=self.INPAINT_EVAL_SEED + 1)[0][-1]
                 self.last_eval["inpaint"] = proc(z)
-                if writer is not None and self.net.in_channels == 1 and k == 25:
+                if pictures:
+                    writer.write_frames("inpaint", z, epoch, crop=crop)
+                elif writer is not None and self.net.in_channels == 1 and k == 25:
                     common.write_grid(writer, "inpaint", self.last_eval["inpaint"], epoch)
             random.randint(0, 2 ** 32)                                # :111 keeps the host RNG consumption
 

@@ -9,7 +9,8 @@ an `EpochLog` that keeps device tensors on the device until the epoch ends (the 
 serialise host and GPU every step), rank-aware logging and checkpointing for one-process-per-GPU runs.
 
 Environment differences (no network, no tensorboard / ignite in the image): `--data synthetic` (default) is an MNIST-shaped
-generator, `--data mnist` reads the IDX files if they are present; the writer is `common.NullWriter`.  `--data_device 1` keeps
+generator, `--data mnist` reads the IDX files if they are present; the writer is `common.NullWriter`, or with `--save_images 1`
+`common.ImageWriter` (PNG / APNG files under <logdir>/images; `--dump_samples N` writes samples as an `npy` dataset).  `--data_device 1` keeps
 `mnist`, `cifar10` or an `npy` array on the GPU and assembles every batch there (data.DeviceDataset).
 
     python -m generative_models_amd.main --model=diffusion --epochs=1 --bs 32
@@ -21,6 +22,7 @@ import time
 from collections import defaultdict
 from pathlib import Path
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import yaml
@@ -55,6 +57,9 @@ DG.train_batches = 8       # synthetic batches per epoch (per rank)
 DG.test_batches = 2
 DG.data_device = 0         # 1: the dataset stays on the GPU as uint8 and one HIP kernel assembles each batch (data.DeviceDataset)
 DG.flip_p = 0.0            # probability of a horizontal flip per train image (data_device 1 only)
+DG.save_images = 0         # 1: evaluation samples go to <logdir>/images as PNG grids and APNG strips (common.ImageWriter)
+DG.image_frames = 60       # most frames an APNG keeps of a sampling trajectory (evenly spread, first and last always)
+DG.dump_samples = 0        # N > 0: after every checkpoint, N samples as <logdir>/samples_{images,labels}.npy (data.load_npy's format)
 
 SyntheticMNIST = datasets.SyntheticMNIST       # kept importable from here
 
@@ -134,7 +139,7 @@ class Session:
         self.autoencoder, self.classifier, self.G = autoencoder, classifier, G
         self.device = getattr(model, "run_device", G.device)
         self.lead = parallel.rank() == 0                               # rank 0 prints, writes hps.yaml and checkpoints
-        self.writer = common.NullWriter(G.logdir)
+        self.writer = common.ImageWriter(G.logdir, G.get("image_frames", 60)) if G.get("save_images", 0) else common.NullWriter(G.logdir)
 
     def _batches(self, ds):
         for batch in ds:
@@ -177,6 +182,26 @@ class Session:
                 log.set(key, vals)
             log.set("dt/eval_heavy", time.time() - started)
             print("DONE HEAVY EVAL")
+        if self.G.get("dump_samples", 0) > 0:
+            self.dump_samples(int(self.G.dump_samples))
+
+    def dump_samples(self, n):
+        """n samples of the model as a dataset: <logdir>/samples_images.npy (uint8 [n, C, H, W]) and samples_labels.npy (uint8 [n]), the
+        format of data.load_npy - renamed to train_* / test_*, a set `--data npy --data_device 1` trains on.  Drawn in batches of `bs`; with
+        class_cond the labels are arange(n) % 10 and the draw is guided as `sample(n, y)` is, else unconditional with labels 0."""
+        cond = bool(self.G.get("class_cond", 0))
+        labels = torch.arange(n, dtype=torch.long, device=self.device) % 10 if cond else torch.zeros(n, dtype=torch.long, device=self.device)
+        was_training = self.model.training
+        self.model.eval()
+        parts = []
+        for lo in range(0, n, int(self.G.bs)):
+            y = labels[lo:lo + int(self.G.bs)]
+            parts.append(self.model.sample_uint8(y.numel(), y.clone() if cond else None))
+        self.model.train(was_training)
+        logdir = Path(self.G.logdir)
+        np.save(logdir / "samples_images.npy", torch.cat(parts).cpu().numpy())
+        np.save(logdir / "samples_labels.npy", labels.cpu().numpy().astype(np.uint8))
+        print("DUMPED", n, "SAMPLES", logdir)
 
     def train_epoch(self, log):
         self.model.train()
@@ -267,6 +292,16 @@ def _check_data_flags(G):
         raise ValueError(f"--flip_p {G.flip_p} needs --data_device 1 (the flip is part of the device batch kernel)")
 
 
+def _check_image_flags(G):
+    """The flags of the picture and sample output, named before any model is built."""
+    if G.save_images not in (0, 1):
+        raise ValueError(f"--save_images {G.save_images}: 0 (no pictures) or 1 (PNG / APNG files under <logdir>/images)")
+    if G.image_frames < 2:
+        raise ValueError(f"--image_frames {G.image_frames}: at least 2 (an animation keeps the first and the last frame)")
+    if G.dump_samples < 0:
+        raise ValueError(f"--dump_samples {G.dump_samples}: 0 (off) or the number of samples to write after a checkpoint")
+
+
 def _device_datasets(G, device, rank, world):
     root = str(G.data_root)
     if G.data == "mnist":
@@ -296,6 +331,7 @@ def load_model_and_data(argv=None):
     """-> (model, train_ds, test_ds, autoencoder, classifier, G), the reference's call shape (gms/main.py:43-92)."""
     G, Model = FlagSpace(DG).resolve(argv)
     _check_data_flags(G)
+    _check_image_flags(G)
     init_distributed()
     device = _run_device(G.device)
     model = Model(G=G).to(device)

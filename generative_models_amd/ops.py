@@ -798,6 +798,59 @@ def batch_gather(images, labels, index, *, pad, binarize, flip_p=0.0, seed=0, of
     return x, y
 
 
+def _image_source(x, ranks, crop, what):
+    """The checks ops.to_uint8 and ops.image_grid share -> (x contiguous and 16-byte aligned, crop).  A slice or a misaligned view is copied,
+    not rejected."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise ValueError(f"{what}: x dtype {getattr(x, 'dtype', type(x))}, expected {torch.float32}")
+    if not x.is_cuda:
+        raise ValueError(f"{what}: x: expected a device tensor (the HIP path has no CPU fallback)")
+    if x.dim() not in ranks:
+        raise ValueError(f"{what}: x of rank {x.dim()}, shape {tuple(x.shape)} (want {' or '.join(ranks.values())})")
+    if x.numel() == 0:
+        raise ValueError(f"{what}: x of shape {tuple(x.shape)} is empty")
+    H, W = x.shape[-2:]
+    if isinstance(crop, bool) or crop != int(crop) or int(crop) < 0 or 2 * int(crop) >= min(H, W):
+        raise ValueError(f"{what}: crop = {crop} of {H} x {W} images (want 0 <= 2 crop < min(H, W))")
+    return aligned(x), int(crop)
+
+
+def to_uint8(x, crop=0):
+    """-> uint8 x.shape[:-2] + (H - 2 crop, W - 2 crop), FRESH on every call: ((x + 1) * 127.5).clamp(0, 255).to(torch.uint8) of
+    x[..., crop:H - crop, crop:W - crop] (fp32 [..., H, W] on the device, rank >= 2) in one pass - the bits of that torch chain, NaN -> 0."""
+    x, crop = _image_source(x, {r: f"rank {r}" for r in range(2, 9)}, crop, "to_uint8")
+    H, W = x.shape[-2:]
+    planes = x.numel() // (H * W)
+    out = torch.empty(tuple(x.shape[:-2]) + (H - 2 * crop, W - 2 * crop), device=x.device, dtype=torch.uint8)
+    with _Timed("to_uint8_kernel", 0.0, _nbytes(out) + 4.0 * out.numel(), fixed=True):
+        check(lib.gmk_to_uint8(_p(x), _p(out), planes, 1, H, W, crop, _s()), "to_uint8")
+    return out
+
+
+def image_grid(x, *, ncol, crop=0, gap=2, fill=0, out_channels=None, row_prefix=0):
+    """x fp32 [N, C, H, W] -> uint8 [GH, row], or [T, N, C, H, W] -> [T, GH, row], FRESH on every call: the images quantised as in to_uint8,
+    cropped and tiled `ncol` to a line with `gap` pixels of the byte `fill` around and between them (include/gmk.h: gmk_image_grid).
+    C 1 or 3; out_channels: C (default), or 3 with C = 1.  row = row_prefix + GW out_channels bytes, channels interleaved; row_prefix 1 puts
+    PNG's filter byte 0 in front of every line (pngio.encode_png takes that buffer as it is)."""
+    x, crop = _image_source(x, {4: "[N, C, H, W]", 5: "[T, N, C, H, W]"}, crop, "image_grid")
+    single = x.dim() == 4
+    T, (N, C, H, W) = (1 if single else x.shape[0]), x.shape[-4:]
+    if C not in (1, 3):
+        raise ValueError(f"image_grid: C = {C} channels (1 or 3)")
+    out_channels = C if out_channels is None else out_channels
+    if out_channels not in (1, 3) or (out_channels != C and C != 1):
+        raise ValueError(f"image_grid: out_channels = {out_channels} with C = {C} (C, or 3 with C = 1)")
+    for name, val, lo, hi in (("ncol", ncol, 1, 1 << 20), ("gap", gap, 0, 1024), ("fill", fill, 0, 255), ("row_prefix", row_prefix, 0, 1)):
+        if isinstance(val, bool) or not isinstance(val, int) or not lo <= val <= hi:
+            raise ValueError(f"image_grid: {name} = {val!r}: an integer in [{lo}, {hi}]")
+    nrow = -(-N // ncol)
+    GH, GW = gap + nrow * (H - 2 * crop + gap), gap + ncol * (W - 2 * crop + gap)
+    out = torch.empty((T, GH, row_prefix + GW * out_channels), device=x.device, dtype=torch.uint8)
+    with _Timed("image_grid_kernel", 0.0, _nbytes(out) + 4.0 * T * N * C * (H - 2 * crop) * (W - 2 * crop), fixed=True):
+        check(lib.gmk_image_grid(_p(x), _p(out), T, N, C, H, W, crop, ncol, gap, fill, out_channels, row_prefix, _s()), "image_grid")
+    return out[0] if single else out
+
+
 def mean(x):
     """0-dim fp32 mean of a contiguous fp32 vector (fixed summation order)."""
     _f32(x, "x")

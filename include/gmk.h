@@ -270,6 +270,24 @@ int gmk_label_drop(int64_t* y, int B, float p, uint64_t seed, uint64_t offset, v
  *   y[b] = labels[index[b]].  Any C H W: rows of whole 16-byte groups ((W + 2 pad) % 4 == 0) take the vector path, others a per-element one. */
 int gmk_batch_gather(const uint8_t* images, const uint8_t* labels, const int64_t* index, int B, int64_t N, int C, int H, int W, int pad,
                      int binarize, float flip_p, uint64_t seed, uint64_t offset, float* x, int64_t* y, void* stream);
+/* samples as bytes, the inverse direction of gmk_batch_gather: q(x) = (uint8) trunc(min(max((x + 1) * 127.5, 0), 255)), the rule of the
+ * reference's `proc` (gms/diffusion/diffusion_model.py:92 `((x + 1) * 127.5).clamp(0, 255).to(torch.uint8)`) with the add and the multiply
+ * rounded separately as torch evaluates them; NaN -> 0, -inf -> 0, +inf and overflow -> 255.  An extension, no reference call site except
+ * the quantisation rule.
+ *   x [n_images][C][H][W] fp32 (16-byte aligned), out [n_images][C][H - 2 crop][W - 2 crop] uint8 (4-byte aligned), planar: the layout
+ *   data.load_npy reads.  crop >= 0, 2 crop < min(H, W): the pad32 crop x[..., 2:-2, 2:-2].  Any C, H, W >= 1.  One pass, no temporaries. */
+int gmk_to_uint8(const float* x, uint8_t* out, int64_t n_images, int C, int H, int W, int crop, void* stream);
+/* T frames of N images each, quantised by the same rule and tiled into pictures, in one launch.  An extension, no reference call site
+ * except the quantisation rule (the reference tiles on the host for tensorboard, gms/common.py:177-193).
+ *   x [T][N][C][H][W] fp32 (16-byte aligned), C 1 or 3; out_channels = C, or 3 with C = 1 (the grey value repeated)
+ *   h = H - 2 crop, w = W - 2 crop, nrow = ceil(N / ncol); a frame has GH = gap + nrow (h + gap) lines of GW = gap + ncol (w + gap) pixels;
+ *   image j sits at tile (j / ncol, j % ncol); the border, the gaps and the empty tiles of a partial last row hold `fill` (0..255) in
+ *   every channel
+ *   out [T][GH][row_prefix + GW out_channels] uint8, channels interleaved; row_prefix 1: every line starts with one byte 0 (PNG filter type
+ *   "None"), so a frame is the byte stream zlib turns into an IDAT payload; row_prefix 0: a plain [GH][GW][out_channels] picture
+ *   Every source element is read once and every output byte written once; out needs no alignment. */
+int gmk_image_grid(const float* x, uint8_t* out, int T, int N, int C, int H, int W, int crop, int ncol, int gap, int fill, int out_channels,
+                   int row_prefix, void* stream);
 /* out[0] = mean(x[0..n)), fixed summation order: the batch mean of the per-sample losses (diffusion_model.py:78) */
 int gmk_mean(const float* x, int n, float* out, void* stream);
 /* C[i][j] = (accumulate ? C[i][j] : 0) + rowscale[i] * (bias[j] + bias2[j] + sum_k fa(A[i*sa0 + k*sa1]) * fb(B[k*sb0 + j*sb1]))
