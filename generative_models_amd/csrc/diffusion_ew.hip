@@ -140,6 +140,36 @@ __device__ __forceinline__ float x_raw_from_out(float out, float out_u, bool gui
 // x-hat = clamp(x_raw, -s, s) / s, a true division: with s = 1 this is clip1's bits
 __device__ __forceinline__ float threshold_x(float xr, float s) { return fminf(fmaxf(xr, -s), s) / s; }
 
+// The network's next time vector, written by one thread per row of a (gx, B) grid.  In the sampler loop u_t(i - 1) = u_s(i)
+// (gaussian_diffusion.py:288-290), so this step's logsnr_s IS the next logsnr_t; with `z_dup` the guided sampler's 2B-row vector takes it twice.
+__device__ __forceinline__ void write_logsnr_next(float* __restrict__ logsnr_next, const float* z_dup, int b, float l) {
+    if (logsnr_next && blockIdx.x == 0 && threadIdx.x == 0) {
+        logsnr_next[b] = l;
+        if (z_dup) logsnr_next[gridDim.y + b] = l;
+    }
+}
+
+// x-hat and eps-hat of element j, the one definition behind both update kernels.  Static clip: the clipped prediction, and with `vu` classifier-
+// free guidance in eps space between two clips (:176-186).  DT: the raw (guided) prediction clamped to the row's threshold s = thr[b] and divided by it.
+template <bool DT>
+__device__ __forceinline__ void predict_x_eps(float out, const float* __restrict__ vu, int64_t j, float w, float zz, const LogsnrCoef& c, int mt,
+                                              float s, float& xh, float& eh) {
+    if (DT) {
+        xh = threshold_x(x_raw_from_out(out, vu ? vu[j] : 0.f, vu != nullptr, w, zz, c, mt), s);
+        eh = c.c1 * (zz - xh * c.c2);
+    } else {
+        xh = clip1(x_from_out(out, zz, c, mt));
+        eh = c.c1 * (zz - xh * c.c2);
+        if (vu) {
+            const float xu = clip1(x_from_out(vu[j], zz, c, mt));
+            const float eu = c.c1 * (zz - xu * c.c2);
+            const float e = (1.0f + w) * eh + (-w) * eu;
+            xh = clip1(c.d1 * (zz - e * c.d2));
+            eh = c.c1 * (zz - xh * c.c2);
+        }
+    }
+}
+
 // grid (ceil(n/256), B).  DT (gmk_sampler_step_dt): x-hat is the raw prediction clamped to thr[b] and divided by it instead of the static clip;
 // everything after x-hat is shared.  The DT = false instantiation is the kernel gmk_sampler_step and gmk_ddim_step_vec have always launched.
 template <bool DT>
@@ -153,11 +183,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
                                                           const float* __restrict__ thr = nullptr) {
     const int b = blockIdx.y;
     if (lt_vec) { lt = lt_vec[b]; ls = ls_vec[b]; }      // per-sample times (teacher steps of the distillation loss)
-    // the next iteration's network time: u_t(i - 1) = u_s(i) (gaussian_diffusion.py:288-290), so logsnr_s IS the next logsnr_t
-    if (logsnr_next && blockIdx.x == 0 && threadIdx.x == 0) {
-        logsnr_next[b] = ls;
-        if (z_dup) logsnr_next[gridDim.y + b] = ls;
-    }
+    write_logsnr_next(logsnr_next, z_dup, b, ls);
     const LogsnrCoef c = logsnr_coef(lt);
     const float alpha_s = sqrtf(1.0f / (1.0f + expf(-ls)));
     const float sigma_s = sqrtf(1.0f / (1.0f + expf(ls)));
@@ -171,20 +197,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float zz = z[base + i];
         float xh, eh;
-        if (DT) {
-            xh = threshold_x(x_raw_from_out(v[base + i], vu ? vu[base + i] : 0.f, vu != nullptr, w, zz, c, mt), thr[b]);
-            eh = c.c1 * (zz - xh * c.c2);
-        } else {
-            xh = clip1(x_from_out(v[base + i], zz, c, mt));
-            eh = c.c1 * (zz - xh * c.c2);
-            if (vu) {   // classifier-free guidance in eps space (:176-186)
-                const float xu = clip1(x_from_out(vu[base + i], zz, c, mt));
-                const float eu = c.c1 * (zz - xu * c.c2);
-                const float e = (1.0f + w) * eh + (-w) * eu;
-                xh = clip1(c.d1 * (zz - e * c.d2));
-                eh = c.c1 * (zz - xh * c.c2);
-            }
-        }
+        predict_x_eps<DT>(v[base + i], vu, base + i, w, zz, c, mt, DT ? thr[b] : 1.0f, xh, eh);
         float zs;
         if (noise) zs = (r * alpha_st * zz + omr * alpha_s * xh) + stdv * noise[base + i];   // :242
         else zs = alpha_s * xh + sigma_s * eh;                                                 // :212
@@ -209,10 +222,7 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __res
                                                              float* __restrict__ z_dup, float* __restrict__ logsnr_next, int64_t n,
                                                              int mt, const float* __restrict__ thr) {
     const int b = blockIdx.y;
-    if (logsnr_next && blockIdx.x == 0 && threadIdx.x == 0) {
-        logsnr_next[b] = ls;
-        if (z_dup) logsnr_next[gridDim.y + b] = ls;
-    }
+    write_logsnr_next(logsnr_next, z_dup, b, ls);
     const LogsnrCoef c = logsnr_coef(lt);
     const float w = cond_w ? cond_w[b] : 0.f;
     const bool second_order = k_prev != 0.0f;            // uniform across the launch
@@ -220,20 +230,7 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __res
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float zz = z[base + i];
         float xh, eh;
-        if (DT) {
-            xh = threshold_x(x_raw_from_out(v[base + i], vu ? vu[base + i] : 0.f, vu != nullptr, w, zz, c, mt), thr[b]);
-            eh = c.c1 * (zz - xh * c.c2);
-        } else {
-            xh = clip1(x_from_out(v[base + i], zz, c, mt));
-            eh = c.c1 * (zz - xh * c.c2);
-            if (vu) {
-                const float xu = clip1(x_from_out(vu[base + i], zz, c, mt));
-                const float eu = c.c1 * (zz - xu * c.c2);
-                const float e = (1.0f + w) * eh + (-w) * eu;
-                xh = clip1(c.d1 * (zz - e * c.d2));
-                eh = c.c1 * (zz - xh * c.c2);
-            }
-        }
+        predict_x_eps<DT>(v[base + i], vu, base + i, w, zz, c, mt, DT ? thr[b] : 1.0f, xh, eh);
         const float d = second_order ? (1.0f + k_prev) * xh - k_prev * x_hist[base + i] : xh;
         const float zs = c_z * zz + c_x * d;
         x_hist[base + i] = xh;
@@ -398,10 +395,7 @@ __global__ __launch_bounds__(256) void inpaint_merge_kernel(float* __restrict__ 
                                                            uint64_t ctr1, uint64_t ctr2, float* __restrict__ z_dup,
                                                            float* __restrict__ logsnr_next, int64_t n) {
     const int row = blockIdx.y;
-    if (logsnr_next && blockIdx.x == 0 && threadIdx.x == 0) {
-        logsnr_next[row] = l_next;
-        if (z_dup) logsnr_next[gridDim.y + row] = l_next;
-    }
+    write_logsnr_next(logsnr_next, z_dup, row, l_next);
     const int64_t base = (int64_t)row * n;
     for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
         const int64_t j = base + i;
@@ -836,15 +830,21 @@ extern "C" int gmk_v_loss(const float* v, const float* z, const float* x, const 
     return gmk_check_launch("gmk_v_loss");
 }
 
+// The checks every entry that forms the (guided) prediction shares: the four gmk_*_step* entries, gmk_ddim_step_vec and gmk_dyn_threshold
+static int step_args_check(const char* who, int mean_type, const float* v_uncond, const float* cond_w, int B, int64_t n) {
+    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "%s: mean_type must be 0 (v), 1 (eps) or 2 (x)", who);
+    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "%s: v_uncond and cond_w go together", who);
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "%s: bad shape", who);
+    return 0;
+}
+
 // The argument checks and the launch behind gmk_sampler_step / gmk_sampler_step_dt (DT: thr is required)
 template <bool DT>
 static int sampler_step_launch(const char* who, const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z,
                                const float* noise, float logsnr_t, float logsnr_s, int is_last, float* z_next, float* x_pred,
                                float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
     GMK_REQUIRE(v && z && z_next && (!DT || thr), "%s: null pointer", who);
-    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "%s: mean_type must be 0 (v), 1 (eps) or 2 (x)", who);
-    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "%s: v_uncond and cond_w go together", who);
-    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "%s: bad shape", who);
+    if (const int err = step_args_check(who, mean_type, v_uncond, cond_w, B, n)) return err;
     const int gx = row_grid(n, 256);
     sampler_step_kernel<DT><<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, noise, logsnr_t, logsnr_s, is_last, z_next,
                                                                          x_pred, eps_pred, n, nullptr, nullptr, mean_type, z_dup,
@@ -873,9 +873,7 @@ static int dpm_solver_step_launch(const char* who, const float* v, const float* 
                                   float coef_prev, int is_last, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
                                   float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
     GMK_REQUIRE(v && z && x_hist && z_next && (!DT || thr), "%s: null pointer", who);
-    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "%s: mean_type must be 0 (v), 1 (eps) or 2 (x)", who);
-    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "%s: v_uncond and cond_w go together", who);
-    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "%s: bad shape", who);
+    if (const int err = step_args_check(who, mean_type, v_uncond, cond_w, B, n)) return err;
     GMK_REQUIRE(isfinite(logsnr_t) && isfinite(logsnr_s) && isfinite(coef_z) && isfinite(coef_x) && isfinite(coef_prev),
                 "%s: non-finite time or coefficient", who);
     const int gx = row_grid(n, 256);
@@ -904,9 +902,8 @@ extern "C" int gmk_dpm_solver_step_dt(const float* v, const float* v_uncond, con
 extern "C" int gmk_dyn_threshold(const float* v, const float* v_uncond, const float* cond_w, const float* z, float logsnr_t, int k_lo,
                                  float frac, float* s_out, float* q_out, int mean_type, int B, int64_t n, void* stream) {
     GMK_REQUIRE(v && z && s_out, "gmk_dyn_threshold: null pointer");
-    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_dyn_threshold");
-    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_dyn_threshold: v_uncond and cond_w go together");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0 && n < ((int64_t)1 << 31), "gmk_dyn_threshold: bad shape B=%d n=%lld (n < 2^31)", B, (long long)n);
+    if (const int err = step_args_check("gmk_dyn_threshold", mean_type, v_uncond, cond_w, B, n)) return err;
     GMK_REQUIRE(k_lo >= 0 && k_lo < n, "gmk_dyn_threshold: rank k_lo = %d outside [0, n = %lld)", k_lo, (long long)n);
     GMK_REQUIRE(frac >= 0.0f && frac < 1.0f, "gmk_dyn_threshold: frac = %g outside [0, 1)", (double)frac);
     GMK_REQUIRE(isfinite(logsnr_t), "gmk_dyn_threshold: non-finite time");
@@ -973,9 +970,7 @@ extern "C" int gmk_ddim_step_vec(const float* v, const float* v_uncond, const fl
                                  const float* logsnr_t, const float* logsnr_s, float* z_next, float* x_pred, float* eps_pred,
                                  int mean_type, int B, int64_t n, void* stream) {
     GMK_REQUIRE(v && z && z_next && logsnr_t && logsnr_s, "gmk_ddim_step_vec: null pointer");
-    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_ddim_step_vec");
-    GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "gmk_ddim_step_vec: v_uncond and cond_w go together");
-    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_ddim_step_vec: bad shape");
+    if (const int err = step_args_check("gmk_ddim_step_vec", mean_type, v_uncond, cond_w, B, n)) return err;
     const int gx = row_grid(n, 256);
     sampler_step_kernel<false><<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, nullptr, 0.f, 0.f, 0, z_next, x_pred,
                                                                             eps_pred, n, logsnr_t, logsnr_s, mean_type);

@@ -48,6 +48,12 @@ def logsnr_schedule_cosine_host(u):
     return np.float32(-2.0) * np.log(np.tan(SCHED_A * u + SCHED_B, dtype=np.float32), dtype=np.float32)
 
 
+def sampler_grid(num_steps):
+    """The samplers' time grid: one row (i, logsnr_t, logsnr_s) per loop iteration i = T-1 ... 0, fp32 host scalars.  The one place that forms
+    it; the update kernels, `dpm_solver_coefs` and `inpaint_coefs` all read these values."""
+    return [(i, *map(logsnr_schedule_cosine_host, sampler_times(i, num_steps))) for i in range(num_steps)[::-1]]
+
+
 DpmCoef = namedtuple("DpmCoef", "i lt ls h coef_z coef_x coef_prev")
 
 
@@ -61,9 +67,8 @@ def dpm_solver_coefs(num_steps):
     sigma = lambda l: math.sqrt(1.0 / (1.0 + math.exp(l)))
     alpha = lambda l: math.sqrt(1.0 / (1.0 + math.exp(-l)))
     rows, h_prev = [], None
-    for i in range(num_steps)[::-1]:
-        u_t, u_s = sampler_times(i, num_steps)
-        lt, ls = float(logsnr_schedule_cosine_host(u_t)), float(logsnr_schedule_cosine_host(u_s))
+    for i, lt, ls in sampler_grid(num_steps):
+        lt, ls = float(lt), float(ls)
         h = 0.5 * (ls - lt)
         # a zero-length previous step (coincident fp32 log-SNRs, only at extreme T) leaves no slope to extrapolate: first order again
         k = 0.0 if (not h_prev or i == 0) else h / (2.0 * h_prev)
@@ -116,9 +121,8 @@ def inpaint_coefs(num_steps):
     All in float64 from the fp32 log-SNRs."""
     sig = lambda l: 1.0 / (1.0 + math.exp(-l))
     rows = []
-    for i in range(num_steps)[::-1]:
-        u_t, u_s = sampler_times(i, num_steps)
-        lt, ls = float(logsnr_schedule_cosine_host(u_t)), float(logsnr_schedule_cosine_host(u_s))
+    for i, lt, ls in sampler_grid(num_steps):
+        lt, ls = float(lt), float(ls)
         a = math.sqrt(sig(lt) / sig(ls))
         b = math.sqrt(-math.expm1(lt - ls) * sig(-lt))
         rows.append(InpaintCoef(i, lt, ls, math.sqrt(sig(ls)), math.sqrt(sig(-ls)), a, b, i == 0))
@@ -129,6 +133,22 @@ def inpaint_passes(i, resample):
     """Network evaluations of inpainting step i: `resample`, the last step (i == 0) one - it never re-noises.  A call of T steps costs
     T r - (r - 1) forwards."""
     return 1 if i == 0 else int(resample)
+
+
+SamplerStep = namedtuple("SamplerStep", "i lt ls is_last passes dpm inp")
+# what inpainting adds to the sampler loop: x0 and the uint8 mask [B, n] (of the whole batch, or of a chunk's rows), the known-region
+# PhiloxStream, resample, and the whole-batch Philox counter of each network evaluation's merge (filled as the loop reserves them)
+InpaintState = namedtuple("InpaintState", "x0 mask rng resample B_total moffs")
+
+
+def sampler_plan(num_steps, sampler="ddim", resample=None):
+    """One row per sampler iteration i = T-1 ... 0: the grid's (i, lt, ls), is_last, the network evaluations of the step (`resample`: the
+    inpainting loop's, None outside it) and the step's DpmCoef (sampler 'dpmpp_2m') / InpaintCoef (inpainting) rows, else None.  The loop
+    reserves its Philox counters and every chunk spends them by walking the same plan."""
+    dpm = dpm_solver_coefs(num_steps) if sampler == "dpmpp_2m" else [None] * num_steps
+    inp = inpaint_coefs(num_steps) if resample is not None else [None] * num_steps
+    return [SamplerStep(i, lt, ls, i == 0, 1 if resample is None else inpaint_passes(i, resample), d, c)
+            for (i, lt, ls), d, c in zip(sampler_grid(num_steps), dpm, inp)]
 
 
 # the variational bound's log-SNR range: the schedule's truncation (diffusion_utils.py:199-200)
@@ -291,6 +311,8 @@ class GaussianDiffusion:
     # ctypes): the host is the bound, and replaying the captured forward removes it.  (Round 3 had measured a graph at 1.34 = 1.34 ms and
     # dropped it - the kernels, then 30 % longer, were the bound.)  Same kernels in the same order: bit-identical images.
     GRAPH_MAX_PIXELS = int(os.environ.get("GMK_SAMPLER_GRAPH_PIXELS", str(64 * 1024)))       # images x H x W of one forward; 0 turns it off
+    SAMPLER_STREAMS = int(os.environ.get("GMK_SAMPLER_STREAMS", "2"))            # 1: every batch on one stream (A/B switch)
+    STREAM_MIN_PIXELS = 1 << 18                                                  # images x H x W of a half-batch
 
     def _graph_path(self, module, nb, H, W):
         """Does a forward of `nb` images of H x W replay a captured graph in the sampler loop?"""
@@ -464,40 +486,31 @@ class GaussianDiffusion:
     # dz / d lambda = f(z, lambda) = 1/2 sigma^2 z - 1/2 sigma eps_hat(z, lambda) (Song et al. 2021, section 4.3 and App. D.2, in lambda = logsnr),
     # discretised on the samplers' grid lambda_i = lambda(i / N) by DDIM's update without the clip: z_j = alpha_j x_hat_i + sigma_j eps_hat_i
     # (j = i + 1 encoding, i - 1 decoding), x_hat / eps_hat the UNCLIPPED predictions of the net output at (z_i, lambda_i).
-    def _ode_net(self, net, what):
+    def _ode_setup(self, what, net, x, num_steps):
+        """The common opening of `encode`, `decode` and `ode_nll`: the checks, then -> (module, guide, N, lam, times) with lam the grid
+        (`ode_logsnr_grid`) and times its fp32 [N + 1, B] device table: row i is the network time of evaluation i (rows start 16-byte aligned)."""
         module, guide, kw_cond_w = _unwrap(net)
         if self.teacher_net is not None or kw_cond_w is not None:
             raise ValueError(f"{what}: a distilled student is conditioned on cond_w (a guided ODE): its probability-flow ODE has no density")
-        return module, guide
-
-    @staticmethod
-    def _ode_check(what, x, num_steps, module):
         N = int(num_steps)
         if N < 1 or N != num_steps:
             raise ValueError(f"{what}: num_steps = {num_steps}, need an integer >= 1")
         if x.dim() != 4 or x.shape[0] == 0 or x.shape[1] != getattr(module, "in_channels", x.shape[1]):
             raise ValueError(f"{what}: x has shape {tuple(x.shape)}, expected [B, {getattr(module, 'in_channels', 'C')}, H, W] with B > 0")
-        return N
-
-    @staticmethod
-    def _ode_times(lam, B, dev):
-        """fp32 [N + 1, Bp] device table of the grid's log-SNRs: row i is the network time of evaluation i (rows start 16-byte aligned)."""
-        Bp = (B + 3) // 4 * 4
-        return torch.tensor(lam, dtype=torch.float32)[:, None].expand(len(lam), Bp).contiguous().to(dev)
+        lam = ode_logsnr_grid(N)
+        B = x.shape[0]
+        times = torch.tensor(lam, dtype=torch.float32)[:, None].expand(len(lam), (B + 3) // 4 * 4).contiguous().to(x.device)
+        return module, guide, N, lam, times[:, :B]
 
     @torch.no_grad()
     def encode(self, *, net, x, num_steps):
         """DDIM inversion: the latent code z_N of x under the probability-flow ODE on N = num_steps steps.  z_0 = x, then N updates
         i = 0 ... N-1 (N forwards).  Deterministic: decode(encode(x)) -> x as N grows.  Runs without dropout.  -> z_N, fp32, x's shape."""
-        module, guide = self._ode_net(net, "encode")
-        N = self._ode_check("encode", x, num_steps, module)
+        module, guide, N, lam, times = self._ode_setup("encode", net, x, num_steps)
         z = x.float().clone(memory_format=torch.contiguous_format)
-        B, dev = z.shape[0], z.device
-        lam = ode_logsnr_grid(N)
-        times = self._ode_times(lam, B, dev)
         with _EvalForward(module):
             for i in range(N):
-                out = module.forward_hip(z, times[i, :B], guide, None)
+                out = module.forward_hip(z, times[i], guide, None)
                 ops.pf_ode_step(out, z, lam[i], lam[i + 1], mean_type=self.mean_type)
                 ops.throttle()
         return z
@@ -506,16 +519,12 @@ class GaussianDiffusion:
     def decode(self, *, net, z, num_steps):
         """The inverse of `encode`: from z at lambda_N = -20, N updates i = N ... 1 (N forwards); returns the x_hat of the last evaluation
         (at lambda_1), as the sampler does at its last step.  Runs without dropout.  -> fp32, z's shape."""
-        module, guide = self._ode_net(net, "decode")
-        N = self._ode_check("decode", z, num_steps, module)
+        module, guide, N, lam, times = self._ode_setup("decode", net, z, num_steps)
         z = z.float().clone(memory_format=torch.contiguous_format)
-        B, dev = z.shape[0], z.device
-        lam = ode_logsnr_grid(N)
-        times = self._ode_times(lam, B, dev)
         x_hat = torch.empty_like(z)
         with _EvalForward(module):
             for i in range(N, 0, -1):
-                out = module.forward_hip(z, times[i, :B], guide, None)
+                out = module.forward_hip(z, times[i], guide, None)
                 ops.pf_ode_step(out, z, lam[i], lam[i - 1] if i > 1 else None, mean_type=self.mean_type, x_out=x_hat if i == 1 else None)
                 ops.throttle()
         return x_hat
@@ -539,8 +548,7 @@ class GaussianDiffusion:
         evaluation (ode_draw_counters).  Runs without dropout.
         -> dict of fp32 [B]: nlogp = -log p(y) / D - log(2 delta) (by Jensen an upper bound on -log P(x's bin) / D, up to the estimator's
         noise), prior = -log N(z_N; 0, I) / D, divergence = the trapezoid sum / D."""
-        module, guide = self._ode_net(net, "ode_nll")
-        N = self._ode_check("ode_nll", x, num_steps, module)
+        module, guide, N, lam, times = self._ode_setup("ode_nll", net, x, num_steps)
         delta = float(delta)
         if not 0.0 < delta <= 0.5:
             raise ValueError(f"ode_nll: delta = {delta}, the bin half-width must lie in (0, 0.5]")
@@ -549,15 +557,13 @@ class GaussianDiffusion:
         D = x.numel() // B
         rng = PhiloxStream(seed)
         z = ops.dequantize(x, delta, rng.seed, rng._take(B * D))
-        lam = ode_logsnr_grid(N)
         wts = ode_trapezoid_weights(lam)
-        times = self._ode_times(lam, B, dev)
         acc = torch.zeros((B,), device=dev)
         prior = torch.empty((B,), device=dev)
         with _EvalForward(module):
             for i in range(N + 1):
                 store = {}
-                out = module.forward_hip(z, times[i, :B], guide, None, ctx=store)
+                out = module.forward_hip(z, times[i], guide, None, ctx=store)
                 r = ops.rng_rademacher(tuple(z.shape), rng.seed, rng._take(B * D), dev)
                 g = module.input_vjp_hip(store, r)
                 a, b = ode_divergence_coefs(lam[i], D, self.mean_type)
@@ -603,7 +609,7 @@ class GaussianDiffusion:
         if n1 % 4:
             raise ValueError(f"inpaint: {n1} values per image, a multiple of 4 is required")
         m = self._inpaint_mask(mask, shape, init_x.device)
-        inp = (ops.aligned(x0.to(init_x.device).float()), m, PhiloxStream(seed), r)
+        inp = InpaintState(ops.aligned(x0.to(init_x.device).float()), m, PhiloxStream(seed), r, shape[0], [])
         return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, inp=inp)
 
     @staticmethod
@@ -624,7 +630,7 @@ class GaussianDiffusion:
         return ops.aligned(m.contiguous())
 
     def _sample(self, *, net, init_x, cond_w=None, record=True, noises=None, net_cond_w=None, inp=None):
-        """The loop behind `sample` and `inpaint` (inp: None, or (x0, uint8 mask [B, n], the known-region PhiloxStream, resample))."""
+        """The loop behind `sample` and `inpaint` (inp: None, or the whole batch's InpaintState)."""
         module, guide, kw_cond_w = _unwrap(net)
         B = init_x.shape[0]
         dev = init_x.device
@@ -651,26 +657,23 @@ class GaussianDiffusion:
         # Never together with the captured-graph path (both halves would replay ONE graph on ONE set of static buffers, whatever
         # GMK_SAMPLER_GRAPH_PIXELS is set to), and only at hidden_size 128: the bit-identity of the halves rests on the embedding GEMMs' K-split
         # not depending on the row count, which `gemm_ksplit` guarantees for K <= 256 = 2 x 128 only.
-        K = 1
         nb_half = (B // 2) * (2 if w is not None else 1)
-        if dev.type == "cuda" and self.SAMPLER_STREAMS >= 2 and B % 2 == 0 and ((B // 2) * n1) % 4 == 0 and (noises is None or isinstance(noises, torch.Tensor)) and \
-                (B // 2) * init_x.shape[2] * init_x.shape[3] >= self.STREAM_MIN_PIXELS and module.channels == 128 and \
-                not self._graph_path(module, nb_half, init_x.shape[2], init_x.shape[3]):
-            K = 2
-        bounds = [(k * B // K, (k + 1) * B // K) for k in range(K)]
+        two = dev.type == "cuda" and self.SAMPLER_STREAMS >= 2 and B % 2 == 0 and ((B // 2) * n1) % 4 == 0 and (noises is None or isinstance(noises, torch.Tensor)) and \
+            (B // 2) * init_x.shape[2] * init_x.shape[3] >= self.STREAM_MIN_PIXELS and module.channels == 128 and \
+            not self._graph_path(module, nb_half, init_x.shape[2], init_x.shape[3])
+        K = 2 if two else 1
         cut = lambda t, a, b_: None if t is None else ops.aligned(t[a:b_])
-        # Philox counter of each network evaluation's noise draw for the WHOLE batch (ancestral sampler), and of each inpainting merge's
-        # known-region draws: chunks take their slice of them
-        offs, moffs = [], []
-        need_rng = self.sampler == "noisy" and noises is None
+        plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample)
+        # Philox counter of each network evaluation's noise draw for the WHOLE batch (ancestral sampler), and (inp.moffs) of each inpainting
+        # merge's known-region draws: chunks take their slice of them
+        offs = []
         cur = torch.cuda.current_stream() if dev.type == "cuda" else None
         streams = [cur] if K == 1 else self._chunk_streams(dev, K)
         gens = []
-        for k, (a, b_) in enumerate(bounds):
-            inp_k = None if inp is None else (cut(inp[0], a, b_), cut(inp[1], a, b_), inp[2].seed, moffs, B, inp[3])
-            args = (module, cut(guide, a, b_), cut(student_w, a, b_), cut(w, a, b_), cut(z_all, a, b_),
-                    noises if (noises is None or K == 1) else torch.as_tensor(noises)[:, a:b_], record, offs, a * n1 // 4, inp_k)
-            gens.append(self._sample_chunk(*args))
+        for a, b_ in [(k * B // K, (k + 1) * B // K) for k in range(K)]:
+            inp_k = None if inp is None else inp._replace(x0=cut(inp.x0, a, b_), mask=cut(inp.mask, a, b_))
+            gens.append(self._sample_chunk(plan, module, cut(guide, a, b_), cut(student_w, a, b_), cut(w, a, b_), cut(z_all, a, b_),
+                                           noises if (noises is None or K == 1) else torch.as_tensor(noises)[:, a:b_], record, offs, a * n1 // 4, inp_k))
         if K > 1:
             # what a forward builds lazily after a weight update (packed weights, frequency tables) is enqueued HERE, on the stream both chunk
             # streams wait for: the first chunk's forward would otherwise re-pack on ITS stream and clear the host flag, and the second chunk's
@@ -680,20 +683,19 @@ class GaussianDiffusion:
                 st.wait_stream(cur)
 
         def advance():
+            if K == 1:
+                return [next(gens[0])]
             outs = []
-            for k in range(K):
-                if K > 1:
-                    with torch.cuda.stream(streams[k]):
-                        outs.append(next(gens[k]))
-                else:
-                    outs.append(next(gens[k]))
+            for st, gen in zip(streams, gens):
+                with torch.cuda.stream(st):
+                    outs.append(next(gen))
             return outs
-        for i in range(self.num_steps)[::-1]:
-            for _ in range(1 if inp is None else inpaint_passes(i, inp[3])):
-                if need_rng:
+        for step in plan:
+            for _ in range(step.passes):
+                if self.sampler == "noisy" and noises is None:
                     offs.append(self.rng._take(B * n1))
                 if inp is not None:
-                    moffs.append(inp[2]._take(2 * B * n1))      # eps1 and eps2 of one merge, used or not
+                    inp.moffs.append(inp.rng._take(2 * B * n1))     # eps1 and eps2 of one merge, used or not
             advance()
             if K > 1:                                   # the throttle's event has to cover both halves
                 for st in streams:
@@ -710,77 +712,59 @@ class GaussianDiffusion:
                     t.record_stream(cur)
         return tuple(None if res[0][j] is None else torch.cat([r[j] for r in res], dim=1) for j in range(3))
 
-    SAMPLER_STREAMS = int(os.environ.get("GMK_SAMPLER_STREAMS", "2"))            # 1: every batch on one stream (A/B switch)
-    STREAM_MIN_PIXELS = 1 << 18                                                  # images x H x W of a half-batch
-
     def _chunk_streams(self, dev, K):
         if getattr(self, "_streams", None) is None or len(self._streams) < K or self._streams[0].device != dev:
             self._streams = [torch.cuda.Stream(device=dev) for _ in range(K)]
         return self._streams[:K]
 
-    def _sample_chunk(self, module, guide, student_w, w, z_t, noises, record, offs, q0, inp=None):
-        """The sampler loop over one (chunk of a) batch as a generator: one `next` per step (everything it launches goes to the stream current at
-        that call), then one more for the result.  offs[f] / q0: Philox counter of network evaluation `f`'s whole-batch noise draw / this chunk's
-        offset in it.  inp (inpainting): None, or (x0, uint8 mask [B, n] of this chunk, seed, moffs, B_total, resample) - moffs[f] is the
+    def _sample_chunk(self, plan, module, guide, student_w, w, z_t, noises, record, offs, q0, inp=None):
+        """The sampler loop over one (chunk of a) batch as a generator: one `next` per step of `plan` (everything it launches goes to the stream
+        current at that call), then one more for the result.  offs[f] / q0: Philox counter of network evaluation `f`'s whole-batch noise draw /
+        this chunk's offset in it.  inp (inpainting): None, or the InpaintState with this chunk's rows of x0 and mask - inp.moffs[f] is the
         whole-batch Philox counter of evaluation f's merge."""
         B = z_t.shape[0]
-        dev = z_t.device
         zs, xs, es = [], [], []
         guided = w is not None
-        nb = 2 * B if guided else B
         if guided:       # conditional + unconditional evaluations share one 2B-image forward (:176-177)
-            guide2 = torch.cat([guide, -torch.ones_like(guide)])
-            sw2 = None if student_w is None else torch.cat([student_w, student_w])
+            guide = torch.cat([guide, -torch.ones_like(guide)])
+            student_w = None if student_w is None else torch.cat([student_w, student_w])
             z2 = torch.cat([z_t, z_t])      # once: afterwards the update kernel writes both halves of the next 2B batch itself
+        # small batches replay a captured forward (one static log-SNR buffer, safe by stream order); large ones launch it kernel by kernel
+        graphed, lvecs = self._forward_runner(module, z2 if guided else z_t, guide, student_w)
         # the network's time vector: filled once here, then by the update kernel (the next logsnr_t is this step's logsnr_s);
         # two buffers alternate so that a forward still queued on the GPU never sees its input overwritten
-        first = logsnr_schedule_cosine_host(sampler_times(self.num_steps - 1, self.num_steps)[0])
-        # small batches replay a captured forward (one static log-SNR buffer, safe by stream order); large ones launch it kernel by kernel
-        graphed, lvecs = self._forward_runner(module, z2 if guided else z_t, guide2 if guided else guide, sw2 if guided else student_w)
-        lvecs[0].fill_(float(first))
+        lvecs[0].fill_(float(plan[0].lt))
+
+        def evaluate(z_in, lvec):
+            """One network evaluation -> (v, vu): the conditional output and, guided, the unconditional one (else None)."""
+            out = graphed(z_in) if graphed else module.forward_hip(z_in, lvec, guide, student_w)
+            return (out[:B], out[B:]) if guided else (out, None)
         # dpmpp_2m: the previous step's x-hat, [B, ...] also when guided (the kernel reads and rewrites it in place; the first step does not read it)
-        dpm = dpm_solver_coefs(self.num_steps) if self.sampler == "dpmpp_2m" else None
-        x_hist = torch.empty_like(z_t) if dpm is not None else None
-        inp_c = inpaint_coefs(self.num_steps) if inp is not None else None
+        x_hist = torch.empty_like(z_t) if self.sampler == "dpmpp_2m" else None
         f = 0                                   # network evaluations so far (one per step unless inpainting resamples)
-        for it, i in enumerate(range(self.num_steps)[::-1]):
-            u_t, u_s = sampler_times(i, self.num_steps)
-            lt, ls = logsnr_schedule_cosine_host(u_t), logsnr_schedule_cosine_host(u_s)
-            npass = 1 if inp is None else inpaint_passes(i, inp[5])
-            for p in range(npass):
+        for step in plan:
+            i, lt, ls, dpm, mrg = step.i, step.lt, step.ls, step.dpm, step.inp
+            for p in range(step.passes):
                 lvec, lnext = lvecs[f & 1], lvecs[(f + 1) & 1]
-                if not guided:
-                    v = graphed(z_t) if graphed else module.forward_hip(z_t, lvec, guide, student_w)
-                    vu = None
-                else:
-                    v2 = graphed(z2) if graphed else module.forward_hip(z2, lvec, guide2, sw2)
-                    v, vu = v2[:B], v2[B:]
+                v, vu = evaluate(z2 if guided else z_t, lvec)
                 noise = None
-                if self.sampler == "noisy":
-                    noise = ops.aligned(noises[i]) if noises is not None else ops.rng_normal(tuple(z_t.shape), self.rng.seed, offs[f] + q0, dev)   # :241
+                if self.sampler == "noisy":                 # :241
+                    noise = ops.aligned(noises[i]) if noises is not None else ops.rng_normal(tuple(z_t.shape), self.rng.seed, offs[f] + q0, z_t.device)
                 # dynamic thresholding: one select launch per network evaluation (per image, so a half-batch gives the whole batch's bits)
-                thr = None
-                if self.dyn_threshold:
-                    thr = ops.dyn_threshold(v, z_t, lt, self.dyn_threshold, v_uncond=vu, cond_w=w, mean_type=self.mean_type)
+                thr = ops.dyn_threshold(v, z_t, lt, self.dyn_threshold, v_uncond=vu, cond_w=w, mean_type=self.mean_type) if self.dyn_threshold else None
                 if dpm is not None:
-                    c = dpm[it]
-                    z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, c.coef_z, c.coef_x, c.coef_prev, i == 0, v_uncond=vu, cond_w=w,
+                    z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, dpm.coef_z, dpm.coef_x, dpm.coef_prev, step.is_last, v_uncond=vu, cond_w=w,
                                                       want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr)
                 else:
-                    z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, i == 0, v_uncond=vu, cond_w=w, noise=noise, want_pred=record,
+                    z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, step.is_last, v_uncond=vu, cond_w=w, noise=noise, want_pred=record,
                                                    mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr)
                 if guided:
                     z_t, z2 = z_t
                 if inp is not None:             # the known region, then (all passes but the step's last) the jump back to time t
-                    c = inp_c[it]
-                    ops.inpaint_merge(z_t, inp[0], inp[1], c.alpha_s, c.sigma_s, c.a, c.b, c.is_last, p < npass - 1, lt, ls, inp[2], inp[3][f],
-                                      q0=q0, B_total=inp[4], z_dup=z2[B:] if guided else None, logsnr_next=lnext)
+                    ops.inpaint_merge(z_t, inp.x0, inp.mask, mrg.alpha_s, mrg.sigma_s, mrg.a, mrg.b, mrg.is_last, p < step.passes - 1, lt, ls, inp.rng.seed,
+                                      inp.moffs[f], q0=q0, B_total=inp.B_total, z_dup=z2[B:] if guided else None, logsnr_next=lnext)
                 f += 1
             if record:
                 zs.append(z_t); xs.append(xp); es.append(ep)
             yield None
-        if record:
-            yield torch.stack(zs), torch.stack(xs), torch.stack(es)
-        else:
-            yield z_t[None], None, None
-
+        yield (torch.stack(zs), torch.stack(xs), torch.stack(es)) if record else (z_t[None], None, None)

@@ -17,6 +17,8 @@ import torch
 from oracle import diffusion_ref as D
 from oracle import unet_ref as U
 
+import sampler_ref as S
+
 
 def x_from_out(out, z, logsnr, mean_type):
     if mean_type == "v":
@@ -80,45 +82,16 @@ def predict(out, z, logsnr, p, mean_type="v", out_uncond=None, w=None, force_s=N
     return x_hat, D.predict_eps_from_x(z.double(), x_hat, logsnr.double()), s, q
 
 
-def _alpha_sigma(l):
-    l = float(l)
-    return math.sqrt(1.0 / (1.0 + math.exp(-l))), math.sqrt(1.0 / (1.0 + math.exp(l)))
-
-
 def sample(params, init_x, guide, num_steps, p, sampler="ddim", cond_w=None, mean_type="v", force_s=None, record=True):
     """The thresholded chain on the samplers' time grid: sampler 'ddim' (z_s = alpha_s x_hat + sigma_s eps_hat) or 'dpmpp_2m' (the update of
     tests/dpm_solver_ref.py on x_hat); the last step returns x_hat.  The network runs in fp32 as the oracle's does, the algebra in float64.
     cond_w: resolved per-sample guidance weights or None.  -> (zs, xs, es) float64 [T, B, ...] when `record`, else the final z."""
-    z_t = init_x.double()
-    zs, xs, es = [], [], []
-    x_prev, h_prev = None, None
-    B = init_x.shape[0]
-    for i in range(num_steps)[::-1]:
-        u_t, u_s = D.sampler_times(i, num_steps)
-        logsnr_t = D.logsnr_schedule_cosine(torch.tensor(u_t))
-        logsnr_s = D.logsnr_schedule_cosine(torch.tensor(u_s))
-        lt = torch.broadcast_to(logsnr_t.reshape(()), (B,))
+    def predict64(z_t, logsnr_t):
+        lt = torch.broadcast_to(logsnr_t.reshape(()), (z_t.shape[0],))
         z32 = z_t.float()
         out = U.unet_forward(params, z32, lt, guide=guide)
         out_u = U.unet_forward(params, z32, lt, guide=-torch.ones_like(guide)) if cond_w is not None else None
-        x_hat, eps_hat, _, _ = predict(out, z_t, lt, p, mean_type, out_u, cond_w, force_s)
-        (a_t, s_t), (a_s, s_s) = _alpha_sigma(logsnr_t), _alpha_sigma(logsnr_s)
-        if sampler == "ddim":
-            z_s = a_s * x_hat + s_s * eps_hat
-        elif sampler == "dpmpp_2m":
-            h = 0.5 * (float(logsnr_s) - float(logsnr_t))
-            if x_prev is None:
-                d = x_hat
-            else:
-                k = 1.0 / (2.0 * (h_prev / h))
-                d = (1.0 + k) * x_hat - k * x_prev
-            z_s = (s_s / s_t) * z_t + (-a_s * math.expm1(-h)) * d
-            x_prev, h_prev = x_hat, h
-        else:
-            raise NotImplementedError(sampler)
-        z_t = x_hat if i == 0 else z_s
-        if record:
-            zs.append(z_t); xs.append(x_hat); es.append(eps_hat)
-    if record:
-        return torch.stack(zs), torch.stack(xs), torch.stack(es)
-    return z_t
+        return predict(out, z_t, lt, p, mean_type, out_u, cond_w, force_s)[:2]
+    if sampler not in ("ddim", "dpmpp_2m"):
+        raise NotImplementedError(sampler)
+    return S.chain(init_x.double(), num_steps, getattr(S, sampler)(predict64), record=record)

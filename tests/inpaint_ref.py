@@ -8,16 +8,9 @@ independently of the package's `inpaint_coefs`.  With alpha^2 = sigmoid(logsnr),
     all passes of a step but its last:  z = (alpha_t / alpha_s) z + sqrt(1 - alpha_t^2 / alpha_s^2) eps2, and the step runs again from z
 The last step (i == 0) runs once.  The random draws are inputs, one entry per network evaluation f: eps1[f], eps2[f] (the merge) and
 noises[f] (sampler 'noisy').  The recorded trajectory is (z, x_hat, eps_hat) of the last pass of each step."""
-import math
-
 import torch
 
-from oracle import diffusion_ref as D
-
-
-def _alpha_sigma(l):
-    l = float(l)
-    return math.sqrt(1.0 / (1.0 + math.exp(-l))), math.sqrt(1.0 / (1.0 + math.exp(l)))
+import sampler_ref as S
 
 
 def forwards(num_steps, resample):
@@ -29,52 +22,8 @@ def sample(params, init_x, x0, mask, guide, num_steps, sampler="ddim", cond_w=No
            mean_type="v", record=True):
     """-> (zs, xs, es) stacked [T, B, ...] when `record`, else the final z.  mask: bool, broadcastable to x0; `cond_w`: the resolved
     per-sample guidance weights or None."""
-    z_t = init_x
-    known_px = torch.broadcast_to(mask.bool(), x0.shape)
-    zs, xs, es = [], [], []
-    x_prev, h_prev = None, None
-    B = init_x.shape[0]
-    f = 0
-    for i in range(num_steps)[::-1]:
-        u_t, u_s = D.sampler_times(i, num_steps)
-        logsnr_t = D.logsnr_schedule_cosine(torch.tensor(u_t))
-        logsnr_s = D.logsnr_schedule_cosine(torch.tensor(u_s))
-        (a_t, s_t), (a_s, s_s) = _alpha_sigma(logsnr_t), _alpha_sigma(logsnr_s)
-        npass = 1 if i == 0 else resample
-        for p in range(npass):
-            if sampler == "ddim":
-                z_s, x_pred, eps_pred = D.ddim_step(params, logsnr_t, logsnr_s, z_t, guide, cond_w, mean_type)
-            elif sampler == "noisy":
-                z_s, x_pred, eps_pred = D.reverse_dpm_step(params, logsnr_t, logsnr_s, z_t, noises[f], guide, cond_w, mean_type)
-            elif sampler == "dpmpp_2m":
-                lt = torch.broadcast_to(logsnr_t.reshape(()), (B,))
-                out = D.run_model(params, z_t, lt, guide=guide, mean_type=mean_type)
-                x_pred, eps_pred = out["model_x"], out["model_eps"]
-                if cond_w is not None:
-                    x_pred, eps_pred = D.cf_guidance(params, z_t, eps_pred, lt, cond_w, guide, mean_type)
-                h = 0.5 * (float(logsnr_s) - float(logsnr_t))
-                if x_prev is None:
-                    d = x_pred
-                else:
-                    k = 1.0 / (2.0 * (h_prev / h))
-                    d = (1.0 + k) * x_pred - k * x_prev
-                z_s = (s_s / s_t) * z_t + (-a_s * math.expm1(-h)) * d
-                x_prev, h_prev = x_pred, h
-            else:
-                raise NotImplementedError(sampler)
-            z_gen = x_pred if i == 0 else z_s
-            known = x0 if i == 0 else a_s * x0 + s_s * eps1[f]
-            z = torch.where(known_px, known, z_gen)
-            if p < npass - 1:
-                a = a_t / a_s
-                z = a * z + math.sqrt(1.0 - a * a) * eps2[f]
-            z_t = z
-            f += 1
-        if record:
-            zs.append(z_t); xs.append(x_pred); es.append(eps_pred)
-    if record:
-        return torch.stack(zs), torch.stack(xs), torch.stack(es)
-    return z_t
+    step = S.oracle_step(params, guide, sampler, cond_w, mean_type, noises)
+    return S.chain(init_x, num_steps, step, S.repaint(x0, mask, eps1, eps2), resample, record)
 
 
 # ---- the learning check (tests/test_gpu_inpaint.py G7, tools/inpaint_probe.py (c)) -------------------------------------------------------

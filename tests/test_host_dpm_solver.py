@@ -47,6 +47,19 @@ def test_coefficient_table(T):
         assert rows[1].coef_prev < 0.5 - 1e-3                           # h shrinks, 1/(2r) < 1/2 (the step's own h would give 1/2)
 
 
+def test_sampler_grid_is_the_samplers_fp32_times():
+    """`sampler_grid` is `sampler_times` + `logsnr_schedule_cosine_host`, bit for bit, and both coefficient tables are read from it."""
+    from generative_models_amd.diffusion import gaussian_diffusion as G
+    for T in (1, 2, 4, 8, 200, 250, 1000):
+        grid = G.sampler_grid(T)
+        assert [i for i, _, _ in grid] == list(range(T))[::-1]
+        for i, lt, ls in grid:
+            for got, u in zip((lt, ls), G.sampler_times(i, T)):
+                assert type(got) is np.float32 and got.tobytes() == G.logsnr_schedule_cosine_host(u).tobytes()
+        for rows in (G.dpm_solver_coefs(T), G.inpaint_coefs(T)):
+            assert [(r.i, r.lt, r.ls) for r in rows] == [(i, float(lt), float(ls)) for i, lt, ls in grid]
+
+
 @pytest.mark.parametrize("T", [2, 10, 250])
 def test_first_order_update_is_ddim_on_random_data(T):
     """(sigma_s / sigma_t) z + coef_x x = alpha_s x + sigma_s eps(x, z), eps(x, z) = (z - alpha_t x) / sigma_t: the first-order step is DDIM's
