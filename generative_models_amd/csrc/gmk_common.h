@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/gmk.h"
 
 typedef __bf16 bf16_t;
@@ -64,6 +66,12 @@ int gmk_conv_wgrad_slots_try(const void* dy, int dy_cstride, const void* src0, c
 static inline hipStream_t gmk_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int gmk_esize(int dtype) { return dtype == GMK_F32 ? 4 : 2; }
 static inline bool gmk_is16(int dtype) { return dtype == GMK_BF16 || dtype == GMK_F16; }
+// Storage type dispatch of the launchers: calls f(gmk_tag<T>{}) for the T among Ts that `dtype` names; false (nothing called) if none does.
+template <typename T> struct gmk_tag { typedef T type; };
+template <typename T> constexpr int gmk_dtype_of = std::is_same<T, float>::value ? GMK_F32 : std::is_same<T, bf16_t>::value ? GMK_BF16 : GMK_F16;
+template <typename... Ts, typename F> static inline bool gmk_with_type(int dtype, F&& f) {
+    return ((dtype == gmk_dtype_of<Ts> ? (f(gmk_tag<Ts>{}), true) : false) || ...);
+}
 
 // ---- device helpers ---------------------------------------------------------------------------
 template <typename T> struct Vec8;   // 8 activation elements as the natural 16/32-byte vector

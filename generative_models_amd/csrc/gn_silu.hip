@@ -1059,10 +1059,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WMIN, W
 }
 
 // pixels per thread of the register-resident kernels: the smallest of 1, 2, 4, 8 that fits the slab into <= 512 threads
-int gn_reg_iter(int HW, int nvec) {
+int gn_reg_iter(bool pow2_only, int HW, int nvec) {
     // 28 x 28 (784 pixels; round 4): 16 pixels per thread leave 49 planes x 8 = 392 of 448 threads busy (4.05 TB/s against 4.65 at 32 x 32, same batch);
-    // 14 per thread make it 56 planes = 448 threads, all busy, on 8 fewer data registers (GMK_GN_KERNEL=6 keeps the power-of-two choice: A/B)
-    if (nvec == 8 && HW == 784 && gmk_kernel_choice(2, "GMK_GN_KERNEL") != 6) return 14;
+    // 14 per thread make it 56 planes = 448 threads, all busy, on 8 fewer data registers (pow2_only, GMK_GN_KERNEL=6, keeps the power-of-two choice: A/B)
+    if (nvec == 8 && HW == 784 && !pow2_only) return 14;
     for (int it = 1; it <= 16; it <<= 1)
         if (((HW + it - 1) / it) * nvec <= 512) return it;
     return 0;
@@ -1195,6 +1195,118 @@ int gn_slab_channels(int mode, int C, int G, int HW, int elem_bytes, bool backwa
     return CS;
 }
 
+// ---- The forward plan: the one place that decides which kernel form a shape gets.  gmk_gn_silu_fwd launches from it, gmk_gn_stats
+// launches from it (so both compute the same statistics bits), the paired forward asks it.  (C, G) have passed gn_shape_ok. ----
+struct GnFwdPlan {
+    enum Form { kReg, kStream, kNarrow } form;
+    int nvec, it, planes;       // register form: 16-byte vectors per pixel of a slab, pixels per thread, pixel planes per workgroup
+    int threads, nblk, CS;      // block, grid, channels per slab
+    int kernel;                 // gmk_note_kernel id
+};
+// mode: the forced kernel form (0 automatic); pow2_iter: mode 6's power-of-two pixels per thread, which gmk_gn_stats follows too
+GnFwdPlan gn_fwd_plan(int mode, bool pow2_iter, int dtype, int B, int HW, int C, int G, bool producer_stats) {
+    GnFwdPlan p = {GnFwdPlan::kStream, 0, 0, 0, kThreads, B, C, 22};
+    if (gn_narrow(C, G)) { p.form = GnFwdPlan::kNarrow; return p; }
+    const bool slabs = gmk_is16(dtype) && !producer_stats && 32 % (C / G) == 0;
+    // 64 x 64 (HW up to 4096): a 32-channel slab of a sample is 256 KiB - the registers of ONE 1024-thread workgroup (16 pixels x 16 B per
+    // thread); single read instead of the streaming kernel's two sweeps
+    const bool big = slabs && (mode == 8 || mode == 0) && HW > 1024 && HW <= 4096 && HW % 16 == 0 && C % 32 == 0;
+    // (at 7x7 / 8x8 the whole-sample streaming kernel wins: 19 vs 26 us at 8x8, B = 2048 - the slabs are too small to pay for a workgroup each)
+    // gn_reg_iter(HW, 8) > 0 means ceil(HW / 16) * 8 <= 512, i.e. HW <= 1024: `big` and `reg` exclude each other, in any order and mode
+    const bool reg = slabs && (mode == 5 || mode == 6 || (mode == 0 && HW > 64)) && C % 64 == 0 && gn_reg_iter(pow2_iter, HW, 8) > 0;
+    if (big || reg) {
+        p.form = GnFwdPlan::kReg;
+        p.kernel = 21;
+        p.nvec = (big || mode == 5) ? 4 : 8;        // 32- or 64-channel slabs (64 = whole 128-B lines)
+        p.it = big ? 16 : gn_reg_iter(pow2_iter, HW, p.nvec);
+        p.planes = (HW + p.it - 1) / p.it;
+        p.threads = (p.planes * p.nvec + 63) / 64 * 64;
+        p.CS = p.nvec * 8;
+    } else
+        p.CS = producer_stats ? C : gn_slab_channels(mode, C, G, HW, gmk_esize(dtype), false);
+    p.nblk = B * (C / p.CS);
+    return p;
+}
+
+// the <pixels per thread, vectors per pixel> instantiations of the register kernels: every pair gn_fwd_plan can return
+template <int IT, int NVEC> struct RegForm { static constexpr int it = IT, nvec = NVEC; };
+template <typename F> void with_reg_form(int it, int nvec, F&& f) {
+    auto one = [&](auto form) { if (form.it == it && form.nvec == nvec) f(form); };
+    one(RegForm<1, 4>{}); one(RegForm<2, 4>{}); one(RegForm<4, 4>{}); one(RegForm<8, 4>{}); one(RegForm<16, 4>{});
+    one(RegForm<1, 8>{}); one(RegForm<2, 8>{}); one(RegForm<4, 8>{}); one(RegForm<8, 8>{}); one(RegForm<14, 8>{}); one(RegForm<16, 8>{});
+}
+
+struct GnFwdArgs {
+    const void* x; void* y; const float *gamma, *beta; float *mean, *rstd;
+    int B, HW, C, G; float eps;
+    const float* part; int TP, ntiles;                          // producer statistics
+    float drop_p; uint64_t drop_seed, drop_off;
+    const float* xadd; int xadd_stride;
+    float *tab_sc, *tab_sh; int tab_stride;                     // gmk_gn_stats: the affine tables instead of y
+};
+// launches what the plan says and notes its kernel id; false if dtype is no type of that kernel form
+bool gn_fwd_launch(const GnFwdPlan& p, int dtype, const GnFwdArgs& a, hipStream_t s) {
+    if (p.form == GnFwdPlan::kReg)
+        return gmk_with_type<f16_t, bf16_t>(dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            gmk_note_kernel(p.kernel);
+            with_reg_form(p.it, p.nvec, [&](auto form) {
+                using Form = decltype(form);
+                gn_silu_fwd_reg_kernel<T, Form::it, Form::nvec><<<p.nblk, p.threads, 0, s>>>(
+                    (const T*)a.x, (T*)a.y, a.gamma, a.beta, a.mean, a.rstd, a.HW, a.C, a.G, a.eps, a.B, p.planes, a.drop_p, a.drop_seed, a.drop_off,
+                    a.xadd, a.xadd_stride, a.tab_sc, a.tab_sh, a.tab_stride);
+            });
+        });
+    return gmk_with_type<bf16_t, f16_t, float>(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        gmk_note_kernel(p.kernel);
+        auto launch = [&](auto kernel) {
+            kernel<<<p.nblk, p.threads, 0, s>>>((const T*)a.x, (T*)a.y, a.gamma, a.beta, a.mean, a.rstd, a.HW, a.C, a.G, a.eps, a.part, a.TP, a.ntiles, p.CS,
+                                                a.B, a.drop_p, a.drop_seed, a.drop_off, a.xadd, a.xadd_stride, a.tab_sc, a.tab_sh, a.tab_stride);
+        };
+        if (p.form == GnFwdPlan::kNarrow) launch(gn_silu_fwd_kernel<T, true>);
+        else launch(gn_silu_fwd_kernel<T>);
+    });
+}
+
+// ---- The backward plan, used the same way by gmk_gn_silu_bwd and the paired backward. ----
+// Hybrid<IT, THREADS, NVEC, KEEP, XREG, EXACT>: one instantiation of gn_silu_bwd_hybrid_kernel (the kernel's own defaults)
+template <int IT, int THREADS, int NVEC = 4, int KEEP = IT, int XREG = 0, bool EXACT = (XREG > 0)> struct Hybrid {
+    template <typename TX> static constexpr auto kernel = gn_silu_bwd_hybrid_kernel<TX, IT, THREADS, NVEC, KEEP, XREG, EXACT>;
+};
+struct GnBwdPlan {
+    enum Row { kHyb4, kHyb13, kHyb8, kHyb8Exact, kHyb64Slab32, kHyb64Slab16, kStream } row;
+    int threads, nblk, CS;      // block, grid, channels per slab
+    size_t lds, lds_limit;      // dynamic LDS bytes; the limit to raise the kernel's to (0: the default 64 KiB covers it)
+    int kernel;                 // gmk_note_kernel id
+};
+GnBwdPlan gn_bwd_plan(int mode, int dtype, int B, int HW, int C, int G, bool dropout) {
+    const bool narrow = gn_narrow(C, G);
+    if (narrow) mode = 1;                                      // narrow groups: whole-sample streaming kernel
+    const bool hybrid = dtype == GMK_BF16 && !dropout && !narrow;
+    const int cpg = narrow ? 1 : C / G;
+    const bool slab32 = hybrid && C % 32 == 0 && 32 % cpg == 0;
+    auto hyb = [&](GnBwdPlan::Row row, int threads, int CS, size_t lds, size_t lds_limit) {
+        return GnBwdPlan{row, threads, B * (C / CS), CS, lds, lds_limit, 23};
+    };
+    if (slab32 && (mode == 0 || mode == 7) && HW > (mode == 7 ? 511 : 64) && HW <= 1024) {      // x parked in LDS: 64 B per pixel of a 32-channel slab
+        const size_t lds = (size_t)HW * 64;
+        if (HW == 1024) return hyb(GnBwdPlan::kHyb8Exact, 512, 32, lds, 0);      // 32x32 exactly: the pipelined form (-0.3 % of the headline step against the masked one)
+        if (HW <= 256) return hyb(GnBwdPlan::kHyb4, 256, 32, lds, 0);           // 14x14 (-16 % against the streaming kernel), 16x16 (-10 %); at 7x7 / 8x8 the whole-sample
+                                                                                // streaming kernel is as fast or faster (42 vs 46 us at 8x8, B = 2048)
+        if (HW <= 832) return hyb(GnBwdPlan::kHyb13, 256, 32, lds, 0);          // 28x28: 3 workgroups of 4 waves per CU
+        return hyb(GnBwdPlan::kHyb8, 512, 32, lds, 0);                          // 32x32: 2 workgroups of 8 waves (-13 % against the streaming kernel)
+    }
+    // 64 x 64 on 32-channel slabs (64-byte segments per pixel row instead of the 16-channel form's 32): one 512-thread workgroup
+    // per CU at 256 registers per lane - 19 / 32 of x in 152 KiB of LDS, the rest of x and 7 / 8 of dy in registers
+    if (slab32 && (mode == 0 || mode == 9) && HW == 4096) return hyb(GnBwdPlan::kHyb64Slab32, 512, 32, 19 * 128 * 64, 19 * 128 * 64);
+    // 64 x 64: 16-channel slabs, one workgroup of 16 waves per CU
+    if (hybrid && (mode == 0 || mode == 7) && C % 16 == 0 && 16 % cpg == 0 && HW > 1024 && HW <= 4096)
+        return hyb(GnBwdPlan::kHyb64Slab16, 1024, 16, (size_t)HW * 32, 4096 * 32);
+    const int CS = gn_slab_channels(mode, C, G, HW, gmk_esize(dtype), true);
+    return GnBwdPlan{GnBwdPlan::kStream, kThreads, B * (C / CS), CS, 0, 0, 24};
+}
+
 }  // namespace
 
 extern "C" int gmk_gn_silu_fwd(const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd,
@@ -1210,81 +1322,16 @@ extern "C" int gmk_gn_silu_fwd(const void* x, void* y, const float* gamma, const
     GMK_REQUIRE(B > 0 && HW > 0 && gn_shape_ok(C, groups), "gmk_gn_silu_fwd: unsupported shape B=%d HW=%d C=%d G=%d", B,
                 HW, C, groups);
     const int gn_mode = gmk_kernel_choice(2, "GMK_GN_KERNEL");
-    // (at 7x7 / 8x8 the whole-sample streaming kernel wins: 19 vs 26 us at 8x8, B = 2048 - the slabs are too small to pay for a workgroup each)
     GMK_REQUIRE(dtype != GMK_F16 || !stats_part, "gmk_gn_silu_fwd: producer statistics go with bf16 tensors only");
-    // 64 x 64 (HW up to 4096): a 32-channel slab of a sample is 256 KiB - the registers of ONE 1024-thread workgroup (16 pixels x 16 B per
-    // thread); single read instead of the streaming kernel's two sweeps
-    if (gn_narrow(C, groups)) {
+    const GnFwdPlan p = gn_fwd_plan(gn_mode, gn_mode == 6, dtype, B, HW, C, groups, stats_part != nullptr);
+    if (p.form == GnFwdPlan::kNarrow) {
         GMK_REQUIRE(!stats_part, "gmk_gn_silu_fwd: producer statistics come in 4-channel units; groups of %d channels", groups < 0 ? -groups : C / groups);
-        gmk_note_kernel(22);
-        if (dtype == GMK_BF16)
-            gn_silu_fwd_kernel<bf16_t, true><<<B, kThreads, 0, gmk_stream(stream)>>>((const bf16_t*)x, (bf16_t*)y, gamma, beta, mean, rstd, HW, C, groups,
-                                                                                   eps, nullptr, 0, 0, C, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
-        else if (dtype == GMK_F16)
-            gn_silu_fwd_kernel<f16_t, true><<<B, kThreads, 0, gmk_stream(stream)>>>((const f16_t*)x, (f16_t*)y, gamma, beta, mean, rstd, HW, C, groups,
-                                                                                  eps, nullptr, 0, 0, C, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
-        else if (dtype == GMK_F32)
-            gn_silu_fwd_kernel<float, true><<<B, kThreads, 0, gmk_stream(stream)>>>((const float*)x, (float*)y, gamma, beta, mean, rstd, HW, C, groups,
-                                                                                  eps, nullptr, 0, 0, C, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
-        else
-            GMK_REQUIRE(false, "gmk_gn_silu_fwd: bad dtype %d", dtype);
-        return gmk_check_launch("gmk_gn_silu_fwd");
+        gmk_note_kernel(p.kernel);      // (noted before the type is looked at)
     }
-    const bool big = gmk_is16(dtype) && !stats_part && (gn_mode == 8 || gn_mode == 0) && HW > 1024 && HW <= 4096 && HW % 16 == 0 &&
-                     C % 32 == 0 && 32 % (C / groups) == 0;
-    if (big || (gmk_is16(dtype) && !stats_part && (gn_mode == 5 || gn_mode == 6 || (gn_mode == 0 && HW > 64)) && C % 64 == 0 &&
-               32 % (C / groups) == 0 && gn_reg_iter(HW, 8) > 0)) {
-        const int nvec = (big || gn_mode == 5) ? 4 : 8;        // 32- or 64-channel slabs (64 = whole 128-B lines)
-        const int it = big ? 16 : gn_reg_iter(HW, nvec), planes = (HW + it - 1) / it, threads = (planes * nvec + 63) / 64 * 64;
-        const int nblk = B * (C / (nvec * 8));
-        gmk_note_kernel(21);
-#define GMK_GN_FWD_REG(IT, NV)                                                                                                           \
-    do {                                                                                                                                 \
-        if (dtype == GMK_F16)                                                                                                            \
-            gn_silu_fwd_reg_kernel<f16_t, IT, NV><<<nblk, threads, 0, gmk_stream(stream)>>>((const f16_t*)x, (f16_t*)y, gamma, beta, mean, rstd, \
-                                                                                            HW, C, groups, eps, B, planes, drop_p, drop_seed,  \
-                                                                                            drop_offset, xadd, xadd_stride);                   \
-        else                                                                                                                             \
-            gn_silu_fwd_reg_kernel<bf16_t, IT, NV><<<nblk, threads, 0, gmk_stream(stream)>>>((const bf16_t*)x, (bf16_t*)y, gamma, beta, mean,  \
-                                                                                             rstd, HW, C, groups, eps, B, planes, drop_p,      \
-                                                                                             drop_seed, drop_offset, xadd, xadd_stride);       \
-    } while (0)
-        if (nvec == 4) {
-            if (it == 1) GMK_GN_FWD_REG(1, 4);
-            else if (it == 2) GMK_GN_FWD_REG(2, 4);
-            else if (it == 4) GMK_GN_FWD_REG(4, 4);
-            else if (it == 8) GMK_GN_FWD_REG(8, 4);
-            else GMK_GN_FWD_REG(16, 4);
-        } else {
-            if (it == 1) GMK_GN_FWD_REG(1, 8);
-            else if (it == 2) GMK_GN_FWD_REG(2, 8);
-            else if (it == 4) GMK_GN_FWD_REG(4, 8);
-            else if (it == 8) GMK_GN_FWD_REG(8, 8);
-            else if (it == 14) GMK_GN_FWD_REG(14, 8);
-            else GMK_GN_FWD_REG(16, 8);
-        }
-#undef GMK_GN_FWD_REG
-    } else if (dtype == GMK_BF16) {
-        gmk_note_kernel(22);
-        const int CS = stats_part ? C : gn_slab_channels(gn_mode, C, groups, HW, 2, false);
-        gn_silu_fwd_kernel<bf16_t><<<B * (C / CS), kThreads, 0, gmk_stream(stream)>>>(
-            (const bf16_t*)x, (bf16_t*)y, gamma, beta, mean, rstd, HW, C, groups, eps, stats_part, tile_pixels, ntiles, CS, B, drop_p,
-            drop_seed, drop_offset, xadd, xadd_stride);
-    } else if (dtype == GMK_F16) {
-        gmk_note_kernel(22);
-        const int CS = gn_slab_channels(gn_mode, C, groups, HW, 2, false);
-        gn_silu_fwd_kernel<f16_t><<<B * (C / CS), kThreads, 0, gmk_stream(stream)>>>(
-            (const f16_t*)x, (f16_t*)y, gamma, beta, mean, rstd, HW, C, groups, eps, nullptr, 0, 0, CS, B, drop_p,
-            drop_seed, drop_offset, xadd, xadd_stride);
-    } else if (dtype == GMK_F32) {
-        gmk_note_kernel(22);
-        const int CS = stats_part ? C : gn_slab_channels(gn_mode, C, groups, HW, 4, false);
-        gn_silu_fwd_kernel<float><<<B * (C / CS), kThreads, 0, gmk_stream(stream)>>>(
-            (const float*)x, (float*)y, gamma, beta, mean, rstd, HW, C, groups, eps, stats_part, tile_pixels, ntiles, CS, B, drop_p,
-            drop_seed, drop_offset, xadd, xadd_stride);
-    }
-    else
-        GMK_REQUIRE(false, "gmk_gn_silu_fwd: bad dtype %d", dtype);
+    if (dtype == GMK_F16 || p.form == GnFwdPlan::kNarrow) tile_pixels = ntiles = 0;      // these never take producer statistics
+    const GnFwdArgs a = {x, y, gamma, beta, mean, rstd, B, HW, C, groups, eps, stats_part, tile_pixels, ntiles, drop_p, drop_seed, drop_offset,
+                         xadd, xadd_stride, nullptr, nullptr, 0};
+    GMK_REQUIRE(gn_fwd_launch(p, dtype, a, gmk_stream(stream)), "gmk_gn_silu_fwd: bad dtype %d", dtype);
     return gmk_check_launch("gmk_gn_silu_fwd");
 }
 
@@ -1301,53 +1348,11 @@ extern "C" int gmk_gn_stats(const void* x, const float* gamma, const float* beta
     GMK_REQUIRE(B > 0 && HW > 0 && gn_shape_ok(C, groups), "gmk_gn_stats: unsupported shape B=%d HW=%d C=%d G=%d", B, HW, C, groups);
     GMK_REQUIRE(gmk_is16(dtype), "gmk_gn_stats: 16-bit tensors only (the fused apply lives in the halo convolution)");
     GMK_REQUIRE(!gn_narrow(C, groups), "gmk_gn_stats: groups of %d channels run the unfused GroupNorm only", groups < 0 ? -groups : C / groups);
-    if (C % 64 == 0 && 32 % (C / groups) == 0 && HW > 64 && gn_reg_iter(HW, 8) > 0) {      // same choice as gmk_gn_silu_fwd: same statistics bits
-        const int nvec = 8;
-        const int it = gn_reg_iter(HW, nvec), planes = (HW + it - 1) / it, threads = (planes * nvec + 63) / 64 * 64;
-        const int nblk = B * (C / (nvec * 8));
-        gmk_note_kernel(21);
-#define GMK_GN_STATS_REG(IT)                                                                                                              \
-    do {                                                                                                                                  \
-        if (dtype == GMK_F16)                                                                                                             \
-            gn_silu_fwd_reg_kernel<f16_t, IT, 8><<<nblk, threads, 0, gmk_stream(stream)>>>((const f16_t*)x, (f16_t*)nullptr, gamma, beta, mean,  \
-                                                                                           rstd, HW, C, groups, eps, B, planes, 0.f, 0, 0, xadd, \
-                                                                                           xadd_stride, tab_scale, tab_shift, tab_stride);        \
-        else                                                                                                                              \
-            gn_silu_fwd_reg_kernel<bf16_t, IT, 8><<<nblk, threads, 0, gmk_stream(stream)>>>((const bf16_t*)x, (bf16_t*)nullptr, gamma, beta,     \
-                                                                                            mean, rstd, HW, C, groups, eps, B, planes, 0.f, 0, 0, \
-                                                                                            xadd, xadd_stride, tab_scale, tab_shift, tab_stride); \
-    } while (0)
-        if (it == 1) GMK_GN_STATS_REG(1);
-        else if (it == 2) GMK_GN_STATS_REG(2);
-        else if (it == 4) GMK_GN_STATS_REG(4);
-        else if (it == 8) GMK_GN_STATS_REG(8);
-        else if (it == 14) GMK_GN_STATS_REG(14);
-        else GMK_GN_STATS_REG(16);
-#undef GMK_GN_STATS_REG
-    } else if (HW > 1024 && HW <= 4096 && HW % 16 == 0 && C % 32 == 0 && 32 % (C / groups) == 0) {
-        // 64 x 64: the 1024-thread register kernel on 32-channel slabs, as gmk_gn_silu_fwd chooses (same statistics bits)
-        const int planes = HW / 16, nblk = B * (C / 32);
-        gmk_note_kernel(21);
-        if (dtype == GMK_F16)
-            gn_silu_fwd_reg_kernel<f16_t, 16, 4><<<nblk, planes * 4, 0, gmk_stream(stream)>>>((const f16_t*)x, (f16_t*)nullptr, gamma, beta, mean, rstd,
-                                                                                             HW, C, groups, eps, B, planes, 0.f, 0, 0, xadd, xadd_stride,
-                                                                                             tab_scale, tab_shift, tab_stride);
-        else
-            gn_silu_fwd_reg_kernel<bf16_t, 16, 4><<<nblk, planes * 4, 0, gmk_stream(stream)>>>((const bf16_t*)x, (bf16_t*)nullptr, gamma, beta, mean, rstd,
-                                                                                              HW, C, groups, eps, B, planes, 0.f, 0, 0, xadd, xadd_stride,
-                                                                                              tab_scale, tab_shift, tab_stride);
-    } else {
-        const int CS = gn_slab_channels(0, C, groups, HW, 2, false);
-        gmk_note_kernel(22);
-        if (dtype == GMK_F16)
-            gn_silu_fwd_kernel<f16_t><<<B * (C / CS), kThreads, 0, gmk_stream(stream)>>>(
-                (const f16_t*)x, (f16_t*)nullptr, gamma, beta, mean, rstd, HW, C, groups, eps, nullptr, 0, 0, CS, B, 0.f, 0, 0, xadd,
-                xadd_stride, tab_scale, tab_shift, tab_stride);
-        else
-            gn_silu_fwd_kernel<bf16_t><<<B * (C / CS), kThreads, 0, gmk_stream(stream)>>>(
-                (const bf16_t*)x, (bf16_t*)nullptr, gamma, beta, mean, rstd, HW, C, groups, eps, nullptr, 0, 0, CS, B, 0.f, 0, 0, xadd,
-                xadd_stride, tab_scale, tab_shift, tab_stride);
-    }
+    // The forward's automatic plan (mode 0), whatever kernel form is forced on the forward: the same statistics bits as the unforced
+    // forward.  Of the forced modes only 6 reaches here, through the pixels per thread at 28 x 28.
+    const GnFwdPlan p = gn_fwd_plan(0, gmk_kernel_choice(2, "GMK_GN_KERNEL") == 6, dtype, B, HW, C, groups, false);
+    const GnFwdArgs a = {x, nullptr, gamma, beta, mean, rstd, B, HW, C, groups, eps, nullptr, 0, 0, 0.f, 0, 0, xadd, xadd_stride, tab_scale, tab_shift, tab_stride};
+    gn_fwd_launch(p, dtype, a, gmk_stream(stream));
     return gmk_check_launch("gmk_gn_stats");
 }
 
@@ -1359,122 +1364,69 @@ extern "C" int gmk_gn_silu_bwd(const void* dy, const void* x, const float* gamma
     GMK_REQUIRE(!xadd || xadd_stride >= C, "gmk_gn_silu_bwd: xadd_stride %d < C %d", xadd_stride, C);
     GMK_REQUIRE(x_dtype == dtype || (dtype == GMK_BF16 && x_dtype == GMK_F16),
                 "gmk_gn_silu_bwd: x of type %d with gradients of type %d (same type, or fp16 activations with bf16 gradients)", x_dtype, dtype);
-    const bool xf16 = x_dtype == GMK_F16;
     GMK_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gmk_gn_silu_bwd: dropout probability %g outside [0, 1)", (double)drop_p);
     GMK_REQUIRE(dy && x && gamma && beta && mean && rstd && dx && dgamma_part && dbeta_part,
                 "gmk_gn_silu_bwd: null pointer");
     GMK_REQUIRE(B > 0 && HW > 0 && gn_shape_ok(C, groups), "gmk_gn_silu_bwd: unsupported shape B=%d HW=%d C=%d G=%d", B,
                 HW, C, groups);
     GMK_REQUIRE(!dxsum || dxsum_stride >= C, "gmk_gn_silu_bwd: dxsum_stride %d < C %d", dxsum_stride, C);
-    const int gn_mode = gn_narrow(C, groups) ? 1 : gmk_kernel_choice(2, "GMK_GN_KERNEL");      // narrow groups: whole-sample streaming kernel
-    if (dtype == GMK_BF16 && (gn_mode == 0 || gn_mode == 7) && C % 32 == 0 && 32 % (C / groups) == 0 && HW > (gn_mode == 7 ? 511 : 64) &&
-               HW <= 1024 && drop_p == 0.f) {
-        const size_t lds = (size_t)HW * 64;
-        gmk_note_kernel(23);
-#define GMK_GN_BWD_HYB(IT, TH)                                                                                                          \
-    do {                                                                                                                                \
-        if (xf16)                                                                                                                       \
-            gn_silu_bwd_hybrid_kernel<f16_t, IT, TH><<<B * (C / 32), TH, lds, gmk_stream(stream)>>>(                                     \
-                (const bf16_t*)dy, (const f16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2, (bf16_t*)dx,     \
-                dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);   \
-        else                                                                                                                            \
-            gn_silu_bwd_hybrid_kernel<bf16_t, IT, TH><<<B * (C / 32), TH, lds, gmk_stream(stream)>>>(                                    \
-                (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2, (bf16_t*)dx,    \
-                dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);   \
-    } while (0)
-        if (HW == 1024) {                            // 32x32 exactly: the pipelined form (-0.3 % of the headline step against the masked one)
-            if (xf16)
-                gn_silu_bwd_hybrid_kernel<f16_t, 8, 512, 4, 8, 0, true><<<B * (C / 32), 512, lds, gmk_stream(stream)>>>(
-                    (const bf16_t*)dy, (const f16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2, (bf16_t*)dx,
-                    dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
-            else
-                gn_silu_bwd_hybrid_kernel<bf16_t, 8, 512, 4, 8, 0, true><<<B * (C / 32), 512, lds, gmk_stream(stream)>>>(
-                    (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2, (bf16_t*)dx,
-                    dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
-        } else
-        if (HW <= 256) GMK_GN_BWD_HYB(4, 256);       // 14x14 (-16 % against the streaming kernel), 16x16 (-10 %); at 7x7 / 8x8 the whole-sample
-                                                     // streaming kernel is as fast or faster (42 vs 46 us at 8x8, B = 2048)
-        else if (HW <= 832) GMK_GN_BWD_HYB(13, 256); // 28x28: 3 workgroups of 4 waves per CU
-        else GMK_GN_BWD_HYB(8, 512);                 // 32x32: 2 workgroups of 8 waves (-13 % against the streaming kernel)
-#undef GMK_GN_BWD_HYB
-    } else if (dtype == GMK_BF16 && (gn_mode == 0 || gn_mode == 9) && C % 32 == 0 && 32 % (C / groups) == 0 && HW == 4096 && drop_p == 0.f) {
-        // 64 x 64 on 32-channel slabs (64-byte segments per pixel row instead of the 16-channel form's 32): one 512-thread workgroup
-        // per CU at 256 registers per lane - 19 / 32 of x in 152 KiB of LDS, the rest of x and 7 / 8 of dy in registers
-        gmk_note_kernel(23);
-        constexpr int kParkBytes = 19 * 128 * 64;
-        static const hipError_t attr = hipFuncSetAttribute((const void*)gn_silu_bwd_hybrid_kernel<bf16_t, 32, 512, 4, 28, 13>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kParkBytes);
-        static const hipError_t attr16 = hipFuncSetAttribute((const void*)gn_silu_bwd_hybrid_kernel<f16_t, 32, 512, 4, 28, 13>,
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, kParkBytes);
-        (void)attr; (void)attr16;
-        if (xf16)
-            gn_silu_bwd_hybrid_kernel<f16_t, 32, 512, 4, 28, 13><<<B * (C / 32), 512, kParkBytes, gmk_stream(stream)>>>(
-                (const bf16_t*)dy, (const f16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2, (bf16_t*)dx,
-                dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
-        else
-            gn_silu_bwd_hybrid_kernel<bf16_t, 32, 512, 4, 28, 13><<<B * (C / 32), 512, kParkBytes, gmk_stream(stream)>>>(
-                (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2, (bf16_t*)dx,
-                dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
-    } else if (dtype == GMK_BF16 && (gn_mode == 0 || gn_mode == 7) && C % 16 == 0 && 16 % (C / groups) == 0 && HW > 1024 &&
-               HW <= 4096 && drop_p == 0.f) {
-        // 64 x 64: 16-channel slabs, one workgroup of 16 waves per CU
-        gmk_note_kernel(23);
-        static const hipError_t attr = hipFuncSetAttribute((const void*)gn_silu_bwd_hybrid_kernel<bf16_t, 8, 1024, 2>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 4096 * 32);
-        static const hipError_t attr16 = hipFuncSetAttribute((const void*)gn_silu_bwd_hybrid_kernel<f16_t, 8, 1024, 2>,
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 4096 * 32);
-        (void)attr; (void)attr16;
-        if (xf16)
-            gn_silu_bwd_hybrid_kernel<f16_t, 8, 1024, 2><<<B * (C / 16), 1024, (size_t)HW * 32, gmk_stream(stream)>>>(
-                (const bf16_t*)dy, (const f16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2, (bf16_t*)dx,
-                dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
-        else
-            gn_silu_bwd_hybrid_kernel<bf16_t, 8, 1024, 2><<<B * (C / 16), 1024, (size_t)HW * 32, gmk_stream(stream)>>>(
-                (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2, (bf16_t*)dx,
-                dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
-    } else if (dtype == GMK_BF16 && xf16) {
-        gmk_note_kernel(24);
-        const int CS = gn_slab_channels(gn_mode, C, groups, HW, 2, true);
-        gn_silu_bwd_kernel<bf16_t, f16_t><<<B * (C / CS), kThreads, 0, gmk_stream(stream)>>>(
-            (const bf16_t*)dy, (const f16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2,
-            (bf16_t*)dx, dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, CS, B, drop_p, drop_seed, drop_offset, xadd,
-            xadd_stride);
-    } else if (dtype == GMK_BF16) {
-        gmk_note_kernel(24);
-        const int CS = gn_slab_channels(gn_mode, C, groups, HW, 2, true);
-        gn_silu_bwd_kernel<bf16_t><<<B * (C / CS), kThreads, 0, gmk_stream(stream)>>>(
-            (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2,
-            (bf16_t*)dx, dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, CS, B, drop_p, drop_seed, drop_offset, xadd,
-            xadd_stride);
-    } else if (dtype == GMK_F32) {
-        gmk_note_kernel(24);
-        const int CS = gn_slab_channels(gn_mode, C, groups, HW, 4, true);
-        gn_silu_bwd_kernel<float><<<B * (C / CS), kThreads, 0, gmk_stream(stream)>>>(
-            (const float*)dy, (const float*)x, gamma, beta, mean, rstd, (const float*)dadd1, (const float*)dadd2,
-            (float*)dx, dgamma_part, dbeta_part, dxsum, dxsum_stride, HW, C, groups, CS, B, drop_p, drop_seed, drop_offset, xadd,
-            xadd_stride);
+    const GnBwdPlan p = gn_bwd_plan(gmk_kernel_choice(2, "GMK_GN_KERNEL"), dtype, B, HW, C, groups, drop_p != 0.f);
+    GMK_REQUIRE(p.row != GnBwdPlan::kStream || dtype == GMK_BF16 || dtype == GMK_F32, "gmk_gn_silu_bwd: bad dtype %d", dtype);
+    gmk_note_kernel(p.kernel);
+    auto hybrid = [&](auto form) {
+        using Form = decltype(form);
+        if (p.lds_limit) {          // once per instantiation, both x types at the first launch of either
+            static const hipError_t attr = hipFuncSetAttribute((const void*)Form::template kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_limit);
+            static const hipError_t attr16 = hipFuncSetAttribute((const void*)Form::template kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_limit);
+            (void)attr; (void)attr16;
+        }
+        gmk_with_type<f16_t, bf16_t>(x_dtype, [&](auto tag) {
+            using TX = typename decltype(tag)::type;
+            Form::template kernel<TX><<<p.nblk, p.threads, p.lds, gmk_stream(stream)>>>(
+                (const bf16_t*)dy, (const TX*)x, gamma, beta, mean, rstd, (const bf16_t*)dadd1, (const bf16_t*)dadd2, (bf16_t*)dx, dgamma_part, dbeta_part,
+                dxsum, dxsum_stride, HW, C, groups, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
+        });
+    };
+    auto streaming = [&](auto t, auto tx) {
+        using T = typename decltype(t)::type; using TX = typename decltype(tx)::type;
+        gn_silu_bwd_kernel<T, TX><<<p.nblk, p.threads, 0, gmk_stream(stream)>>>(
+            (const T*)dy, (const TX*)x, gamma, beta, mean, rstd, (const T*)dadd1, (const T*)dadd2, (T*)dx, dgamma_part, dbeta_part, dxsum, dxsum_stride,
+            HW, C, groups, p.CS, B, drop_p, drop_seed, drop_offset, xadd, xadd_stride);
+    };
+    switch (p.row) {
+        case GnBwdPlan::kHyb4: hybrid(Hybrid<4, 256>{}); break;
+        case GnBwdPlan::kHyb13: hybrid(Hybrid<13, 256>{}); break;
+        case GnBwdPlan::kHyb8: hybrid(Hybrid<8, 512>{}); break;
+        case GnBwdPlan::kHyb8Exact: hybrid(Hybrid<8, 512, 4, 8, 0, true>{}); break;
+        case GnBwdPlan::kHyb64Slab32: hybrid(Hybrid<32, 512, 4, 28, 13>{}); break;
+        case GnBwdPlan::kHyb64Slab16: hybrid(Hybrid<8, 1024, 2>{}); break;
+        case GnBwdPlan::kStream:
+            if (dtype == GMK_F32) streaming(gmk_tag<float>{}, gmk_tag<float>{});
+            else gmk_with_type<f16_t, bf16_t>(x_dtype, [&](auto tx) { streaming(gmk_tag<bf16_t>{}, tx); });
     }
-    else
-        GMK_REQUIRE(false, "gmk_gn_silu_bwd: bad dtype %d", dtype);
     return gmk_check_launch("gmk_gn_silu_bwd");
 }
 
-// The shapes the paired backward takes: those where gmk_gn_silu_bwd runs the hybrid kernel without pixel masks (32 x 32 and 16 x 16), bf16
+// The shapes the paired backward takes: those where the backward plan is a hybrid row without pixel masks (32 x 32 and 16 x 16), bf16
 // gradients beside 16-bit activations, groups of 4, 8 or 16 channels.
 extern "C" int gmk_gn_pair_ok(int HW, int C, int groups_a, int groups_b, int x_dtype, int grad_dtype) {
-    if (!gmk_is16(x_dtype) || grad_dtype != GMK_BF16 || gmk_kernel_choice(2, "GMK_GN_KERNEL") != 0) return 0;
-    if (C <= 0 || C > 256 || C % 32 || (HW != 1024 && HW != 256)) return 0;
-    for (int G : {groups_a, groups_b})
-        if (!gn_shape_ok(C, G) || gn_narrow(C, G) || 32 % (C / G)) return 0;
+    if (!gmk_is16(x_dtype) || gmk_kernel_choice(2, "GMK_GN_KERNEL") != 0) return 0;
+    for (int G : {groups_a, groups_b}) {
+        if (!gn_shape_ok(C, G)) return 0;
+        const GnBwdPlan::Row row = gn_bwd_plan(0, grad_dtype, 1, HW, C, G, false).row;
+        if (row != GnBwdPlan::kHyb8Exact && !(row == GnBwdPlan::kHyb4 && HW == 256)) return 0;
+    }
     return 1;
 }
 
-// The paired forward: where gmk_gn_silu_fwd runs the register kernel on 64-channel slabs at 4 pixels per thread (16 x 16).
+// The paired forward: where the forward plan is the register kernel on 64-channel slabs at 4 pixels per thread, at 16 x 16.
 extern "C" int gmk_gn_pair_fwd_ok(int HW, int C, int groups_a, int groups_b, int dtype) {
-    if (!gmk_is16(dtype) || gmk_kernel_choice(2, "GMK_GN_KERNEL") != 0) return 0;
-    if (C <= 0 || C > 256 || C % 64 || HW != 256) return 0;
-    for (int G : {groups_a, groups_b})
-        if (!gn_shape_ok(C, G) || gn_narrow(C, G) || 32 % (C / G)) return 0;
+    if (gmk_kernel_choice(2, "GMK_GN_KERNEL") != 0 || HW != 256) return 0;
+    for (int G : {groups_a, groups_b}) {
+        if (!gn_shape_ok(C, G)) return 0;
+        const GnFwdPlan p = gn_fwd_plan(0, false, dtype, 1, HW, C, G, false);
+        if (p.form != GnFwdPlan::kReg || p.nvec != 8 || p.it != 4) return 0;
+    }
     return 1;
 }
 
@@ -1486,14 +1438,13 @@ extern "C" int gmk_gn_silu_fwd_pair(const void* x, void* y_a, void* y_b, const f
     GMK_REQUIRE(!xadd || xadd_stride >= C, "gmk_gn_silu_fwd_pair: xadd_stride %d < C %d", xadd_stride, C);
     GMK_REQUIRE(B > 0 && gmk_gn_pair_fwd_ok(HW, C, groups_a, groups_b, dtype),
                 "gmk_gn_silu_fwd_pair: unsupported shape B=%d HW=%d C=%d G=%d,%d dtype=%d (gmk_gn_pair_fwd_ok)", B, HW, C, groups_a, groups_b, dtype);
-    const int it = gn_reg_iter(HW, 8), planes = HW / it, threads = planes * 8, nblk = B * (C / 64);      // as gmk_gn_silu_fwd chooses: 4, 64, 512
-    GMK_REQUIRE(it == 4 && threads == 512, "gmk_gn_silu_fwd_pair: internal: %d pixels per thread, %d threads", it, threads);
+    const GnFwdPlan p = gn_fwd_plan(0, false, dtype, B, HW, C, groups_a, false);      // the plan gmk_gn_pair_fwd_ok asked: <4, 8>, 512 threads
     const GnFwdSide sa = {y_a, gamma_a, beta_a, mean_a, rstd_a, groups_a}, sb = {y_b, gamma_b, beta_b, mean_b, rstd_b, groups_b};
     gmk_note_kernel(26);
-    if (dtype == GMK_F16)
-        gn_silu_fwd_pair_kernel<f16_t, 4, 8><<<nblk, threads, 0, gmk_stream(stream)>>>((const f16_t*)x, sa, sb, HW, C, eps, B, planes, xadd, xadd_stride);
-    else
-        gn_silu_fwd_pair_kernel<bf16_t, 4, 8><<<nblk, threads, 0, gmk_stream(stream)>>>((const bf16_t*)x, sa, sb, HW, C, eps, B, planes, xadd, xadd_stride);
+    gmk_with_type<f16_t, bf16_t>(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        gn_silu_fwd_pair_kernel<T, 4, 8><<<p.nblk, p.threads, 0, gmk_stream(stream)>>>((const T*)x, sa, sb, HW, C, eps, B, p.planes, xadd, xadd_stride);
+    });
     return gmk_check_launch("gmk_gn_silu_fwd_pair");
 }
 
@@ -1512,18 +1463,18 @@ extern "C" int gmk_gn_silu_bwd_pair(const void* x, const void* dy_up, const void
                 x_dtype);
     const GnBwdSide up = {(const bf16_t*)dy_up, (const bf16_t*)dadd_up, gamma_up, beta_up, mean_up, rstd_up, dgamma_part_up, dbeta_part_up, groups_up};
     const GnBwdSide dn = {(const bf16_t*)dy_dn, (const bf16_t*)dadd_dn, gamma_dn, beta_dn, mean_dn, rstd_dn, dgamma_part_dn, dbeta_part_dn, groups_dn};
-    const size_t lds = (size_t)HW * 64;
-    const int nblk = B * (C / 32);
-    const bool xf16 = x_dtype == GMK_F16;
+    const GnBwdPlan p = gn_bwd_plan(0, GMK_BF16, B, HW, C, groups_dn, false);      // the row gmk_gn_pair_ok asked: its block, grid and LDS bytes
     gmk_note_kernel(25);
-#define GMK_GN_BWD_PAIR(TT, IT, TH, KB, W0, W1)                                                                                          \
-    gn_silu_bwd_pair_kernel<TT, IT, TH, KB, W0, W1><<<nblk, TH, lds, gmk_stream(stream)>>>((const TT*)x, up, dn, (bf16_t*)dx, dxsum,        \
-                                                                                       dxsum_stride, HW, C, B, xadd, xadd_stride)
-    // 32 x 32: dy_dn is read again in phase B's second sweep (7 tensor passes) so that ds + the pipeline buffers fit 128 registers and two
-    // workgroups share a CU like the single kernel's; keeping it resident (6 passes, 141 registers, one workgroup per CU) measured 9 % slower.
-    if (HW == 1024) { if (xf16) GMK_GN_BWD_PAIR(f16_t, 8, 512, 0, 4, 4); else GMK_GN_BWD_PAIR(bf16_t, 8, 512, 0, 4, 4); }
-    else { if (xf16) GMK_GN_BWD_PAIR(f16_t, 4, 256, 4, 3, 4); else GMK_GN_BWD_PAIR(bf16_t, 4, 256, 4, 3, 4); }
-#undef GMK_GN_BWD_PAIR
+    gmk_with_type<f16_t, bf16_t>(x_dtype, [&](auto tag) {
+        using TX = typename decltype(tag)::type;
+        auto launch = [&](auto kernel) {
+            kernel<<<p.nblk, p.threads, p.lds, gmk_stream(stream)>>>((const TX*)x, up, dn, (bf16_t*)dx, dxsum, dxsum_stride, HW, C, B, xadd, xadd_stride);
+        };
+        // 32 x 32: dy_dn is read again in phase B's second sweep (7 tensor passes) so that ds + the pipeline buffers fit 128 registers and two
+        // workgroups share a CU like the single kernel's; keeping it resident (6 passes, 141 registers, one workgroup per CU) measured 9 % slower.
+        if (p.row == GnBwdPlan::kHyb8Exact) launch(gn_silu_bwd_pair_kernel<TX, 8, 512, 0, 4, 4>);
+        else launch(gn_silu_bwd_pair_kernel<TX, 4, 256, 4, 3, 4>);
+    });
     return gmk_check_launch("gmk_gn_silu_bwd_pair");
 }
 
@@ -1531,12 +1482,12 @@ extern "C" int gmk_cast16(const void* src, void* dst, int64_t n, int src_dtype, 
     GMK_REQUIRE(src && dst && n > 0 && n % 8 == 0, "gmk_cast16: null pointer or n %lld not a multiple of 8", (long long)n);
     const int64_t nvec = n / 8;
     const int blocks = (int)((nvec + 255) / 256 < 8192 ? (nvec + 255) / 256 : 8192);
-    if (src_dtype == GMK_F16 && dst_dtype == GMK_BF16)
-        cast16_kernel<f16_t, bf16_t><<<blocks, 256, 0, gmk_stream(stream)>>>((const f16_t*)src, (bf16_t*)dst, nvec);
-    else if (src_dtype == GMK_BF16 && dst_dtype == GMK_F16)
-        cast16_kernel<bf16_t, f16_t><<<blocks, 256, 0, gmk_stream(stream)>>>((const bf16_t*)src, (f16_t*)dst, nvec);
-    else
-        GMK_REQUIRE(false, "gmk_cast16: %d -> %d (fp16 <-> bf16 only)", src_dtype, dst_dtype);
+    const bool ok = gmk_is16(dst_dtype) && dst_dtype != src_dtype && gmk_with_type<f16_t, bf16_t>(src_dtype, [&](auto tag) {
+        using TS = typename decltype(tag)::type;
+        using TD = typename std::conditional<std::is_same<TS, f16_t>::value, bf16_t, f16_t>::type;      // the other 16-bit type
+        cast16_kernel<TS, TD><<<blocks, 256, 0, gmk_stream(stream)>>>((const TS*)src, (TD*)dst, nvec);
+    });
+    GMK_REQUIRE(ok, "gmk_cast16: %d -> %d (fp16 <-> bf16 only)", src_dtype, dst_dtype);
     return gmk_check_launch("gmk_cast16");
 }
 
@@ -1544,12 +1495,11 @@ extern "C" int gmk_chansum(const void* x, float* out, int out_stride, int B, int
     GMK_REQUIRE(x && out, "gmk_chansum: null pointer");
     GMK_REQUIRE(B > 0 && HW > 0 && C > 0 && C <= 256 && !(C & 7) && 256 % (C >> 3) == 0 && out_stride >= C,
                 "gmk_chansum: unsupported shape B=%d HW=%d C=%d stride=%d", B, HW, C, out_stride);
-    if (dtype == GMK_BF16)
-        chansum_kernel<bf16_t><<<B, kThreads, 0, gmk_stream(stream)>>>((const bf16_t*)x, out, out_stride, HW, C);
-    else if (dtype == GMK_F32)
-        chansum_kernel<float><<<B, kThreads, 0, gmk_stream(stream)>>>((const float*)x, out, out_stride, HW, C);
-    else
-        GMK_REQUIRE(false, "gmk_chansum: bad dtype %d", dtype);
+    GMK_REQUIRE((gmk_with_type<bf16_t, float>(dtype, [&](auto tag) {
+                    using T = typename decltype(tag)::type;
+                    chansum_kernel<T><<<B, kThreads, 0, gmk_stream(stream)>>>((const T*)x, out, out_stride, HW, C);
+                })),
+                "gmk_chansum: bad dtype %d", dtype);
     return gmk_check_launch("gmk_chansum");
 }
 
@@ -1565,12 +1515,10 @@ extern "C" int gmk_sumpool2x2(const void* x, void* y, int B, int H, int W, int C
     GMK_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && !(C & 7), "gmk_sumpool2x2: bad shape");
     const int64_t total = (int64_t)B * H * W * (C >> 3);
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    if (dtype == GMK_BF16)
-        sumpool2x2_kernel<bf16_t><<<blocks, 256, 0, gmk_stream(stream)>>>((const bf16_t*)x, (bf16_t*)y, total, H, W, C);
-    else if (dtype == GMK_F32)
-        sumpool2x2_kernel<float><<<blocks, 256, 0, gmk_stream(stream)>>>((const float*)x, (float*)y, total, H, W, C);
-    else
-        GMK_REQUIRE(false, "gmk_sumpool2x2: bad dtype %d", dtype);
+    GMK_REQUIRE((gmk_with_type<bf16_t, float>(dtype, [&](auto tag) {
+                    using T = typename decltype(tag)::type;
+                    sumpool2x2_kernel<T><<<blocks, 256, 0, gmk_stream(stream)>>>((const T*)x, (T*)y, total, H, W, C);
+                })),
+                "gmk_sumpool2x2: bad dtype %d", dtype);
     return gmk_check_launch("gmk_sumpool2x2");
 }
-

@@ -188,6 +188,33 @@ def test_groupnorm_fp16_forward_and_mixed_backward(ops, C, G, S):
     assert torch.equal(dx1, dx2) and torch.equal(g1, g2) and torch.equal(b1, b2)
 
 
+@pytest.mark.parametrize("with_xadd", [False, True], ids=["plain", "xadd"])
+@pytest.mark.parametrize("dtype", [H, BF], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("C,G", [(128, 32), (64, 16)])
+@pytest.mark.parametrize("S", [8, 16, 28, 32, 64])
+def test_groupnorm_statistics_agree_across_the_forward_entry_points(ops, lib, S, C, G, dtype, with_xadd):
+    """gn_stats, gn_silu_fwd and (at 16 x 16) both sides of gn_silu_fwd_pair launch from one forward plan: the same kernel form
+    (streaming at 8 x 8, register-resident above) and with it the same mean / rstd bits, at the five plan rows of the U-Net levels."""
+    B = 2
+    x = (rnd(B, S, S, C, seed=31) * 1.4 + 0.25).to(dtype).cuda()
+    gamma = (1 + 0.1 * rnd(C, seed=32)).cuda(); beta = (0.1 * rnd(C, seed=33)).cuda()
+    xadd = (0.3 * rnd(B, C, seed=34)).cuda() if with_xadd else None
+    want = 22 if S == 8 else 21
+    _, mean, rstd = ops.gn_silu_fwd(x, gamma, beta, G, xadd=xadd)
+    assert lib.gmk_last_kernel() == want
+    tsc = torch.empty((B, C), device="cuda"); tsh = torch.empty_like(tsc)
+    smean, srstd = ops.gn_stats(x, gamma, beta, G, tsc, tsh, xadd=xadd)
+    assert lib.gmk_last_kernel() == want
+    assert torch.isfinite(mean).all() and torch.isfinite(rstd).all()
+    assert torch.equal(smean, mean) and torch.equal(srstd, rstd)
+    assert ops.gn_pair_fwd_ok(x, G, G) == (S == 16)
+    if S == 16:
+        sides = ops.gn_silu_fwd_pair(x, (gamma, beta, G), (gamma, beta, G), xadd=xadd)
+        assert lib.gmk_last_kernel() == 26
+        for _, m, r in sides:
+            assert torch.equal(m, mean) and torch.equal(r, rstd)
+
+
 @pytest.mark.parametrize("B,S,two,mode,ks,force", [
     (6, 28, False, 0, 3, 3), (4, 32, True, 0, 3, 3), (2, 64, False, 0, 3, 3), (3, 16, False, 2, 3, 3), (5, 14, True, 0, 3, 1),
     (4, 16, True, 0, 1, 1), (3, 28, False, 1, 3, 1), (600, 14, False, 0, 3, 0)])

@@ -909,3 +909,83 @@ def test_counter_records_are_keyed_per_template_instantiation():
         assert short(name) == want.split("<")[0]
     assert instantiation("_ZN12_GLOBAL__N_125gn_silu_bwd_hybrid_kernelIDF16_Li8ELi512ELi4ELi8ELi0ELb1EEEvPKDF16bPKT_") is None
     assert short("void (anonymous namespace)::wgrad_reduce_kernel<4>(float const*, float*, int, int, int, int)") == "wgrad_reduce_kernel"
+
+
+@pytest.fixture(scope="module")
+def gn_launch_trace():
+    """tools/gn_launch_trace.cpp built against the tree's gn_silu.hip (host objects + a stand-in HIP runtime, no GPU, about half a minute):
+    returns run(which) -> the trace lines."""
+    import shutil
+    import tempfile
+    csrc = os.path.join(ROOT, "generative_models_amd", "csrc")
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    rocm = Path(os.path.realpath(hipcc)).parent.parent
+    llvm = next((d for d in (rocm / "llvm" / "bin", rocm / "lib" / "llvm" / "bin") if (d / "clang++").exists()), None)
+    if llvm is None:
+        pytest.skip("clang++ of the ROCm toolchain not found")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    with tempfile.TemporaryDirectory() as tmp:
+        jobs = [[hipcc] + flags + ["-c", os.path.join(csrc, src + ".hip"), "-o", os.path.join(tmp, src + ".o")] for src in ("gn_silu", "gmk_common")]
+        jobs.append([hipcc] + flags + ["--cuda-device-only", "--no-gpu-bundle-output", "-c", os.path.join(csrc, "gn_silu.hip"), "-o", os.path.join(tmp, "gn_silu.co")])
+        procs = [subprocess.Popen(j, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for j in jobs]
+        for pr in procs:
+            out = pr.communicate(timeout=900)[0]
+            assert pr.returncode == 0, out[-2000:]
+        notes = os.path.join(tmp, "notes.txt")
+        with open(notes, "w") as f:
+            subprocess.run([str(llvm / "llvm-readelf"), "--notes", os.path.join(tmp, "gn_silu.co")], stdout=f, check=True, timeout=120)
+        exe = os.path.join(tmp, "gn_launch_trace")
+        r = subprocess.run([str(llvm / "clang++"), "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I" + str(rocm / "include"),
+                            os.path.join(ROOT, "tools", "gn_launch_trace.cpp"), os.path.join(ROOT, "tools", "launch_trace_stub.cpp"),
+                            os.path.join(tmp, "gn_silu.o"), os.path.join(tmp, "gmk_common.o"), "-o", exe], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+
+        def run(which):
+            env = {k: v for k, v in os.environ.items() if k != "GMK_GN_KERNEL"}
+            r = subprocess.run([exe, which], capture_output=True, text=True, timeout=600, env=dict(env, LAUNCH_TRACE_NOTES=notes))
+            assert r.returncode == 0, r.stderr[-2000:]
+            return r.stdout.splitlines()
+        yield run
+
+
+def test_groupnorm_dispatch_landmarks(gn_launch_trace):
+    """The plan rows that the comments of csrc/gn_silu.hip and DESIGN.md quote, read off the host dispatch itself (C = 128, 32 groups, B = 2;
+    16-bit = fp16 activations beside bf16 gradients): which instantiation, how many threads, how much LDS - and that gmk_gn_stats and the two
+    pair predicates follow the same plans."""
+    rows = {}
+    for line in gn_launch_trace("landmarks"):
+        head, _, tail = line.partition(" -> ")
+        f = dict(kv.split("=", 1) for kv in (head.split()[1:] + re.sub(r'err="[^"]*"', "", tail).split()) if "=" in kv)
+        rows[(head.split()[0], int(f.get("dtype", f.get("grad_dtype", -1))), int(f.get("x_dtype", -1)), int(f["HW"]))] = f
+        assert "no-metadata" not in tail
+    F32, BF16, F16 = 0, 1, 2
+    ints = lambda name: [int(v) for v in re.findall(r"L[ib](\d+)E", name)]
+    reg = {256: ([4, 8], 512), 784: ([14, 8], 448), 1024: ([16, 8], 512), 4096: ([16, 4], 1024)}
+    hyb = {256: ([4, 256, 4, 4, 0, 0], 16 << 10), 784: ([13, 256, 4, 13, 0, 0], 49 << 10), 1024: ([8, 512, 4, 8, 0, 1], 64 << 10),
+           4096: ([32, 512, 4, 28, 13, 1], 152 << 10)}
+    for HW in (64, 256, 784, 1024, 4096):
+        fwd, st, bwd = rows[("gn_silu_fwd", F16, -1, HW)], rows[("gn_stats", F16, -1, HW)], rows[("gn_silu_bwd", BF16, F16, HW)]
+        assert fwd["rc"] == st["rc"] == bwd["rc"] == "0"
+        if HW == 64:        # 8 x 8: the whole-sample streaming kernels
+            assert fwd["kernel"] == "22" and "gn_silu_fwd_kernelIDF16_Lb0E" in fwd["launch"] and fwd["block"] == "256,1,1" and fwd["grid"] == "2,1,1"
+            assert bwd["kernel"] == "24" and "gn_silu_bwd_kernelIDF16bDF16_E" in bwd["launch"] and bwd["lds"] == "0"
+        else:
+            assert fwd["kernel"] == "21" and "gn_silu_fwd_reg_kernelIDF16_" in fwd["launch"]
+            assert (ints(fwd["launch"]), int(fwd["block"].split(",")[0])) == reg[HW]
+            assert fwd["grid"] == "%d,1,1" % (2 * 128 // (8 * reg[HW][0][1]))
+            assert bwd["kernel"] == "23" and "gn_silu_bwd_hybrid_kernelIDF16_" in bwd["launch"]
+            assert (ints(bwd["launch"]), int(bwd["lds"])) == hyb[HW] and bwd["block"] == "%d,1,1" % hyb[HW][0][1] and bwd["grid"] == "8,1,1"
+            assert ("attr" in bwd) == (HW == 4096)      # only the 152 KiB form raises the kernel's LDS limit
+        # the statistics pass picks the forward's row: same instantiation, same geometry (and the bf16 one its bf16 twin)
+        assert (st["kernel"], st["launch"], st["grid"], st["block"]) == (fwd["kernel"], fwd["launch"], fwd["grid"], fwd["block"])
+        st_bf = rows[("gn_stats", BF16, -1, HW)]
+        assert (st_bf["launch"], st_bf["grid"], st_bf["block"]) == (fwd["launch"].replace("DF16_", "DF16b"), fwd["grid"], fwd["block"])
+        # fp32 always streams
+        f32, b32 = rows[("gn_silu_fwd", F32, -1, HW)], rows[("gn_silu_bwd", F32, F32, HW)]
+        assert f32["kernel"] == "22" and "gn_silu_fwd_kernelIfLb0E" in f32["launch"] and b32["kernel"] == "24" and "gn_silu_bwd_kernelIffE" in b32["launch"]
+        assert rows[("gn_pair_fwd_ok", F16, -1, HW)]["rc"] == ("1" if HW == 256 else "0")
+        assert rows[("gn_pair_ok", BF16, F16, HW)]["rc"] == ("1" if HW in (256, 1024) else "0")
+        assert rows[("gn_pair_ok", F16, F16, HW)]["rc"] == "0"      # fp16 gradients: never
