@@ -95,6 +95,13 @@ class MnistLoader:
             idx = perm[i * self.bs:(i + 1) * self.bs]
             yield self.x[idx].to(self.device, non_blocking=True), self.y[idx].to(self.device, non_blocking=True)
 
+    def state_dict(self):
+        """What the next epoch's shuffle depends on: the generator (part of a resumable run's state, between epochs)."""
+        return {"gen": self.gen.get_state()}
+
+    def load_state_dict(self, sd):
+        self.gen.set_state(sd["gen"].cpu())
+
 
 def load_mnist(bs, binarize=True, pad32=False, root="data", device="cpu", seed=0, rank=0, world=1):
     """-> (train_loader, test_loader), the call shape of gms/common.py:102."""
@@ -141,6 +148,14 @@ class SyntheticMNIST:
             if self.pad32:
                 x = torch.nn.functional.pad(x, (2, 2, 2, 2))       # :110-111 (zeros)
             yield x, labels
+
+    def state_dict(self):
+        """The position of both draw paths: the Philox counter (GPU) and the host generator (CPU)."""
+        return {"counter": self._counter, "host_gen": self._host_gen.get_state()}
+
+    def load_state_dict(self, sd):
+        self._counter = int(sd["counter"])
+        self._host_gen.set_state(sd["host_gen"].cpu())
 
 
 # ---- device-resident datasets (an extension: the reference's DataLoader has no counterpart) -------------------------------------------
@@ -231,6 +246,13 @@ class DeviceDataset:
         self.epoch += 1
         perm = torch.sort(keys, stable=True).indices[self.rank::self.world].contiguous()      # built once per epoch
         return self._batches(perm)
+
+    def state_dict(self):
+        """Between epochs: the number of the next shuffle and of the next batch's flip draw."""
+        return {"epoch": self.epoch, "k": self._k}
+
+    def load_state_dict(self, sd):
+        self.epoch, self._k = int(sd["epoch"]), int(sd["k"])
 
     def _batches(self, perm):
         from . import ops

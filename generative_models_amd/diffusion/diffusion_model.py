@@ -22,7 +22,7 @@ import os
 
 import torch
 
-from .. import common, ops, parallel
+from .. import checkpoint, common, ops, parallel
 from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
@@ -170,6 +170,38 @@ def make_plugin(GMBase, AttrDict):
             out = super().load_state_dict(state_dict, strict=strict, assign=assign)
             self.optimizer.ema_seeded = True
             return out
+
+        # -- the state of a resumable run (an extension; checkpoint.py writes it beside model.pt as train_state.pt)
+        def arena_digests(self):
+            """64-bit digests (ops.arena_digest) of the four arenas a resumed run must find again; None for one that does not exist (yet)."""
+            opt = self.optimizer
+            arenas = {"params": self.net.flat_params, "ema": None if self.ema_net is None else self.ema_net.flat_params, "m": opt.m, "v": opt.v}
+            return {name: None if t is None else checkpoint.arena_digest(t) for name, t in arenas.items()}
+
+        def train_state(self):
+            """Everything a continued run needs beside the weights of `state_dict()`: Adam's moments, step count and skipped-step count, the
+            counters of the three Philox streams (noise and timesteps; label drop and sampling; dropout masks) and the arena digests."""
+            return {"optimizer": self.optimizer.state_dict(), "rng": self.diffusion.rng.state_dict(), "aux_rng": self._aux_rng.state_dict(),
+                    "dropout": self.net.dropout_state(), "digests": self.arena_digests()}
+
+        def load_train_state(self, state):
+            """The inverse of train_state(), on a model that has loaded the `state_dict()` saved with it: the parameter and EMA arenas must
+            carry the digests the state recorded - weights of another checkpoint are refused before anything is changed."""
+            want, have = state["digests"], self.arena_digests()
+            for name in ("params", "ema"):
+                if want[name] != have[name]:
+                    as_hex = lambda d: "none" if d is None else f"{d:#018x}"
+                    raise RuntimeError(f"the train state was saved with a '{name}' arena of digest {as_hex(want[name])}, the loaded weights have "
+                                       f"{as_hex(have[name])}: model.pt and train_state.pt come from different checkpoints (or the ema_decay "
+                                       f"flag changed) - restore the pair from one checkpoint, or start from the weights with --weights_from")
+            self.optimizer.load_state_dict(state["optimizer"])
+            self.diffusion.rng.load_state_dict(state["rng"])
+            self._aux_rng.load_state_dict(state["aux_rng"])
+            self.net.load_dropout_state(state["dropout"])
+            have = self.arena_digests()
+            for name in ("m", "v"):
+                if want[name] != have[name]:
+                    raise RuntimeError(f"optimizer moment '{name}' does not carry the digest recorded with it: train_state.pt is damaged")
 
         def _sampling_net(self):
             """The network sample() and evaluate() run: the weight average when EMA is on."""
@@ -382,7 +414,8 @@ def make_plugin(GMBase, AttrDict):
                 writer.write_frames("diffusion_model/x", xs, epoch, crop=crop)
             zs, xs, eps = proc(zs), proc(xs), proc(eps)
             self.last_eval = {"samples": zs[-1], "sampling_process": zs, "eps": eps, "x": xs}
-            if not pictures and writer is not None and self.net.in_channels == 1:        # :105-110, same tags
+            grids = tuple(zs.shape[2:]) == (1, 28, 28)                # the reference's grid helpers take 25 images of 1 x 28 x 28 and nothing else
+            if not pictures and writer is not None and grids:         # :105-110, same tags
                 common.write_grid(writer, "samples", zs[-1], epoch)
                 common.write_gridvid(writer, "sampling_process", zs, epoch)
                 common.write_gridvid(writer, "diffusion_model/eps", eps, epoch)
@@ -398,7 +431,7 @@ def make_plugin(GMBase, AttrDict):
                 self.last_eval["inpaint"] = proc(z)
                 if pictures:
                     writer.write_frames("inpaint", z, epoch, crop=crop)
-                elif writer is not None and self.net.in_channels == 1 and k == 25:
+                elif writer is not None and grids and k == 25:
                     common.write_grid(writer, "inpaint", self.last_eval["inpaint"], epoch)
             random.randint(0, 2 ** 32)                                # :111 keeps the host RNG consumption
 

@@ -222,6 +222,16 @@ class PhiloxStream:
         self.counter += (n + 3) // 4
         return off
 
+    def state_dict(self):
+        return {"seed": self.seed, "counter": self.counter}
+
+    def load_state_dict(self, sd):
+        """The counter of a saved stream; the seed is how the stream was built (flags, rank) and has to agree."""
+        if int(sd["seed"]) != self.seed:
+            raise ValueError(f"saved Philox stream has seed {int(sd['seed'])}, this one {self.seed}: the run was built with another --seed "
+                             f"(or on another rank)")
+        self.counter = int(sd["counter"])
+
     def normal(self, shape, device):
         n = int(np.prod(shape))
         return ops.rng_normal(tuple(shape), self.seed, self._take(n), device)

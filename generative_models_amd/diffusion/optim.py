@@ -117,10 +117,26 @@ class FusedAdam:
         return int(self._skipped0 if self.ctl_state is None else self.ctl_state[ops.SKIPPED].item())
 
     def state_dict(self):
-        return {"step": self.step_count, "m": self.m, "v": self.v, "lr": self.lr, "skipped": self.skipped_steps()}
+        """`m` and `v` are None before the first step (a checkpoint taken at epoch 0)."""
+        return {"step": self.step_count, "m": self.m, "v": self.v, "lr": self.lr, "skipped": self.skipped_steps(),
+                "ema_seeded": self.ema_seeded}
 
     def load_state_dict(self, sd):
-        self.step_count, self.m, self.v, self.lr = sd["step"], sd["m"], sd["v"], sd["lr"]
+        """The moments move to the arena's device; one of another size (another hidden_size, in_channels or attention flag) is refused."""
+        p = self.net.flat_params
+        moments = {}
+        for name in ("m", "v"):
+            t = sd[name]
+            if t is not None:
+                if t.dtype != p.dtype or t.numel() != p.numel():
+                    raise ValueError(f"optimizer state '{name}' holds {t.numel()} {t.dtype} elements, the parameter arena {p.numel()} "
+                                     f"{p.dtype}: the state was saved by a model of another shape")
+                t = t.detach().reshape(p.shape).to(p.device)
+            moments[name] = t
+        if (moments["m"] is None) != (moments["v"] is None):
+            raise ValueError("optimizer state holds one of 'm' and 'v' only: both, or neither (a state saved before the first step)")
+        self.step_count, self.m, self.v, self.lr = int(sd["step"]), moments["m"], moments["v"], sd["lr"]
+        self.ema_seeded = bool(sd.get("ema_seeded", self.ema_seeded))
         self._skipped0 = float(sd.get("skipped", 0))
         if self.ctl_state is not None:
             self.ctl_state[ops.SKIPPED] = self._skipped0

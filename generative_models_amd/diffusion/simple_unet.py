@@ -320,6 +320,13 @@ class SimpleUnet(nn.Module):
     def mark_params_changed(self):
         self._packs_stale = True
 
+    def dropout_state(self):
+        """The position of the dropout stream (the seed comes from the model's flags); part of a resumable run's state."""
+        return {"counter": self._drop_counter}
+
+    def load_dropout_state(self, sd):
+        self._drop_counter = int(sd["counter"])
+
     def _version_sum(self):
         """Sum of the parameters' autograd version counters: any in-place update through torch (torch.optim, EMA copy_,
         p.data.mul_ ...) bumps one of them, so the packed convolution weights are refreshed without the caller having to

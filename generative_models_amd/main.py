@@ -27,6 +27,7 @@ import torch
 import torch.distributed as dist
 import yaml
 
+from . import checkpoint as train_state
 from . import common, parallel
 from . import data as datasets
 from . import metrics as heavy
@@ -59,14 +60,17 @@ DG.data_device = 0         # 1: the dataset stays on the GPU as uint8 and one HI
 DG.flip_p = 0.0            # probability of a horizontal flip per train image (data_device 1 only)
 DG.save_images = 0         # 1: evaluation samples go to <logdir>/images as PNG grids and APNG strips (common.ImageWriter)
 DG.image_frames = 60       # most frames an APNG keeps of a sampling trajectory (evenly spread, first and last always)
+DG.save_state = 0          # 1: every checkpoint also writes <logdir>/train_state.pt, what --resume needs beside model.pt (checkpoint.py)
+DG.resume = Path(".")      # <dir>: continue the run that wrote <dir>/model.pt + train_state.pt, with its hps.yaml under the command line
 DG.dump_samples = 0        # N > 0: after every checkpoint, N samples as <logdir>/samples_{images,labels}.npy (data.load_npy's format)
 
 SyntheticMNIST = datasets.SyntheticMNIST       # kept importable from here
 
 
 class FlagSpace:
-    """Flags in layers: the driver's table, then either the model's own `DG` or — with `--weights_from` — the `hps.yaml`
-    saved next to the checkpoint, then the command line.  Driver keys parse through `common.args_type` (bools as
+    """Flags in layers: the driver's table, then either the model's own `DG` or — with `--weights_from` or `--resume` — the `hps.yaml`
+    saved next to the checkpoint, then the command line (`--resume run --epochs 100` extends a run).  Only the command line starts a resume:
+    a `resume` key in an `hps.yaml` is the record of how that run was started.  Driver keys parse through `common.args_type` (bools as
     'True'/'False', '1e3' for ints, expanded Paths); keys a later layer introduces parse with the type of their default."""
 
     def __init__(self, base):
@@ -84,11 +88,18 @@ class FlagSpace:
         typed = {key: (common.args_type(value), value) for key, value in self.base.items()}
         peek, _ = self._parser(typed).parse_known_args(argv)          # first look: which model, which checkpoint, which logdir
         registry = common.discover_models()
-        if peek.weights_from != Path("."):
-            with open(peek.weights_from.parent / "hps.yaml") as f:
+        resuming = peek.resume != Path(".")
+        if resuming and peek.weights_from != Path("."):
+            raise ValueError(f"--resume {peek.resume} together with --weights_from {peek.weights_from}: a resumed run takes its weights from "
+                             f"<resume>/model.pt; give one of the two")
+        if resuming or peek.weights_from != Path("."):
+            with open((peek.resume if resuming else peek.weights_from.parent) / "hps.yaml") as f:
                 layer = dict(yaml.load(f, Loader=yaml.Loader))
             layer.pop("full_cmd", None)                                   # the saved command line is a record, not a flag
             layer.pop("arbiters", None)                                   # ... and so is the feature space of that run's eval/* numbers
+            layer.pop("resume", None)                                     # ... and so is the directory that run itself was resumed from
+            if resuming:
+                layer["logdir"] = peek.resume
             Model = registry[layer["model"]]
         else:
             Model = registry[peek.model]
@@ -98,6 +109,8 @@ class FlagSpace:
             convert = typed[key][0] if key in typed else type(value)
             typed[key] = (convert, value)
         G = common.AttrDict(vars(self._parser(typed).parse_args(argv)))
+        if resuming:
+            G.save_state = 1                                              # a resumed run stays resumable
         return G, Model
 
 
@@ -167,9 +180,17 @@ class Session:
         log.set("num_vars", common.count_vars(self.model))
         return last
 
-    def checkpoint(self, log, last_batch):
-        if not self.lead:
-            return
+    def checkpoint(self, log, last_batch, epoch=0):
+        if self.lead:
+            self._write_checkpoint(log, last_batch)
+        # last: the heavy evaluation and dump_samples draw from the model's streams and advance the test loader.  Every rank enters (the
+        # replica check of a data-parallel run is a collective), rank 0 writes
+        if self.G.get("save_state", 0):
+            train_state.save(Path(self.G.logdir), self.model, self.train_ds, self.test_ds, epoch)
+            if self.lead:
+                print("SAVED TRAIN STATE", self.G.logdir)
+
+    def _write_checkpoint(self, log, last_batch):
         Path(self.G.logdir).mkdir(parents=True, exist_ok=True)
         self.model.save(Path(self.G.logdir), *last_batch)
         print("SAVED MODEL", self.G.logdir)
@@ -212,16 +233,20 @@ class Session:
         log.set("dt/train", time.time() - started)
 
     def run(self):
-        log = self.flush(EpochLog(self.G.model), 0)                     # writes hps.yaml before anything else, like the reference
-        epoch = 0
+        # a resumed run's state is "after evaluate(e) and checkpoint(e)": it enters the loop at train_epoch(e)
+        resumed = getattr(self.model, "resumed_epoch", None)
+        epoch = 0 if resumed is None else int(resumed)
+        log = self.flush(EpochLog(self.G.model), epoch)                 # writes hps.yaml before anything else, like the reference
         while True:
-            last = self.evaluate(log, epoch)
-            if epoch % self.G.save_n == 0:
-                self.checkpoint(log, last)
-            final = log.to_host() if epoch >= self.G.epochs else None
-            log = self.flush(log, epoch)
-            if final is not None:
-                return final
+            if resumed is None:
+                last = self.evaluate(log, epoch)
+                if epoch % self.G.save_n == 0:
+                    self.checkpoint(log, last, epoch)
+                final = log.to_host() if epoch >= self.G.epochs else None
+                log = self.flush(log, epoch)
+                if final is not None:
+                    return final
+            resumed = None
             self.train_epoch(log)
             epoch += 1
 
@@ -292,6 +317,19 @@ def _check_data_flags(G):
         raise ValueError(f"--flip_p {G.flip_p} needs --data_device 1 (the flip is part of the device batch kernel)")
 
 
+def _check_resume_flags(G, Model):
+    """The flags of the train state, named before any model is built."""
+    if G.save_state not in (0, 1):
+        raise ValueError(f"--save_state {G.save_state}: 0 (weights only) or 1 (also <logdir>/train_state.pt, for --resume)")
+    if G.save_state and not hasattr(Model, "train_state"):
+        raise ValueError(f"--save_state 1: the model {G.model!r} has no train_state() / load_train_state() to save and resume from")
+    if G.resume != Path("."):
+        state = train_state.read(G.resume)                             # missing file, unknown format, another world size: before the model exists
+        if int(state["epoch"]) >= G.epochs:
+            raise ValueError(f"{G.resume / train_state.FILE} holds the state after epoch {state['epoch']} and --epochs is {G.epochs}: "
+                             f"nothing is left to train - extend the run with --epochs N, N > {state['epoch']}")
+
+
 def _check_image_flags(G):
     """The flags of the picture and sample output, named before any model is built."""
     if G.save_images not in (0, 1):
@@ -333,10 +371,12 @@ def load_model_and_data(argv=None):
     _check_data_flags(G)
     _check_image_flags(G)
     init_distributed()
+    _check_resume_flags(G, Model)                                      # after init_distributed: the state file names its world size
     device = _run_device(G.device)
     model = Model(G=G).to(device)
     model.run_device = device
-    if G.weights_from != Path("."):
+    resuming = G.resume != Path(".")
+    if G.weights_from != Path(".") and not resuming:                   # a resumed run is built as its first start was; its weights come below
         model.load_state_dict(torch.load(G.weights_from, map_location=device), strict=False)
     if parallel.world() > 1 and hasattr(model, "net"):
         parallel.GradSync(model.net).broadcast_params(0)
@@ -344,6 +384,11 @@ def load_model_and_data(argv=None):
     if parallel.rank() == 0:
         print("num_vars", common.count_vars(model))
     autoencoder, classifier = _feature_extractors(G, device, test_ds)
+    if resuming:                                                       # last: everything above ran as at the first start, on fresh loaders
+        model.load_state_dict(torch.load(G.resume / "model.pt", map_location=device))
+        model.resumed_epoch = train_state.load(G.resume, model, train_ds, test_ds)
+        if parallel.rank() == 0:
+            print("RESUMED", G.resume, "AT EPOCH", model.resumed_epoch)
     return model, train_ds, test_ds, autoencoder, classifier, G
 
 

@@ -1267,6 +1267,16 @@ def adam_step_ctl(p, g, m, v, state, lr, beta1, beta2, eps, step, grad_scale=1.0
                                 1.0 - float(decay_t), _p(state), _s()), "adam_step_ctl")
 
 
+def arena_digest(t):
+    """64-bit digest of a tensor's bytes read as 4-byte words (gmk_arena_digest; checkpoint.digest_host is the same function in numpy):
+    any contiguous CUDA tensor whose byte size is a positive multiple of 4.  -> an unsigned Python int (reads the device: a host sync)"""
+    nbytes = t.numel() * t.element_size()
+    assert t.is_cuda and t.is_contiguous() and nbytes > 0 and nbytes % 4 == 0, (t.device, tuple(t.shape), tuple(t.stride()), t.dtype)
+    out = torch.empty((1,), dtype=torch.int64, device=t.device)
+    check(lib.gmk_arena_digest(_p(t), nbytes // 4, _p(out), _s()), "arena_digest")
+    return int(out.item()) & 0xFFFFFFFFFFFFFFFF
+
+
 # ---- self-attention core (north_star extension; no reference call site) -----------------------------------------
 def bgemm_nt(A, B, out=None, alpha=1.0, out_dtype=None):
     """C[b] = alpha * A[b] @ B[b]^T for batches of K-contiguous matrices (row / batch strides free): A [batch, M, K],

@@ -45,6 +45,23 @@ def exchanging():
     return dist.get_world_size() > 1 or os.environ.get("GMK_FORCE_EXCHANGE", "0") == "1"
 
 
+def check_replicas(digest, what, device, group=None):
+    """Every rank's 64-bit digest (ops.arena_digest) of an arena that data-parallel training keeps identical, all-gathered as two 32-bit
+    halves: 16 bytes per rank instead of the arena.  A collective - every rank calls it; raises on every rank, naming the ranks that differ
+    from rank 0.  Runs in a one-rank group too (GMK_FORCE_EXCHANGE=1), where it can only pass."""
+    if dist.get_backend(group) == "gloo":                 # gloo gathers host tensors only
+        device = "cpu"
+    mine = torch.tensor([digest & 0xFFFFFFFF, digest >> 32], dtype=torch.int64, device=device)
+    every = [torch.empty_like(mine) for _ in range(world())]
+    dist.all_gather(every, mine, group=group)
+    digests = [int(lo) | (int(hi) << 32) for lo, hi in (t.tolist() for t in every)]
+    odd = [r for r, d in enumerate(digests) if d != digests[0]]
+    if odd:
+        raise RuntimeError(f"data-parallel replicas of {what} differ: rank 0 has digest {digests[0]:#018x}, rank(s) {odd} have "
+                           f"{[f'{digests[r]:#018x}' for r in odd]} - the ranks no longer train one model; do not save this state")
+    return digests
+
+
 def shard_batch(x, r=None, w=None):
     """Rank r's contiguous, equal shard of a global batch (dim 0 must divide evenly: equal shards keep the
     mean-of-means equal to the global mean)."""

@@ -476,6 +476,14 @@ int gmk_grad_norm(const float* g, int64_t n, float grad_scale, float max_norm, f
  * launch returns before it touches p, m, v or ema. */
 int gmk_adam_step_ctl(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2, float eps,
                       int step, float grad_scale, float ema_w, const float* state, void* stream);
+/* 64-bit digest of a device buffer of n_words 4-byte words (no reference call site: checkpoint.py ties model.pt to train_state.pt with it,
+ * compares data-parallel replicas and arenas without a host copy).  In uint64 arithmetic mod 2^64, w_i the raw bits of word i (from 0):
+ *   digest = sum_i mix(w_i + (i + 1) 0x9E3779B97F4A7C15),   mix = splitmix64's finaliser (x ^= x >> 30; x *= 0xBF58476D1CE4E5B9;
+ *                                                           x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31)
+ * The sum is exact and commutative: the value does not depend on the launch shape (a function of n_words alone, not of gmk_set_cu_limit).
+ * data: 4-byte aligned (16-byte loads from the first 16-byte boundary on); out: one uint64 on the device, zeroed by this entry on `stream`
+ * and then added to by one 64-bit atomic per workgroup. */
+int gmk_arena_digest(const void* data, int64_t n_words, uint64_t* out, void* stream);
 
 #ifdef __cplusplus
 }
