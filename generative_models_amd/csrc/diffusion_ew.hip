@@ -8,6 +8,8 @@
 // the inpainting merge gmk_inpaint_merge (RePaint, Lugmayr et al. 2022) and dynamic thresholding (gmk_dyn_threshold, gmk_sampler_step_dt,
 // gmk_dpm_solver_step_dt; Saharia et al. 2022).  gmk_grad_norm / gmk_adam_step_ctl (global-norm clipping by
 // torch.nn.utils.clip_grad_norm_'s rule, and the non-finite guard GradScaler.step gives the reference at diffusion_model.py:71) are extensions.
+// gmk_x_loss_w (the SNR+1 weighting of Salimans & Ho 2022 and Min-SNR-gamma, Hang et al. 2023, as w(logsnr) x_mse) and gmk_u_stratified
+// (low-discrepancy training times, Kingma et al. 2021) are extensions too.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -123,6 +125,116 @@ __global__ __launch_bounds__(256) void v_loss_kernel(const float* __restrict__ v
         const float dxh = kx * (xh - x[base + i]) + ke * (eh - eps[base + i]);
         dv[base + i] = (raw >= -1.0f && raw <= 1.0f) ? dx_dout(c, mt) * dxh : 0.f;
     }
+}
+
+// ---- weighted x-space losses (gmk_x_loss_w); an extension, no reference call site.
+// loss_b = w(l) mean_i (x_hat_i - x_i)^2 with w = 1 + e^l (GMK_LOSS_W_SNR_PLUS1: Salimans & Ho 2022, section 4, the v-space MSE) or
+// w = min(e^l, gamma) (GMK_LOSS_W_MIN_SNR: Hang et al. 2023), x_hat the clipped prediction of v_loss_kernel.  Neither needs eps or eps-hat,
+// so the pass reads v, z and x where v_loss_kernel reads four tensors twice.
+//
+// One workgroup of 256 threads per image.  The residuals d_i = x_hat_i - x_i go through LDS in chunks of kXLossKeep values: the loads are
+// 16 bytes wide where VEC allows (thread t takes elements 4t .. 4t + 3 of every 1024), the sums are not - thread t adds d_i^2 for
+// i = t, t + 256, ... in ascending order with fmaf, then block_sum: v_loss_kernel's element-to-thread assignment and order on either path
+// (kXLossKeep is a multiple of 256, so a chunk boundary does not move an element to another thread), hence its x_mse bits.
+// An image of n <= kXLossKeep values is one chunk, and the gradient pass reads it back from LDS instead of from global memory: each thread
+// re-reads the residuals it wrote itself and zeroes those whose raw prediction left [-1, 1] (one bit per element, at most 48, in a register
+// pair).  Larger images are read again.  LDS: 4 min(n, kXLossKeep) bytes (12 KiB at 3 x 32 x 32, 48 KiB at the capacity) + 16 for block_sum,
+// all of it dynamic so that the 16-byte accesses stay aligned.
+constexpr int kXLossKeep = 12288;    // kDynKeys: covers 3 x 64 x 64
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void x_loss_w_kernel(const float* __restrict__ v, const float* __restrict__ z, const float* __restrict__ x,
+                                                      const float* __restrict__ logsnr, float* __restrict__ loss_b,
+                                                      float* __restrict__ x_mse_o, float* __restrict__ dv, float grad_scale, int weight_type,
+                                                      float gamma, int64_t n, int mt, int lds_floats) {
+    extern __shared__ __attribute__((aligned(16))) float res[];      // lds_floats residuals, then block_sum's four partials
+    float* red = res + lds_floats;
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float l = logsnr[b];
+    const LogsnrCoef c = logsnr_coef(l);
+    const int64_t base = (int64_t)b * n;
+    const bool keep = dv && n <= kXLossKeep;
+    constexpr int STEP = VEC ? 4 : 1;        // consecutive elements a thread takes per pass over 256 * STEP
+    uint64_t clipped = 0;                    // keep: bit (STEP g + k) for element k of this thread's g-th group
+    float sx = 0.f;
+    for (int64_t c0 = 0; c0 < n; c0 += kXLossKeep) {
+        const int m = (int)(n - c0 < kXLossKeep ? n - c0 : kXLossKeep);
+        if (c0) __syncthreads();             // the last chunk's residuals have been summed
+        int bit = 0;
+        for (int i = tid * STEP; i < m; i += 256 * STEP, bit += STEP) {
+            float vv[STEP], zv[STEP], xv[STEP], d[STEP];
+            if constexpr (VEC) {
+                load4(v + base + c0 + i, vv); load4(z + base + c0 + i, zv); load4(x + base + c0 + i, xv);
+            } else {
+                vv[0] = v[base + c0 + i]; zv[0] = z[base + c0 + i]; xv[0] = x[base + c0 + i];
+            }
+#pragma unroll
+            for (int k = 0; k < STEP; ++k) {
+                const float raw = x_from_out(vv[k], zv[k], c, mt);
+                d[k] = clip1(raw) - xv[k];
+                if (keep && !(raw >= -1.0f && raw <= 1.0f)) clipped |= (uint64_t)1 << (bit + k);
+            }
+            if constexpr (VEC) store4(res + i, d); else res[i] = d[0];
+        }
+        __syncthreads();
+        for (int i = tid; i < m; i += 256) {
+            const float dx = res[i];
+            sx = fmaf(dx, dx, sx);
+        }
+    }
+    sx = block_sum(sx, red);
+    const float xm = sx / (float)n;
+    const float el = expf(l);
+    const float w = weight_type == GMK_LOSS_W_SNR_PLUS1 ? 1.0f + el : fminf(el, gamma);
+    if (tid == 0) {
+        loss_b[b] = w * xm;
+        x_mse_o[b] = xm;
+    }
+    if (!dv) return;
+    // torch.clip passes the gradient inside [-1, 1], ends included (v_loss_kernel's rule); w depends on l alone
+    const float kx = grad_scale * w * 2.f / (float)n;
+    const float dxo = dx_dout(c, mt);
+    if (keep) {
+        int bit = 0;
+        for (int i = tid * STEP; i < (int)n; i += 256 * STEP, bit += STEP) {
+            float d[STEP];
+            if constexpr (VEC) load4(res + i, d); else d[0] = res[i];
+#pragma unroll
+            for (int k = 0; k < STEP; ++k) d[k] = ((clipped >> (bit + k)) & 1) ? 0.f : dxo * (kx * d[k]);
+            if constexpr (VEC) store4(dv + base + i, d); else dv[base + i] = d[0];
+        }
+        return;
+    }
+    for (int64_t i = (int64_t)tid * STEP; i < n; i += 256 * STEP) {
+        float vv[STEP], zv[STEP], xv[STEP], d[STEP];
+        if constexpr (VEC) {
+            load4(v + base + i, vv); load4(z + base + i, zv); load4(x + base + i, xv);
+        } else {
+            vv[0] = v[base + i]; zv[0] = z[base + i]; xv[0] = x[base + i];
+        }
+#pragma unroll
+        for (int k = 0; k < STEP; ++k) {
+            const float raw = x_from_out(vv[k], zv[k], c, mt);
+            d[k] = (raw >= -1.0f && raw <= 1.0f) ? dxo * (kx * (clip1(raw) - xv[k])) : 0.f;
+        }
+        if constexpr (VEC) store4(dv + base + i, d); else dv[base + i] = d[0];
+    }
+}
+
+// u[b] = frac(u0[0] + b / B): one uniform offset per batch, evenly spaced times (Kingma et al. 2021, VDM, App. I.1), as
+//   s = b / B,  c = 1 - s,  u[b] = u0 >= c ? u0 - c : min(u0 + s, 1 - 2^-24)
+// - single correctly rounded fp32 operations, so numpy float32 restates it bit for bit.  The wrap is taken BEFORE the sum: u0 + s itself is
+// not exact at or above 1 (fp32 keeps multiples of 2^-23 there: with u0 = 1 - 2^-24 and B = 8 it rounds 1.125 - 2^-24 up to 1.125 and leaves
+// [0, 1/8) empty).  With B a power of two and u0 a multiple of 2^-24 (what gmk_rng_uniform draws) every operation here is exact: each
+// [k / B, (k + 1) / B) holds exactly one u.  The min only guards other B, where u0 + s just below 1 could round to 1.
+__global__ __launch_bounds__(256) void u_stratified_kernel(const float* __restrict__ u0, float* __restrict__ u, int B) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const float o = u0[0];
+    const float s = __fdiv_rn((float)b, (float)B);
+    const float c = __fsub_rn(1.0f, s);
+    u[b] = o >= c ? __fsub_rn(o, c) : fminf(__fadd_rn(o, s), 0x1.fffffep-1f);
 }
 
 // ---- dynamic thresholding (Saharia et al. 2022, Imagen, section 2.3); an extension, no reference call site.
@@ -828,6 +940,32 @@ extern "C" int gmk_v_loss(const float* v, const float* z, const float* x, const 
     GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_v_loss");
     v_loss_kernel<<<B, 256, 0, gmk_stream(stream)>>>(v, z, x, eps, logsnr, loss_b, x_mse, eps_mse, dv, grad_scale, n, loss_type, mean_type);
     return gmk_check_launch("gmk_v_loss");
+}
+
+extern "C" int gmk_x_loss_w(const float* v, const float* z, const float* x, const float* logsnr, float* loss_b, float* x_mse, float* dv,
+                            float grad_scale, int weight_type, float gamma, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && z && x && logsnr && loss_b && x_mse, "gmk_x_loss_w: null pointer");
+    GMK_REQUIRE(B > 0 && n > 0, "gmk_x_loss_w: bad shape B=%d n=%lld", B, (long long)n);
+    GMK_REQUIRE(weight_type == GMK_LOSS_W_SNR_PLUS1 || weight_type == GMK_LOSS_W_MIN_SNR,
+                "gmk_x_loss_w: weight_type must be 0 (snr_plus1) or 1 (min_snr)");
+    GMK_REQUIRE(isfinite(gamma) && gamma > 0.0f, "gmk_x_loss_w: gamma = %g, need a finite value > 0", (double)gamma);
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_x_loss_w");
+    const int64_t m = n < kXLossKeep ? n : kXLossKeep;
+    const int lds_floats = (int)((m + 3) / 4 * 4);
+    const size_t lds = (size_t)(lds_floats + 4) * sizeof(float);
+    // 16-byte accesses need every row to start on a 16-byte boundary: n a multiple of 4 and aligned tensors
+    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(x) |
+                                     reinterpret_cast<uintptr_t>(dv)) & 15) == 0;
+    if (vec) x_loss_w_kernel<true><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, weight_type, gamma, n, mean_type, lds_floats);
+    else x_loss_w_kernel<false><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, weight_type, gamma, n, mean_type, lds_floats);
+    return gmk_check_launch("gmk_x_loss_w");
+}
+
+extern "C" int gmk_u_stratified(const float* u0, float* u, int B, void* stream) {
+    GMK_REQUIRE(u0 && u, "gmk_u_stratified: null pointer");
+    GMK_REQUIRE(B > 0 && B <= (1 << 24), "gmk_u_stratified: B = %d outside [1, 2^24] (b and B must be exact in fp32)", B);
+    u_stratified_kernel<<<(B + 255) / 256, 256, 0, gmk_stream(stream)>>>(u0, u, B);
+    return gmk_check_launch("gmk_u_stratified");
 }
 
 // The checks every entry that forms the (guided) prediction shares: the four gmk_*_step* entries, gmk_ddim_step_vec and gmk_dyn_threshold

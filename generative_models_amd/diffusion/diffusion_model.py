@@ -23,7 +23,7 @@ import os
 import torch
 
 from .. import checkpoint, common, ops, parallel
-from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check
+from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check, loss_weight_check
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -70,6 +70,12 @@ def make_plugin(GMBase, AttrDict):
         DG.lr_warmup = 0               # W > 0: lr times min(1, (t + 1) / W) after t steps, under either lr_scheduler
         DG.lr_decay_steps = 0          # 'cosine': steps from lr down to lr_min_ratio * lr, counted from the end of the warm-up
         DG.lr_min_ratio = 0.1
+        DG.loss_weight = "snr_trunc"   # the training loss: 'snr_trunc' (reference: max(x_mse, eps_mse)) | 'snr' (eps_mse) | 'snr_plus1' ((1 + SNR) x_mse, the v-space
+                                       # MSE of Salimans & Ho 2022) | 'min_snr' (min(SNR, loss_gamma) x_mse, Hang et al. 2023); other than the default
+                                       # loss() also reports `x_mse` (logged as <model>/test/x_mse); not with teacher_path; not in the reference
+        DG.loss_gamma = 5.0            # Min-SNR's gamma, finite and > 0
+        DG.time_sampler = "uniform"    # 'uniform' (reference: independent times) | 'stratified' (one offset per batch, evenly spaced times: Kingma et al.
+                                       # 2021, VDM App. I.1; every rank of a data-parallel run stratifies its own batch); not with teacher_path
         DG.image_size = 0              # S > 0: images are S x S (CIFAR-10: 32 with in_channels 3); 0: the reference's 28, or 32 with pad32
 
         def __init__(self, G):
@@ -108,11 +114,14 @@ def make_plugin(GMBase, AttrDict):
                 raise ValueError(f"inpaint_eval = {self.inpaint_eval}: 0 (off) or the resample count r >= 1")
             self.binarize = int(get("binarize"))
             dyn_threshold = dyn_threshold_check(get("dyn_threshold"))
+            loss_weight, loss_gamma, time_sampler = loss_weight_check(get("loss_weight"), get("loss_gamma"), get("time_sampler"),
+                                                                      self.teacher_net is not None)
             seed = int(get("seed")) * 1000 + parallel.rank()
             self.diffusion = GaussianDiffusion(mean_type=get("mean_type"), num_steps=int(get("timesteps")),
                                                sampler=get("sampler"), teacher_net=self.teacher_net,
                                                teacher_mode=get("teacher_mode"), sample_cond_w=get("sample_cond_w"),
-                                               seed=seed, dyn_threshold=dyn_threshold)
+                                               seed=seed, dyn_threshold=dyn_threshold, loss_weight=loss_weight, loss_gamma=loss_gamma,
+                                               time_sampler=time_sampler)
             self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
             # EMA of the weights (an extension): a second SimpleUnet of the same arena layout, so one fused launch updates both.  It is seeded
             # from `net` at the first optimiser step (after a data-parallel broadcast of the initial weights) or by a checkpoint load.
@@ -278,7 +287,7 @@ def make_plugin(GMBase, AttrDict):
             B, dev = x.shape[0], x.device
             rng = self.diffusion.rng
             eps = rng.normal(x.shape, dev)                      # the draw order of GaussianDiffusion._prepare: eps, then u
-            u = rng.uniform((B,), dev)
+            u = self.diffusion.draw_u(B, dev)                   # outside the capture, like every draw ('stratified': one draw + gmk_u_stratified)
             key = (tuple(x.shape), y.dtype)
             graphs = self.__dict__.setdefault("_train_graphs", {})
             ent = graphs.get(key)

@@ -14,6 +14,8 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
                                         an extension, no reference call site)
 * probability-flow ODE (`encode`, `decode`, `ode_nll`)  gmk_pf_ode_step, gmk_rng_rademacher, gmk_dequantize and the network's input gradient
                                         (SimpleUnet.input_vjp_hip, gmk_stem_dgrad) (an extension, no reference call site)
+* loss weightings (`loss_weight=`)      'snr' through gmk_v_loss(loss_type 1); 'snr_plus1' (Salimans & Ho 2022) and 'min_snr' (Hang et al. 2023) through
+                                        gmk_x_loss_w; `time_sampler='stratified'` through gmk_u_stratified (extensions, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -86,6 +88,34 @@ def dyn_threshold_check(p):
     if not 0.0 <= p <= 1.0:
         raise ValueError(f"dyn_threshold = {p}: 0 (off) or a percentile in (0, 1]")
     return p
+
+
+LOSS_WEIGHTS = ("snr_trunc", "snr", "snr_plus1", "min_snr")
+TIME_SAMPLERS = ("uniform", "stratified")
+
+
+def loss_weight_check(loss_weight, loss_gamma, time_sampler, has_teacher=False):
+    """The training-objective options: loss_weight 'snr_trunc' (the reference's max(x_mse, eps_mse)), 'snr' (eps_mse), 'snr_plus1'
+    ((1 + e^logsnr) x_mse) or 'min_snr' (min(e^logsnr, loss_gamma) x_mse); loss_gamma finite and > 0; time_sampler 'uniform' (independent
+    draws) or 'stratified' (one offset per batch, evenly spaced times).  With a teacher only the defaults: distillation sets its own
+    weighting, and its step 2 draws discrete times.  -> (loss_weight, float(loss_gamma), time_sampler), or ValueError naming the flag."""
+    if loss_weight not in LOSS_WEIGHTS:
+        raise ValueError(f"loss_weight = {loss_weight!r}: one of {', '.join(LOSS_WEIGHTS)}")
+    if time_sampler not in TIME_SAMPLERS:
+        raise ValueError(f"time_sampler = {time_sampler!r}: one of {', '.join(TIME_SAMPLERS)}")
+    try:
+        gamma = float(loss_gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"loss_gamma = {loss_gamma!r}: a finite number > 0") from None
+    if not (math.isfinite(gamma) and gamma > 0.0):
+        raise ValueError(f"loss_gamma = {gamma}: a finite number > 0")
+    if has_teacher and loss_weight != "snr_trunc":
+        raise ValueError(f"loss_weight = {loss_weight!r} with a teacher (teacher_path): distillation sets its own weighting; leave loss_weight "
+                         f"at 'snr_trunc'")
+    if has_teacher and time_sampler != "uniform":
+        raise ValueError(f"time_sampler = {time_sampler!r} with a teacher (teacher_path): distillation step 2 draws discrete times; leave "
+                         f"time_sampler at 'uniform'")
+    return loss_weight, gamma, time_sampler
 
 
 def dyn_threshold_rank(p, n):
@@ -291,9 +321,27 @@ class _VLoss(torch.autograd.Function):
         return out, None, None, None, None, None, None
 
 
+class _XLossW(torch.autograd.Function):
+    """(loss_b, x_mse) of `ops.x_loss_w`, loss_b = w(logsnr) x_mse differentiable w.r.t. v; x_mse is a reported number only."""
+
+    @staticmethod
+    def forward(ctx, v, z, x, logsnr, weight, gamma, mean_type="v"):
+        loss_b, x_mse, dv = ops.x_loss_w(v.contiguous(), z, x, logsnr, weight, gamma, grad_scale=1.0, mean_type=mean_type)
+        ctx.save_for_backward(dv)
+        ctx.mark_non_differentiable(x_mse)
+        return loss_b, x_mse
+
+    @staticmethod
+    def backward(ctx, g, _g_x_mse):
+        (dv,) = ctx.saved_tensors
+        B = dv.shape[0]
+        out = ops.scale_rows(dv.view(B, -1), g.contiguous().float()).view_as(dv)
+        return out, None, None, None, None, None, None
+
+
 class GaussianDiffusion:
     def __init__(self, *, mean_type, num_steps, teacher_net=None, teacher_mode=None, sampler="ddim", sample_cond_w=None,
-                 seed=0, dyn_threshold=0.0):
+                 seed=0, dyn_threshold=0.0, loss_weight="snr_trunc", loss_gamma=5.0, time_sampler="uniform"):
         if mean_type not in ops.MEAN_TYPES:                     # :70-71
             raise NotImplementedError(mean_type)
         # dynamic thresholding of the samplers' x-hat (Saharia et al. 2022, section 2.3; an extension, no reference call site): 0 is off (the
@@ -306,7 +354,10 @@ class GaussianDiffusion:
         self.teacher_net = teacher_net
         self.sampler = sampler
         self.sample_cond_w = sample_cond_w
-        self.loss_weight_type = "snr_trunc"
+        # the training objective (extensions beside the reference's 'snr_trunc', all off by default): the loss weighting, Min-SNR's gamma and
+        # how a batch's times are drawn (`loss_weight_check`); `loss_weight` is the caller's choice, `loss_weight_type` what a step applies
+        self.loss_weight, self.loss_gamma, self.time_sampler = loss_weight_check(loss_weight, loss_gamma, time_sampler, teacher_net is not None)
+        self.loss_weight_type = self.loss_weight
         if self.teacher_net is not None:                      # :39-43
             assert teacher_mode in ["step1", "step2"]
             self.teacher_mode = teacher_mode
@@ -382,6 +433,13 @@ class GaussianDiffusion:
         v2 = t.forward_hip(torch.cat([z, z]), torch.cat([logsnr, logsnr]), torch.cat([guide, -torch.ones_like(guide)]), None)
         return v2[:B], v2[B:]
 
+    def draw_u(self, B, dev):
+        """The continuous times of one batch from self.rng, fp32 [B] in [0, 1): 'uniform' B independent draws (:94); 'stratified' ONE draw
+        (one Philox counter) expanded to u0 + b / B mod 1 by gmk_u_stratified.  `_prepare` and the graphed train step both draw here."""
+        if self.time_sampler == "stratified":
+            return ops.u_stratified(self.rng.uniform((1,), dev), B)
+        return self.rng.uniform((B,), dev)
+
     def _prepare(self, net, x, u, eps, i_times=None, cond_w=None):
         """Everything ahead of the student's forward pass: draws, q_sample and (distillation) the teacher's targets.
         -> (module, guide, student cond_w, z_t, logsnr, x_target, eps_target, loss_type)"""
@@ -399,11 +457,11 @@ class GaussianDiffusion:
             _, u = ops.logsnr_schedule(B, dev, i_times=i_times, num_steps=self.num_steps, want_u=True)
         else:
             if u is None:
-                u = self.rng.uniform((B,), dev)                                   # :94 continuous time
+                u = self.draw_u(B, dev)                                           # :94 continuous time
             u = ops.aligned(u.float())
         logsnr, z_t = ops.q_sample(x, eps, u)                                     # :95-100
         if not distill:
-            return module, guide, None, z_t, logsnr, x, eps, 0
+            return module, guide, None, z_t, logsnr, x, eps, 1 if self.loss_weight_type == "snr" else 0
         if cond_w is None:
             cond_w = 4.0 * self.rng.uniform((B,), dev)                            # :107
         cond_w = ops.aligned(cond_w.float())
@@ -428,11 +486,19 @@ class GaussianDiffusion:
         assert x.dtype in [torch.float32, torch.float64]
         module, guide, w, z_t, logsnr, x_t, eps_t, loss_type = self._prepare(net, x, u, eps, i_times, cond_w)
         v = module(z_t, logsnr, guide=guide, cond_w=w)
-        if torch.is_grad_enabled() and v.requires_grad:
+        grad = torch.is_grad_enabled() and v.requires_grad
+        if self.loss_weight_type in ops.X_LOSS_WEIGHTS:           # 'snr_plus1' / 'min_snr': w(logsnr) x_mse, no eps anywhere
+            if grad:
+                loss, x_mse = _XLossW.apply(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, self.mean_type)
+            else:
+                loss, x_mse, _ = ops.x_loss_w(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, mean_type=self.mean_type)
+            return {"loss": loss, "x_mse": x_mse}
+        if grad:
             loss = _VLoss.apply(v, z_t, x_t, eps_t, logsnr, loss_type, self.mean_type)
-        else:
-            loss = ops.v_loss(v, z_t, x_t, eps_t, logsnr, loss_type=loss_type, mean_type=self.mean_type)[0]
-        return {"loss": loss}
+            return {"loss": loss}
+        loss, x_mse = ops.v_loss(v, z_t, x_t, eps_t, logsnr, loss_type=loss_type, mean_type=self.mean_type)[:2]
+        # a weighting chosen by the caller also reports the unweighted x_mse: one number that compares runs under different weightings
+        return {"loss": loss, "x_mse": x_mse} if self.loss_weight != "snr_trunc" else {"loss": loss}
 
     def train_forward_backward(self, *, net, x, grad_scale, u=None, eps=None, i_times=None, cond_w=None,
                                on_grads_ready=None, join_side_before_ready=True):
@@ -441,6 +507,10 @@ class GaussianDiffusion:
         module, guide, w, z_t, logsnr, x_t, eps_t, loss_type = self._prepare(net, x, u, eps, i_times, cond_w)
         ctx = {}
         v = module.forward_hip(z_t, logsnr, guide, w, ctx=ctx)
+        if self.loss_weight_type in ops.X_LOSS_WEIGHTS:
+            loss_b, x_mse, dv = ops.x_loss_w(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, grad_scale=grad_scale, mean_type=self.mean_type)
+            module.backward_hip(ctx, dv, on_grads_ready=on_grads_ready, join_side_before_ready=join_side_before_ready)
+            return {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
         loss_b, x_mse, eps_mse, dv = ops.v_loss(v, z_t, x_t, eps_t, logsnr, grad_scale=grad_scale, loss_type=loss_type, mean_type=self.mean_type)
         module.backward_hip(ctx, dv, on_grads_ready=on_grads_ready, join_side_before_ready=join_side_before_ready)
         return {"loss": loss_b, "x_mse": x_mse, "eps_mse": eps_mse, "logsnr": logsnr}

@@ -941,6 +941,49 @@ def v_loss(v, z, x, eps, logsnr, grad_scale=None, loss_type=0, mean_type="v"):
     return loss_b, xm, em, dv
 
 
+X_LOSS_WEIGHTS = {"snr_plus1": 0, "min_snr": 1}      # GMK_LOSS_W_* of include/gmk.h: the weightings gmk_x_loss_w evaluates
+X_LOSS_KEEP = 12288             # kXLossKeep of csrc/diffusion_ew.hip: images of up to this many values keep their residuals in LDS, larger ones are re-read
+
+
+def x_loss_w(v, z, x, logsnr, weight, gamma, grad_scale=None, mean_type="v"):
+    """Weighted x-space loss (gmk_x_loss_w; an extension): loss_b = w(logsnr) x_mse with weight 'snr_plus1' (w = 1 + e^logsnr, Salimans & Ho
+    2022) or 'min_snr' (w = min(e^logsnr, gamma), Hang et al. 2023), x_mse = mean (x_hat - x)^2 of the clipped prediction - the bits of
+    `v_loss`'s x_mse.  v, z, x: fp32 [B, ...], contiguous (16-byte aligned tensors with n % 4 == 0 take the 16-byte path, anything else the
+    scalar one); logsnr: fp32 [B].  -> (loss_b, x_mse, dv or None), dv = d(grad_scale sum_b loss_b)/dv when grad_scale is given."""
+    if weight not in X_LOSS_WEIGHTS:
+        raise ValueError(f"weight {weight!r}: expected one of {sorted(X_LOSS_WEIGHTS)}")
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    gamma = float(gamma)
+    if not (math.isfinite(gamma) and gamma > 0.0):
+        raise ValueError(f"gamma = {gamma}: need a finite value > 0")
+    for t, nm in ((v, "v"), (z, "z"), (x, "x"), (logsnr, "logsnr")):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
+            raise ValueError(f"{nm}: expected a contiguous fp32 device tensor")
+    B = x.shape[0]
+    n = x.numel() // B
+    assert v.shape == x.shape == z.shape and logsnr.numel() == B
+    loss_b = torch.empty((B,), device=x.device, dtype=torch.float32)
+    xm = torch.empty_like(loss_b)
+    dv = torch.empty_like(v) if grad_scale is not None else None
+    check(lib.gmk_x_loss_w(_p(v), _p(z), _p(x), _p(logsnr), _p(loss_b), _p(xm), _p(dv), float(grad_scale or 0.0), X_LOSS_WEIGHTS[weight], gamma,
+                           MEAN_TYPES[mean_type], B, n, _s()), "x_loss_w")
+    return loss_b, xm, dv
+
+
+def u_stratified(u0, B):
+    """Low-discrepancy times (gmk_u_stratified; Kingma et al. 2021, VDM, App. I.1): u[b] = frac(u0 + b / B) in fp32 from ONE uniform draw u0
+    (fp32, one element, on the device); exactly one u in every [k / B, (k + 1) / B) when B is a power of two and u0 a multiple of 2^-24
+    (`rng_uniform`'s values), in [0, 1) for every B.  -> fp32 [B]"""
+    _f32(u0, "u0")
+    B = int(B)
+    if u0.numel() != 1 or not 1 <= B <= 1 << 24:
+        raise ValueError(f"u_stratified: u0 of {u0.numel()} values, B = {B}: one offset and 1 <= B <= 2^24")
+    u = torch.empty((B,), device=u0.device, dtype=torch.float32)
+    check(lib.gmk_u_stratified(_p(u0), _p(u), B, _s()), "u_stratified")
+    return u
+
+
 def _sampler_check(v, z, same_shape, cond_w):
     """The input checks `sampler_step`, `dpm_solver_step` and `dyn_threshold` share.  same_shape: (tensor or None, name) pairs of z's shape.
     -> (B, n)"""

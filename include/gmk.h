@@ -324,6 +324,28 @@ int gmk_v_loss(const float* v, const float* z, const float* x, const float* eps,
                void* stream);
 /* loss_type 0 = 'snr_trunc' (max of the two MSEs, :168-169), 1 = 'snr' (eps MSE only, :170-171, distillation step1);
  * x / eps are the denoising targets (x0, eps) or the teacher's (x_target, eps_target). */
+/* weighted x-space losses; an extension, no reference call site.  Per image b with l = logsnr[b] (SNR = e^l):
+ *   x_hat = clip(x_from_output(v), -1, 1) by mean_type (gmk_v_loss's three formulas), m_b = mean_i (x_hat_i - x_i)^2,
+ *   loss_b[b] = w(l) m_b, x_mse[b] = m_b, with
+ *     weight_type GMK_LOSS_W_SNR_PLUS1: w = 1 + e^l        (Salimans & Ho 2022, "Progressive Distillation for Fast Sampling of Diffusion
+ *                                                           Models", section 4: the 'SNR+1' weighting, the MSE in v space)
+ *     weight_type GMK_LOSS_W_MIN_SNR:   w = min(e^l, gamma) (Hang et al. 2023, "Efficient Diffusion Training via Min-SNR Weighting Strategy")
+ *   dv (optional) = d(grad_scale * sum_b loss_b)/dv: dv_i = grad_scale w (2 / n) (x_hat_i - x_i) dx/dout where the raw prediction lies in
+ *   [-1, 1] (ends included), else 0 - gmk_v_loss's clip rule; w depends on l alone, so the min routes nothing.
+ * x_mse carries the bits gmk_v_loss writes to its x_mse for the same (v, z, x, logsnr, mean_type): the same element-to-thread assignment and
+ * summation order, on the 16-byte path (n % 4 == 0 and v, z, x, dv 16-byte aligned) and on the scalar one.  Images of up to 12,288 values keep
+ * their residuals in LDS between the reduction and the gradient (v, z, x are read once); larger ones are read again.  gamma: finite, > 0
+ * (checked for either weight_type).  loss_b, x_mse: fp32 [B], both required. */
+#define GMK_LOSS_W_SNR_PLUS1 0
+#define GMK_LOSS_W_MIN_SNR 1
+int gmk_x_loss_w(const float* v, const float* z, const float* x, const float* logsnr, float* loss_b, float* x_mse, float* dv,
+                 float grad_scale, int weight_type, float gamma, int mean_type, int B, int64_t n, void* stream);
+/* low-discrepancy training times (Kingma et al. 2021, "Variational Diffusion Models", App. I.1); an extension: u[b] = frac(u0[0] + b / B) as
+ *   s = fdiv(b, B), c = fsub(1, s), u[b] = u0 >= c ? fsub(u0, c) : min(fadd(u0, s), 1 - 2^-24)
+ * - single correctly rounded fp32 operations; the wrap comes before the sum because fadd(u0, s) is not exact at or above 1.  With B a power
+ * of two and u0 a multiple of 2^-24 (gmk_rng_uniform's values) all of it is exact and every [k / B, (k + 1) / B) holds exactly one u; u lies in
+ * [0, 1) for every B.  u0: one value in [0, 1); u: fp32 [B], 1 <= B <= 2^24. */
+int gmk_u_stratified(const float* u0, float* u, int B, void* stream);
 /* one reverse step on a batch (gaussian_diffusion.py:189-243,174-187,292):
  *   v: conditional net output; v_uncond/cond_w: NULL or the unconditional output + per-sample guidance weight;
  *   noise: NULL -> DDIM update, else ancestral ('noisy') update with that noise; is_last: the i == 0 select.
