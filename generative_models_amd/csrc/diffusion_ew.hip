@@ -237,6 +237,143 @@ __global__ __launch_bounds__(256) void u_stratified_kernel(const float* __restri
     u[b] = o >= c ? __fsub_rn(o, c) : fminf(__fadd_rn(o, s), 0x1.fffffep-1f);
 }
 
+// ---- the per-log-SNR loss profile and the loss-aware time sampler (Nichol & Dhariwal 2021, "Improved DDPM", section 3.3); extensions, no
+// reference call site.  GMK_PROFILE_BINS = 64 bins of equal width in u, one per lane of a wavefront; the state is fp32 [5][64]: W (decayed
+// sample count), then (S1, S2) = decayed sum and sum of squares of value channel 0 and of value channel 1.  Both kernels are single correctly
+// rounded fp32 operations in a stated order (u_stratified_kernel's idiom), so numpy float32 restates them bit for bit.  The square root is
+// __builtin_sqrtf, which this build rounds correctly (as it does `/`); __fsqrt_rn is the native approximation without OCML's rounded operations.
+constexpr int kProfileBins = GMK_PROFILE_BINS;
+constexpr int kProfileTile = 1024;                // samples staged in LDS per pass: bin, v0, v1 = 12 KiB
+static_assert(kProfileBins == 64, "one bin per lane of a wavefront");
+
+__device__ __forceinline__ float sqrt_rn(float x) { return __builtin_sqrtf(x); }
+
+struct ProfileAcc {
+    int n;
+    float a0, q0, a1, q1;
+    __device__ __forceinline__ void add(int bin, int lane, float x0, float x1) {
+        if (bin == lane) {
+            ++n;
+            a0 = __fadd_rn(a0, x0); q0 = __fadd_rn(q0, __fmul_rn(x0, x0));
+            a1 = __fadd_rn(a1, x1); q1 = __fadd_rn(q1, __fmul_rn(x1, x1));
+        }
+    }
+};
+
+// One workgroup.  All 256 threads stage a tile of samples in LDS as (bin or -1, v0, v1): bin = min((int)(u 64), 63), -1 for a sample that is
+// skipped (u outside [0, 1), or a value that is not finite - one NaN loss must not poison the state for the rest of the run).  Then lane k of
+// wave 0 walks the tile in ascending b and adds the samples of bin k: n = their count, a_c = the sequential sum of the values, q_c of their
+// squares (LDS reads of one address by every lane: broadcasts).  After the last tile a bin with n > 0 takes
+//   W = decay W + n,  S1_c = decay S1_c + a_c,  S2_c = decay S2_c + q_c;
+// a bin with n = 0 keeps its five words' bits, and rows 3 and 4 keep theirs when v1 is NULL.  No atomics: a pure function of the inputs.
+__global__ __launch_bounds__(256) void loss_profile_kernel(const float* __restrict__ u, const float* __restrict__ v0, const float* __restrict__ v1,
+                                                           int B, float decay, float* __restrict__ state) {
+    __shared__ __align__(16) int s_bin[kProfileTile];
+    __shared__ __align__(16) float s_v0[kProfileTile];
+    __shared__ __align__(16) float s_v1[kProfileTile];
+    const int lane = threadIdx.x;
+    ProfileAcc acc = {0, 0.f, 0.f, 0.f, 0.f};
+    for (int base = 0; base < B; base += kProfileTile) {
+        const int m = min(kProfileTile, B - base);
+        const int m4 = (m + 3) & ~3;                    // the walk reads four samples at a time: the tail is padded with skipped ones
+        __syncthreads();                                // the previous tile has been walked
+        for (int i = threadIdx.x; i < m4; i += 256) {
+            int bin = -1;
+            float x0 = 0.f, x1 = 0.f;
+            if (i < m) {
+                const float uu = u[base + i];
+                x0 = v0[base + i];
+                x1 = v1 ? v1[base + i] : 0.f;
+                if (uu >= 0.f && uu < 1.f && isfinite(x0) && isfinite(x1)) bin = min((int)__fmul_rn(uu, 64.f), kProfileBins - 1);
+            }
+            s_bin[i] = bin; s_v0[i] = x0; s_v1[i] = x1;
+        }
+        __syncthreads();
+        if (threadIdx.x < kProfileBins) {
+            for (int i = 0; i < m4; i += 4) {
+                const int4 b4 = *reinterpret_cast<const int4*>(s_bin + i);
+                const float4 x = *reinterpret_cast<const float4*>(s_v0 + i);
+                const float4 y = *reinterpret_cast<const float4*>(s_v1 + i);
+                acc.add(b4.x, lane, x.x, y.x);
+                acc.add(b4.y, lane, x.y, y.y);
+                acc.add(b4.z, lane, x.z, y.z);
+                acc.add(b4.w, lane, x.w, y.w);
+            }
+        }
+    }
+    if (threadIdx.x < kProfileBins && acc.n > 0) {
+        float* W = state + lane;
+        W[0] = __fadd_rn(__fmul_rn(decay, W[0]), (float)acc.n);
+        W[1 * kProfileBins] = __fadd_rn(__fmul_rn(decay, W[1 * kProfileBins]), acc.a0);
+        W[2 * kProfileBins] = __fadd_rn(__fmul_rn(decay, W[2 * kProfileBins]), acc.q0);
+        if (v1) {
+            W[3 * kProfileBins] = __fadd_rn(__fmul_rn(decay, W[3 * kProfileBins]), acc.a1);
+            W[4 * kProfileBins] = __fadd_rn(__fmul_rn(decay, W[4 * kProfileBins]), acc.q1);
+        }
+    }
+}
+
+// The inverse-CDF draw from the profile and its importance weight.  Every workgroup forms the same table in bin order (wave 0, lane k = bin k;
+// the two running sums are the same 64 sequential additions in every lane):
+//   ready = every W_k >= warm;  r_k = sqrt(S2_k / W_k) (channel 0),  R = r_0 + ... + r_63 in that order
+//   p_k = (r_k / R) (1 - floor) + floor / 64  when ready and R is finite and > 0,  else 2^-6 (uniform)
+//   c_0 = 0, c_{k+1} = c_k + p_k, C = c_64;  w_k = C / (64 p_k)
+// and thread b draws t = u0[b] C, k = the largest index with c_k <= t, f = min((t - c_k) / p_k, 1 - 2^-24),
+//   u[b] = min((k + f) 2^-6, the float below (k + 1) 2^-6),  w[b] = w_k.
+// The last min keeps u inside bin k and below 1, so w[b] is the table's entry of u[b]'s bin.  With p_k = 2^-6 every operation is exact for
+// every fp32 u0 in [0, 1): u = u0 bit for bit and w = 1 - a run inside the sampler's warm-up is the run without it.
+__global__ __launch_bounds__(256) void u_importance_kernel(const float* __restrict__ state, const float* __restrict__ u0, float* __restrict__ u,
+                                                           float* __restrict__ w, int B, float warm, float floor_, float* __restrict__ p_out,
+                                                           float* __restrict__ w_out) {
+    __shared__ float s_r[kProfileBins], s_p[kProfileBins], s_w[kProfileBins], s_c[kProfileBins + 1];
+    const int k0 = threadIdx.x;
+    const bool table = k0 < kProfileBins;               // wave 0, all 64 lanes
+    bool ready = false;
+    float r = 0.f, p = 0.015625f;
+    if (table) {
+        const float W = state[k0], S2 = state[2 * kProfileBins + k0];
+        ready = __ballot(W >= warm) == ~0ull;
+        r = sqrt_rn(__fdiv_rn(S2, W));
+        s_r[k0] = r;
+    }
+    __syncthreads();
+    if (table) {
+        float R = 0.f;
+        for (int j = 0; j < kProfileBins; ++j) R = __fadd_rn(R, s_r[j]);
+        if (ready && isfinite(R) && R > 0.f)
+            p = __fadd_rn(__fmul_rn(__fdiv_rn(r, R), __fsub_rn(1.0f, floor_)), __fdiv_rn(floor_, 64.f));
+        s_p[k0] = p;
+    }
+    __syncthreads();
+    if (table) {
+        float c = 0.f, ck = 0.f;
+        for (int j = 0; j < kProfileBins; ++j) {
+            if (j == k0) ck = c;
+            c = __fadd_rn(c, s_p[j]);
+        }
+        const float wk = __fdiv_rn(c, __fmul_rn(64.f, p));
+        s_c[k0] = ck;
+        if (k0 == 0) s_c[kProfileBins] = c;
+        s_w[k0] = wk;
+        if (blockIdx.x == 0) {
+            if (p_out) p_out[k0] = p;
+            if (w_out) w_out[k0] = wk;
+        }
+    }
+    __syncthreads();
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const float t = __fmul_rn(u0[b], s_c[kProfileBins]);
+    int k = 0;
+#pragma unroll
+    for (int step = kProfileBins / 2; step > 0; step >>= 1)
+        if (s_c[k + step] <= t) k += step;              // k + step <= 63
+    const float f = fminf(__fdiv_rn(__fsub_rn(t, s_c[k]), s_p[k]), 0x1.fffffep-1f);
+    const float below = __uint_as_float(__float_as_uint(__fmul_rn((float)(k + 1), 0.015625f)) - 1u);      // nextafterf((k + 1) / 64, 0)
+    u[b] = fminf(__fmul_rn(__fadd_rn((float)k, f), 0.015625f), below);
+    w[b] = s_w[k];
+}
+
 // ---- dynamic thresholding (Saharia et al. 2022, Imagen, section 2.3); an extension, no reference call site.
 // The UNCLIPPED data prediction of one element: x_from_out of the conditional output, and when guided the extrapolation of sampler_step_kernel
 // without its three clips (a prediction clipped at +-1 before the extrapolation would defeat the threshold).  Guidance is defined in eps space,
@@ -966,6 +1103,24 @@ extern "C" int gmk_u_stratified(const float* u0, float* u, int B, void* stream) 
     GMK_REQUIRE(B > 0 && B <= (1 << 24), "gmk_u_stratified: B = %d outside [1, 2^24] (b and B must be exact in fp32)", B);
     u_stratified_kernel<<<(B + 255) / 256, 256, 0, gmk_stream(stream)>>>(u0, u, B);
     return gmk_check_launch("gmk_u_stratified");
+}
+
+extern "C" int gmk_loss_profile(const float* u, const float* v0, const float* v1, int B, float decay, float* state, void* stream) {
+    GMK_REQUIRE(u && v0 && state, "gmk_loss_profile: null pointer");
+    GMK_REQUIRE(B > 0 && B <= (1 << 24), "gmk_loss_profile: B = %d outside [1, 2^24] (a bin's count must be exact in fp32)", B);
+    GMK_REQUIRE(decay > 0.0f && decay <= 1.0f, "gmk_loss_profile: decay = %g outside (0, 1]", (double)decay);
+    loss_profile_kernel<<<1, 256, 0, gmk_stream(stream)>>>(u, v0, v1, B, decay, state);
+    return gmk_check_launch("gmk_loss_profile");
+}
+
+extern "C" int gmk_u_importance(const float* state, const float* u0, float* u, float* w, int B, float warm, float floor, float* p_out,
+                                float* w_out, void* stream) {
+    GMK_REQUIRE(state && u0 && u && w, "gmk_u_importance: null pointer");
+    GMK_REQUIRE(B > 0 && B <= (1 << 24), "gmk_u_importance: B = %d outside [1, 2^24]", B);
+    GMK_REQUIRE(warm >= 0.0f, "gmk_u_importance: warm = %g, need a count >= 0", (double)warm);
+    GMK_REQUIRE(floor > 0.0f && floor <= 1.0f, "gmk_u_importance: floor = %g outside (0, 1]", (double)floor);
+    u_importance_kernel<<<(B + 255) / 256, 256, 0, gmk_stream(stream)>>>(state, u0, u, w, B, warm, floor, p_out, w_out);
+    return gmk_check_launch("gmk_u_importance");
 }
 
 // The checks every entry that forms the (guided) prediction shares: the four gmk_*_step* entries, gmk_ddim_step_vec and gmk_dyn_threshold

@@ -23,7 +23,7 @@ import os
 import torch
 
 from .. import checkpoint, common, ops, parallel
-from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check, loss_weight_check
+from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check, loss_weight_check, time_importance_check
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -76,6 +76,14 @@ def make_plugin(GMBase, AttrDict):
         DG.loss_gamma = 5.0            # Min-SNR's gamma, finite and > 0
         DG.time_sampler = "uniform"    # 'uniform' (reference: independent times) | 'stratified' (one offset per batch, evenly spaced times: Kingma et al.
                                        # 2021, VDM App. I.1; every rank of a data-parallel run stratifies its own batch); not with teacher_path
+        DG.time_importance = 0         # 1: draw the training times with p(t) proportional to sqrt(E[L_t^2]) of a running 64-bin loss profile and reweight by
+                                       # 1 / p (Nichol & Dhariwal 2021, section 3.3; gmk_u_importance); uniform until every bin holds importance_warmup
+                                       # samples; one rank only; not with teacher_path; not in the reference, off by default
+        DG.importance_decay = 0.9      # per-bin decay of the profile, in (0, 1]: a window of about 1 / (1 - decay) of the bin's own samples (untuned)
+        DG.importance_warmup = 5       # samples every bin must hold before the sampler leaves uniform, <= 0.5 / (1 - importance_decay) (untuned)
+        DG.importance_floor = 0.01     # the uniform share of the sampling distribution, in (0, 1] (untuned)
+        DG.loss_profile = 0            # 1: keep the per-time profile of the train and test losses (gmk_loss_profile) and write it to
+                                       # <logdir>/loss_profile.csv after every evaluation; nothing is sampled from it; not with teacher_path
         DG.image_size = 0              # S > 0: images are S x S (CIFAR-10: 32 with in_channels 3); 0: the reference's 28, or 32 with pad32
 
         def __init__(self, G):
@@ -116,12 +124,17 @@ def make_plugin(GMBase, AttrDict):
             dyn_threshold = dyn_threshold_check(get("dyn_threshold"))
             loss_weight, loss_gamma, time_sampler = loss_weight_check(get("loss_weight"), get("loss_gamma"), get("time_sampler"),
                                                                       self.teacher_net is not None)
+            time_importance, importance_decay, importance_warmup, importance_floor, loss_profile = time_importance_check(
+                get("time_importance"), get("importance_decay"), get("importance_warmup"), get("importance_floor"), get("loss_profile"),
+                self.teacher_net is not None, parallel.world())
+            self.loss_profile = loss_profile
             seed = int(get("seed")) * 1000 + parallel.rank()
             self.diffusion = GaussianDiffusion(mean_type=get("mean_type"), num_steps=int(get("timesteps")),
                                                sampler=get("sampler"), teacher_net=self.teacher_net,
                                                teacher_mode=get("teacher_mode"), sample_cond_w=get("sample_cond_w"),
                                                seed=seed, dyn_threshold=dyn_threshold, loss_weight=loss_weight, loss_gamma=loss_gamma,
-                                               time_sampler=time_sampler)
+                                               time_sampler=time_sampler, time_importance=time_importance, importance_decay=importance_decay,
+                                               importance_warmup=importance_warmup, importance_floor=importance_floor, loss_profile=loss_profile)
             self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
             # EMA of the weights (an extension): a second SimpleUnet of the same arena layout, so one fused launch updates both.  It is seeded
             # from `net` at the first optimiser step (after a data-parallel broadcast of the initial weights) or by a checkpoint load.
@@ -189,9 +202,17 @@ def make_plugin(GMBase, AttrDict):
 
         def train_state(self):
             """Everything a continued run needs beside the weights of `state_dict()`: Adam's moments, step count and skipped-step count, the
-            counters of the three Philox streams (noise and timesteps; label drop and sampling; dropout masks) and the arena digests."""
-            return {"optimizer": self.optimizer.state_dict(), "rng": self.diffusion.rng.state_dict(), "aux_rng": self._aux_rng.state_dict(),
-                    "dropout": self.net.dropout_state(), "digests": self.arena_digests()}
+            counters of the three Philox streams (noise and timesteps; label drop and sampling; dropout masks) and the arena digests; with
+            time_importance or loss_profile on also `time_profile`, the CPU copy of the train pass's loss profile (fp32 [5, 64])."""
+            state = {"optimizer": self.optimizer.state_dict(), "rng": self.diffusion.rng.state_dict(), "aux_rng": self._aux_rng.state_dict(),
+                     "dropout": self.net.dropout_state(), "digests": self.arena_digests()}
+            if self._profiled():
+                prof = self.diffusion.time_profile
+                state["time_profile"] = torch.zeros((5, ops.PROFILE_BINS)) if prof is None else prof.detach().cpu().clone()
+            return state
+
+        def _profiled(self):
+            return bool(self.diffusion.time_importance or self.diffusion.loss_profile)
 
         def load_train_state(self, state):
             """The inverse of train_state(), on a model that has loaded the `state_dict()` saved with it: the parameter and EMA arenas must
@@ -207,6 +228,10 @@ def make_plugin(GMBase, AttrDict):
             self.diffusion.rng.load_state_dict(state["rng"])
             self._aux_rng.load_state_dict(state["aux_rng"])
             self.net.load_dropout_state(state["dropout"])
+            if self._profiled():                    # a state saved without the flags carries no profile: the sampler warms up again from zeros
+                prof = state.get("time_profile")
+                prof = torch.zeros((5, ops.PROFILE_BINS)) if prof is None else prof.float().reshape(5, ops.PROFILE_BINS)
+                self.diffusion.time_profile = prof.to(self.net.flat_params.device).contiguous()
             have = self.arena_digests()
             for name in ("m", "v"):
                 if want[name] != have[name]:
@@ -280,8 +305,9 @@ def make_plugin(GMBase, AttrDict):
         TRAIN_GRAPH_MAX_PIXELS = int(os.environ.get("GMK_TRAIN_GRAPH_PIXELS", str(64 * 1024)))
 
         def _graphable(self, x, world):
+            # (the loss-profile kernels are not captured: with time_importance or loss_profile the small-batch step runs kernel by kernel)
             return (world == 1 and not parallel.exchanging() and self.teacher_net is None and self.net.dropout == 0.0 and x.is_cuda and x.dim() == 4 and
-                    0 < x.shape[0] * x.shape[2] * x.shape[3] <= self.TRAIN_GRAPH_MAX_PIXELS and ops.PROFILE is None)
+                    0 < x.shape[0] * x.shape[2] * x.shape[3] <= self.TRAIN_GRAPH_MAX_PIXELS and ops.PROFILE is None and not self._profiled())
 
         def _train_step_graphed(self, x, y):
             B, dev = x.shape[0], x.device

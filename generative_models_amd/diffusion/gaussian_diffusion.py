@@ -16,6 +16,8 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
                                         (SimpleUnet.input_vjp_hip, gmk_stem_dgrad) (an extension, no reference call site)
 * loss weightings (`loss_weight=`)      'snr' through gmk_v_loss(loss_type 1); 'snr_plus1' (Salimans & Ho 2022) and 'min_snr' (Hang et al. 2023) through
                                         gmk_x_loss_w; `time_sampler='stratified'` through gmk_u_stratified (extensions, no reference call site)
+* loss profile (`loss_profile=`, `time_importance=`)  gmk_loss_profile keeps the per-time profile of the loss on the device; gmk_u_importance draws
+                                        the training times from it (Nichol & Dhariwal 2021, section 3.3) (extensions, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -116,6 +118,74 @@ def loss_weight_check(loss_weight, loss_gamma, time_sampler, has_teacher=False):
         raise ValueError(f"time_sampler = {time_sampler!r} with a teacher (teacher_path): distillation step 2 draws discrete times; leave "
                          f"time_sampler at 'uniform'")
     return loss_weight, gamma, time_sampler
+
+
+def time_importance_check(time_importance, importance_decay, importance_warmup, importance_floor, loss_profile, has_teacher=False, world=1):
+    """The loss-profile options: time_importance 0 | 1 (draw training times with p(t) proportional to sqrt(E[L_t^2]) of the running profile and
+    reweight by 1 / p: Nichol & Dhariwal 2021, section 3.3), loss_profile 0 | 1 (keep the per-time profile of the train and test losses without
+    sampling from it); importance_decay in (0, 1] (a bin's window over its own samples), importance_warmup >= 0 (samples every bin must hold
+    before the sampler leaves uniform), importance_floor in (0, 1] (the uniform share of p).  With decay < 1 a bin's count settles at
+    1 / (1 - decay); warmup <= 0.5 / (1 - decay), half of that, is asked: then W >= warmup implies decay W + 1 >= warmup, so a bin that has
+    reached the warm-up count never falls below it again, and the sampler cannot flip back to uniform.  Not with a teacher (distillation step 2 draws
+    discrete times); time_importance not with more than one rank.
+    -> (time_importance, decay, warmup, floor, loss_profile) as (int, float, float, float, int), or ValueError naming the flag."""
+    flags = {}
+    for name, val in (("time_importance", time_importance), ("loss_profile", loss_profile)):
+        try:
+            ok = not isinstance(val, bool) and float(val) in (0.0, 1.0)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{name} = {val!r}: 0 (off) or 1")
+        flags[name] = int(val)
+    nums = {}
+    for name, val in (("importance_decay", importance_decay), ("importance_warmup", importance_warmup), ("importance_floor", importance_floor)):
+        try:
+            nums[name] = float(val)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} = {val!r}: a number") from None
+    decay, warmup, floor = nums["importance_decay"], nums["importance_warmup"], nums["importance_floor"]
+    if not 0.0 < decay <= 1.0:
+        raise ValueError(f"importance_decay = {decay}: the per-bin decay of the loss profile, in (0, 1]")
+    if not 0.0 < floor <= 1.0:
+        raise ValueError(f"importance_floor = {floor}: the uniform share of the sampling distribution, in (0, 1]")
+    if not (warmup >= 0.0 and math.isfinite(warmup)):
+        raise ValueError(f"importance_warmup = {warmup}: the sample count every bin must hold before the sampler leaves uniform, >= 0")
+    if decay < 1.0 and warmup * (1.0 - decay) > 0.5 + 1e-9:         # (1e-9: 1 - decay is not exact in binary; 0.99 and 50 pass)
+        raise ValueError(f"importance_warmup = {warmup} with importance_decay = {decay}: above 0.5 / (1 - decay) = {0.5 / (1.0 - decay):g} a bin that "
+                         f"reached the warm-up count could fall below it again (its count settles at {1.0 / (1.0 - decay):g}) and the sampler "
+                         f"would flip back to uniform; lower importance_warmup or raise importance_decay")
+    for name, on in flags.items():
+        if on and has_teacher:
+            raise ValueError(f"{name} = 1 with a teacher (teacher_path): distillation step 2 draws discrete times; leave {name} at 0")
+    if flags["time_importance"] and int(world) > 1:
+        raise ValueError(f"time_importance = 1 on {int(world)} ranks: one train_state.pt serves every rank, and a replicated loss profile needs a "
+                         f"per-step collective that nobody here can test; importance sampling runs on one rank only (loss_profile = 1 does run "
+                         f"data-parallel: every rank keeps its own profile)")
+    return flags["time_importance"], decay, warmup, floor, flags["loss_profile"]
+
+
+def profile_bin_edges():
+    """The 64 bins of the loss profile on the host: (u_lo, u_hi, logsnr_hi, logsnr_lo), fp32 [64] each - bin k is [k / 64, (k + 1) / 64) in u,
+    and its log-SNR range follows from the schedule (`logsnr_schedule_cosine_host`; the schedule falls, so u_lo carries the high end)."""
+    n = ops.PROFILE_BINS
+    u_lo = np.arange(n, dtype=np.float32) / np.float32(n)
+    u_hi = np.arange(1, n + 1, dtype=np.float32) / np.float32(n)
+    return u_lo, u_hi, logsnr_schedule_cosine_host(u_lo), logsnr_schedule_cosine_host(u_hi)
+
+
+def profile_rows(state, p=None):
+    """Host view of a profile state (fp32 [5, 64] array): dict of [64] arrays - u_lo, u_hi, logsnr_hi, logsnr_lo (`profile_bin_edges`), weight = W,
+    loss_mean = S1_0 / W, loss_rms = sqrt(S2_0 / W), x_mse_mean = S1_1 / W (NaN where W = 0), and p: the sampling probabilities given, or None."""
+    s = np.asarray(state, dtype=np.float64)
+    if s.shape != (5, ops.PROFILE_BINS):
+        raise ValueError(f"profile state of shape {s.shape}, expected (5, {ops.PROFILE_BINS})")
+    u_lo, u_hi, l_hi, l_lo = profile_bin_edges()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        W = s[0]
+        rows = {"u_lo": u_lo, "u_hi": u_hi, "logsnr_hi": l_hi, "logsnr_lo": l_lo, "weight": W, "loss_mean": s[1] / W, "loss_rms": np.sqrt(s[2] / W),
+                "x_mse_mean": s[3] / W, "p": None if p is None else np.asarray(p, dtype=np.float64)}
+    return rows
 
 
 def dyn_threshold_rank(p, n):
@@ -341,7 +411,8 @@ class _XLossW(torch.autograd.Function):
 
 class GaussianDiffusion:
     def __init__(self, *, mean_type, num_steps, teacher_net=None, teacher_mode=None, sampler="ddim", sample_cond_w=None,
-                 seed=0, dyn_threshold=0.0, loss_weight="snr_trunc", loss_gamma=5.0, time_sampler="uniform"):
+                 seed=0, dyn_threshold=0.0, loss_weight="snr_trunc", loss_gamma=5.0, time_sampler="uniform", time_importance=0,
+                 importance_decay=0.9, importance_warmup=5, importance_floor=0.01, loss_profile=0):
         if mean_type not in ops.MEAN_TYPES:                     # :70-71
             raise NotImplementedError(mean_type)
         # dynamic thresholding of the samplers' x-hat (Saharia et al. 2022, section 2.3; an extension, no reference call site): 0 is off (the
@@ -363,6 +434,13 @@ class GaussianDiffusion:
             self.teacher_mode = teacher_mode
             if self.teacher_mode == "step1":
                 self.loss_weight_type = "snr"
+        # the loss profile (extensions, off by default; `time_importance_check`): with either flag the fused train pass keeps `time_profile`, the
+        # fp32 [5, 64] device state of gmk_loss_profile over its own (u, loss_b, x_mse), and with `time_importance` it draws its times from it
+        # (gmk_u_importance); with `loss_profile` the test pass (`training_losses`) sums into a state of its own.  Allocated on first use, zeros.
+        self.time_importance, self.importance_decay, self.importance_warmup, self.importance_floor, self.loss_profile = time_importance_check(
+            time_importance, importance_decay, importance_warmup, importance_floor, loss_profile, teacher_net is not None)
+        self.time_profile = None
+        self._test_profile = None
         self.rng = PhiloxStream(seed)
         self._graphs = {}                   # small-batch sampling: one captured U-Net forward per (net, shape, conditioning kind)
 
@@ -440,6 +518,32 @@ class GaussianDiffusion:
             return ops.u_stratified(self.rng.uniform((1,), dev), B)
         return self.rng.uniform((B,), dev)
 
+    # ---- the loss profile and the loss-aware time sampler (extensions, no reference call site) --------------------------------------------
+    def profile_state(self, split, dev):
+        """The fp32 [5, 64] profile state of `split` ('train': `time_profile`, 'test') on `dev`, allocated as zeros on first use."""
+        name = {"train": "time_profile", "test": "_test_profile"}[split]
+        t = getattr(self, name)
+        if t is None or t.device != torch.device(dev):
+            t = torch.zeros((5, ops.PROFILE_BINS), device=dev) if t is None else t.to(dev)
+            setattr(self, name, t)
+        return t
+
+    def profile(self, split, reset=False):
+        """Host arrays of one split's profile (`profile_rows`: bin edges in u and log-SNR, weight, loss_mean, loss_rms, x_mse_mean), None when
+        the split has no state yet; for 'train' under time_importance also p, the current sampling probability of each bin.  reset: zero the
+        state after the read (the test pass: one evaluation per read).  Reads the device: not for the inside of a step."""
+        name = {"train": "time_profile", "test": "_test_profile"}[split]
+        t = getattr(self, name)
+        if t is None:
+            return None
+        p = None
+        if split == "train" and self.time_importance:
+            p = ops.u_importance(t, torch.zeros((1,), device=t.device), self.importance_warmup, self.importance_floor, want_table=True)[2].cpu().numpy()
+        rows = profile_rows(t.cpu().numpy(), p)
+        if reset:
+            t.zero_()
+        return rows
+
     def _prepare(self, net, x, u, eps, i_times=None, cond_w=None):
         """Everything ahead of the student's forward pass: draws, q_sample and (distillation) the teacher's targets.
         -> (module, guide, student cond_w, z_t, logsnr, x_target, eps_target, loss_type)"""
@@ -484,19 +588,33 @@ class GaussianDiffusion:
     def training_losses(self, *, net, x, u=None, eps=None, i_times=None, cond_w=None):
         """Reference call shape (:81).  Differentiable through torch.autograd when grad mode is on."""
         assert x.dtype in [torch.float32, torch.float64]
+        if self.loss_profile:                                     # the same draws in the same order (`_prepare`: eps, then u), made here to keep u
+            if eps is None:
+                eps = self.rng.normal(x.shape, x.device)
+            if u is None:
+                u = self.draw_u(x.shape[0], x.device)
+            u = ops.aligned(u.float())
         module, guide, w, z_t, logsnr, x_t, eps_t, loss_type = self._prepare(net, x, u, eps, i_times, cond_w)
         v = module(z_t, logsnr, guide=guide, cond_w=w)
         grad = torch.is_grad_enabled() and v.requires_grad
+
+        def note(loss, x_mse):
+            """loss_profile: the batch into the test profile at decay 1 (plain sums; x_mse where the branch has it)."""
+            if self.loss_profile:
+                ops.loss_profile(u, loss.detach(), x_mse, self.profile_state("test", u.device), 1.0)
         if self.loss_weight_type in ops.X_LOSS_WEIGHTS:           # 'snr_plus1' / 'min_snr': w(logsnr) x_mse, no eps anywhere
             if grad:
                 loss, x_mse = _XLossW.apply(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, self.mean_type)
             else:
                 loss, x_mse, _ = ops.x_loss_w(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, mean_type=self.mean_type)
+            note(loss, x_mse)
             return {"loss": loss, "x_mse": x_mse}
         if grad:
             loss = _VLoss.apply(v, z_t, x_t, eps_t, logsnr, loss_type, self.mean_type)
+            note(loss, None)
             return {"loss": loss}
         loss, x_mse = ops.v_loss(v, z_t, x_t, eps_t, logsnr, loss_type=loss_type, mean_type=self.mean_type)[:2]
+        note(loss, x_mse)
         # a weighting chosen by the caller also reports the unweighted x_mse: one number that compares runs under different weightings
         return {"loss": loss, "x_mse": x_mse} if self.loss_weight != "snr_trunc" else {"loss": loss}
 
@@ -504,16 +622,34 @@ class GaussianDiffusion:
                                on_grads_ready=None, join_side_before_ready=True):
         """Fused training pass used by DiffusionModel.train_step: forward, loss, dL/dv and the explicit backward
         schedule, leaving d(grad_scale * sum_b loss_b)/d(theta) in `module.flat_grads`.  No autograd graph."""
+        # the loss profile: only when this pass draws the times itself.  u0 is today's draw (same stream, same counters: eps, then u); with
+        # time_importance it goes through the profile's inverse CDF, and every image's gradient and loss take the importance weight 1 / (64 p).
+        profiled = (self.time_importance or self.loss_profile) and u is None
+        time_w = None
+        if profiled:
+            if eps is None:
+                eps = self.rng.normal(x.shape, x.device)
+            u = self.draw_u(x.shape[0], x.device)
+            if self.time_importance:
+                u, time_w = ops.u_importance(self.profile_state("train", x.device), u, self.importance_warmup, self.importance_floor)
         module, guide, w, z_t, logsnr, x_t, eps_t, loss_type = self._prepare(net, x, u, eps, i_times, cond_w)
         ctx = {}
         v = module.forward_hip(z_t, logsnr, guide, w, ctx=ctx)
         if self.loss_weight_type in ops.X_LOSS_WEIGHTS:
             loss_b, x_mse, dv = ops.x_loss_w(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, grad_scale=grad_scale, mean_type=self.mean_type)
-            module.backward_hip(ctx, dv, on_grads_ready=on_grads_ready, join_side_before_ready=join_side_before_ready)
-            return {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
-        loss_b, x_mse, eps_mse, dv = ops.v_loss(v, z_t, x_t, eps_t, logsnr, grad_scale=grad_scale, loss_type=loss_type, mean_type=self.mean_type)
+            out = {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
+        else:
+            loss_b, x_mse, eps_mse, dv = ops.v_loss(v, z_t, x_t, eps_t, logsnr, grad_scale=grad_scale, loss_type=loss_type, mean_type=self.mean_type)
+            out = {"loss": loss_b, "x_mse": x_mse, "eps_mse": eps_mse, "logsnr": logsnr}
+        if time_w is not None:
+            dv = ops.scale_rows(dv.view(dv.shape[0], -1), time_w).view_as(dv)
         module.backward_hip(ctx, dv, on_grads_ready=on_grads_ready, join_side_before_ready=join_side_before_ready)
-        return {"loss": loss_b, "x_mse": x_mse, "eps_mse": eps_mse, "logsnr": logsnr}
+        if profiled:                    # the UNWEIGHTED loss enters the profile: p must follow the loss itself, not the loss it reweighted
+            ops.loss_profile(u, loss_b, x_mse, self.profile_state("train", u.device), self.importance_decay)
+            out["u"] = u
+            if time_w is not None:      # loss: the unbiased estimate of the uniform-time loss
+                out.update(loss=time_w * loss_b, loss_b=loss_b, time_w=time_w)
+        return out
 
     # ---- likelihood: the continuous-time variational bound (an extension, no reference call site) ------------------------------------------
     @torch.no_grad()

@@ -144,6 +144,27 @@ class EpochLog:
         return out
 
 
+LOSS_PROFILE_FILE = "loss_profile.csv"
+LOSS_PROFILE_COLUMNS = ("epoch", "split", "bin", "u_lo", "u_hi", "logsnr_hi", "logsnr_lo", "weight", "loss_mean", "loss_rms", "x_mse_mean", "p")
+
+
+def append_loss_profile(logdir, epoch, split, rows):
+    """Append one split's loss profile (`GaussianDiffusion.profile`'s dict of [64] arrays) to <logdir>/loss_profile.csv, one row per bin under
+    LOSS_PROFILE_COLUMNS (the header when the file is new).  A mean of an empty bin (weight 0) and `p` without time_importance are left empty."""
+    path = Path(logdir) / LOSS_PROFILE_FILE
+    path.parent.mkdir(parents=True, exist_ok=True)
+    new = not path.exists()
+    num = lambda v: "" if v is None or not np.isfinite(v) else f"{float(v):.9g}"
+    with open(path, "a") as f:
+        if new:
+            f.write(",".join(LOSS_PROFILE_COLUMNS) + "\n")
+        for k in range(len(rows["weight"])):
+            cells = [str(int(epoch)), split, str(k)] + [num(rows[c][k]) for c in LOSS_PROFILE_COLUMNS[3:-1]]
+            cells.append("" if rows.get("p") is None else num(rows["p"][k]))
+            f.write(",".join(cells) + "\n")
+    return path
+
+
 class Session:
     """One run of the driver: model, data, feature extractors, flags."""
 
@@ -174,11 +195,22 @@ class Session:
                     log.add("test", self.model.loss(*last)[1])
             else:
                 last = next(self._batches(self.test_ds))
+            if getattr(self.model, "loss_profile", 0):                  # an extension: where along the noise axis the loss sits
+                self.write_loss_profile(epoch)
             started = time.time()
             self.model.evaluate(self.writer if self.lead else None, last[0], last[1], epoch)
             log.set("dt/eval", time.time() - started)
         log.set("num_vars", common.count_vars(self.model))
         return last
+
+    def write_loss_profile(self, epoch):
+        """After the test pass: the test split's profile of this evaluation (64 rows; the state is reset on read) and, once it holds any
+        weight, the train split's running one, appended to <logdir>/loss_profile.csv by rank 0 (its own ranks' samples)."""
+        diffusion = self.model.diffusion
+        for split in ("test", "train"):
+            rows = diffusion.profile(split, reset=split == "test")
+            if self.lead and rows is not None and (split == "test" or rows["weight"].sum() > 0):
+                append_loss_profile(self.G.logdir, epoch, split, rows)
 
     def checkpoint(self, log, last_batch, epoch=0):
         if self.lead:

@@ -984,6 +984,60 @@ def u_stratified(u0, B):
     return u
 
 
+PROFILE_BINS = 64               # GMK_PROFILE_BINS of include/gmk.h: bins of equal width in u, one per lane of a wavefront
+
+
+def _profile_state(state):
+    _f32(state, "state")
+    if tuple(state.shape) != (5, PROFILE_BINS):
+        raise ValueError(f"state: shape {tuple(state.shape)}, expected (5, {PROFILE_BINS}) (W, then S1 and S2 of two value channels)")
+    return state
+
+
+def loss_profile(u, v0, v1, state, decay):
+    """Add one batch to a per-time loss profile (gmk_loss_profile; an extension), in place: sample b falls into bin min(int(64 u[b]), 63) and is
+    skipped when u[b] is outside [0, 1) or a value is not finite; a bin that received n samples takes W = decay W + n, S1 = decay S1 + sum v,
+    S2 = decay S2 + sum v^2 per value channel (v0 -> rows 1, 2; v1 -> rows 3, 4, untouched when v1 is None), every other bin keeps its bits.
+    u, v0, v1: fp32 [B], 1 <= B <= 2^24; state: fp32 [5, 64]; 0 < decay <= 1.  Sequential fp32 sums in ascending b, no atomics: the same
+    inputs give the same bits.  -> state"""
+    _profile_state(state)
+    _f32(u, "u"); _f32(v0, "v0")
+    B = u.numel()
+    if not 1 <= B <= 1 << 24:
+        raise ValueError(f"loss_profile: {B} samples, 1 <= B <= 2^24")
+    for t, nm in ((u, "u"), (v0, "v0"), (v1, "v1")):
+        if t is not None and (_f32(t, nm).numel() != B or t.device != state.device):
+            raise ValueError(f"loss_profile: {nm} of {t.numel()} values on {t.device}, u has {B} and the state is on {state.device}")
+    decay = float(decay)
+    if not 0.0 < decay <= 1.0:
+        raise ValueError(f"loss_profile: decay = {decay} outside (0, 1]")
+    check(lib.gmk_loss_profile(_p(u), _p(v0), _p(v1), B, decay, _p(state), _s()), "loss_profile")
+    return state
+
+
+def u_importance(state, u0, warm, floor, want_table=False):
+    """Loss-aware times (gmk_u_importance; Nichol & Dhariwal 2021, section 3.3): the uniform draws u0 (fp32 [B] in [0, 1)) through the inverse
+    CDF of p_k = (1 - floor) r_k / sum r + floor / 64, r_k = sqrt(S2_k / W_k) of the profile `state`'s channel 0, and the importance weights
+    w = C / (64 p_k) of the bins they land in.  While a bin holds fewer than `warm` samples (or the profile has no finite positive mass) the
+    table is uniform: u == u0 bit for bit and w == 1.  warm >= 0, 0 < floor <= 1.
+    -> (u, w), fp32 [B]; with want_table also the table's (p, w), fp32 [64] each."""
+    _profile_state(state)
+    _f32(u0, "u0")
+    B = u0.numel()
+    if u0.dim() != 1 or not 1 <= B <= 1 << 24 or u0.device != state.device:
+        raise ValueError(f"u_importance: u0 of shape {tuple(u0.shape)} on {u0.device}: a vector of 1 <= B <= 2^24 draws on the state's device")
+    warm, floor = float(warm), float(floor)
+    if not warm >= 0.0:
+        raise ValueError(f"u_importance: warm = {warm}, need a sample count >= 0")
+    if not 0.0 < floor <= 1.0:
+        raise ValueError(f"u_importance: floor = {floor} outside (0, 1]")
+    u, w = torch.empty_like(u0), torch.empty_like(u0)
+    p_t = torch.empty((PROFILE_BINS,), device=u0.device, dtype=torch.float32) if want_table else None
+    w_t = torch.empty_like(p_t) if want_table else None
+    check(lib.gmk_u_importance(_p(state), _p(u0), _p(u), _p(w), B, warm, floor, _p(p_t), _p(w_t), _s()), "u_importance")
+    return (u, w, p_t, w_t) if want_table else (u, w)
+
+
 def _sampler_check(v, z, same_shape, cond_w):
     """The input checks `sampler_step`, `dpm_solver_step` and `dyn_threshold` share.  same_shape: (tensor or None, name) pairs of z's shape.
     -> (B, n)"""

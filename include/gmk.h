@@ -346,6 +346,30 @@ int gmk_x_loss_w(const float* v, const float* z, const float* x, const float* lo
  * of two and u0 a multiple of 2^-24 (gmk_rng_uniform's values) all of it is exact and every [k / B, (k + 1) / B) holds exactly one u; u lies in
  * [0, 1) for every B.  u0: one value in [0, 1); u: fp32 [B], 1 <= B <= 2^24. */
 int gmk_u_stratified(const float* u0, float* u, int B, void* stream);
+/* the per-log-SNR loss profile and the loss-aware time sampler (Nichol & Dhariwal 2021, "Improved DDPM", section 3.3); extensions.
+ * GMK_PROFILE_BINS bins of equal width in the time variable u in [0, 1) (one per lane of a wavefront; equal mass under uniform draws).
+ * state: fp32 [5][64] - row 0 W, the decayed sample count; rows 1, 2 S1, S2, the decayed sum and sum of squares of value channel 0; rows 3, 4
+ * the same of value channel 1.  Single correctly rounded fp32 operations in a stated order, as gmk_u_stratified: numpy float32 restates both
+ * entries bit for bit.
+ * gmk_loss_profile: sample b belongs to bin k = min((int)fmul(u[b], 64), 63); it is skipped entirely when u[b] is not in [0, 1) or v0[b] (or
+ * v1[b], when given) is not finite.  Per bin, over its samples in ascending b: n = their count, a_c = the sequential fadd of the values (from
+ * 0), q_c = the sequential fadd(q, fmul(v, v)).  A bin with n > 0 takes W = fadd(fmul(decay, W), n), S1_c = fadd(fmul(decay, S1_c), a_c),
+ * S2_c = fadd(fmul(decay, S2_c), q_c): a per-bin window over the bin's own samples (decay = 1: plain sums).  A bin with n = 0 keeps its five
+ * words' bits; rows 3 and 4 keep theirs when v1 is NULL.  No atomics: a pure function of the inputs.  One workgroup.
+ * u, v0, v1: fp32 [B], 1 <= B <= 2^24; 0 < decay <= 1. */
+#define GMK_PROFILE_BINS 64
+int gmk_loss_profile(const float* u, const float* v0, const float* v1, int B, float decay, float* state, void* stream);
+/* gmk_u_importance: the inverse-CDF draw from the profile and its importance weight.  The table, in bin order:
+ *   ready = every W_k >= warm;  r_k = fsqrt(fdiv(S2_k, W_k)) on channel 0;  R = the sequential fadd of r_k (from 0)
+ *   p_k = fadd(fmul(fdiv(r_k, R), fsub(1, floor)), fdiv(floor, 64)) when ready and R is finite and > 0, else 2^-6
+ *   c_0 = 0, c_{k+1} = fadd(c_k, p_k), C = c_64;  w_k = fdiv(C, fmul(64, p_k))
+ * per draw: t = fmul(u0[b], C), k = the largest index in 0..63 with c_k <= t, f = min(fdiv(fsub(t, c_k), p_k), 1 - 2^-24),
+ *   u[b] = min(fmul(fadd((float)k, f), 2^-6), nextafterf((k + 1) 2^-6, 0)),  w[b] = w_k
+ * - the last min keeps u inside bin k and below 1, so w[b] == w_out[floor(64 u[b])].  With p_k = 2^-6 every operation is exact for every fp32
+ * u0 in [0, 1): u == u0 bit for bit and w == 1.  E[w g(u)] over uniform u0 is the integral of g.
+ * u0, u, w: fp32 [B], u0 in [0, 1), 1 <= B <= 2^24; warm >= 0; 0 < floor <= 1; p_out, w_out: NULL or fp32 [64], the table's p_k and w_k. */
+int gmk_u_importance(const float* state, const float* u0, float* u, float* w, int B, float warm, float floor, float* p_out, float* w_out,
+                     void* stream);
 /* one reverse step on a batch (gaussian_diffusion.py:189-243,174-187,292):
  *   v: conditional net output; v_uncond/cond_w: NULL or the unconditional output + per-sample guidance weight;
  *   noise: NULL -> DDIM update, else ancestral ('noisy') update with that noise; is_last: the i == 0 select.
