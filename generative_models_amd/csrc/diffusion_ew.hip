@@ -9,7 +9,7 @@
 // gmk_dpm_solver_step_dt; Saharia et al. 2022).  gmk_grad_norm / gmk_adam_step_ctl (global-norm clipping by
 // torch.nn.utils.clip_grad_norm_'s rule, and the non-finite guard GradScaler.step gives the reference at diffusion_model.py:71) are extensions.
 // gmk_x_loss_w (the SNR+1 weighting of Salimans & Ho 2022 and Min-SNR-gamma, Hang et al. 2023, as w(logsnr) x_mse) and gmk_u_stratified
-// (low-discrepancy training times, Kingma et al. 2021) are extensions too.
+// (low-discrepancy training times, Kingma et al. 2021) are extensions too.  gmk_slerp (spherical interpolation of latent codes) is an extension as well.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -1033,6 +1033,94 @@ __global__ __launch_bounds__(256) void pf_ode_step_kernel(const float* __restric
     }
 }
 
+// ---- spherical interpolation of latent codes (gmk_slerp; Shoemake 1985, as the DDIM paper's section 5.3 / App. D.5 uses it on x_T); an
+// extension, no reference call site.  Per image b, over its n values, in fp32:
+//   dot = sum a b, na = sum a^2, nb = sum b^2;  c = clamp(dot / sqrt(na nb), -1, 1), theta = acosf(c), s = sinf(theta)
+//   out[k] = w_a a + w_b b,  w_a = sinf((1 - t_k) theta) / s,  w_b = sinf(t_k theta) / s          for every k < K
+//   where s < 1e-6 or c is not finite (parallel, antipodal and all-zero rows): w_a = 1 - t_k, w_b = t_k, the lerp - no division, so finite
+//   inputs never give a NaN.
+// t_k = 0 gives w_a = s / s = 1 and w_b = sinf(0) / s = 0, hence a's values exactly (t_k = 1: b's); the division is IEEE's and the library builds
+// with -ffp-contract=off, so nothing here is fused or reordered.  The clamp is written with comparisons: a NaN stays a NaN (fminf / fmaxf would
+// drop it) and reaches cos_out as one.
+// One workgroup of 256 threads per image, thread t takes elements 4t .. 4t + 3 of every 1024 (16-byte loads and stores, n % 4 == 0).  Each thread
+// adds its products in ascending order with fmaf, then block_sum: a fixed order and no floating-point atomics, so the same call gives the same
+// bits.  GROUPS > 0: the image has at most 1024 GROUPS values and stays in registers between the reduction and the K output passes (4 GROUPS
+// values of a and of b per thread: 96 of the kernel's 114 registers at the capacity kSlerpKeep = 1024 x 12, four waves per SIMD, no scratch), so
+// a and b come from HBM once.  GROUPS == 0: any n, a and b are read again for every k.  (A second resident instantiation with GROUPS = 4 for
+// n <= 4096, 74 registers, measured 37.7 - 37.9 us against this one's 38.6 at B = 2048, n = 3072, K = 8: not kept.)
+constexpr int kSlerpKeep = 12288;    // kDynKeys, kXLossKeep: covers 3 x 64 x 64
+
+template <int GROUPS>
+__global__ __launch_bounds__(256) void slerp_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ t,
+                                                   float* __restrict__ out, float* __restrict__ cos_out, int B, int64_t n, int K) {
+    __shared__ float red[4];
+    const int img = blockIdx.x;
+    const int64_t base = (int64_t)img * n;
+    const int64_t i0 = (int64_t)threadIdx.x * 4;
+    constexpr int G = GROUPS > 0 ? GROUPS : 1;
+    float ra[G][4], rb[G][4];
+    float dot = 0.f, na = 0.f, nb = 0.f;
+    auto sums = [&](const float (&av)[4], const float (&bv)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            dot = fmaf(av[j], bv[j], dot);
+            na = fmaf(av[j], av[j], na);
+            nb = fmaf(bv[j], bv[j], nb);
+        }
+    };
+    if constexpr (GROUPS > 0) {
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g) {
+            const int64_t i = i0 + (int64_t)g * 1024;
+            if (i < n) {
+                load4(a + base + i, ra[g]);
+                load4(b + base + i, rb[g]);
+                sums(ra[g], rb[g]);
+            }
+        }
+    } else {
+        for (int64_t i = i0; i < n; i += 1024) {
+            load4(a + base + i, ra[0]);
+            load4(b + base + i, rb[0]);
+            sums(ra[0], rb[0]);
+        }
+    }
+    dot = block_sum(dot, red);
+    na = block_sum(na, red);
+    nb = block_sum(nb, red);
+    const float q = dot / sqrtf(na * nb);
+    const float c = q < -1.0f ? -1.0f : (q > 1.0f ? 1.0f : q);
+    const float theta = acosf(c);
+    const float s = sinf(theta);
+    const bool lerp = !(isfinite(c) && s >= 1e-6f);
+    if (threadIdx.x == 0 && cos_out) cos_out[img] = c;
+    for (int k = 0; k < K; ++k) {
+        const float tk = t[k];
+        const float wa = lerp ? 1.0f - tk : sinf((1.0f - tk) * theta) / s;
+        const float wb = lerp ? tk : sinf(tk * theta) / s;
+        float* __restrict__ o = out + ((int64_t)k * B + img) * n;
+        auto mix = [&](const float (&av)[4], const float (&bv)[4], int64_t i) {
+            float ov[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ov[j] = wa * av[j] + wb * bv[j];
+            store4(o + i, ov);
+        };
+        if constexpr (GROUPS > 0) {
+#pragma unroll
+            for (int g = 0; g < GROUPS; ++g) {
+                const int64_t i = i0 + (int64_t)g * 1024;
+                if (i < n) mix(ra[g], rb[g], i);
+            }
+        } else {
+            for (int64_t i = i0; i < n; i += 1024) {
+                load4(a + base + i, ra[0]);
+                load4(b + base + i, rb[0]);
+                mix(ra[0], rb[0], i);
+            }
+        }
+    }
+}
+
 // blocks per row of a (gx, B) grid whose blocks take `per_block` elements per pass: enough for the row, at most 64
 int row_grid(int64_t n, int per_block) {
     const int64_t g = (n + per_block - 1) / per_block;
@@ -1414,4 +1502,16 @@ extern "C" int gmk_pf_ode_step(const float* out, float* z, const float* r, const
     pf_ode_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(out, z, r, g, acc, prior, x_out, logsnr_i, logsnr_j, update, div_a,
                                                                      div_b, prior_c, n, mean_type);
     return gmk_check_launch("gmk_pf_ode_step");
+}
+
+extern "C" int gmk_slerp(const float* a, const float* b, const float* t, float* out, float* cos_out, int B, int64_t n, int K, void* stream) {
+    GMK_REQUIRE(a && b && t && out, "gmk_slerp: null pointer");
+    GMK_REQUIRE(B >= 1 && K >= 1 && n >= 4 && n % 4 == 0, "gmk_slerp: bad shape B=%d n=%lld K=%d (B, K >= 1, n >= 4, n %% 4 == 0 required)", B,
+                (long long)n, K);
+    GMK_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+                "gmk_slerp: a, b and out must be 16-byte aligned");
+    hipStream_t st = gmk_stream(stream);
+    if (n <= kSlerpKeep) slerp_kernel<kSlerpKeep / 1024><<<B, 256, 0, st>>>(a, b, t, out, cos_out, B, n, K);
+    else slerp_kernel<0><<<B, 256, 0, st>>>(a, b, t, out, cos_out, B, n, K);
+    return gmk_check_launch("gmk_slerp");
 }

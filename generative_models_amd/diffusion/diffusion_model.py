@@ -23,7 +23,7 @@ import os
 import torch
 
 from .. import checkpoint, common, ops, parallel
-from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check, loss_weight_check, time_importance_check
+from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check, edit_start, loss_weight_check, time_importance_check
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -62,6 +62,10 @@ def make_plugin(GMBase, AttrDict):
                                        # <model>/test/ode_nlogp) of the sampling net on N steps; not in the reference, off by default
         DG.inpaint_eval = 0            # r >= 1: evaluate() also fills in the bottom half of the first 25 test images (RePaint, resample = r) as
                                        # last_eval['inpaint'] / grid 'inpaint'; not in the reference, off by default
+        DG.edit_eval = 0.0             # strength in (0, 1]: evaluate() also edits the first 25 test images (SDEdit: noised up to that share of the chain and
+                                       # denoised from there) as last_eval['edit'] / frames 'edit'; not in the reference, off by default
+        DG.interp_eval = 0             # K >= 2: evaluate() also interpolates test images 0-4 into 5-9 through their latent codes in K frames (DDIM
+                                       # inversion, slerp, decode) as last_eval['interp'] / frames 'interp'; not in the reference, off by default
         DG.dyn_threshold = 0.0         # p in (0, 1]: sample() / evaluate() / inpaint() clamp each image's x-hat to its own p-th percentile of |x| and rescale
                                        # (dynamic thresholding, Saharia et al. 2022; e.g. 0.995) instead of the clip at 1; not in the reference, off by default
         DG.grad_clip = 0.0             # c > 0: clip the global gradient norm to c inside the optimiser step (torch.nn.utils.clip_grad_norm_'s rule) and
@@ -120,6 +124,18 @@ def make_plugin(GMBase, AttrDict):
             self.inpaint_eval = int(get("inpaint_eval"))
             if self.inpaint_eval < 0:
                 raise ValueError(f"inpaint_eval = {self.inpaint_eval}: 0 (off) or the resample count r >= 1")
+            try:
+                self.edit_eval = float(get("edit_eval"))
+            except (TypeError, ValueError):
+                raise ValueError(f"edit_eval = {get('edit_eval')!r}: 0 (off) or the strength in (0, 1]") from None
+            if not 0.0 <= self.edit_eval <= 1.0:
+                raise ValueError(f"edit_eval = {self.edit_eval}: 0 (off) or the strength in (0, 1]")
+            self.interp_eval = int(get("interp_eval"))
+            if self.interp_eval < 0 or self.interp_eval == 1 or self.interp_eval != float(get("interp_eval")):
+                raise ValueError(f"interp_eval = {get('interp_eval')}: 0 (off) or the number of frames K >= 2")
+            if self.interp_eval > 0 and self.teacher_net is not None:
+                raise ValueError("interp_eval > 0 with teacher_path: a distilled student is conditioned on cond_w; its probability-flow ODE has "
+                                 "no density")
             self.binarize = int(get("binarize"))
             dyn_threshold = dyn_threshold_check(get("dyn_threshold"))
             loss_weight, loss_gamma, time_sampler = loss_weight_check(get("loss_weight"), get("loss_gamma"), get("time_sampler"),
@@ -428,7 +444,26 @@ def make_plugin(GMBase, AttrDict):
                 cond_w = 0.5 if y is not None else None
                 return self.diffusion.inpaint(net=net, x0=x, mask=mask, init_x=noise, cond_w=cond_w, resample=resample, seed=seed)[0][-1]
 
+        # -- editing and interpolation (extensions): SDEdit and latent-code interpolation on the net sample() uses
+        def edit(self, x, strength, y=None, mask=None, seed=0):
+            """Edit x ([B, C, S, S] in [-1, 1]) with `GaussianDiffusion.edit`: noised up to step k = edit_start(strength, timesteps) of the
+            chain (strength in (0, 1]; 1 keeps nothing of x but what `mask` keeps) and denoised from there.  y: labels, as in sample() (then
+            guided with cond_w = 0.5); mask (broadcastable to x, {0, 1}): pixels with 1 come back as x's own.  The noise comes from
+            PhiloxStream(seed).  -> [B, C, S, S]"""
+            with torch.no_grad():
+                net = partial(self._sampling_net(), guide=y)
+                cond_w = 0.5 if y is not None else None
+                k = edit_start(strength, self.diffusion.num_steps)
+                return self.diffusion.edit(net=net, x=x, start=k, cond_w=cond_w, mask=mask, seed=seed)[0][-1]
+
+        def interpolate(self, xa, xb, frames=9, y=None, steps=None):
+            """`frames` images from xa to xb ([B, C, S, S] each) through their latent codes (`GaussianDiffusion.interpolate`) on `steps` ODE
+            steps (default `timesteps`); y: labels of the pairs (the conditional ODE), None: unconditional (guide -1).  -> [frames, B, C, S, S]"""
+            return self.diffusion.interpolate(net=partial(self._sampling_net(), guide=self._ode_guide(xa, y)), xa=xa, xb=xb, frames=frames,
+                                              num_steps=steps or self.diffusion.num_steps)
+
         INPAINT_EVAL_SEED = 104723                  # evaluate()'s inpainting: initial noise from PhiloxStream(this), known-region noise from this + 1
+        EDIT_EVAL_SEED = 104743                     # evaluate()'s editing: the forward noise (and nothing else) from PhiloxStream(this)
 
         # -- evaluate (:89-111): 25 class-conditional samples without guidance, trajectories as uint8
         def evaluate(self, writer, x, y, epoch):
@@ -468,6 +503,20 @@ def make_plugin(GMBase, AttrDict):
                     writer.write_frames("inpaint", z, epoch, crop=crop)
                 elif writer is not None and grids and k == 25:
                     common.write_grid(writer, "inpaint", self.last_eval["inpaint"], epoch)
+            if self.edit_eval > 0:                                    # an extension, as above: its noise from PhiloxStream(EDIT_EVAL_SEED)
+                k = min(25, x.shape[0])
+                z = self.diffusion.edit(net=partial(self._sampling_net(), guide=None if y is None else y[:k]), x=x[:k].float(),
+                                        start=edit_start(self.edit_eval, self.diffusion.num_steps), seed=self.EDIT_EVAL_SEED)[0][-1]
+                self.last_eval["edit"] = proc(z)
+                if pictures:
+                    writer.write_frames("edit", z, epoch, crop=crop)
+                elif writer is not None and grids and k == 25:
+                    common.write_grid(writer, "edit", self.last_eval["edit"], epoch)
+            if self.interp_eval > 0 and x.shape[0] >= 10:             # an extension: deterministic (no draw), unconditional
+                z = self.interpolate(x[0:5].float(), x[5:10].float(), frames=self.interp_eval)
+                self.last_eval["interp"] = proc(z)
+                if pictures:
+                    writer.write_frames("interp", z, epoch, crop=crop)
             random.randint(0, 2 ** 32)                                # :111 keeps the host RNG consumption
 
     return DiffusionModel

@@ -18,6 +18,8 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
                                         gmk_x_loss_w; `time_sampler='stratified'` through gmk_u_stratified (extensions, no reference call site)
 * loss profile (`loss_profile=`, `time_importance=`)  gmk_loss_profile keeps the per-time profile of the loss on the device; gmk_u_importance draws
                                         the training times from it (Nichol & Dhariwal 2021, section 3.3) (extensions, no reference call site)
+* editing and interpolation (`edit`, `interpolate`)  sampler chains that start part-way (`start=`), gmk_q_sample_logsnr for the forward noising, gmk_slerp
+                                        between two latent codes (SDEdit, Meng et al. 2022; DDIM's interpolation, Song et al. 2021; extensions, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -61,13 +63,40 @@ def sampler_grid(num_steps):
 DpmCoef = namedtuple("DpmCoef", "i lt ls h coef_z coef_x coef_prev")
 
 
-def dpm_solver_coefs(num_steps):
+def sampler_start(start, num_steps):
+    """The `start` of a sampler chain that begins part-way: None is T = num_steps (the prior end, the whole chain), else an integer k with
+    1 <= k <= T: the chain runs the iterations i = k-1 ... 0 from z at logsnr(k / T).  -> k, or ValueError (bools and floats included)."""
+    T = int(num_steps)
+    if start is None:
+        return T
+    if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or not 1 <= start <= T:
+        raise ValueError(f"start = {start!r}: None (the whole chain) or an integer in [1, num_steps = {T}]")
+    return int(start)
+
+
+def edit_start(strength, num_steps):
+    """The `start` of `GaussianDiffusion.edit` for an SDEdit strength in (0, 1] (Meng et al. 2022: the share of the chain that is re-run, 1 the
+    whole of it): k = min(T, max(1, floor(strength T + 1/2))).  -> k, or ValueError (NaN included)."""
+    try:
+        s = float(strength)
+    except (TypeError, ValueError):
+        raise ValueError(f"strength = {strength!r}: a number in (0, 1]") from None
+    if not 0.0 < s <= 1.0:
+        raise ValueError(f"strength = {s}: the share of the chain to re-run, in (0, 1]")
+    T = int(num_steps)
+    return min(T, max(1, int(math.floor(s * T + 0.5))))
+
+
+def dpm_solver_coefs(num_steps, start=None):
     """Per-step coefficients of sampler='dpmpp_2m' (DPM-Solver++(2M), Lu et al. 2022, Algorithm 2, data prediction; an extension with no
     reference call site), one row per loop iteration i = T-1 ... 0 on DDIM's time grid.  lt / ls are the fp32 log-SNRs the DDIM path uses;
     with lambda = logsnr / 2, alpha = sqrt(sigmoid(logsnr)), sigma = sqrt(sigmoid(-logsnr)) and h = lambda_s - lambda_t:
       coef_z = sigma_s / sigma_t, coef_x = -alpha_s expm1(-h), coef_prev = 1 / (2 r), r = h_prev / h,
     so that z_s = coef_z z_t + coef_x ((1 + coef_prev) x_hat - coef_prev x_hat_prev).  coef_prev is 0 on the first step (first order: DDIM's
-    update) and on the last (i == 0 returns x_hat itself, gaussian_diffusion.py:292), so T <= 2 is DDIM.  All in float64 from the fp32 log-SNRs."""
+    update) and on the last (i == 0 returns x_hat itself, gaussian_diffusion.py:292), so T <= 2 is DDIM.  All in float64 from the fp32 log-SNRs.
+    start = k (`sampler_start`) keeps the rows i = k-1 ... 0; the first of them has no history either, so its coef_prev is 0, and every later
+    row is the full list's."""
+    k_start = sampler_start(start, num_steps)
     sigma = lambda l: math.sqrt(1.0 / (1.0 + math.exp(l)))
     alpha = lambda l: math.sqrt(1.0 / (1.0 + math.exp(-l)))
     rows, h_prev = [], None
@@ -78,6 +107,8 @@ def dpm_solver_coefs(num_steps):
         k = 0.0 if (not h_prev or i == 0) else h / (2.0 * h_prev)
         rows.append(DpmCoef(i, lt, ls, h, sigma(ls) / sigma(lt), -alpha(ls) * math.expm1(-h), k))
         h_prev = h
+    rows = rows[len(rows) - k_start:]
+    rows[0] = rows[0]._replace(coef_prev=0.0)
     return rows
 
 
@@ -241,14 +272,17 @@ SamplerStep = namedtuple("SamplerStep", "i lt ls is_last passes dpm inp")
 InpaintState = namedtuple("InpaintState", "x0 mask rng resample B_total moffs")
 
 
-def sampler_plan(num_steps, sampler="ddim", resample=None):
+def sampler_plan(num_steps, sampler="ddim", resample=None, start=None):
     """One row per sampler iteration i = T-1 ... 0: the grid's (i, lt, ls), is_last, the network evaluations of the step (`resample`: the
     inpainting loop's, None outside it) and the step's DpmCoef (sampler 'dpmpp_2m') / InpaintCoef (inpainting) rows, else None.  The loop
-    reserves its Philox counters and every chunk spends them by walking the same plan."""
-    dpm = dpm_solver_coefs(num_steps) if sampler == "dpmpp_2m" else [None] * num_steps
-    inp = inpaint_coefs(num_steps) if resample is not None else [None] * num_steps
+    reserves its Philox counters and every chunk spends them by walking the same plan.  start = k (`sampler_start`): a chain that begins
+    part-way, from z at plan[0].lt = logsnr(k / T) - the rows i = k-1 ... 0 of the same grid (None: all T of them)."""
+    k = sampler_start(start, num_steps)
+    skip = num_steps - k
+    dpm = dpm_solver_coefs(num_steps, start) if sampler == "dpmpp_2m" else [None] * k
+    inp = inpaint_coefs(num_steps)[skip:] if resample is not None else [None] * k
     return [SamplerStep(i, lt, ls, i == 0, 1 if resample is None else inpaint_passes(i, resample), d, c)
-            for (i, lt, ls), d, c in zip(sampler_grid(num_steps), dpm, inp)]
+            for (i, lt, ls), d, c in zip(sampler_grid(num_steps)[skip:], dpm, inp)]
 
 
 # the variational bound's log-SNR range: the schedule's truncation (diffusion_utils.py:199-200)
@@ -791,16 +825,18 @@ class GaussianDiffusion:
 
     # ---- sampling ----------------------------------------------------------------------------------------
     @torch.no_grad()
-    def sample(self, *, net, init_x, cond_w=None, record=True, noises=None, net_cond_w=None):
+    def sample(self, *, net, init_x, cond_w=None, record=True, noises=None, net_cond_w=None, start=None):
         """:245-296.  Returns (all_zs, all_xs, all_eps) stacked [T, B, C, H, W] like the reference when `record`;
         with record=False only the final z is produced and returned as a 1-tuple-compatible triple
         (z[None], None, None) — the 3*T*B*C*H*W*4-byte trajectory is the dominant cost at large T*B otherwise.
-        `noises` ([T, ...], indexed by step i) / `net_cond_w` inject the random draws (tests)."""
-        return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, noises=noises, net_cond_w=net_cond_w)
+        `noises` ([T, ...], indexed by step i) / `net_cond_w` inject the random draws (tests).
+        start = k (an extension; `sampler_start`): the chain begins part-way - init_x is z at logsnr(k / T), the iterations i = k-1 ... 0 run
+        and a recorded trajectory has k rows; None is the reference's chain from the prior end."""
+        return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, noises=noises, net_cond_w=net_cond_w, start=start)
 
     # ---- inpainting (RePaint, Lugmayr et al. 2022, Algorithm 1; an extension, no reference call site) -------------------------------------
     @torch.no_grad()
-    def inpaint(self, *, net, x0, mask, init_x, cond_w=None, resample=1, seed=0, record=False):
+    def inpaint(self, *, net, x0, mask, init_x, cond_w=None, resample=1, seed=0, record=False, start=None):
         """Fill in the unknown part of x0 with this sampler: after every step t -> s the known pixels (mask 1) of z are replaced by a fresh noisy
         copy alpha_s x0 + sigma_s eps of x0 (by x0 itself at the last step), the others keep the sampler's value.  With resample = r > 1 every
         step except the last runs r network evaluations, each but the final one followed by a jump back to time t through q(z_t | z_s) (jump
@@ -808,8 +844,8 @@ class GaussianDiffusion:
         ([B, C, H, W]); x0: init_x's shape.  Samplers 'ddim', 'noisy', 'teacher_test' take any r >= 1; 'dpmpp_2m' only r = 1 (its x-hat
         history has no meaning across a jump back).  `net` / `cond_w` (guidance) as in `sample`, and so is the noise of 'noisy' (one draw from
         self.rng per network evaluation).  The known-region noise comes from a PhiloxStream(seed) of its own, advanced by 2 B n values per
-        merge, so calls with the same seed see the same numbers.  -> sample()'s triple; with `record` the (z, x_hat, eps_hat) of the last pass
-        of each step, [T, B, C, H, W] each."""
+        merge, so calls with the same seed see the same numbers.  start: as in `sample` (init_x is then z at logsnr(k / T)).  -> sample()'s
+        triple; with `record` the (z, x_hat, eps_hat) of the last pass of each step, [T, B, C, H, W] each."""
         r = resample
         if isinstance(r, bool) or int(r) != r or r < 1:
             raise ValueError(f"inpaint: resample = {resample}, need an integer >= 1")
@@ -819,14 +855,18 @@ class GaussianDiffusion:
         shape = tuple(init_x.shape)
         if tuple(x0.shape) != shape:
             raise ValueError(f"inpaint: x0 shape {tuple(x0.shape)} differs from init_x shape {shape}")
+        m = self._inpaint_known(mask, shape, init_x.device)
+        inp = InpaintState(ops.aligned(x0.to(init_x.device).float()), m, PhiloxStream(seed), r, shape[0], [])
+        return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, inp=inp, start=start)
+
+    def _inpaint_known(self, mask, shape, device):
+        """The shape rules of the inpainting loop ([B, ...], a multiple of 4 values per image), then the mask -> uint8 [B, n] (`_inpaint_mask`)."""
         if len(shape) < 2 or 0 in shape:
             raise ValueError(f"inpaint: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
         n1 = math.prod(shape[1:])
         if n1 % 4:
             raise ValueError(f"inpaint: {n1} values per image, a multiple of 4 is required")
-        m = self._inpaint_mask(mask, shape, init_x.device)
-        inp = InpaintState(ops.aligned(x0.to(init_x.device).float()), m, PhiloxStream(seed), r, shape[0], [])
-        return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, inp=inp)
+        return self._inpaint_mask(mask, shape, device)
 
     @staticmethod
     def _inpaint_mask(mask, shape, device):
@@ -845,8 +885,61 @@ class GaussianDiffusion:
         m = mask.to(device=device).to(torch.uint8).expand(shape).reshape(shape[0], -1)
         return ops.aligned(m.contiguous())
 
-    def _sample(self, *, net, init_x, cond_w=None, record=True, noises=None, net_cond_w=None, inp=None):
-        """The loop behind `sample` and `inpaint` (inp: None, or the whole batch's InpaintState)."""
+    # ---- editing a given image (SDEdit, Meng et al. 2022; an extension, no reference call site) ----------------------------------------------
+    @torch.no_grad()
+    def edit(self, *, net, x, start, cond_w=None, mask=None, seed=0, record=False):
+        """Noise x ([B, C, H, W]) up to the intermediate time of `start` = k (1 <= k <= T; `edit_start` turns a strength into it) and denoise
+        it from there with this sampler: z_k = alpha_k x + sigma_k eps at logsnr(k / T), then the iterations i = k-1 ... 0 of `sample`
+        (k forwards instead of T).  rng = PhiloxStream(seed); eps is its first draw (B n values: ops.rng_normal(x.shape, seed, 0)).
+        mask (optional; 1 = keep, `inpaint`'s rules): the loop also runs RePaint's merge with resample 1 against x itself, its draws following
+        eps on the same stream (merge f at counter ceil(B n / 4) + f B n / 2), so the known pixels come back as x's own values.  `net`,
+        `cond_w` (guidance) and the noise of 'noisy' (self.rng) as in `sample`; every sampler of `inpaint` at r = 1.  -> sample()'s triple;
+        with `record` k rows."""
+        k = sampler_start(start, self.num_steps)
+        if start is None:
+            raise ValueError("edit: start = None: give the step k to noise up to (edit_start(strength, num_steps))")
+        shape = tuple(x.shape)
+        dev = x.device
+        m = None if mask is None else self._inpaint_known(mask, shape, dev)
+        x = ops.aligned(x.float())
+        rng = PhiloxStream(seed)
+        eps = rng.normal(shape, dev)
+        lt_k = logsnr_schedule_cosine_host(sampler_times(k - 1, self.num_steps)[0])      # the grid's logsnr_t of iteration k-1
+        z_k = ops.q_sample_logsnr(x, eps, torch.full((shape[0],), float(lt_k), device=dev))
+        inp = None if m is None else InpaintState(x, m, rng, 1, shape[0], [])
+        return self._sample(net=net, init_x=z_k, cond_w=cond_w, record=record, inp=inp, start=k)
+
+    # ---- interpolating between two images through their latent codes (Song et al. 2021, DDIM, section 5.3; an extension) -------------------
+    INTERP_MAX_BATCH = 1024                 # images of one decode() call of `interpolate` (whole frames; one frame when B is larger)
+
+    @torch.no_grad()
+    def interpolate(self, *, net, xa, xb, frames, num_steps, return_latents=False):
+        """K = frames images from xa to xb ([B, C, H, W] each): ONE `encode` of cat([xa, xb]) (the guide repeated), the spherical
+        interpolation z_k = slerp(z_a, z_b, t_k) of the latent codes at t_k = k / (K - 1) (fp32; ops.slerp, one launch), and `decode` of the K B
+        latents in chunks of whole frames of at most INTERP_MAX_BATCH images (the guide tiled).  (2 + K) num_steps forwards per pair.
+        Deterministic, no guidance; checks as `encode` (a distilled student or a `cond_w` raises).
+        -> fp32 [K, B, C, H, W]; with return_latents also the latents, [K, B, C, H, W]."""
+        if tuple(xa.shape) != tuple(xb.shape):
+            raise ValueError(f"interpolate: xa shape {tuple(xa.shape)} differs from xb shape {tuple(xb.shape)}")
+        K = frames
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 2:
+            raise ValueError(f"interpolate: frames = {frames!r}, need an integer >= 2")
+        K = int(K)
+        module, guide, N, _, _ = self._ode_setup("interpolate", net, xa, num_steps)
+        B = xa.shape[0]
+        if math.prod(xa.shape[1:]) % 4:
+            raise ValueError(f"interpolate: {math.prod(xa.shape[1:])} values per image, a multiple of 4 is required")
+        with_guide = lambda reps: module if guide is None else partial(module, guide=guide.repeat(reps))
+        z = self.encode(net=with_guide(2), x=torch.cat([xa.float(), xb.float()]), num_steps=N)
+        t = torch.tensor([k / (K - 1) for k in range(K)], dtype=torch.float32, device=z.device)
+        lat = ops.slerp(z[:B], ops.aligned(z[B:]), t)
+        per = max(1, self.INTERP_MAX_BATCH // B)         # frames per decode
+        out = torch.cat([self.decode(net=with_guide(len(c)), z=c.reshape((-1,) + tuple(xa.shape[1:])), num_steps=N).view_as(c)
+                         for c in lat.split(per)])
+        return (out, lat) if return_latents else out
+
+    def _sample(self, *, net, init_x, cond_w=None, record=True, noises=None, net_cond_w=None, inp=None, start=None):
+        """The loop behind `sample`, `inpaint` and `edit` (inp: None, or the whole batch's InpaintState; start: `sampler_plan`'s)."""
         module, guide, kw_cond_w = _unwrap(net)
         B = init_x.shape[0]
         dev = init_x.device
@@ -879,7 +972,7 @@ class GaussianDiffusion:
             not self._graph_path(module, nb_half, init_x.shape[2], init_x.shape[3])
         K = 2 if two else 1
         cut = lambda t, a, b_: None if t is None else ops.aligned(t[a:b_])
-        plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample)
+        plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample, start)
         # Philox counter of each network evaluation's noise draw for the WHOLE batch (ancestral sampler), and (inp.moffs) of each inpainting
         # merge's known-region draws: chunks take their slice of them
         offs = []

@@ -1274,6 +1274,36 @@ def pf_ode_step(out, z, logsnr_i, logsnr_j=None, mean_type="v", r=None, g=None, 
     return z
 
 
+SLERP_KEEP = 12288              # kSlerpKeep of csrc/diffusion_ew.hip: images of up to this many values are read once, larger ones again for every t
+
+
+def slerp(a, b, t, want_cos=False):
+    """Spherical interpolation between the latent codes a and b (gmk_slerp; an extension): per image, out[k] = (sin((1 - t_k) theta) a +
+    sin(t_k theta) b) / sin(theta) with cos(theta) = a.b / (|a| |b|), the lerp (1 - t_k) a + t_k b where sin(theta) < 1e-6 or the cosine is
+    not finite.  a, b: fp32 [B, ...] of one shape with a multiple of 4 values per image; t: fp32 [K] on the device.
+    -> out, fp32 [K, B, ...]; or (out, cos) with want_cos, cos fp32 [B]."""
+    for x, nm in ((a, "a"), (b, "b"), (t, "t")):
+        if x.dtype != torch.float32:
+            raise ValueError(f"{nm}: dtype {x.dtype}, expected torch.float32")
+    shape = tuple(a.shape)
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f"a: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
+    if tuple(b.shape) != shape:
+        raise ValueError(f"b: shape {tuple(b.shape)}, expected {shape}")
+    B, n = shape[0], math.prod(shape[1:])
+    if n % 4:
+        raise ValueError(f"a: {n} values per image, a multiple of 4 is required")
+    if t.dim() != 1 or t.numel() < 1:
+        raise ValueError(f"t: shape {tuple(t.shape)}, expected (K,) with K >= 1")
+    _f32(a, "a"); _f32(b, "b"); _f32(t, "t")
+    K = t.numel()
+    out = torch.empty((K,) + tuple(a.shape), device=a.device, dtype=torch.float32)
+    cos = torch.empty((B,), device=a.device, dtype=torch.float32) if want_cos else None
+    with _Timed("slerp_kernel", 0.0, _nbytes(a, b, out), fixed=True):
+        check(lib.gmk_slerp(_p(a), _p(b), _p(t), _p(out), _p(cos), B, n, K, _s()), "slerp")
+    return (out, cos) if want_cos else out
+
+
 def logsnr_schedule(B, device, u=None, i_times=None, num_steps=1, shift=0.0, want_u=False):
     """logsnr = schedule(u - shift), u given or (i_times + 1) / num_steps.  -> logsnr (, u_shifted)"""
     if u is not None:

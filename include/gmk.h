@@ -455,6 +455,18 @@ int gmk_rng_rademacher(float* out, int64_t n, uint64_t seed, uint64_t offset, vo
 int gmk_dequantize(const float* x, float* y, float delta, int64_t n, uint64_t seed, uint64_t offset, void* stream);
 int gmk_pf_ode_step(const float* out, float* z, const float* r, const float* g, float* acc, float* prior, float* x_out, float logsnr_i,
                     float logsnr_j, int update, float div_a, float div_b, float prior_c, int mean_type, int B, int64_t n, void* stream);
+/* spherical interpolation between two batches of latent codes (Shoemake 1985; the DDIM paper's interpolation of x_T, Song et al. 2021,
+ * section 5.3); an extension, no reference call site.  a, b: B x n fp32; t: K fp32 values on the device; out: K x B x n.  Per image, in fp32:
+ *   dot = sum a b, na = sum a^2, nb = sum b^2, c = clamp(dot / sqrt(na nb), -1, 1), theta = acosf(c), s = sinf(theta)
+ *   out[k] = w_a a + w_b b with w_a = sinf((1 - t_k) theta) / s, w_b = sinf(t_k theta) / s
+ *   fallback (s < 1e-6 or c not finite: parallel, antipodal and all-zero rows): w_a = 1 - t_k, w_b = t_k - the lerp, which writes no NaN for
+ *   finite inputs.
+ * t_k = 0 gives a's values and t_k = 1 gives b's exactly on either branch (s / s = 1, sinf(0) = 0; IEEE division, nothing contracted).
+ * cos_out (optional, B floats) receives c (NaN for an all-zero row: the clamp keeps it).  One launch, one workgroup per image; the sums run in
+ * a fixed order without floating-point atomics, so the same call gives the same bits.  Images of up to 12,288 values stay in registers between
+ * the reduction and the K output passes (a and b are read once), larger ones are read again per k.  B, K >= 1, n >= 4, n % 4 == 0; a, b and
+ * out 16-byte aligned (16-byte loads and stores). */
+int gmk_slerp(const float* a, const float* b, const float* t, float* out, float* cos_out, int B, int64_t n, int K, void* stream);
 
 /* ---- self-attention core (north_star "optional self-attention block", BASELINE config 5) -------------
  * The reference SimpleUnet has no attention block: these have NO reference call site (parity unpinned; their definition is the
