@@ -10,6 +10,8 @@
 // torch.nn.utils.clip_grad_norm_'s rule, and the non-finite guard GradScaler.step gives the reference at diffusion_model.py:71) are extensions.
 // gmk_x_loss_w (the SNR+1 weighting of Salimans & Ho 2022 and Min-SNR-gamma, Hang et al. 2023, as w(logsnr) x_mse) and gmk_u_stratified
 // (low-discrepancy training times, Kingma et al. 2021) are extensions too.  gmk_slerp (spherical interpolation of latent codes) is an extension as well.
+// gmk_box_mean / gmk_box_residual / gmk_sampler_step_ns / gmk_dpm_solver_step_ns (DDNM's range-null-space projection of x-hat for box-mean
+// operators: Wang, Yu & Zhang 2023) are extensions too.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -419,9 +421,86 @@ __device__ __forceinline__ void predict_x_eps(float out, const float* __restrict
     }
 }
 
+// ---- DDNM restoration (Wang, Yu & Zhang 2023, "Zero-Shot Image Restoration Using Denoising Diffusion Null-Space Model", eq. 13-14, without
+// noise); an extension, no reference call site.  The operator A is a box mean over NCHW images: cf in {1, C} channels times an N x N spatial
+// box, k = cf N^2 members; box g = (c', i, j) holds the elements (c' cf + dc, i N + dy, j N + dx), and the low-resolution layout is
+// [B][C / cf][H / N][W / N].  A+ replicates a box's value over its members, so A A+ = I and x + A+(y - A x) projects onto {x : A x = y}.
+// i / d for i < 2^31 by one 32 x 32 -> 64-bit multiply and a shift: with s = ceil(log2 d), sh = 31 + s and M = ceil(2^sh / d) (< 2^32),
+// M d = 2^sh + e with 0 <= e < d <= 2^s, so i M / 2^sh = i / d + i e / (d 2^sh) and i e < 2^sh: the floor is floor(i / d).  The host forms (M, sh).
+struct FastDiv {
+    uint32_t M, sh;
+};
+__device__ __forceinline__ uint32_t fast_div(uint32_t i, FastDiv f) { return (uint32_t)(((uint64_t)i * f.M) >> f.sh); }
+
+struct BoxGeom {
+    uint32_t C, H, W, cf, N;
+    uint32_t HW, Hb, Wb, n_box;          // H W, H / N, W / N, (C / cf) Hb Wb
+    FastDiv by_HW, by_W, by_N;           // the update kernels' divisions, per element
+};
+
+// the box of element i (< C H W < 2^31) of an image
+__device__ __forceinline__ uint32_t box_of(uint32_t i, const BoxGeom& g) {
+    const uint32_t ch = fast_div(i, g.by_HW), rem = i - ch * g.HW;
+    const uint32_t y = fast_div(rem, g.by_W), x = rem - y * g.W;
+    return ((g.cf == 1 ? ch : 0u) * g.Hb + fast_div(y, g.by_N)) * g.Wb + fast_div(x, g.by_N);      // cf is 1 or C: c' = ch or 0
+}
+
+// grid (ceil(n_box / 256), B), one thread per box.  mean = fdiv(s, (float)k), s the sequential fp32 add, from 0, of the box's members in
+// row-major (dc, dy, dx) order: single rounded operations in a fixed order, so the same call gives the same bits.
+// RES = false (gmk_box_mean): the members are x's, out = mean.
+// RES = true (gmk_box_residual): the members are the x-hat predict_x_eps<false> forms for (v, vu, w, z, lt, mt) - the step kernels' own device
+// function, hence their bits - and out = fsub(obs, mean).  v, z (and vu) are read once.
+template <bool RES>
+__global__ __launch_bounds__(256) void box_kernel(const float* __restrict__ v, const float* __restrict__ vu, const float* __restrict__ cond_w,
+                                                  const float* __restrict__ z, const float* __restrict__ obs, float lt, int mt,
+                                                  float* __restrict__ out, BoxGeom g) {
+    const int b = blockIdx.y;
+    const uint32_t box = blockIdx.x * 256 + threadIdx.x;
+    if (box >= g.n_box) return;
+    const uint32_t j = box % g.Wb, t = box / g.Wb, i = t % g.Hb, cp = t / g.Hb;
+    LogsnrCoef c = {};
+    float w = 0.f;
+    if constexpr (RES) {
+        c = logsnr_coef(lt);
+        w = cond_w ? cond_w[b] : 0.f;
+    }
+    const int64_t base = (int64_t)b * g.C * g.HW;
+    float s = 0.f;
+    for (uint32_t dc = 0; dc < g.cf; ++dc)
+        for (uint32_t dy = 0; dy < g.N; ++dy) {
+            const int64_t row = base + (int64_t)(cp * g.cf + dc) * g.HW + (i * g.N + dy) * g.W + j * g.N;
+            for (uint32_t dx = 0; dx < g.N; ++dx) {
+                float xh;
+                if constexpr (RES) {
+                    float eh;
+                    predict_x_eps<false>(v[row + dx], vu, row + dx, w, z[row + dx], c, mt, 1.0f, xh, eh);
+                } else {
+                    xh = v[row + dx];
+                }
+                s = __fadd_rn(s, xh);
+            }
+        }
+    const float mean = __fdiv_rn(s, (float)(g.cf * g.N * g.N));
+    const int64_t o = (int64_t)b * g.n_box + box;
+    out[o] = RES ? __fsub_rn(obs[o], mean) : mean;
+}
+
+// NS (gmk_sampler_step_ns / gmk_dpm_solver_step_ns): x-hat' = fadd(x-hat, res[b][box of the element]) - with res = gmk_box_residual's output
+// that is x-hat + A+(obs - A x-hat), DDNM's projection - and eps-hat = c1 (z - x-hat' c2).  x-hat' is NOT clipped again (a second clip would
+// break A x-hat' = obs; it lies in [-3, 3]); everything after it uses x-hat'.
+template <bool NS>
+__device__ __forceinline__ void null_space_fix(const float* __restrict__ res, const BoxGeom& g, int b, int64_t i, float zz, const LogsnrCoef& c,
+                                               float& xh, float& eh) {
+    if constexpr (NS) {
+        xh = __fadd_rn(xh, res[(int64_t)b * g.n_box + box_of((uint32_t)i, g)]);
+        eh = c.c1 * (zz - xh * c.c2);
+    }
+}
+
 // grid (ceil(n/256), B).  DT (gmk_sampler_step_dt): x-hat is the raw prediction clamped to thr[b] and divided by it instead of the static clip;
 // everything after x-hat is shared.  The DT = false instantiation is the kernel gmk_sampler_step and gmk_ddim_step_vec have always launched.
-template <bool DT>
+// NS (gmk_sampler_step_ns): `null_space_fix` after the static clip.
+template <bool DT, bool NS = false>
 __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restrict__ v, const float* __restrict__ vu,
                                                           const float* __restrict__ cond_w, const float* __restrict__ z,
                                                           const float* __restrict__ noise, float lt, float ls, int is_last,
@@ -429,7 +508,8 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
                                                           float* __restrict__ eps_pred, int64_t n,
                                                           const float* __restrict__ lt_vec, const float* __restrict__ ls_vec, int mt,
                                                           float* __restrict__ z_dup = nullptr, float* __restrict__ logsnr_next = nullptr,
-                                                          const float* __restrict__ thr = nullptr) {
+                                                          const float* __restrict__ thr = nullptr, const float* __restrict__ res = nullptr,
+                                                          BoxGeom geom = BoxGeom{}) {
     const int b = blockIdx.y;
     if (lt_vec) { lt = lt_vec[b]; ls = ls_vec[b]; }      // per-sample times (teacher steps of the distillation loss)
     write_logsnr_next(logsnr_next, z_dup, b, ls);
@@ -447,6 +527,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
         const float zz = z[base + i];
         float xh, eh;
         predict_x_eps<DT>(v[base + i], vu, base + i, w, zz, c, mt, DT ? thr[b] : 1.0f, xh, eh);
+        null_space_fix<NS>(res, geom, b, i, zz, c, xh, eh);
         float zs;
         if (noise) zs = (r * alpha_st * zz + omr * alpha_s * xh) + stdv * noise[base + i];   // :242
         else zs = alpha_s * xh + sigma_s * eh;                                                 // :212
@@ -461,15 +542,16 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
 // and the guidance exactly as sampler_step_kernel forms them; then D = (1 + k) x_hat - k x_prev (k = 1 / 2r, 0 on the first step: x_prev
 // is then not read) and z_s = c_z z + c_x D with c_z = sigma_s / sigma_t, c_x = -alpha_s expm1(-h), all three from the host.  x_hist
 // holds the previous step's x-hat on entry and this step's on exit (same element, same thread).  An extension: no reference call site.
-// DT (gmk_dpm_solver_step_dt): x-hat by the dynamic threshold thr[b], as in sampler_step_kernel<true>.
-template <bool DT>
+// DT (gmk_dpm_solver_step_dt): x-hat by the dynamic threshold thr[b], as in sampler_step_kernel<true>.  NS (gmk_dpm_solver_step_ns): as there.
+template <bool DT, bool NS = false>
 __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __restrict__ v, const float* __restrict__ vu,
                                                              const float* __restrict__ cond_w, const float* __restrict__ z,
                                                              float* __restrict__ x_hist, float lt, float ls, float c_z, float c_x,
                                                              float k_prev, int is_last, float* __restrict__ z_next,
                                                              float* __restrict__ x_pred, float* __restrict__ eps_pred,
                                                              float* __restrict__ z_dup, float* __restrict__ logsnr_next, int64_t n,
-                                                             int mt, const float* __restrict__ thr) {
+                                                             int mt, const float* __restrict__ thr, const float* __restrict__ res = nullptr,
+                                                             BoxGeom geom = BoxGeom{}) {
     const int b = blockIdx.y;
     write_logsnr_next(logsnr_next, z_dup, b, ls);
     const LogsnrCoef c = logsnr_coef(lt);
@@ -480,6 +562,7 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __res
         const float zz = z[base + i];
         float xh, eh;
         predict_x_eps<DT>(v[base + i], vu, base + i, w, zz, c, mt, DT ? thr[b] : 1.0f, xh, eh);
+        null_space_fix<NS>(res, geom, b, i, zz, c, xh, eh);
         const float d = second_order ? (1.0f + k_prev) * xh - k_prev * x_hist[base + i] : xh;
         const float zs = c_z * zz + c_x * d;
         x_hist[base + i] = xh;
@@ -1219,17 +1302,59 @@ static int step_args_check(const char* who, int mean_type, const float* v_uncond
     return 0;
 }
 
-// The argument checks and the launch behind gmk_sampler_step / gmk_sampler_step_dt (DT: thr is required)
-template <bool DT>
+// (M, sh) of fast_div for a divisor 1 <= d < 2^31
+static FastDiv fast_div_of(uint32_t d) {
+    uint32_t s = 0;
+    while (((uint32_t)1 << s) < d) ++s;
+    const uint32_t sh = 31 + s;
+    return FastDiv{(uint32_t)((((uint64_t)1 << sh) + d - 1) / d), sh};
+}
+
+// The box-mean operator's geometry (gmk_box_mean, gmk_box_residual and the *_ns entries): cf in {1, C}, N dividing H and W, B n_box < 2^31
+static int box_geom_check(const char* who, int B, int C, int H, int W, int cf, int N, BoxGeom* g) {
+    GMK_REQUIRE(B > 0 && B < 65536 && C > 0 && H > 0 && W > 0 && (int64_t)C * H * W < ((int64_t)1 << 31),
+                "%s: bad shape B=%d C=%d H=%d W=%d (C H W < 2^31)", who, B, C, H, W);
+    GMK_REQUIRE(cf == 1 || cf == C, "%s: cf = %d, the channels averaged together: 1 or C = %d", who, cf, C);
+    GMK_REQUIRE(N >= 1 && H % N == 0 && W % N == 0, "%s: N = %d does not divide H = %d and W = %d", who, N, H, W);
+    const int64_t n_box = (int64_t)(C / cf) * (H / N) * (W / N);
+    GMK_REQUIRE((int64_t)B * n_box < ((int64_t)1 << 31), "%s: B n_box = %lld, need < 2^31", who, (long long)((int64_t)B * n_box));
+    *g = BoxGeom{(uint32_t)C, (uint32_t)H, (uint32_t)W, (uint32_t)cf, (uint32_t)N, (uint32_t)(H * W), (uint32_t)(H / N), (uint32_t)(W / N),
+                 (uint32_t)n_box, fast_div_of((uint32_t)(H * W)), fast_div_of((uint32_t)W), fast_div_of((uint32_t)N)};
+    return 0;
+}
+
+extern "C" int gmk_box_mean(const float* x, float* out, int B, int C, int H, int W, int cf, int N, void* stream) {
+    GMK_REQUIRE(x && out, "gmk_box_mean: null pointer");
+    BoxGeom g;
+    if (const int err = box_geom_check("gmk_box_mean", B, C, H, W, cf, N, &g)) return err;
+    box_kernel<false><<<dim3((g.n_box + 255) / 256, B), 256, 0, gmk_stream(stream)>>>(x, nullptr, nullptr, nullptr, nullptr, 0.f, 0, out, g);
+    return gmk_check_launch("gmk_box_mean");
+}
+
+extern "C" int gmk_box_residual(const float* v, const float* v_uncond, const float* cond_w, const float* z, const float* obs, float logsnr_t,
+                                float* r, int mean_type, int B, int C, int H, int W, int cf, int N, void* stream) {
+    GMK_REQUIRE(v && z && obs && r, "gmk_box_residual: null pointer");
+    BoxGeom g;
+    if (const int err = box_geom_check("gmk_box_residual", B, C, H, W, cf, N, &g)) return err;
+    if (const int err = step_args_check("gmk_box_residual", mean_type, v_uncond, cond_w, B, (int64_t)C * H * W)) return err;
+    GMK_REQUIRE(isfinite(logsnr_t), "gmk_box_residual: non-finite time");
+    box_kernel<true><<<dim3((g.n_box + 255) / 256, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, obs, logsnr_t, mean_type, r, g);
+    return gmk_check_launch("gmk_box_residual");
+}
+
+// The argument checks and the launch behind gmk_sampler_step / gmk_sampler_step_dt (DT: thr is required) / gmk_sampler_step_ns (NS: res and
+// the box geometry)
+template <bool DT, bool NS = false>
 static int sampler_step_launch(const char* who, const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z,
                                const float* noise, float logsnr_t, float logsnr_s, int is_last, float* z_next, float* x_pred,
-                               float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
-    GMK_REQUIRE(v && z && z_next && (!DT || thr), "%s: null pointer", who);
+                               float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream,
+                               const float* res = nullptr, BoxGeom geom = BoxGeom{}) {
+    GMK_REQUIRE(v && z && z_next && (!DT || thr) && (!NS || res), "%s: null pointer", who);
     if (const int err = step_args_check(who, mean_type, v_uncond, cond_w, B, n)) return err;
     const int gx = row_grid(n, 256);
-    sampler_step_kernel<DT><<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, noise, logsnr_t, logsnr_s, is_last, z_next,
-                                                                         x_pred, eps_pred, n, nullptr, nullptr, mean_type, z_dup,
-                                                                         logsnr_next, thr);
+    sampler_step_kernel<DT, NS><<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, noise, logsnr_t, logsnr_s, is_last, z_next,
+                                                                             x_pred, eps_pred, n, nullptr, nullptr, mean_type, z_dup,
+                                                                             logsnr_next, thr, res, geom);
     return gmk_check_launch(who);
 }
 
@@ -1248,19 +1373,20 @@ extern "C" int gmk_sampler_step_dt(const float* v, const float* v_uncond, const 
                                      eps_pred, z_dup, logsnr_next, mean_type, B, n, stream);
 }
 
-template <bool DT>
+template <bool DT, bool NS = false>
 static int dpm_solver_step_launch(const char* who, const float* v, const float* v_uncond, const float* cond_w, const float* thr,
                                   const float* z, float* x_hist, float logsnr_t, float logsnr_s, float coef_z, float coef_x,
                                   float coef_prev, int is_last, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
-                                  float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
-    GMK_REQUIRE(v && z && x_hist && z_next && (!DT || thr), "%s: null pointer", who);
+                                  float* logsnr_next, int mean_type, int B, int64_t n, void* stream, const float* res = nullptr,
+                                  BoxGeom geom = BoxGeom{}) {
+    GMK_REQUIRE(v && z && x_hist && z_next && (!DT || thr) && (!NS || res), "%s: null pointer", who);
     if (const int err = step_args_check(who, mean_type, v_uncond, cond_w, B, n)) return err;
     GMK_REQUIRE(isfinite(logsnr_t) && isfinite(logsnr_s) && isfinite(coef_z) && isfinite(coef_x) && isfinite(coef_prev),
                 "%s: non-finite time or coefficient", who);
     const int gx = row_grid(n, 256);
-    dpm_solver_step_kernel<DT><<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x,
-                                                                            coef_prev, is_last, z_next, x_pred, eps_pred, z_dup, logsnr_next,
-                                                                            n, mean_type, thr);
+    dpm_solver_step_kernel<DT, NS><<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, x_hist, logsnr_t, logsnr_s, coef_z,
+                                                                                coef_x, coef_prev, is_last, z_next, x_pred, eps_pred, z_dup,
+                                                                                logsnr_next, n, mean_type, thr, res, geom);
     return gmk_check_launch(who);
 }
 
@@ -1278,6 +1404,34 @@ extern "C" int gmk_dpm_solver_step_dt(const float* v, const float* v_uncond, con
                                       int mean_type, int B, int64_t n, void* stream) {
     return dpm_solver_step_launch<true>("gmk_dpm_solver_step_dt", v, v_uncond, cond_w, thr, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x,
                                         coef_prev, is_last, z_next, x_pred, eps_pred, z_dup, logsnr_next, mean_type, B, n, stream);
+}
+
+// the *_ns entries: the box geometry must describe the rows, n = C H W
+static int ns_geom_check(const char* who, int B, int64_t n, int C, int H, int W, int cf, int N, BoxGeom* g) {
+    if (const int err = box_geom_check(who, B, C, H, W, cf, N, g)) return err;
+    GMK_REQUIRE(n == (int64_t)C * H * W, "%s: n = %lld is not C H W = %lld", who, (long long)n, (long long)((int64_t)C * H * W));
+    return 0;
+}
+
+extern "C" int gmk_sampler_step_ns(const float* v, const float* v_uncond, const float* cond_w, const float* r, const float* z,
+                                   const float* noise, float logsnr_t, float logsnr_s, int is_last, float* z_next, float* x_pred,
+                                   float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, int C, int H, int W,
+                                   int cf, int N, void* stream) {
+    BoxGeom g;
+    if (const int err = ns_geom_check("gmk_sampler_step_ns", B, n, C, H, W, cf, N, &g)) return err;
+    return sampler_step_launch<false, true>("gmk_sampler_step_ns", v, v_uncond, cond_w, nullptr, z, noise, logsnr_t, logsnr_s, is_last, z_next,
+                                            x_pred, eps_pred, z_dup, logsnr_next, mean_type, B, n, stream, r, g);
+}
+
+extern "C" int gmk_dpm_solver_step_ns(const float* v, const float* v_uncond, const float* cond_w, const float* r, const float* z,
+                                      float* x_hist, float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_prev,
+                                      int is_last, float* z_next, float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next,
+                                      int mean_type, int B, int64_t n, int C, int H, int W, int cf, int N, void* stream) {
+    BoxGeom g;
+    if (const int err = ns_geom_check("gmk_dpm_solver_step_ns", B, n, C, H, W, cf, N, &g)) return err;
+    return dpm_solver_step_launch<false, true>("gmk_dpm_solver_step_ns", v, v_uncond, cond_w, nullptr, z, x_hist, logsnr_t, logsnr_s, coef_z,
+                                               coef_x, coef_prev, is_last, z_next, x_pred, eps_pred, z_dup, logsnr_next, mean_type, B, n,
+                                               stream, r, g);
 }
 
 extern "C" int gmk_dyn_threshold(const float* v, const float* v_uncond, const float* cond_w, const float* z, float logsnr_t, int k_lo,

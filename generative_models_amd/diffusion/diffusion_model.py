@@ -23,7 +23,7 @@ import os
 import torch
 
 from .. import checkpoint, common, ops, parallel
-from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check, edit_start, loss_weight_check, time_importance_check
+from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check, edit_start, loss_weight_check, restore_operator, time_importance_check
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -66,6 +66,10 @@ def make_plugin(GMBase, AttrDict):
                                        # denoised from there) as last_eval['edit'] / frames 'edit'; not in the reference, off by default
         DG.interp_eval = 0             # K >= 2: evaluate() also interpolates test images 0-4 into 5-9 through their latent codes in K frames (DDIM
                                        # inversion, slerp, decode) as last_eval['interp'] / frames 'interp'; not in the reference, off by default
+        DG.restore_eval = 0            # N >= 2: evaluate() also restores the first 25 test images from their N x N box means (DDNM super-resolution,
+                                       # Wang, Yu & Zhang 2023) as last_eval['restore'] / frames 'restore', 'restore_input', with last_eval['restore_psnr'];
+                                       # not in the reference, off by default
+        DG.restore_gray = 0            # 1: that restoration also (or, with restore_eval = 0, only) starts from the channel mean (colourisation)
         DG.dyn_threshold = 0.0         # p in (0, 1]: sample() / evaluate() / inpaint() clamp each image's x-hat to its own p-th percentile of |x| and rescale
                                        # (dynamic thresholding, Saharia et al. 2022; e.g. 0.995) instead of the clip at 1; not in the reference, off by default
         DG.grad_clip = 0.0             # c > 0: clip the global gradient norm to c inside the optimiser step (torch.nn.utils.clip_grad_norm_'s rule) and
@@ -136,6 +140,16 @@ def make_plugin(GMBase, AttrDict):
             if self.interp_eval > 0 and self.teacher_net is not None:
                 raise ValueError("interp_eval > 0 with teacher_path: a distilled student is conditioned on cond_w; its probability-flow ODE has "
                                  "no density")
+            self.restore_eval = int(get("restore_eval"))
+            if self.restore_eval < 0 or self.restore_eval == 1 or self.restore_eval != float(get("restore_eval")):
+                raise ValueError(f"restore_eval = {get('restore_eval')}: 0 (off) or the super-resolution factor N >= 2")
+            if get("restore_gray") not in (0, 1):
+                raise ValueError(f"restore_gray = {get('restore_gray')!r}: 0 (off) or 1")
+            self.restore_gray = int(get("restore_gray"))
+            if self.restore_gray and int(get("in_channels")) == 1:
+                raise ValueError("restore_gray = 1 with in_channels = 1: there is no colour to restore")
+            if (self.restore_eval or self.restore_gray) and float(get("dyn_threshold")) > 0:
+                raise ValueError("restore_eval / restore_gray with dyn_threshold: restoration together with dynamic thresholding is out of scope")
             self.binarize = int(get("binarize"))
             dyn_threshold = dyn_threshold_check(get("dyn_threshold"))
             loss_weight, loss_gamma, time_sampler = loss_weight_check(get("loss_weight"), get("loss_gamma"), get("time_sampler"),
@@ -444,6 +458,25 @@ def make_plugin(GMBase, AttrDict):
                 cond_w = 0.5 if y is not None else None
                 return self.diffusion.inpaint(net=net, x0=x, mask=mask, init_x=noise, cond_w=cond_w, resample=resample, seed=seed)[0][-1]
 
+        # -- restoration (an extension): DDNM super-resolution and colourisation on the net sample() uses
+        def degrade(self, x, factor=1, gray=False):
+            """The observation A x that `restore` starts from: x ([B, C, S, S]) averaged over factor x factor pixels and, with gray, over its
+            channels (`ops.box_mean`).  -> fp32 [B, C or 1, S / factor, S / factor]"""
+            x = ops.aligned(x.float().contiguous())
+            cf, N, _ = restore_operator(tuple(x.shape), factor, gray)
+            return ops.box_mean(x, cf, N)
+
+        def restore(self, obs, factor=1, gray=False, y=None, seed=0):
+            """An image of this model whose `degrade(., factor, gray)` is obs ([B, C or 1, S / factor, S / factor]), with
+            `GaussianDiffusion.restore` (DDNM).  y: labels, as in sample() (then guided with cond_w = 0.5).  The initial noise comes from
+            PhiloxStream(seed).  -> [B, C, S, S]"""
+            with torch.no_grad():
+                shape = (obs.shape[0], self.net.in_channels, self.size, self.size)
+                noise = PhiloxStream(seed).normal(shape, obs.device)
+                net = partial(self._sampling_net(), guide=y)
+                cond_w = 0.5 if y is not None else None
+                return self.diffusion.restore(net=net, obs=obs, factor=factor, gray=gray, init_x=noise, cond_w=cond_w)[0][-1]
+
         # -- editing and interpolation (extensions): SDEdit and latent-code interpolation on the net sample() uses
         def edit(self, x, strength, y=None, mask=None, seed=0):
             """Edit x ([B, C, S, S] in [-1, 1]) with `GaussianDiffusion.edit`: noised up to step k = edit_start(strength, timesteps) of the
@@ -463,6 +496,7 @@ def make_plugin(GMBase, AttrDict):
                                               num_steps=steps or self.diffusion.num_steps)
 
         INPAINT_EVAL_SEED = 104723                  # evaluate()'s inpainting: initial noise from PhiloxStream(this), known-region noise from this + 1
+        RESTORE_EVAL_SEED = 104759                  # evaluate()'s restoration: the initial noise (and nothing else) from PhiloxStream(this)
         EDIT_EVAL_SEED = 104743                     # evaluate()'s editing: the forward noise (and nothing else) from PhiloxStream(this)
 
         # -- evaluate (:89-111): 25 class-conditional samples without guidance, trajectories as uint8
@@ -517,6 +551,24 @@ def make_plugin(GMBase, AttrDict):
                 self.last_eval["interp"] = proc(z)
                 if pictures:
                     writer.write_frames("interp", z, epoch, crop=crop)
+            if self.restore_eval >= 2 or self.restore_gray:           # an extension, as above: its noise from PhiloxStream(RESTORE_EVAL_SEED)
+                k = min(25, x.shape[0])
+                x0 = ops.aligned(x[:k].float().contiguous())
+                N, gray = max(1, self.restore_eval), bool(self.restore_gray)
+                cf = x0.shape[1] if gray else 1
+                obs = ops.box_mean(x0, cf, N)
+                init = PhiloxStream(self.RESTORE_EVAL_SEED).normal(tuple(x0.shape), x.device)
+                z = self.diffusion.restore(net=partial(self._sampling_net(), guide=None if y is None else y[:k]), obs=obs, factor=N, gray=gray,
+                                           init_x=init)[0][-1]
+                # the replicated observation A+ obs: what a viewer would see without the model
+                z_in = obs.repeat_interleave(N, dim=2).repeat_interleave(N, dim=3).repeat_interleave(cf, dim=1)
+                psnr = lambda t: 10.0 * torch.log10(4.0 / (t.double() - x0.double()).square().mean(dim=(1, 2, 3)))
+                self.last_eval["restore"] = proc(z)
+                self.last_eval["restore_psnr"] = psnr(z).cpu()
+                self.last_eval["restore_input_psnr"] = psnr(z_in).cpu()
+                if pictures:
+                    writer.write_frames("restore", z, epoch, crop=crop)
+                    writer.write_frames("restore_input", z_in, epoch, crop=crop)
             random.randint(0, 2 ** 32)                                # :111 keeps the host RNG consumption
 
     return DiffusionModel

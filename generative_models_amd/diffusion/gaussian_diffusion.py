@@ -20,6 +20,8 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
                                         the training times from it (Nichol & Dhariwal 2021, section 3.3) (extensions, no reference call site)
 * editing and interpolation (`edit`, `interpolate`)  sampler chains that start part-way (`start=`), gmk_q_sample_logsnr for the forward noising, gmk_slerp
                                         between two latent codes (SDEdit, Meng et al. 2022; DDIM's interpolation, Song et al. 2021; extensions, no reference call site)
+* restoration (`restore`)               gmk_box_residual, then gmk_sampler_step_ns / gmk_dpm_solver_step_ns: DDNM's projection of x-hat onto the images that
+                                        agree with a low-resolution and / or grey observation (Wang, Yu & Zhang 2023; an extension, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -270,6 +272,32 @@ SamplerStep = namedtuple("SamplerStep", "i lt ls is_last passes dpm inp")
 # what inpainting adds to the sampler loop: x0 and the uint8 mask [B, n] (of the whole batch, or of a chunk's rows), the known-region
 # PhiloxStream, resample, and the whole-batch Philox counter of each network evaluation's merge (filled as the loop reserves them)
 InpaintState = namedtuple("InpaintState", "x0 mask rng resample B_total moffs")
+
+
+# what restoration (DDNM) adds to the sampler loop: the observation obs = A x, fp32 [B, C / cf, H / N, W / N] (of the whole batch, or of a
+# chunk's rows), and the box-mean operator's parameters (cf channels averaged together, an N x N spatial box)
+RestoreState = namedtuple("RestoreState", "obs cf N")
+
+
+def restore_operator(shape, factor=1, gray=False):
+    """The box-mean operator of `restore` / `degrade` on images of `shape` = [B, C, H, W]: factor = N (the side of the spatial box, N = 1 keeps
+    the resolution), gray = average the C channels.  -> (cf, N, observation shape [B, C / cf, H / N, W / N]), or ValueError: a shape that is
+    not [B, C, H, W], N not an integer >= 1 dividing H and W, gray with C == 1, or k = cf N^2 < 2 (nothing is degraded)."""
+    if len(shape) != 4 or 0 in shape:
+        raise ValueError(f"restore: shape {tuple(shape)}, expected [B, C, H, W] with every dimension > 0")
+    B, C, H, W = (int(d) for d in shape)
+    N = factor
+    if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or N < 1:
+        raise ValueError(f"restore: factor = {factor!r}, need an integer >= 1")
+    N = int(N)
+    if H % N or W % N:
+        raise ValueError(f"restore: factor = {N} does not divide H = {H} and W = {W}")
+    if gray and C == 1:
+        raise ValueError("restore: gray = True with one channel: there is no colour to restore")
+    cf = C if gray else 1
+    if cf * N * N < 2:
+        raise ValueError("restore: factor = 1 without gray: the box size k = cf factor^2 is 1, the observation is the image itself")
+    return cf, N, (B, C // cf, H // N, W // N)
 
 
 def sampler_plan(num_steps, sampler="ddim", resample=None, start=None):
@@ -859,6 +887,29 @@ class GaussianDiffusion:
         inp = InpaintState(ops.aligned(x0.to(init_x.device).float()), m, PhiloxStream(seed), r, shape[0], [])
         return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, inp=inp, start=start)
 
+    # ---- restoration from a degraded observation (DDNM, Wang, Yu & Zhang 2023; an extension, no reference call site) -----------------------
+    @torch.no_grad()
+    def restore(self, *, net, obs, factor=1, gray=False, init_x, cond_w=None, record=False):
+        """Sample an image that agrees with the observation obs = A x, A the box mean over factor x factor pixels (super-resolution) and, with
+        gray, over the C channels (colourisation): at every step the data prediction x-hat is replaced by x-hat + A+(obs - A x-hat) (DDNM, eq.
+        13-14: the observation fixes the range-space part, the network fills in the null-space part), so the result r satisfies A r = obs up to
+        fp32 rounding.  obs: fp32 [B, C / cf, H / factor, W / factor] (cf = C with gray, else 1; `ops.box_mean` makes one); init_x: [B, C, H, W]
+        noise.  Two extra launches per network evaluation: gmk_box_residual, then the *_ns update.  Samplers 'ddim', 'noisy', 'dpmpp_2m'; `net`
+        / `cond_w` (guidance) and the noise of 'noisy' as in `sample`.  Out of scope, and a ValueError: noisy observations (DDNM+), time
+        travel, and restoration together with dynamic thresholding or inpainting.  -> sample()'s triple."""
+        if self.sampler == "teacher_test":
+            raise ValueError("restore: sampler 'teacher_test' is not supported (samplers 'ddim', 'noisy', 'dpmpp_2m')")
+        if self.dyn_threshold:
+            raise ValueError("restore: dyn_threshold is set: restoration together with dynamic thresholding (or inpainting) is out of scope - "
+                             "the projected x-hat must not be rescaled")
+        shape = tuple(init_x.shape)
+        cf, N, low = restore_operator(shape, factor, gray)
+        if not isinstance(obs, torch.Tensor) or tuple(obs.shape) != low:
+            raise ValueError(f"restore: obs shape {tuple(obs.shape) if isinstance(obs, torch.Tensor) else type(obs).__name__}, expected {low} for "
+                             f"init_x {shape}, factor = {N}, gray = {bool(gray)}")
+        rst = RestoreState(ops.aligned(obs.to(init_x.device).float().contiguous()), cf, N)
+        return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, rst=rst)
+
     def _inpaint_known(self, mask, shape, device):
         """The shape rules of the inpainting loop ([B, ...], a multiple of 4 values per image), then the mask -> uint8 [B, n] (`_inpaint_mask`)."""
         if len(shape) < 2 or 0 in shape:
@@ -938,8 +989,11 @@ class GaussianDiffusion:
                          for c in lat.split(per)])
         return (out, lat) if return_latents else out
 
-    def _sample(self, *, net, init_x, cond_w=None, record=True, noises=None, net_cond_w=None, inp=None, start=None):
-        """The loop behind `sample`, `inpaint` and `edit` (inp: None, or the whole batch's InpaintState; start: `sampler_plan`'s)."""
+    def _sample(self, *, net, init_x, cond_w=None, record=True, noises=None, net_cond_w=None, inp=None, start=None, rst=None):
+        """The loop behind `sample`, `inpaint`, `edit` and `restore` (inp: None, or the whole batch's InpaintState; start: `sampler_plan`'s; rst:
+        None, or the whole batch's RestoreState)."""
+        if rst is not None and (inp is not None or self.dyn_threshold):
+            raise ValueError("restore: restoration together with inpainting or dynamic thresholding is out of scope")
         module, guide, kw_cond_w = _unwrap(net)
         B = init_x.shape[0]
         dev = init_x.device
@@ -981,8 +1035,9 @@ class GaussianDiffusion:
         gens = []
         for a, b_ in [(k * B // K, (k + 1) * B // K) for k in range(K)]:
             inp_k = None if inp is None else inp._replace(x0=cut(inp.x0, a, b_), mask=cut(inp.mask, a, b_))
+            rst_k = None if rst is None else rst._replace(obs=cut(rst.obs, a, b_))
             gens.append(self._sample_chunk(plan, module, cut(guide, a, b_), cut(student_w, a, b_), cut(w, a, b_), cut(z_all, a, b_),
-                                           noises if (noises is None or K == 1) else torch.as_tensor(noises)[:, a:b_], record, offs, a * n1 // 4, inp_k))
+                                           noises if (noises is None or K == 1) else torch.as_tensor(noises)[:, a:b_], record, offs, a * n1 // 4, inp_k, rst_k))
         if K > 1:
             # what a forward builds lazily after a weight update (packed weights, frequency tables) is enqueued HERE, on the stream both chunk
             # streams wait for: the first chunk's forward would otherwise re-pack on ITS stream and clear the host flag, and the second chunk's
@@ -1026,11 +1081,11 @@ class GaussianDiffusion:
             self._streams = [torch.cuda.Stream(device=dev) for _ in range(K)]
         return self._streams[:K]
 
-    def _sample_chunk(self, plan, module, guide, student_w, w, z_t, noises, record, offs, q0, inp=None):
+    def _sample_chunk(self, plan, module, guide, student_w, w, z_t, noises, record, offs, q0, inp=None, rst=None):
         """The sampler loop over one (chunk of a) batch as a generator: one `next` per step of `plan` (everything it launches goes to the stream
         current at that call), then one more for the result.  offs[f] / q0: Philox counter of network evaluation `f`'s whole-batch noise draw /
         this chunk's offset in it.  inp (inpainting): None, or the InpaintState with this chunk's rows of x0 and mask - inp.moffs[f] is the
-        whole-batch Philox counter of evaluation f's merge."""
+        whole-batch Philox counter of evaluation f's merge.  rst (restoration): None, or the RestoreState with this chunk's rows of obs."""
         B = z_t.shape[0]
         zs, xs, es = [], [], []
         guided = w is not None
@@ -1061,12 +1116,15 @@ class GaussianDiffusion:
                     noise = ops.aligned(noises[i]) if noises is not None else ops.rng_normal(tuple(z_t.shape), self.rng.seed, offs[f] + q0, z_t.device)
                 # dynamic thresholding: one select launch per network evaluation (per image, so a half-batch gives the whole batch's bits)
                 thr = ops.dyn_threshold(v, z_t, lt, self.dyn_threshold, v_uncond=vu, cond_w=w, mean_type=self.mean_type) if self.dyn_threshold else None
+                # restoration: one residual launch per network evaluation (per image, so a half-batch gives the whole batch's bits)
+                ns = None if rst is None else (ops.box_residual(v, z_t, rst.obs, lt, rst.cf, rst.N, v_uncond=vu, cond_w=w, mean_type=self.mean_type),
+                                               rst.cf, rst.N)
                 if dpm is not None:
                     z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, dpm.coef_z, dpm.coef_x, dpm.coef_prev, step.is_last, v_uncond=vu, cond_w=w,
-                                                      want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr)
+                                                      want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr, ns=ns)
                 else:
                     z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, step.is_last, v_uncond=vu, cond_w=w, noise=noise, want_pred=record,
-                                                   mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr)
+                                                   mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr, ns=ns)
                 if guided:
                     z_t, z2 = z_t
                 if inp is not None:             # the known region, then (all passes but the step's last) the jump back to time t

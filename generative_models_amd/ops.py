@@ -1074,14 +1074,76 @@ def _thr_check(thr, B):
     return thr
 
 
+def box_geometry(shape, cf, N):
+    """The box-mean operator A of DDNM restoration (gmk_box_mean) on images of `shape` = [B, C, H, W]: cf in {1, C} channels averaged together,
+    an N x N spatial box.  -> (B, C, H, W, cf, N, low-resolution shape [B, C / cf, H / N, W / N]), or ValueError."""
+    if len(shape) != 4 or 0 in shape:
+        raise ValueError(f"box operator: shape {tuple(shape)}, expected [B, C, H, W] with every dimension > 0")
+    B, C, H, W = (int(d) for d in shape)
+    if isinstance(cf, bool) or isinstance(N, bool) or int(cf) != cf or int(N) != N:
+        raise ValueError(f"box operator: cf = {cf!r}, N = {N!r}: integers")
+    cf, N = int(cf), int(N)
+    if cf not in (1, C):
+        raise ValueError(f"box operator: cf = {cf}, the channels averaged together: 1 or C = {C}")
+    if N < 1 or H % N or W % N:
+        raise ValueError(f"box operator: N = {N} does not divide H = {H} and W = {W}")
+    low = (B, C // cf, H // N, W // N)
+    if C * H * W >= 1 << 31 or math.prod(low) >= 1 << 31:
+        raise ValueError(f"box operator: shape {tuple(shape)} has 2^31 or more values per image, or boxes per batch")
+    return B, C, H, W, cf, N, low
+
+
+def box_mean(x, cf, N):
+    """A x of DDNM restoration (gmk_box_mean; an extension): x fp32 [B, C, H, W] -> fp32 [B, C / cf, H / N, W / N], each value the mean of a
+    box of cf channels x N x N pixels: the sequential fp32 sum of the members in (dc, dy, dx) order, divided by k = cf N^2."""
+    _f32(x, "x")
+    B, C, H, W, cf, N, low = box_geometry(tuple(x.shape), cf, N)
+    out = torch.empty(low, device=x.device, dtype=torch.float32)
+    check(lib.gmk_box_mean(_p(x), _p(out), B, C, H, W, cf, N, _s()), "box_mean")
+    return out
+
+
+def _ns_check(ns, z):
+    """`ns` of the *_ns entries: (r, cf, N) with r fp32 [B, C / cf, H / N, W / N] (`box_residual`'s output) -> (r, C, H, W, cf, N)"""
+    r, cf, N = ns
+    _, C, H, W, cf, N, low = box_geometry(tuple(z.shape), cf, N)
+    _f32(r, "ns residual")
+    if tuple(r.shape) != low:
+        raise ValueError(f"ns residual: shape {tuple(r.shape)}, expected {low}")
+    return r, C, H, W, cf, N
+
+
+def box_residual(v, z, obs, logsnr_t, cf, N, v_uncond=None, cond_w=None, mean_type="v"):
+    """DDNM's residual obs - A x-hat (gmk_box_residual; Wang, Yu & Zhang 2023; an extension): x-hat the clipped (guided, when v_uncond /
+    cond_w are given) data prediction `sampler_step` forms for the network output v at (z, logsnr_t), bit for bit.  v, z, v_uncond: fp32
+    [B, C, H, W]; obs: fp32 [B, C / cf, H / N, W / N].  -> r of obs's shape: the `ns=(r, cf, N)` of `sampler_step` / `dpm_solver_step`."""
+    _sampler_check(v, z, ((v_uncond, "v_uncond"),), cond_w)
+    B, C, H, W, cf, N, low = box_geometry(tuple(z.shape), cf, N)
+    _f32(obs, "obs")
+    if tuple(obs.shape) != low:
+        raise ValueError(f"obs: shape {tuple(obs.shape)}, expected {low}")
+    r = torch.empty_like(obs)
+    check(lib.gmk_box_residual(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(obs), float(logsnr_t), _p(r), MEAN_TYPES[mean_type], B, C, H, W,
+                               cf, N, _s()), "box_residual")
+    return r
+
+
 def sampler_step(v, z, logsnr_t, logsnr_s, is_last, v_uncond=None, cond_w=None, noise=None, want_pred=False, mean_type="v",
-                 dup=False, logsnr_next=None, thr=None):
+                 dup=False, logsnr_next=None, thr=None, ns=None):
     """dup: z_next is returned as the first half of a [2B, ...] tensor whose second half holds the same values (z2 = returned[1]);
     logsnr_next: fp32 [B] (or [2B] with dup) filled with logsnr_s.  thr: None, or fp32 [B] - dynamic thresholding (gmk_sampler_step_dt):
-    x-hat is the unclipped (guided) prediction clamped to +-thr[b] and divided by thr[b] (`dyn_threshold` gives thr)."""
+    x-hat is the unclipped (guided) prediction clamped to +-thr[b] and divided by thr[b] (`dyn_threshold` gives thr).  ns: None, or
+    (r, cf, N) - DDNM's null-space projection (gmk_sampler_step_ns): x-hat + A+ r with r = `box_residual`'s output; not together with thr."""
     B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((v_uncond, "v_uncond"), (noise, "noise")), cond_w, want_pred, dup, logsnr_next)
     tail = (float(logsnr_t), float(logsnr_s), int(is_last), _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next),
-            MEAN_TYPES[mean_type], B, n, _s())
+            MEAN_TYPES[mean_type], B, n)
+    if ns is not None:
+        if thr is not None:
+            raise ValueError("sampler_step: ns (restoration) together with thr (dynamic thresholding) is not supported")
+        r, *geom = _ns_check(ns, z)
+        check(lib.gmk_sampler_step_ns(_p(v), _p(v_uncond), _p(cond_w), _p(r), _p(z), _p(noise), *tail, *geom, _s()), "sampler_step_ns")
+        return ((z_next, z2) if dup else z_next), xp, ep
+    tail += (_s(),)
     if thr is None:
         check(lib.gmk_sampler_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(noise), *tail), "sampler_step")
     else:
@@ -1090,13 +1152,20 @@ def sampler_step(v, z, logsnr_t, logsnr_s, is_last, v_uncond=None, cond_w=None, 
 
 
 def dpm_solver_step(v, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x, coef_prev, is_last, v_uncond=None, cond_w=None, want_pred=False,
-                    mean_type="v", dup=False, logsnr_next=None, thr=None):
+                    mean_type="v", dup=False, logsnr_next=None, thr=None, ns=None):
     """One DPM-Solver++(2M) step (gmk_dpm_solver_step).  x_hist: fp32 [B, ...], the previous x-hat, overwritten with this step's (not read
     when coef_prev == 0).  Arguments and returns otherwise as `sampler_step` (no noise: the solver is deterministic); thr as there
-    (gmk_dpm_solver_step_dt)."""
+    (gmk_dpm_solver_step_dt), ns as there (gmk_dpm_solver_step_ns)."""
     B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((x_hist, "x_hist"), (v_uncond, "v_uncond")), cond_w, want_pred, dup, logsnr_next)
     tail = (_p(x_hist), float(logsnr_t), float(logsnr_s), float(coef_z), float(coef_x), float(coef_prev), int(is_last), _p(z_next), _p(xp),
-            _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s())
+            _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next), MEAN_TYPES[mean_type], B, n)
+    if ns is not None:
+        if thr is not None:
+            raise ValueError("dpm_solver_step: ns (restoration) together with thr (dynamic thresholding) is not supported")
+        r, *geom = _ns_check(ns, z)
+        check(lib.gmk_dpm_solver_step_ns(_p(v), _p(v_uncond), _p(cond_w), _p(r), _p(z), *tail, *geom, _s()), "dpm_solver_step_ns")
+        return ((z_next, z2) if dup else z_next), xp, ep
+    tail += (_s(),)
     if thr is None:
         check(lib.gmk_dpm_solver_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), *tail), "dpm_solver_step")
     else:

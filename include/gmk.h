@@ -413,6 +413,33 @@ int gmk_sampler_step_dt(const float* v, const float* v_uncond, const float* cond
 int gmk_dpm_solver_step_dt(const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z, float* x_hist,
                            float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last, float* z_next,
                            float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+/* DDNM restoration for box-mean operators (Wang, Yu & Zhang 2023, "Zero-Shot Image Restoration Using Denoising Diffusion Null-Space Model",
+ * eq. 13-14, noise-free); an extension, no reference call site.  Images are NCHW fp32, n = C H W.  The operator A has parameters (cf, N):
+ * cf in {1, C} channels are averaged together (cf = C: colourisation), N >= 1 is the side of the spatial box (H % N == 0, W % N == 0), k = cf N^2.
+ * Box g = (c', i, j), c' < C / cf, i < H / N, j < W / N, holds the elements (c' cf + dc, i N + dy, j N + dx); the low-resolution layout is
+ * [B][C / cf][H / N][W / N] fp32, n_box = n / k values per image.
+ *   A x [g] = fdiv(s, (float)k), s the sequential fp32 add, from 0, of the members in row-major (dc, dy, dx) order (nothing contracted: the same
+ *     call gives the same bits).  A+ u replicates u[g] over the members of g, so A A+ = I and x + A+(y - A x) projects onto {x : A x = y}.
+ *   gmk_box_mean: out = A x.  Any k >= 1.
+ *   gmk_box_residual: r[b][g] = fsub(obs[b][g], (A x_hat)[b][g]), x_hat exactly the clipped (and, with v_uncond / cond_w, guided) data prediction
+ *     gmk_sampler_step forms for (v, v_uncond, cond_w, z, logsnr_t, mean_type): the same device function, the same bits.  One thread per box;
+ *     v, z (and v_uncond) are read once, n_box floats per image are written.
+ *   gmk_sampler_step_ns / gmk_dpm_solver_step_ns: gmk_sampler_step / gmk_dpm_solver_step with x_hat' = fadd(x_hat, r[b][box of the element]) in
+ *     place of x_hat and eps_hat = eps(z, x_hat'); everything after it (the DDIM / ancestral / solver update, x_hist, the is_last select, z_dup,
+ *     logsnr_next, x_pred, eps_pred) unchanged and on x_hat'.  x_hat' is not clipped again (a second clip would break A x_hat' = obs); it lies in
+ *     [-3, 3].  r: B x n_box floats, required (gmk_box_residual's output); n must equal C H W.  With r = 0 they give the bits of the entries
+ *     without _ns: the same kernels, instantiated once more.
+ * Errors (GMK_ERR_ARG): cf not in {1, C}; N not dividing H or W; B n_box >= 2^31; C H W >= 2^31. */
+int gmk_box_mean(const float* x, float* out, int B, int C, int H, int W, int cf, int N, void* stream);
+int gmk_box_residual(const float* v, const float* v_uncond, const float* cond_w, const float* z, const float* obs, float logsnr_t, float* r,
+                     int mean_type, int B, int C, int H, int W, int cf, int N, void* stream);
+int gmk_sampler_step_ns(const float* v, const float* v_uncond, const float* cond_w, const float* r, const float* z, const float* noise,
+                        float logsnr_t, float logsnr_s, int is_last, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
+                        float* logsnr_next, int mean_type, int B, int64_t n, int C, int H, int W, int cf, int N, void* stream);
+int gmk_dpm_solver_step_ns(const float* v, const float* v_uncond, const float* cond_w, const float* r, const float* z, float* x_hist,
+                           float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last, float* z_next,
+                           float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, int C, int H,
+                           int W, int cf, int N, void* stream);
 /* RePaint inpainting merge (Lugmayr et al. 2022, Algorithm 1, jump length 1); an extension, no reference call site.  In place on z (B x n,
  * fp32), after the sampler update of a step t -> s has written it.  mask: uint8 B x n in x's element order, nonzero = known pixel; x0: the
  * known image (B x n fp32).  n % 4 == 0.
