@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "gmk_common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(512) void conv1x1_wgrad_stream_kernel(const bf16_t*
 }  // namespace
 
 // 1 if the launch was taken (16-bit, 128 input channels, enough tiles for one per CU and 32-bit offsets), 0 otherwise
-int gmk_conv1x1_pair_stream_try(const void* src, int64_t npix, const void* w_rows256, void* out_a, void* out_b, int dtype, hipStream_t stream) {
+int gmk_conv1x1_pair_stream_try(const void* src, int64_t npix, const void* w_rows256, void* out_a, void* out_b, int dtype, void* stream) {
     if (!gmk_is16(dtype) || gmk_kernel_choice(3, "GMK_DEV_VARIANT") == 46) return 0;
     const int64_t bytes = npix * 256;
     if (bytes >= 0xFFFFFF00ll) return 0;
@@ -237,17 +238,17 @@ int gmk_conv1x1_pair_stream_try(const void* src, int64_t npix, const void* w_row
     if (ntiles < 2 * ncu) return 0;                       // small problems: the general kernel (or two plain launches)
     const unsigned grid = (unsigned)ncu;
     if (dtype == GMK_BF16)
-        conv1x1_pair_stream_kernel<bf16_t><<<grid, 256, 0, stream>>>((const bf16_t*)src, (const bf16_t*)w_rows256, (bf16_t*)out_a, (bf16_t*)out_b,
+        conv1x1_pair_stream_kernel<bf16_t><<<grid, 256, 0, gmk_stream(stream)>>>((const bf16_t*)src, (const bf16_t*)w_rows256, (bf16_t*)out_a, (bf16_t*)out_b,
                                                                     (unsigned)npix, (unsigned)ntiles, (unsigned)bytes);
     else
-        conv1x1_pair_stream_kernel<f16_t><<<grid, 256, 0, stream>>>((const f16_t*)src, (const f16_t*)w_rows256, (f16_t*)out_a, (f16_t*)out_b,
+        conv1x1_pair_stream_kernel<f16_t><<<grid, 256, 0, gmk_stream(stream)>>>((const f16_t*)src, (const f16_t*)w_rows256, (f16_t*)out_a, (f16_t*)out_b,
                                                                    (unsigned)npix, (unsigned)ntiles, (unsigned)bytes);
     return 1;
 }
 
 // Number of slabs written (> 0) if the launch was taken: bf16 gradients, 128 + 128 input channels, 128 output channels, enough 64-pixel steps
 int gmk_conv1x1_wgrad_stream_try(const void* dy, int dy_cstride, const void* src0, const void* src1, int64_t npix, float* slab, int64_t slab_bytes,
-                                 bool x_f16, hipStream_t stream) {
+                                 bool x_f16, void* stream) {
     if (gmk_kernel_choice(3, "GMK_DEV_VARIANT") == 47) return 0;
     const int ncu = gmk_cu_limit();
     if (npix < (int64_t)ncu * 64 * 8 || npix >= (1ll << 31) - 64) return 0;        // at least 8 steps per workgroup
@@ -256,8 +257,8 @@ int gmk_conv1x1_wgrad_stream_try(const void* dy, int dy_cstride, const void* src
     chunk = (chunk + 63) / 64 * 64;
     const int ns = (int)((npix + chunk - 1) / chunk);
     if (x_f16)
-        conv1x1_wgrad_stream_kernel<f16_t><<<ns, 512, 0, stream>>>((const bf16_t*)dy, dy_cstride, (const f16_t*)src0, (const f16_t*)src1, slab, (int)npix, (int)chunk);
+        conv1x1_wgrad_stream_kernel<f16_t><<<ns, 512, 0, gmk_stream(stream)>>>((const bf16_t*)dy, dy_cstride, (const f16_t*)src0, (const f16_t*)src1, slab, (int)npix, (int)chunk);
     else
-        conv1x1_wgrad_stream_kernel<bf16_t><<<ns, 512, 0, stream>>>((const bf16_t*)dy, dy_cstride, (const bf16_t*)src0, (const bf16_t*)src1, slab, (int)npix, (int)chunk);
+        conv1x1_wgrad_stream_kernel<bf16_t><<<ns, 512, 0, gmk_stream(stream)>>>((const bf16_t*)dy, dy_cstride, (const bf16_t*)src0, (const bf16_t*)src1, slab, (int)npix, (int)chunk);
     return ns;
 }

@@ -31,6 +31,7 @@
 // weight tiles are already in flight during the epilogue, which runs straight from the accumulators (same
 // D[channel][pixel] orientation + v_permlane32_swap widening as conv_igemm_dma_kernel).
 #include "gmk_common.h"
+#include "conv_plan.h"
 
 
 namespace {
@@ -1848,8 +1849,7 @@ int gmk_halo_geometry(int B, int H, int W, int c0, int c1, int w_rows, int cout,
     const int64_t Msrc = upsample ? M / 4 : M;
     const int64_t nb0 = Msrc * c0 * 2, nb1 = Msrc * c1 * 2;
     const int64_t nbw = (int64_t)9 * w_rows * (c0 + c1) * 2, nbo = M * out_cstride * 2;
-    const int64_t lim = 0xFFFF0000ll;     // below (kBadPix * bytes-per-pixel) mod 2^32 for pixels of up to 4 KiB
-    if (nb0 >= lim || nb1 >= lim || nbw >= lim || nbo >= lim || M >= 0x00FFFFFF || c0 > 2048 || c1 > 2048) return 0;
+    if (!gmk_fits32(nb0) || !gmk_fits32(nb1) || !gmk_fits32(nbw) || !gmk_fits32(nbo) || M >= 0x00FFFFFF || c0 > 2048 || c1 > 2048) return 0;
     const int64_t ntiles = (rows_total + R - 1) / R;
     if (ntiles < min_tiles) return 0;                         // not enough tiles to fill the chip: im2col kernels
     if (fused_gn && (upsample || R > H)) return 0;
@@ -1861,18 +1861,31 @@ int gmk_halo_geometry(int B, int H, int W, int c0, int c1, int w_rows, int cout,
     return 1;
 }
 
+// Tile schedule of the wave-specialised kernel over G = min(ntiles, cu_limit) workgroups: tiles [0, nfull) run as whole jobs, the rest as nhalf
+// half-channel jobs.  A last round of at most G / 2 tiles runs as twice as many half jobs - not for variant 4 of the plain launch (its vmcnt
+// waits count 4 weight DMAs per step); variant 6 is the A/B switch.  Small problems (round 4: the reference's own sampler sizes, 25 images
+// in `evaluate`, diffusion_model.py:98-104): with at most half as many tiles as CUs EVERY tile runs as two half jobs on two CUs - the launch
+// is one tile time long either way, and a half job's K-step carries half the MFMA work.  GMK_DEV_VARIANT=8 keeps whole jobs (A/B).
+void gmk_halo_schedule(int64_t ntiles, int cu_limit, int variant, bool fold, int* grid_x, int* nfull, int* nhalf) {
+    const bool no_tail = variant == 6 || (variant == 4 && !fold), no_all_half = no_tail || variant == 8;
+    const int G = (int)(ntiles < cu_limit ? ntiles : cu_limit), rem = (int)(ntiles % G);
+    *grid_x = G; *nfull = (int)ntiles; *nhalf = 0;
+    if (ntiles > G && rem > 0 && 2 * rem <= G && !no_tail) { *nfull = (int)ntiles - rem; *nhalf = 2 * rem; }
+    else if (2 * ntiles <= cu_limit && !no_all_half) { *nfull = 0; *nhalf = 2 * (int)ntiles; *grid_x = *nhalf; }
+}
+
 // Returns 1 (8-compute-wave kernel) or 2 (wave-specialised kernel) if a halo kernel was launched, 0 if the problem is not eligible (caller falls back), <0 / >0 on error.
 int gmk_conv3x3_halo_try(const void* src0, const void* src1, int c0, int c1, int B, int H, int W, const void* w, int w_rows,
                          int n0, int cout, const float* bias, const float* emb, int emb_stride, const void* residual,
                          void* out, int out_cstride, int min_tiles, int upsample, float* stats, int64_t stats_bytes,
-                         const float* gn_scale, const float* gn_shift, int gn_stride, int dtype, hipStream_t stream) {
+                         const float* gn_scale, const float* gn_shift, int gn_stride, int dtype, void* stream) {
     HaloGeometry g;
     if (!gmk_halo_geometry(B, H, W, c0, c1, w_rows, cout, out_cstride, min_tiles, upsample, gn_scale != nullptr, &g)) return 0;
     if (gn_scale && (!gn_shift || gn_stride < c0 + c1)) return 0;
     const int R = g.R, TP = g.TP;
     const int64_t rows_total = g.rows_total, M = g.M, ntiles = g.ntiles;
     const int64_t nb0 = g.nb0, nb1 = g.nb1, nbw = g.nbw, nbo = g.nbo;
-    HaloParams p;
+    HaloParams p = {};
     p.src0 = src0; p.src1 = src1; p.c0 = c0; p.c1 = c1; p.ktot = c0 + c1;
     p.shift = upsample ? 1 : 0; p.pmask = upsample == 2 ? 1 : 0;      // upsample: 1 nearest x2, 2 zero-stuffed x2 (transposed conv)
     p.B = B; p.H = H; p.W = W; p.WE = W + 1; p.R = R; p.TP = TP; p.ntiles = (int)ntiles; p.rows_total = (int)rows_total;
@@ -1885,18 +1898,9 @@ int gmk_conv3x3_halo_try(const void* src0, const void* src1, int c0, int c1, int
     p.variant = gmk_kernel_choice(3, "GMK_DEV_VARIANT") & 0xFF;      // code variant (A/B switches, see below)
     if (stats && cout == out_cstride && stats_bytes >= ntiles * 8 * 2 * (int64_t)(out_cstride / 4) * 2 * 4 && H * W >= 32) p.stats = stats;
     p.inv_hp2 = 1.0f / (float)(H + 2); p.inv_h = 1.0f / (float)H; p.inv_we = 1.0f / (float)(W + 1); p.inv_w = 1.0f / (float)W;
-    const int ncu = gmk_cu_limit();
-    dim3 grid((unsigned)(ntiles < ncu ? ntiles : ncu), cout / 128);
-    p.nfull = (int)ntiles; p.nhalf = 0;
-    {   // tail balancing of the wave-specialised kernel: a last round of at most G/2 tiles runs as twice as many half jobs
-        const int G = (int)grid.x, rem = (int)(ntiles % G);
-        // not for variant 4 (its vmcnt waits count 4 weight DMAs per step); variant 6 is the A/B switch
-        if (ntiles > G && rem > 0 && 2 * rem <= G && p.variant != 4 && p.variant != 6) { p.nfull = (int)ntiles - rem; p.nhalf = 2 * rem; }
-        // Small problems (round 4: the reference's own sampler sizes, 25 images in `evaluate`, diffusion_model.py:98-104): with at most
-        // half as many tiles as CUs EVERY tile runs as two half jobs on two CUs - the launch is one tile time long either way, and a
-        // half job's K-step carries half the MFMA work.  GMK_DEV_VARIANT=8 keeps whole jobs (A/B).
-        else if (2 * ntiles <= ncu && p.variant != 4 && p.variant != 6 && p.variant != 8) { p.nfull = 0; p.nhalf = 2 * (int)ntiles; grid.x = (unsigned)p.nhalf; }
-    }
+    int grid_x;
+    gmk_halo_schedule(ntiles, gmk_cu_limit(), p.variant, false, &grid_x, &p.nfull, &p.nhalf);
+    const dim3 grid((unsigned)grid_x, cout / 128);
     const bool use16 = p.variant != 32 && p.variant != 1 && p.variant != 3;      // (variants 1 / 3: the 8-compute-wave kernel)
     // MFMA shape of the consumers: bit-identical results either way; v_mfma_f32_16x16x32 measured +2 ... +4 % at K = 2304 and at
     // 64- / 32- / 14-pixel rows in round 2.  At 28 x 28 with K = 1152 it had measured -2 % with bf16 operands and kept the 32 x 32 x 16 form
@@ -1911,21 +1915,21 @@ int gmk_conv3x3_halo_try(const void* src0, const void* src1, int c0, int c1, int
     auto launch = [&](auto tag) {
         typedef decltype(tag) T;
         if (kind == 1) {
-            if (use16) conv3x3_halo_ws_kernel<T, true, 16, true><<<grid, 512, 0, stream>>>(p);
-            else conv3x3_halo_ws_kernel<T, true, 32, true><<<grid, 512, 0, stream>>>(p);
-        } else if (kind == 2) conv3x3_halo_ws_kernel<T, false><<<grid, 512, 0, stream>>>(p);
+            if (use16) conv3x3_halo_ws_kernel<T, true, 16, true><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+            else conv3x3_halo_ws_kernel<T, true, 32, true><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+        } else if (kind == 2) conv3x3_halo_ws_kernel<T, false><<<grid, 512, 0, gmk_stream(stream)>>>(p);
         else if (kind == 3) {
             // four-slot weight ring (6-piece halos) where a tile fits 384 slots and there is no residual: 32 x 32, 16 x 16, 14 x 14 (GMK_DEV_VARIANT=13: the A/B switch)
             const bool ring4 = use16 && !residual && g.slots <= 384 && p.variant != 13;
             if (use16 && g_stamps && g_stamp_bytes >= (int64_t)grid.x * 512) {
                 p.stamps = g_stamps;
-                if (ring4) conv3x3_halo_ws_kernel<T, true, 16, false, false, true, false, 0, true><<<grid, 512, 0, stream>>>(p);
-                else conv3x3_halo_ws_kernel<T, true, 16, false, false, true><<<grid, 512, 0, stream>>>(p);
-            } else if (ring4) conv3x3_halo_ws_kernel<T, true, 16, false, false, false, false, 0, true><<<grid, 512, 0, stream>>>(p);
-            else if (use16 && residual) conv3x3_halo_ws_kernel<T, true, 16, false, false, false, false, 1><<<grid, 512, 0, stream>>>(p);
-            else if (use16) conv3x3_halo_ws_kernel<T, true, 16, false, false, false, false, 0><<<grid, 512, 0, stream>>>(p);
-            else conv3x3_halo_ws_kernel<T, true, 32><<<grid, 512, 0, stream>>>(p);
-        } else conv3x3_halo_kernel<T><<<grid, 512, 0, stream>>>(p);
+                if (ring4) conv3x3_halo_ws_kernel<T, true, 16, false, false, true, false, 0, true><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+                else conv3x3_halo_ws_kernel<T, true, 16, false, false, true><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+            } else if (ring4) conv3x3_halo_ws_kernel<T, true, 16, false, false, false, false, 0, true><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+            else if (use16 && residual) conv3x3_halo_ws_kernel<T, true, 16, false, false, false, false, 1><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+            else if (use16) conv3x3_halo_ws_kernel<T, true, 16, false, false, false, false, 0><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+            else conv3x3_halo_ws_kernel<T, true, 32><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+        } else conv3x3_halo_kernel<T><<<grid, 512, 0, gmk_stream(stream)>>>(p);
     };
     if (dtype == GMK_F16) launch(f16_t{});
     else launch(bf16_t{});
@@ -1936,12 +1940,11 @@ int gmk_conv3x3_halo_try(const void* src0, const void* src1, int c0, int c1, int
 static int skipfold_geometry(int B, int H, int W, int c0, int cs, int cout, int w_rows, int out_cstride, int min_tiles, HaloGeometry* g) {
     if (c0 != 128 || cs != 128 || cout != 128) return 0;          // two halo phases + eight 32-channel sub-phases: the C = 128 nets
     if (!gmk_halo_geometry(B, H, W, c0, 0, w_rows, cout, out_cstride, min_tiles, 0, 0, g)) return 0;
-    return (int64_t)g->M * cs * 2 < 0xFFFF0000ll;
+    return gmk_fits32((int64_t)g->M * cs * 2);
 }
 
 extern "C" int gmk_conv3x3_skipfold_ok(int B, int H, int W, int c0, int cs, int cout) {
-    const int force = gmk_kernel_choice(0, "GMK_CONV_KERNEL");
-    if (force != 0 && force != 3) return 0;
+    if (!gmk_halo_family_allowed(gmk_kernel_choice(0, "GMK_CONV_KERNEL"))) return 0;
     HaloGeometry g;
     return skipfold_geometry(B, H, W, c0, cs, cout, cout, cout, 1, &g);
 }
@@ -1969,14 +1972,9 @@ extern "C" int gmk_conv3x3_skipfold(const void* src, int c0, int B, int H, int W
     p.inv_hp2 = 1.0f / (float)(H + 2); p.inv_h = 1.0f / (float)H; p.inv_we = 1.0f / (float)(W + 1); p.inv_w = 1.0f / (float)W;
     p.sk0 = sk0; p.sk1 = sk1; p.wsk = wsk; p.bias2 = bias_sk; p.cs = cs; p.sk_ktot = 2 * cs; p.nsk0 = nsk0;
     p.nbs = (unsigned)((int64_t)g.M * cs * 2); p.nbws = (unsigned)((int64_t)wsk_rows * 2 * cs * 2);
-    const int ncu = gmk_cu_limit();
-    dim3 grid((unsigned)(g.ntiles < ncu ? g.ntiles : ncu), cout / 128);
-    p.nfull = (int)g.ntiles; p.nhalf = 0;
-    {   // half jobs as in gmk_conv3x3_halo_try: the last partly filled round, or every tile of a small problem
-        const int G = (int)grid.x, rem = (int)(g.ntiles % G);
-        if (g.ntiles > G && rem > 0 && 2 * rem <= G && p.variant != 6) { p.nfull = (int)g.ntiles - rem; p.nhalf = 2 * rem; }
-        else if (2 * g.ntiles <= ncu && p.variant != 6 && p.variant != 8) { p.nfull = 0; p.nhalf = 2 * (int)g.ntiles; grid.x = (unsigned)p.nhalf; }
-    }
+    int grid_x;
+    gmk_halo_schedule(g.ntiles, gmk_cu_limit(), p.variant, true, &grid_x, &p.nfull, &p.nhalf);
+    const dim3 grid((unsigned)grid_x, cout / 128);
     // merged dense sub-phases (9 barriers per phase) where a tile's halo fits 6 of the 7 fill pieces: 32 x 32, 16 x 16 (GMK_DEV_VARIANT=12: the A/B switch)
     const bool merge = g.slots <= 384 && p.variant != 12;
     const bool stamp = g_stamps && g_stamp_bytes >= (int64_t)grid.x * 512;      // development: the stamped instantiations (tools/step_stamps.py)

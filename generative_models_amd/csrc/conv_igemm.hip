@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "gmk_common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -952,11 +953,15 @@ __global__ __launch_bounds__(64 * NG) void wgrad_reduce_kernel(const float* __re
     }
 }
 
-static void launch_wgrad_reduce(const float* slab, float* dw, int nsplit, int taps, int cout, int ktot, hipStream_t stream) {
+// checks the slab launch `what`, then folds the nsplit slabs into dw
+static int wgrad_reduce(const char* what, const float* slab, float* dw, int nsplit, int taps, int cout, int ktot, void* stream) {
+    const int rc = gmk_check_launch(what);
+    if (rc) return rc;
     const int64_t per = (int64_t)taps * cout * ktot;
     const int blocks = (int)((per / 4 + 63) / 64);
-    if (blocks < 512 && nsplit >= 64) wgrad_reduce_kernel<16><<<blocks, 1024, 0, stream>>>(slab, dw, nsplit, taps, cout, ktot);
-    else wgrad_reduce_kernel<4><<<blocks, 256, 0, stream>>>(slab, dw, nsplit, taps, cout, ktot);
+    if (blocks < 512 && nsplit >= 64) wgrad_reduce_kernel<16><<<blocks, 1024, 0, gmk_stream(stream)>>>(slab, dw, nsplit, taps, cout, ktot);
+    else wgrad_reduce_kernel<4><<<blocks, 256, 0, gmk_stream(stream)>>>(slab, dw, nsplit, taps, cout, ktot);
+    return gmk_check_launch("gmk_conv_wgrad(reduce)");
 }
 
 // One element of an fp32 pack.  Plain: the fp32 value at position `pos`.  Split (the fp32 mode's default since round 6, see split_bf16): every
@@ -1037,7 +1042,7 @@ extern "C" int64_t gmk_conv_wgrad_workspace_bytes(int64_t n_pixels, int taps, in
     int chunk;
     int64_t ns = wgrad_nsplit(n_pixels, taps, cout, ktot, &chunk);
     if (taps == 9) {
-        const int64_t ns2 = gmk_wgrad_slots_nsplit(cout, ktot);
+        const int64_t ns2 = gmk_wgrad_slots_nsplit(cout, ktot, gmk_cu_limit());
         if (ns2 > ns) ns = ns2;
     }
     return ns * taps * cout * ktot * 4;
@@ -1046,24 +1051,15 @@ extern "C" int64_t gmk_conv_wgrad_workspace_bytes(int64_t n_pixels, int taps, in
 extern "C" int gmk_pack_conv_weight(const float* w, void* w_fwd, void* w_dgrad, int cout, int cin, int ksize, int dtype,
                                     void* stream) {
     GMK_REQUIRE(w && (w_fwd || w_dgrad), "gmk_pack_conv_weight: null pointer");
-    if (dtype == GMK_F16) {      // an fp16 pack: the forward operand of the 16-bit mode
-        GMK_REQUIRE(cout > 0 && cin > 0 && (ksize == 1 || ksize == 3), "gmk_pack_conv_weight: bad shape");
-        const int64_t n16 = (int64_t)cout * cin * ksize * ksize;
-        pack_weight_kernel<f16_t><<<(int)((n16 + 255) / 256), 256, 0, gmk_stream(stream)>>>(w, (f16_t*)w_fwd, (f16_t*)w_dgrad, cout, cin, ksize * ksize);
-        return gmk_check_launch("gmk_pack_conv_weight");
-    }
     GMK_REQUIRE(cout > 0 && cin > 0 && (ksize == 1 || ksize == 3), "gmk_pack_conv_weight: bad shape");
     const int taps = ksize * ksize;
-    const int64_t n = (int64_t)cout * cin * taps;
-    const int blocks = (int)((n + 255) / 256);
-    if (dtype == GMK_BF16)
-        pack_weight_kernel<bf16_t><<<blocks, 256, 0, gmk_stream(stream)>>>(w, (bf16_t*)w_fwd, (bf16_t*)w_dgrad, cout, cin,
-                                                                           taps);
-    else if (dtype == GMK_F32)
-        pack_weight_kernel<float><<<blocks, 256, 0, gmk_stream(stream)>>>(w, (float*)w_fwd, (float*)w_dgrad, cout, cin,
-                                                                         taps, fp32_split() && cin % 8 == 0 && cout % 8 == 0);
-    else
-        GMK_REQUIRE(false, "gmk_pack_conv_weight: bad dtype %d", dtype);
+    const int blocks = (int)(((int64_t)cout * cin * taps + 255) / 256);
+    const bool known = gmk_with_type<float, bf16_t, f16_t>(dtype, [&](auto tag) {      // (an fp16 pack: the forward operand of the 16-bit mode)
+        typedef typename decltype(tag)::type T;
+        const bool split = std::is_same<T, float>::value && fp32_split() && cin % 8 == 0 && cout % 8 == 0;
+        pack_weight_kernel<T><<<blocks, 256, 0, gmk_stream(stream)>>>(w, (T*)w_fwd, (T*)w_dgrad, cout, cin, taps, split);
+    });
+    GMK_REQUIRE(known, "gmk_pack_conv_weight: bad dtype %d", dtype);
     return gmk_check_launch("gmk_pack_conv_weight");
 }
 
@@ -1072,9 +1068,8 @@ extern "C" int gmk_pack_conv_weights_multi(const float* arena, void* packs, int 
                                            void* stream) {
     GMK_REQUIRE(arena && packs && w_off && pack_off && cout && cin && ksize, "gmk_pack_conv_weights_multi: null pointer");
     GMK_REQUIRE(count > 0 && count <= 40, "gmk_pack_conv_weights_multi: 1..40 tensors per call, got %d", count);
-    PackTable t;
+    PackTable t = {};
     t.n = count;
-    t.fwd_f16 = 0;
     int nmax = 0;
     for (int e = 0; e < count; ++e) {
         if (fwd_f16 && fwd_f16[e]) {
@@ -1090,10 +1085,72 @@ extern "C" int gmk_pack_conv_weights_multi(const float* arena, void* packs, int 
     int bx = (nmax + 255) / 256;
     if (bx > 256) bx = 256;
     const dim3 grid(bx, count);
-    if (dtype == GMK_BF16) pack_weights_multi_kernel<bf16_t><<<grid, 256, 0, gmk_stream(stream)>>>(arena, (bf16_t*)packs, t);
-    else if (dtype == GMK_F32) pack_weights_multi_kernel<float><<<grid, 256, 0, gmk_stream(stream)>>>(arena, (float*)packs, t, fp32_split());
-    else GMK_REQUIRE(false, "gmk_pack_conv_weights_multi: bad dtype %d", dtype);
+    const bool known = gmk_with_type<float, bf16_t>(dtype, [&](auto tag) {      // (the order of the list fixes kernel addresses: see gmk_with_type)
+        typedef typename decltype(tag)::type T;
+        pack_weights_multi_kernel<T><<<grid, 256, 0, gmk_stream(stream)>>>(arena, (T*)packs, t, std::is_same<T, float>::value && fp32_split());
+    });
+    GMK_REQUIRE(known, "gmk_pack_conv_weights_multi: bad dtype %d", dtype);
     return gmk_check_launch("gmk_pack_conv_weights_multi");
+}
+
+// ---- the route of a gmk_conv_igemm call (conv_plan.h) ------------------------------------------------------------------------------------
+// kernel choice: 0 = automatic, 1 = register-staged 128x128, 2 = LDS-DMA im2col 256x128, 3 = LDS halo (3x3 s1 bf16)
+ConvRoutePlan gmk_conv_route(const ConvCall& c, int force, bool subpixel_on) {
+    ConvRoutePlan r = {};
+    // the transposed form (data gradient of the stride-2 conv) is the plain 3x3 conv of the zero-stuffed gradient: on the halo
+    // kernel 3/4 of the resident pixels are zeros, but it still beats the im2col gather by 1.7x (215 vs 360 us at 28x28)
+    const bool stuffed = r.stuffed = c.mode == GMK_CONV_TRANSPOSED2 && !((c.ho | c.wo) & 1);
+    // The transposed form in its sub-pixel shape (conv_subpixel.hip, round 5): output parities meet 1 / 2 / 2 / 4 of the 9 taps over the gradient's
+    // own grid, the halo of a low-resolution tile stays in LDS for all four parities - the zero-stuffed form below multiplies 27 of 36 tap-images by zero.
+    if (stuffed && force == 0 && gmk_is16(c.dtype) && c.ksize == 3 && c.c0 == 128 && c.c1 == 0 && c.cout == 128 && !c.emb && !c.gn_scale && !c.gn_stats &&
+        !c.out2 && c.ho == 2 * c.hs && c.wo == 2 * c.ws && c.n0 >= 0 && c.n0 + c.cout <= c.w_rows &&
+        gmk_subpixel_takes(force, subpixel_on, c.B, c.hs, c.ws, c.c0, c.cout, c.w_rows, 9, c.out_cstride, c.dtype)) {
+        r.route = GMK_ROUTE_SUBPIXEL;
+        return r;
+    }
+    // Tile-count floor of the halo kernel: NONE for the plain and the nearest-x2 forms since round 4 - the reference's own sampler sizes
+    // (25 images in `evaluate`, diffusion_model.py:98-104) put the 14 x 14 / 7 x 7 levels at 20 / 5 tiles, where the register-staged im2col
+    // kernel took 32 us a launch against the halo kernel's 19 (as half jobs on twice the CUs): B = 25 DDIM step 1.25 -> 1.15 ms, B = 8
+    // 1.46 -> 1.16 ms.  The zero-stuffed transposed form keeps 32 (below it the four parity phases win).
+    if (gmk_halo_family_allowed(force) && gmk_is16(c.dtype) && (c.mode == GMK_CONV_NORMAL || c.mode == GMK_CONV_UPSAMPLE2 || stuffed) && c.ksize == 3) {
+        r.halo_min_tiles = (force == 3 || !stuffed) ? 1 : 32;
+        r.halo_upsample = stuffed ? 2 : c.mode == GMK_CONV_UPSAMPLE2;
+        // what gmk_conv3x3_halo_try launches by: the halo geometry, and whole GroupNorm tables where it is to apply them
+        if (gmk_halo_geometry(c.B, c.ho, c.wo, c.c0, c.c1, c.w_rows, c.cout, c.out_cstride, r.halo_min_tiles, r.halo_upsample, c.gn_scale, nullptr) &&
+            (!c.gn_scale || (c.gn_shift && c.gn_stride >= c.c0 + c.c1))) {
+            r.route = GMK_ROUTE_HALO;
+            return r;
+        }
+    }
+    // LDS-DMA kernel: buffers addressable with 32-bit offsets
+    const int es = gmk_esize(c.dtype);
+    const int64_t M = (int64_t)c.B * c.ho * c.wo, Msrc = (int64_t)c.B * c.hs * c.ws;
+    r.nb0 = Msrc * c.c0 * es; r.nb1 = Msrc * c.c1 * es;
+    r.nbw = (int64_t)c.ksize * c.ksize * c.w_rows * (c.c0 + c.c1) * es; r.nbo = M * c.out_cstride * es;
+    const bool fits = gmk_fits32(r.nb0) && gmk_fits32(r.nb1) && gmk_fits32(r.nbw) && gmk_fits32(r.nbo) && Msrc < 0x00FFFFFF &&
+                      (int64_t)c.c0 * es <= 4096 && (int64_t)c.c1 * es <= 4096;
+    // Where the halo kernel does not take the transposed form (fp32, fewer than 32 tiles, GMK_CONV_KERNEL=2): four output-parity phases on
+    // the LDS-DMA kernel, each a 1- / 2- / 2- / 4-tap convolution over the gradient's own grid with a stride-2 scatter of its rows
+    // (make_phase_gather): 9 / 4 tap-images of MFMA work where the masked im2col gather does 9.  At the train step's sizes the zero-stuffed
+    // halo form stays in front (536 vs 565 us at 16x16 -> 32x32, B = 2048, with the residual: each phase launch walks every DRAM page
+    // of the output and of the residual for a quarter of their bytes; without a residual the phases win, 393 vs 462 us; docs/EXPERIMENTS.md 7b.9).
+    if (stuffed && force != 1 && !c.out2 && !c.gn_scale && !c.gn_stats && fits) r.route = GMK_ROUTE_PHASES;
+    else if (c.gn_scale) r.route = GMK_ROUTE_NEEDS_HALO;
+    // problems with at least ~2 tiles of 256 pixels per CU
+    else if (fits && (force == 2 || (force != 1 && (int)M >= 256 * 512))) r.route = GMK_ROUTE_DMA;
+    else r.route = c.out2 ? GMK_ROUTE_TWO_CALLS : GMK_ROUTE_REG;      // the pair form lives in the LDS-DMA kernel only
+    return r;
+}
+
+// conv_igemm_dma_kernel over min(tiles of 256 rows, CU limit) persistent workgroups
+static void launch_conv_dma(ConvParams p, const ConvRoutePlan& r, int cout, int dtype, void* stream) {
+    p.nb0 = (unsigned)r.nb0; p.nb1 = (unsigned)r.nb1; p.nbw = (unsigned)r.nbw; p.nbo = (unsigned)r.nbo;
+    const int ncu = gmk_cu_limit(), ntiles = (p.M + 255) / 256;
+    const dim3 grid(ntiles < ncu ? ntiles : ncu, cout / kBN);
+    if (dtype == GMK_BF16) conv_igemm_dma_kernel<bf16_t><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+    else if (dtype == GMK_F16) conv_igemm_dma_kernel<f16_t><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+    else if (fp32_split()) conv_igemm_dma_kernel<float, true><<<grid, 512, 0, gmk_stream(stream)>>>(p);
+    else conv_igemm_dma_kernel<float><<<grid, 512, 0, gmk_stream(stream)>>>(p);
 }
 
 static int conv_igemm_impl(const void* src0, const void* src1, int c0, int c1, int B, int hs, int ws, int ho, int wo,
@@ -1110,95 +1167,47 @@ static int conv_igemm_impl(const void* src0, const void* src1, int c0, int c1, i
                 "gmk_conv_igemm: bad output channels n0=%d cout=%d w_rows=%d cstride=%d", n0, cout, w_rows, out_cstride);
     GMK_REQUIRE(B > 0 && (int64_t)B * ho * wo < (1ll << 31) - 256 && (int64_t)B * hs * ws < (1ll << 31),
                 "gmk_conv_igemm: problem too large for 32-bit pixel indices");
-    ConvParams p;
-    GMK_REQUIRE(make_gather(mode, ksize, hs, ws, ho, wo, &p.g), "gmk_conv_igemm: mode %d inconsistent with %dx%d -> %dx%d",
-                mode, hs, ws, ho, wo);
+    ConvParams p = {};
+    GMK_REQUIRE(make_gather(mode, ksize, hs, ws, ho, wo, &p.g), "gmk_conv_igemm: mode %d inconsistent with %dx%d -> %dx%d", mode, hs, ws, ho, wo);
     GMK_REQUIRE(!emb || emb_stride >= cout, "gmk_conv_igemm: emb_stride");
     p.src0 = src0; p.src1 = src1; p.c0 = c0; p.c1 = c1; p.ktot = c0 + c1;
     p.w = w; p.w_tap_stride = (int64_t)w_rows * (c0 + c1); p.n0 = n0;
-    p.bias = bias; p.emb = emb; p.emb_stride = emb_stride; p.residual = residual; p.out = out; p.out2 = nullptr;
+    p.bias = bias; p.emb = emb; p.emb_stride = emb_stride; p.residual = residual; p.out = out; p.out2 = out2;
     p.out_cstride = out_cstride; p.M = B * ho * wo;
-    // kernel choice: 0 = automatic, 1 = register-staged 128x128, 2 = LDS-DMA im2col 256x128, 3 = LDS halo (3x3 s1 bf16)
-    const int force = gmk_kernel_choice(0, "GMK_CONV_KERNEL");
-    const int es = gmk_esize(dtype);
-    // kBadOff and (kBadPix * bytes-per-pixel) mod 2^32 (>= 0xFFFFF000 for pixels of up to 4 KiB) must lie beyond every buffer
-    const int64_t lim = 0xFFFF0000ll;
-    const int64_t nb0 = (int64_t)B * hs * ws * c0 * es, nb1 = (int64_t)B * hs * ws * c1 * es;
-    const int64_t nbw = (int64_t)ksize * ksize * w_rows * (c0 + c1) * es;
-    // Tile-count floor of the halo kernel: NONE for the plain and the nearest-x2 forms since round 4 - the reference's own sampler sizes
-    // (25 images in `evaluate`, diffusion_model.py:98-104) put the 14 x 14 / 7 x 7 levels at 20 / 5 tiles, where the register-staged im2col
-    // kernel took 32 us a launch against the halo kernel's 19 (as half jobs on twice the CUs): B = 25 DDIM step 1.25 -> 1.15 ms, B = 8
-    // 1.46 -> 1.16 ms.  The zero-stuffed transposed form keeps 32 (below it the four parity phases win).
-    // the transposed form (data gradient of the stride-2 conv) is the plain 3x3 conv of the zero-stuffed gradient: on the halo
-    // kernel 3/4 of the resident pixels are zeros, but it still beats the im2col gather by 1.7x (215 vs 360 us at 28x28)
-    const bool stuffed = mode == GMK_CONV_TRANSPOSED2 && !((ho | wo) & 1);
-    // The transposed form in its sub-pixel shape (conv_subpixel.hip, round 5): output parities meet 1 / 2 / 2 / 4 of the 9 taps over the gradient's
-    // own grid, the halo of a low-resolution tile stays in LDS for all four parities - the zero-stuffed form below multiplies 27 of 36 tap-images by zero.
-    if (stuffed && force == 0 && gmk_is16(dtype) && ksize == 3 && c0 == 128 && c1 == 0 && cout == 128 && !emb && !gn_scale && !gn_stats && !out2 &&
-        ho == 2 * hs && wo == 2 * ws && n0 >= 0 && n0 + cout <= w_rows && gmk_conv_subpixel_takes(B, hs, ws, c0, cout, w_rows, 9, out_cstride, dtype))
+    const ConvCall call = {c0, c1, B, hs, ws, ho, wo, ksize, mode, w_rows, n0, cout, out_cstride, dtype, emb != nullptr, out2 != nullptr, gn_stats != nullptr,
+                           gn_scale != nullptr, gn_shift != nullptr, gn_stride};
+    const ConvRoutePlan r = gmk_conv_route(call, gmk_kernel_choice(0, "GMK_CONV_KERNEL"), gmk_subpixel_enabled());
+    if (r.route == GMK_ROUTE_SUBPIXEL)
         return gmk_conv_subpixel(src0, B, hs, ws, c0, w, w_rows, n0, cout, GMK_SUBPIXEL_TRANSPOSED, bias, residual, out, out_cstride, dtype, stream);
-    if ((force == 0 || force == 3) && gmk_is16(dtype) && (mode == GMK_CONV_NORMAL || mode == GMK_CONV_UPSAMPLE2 || stuffed) && ksize == 3) {
-        const int rc = gmk_conv3x3_halo_try(src0, src1, c0, c1, B, ho, wo, w, w_rows, n0, cout, bias, emb, emb_stride, residual,
-                                            out, out_cstride, (force == 3 || !stuffed) ? 1 : 32, stuffed ? 2 : mode == GMK_CONV_UPSAMPLE2, gn_stats,
-                                            gn_stats_bytes, gn_scale, gn_shift, gn_stride, dtype, gmk_stream(stream));
-        if (rc == 1 || rc == 2) {
-            gmk_note_kernel(stuffed ? 5 : rc == 2 ? 4 : 3);       // 5: a halo kernel on the zero-stuffed source (transposed conv)
-            return gmk_check_launch("gmk_conv_igemm(halo)");
-        }
+    if (r.route == GMK_ROUTE_HALO) {
+        const int rc = gmk_conv3x3_halo_try(src0, src1, c0, c1, B, ho, wo, w, w_rows, n0, cout, bias, emb, emb_stride, residual, out, out_cstride,
+                                            r.halo_min_tiles, r.halo_upsample, gn_stats, gn_stats_bytes, gn_scale, gn_shift, gn_stride, dtype, stream);
+        gmk_note_kernel(r.stuffed ? 5 : rc == 2 ? 4 : 3);       // 5: a halo kernel on the zero-stuffed source (transposed conv)
+        return gmk_check_launch("gmk_conv_igemm(halo)");
     }
-    // Where the halo kernel does not take the transposed form (fp32, fewer than 32 tiles, GMK_CONV_KERNEL=2): four output-parity phases on
-    // the LDS-DMA kernel, each a 1- / 2- / 2- / 4-tap convolution over the gradient's own grid with a stride-2 scatter of its rows
-    // (make_phase_gather): 9 / 4 tap-images of MFMA work where the masked im2col gather does 9.  At the train step's sizes the zero-stuffed
-    // halo form stays in front (536 vs 565 us at 16x16 -> 32x32, B = 2048, with the residual: each phase launch walks every DRAM page
-    // of the output and of the residual for a quarter of their bytes; without a residual the phases win, 393 vs 462 us; docs/EXPERIMENTS.md 7b.9).
-    if (stuffed && force != 1 && !out2 && !gn_scale && !gn_stats) {
-        const int64_t nbo = (int64_t)B * ho * wo * out_cstride * es;
-        if (nb0 < lim && nb1 < lim && nbw < lim && nbo < lim && (int64_t)B * hs * ws < 0x00FFFFFF && (int64_t)c0 * es <= 4096 &&
-            (int64_t)c1 * es <= 4096) {
-            gmk_note_kernel(6);
-            const int ncu = gmk_cu_limit();
-            for (int ph = 0; ph < 4; ++ph) {
-                ConvParams q = p;
-                make_phase_gather(ph >> 1, ph & 1, hs, ws, ho, wo, &q.g);
-                q.M = B * hs * ws;
-                q.nb0 = (unsigned)nb0; q.nb1 = (unsigned)nb1; q.nbw = (unsigned)nbw; q.nbo = (unsigned)nbo;
-                const int ntiles = (q.M + 255) / 256;
-                dim3 grid(ntiles < ncu ? ntiles : ncu, cout / kBN);
-                if (dtype == GMK_BF16) conv_igemm_dma_kernel<bf16_t><<<grid, 512, 0, gmk_stream(stream)>>>(q);
-                else if (dtype == GMK_F16) conv_igemm_dma_kernel<f16_t><<<grid, 512, 0, gmk_stream(stream)>>>(q);
-                else if (fp32_split()) conv_igemm_dma_kernel<float, true><<<grid, 512, 0, gmk_stream(stream)>>>(q);
-                else conv_igemm_dma_kernel<float><<<grid, 512, 0, gmk_stream(stream)>>>(q);
-            }
-            return gmk_check_launch("gmk_conv_igemm(stride-2 dgrad phases)");
+    if (r.route == GMK_ROUTE_PHASES) {
+        gmk_note_kernel(6);
+        for (int ph = 0; ph < 4; ++ph) {
+            ConvParams q = p;
+            make_phase_gather(ph >> 1, ph & 1, hs, ws, ho, wo, &q.g);
+            q.M = B * hs * ws;
+            launch_conv_dma(q, r, cout, dtype, stream);
         }
+        return gmk_check_launch("gmk_conv_igemm(stride-2 dgrad phases)");
     }
-    GMK_REQUIRE(!gn_scale, "gmk_conv_igemm: the fused GroupNorm-apply needs the 3x3 halo kernel (16-bit, plain 3x3, a tile within two samples): "
-                           "ask gmk_conv_gn_fusable first");
-    // LDS-DMA kernel: problems with at least ~2 tiles of 256 pixels per CU, buffers addressable with 32-bit offsets
-    const int64_t nbo = (int64_t)p.M * out_cstride * es;
-    const bool fits = nb0 < lim && nb1 < lim && nbw < lim && nbo < lim && (int64_t)B * hs * ws < 0x00FFFFFF &&
-                      (int64_t)c0 * es <= 4096 && (int64_t)c1 * es <= 4096;
-    const bool dma = fits && (force == 2 || (force != 1 && p.M >= 256 * 512));
-    if (out2 && !dma) {        // the pair form lives in the LDS-DMA kernel only: small problems run as two plain launches
+    GMK_REQUIRE(r.route != GMK_ROUTE_NEEDS_HALO, "gmk_conv_igemm: the fused GroupNorm-apply needs the 3x3 halo kernel (16-bit, plain 3x3, a tile within two samples): "
+                                                 "ask gmk_conv_gn_fusable first");
+    if (r.route == GMK_ROUTE_TWO_CALLS) {       // small problems run as two plain launches
         const int rc = conv_igemm_impl(src0, src1, c0, c1, B, hs, ws, ho, wo, ksize, mode, w, w_rows, n0, cout, bias, emb, emb_stride,
                                        residual, out, nullptr, out_cstride, nullptr, 0, nullptr, nullptr, 0, dtype, stream);
         if (rc) return rc;
         return conv_igemm_impl(src0, src1, c0, c1, B, hs, ws, ho, wo, ksize, mode, w, w_rows, n0 + cout, cout, bias, emb, emb_stride,
                                residual, out2, nullptr, out_cstride, nullptr, 0, nullptr, nullptr, 0, dtype, stream);
     }
-    p.out2 = out2;
-    gmk_note_kernel(dma ? 2 : 1);
-    if (dma) {
-        p.nb0 = (unsigned)nb0; p.nb1 = (unsigned)nb1; p.nbw = (unsigned)nbw; p.nbo = (unsigned)nbo;
-        const int ncu = gmk_cu_limit();
-        const int ntiles = (p.M + 255) / 256;
-        dim3 grid(ntiles < ncu ? ntiles : ncu, cout / kBN);
-        if (dtype == GMK_BF16) conv_igemm_dma_kernel<bf16_t><<<grid, 512, 0, gmk_stream(stream)>>>(p);
-        else if (dtype == GMK_F16) conv_igemm_dma_kernel<f16_t><<<grid, 512, 0, gmk_stream(stream)>>>(p);
-        else if (fp32_split()) conv_igemm_dma_kernel<float, true><<<grid, 512, 0, gmk_stream(stream)>>>(p);
-        else conv_igemm_dma_kernel<float><<<grid, 512, 0, gmk_stream(stream)>>>(p);
-    } else {
-        dim3 grid((p.M + kBM - 1) / kBM, cout / kBN);
+    gmk_note_kernel(r.route == GMK_ROUTE_DMA ? 2 : 1);
+    if (r.route == GMK_ROUTE_DMA) launch_conv_dma(p, r, cout, dtype, stream);
+    else {
+        const dim3 grid((p.M + kBM - 1) / kBM, cout / kBN);
         if (dtype == GMK_BF16) conv_igemm_kernel<bf16_t><<<grid, 256, 0, gmk_stream(stream)>>>(p);
         else if (dtype == GMK_F16) conv_igemm_kernel<f16_t><<<grid, 256, 0, gmk_stream(stream)>>>(p);
         else if (fp32_split()) conv_igemm_kernel<float, true><<<grid, 256, 0, gmk_stream(stream)>>>(p);
@@ -1222,7 +1231,7 @@ extern "C" int gmk_conv1x1_pair(const void* src, int c, int B, int H, int W, con
     GMK_REQUIRE(n0 >= 0 && n0 + 256 <= w_rows, "gmk_conv1x1_pair: rows n0 .. n0 + 255 outside the %d packed rows", w_rows);
     if (c == 128 && B > 0 && H > 0 && W > 0) {             // the streaming form for the train step's sizes (conv1x1_stream.hip)
         const size_t es = 2;
-        if (gmk_conv1x1_pair_stream_try(src, (int64_t)B * H * W, (const char*)w + (size_t)n0 * 128 * es, out_a, out_b, dtype, gmk_stream(stream))) {
+        if (gmk_conv1x1_pair_stream_try(src, (int64_t)B * H * W, (const char*)w + (size_t)n0 * 128 * es, out_a, out_b, dtype, stream)) {
             gmk_note_kernel(14);
             return gmk_check_launch("gmk_conv1x1_pair(stream)");
         }
@@ -1231,12 +1240,13 @@ extern "C" int gmk_conv1x1_pair(const void* src, int c, int B, int H, int W, con
                            out_a, out_b, 128, nullptr, 0, nullptr, nullptr, 0, dtype, stream);
 }
 
-// 1 if gmk_conv_igemm(ksize 3, GMK_CONV_NORMAL, bf16) of this shape runs on the halo kernel AND can apply a GroupNorm to its source
+// 1 if gmk_conv_igemm(ksize 3, GMK_CONV_NORMAL, 16-bit) of this shape runs on the halo kernel AND can apply a GroupNorm to its source: the
+// route of that very call (weights [9][cout][c0 + c1], dense output, tables of c0 + c1 columns)
 extern "C" int gmk_conv_gn_fusable(int B, int H, int W, int c0, int c1, int cout) {
-    const int force = gmk_kernel_choice(0, "GMK_CONV_KERNEL");
-    if (force != 0 && force != 3) return 0;
-    // the same rule gmk_conv_igemm applies when it hands the launch to the halo kernel (weights [9][cout][c0 + c1], dense output)
-    return gmk_halo_geometry(B, H, W, c0, c1, cout, cout, cout, 1, 0, 1, nullptr);
+    ConvCall call = {};
+    call.c0 = c0; call.c1 = c1; call.B = B; call.hs = call.ho = H; call.ws = call.wo = W; call.ksize = 3; call.mode = GMK_CONV_NORMAL;
+    call.w_rows = call.cout = call.out_cstride = cout; call.dtype = GMK_BF16; call.gn_scale = call.gn_shift = true; call.gn_stride = c0 + c1;
+    return gmk_conv_route(call, gmk_kernel_choice(0, "GMK_CONV_KERNEL"), gmk_subpixel_enabled()).route == GMK_ROUTE_HALO;
 }
 
 extern "C" int gmk_conv_wgrad(const void* dy, int dy_cstride, const void* src0, const void* src1, int c0, int c1, int B,
@@ -1254,9 +1264,8 @@ extern "C" int gmk_conv_wgrad(const void* dy, int dy_cstride, const void* src0, 
     GMK_REQUIRE(B > 0 && (int64_t)B * ho * wo < (1ll << 31) - 256 && (int64_t)B * hs * ws < (1ll << 31),
                 "gmk_conv_wgrad: problem too large for 32-bit pixel indices");
     GMK_REQUIRE(mode != GMK_CONV_TRANSPOSED2, "gmk_conv_wgrad: no weight gradient for the transposed gather");
-    WgradParams p;
-    GMK_REQUIRE(make_gather(mode, ksize, hs, ws, ho, wo, &p.g), "gmk_conv_wgrad: mode %d inconsistent with %dx%d -> %dx%d",
-                mode, hs, ws, ho, wo);
+    WgradParams p = {};
+    GMK_REQUIRE(make_gather(mode, ksize, hs, ws, ho, wo, &p.g), "gmk_conv_wgrad: mode %d inconsistent with %dx%d -> %dx%d", mode, hs, ws, ho, wo);
     const int taps = ksize * ksize;
     // kernel choice: 0 = automatic, 1 = im2col split-K, 2 = padded-slot correlation (3x3 s1 bf16)
     const int wforce = gmk_kernel_choice(1, "GMK_WGRAD_KERNEL");
@@ -1264,24 +1273,15 @@ extern "C" int gmk_conv_wgrad(const void* dy, int dy_cstride, const void* src0, 
     const bool s2 = mode == GMK_CONV_STRIDE2 && hs == 2 * ho && ws == 2 * wo;
     if (wforce != 1 && dtype == GMK_BF16 && (mode == GMK_CONV_NORMAL || mode == GMK_CONV_UPSAMPLE2 || s2) && ksize == 3) {
         const int ns2 = gmk_conv_wgrad_slots_try(dy, dy_cstride, src0, src1, c0, c1, B, ho, wo, cout, (float*)workspace,
-                                                 workspace_bytes, wforce, mode == GMK_CONV_UPSAMPLE2, xf16, gmk_stream(stream), s2);
-        if (ns2 > 0) {
-            int rc2 = gmk_check_launch("gmk_conv_wgrad(slots)");
-            if (rc2) return rc2;
-            launch_wgrad_reduce((const float*)workspace, dw, ns2, taps, cout, c0 + c1, gmk_stream(stream));
-            return gmk_check_launch("gmk_conv_wgrad(reduce)");
-        }
+                                                 workspace_bytes, wforce, mode == GMK_CONV_UPSAMPLE2, xf16, stream, s2);
+        if (ns2 > 0) return wgrad_reduce("gmk_conv_wgrad(slots)", (const float*)workspace, dw, ns2, taps, cout, c0 + c1, stream);
     }
     if (wforce != 1 && ksize == 1 && mode == GMK_CONV_NORMAL && dtype == GMK_BF16 && c0 == 128 && c1 == 128 && cout == 128) {
         // the skip convolution over the concatenated input at the train step's sizes: one workgroup per pixel range owns both input blocks
-        const int ns1 = gmk_conv1x1_wgrad_stream_try(dy, dy_cstride, src0, src1, (int64_t)B * ho * wo, (float*)workspace, workspace_bytes, xf16,
-                                                     gmk_stream(stream));
+        const int ns1 = gmk_conv1x1_wgrad_stream_try(dy, dy_cstride, src0, src1, (int64_t)B * ho * wo, (float*)workspace, workspace_bytes, xf16, stream);
         if (ns1 > 0) {
             gmk_note_kernel(15);
-            int rc1 = gmk_check_launch("gmk_conv_wgrad(1x1 stream)");
-            if (rc1) return rc1;
-            launch_wgrad_reduce((const float*)workspace, dw, ns1, 1, cout, 256, gmk_stream(stream));
-            return gmk_check_launch("gmk_conv_wgrad(reduce)");
+            return wgrad_reduce("gmk_conv_wgrad(1x1 stream)", (const float*)workspace, dw, ns1, 1, cout, 256, stream);
         }
     }
     p.dy = dy; p.dy_cstride = dy_cstride; p.src0 = src0; p.src1 = src1; p.c0 = c0; p.c1 = c1; p.ktot = c0 + c1;
@@ -1298,8 +1298,5 @@ extern "C" int gmk_conv_wgrad(const void* dy, int dy_cstride, const void* src0, 
     else if (dtype == GMK_BF16) conv_wgrad_kernel<bf16_t><<<grid, 256, 0, gmk_stream(stream)>>>(p);
     else if (fp32_split()) conv_wgrad_kernel<float, float, true><<<grid, 256, 0, gmk_stream(stream)>>>(p);
     else conv_wgrad_kernel<float><<<grid, 256, 0, gmk_stream(stream)>>>(p);
-    int rc = gmk_check_launch("gmk_conv_wgrad");
-    if (rc) return rc;
-    launch_wgrad_reduce(p.slab, dw, ns, taps, cout, p.ktot, gmk_stream(stream));
-    return gmk_check_launch("gmk_conv_wgrad(reduce)");
+    return wgrad_reduce("gmk_conv_wgrad", p.slab, dw, ns, taps, cout, p.ktot, stream);
 }

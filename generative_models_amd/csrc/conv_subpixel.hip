@@ -24,6 +24,7 @@
 // next segment's 7 pieces stream in during the current segment's 4 K-steps (conv_halo.hip's double buffering at 4 steps per phase instead of 9),
 // one accumulator set, one dense epilogue per tile.
 #include "gmk_common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -472,7 +473,9 @@ __global__ __launch_bounds__(256) void pack_upsample_kernel(const float* __restr
                 }
 }
 
-bool subpixel_enabled() {
+}  // namespace
+
+bool gmk_subpixel_enabled(void) {
     static int on = -1;
     if (on < 0) {
         const char* e = getenv("GMK_SUBPIXEL");
@@ -481,34 +484,25 @@ bool subpixel_enabled() {
     return on != 0;
 }
 
-}  // namespace
-
-// geometry of the low-resolution tiling; 0 if the sub-pixel kernel does not take the problem
-static int subpixel_geometry(int B, int H, int W, int cin, int cout, int w_rows, int ntaps, int out_cstride, HaloGeometry* g) {
+int gmk_subpixel_plan(int B, int H, int W, int cin, int cout, int w_rows, int ntaps, int out_cstride, HaloGeometry* g) {
     if (cin != 128 || cout != 128) return 0;                       // one 128-channel source, one output block: the C = 128 nets
     if (!gmk_halo_geometry(B, H, W, cin, 0, w_rows, cout, out_cstride, 1, 0, 0, g)) return 0;
-    const int64_t lim = 0xFFFF0000ll;
     const int64_t nbo = 4 * g->M * out_cstride * 2, nbw = (int64_t)ntaps * w_rows * cin * 2;
-    if (nbo >= lim || nbw >= lim || 4 * g->nb0 >= lim || 4 * g->M >= 0x00FFFFFF) return 0;      // (4 M: pixel indices of the high-resolution tensor, 24 bits)
+    if (!gmk_fits32(nbo) || !gmk_fits32(nbw) || !gmk_fits32(4 * g->nb0) || 4 * g->M >= 0x00FFFFFF) return 0;      // (4 M: pixel indices of the high-resolution tensor, 24 bits)
     g->nbo = nbo; g->nbw = nbw;
     return 1;
 }
 
-extern "C" int gmk_conv_subpixel_ok(int B, int H, int W, int cin, int cout, int dtype) {
-    const int force = gmk_kernel_choice(0, "GMK_CONV_KERNEL");
-    if ((force != 0 && force != 3) || !subpixel_enabled() || !gmk_is16(dtype)) return 0;
-    HaloGeometry g;
-    return subpixel_geometry(B, H, W, cin, cout, cout, 16, cout, &g);
-}
-
-// the same answer for the EXACT launch a caller is about to make (its own weight-row count and output stride enter the byte limits): what
-// gmk_conv_igemm's dispatch asks, so that a shape the launch would refuse falls through to the other kernels instead of failing the call
-int gmk_conv_subpixel_takes(int B, int H, int W, int cin, int cout, int w_rows, int ntaps, int out_cstride, int dtype) {
-    const int force = gmk_kernel_choice(0, "GMK_CONV_KERNEL");
-    if ((force != 0 && force != 3) || !subpixel_enabled() || !gmk_is16(dtype)) return 0;
+// what gmk_conv_igemm's dispatch asks, so that a shape the launch would refuse falls through to the other kernels instead of failing the call
+int gmk_subpixel_takes(int conv_choice, bool subpixel_on, int B, int H, int W, int cin, int cout, int w_rows, int ntaps, int out_cstride, int dtype) {
+    if (!gmk_halo_family_allowed(conv_choice) || !subpixel_on || !gmk_is16(dtype)) return 0;
     if (w_rows < cout || out_cstride < cout) return 0;
     HaloGeometry g;
-    return subpixel_geometry(B, H, W, cin, cout, w_rows, ntaps, out_cstride, &g);
+    return gmk_subpixel_plan(B, H, W, cin, cout, w_rows, ntaps, out_cstride, &g);
+}
+
+extern "C" int gmk_conv_subpixel_ok(int B, int H, int W, int cin, int cout, int dtype) {
+    return gmk_subpixel_takes(gmk_kernel_choice(0, "GMK_CONV_KERNEL"), gmk_subpixel_enabled(), B, H, W, cin, cout, cout, 16, cout, dtype);
 }
 
 extern "C" int gmk_pack_upsample_weight(const float* w, void* w_sub, void* w_sub_dgrad, int cout, int cin, int dtype, int dgrad_dtype, void* stream) {
@@ -516,10 +510,13 @@ extern "C" int gmk_pack_upsample_weight(const float* w, void* w_sub, void* w_sub
     GMK_REQUIRE(gmk_is16(dtype) && gmk_is16(dgrad_dtype), "gmk_pack_upsample_weight: 16-bit packs only (dtypes %d, %d)", dtype, dgrad_dtype);
     const int blocks = (cout * cin + 255) / 256;
     hipStream_t st = gmk_stream(stream);
-    if (dtype == GMK_F16 && dgrad_dtype == GMK_BF16) pack_upsample_kernel<f16_t, bf16_t><<<blocks, 256, 0, st>>>(w, (f16_t*)w_sub, (bf16_t*)w_sub_dgrad, cout, cin);
-    else if (dtype == GMK_BF16 && dgrad_dtype == GMK_BF16) pack_upsample_kernel<bf16_t, bf16_t><<<blocks, 256, 0, st>>>(w, (bf16_t*)w_sub, (bf16_t*)w_sub_dgrad, cout, cin);
-    else if (dtype == GMK_F16 && dgrad_dtype == GMK_F16) pack_upsample_kernel<f16_t, f16_t><<<blocks, 256, 0, st>>>(w, (f16_t*)w_sub, (f16_t*)w_sub_dgrad, cout, cin);
-    else GMK_REQUIRE(false, "gmk_pack_upsample_weight: forward packs fp16 or bf16, data-gradient packs of the same type or bf16");
+    GMK_REQUIRE(dgrad_dtype == GMK_BF16 || dtype == GMK_F16, "gmk_pack_upsample_weight: forward packs fp16 or bf16, data-gradient packs of the same type or bf16");
+    if (dgrad_dtype == GMK_BF16)
+        gmk_with_type<bf16_t, f16_t>(dtype, [&](auto ftag) {      // (the order of the list fixes kernel addresses: see gmk_with_type)
+            typedef typename decltype(ftag)::type TF;
+            pack_upsample_kernel<TF, bf16_t><<<blocks, 256, 0, st>>>(w, (TF*)w_sub, (bf16_t*)w_sub_dgrad, cout, cin);
+        });
+    else pack_upsample_kernel<f16_t, f16_t><<<blocks, 256, 0, st>>>(w, (f16_t*)w_sub, (f16_t*)w_sub_dgrad, cout, cin);
     return gmk_check_launch("gmk_pack_upsample_weight");
 }
 
@@ -533,7 +530,7 @@ extern "C" int gmk_conv_subpixel(const void* src, int B, int H, int W, int cin, 
     const bool down = mode == GMK_SUBPIXEL_UPSAMPLE_DGRAD;
     const int ntaps = mode == GMK_SUBPIXEL_TRANSPOSED ? 9 : 16;
     HaloGeometry g;
-    GMK_REQUIRE(subpixel_geometry(B, H, W, cin, cout, w_rows, ntaps, out_cstride, &g),
+    GMK_REQUIRE(gmk_subpixel_plan(B, H, W, cin, cout, w_rows, ntaps, out_cstride, &g),
                 "gmk_conv_subpixel: shape B=%d %dx%d cin=%d cout=%d is not eligible (ask gmk_conv_subpixel_ok first)", B, H, W, cin, cout);
     SubParams p = {};
     p.src = src; p.B = B; p.H = H; p.W = W; p.WE = W + 2; p.R = g.R; p.TP = g.TP; p.ntiles = (int)g.ntiles; p.M = (int)g.M;
@@ -545,16 +542,12 @@ extern "C" int gmk_conv_subpixel(const void* src, int B, int H, int W, int cin, 
     const int ncu = gmk_cu_limit();
     const dim3 grid((unsigned)(g.ntiles < ncu ? g.ntiles : ncu));
     hipStream_t st = gmk_stream(stream);
-    if (mode == GMK_SUBPIXEL_UPSAMPLE) {
-        if (dtype == GMK_F16) conv_subpixel_ws_kernel<f16_t, 0><<<grid, 512, 0, st>>>(p);
-        else conv_subpixel_ws_kernel<bf16_t, 0><<<grid, 512, 0, st>>>(p);
-    } else if (mode == GMK_SUBPIXEL_TRANSPOSED) {
-        if (dtype == GMK_F16) conv_subpixel_ws_kernel<f16_t, 1><<<grid, 512, 0, st>>>(p);
-        else conv_subpixel_ws_kernel<bf16_t, 1><<<grid, 512, 0, st>>>(p);
-    } else {
-        if (dtype == GMK_F16) conv_subpixel_ws_kernel<f16_t, 2><<<grid, 512, 0, st>>>(p);
-        else conv_subpixel_ws_kernel<bf16_t, 2><<<grid, 512, 0, st>>>(p);
-    }
+    auto launch = [&](auto m) {      // m: the kernel's mode as a constant
+        gmk_with_type<bf16_t, f16_t>(dtype, [&](auto tag) { conv_subpixel_ws_kernel<typename decltype(tag)::type, decltype(m)::value><<<grid, 512, 0, st>>>(p); });
+    };
+    if (mode == GMK_SUBPIXEL_UPSAMPLE) launch(IntTag<0>{});
+    else if (mode == GMK_SUBPIXEL_TRANSPOSED) launch(IntTag<1>{});
+    else launch(IntTag<2>{});
     gmk_note_kernel(mode == GMK_SUBPIXEL_UPSAMPLE ? 8 : mode == GMK_SUBPIXEL_TRANSPOSED ? 9 : 10);
     return gmk_check_launch("gmk_conv_subpixel");
 }

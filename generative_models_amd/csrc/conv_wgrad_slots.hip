@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "gmk_common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -651,89 +652,87 @@ __global__ __launch_bounds__(512, kS2 ? 1 : 2) void conv_wgrad_slots_ws_kernel(c
 
 }  // namespace
 
-int gmk_wgrad_slots_nsplit(int cout, int ktot) {
+int gmk_wgrad_slots_nsplit(int cout, int ktot, int cu_limit) {
     const int tiles = (cout / 128) * (ktot / 64);
-    int ns = gmk_cu_limit() / tiles;
+    int ns = cu_limit / tiles;
     return ns < 1 ? 1 : ns;
 }
 
-// Returns the number of splits written (>= 1) if the slot kernel was launched, 0 if the problem is not eligible.
-// stride2: (H, W) is the convolution's OUTPUT (= dY) size, the source is (2H, 2W): the four-plane form of the wave-specialised kernel (kS2)
-int gmk_conv_wgrad_slots_try(const void* dy, int dy_cstride, const void* src0, const void* src1, int c0, int c1, int B, int H,
-                             int W, int cout, float* slab, int64_t slab_bytes, int forced, int upsample, bool x_f16,
-                             hipStream_t stream, int stride2) {
+int gmk_wgrad_slot_plan(int B, int H, int W, int c0, int c1, int cout, int dy_cstride, int forced, int upsample, bool x_f16, int stride2,
+                        int cu_limit, SlotPlan* plan) {
+    *plan = {};
     if (c0 % 64 || c1 % 64 || cout % 128) return 0;
     if (x_f16 && forced == 2) return 0;                      // the 8-compute-wave A/B kernel has no fp16-activation form
     if (stride2 && (upsample || c1 || forced == 2 || W + 2 > 64)) return 0;
-    const int WE = W + 1, RE = H + 1;
+    const int WE = plan->WE = W + 1, RE = plan->RE = H + 1;
     if (WE + 1 > 128 || W < 4 || H < 2) return 0;
-    const bool wide = WE + 1 > 64;
+    plan->wide = WE + 1 > 64;
     const int64_t M = (int64_t)B * H * W;
     const int64_t total = (int64_t)B * RE * WE;              // the last image's lower border lies beyond: b == B reads as zero
     if (M >= 0x00FFFFFF || total >= (1ll << 30)) return 0;
     if (upsample && ((H | W) & 1)) return 0;
     const int64_t Msrc = upsample ? M / 4 : stride2 ? M * 4 : M;
     if (Msrc >= 0x00FFFFFF) return 0;
-    const int64_t nbdy = M * dy_cstride * 2, nb0 = Msrc * c0 * 2, nb1 = Msrc * c1 * 2;
-    const int64_t lim = 0xFFFF0000ll;     // below (kBadPix * bytes-per-pixel) mod 2^32 for pixels of up to 4 KiB
-    if (nbdy >= lim || nb0 >= lim || nb1 >= lim || c0 > 2048 || c1 > 2048 || dy_cstride > 2048) return 0;
+    plan->nbdy = M * dy_cstride * 2; plan->nb0 = Msrc * c0 * 2; plan->nb1 = Msrc * c1 * 2;
+    if (!gmk_fits32(plan->nbdy) || !gmk_fits32(plan->nb0) || !gmk_fits32(plan->nb1) || c0 > 2048 || c1 > 2048 || dy_cstride > 2048) return 0;
     const int ktot = c0 + c1;
-    const int nchunks = (int)((total + 63) / 64);
-    int ns = gmk_wgrad_slots_nsplit(cout, ktot);
-    if (nchunks < 8 * ns) {                                 // too little work per split: the im2col kernel
+    const int nchunks = plan->nchunks = (int)((total + 63) / 64);
+    // the 8-compute-wave kernel's splits: they decide whether the automatic choice takes the slot family at all
+    int ns = gmk_wgrad_slots_nsplit(cout, ktot, cu_limit);
+    plan->auto_ok = nchunks >= 8 * ns;
+    if (!plan->auto_ok) {                                   // too little work per split: the im2col kernel
         if (!forced) return 0;
         ns = nchunks / 4 > 0 ? nchunks / 4 : 1;
     }
     const int cps = (nchunks + ns - 1) / ns;
     ns = (nchunks + cps - 1) / cps;
-    if ((int64_t)ns * 9 * cout * ktot * 4 > slab_bytes) return 0;
-    SlotParams p;
-    p.dy = dy; p.dy_cstride = dy_cstride; p.src0 = src0; p.src1 = src1; p.c0 = c0; p.c1 = c1; p.ktot = ktot; p.cout = cout;
-    p.xshift = upsample ? 1 : 0;
-    p.HS = 2 * H; p.WS = 2 * W; p.ntile = ktot / 64;
-    p.B = B; p.H = H; p.W = W; p.WE = WE; p.RE = RE; p.slab = slab; p.nchunks = nchunks; p.chunks_per_split = cps;
-    p.nbdy = (unsigned)nbdy; p.nb0 = (unsigned)nb0; p.nb1 = (unsigned)nb1;
-    p.variant = gmk_kernel_choice(3, "GMK_DEV_VARIANT") & 0xFF;
-    dim3 grid(ns, ktot / 64, cout / 128);
+    const int64_t slab8 = (int64_t)ns * 9 * cout * ktot * 4;
     // forced: 0 automatic = 3 the wave-specialised kernel (1.37 - 1.58 x the 8-compute-wave kernel at every shape of the train step:
     // docs/EXPERIMENTS.md 7b.11); 2 the 8-compute-wave kernel (A/B)
-    const bool ws = forced != 2;
-    if (ws) {
-        const int ytiles = (stride2 ? 4 : 1) * (ktot / 64);
-        int ns3 = gmk_cu_limit() / ((cout / 64) * ytiles);
-        if (ns3 >= 8) {                   // workgroups that stream the same dY / X are ns3 block ids apart: a multiple of 8 keeps them on one XCD
-            const int all8 = ns3 & ~7, two = ns3 & ~3;       // (a multiple of 4: on two XCDs) - taken when the CU limit of a data-parallel
-            ns3 = all8 * 16 < ns3 * 15 ? two : all8;      // run (248) would otherwise leave 10 % of the CUs without a workgroup (1.18 -> 1.25 PFLOP/s at 64 x 64)
-        }
-        if (ns3 < 1) ns3 = 1;
-        if (nchunks < 8 * ns3) ns3 = nchunks / 8 > 0 ? nchunks / 8 : 1;
-        const int cps3 = (nchunks + ns3 - 1) / ns3;
-        ns3 = (nchunks + cps3 - 1) / cps3;
-        if ((int64_t)ns3 * 9 * cout * ktot * 4 > slab_bytes) return 0;
-        p.chunks_per_split = cps3;
-        dim3 grid3(ns3, ytiles, cout / 64);
-        if (stride2) {
-            if (x_f16) conv_wgrad_slots_ws_kernel<1, true, true, true><<<grid3, 512, 0, stream>>>(p);
-            else conv_wgrad_slots_ws_kernel<1, false, true, true><<<grid3, 512, 0, stream>>>(p);
-            gmk_note_kernel(17);
-            return ns3;
-        }
-        const bool share = !upsample;          // dY slot S and X slot S are the same pixel: decode once (kShare)
-#define GMK_SLOT_WS(LK)                                                                                        \
-    do {                                                                                                       \
-        if (x_f16 && share) conv_wgrad_slots_ws_kernel<LK, true, true><<<grid3, 512, 0, stream>>>(p);         \
-        else if (x_f16) conv_wgrad_slots_ws_kernel<LK, true, false><<<grid3, 512, 0, stream>>>(p);            \
-        else if (share) conv_wgrad_slots_ws_kernel<LK, false, true><<<grid3, 512, 0, stream>>>(p);            \
-        else conv_wgrad_slots_ws_kernel<LK, false, false><<<grid3, 512, 0, stream>>>(p);                      \
-    } while (0)
-        if (wide) GMK_SLOT_WS(2);
-        else GMK_SLOT_WS(1);
-#undef GMK_SLOT_WS
-        gmk_note_kernel(13);
-        return ns3;
+    if (forced == 2) {
+        plan->kernel = 12; plan->ns_cu = plan->ns = ns; plan->cps = cps; plan->slab_bytes = slab8;
+        plan->grid[0] = ns; plan->grid[1] = ktot / 64; plan->grid[2] = cout / 128;
+        return 1;
     }
-    if (wide) conv_wgrad_slots_kernel<2><<<grid, 512, 0, stream>>>(p);
-    else conv_wgrad_slots_kernel<1><<<grid, 512, 0, stream>>>(p);
-    gmk_note_kernel(12);
-    return ns;
+    const int ytiles = (stride2 ? 4 : 1) * (ktot / 64);
+    int ns3 = plan->ns_cu = gmk_xcd_splits(cu_limit / ((cout / 64) * ytiles));
+    if (nchunks < 8 * ns3) ns3 = nchunks / 8 > 0 ? nchunks / 8 : 1;
+    plan->cps = (nchunks + ns3 - 1) / ns3;
+    plan->ns = ns3 = (nchunks + plan->cps - 1) / plan->cps;
+    const int64_t slab3 = (int64_t)ns3 * 9 * cout * ktot * 4;
+    plan->slab_bytes = slab3 > slab8 ? slab3 : slab8;      // (the 8-compute-wave kernel's slabs are asked for as well: gmk_conv_wgrad_workspace_bytes covers both)
+    plan->kernel = stride2 ? 17 : 13;
+    plan->share = !upsample;          // dY slot S and X slot S are the same pixel: decode once (kShare)
+    plan->grid[0] = ns3; plan->grid[1] = ytiles; plan->grid[2] = cout / 64;
+    return 1;
+}
+
+// Returns the number of splits written (>= 1) if the slot kernel was launched, 0 if the problem is not eligible or the slab is short.
+int gmk_conv_wgrad_slots_try(const void* dy, int dy_cstride, const void* src0, const void* src1, int c0, int c1, int B, int H,
+                             int W, int cout, float* slab, int64_t slab_bytes, int forced, int upsample, bool x_f16,
+                             void* stream, int stride2) {
+    SlotPlan pl;
+    if (!gmk_wgrad_slot_plan(B, H, W, c0, c1, cout, dy_cstride, forced, upsample, x_f16, stride2, gmk_cu_limit(), &pl)) return 0;
+    if (pl.slab_bytes > slab_bytes) return 0;
+    SlotParams p = {};
+    p.dy = dy; p.dy_cstride = dy_cstride; p.src0 = src0; p.src1 = src1; p.c0 = c0; p.c1 = c1; p.ktot = c0 + c1; p.cout = cout;
+    p.xshift = upsample ? 1 : 0;
+    p.HS = 2 * H; p.WS = 2 * W; p.ntile = p.ktot / 64;
+    p.B = B; p.H = H; p.W = W; p.WE = pl.WE; p.RE = pl.RE; p.slab = slab; p.nchunks = pl.nchunks; p.chunks_per_split = pl.cps;
+    p.nbdy = (unsigned)pl.nbdy; p.nb0 = (unsigned)pl.nb0; p.nb1 = (unsigned)pl.nb1;
+    p.variant = gmk_kernel_choice(3, "GMK_DEV_VARIANT") & 0xFF;
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+    hipStream_t st = gmk_stream(stream);
+    // the instantiations that exist: <LOOK (2 = the 128-slot window), kXF16, kShare, kS2>
+    const bool f = x_f16, s = pl.share;
+#define GMK_SLOT_WS conv_wgrad_slots_ws_kernel
+    void (*const k)(const SlotParams) =
+        pl.kernel == 17 ? (f ? GMK_SLOT_WS<1, true, true, true> : GMK_SLOT_WS<1, false, true, true>)
+        : pl.kernel == 13 && pl.wide ? (f ? (s ? GMK_SLOT_WS<2, true, true> : GMK_SLOT_WS<2, true, false>) : (s ? GMK_SLOT_WS<2, false, true> : GMK_SLOT_WS<2, false, false>))
+        : pl.kernel == 13 ? (f ? (s ? GMK_SLOT_WS<1, true, true> : GMK_SLOT_WS<1, true, false>) : (s ? GMK_SLOT_WS<1, false, true> : GMK_SLOT_WS<1, false, false>))
+        : pl.wide ? conv_wgrad_slots_kernel<2> : conv_wgrad_slots_kernel<1>;      // 12
+#undef GMK_SLOT_WS
+    k<<<grid, 512, 0, st>>>(p);
+    gmk_note_kernel(pl.kernel);
+    return pl.ns;
 }

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "gmk_common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -309,31 +310,26 @@ __global__ __launch_bounds__(256) void subpixel_taps_kernel(const float* __restr
 
 }  // namespace
 
-static int wgrad_subpixel_plan(int B, int H, int W, int cin, int cout, int dy_cstride, int* nsplit, int* cps, int* nchunks) {
+int gmk_wgrad_subpixel_plan(int B, int H, int W, int cin, int cout, int dy_cstride, int cu_limit, SubWgradPlan* plan) {
+    *plan = {};
     if (cin != 128 || cout != 128 || dy_cstride < cout || dy_cstride > 2048) return 0;
     const int WE = W + 1, RE = H + 1;
     if (WE + 1 > 64 || W < 4 || H < 2) return 0;
     const int64_t M = (int64_t)B * H * W, total = (int64_t)B * RE * WE;
     if (4 * M >= 0x00FFFFFF || total >= (1ll << 22) * WE) return 0;          // 24-bit pixel indices of the high-resolution tensor; row < 2^22
-    const int64_t lim = 0xFFFF0000ll;
-    if (4 * M * dy_cstride * 2 >= lim || M * cin * 2 >= lim) return 0;
+    if (!gmk_fits32(4 * M * dy_cstride * 2) || !gmk_fits32(M * cin * 2)) return 0;
     const int nch = (int)((total + 63) / 64);
-    int ns = gmk_cu_limit() / ((cout / 64) * (cin / 64) * 2);                  // both row parities in one launch
-    if (ns >= 8) {                                                             // the 8 workgroups of a slot range sit on one XCD (a multiple of 8 splits) -
-        const int all8 = ns & ~7, two = ns & ~3;                               // or on two (a multiple of 4) when the CU limit of a data-parallel run (248)
-        ns = all8 * 16 < ns * 15 ? two : all8;                                 // would otherwise leave a fifth of the CUs without a workgroup
-    }
-    if (ns < 1) ns = 1;
+    const int ns = gmk_xcd_splits(cu_limit / ((cout / 64) * (cin / 64) * 2));      // both row parities in one launch
     if (nch < 8 * ns) return 0;                                                // too little work per split: the nearest-x2 forms
-    const int c = (nch + ns - 1) / ns;
-    *cps = c; *nsplit = (nch + c - 1) / c; *nchunks = nch;
+    plan->cps = (nch + ns - 1) / ns; plan->ns = (nch + plan->cps - 1) / plan->cps; plan->nchunks = nch;
+    plan->grid[0] = plan->ns; plan->grid[1] = cin / 64; plan->grid[2] = (cout / 64) * 2;
+    plan->slab_bytes = ((int64_t)2 * plan->ns * 8 + 16) * cout * cin * 4;      // the parity slabs of every split and the reduced pair
     return 1;
 }
 
 extern "C" int64_t gmk_conv_wgrad_subpixel_workspace_bytes(int B, int H, int W, int cin, int cout) {
-    int ns, cps, nch;
-    if (!wgrad_subpixel_plan(B, H, W, cin, cout, cout, &ns, &cps, &nch)) return 0;
-    return ((int64_t)2 * ns * 8 + 16) * cout * cin * 4;
+    SubWgradPlan pl;
+    return gmk_wgrad_subpixel_plan(B, H, W, cin, cout, cout, gmk_cu_limit(), &pl) ? pl.slab_bytes : 0;
 }
 
 extern "C" int gmk_conv_wgrad_subpixel_ok(int B, int H, int W, int cin, int cout) {
@@ -348,22 +344,22 @@ extern "C" int gmk_conv_wgrad_subpixel(const void* dy, int dy_cstride, const voi
     GMK_REQUIRE(dy && x && dw && workspace, "gmk_conv_wgrad_subpixel: null pointer");
     GMK_REQUIRE(dtype == GMK_BF16 && (x_dtype == GMK_BF16 || x_dtype == GMK_F16),
                 "gmk_conv_wgrad_subpixel: bf16 gradients with bf16 or fp16 activations (dtypes %d, %d)", dtype, x_dtype);
-    int ns, cps, nch;
-    GMK_REQUIRE(wgrad_subpixel_plan(B, H, W, cin, cout, dy_cstride, &ns, &cps, &nch),
+    SubWgradPlan pl;
+    GMK_REQUIRE(gmk_wgrad_subpixel_plan(B, H, W, cin, cout, dy_cstride, gmk_cu_limit(), &pl),
                 "gmk_conv_wgrad_subpixel: shape B=%d %dx%d cin=%d cout=%d is not eligible (ask gmk_conv_wgrad_subpixel_ok first)", B, H, W, cin, cout);
     const int64_t per = (int64_t)8 * cout * cin;
-    GMK_REQUIRE(workspace_bytes >= ((int64_t)2 * ns * 8 + 16) * cout * cin * 4, "gmk_conv_wgrad_subpixel: workspace too small");
-    SubWgradParams p;
+    GMK_REQUIRE(workspace_bytes >= pl.slab_bytes, "gmk_conv_wgrad_subpixel: workspace too small");
+    SubWgradParams p = {};
     p.dy = dy; p.dy_cstride = dy_cstride; p.x = x; p.cin = cin; p.cout = cout;
     p.B = B; p.H = H; p.W = W; p.WE = W + 1; p.RE = H + 1;
-    p.slab = (float*)workspace; p.nchunks = nch; p.chunks_per_split = cps; p.nsplit = ns;
+    p.slab = (float*)workspace; p.nchunks = pl.nchunks; p.chunks_per_split = pl.cps; p.nsplit = pl.ns;
     p.nbdy = (unsigned)((int64_t)4 * B * H * W * dy_cstride * 2); p.nbx = (unsigned)((int64_t)B * H * W * cin * 2);
     hipStream_t st = gmk_stream(stream);
-    const dim3 grid(ns, cin / 64, (cout / 64) * 2);
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
     if (x_dtype == GMK_F16) conv_wgrad_subpixel_ws_kernel<true><<<grid, 512, 0, st>>>(p);
     else conv_wgrad_subpixel_ws_kernel<false><<<grid, 512, 0, st>>>(p);
-    float* G = p.slab + (int64_t)2 * ns * per;
-    subpixel_split_reduce_kernel<<<dim3((unsigned)((per / 4 + 255) / 256), 2), 256, 0, st>>>(p.slab, G, ns, (int)per);
+    float* G = p.slab + (int64_t)2 * pl.ns * per;
+    subpixel_split_reduce_kernel<<<dim3((unsigned)((per / 4 + 255) / 256), 2), 256, 0, st>>>(p.slab, G, pl.ns, (int)per);
     subpixel_taps_kernel<<<(cout * cin + 255) / 256, 256, 0, st>>>(G, dw, cout * cin);
     gmk_note_kernel(16);
     return gmk_check_launch("gmk_conv_wgrad_subpixel");

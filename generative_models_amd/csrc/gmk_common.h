@@ -26,16 +26,9 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 void gmk_set_error(const char* fmt, ...);
 int gmk_check_launch(const char* what);   // returns 0 or the positive hipError_t of the launch
 int gmk_kernel_choice(int which, const char* env);   // 0 conv (GMK_CONV_KERNEL), 1 wgrad (GMK_WGRAD_KERNEL), 2 GN
-int gmk_conv1x1_pair_stream_try(const void* src, int64_t npix, const void* w_rows256, void* out_a, void* out_b, int dtype, hipStream_t stream);   // conv1x1_stream.hip
-int gmk_conv1x1_wgrad_stream_try(const void* dy, int dy_cstride, const void* src0, const void* src1, int64_t npix, float* slab, int64_t slab_bytes,
-                                 bool x_f16, hipStream_t stream);        // conv1x1_stream.hip: > 0 = slabs written
-int gmk_conv_subpixel_takes(int B, int H, int W, int cin, int cout, int w_rows, int ntaps, int out_cstride, int dtype);      // conv_subpixel.hip
 bool fp32_split(void);                // fp32 mode: exact fp32 MFMA chains (default) or operands as bf16 hi + lo on the bf16 matrix cores (GMK_FP32_SPLIT=1 / gmk_set_fp32_exact(0))
 int gmk_cu_limit(void);                   // workgroups a persistent kernel may occupy (gmk_set_cu_limit / GMK_CU_LIMIT, default 256)
-void gmk_note_kernel(int id);             // 1 conv_igemm_kernel, 2 conv_igemm_dma_kernel, 3 conv3x3_halo_kernel,
-                                          // 4 conv3x3_halo_ws_kernel, 5 halo kernel on a zero-stuffed source, 6 stride-2 dgrad as four phase launches of the LDS-DMA kernel, 7 halo kernel with the folded 1x1 skip
-                                          // convolution, 8 / 9 / 10 conv_subpixel_ws_kernel (upsample / transposed / upsample data gradient), 11 conv_wgrad_kernel, 12 conv_wgrad_slots_kernel, 13 conv_wgrad_slots_ws_kernel,
-                                          // 14 / 15 conv1x1_pair_stream_kernel / conv1x1_wgrad_stream_kernel, 16 conv_wgrad_subpixel_ws_kernel,
+void gmk_note_kernel(int id);             // 1 .. 17 the convolution kernels (listed in conv_plan.h),
                                           // 21 gn_silu_fwd_reg_kernel, 22 gn_silu_fwd_kernel, 23 gn_silu_bwd_hybrid_kernel, 24 gn_silu_bwd_kernel, 25 gn_silu_bwd_pair_kernel, 26 gn_silu_fwd_pair_kernel
 
 #define GMK_REQUIRE(cond, ...)                 \
@@ -46,27 +39,14 @@ void gmk_note_kernel(int id);             // 1 conv_igemm_kernel, 2 conv_igemm_d
         }                                      \
     } while (0)
 
-// conv_halo.hip: 3x3 stride-1 convolution of 16-bit operands (dtype GMK_BF16 / GMK_F16) with an LDS-resident halo; returns 1 / 2 if launched, 0 if not eligible
-int gmk_conv3x3_halo_try(const void* src0, const void* src1, int c0, int c1, int B, int H, int W, const void* w, int w_rows,
-                         int n0, int cout, const float* bias, const float* emb, int emb_stride, const void* residual,
-                         void* out, int out_cstride, int min_tiles, int upsample, float* stats, int64_t stats_bytes,
-                         const float* gn_scale, const float* gn_shift, int gn_stride, int dtype, hipStream_t stream);
-
-struct HaloGeometry { int R, TP, slots; int64_t rows_total, M, ntiles, nb0, nb1, nbw, nbo; };      // slots: halo slots a tile uses (<= 448)
-int gmk_halo_geometry(int B, int H, int W, int c0, int c1, int w_rows, int cout, int out_cstride, int min_tiles, int upsample,
-                      int fused_gn, HaloGeometry* g);      // conv_halo.hip: 1 if the halo kernels take this problem (g filled), else 0
-
-// conv_wgrad_slots.hip: 3x3 stride-1 bf16 weight gradient over padded slots; returns the number of slabs written or 0
-int gmk_wgrad_slots_nsplit(int cout, int ktot);
-int gmk_conv_wgrad_slots_try(const void* dy, int dy_cstride, const void* src0, const void* src1, int c0, int c1, int B, int H,
-                             int W, int cout, float* slab, int64_t slab_bytes, int forced, int upsample, bool x_f16,
-                             hipStream_t stream, int stride2 = 0);
-
-
 static inline hipStream_t gmk_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int gmk_esize(int dtype) { return dtype == GMK_F32 ? 4 : 2; }
 static inline bool gmk_is16(int dtype) { return dtype == GMK_BF16 || dtype == GMK_F16; }
 // Storage type dispatch of the launchers: calls f(gmk_tag<T>{}) for the T among Ts that `dtype` names; false (nothing called) if none does.
+// The lambda is instantiated for Ts LAST TO FIRST, and a code object holds its kernels in the order in which they were instantiated: in the
+// convolution files the lists (and the order of the launch ladders) are written so that every kernel keeps the address it has always had.  That
+// order is load-bearing - the graph-replayed B = 8 sampler ran 0.2 - 0.3 % slower with the same kernels in another order
+// (profiles/conv_dispatch_ab.txt, F); `nm -n` of the code object shows it.
 template <typename T> struct gmk_tag { typedef T type; };
 template <typename T> constexpr int gmk_dtype_of = std::is_same<T, float>::value ? GMK_F32 : std::is_same<T, bf16_t>::value ? GMK_BF16 : GMK_F16;
 template <typename... Ts, typename F> static inline bool gmk_with_type(int dtype, F&& f) {

@@ -1,6 +1,6 @@
 """Float64 restatement of the four convolution modes of gmk_conv_igemm / gmk_conv_wgrad, a host mirror of the two planners that
-schedule the persistent kernels (gmk_halo_geometry + the nfull / nhalf rule of gmk_conv3x3_halo_try; the ns3 rule of
-gmk_conv_wgrad_slots_try), and the case tables of tests/test_gpu_conv_wide.py.  Host code only: tests/test_host_conv_ref.py checks the
+schedule the persistent kernels (gmk_halo_geometry + the nfull / nhalf rule of gmk_halo_schedule; the ns3 rule of
+gmk_wgrad_slot_plan: csrc/conv_plan.h), and the case tables of tests/test_gpu_conv_wide.py.  Host code only: tests/test_host_conv_ref.py checks the
 reference against itself and the case tables against the planners' branches."""
 import torch
 import torch.nn.functional as F
@@ -51,13 +51,14 @@ def grads64(mode, srcs, w, dy, want="both"):
 
 
 # ---- the planners ----------------------------------------------------------------------------------------------------------------
-def halo_plan(B, H, W, cu_limit=256):
+def halo_plan(B, H, W, cu_limit=256, no_tail=False, no_all_half=False):
     """Tiling and schedule of a halo launch over the B x H x W OUTPUT grid: R rows of the global row list per tile, ntiles, whether a tile
     can span an image boundary, and how the wave-specialised kernel spreads the tiles over G = min(ntiles, cu_limit) workgroups:
       all_half       2 ntiles <= cu_limit: every tile as two half-channel jobs (grid 2 ntiles)
       whole_rounds   whole jobs, every round full (ntiles a multiple of G)
       half_tail      whole jobs, then a last round of rem <= G / 2 tiles as 2 rem half jobs
-      whole_partial  whole jobs, the last round (rem > G / 2 tiles) partly filled"""
+      whole_partial  whole jobs, the last round (rem > G / 2 tiles) partly filled
+    no_tail / no_all_half: the GMK_DEV_VARIANT values that switch the half-job tail / the all-half form off (gmk_halo_schedule)"""
     R = 256 // W if W else 0
     ok = 4 <= W <= 254 and H >= 2 and R >= 1
     if not ok:
@@ -69,9 +70,9 @@ def halo_plan(B, H, W, cu_limit=256):
     G = min(ntiles, cu_limit)
     rem = ntiles % G
     nfull, nhalf, grid = ntiles, 0, G
-    if ntiles > G and rem > 0 and 2 * rem <= G:
+    if ntiles > G and rem > 0 and 2 * rem <= G and not no_tail:
         nfull, nhalf, schedule = ntiles - rem, 2 * rem, "half_tail"
-    elif 2 * ntiles <= cu_limit:
+    elif 2 * ntiles <= cu_limit and not no_all_half:
         nfull, nhalf, grid, schedule = 0, 2 * ntiles, 2 * ntiles, "all_half"
     else:
         schedule = "whole_rounds" if rem == 0 else "whole_partial"
@@ -80,7 +81,7 @@ def halo_plan(B, H, W, cu_limit=256):
 
 
 def slot_plan(B, H, W, cout, ktot, stride2=False, cu_limit=256):
-    """The slot weight-gradient kernels over the B x (H + 1) x (W + 1) slot grid of the OUTPUT gradient (gmk_conv_wgrad_slots_try):
+    """The slot weight-gradient kernels over the B x (H + 1) x (W + 1) slot grid of the OUTPUT gradient (gmk_wgrad_slot_plan):
     `wide` the 128-slot window of rows beyond 62 pixels, `auto` whether the automatic choice takes the slot kernel, `ns3_plan` the
     wave-specialised kernel's split count as the CU limit sets it (the value the planner compares with 8), `ns3` after the work clamps."""
     WE, RE = W + 1, H + 1

@@ -1,8 +1,7 @@
 """Host checks of tests/conv_ref.py: the float64 convolution reference against itself (finite differences, the adjoint identity, the
-nearest-x2 identity), the planner mirrors against the lines of the library they restate, and the case tables of
+nearest-x2 identity), the planner mirrors against the library's own planners, and the case tables of
 tests/test_gpu_conv_wide.py against the branches those planners have - the tables may not quietly lose one."""
 import os
-import re
 import sys
 
 import pytest
@@ -129,36 +128,70 @@ def test_rms_ratio_separates_one_rounding_from_two():
 
 
 # ---- the planners ------------------------------------------------------------------------------------------------------------------
-def _source(name):
-    with open(os.path.join(ROOT, "generative_models_amd", "csrc", name)) as f:
-        return re.sub(r"\s+", " ", f.read())
+# (variant, fold) -> (no half-job tail, no all-half form): variant 4 counts for the plain launch only, 6 switches both off, 8 the all-half form
+_NO_HALF = {(0, 0): (False, False), (4, 0): (True, True), (6, 0): (True, True), (8, 0): (False, True),
+            (0, 1): (False, False), (4, 1): (False, False), (6, 1): (True, True), (8, 1): (False, True)}
+
+
+def _planner_cases():
+    """(halo cases (B, H, W, limit, variant, fold), slot cases (B, H, W, cout, ktot, stride2, limit, forced)): the case tables at their limits, every
+    small grid and the widest ones at four batch sizes under the three CU limits, one small problem under every CU limit; the variants that
+    switch half jobs off, for the plain launch and the fold, and the automatic choice's work floor over the case tables"""
+    grids = [(B, H, W, lim) for H in range(2, 67) for W in list(range(2, 67)) + [126, 127, 128, 254, 255] for B in (1, 3, 9, 37) for lim in (8, 248, 256)]
+    table = [(B, H, W, lim) for (H, W, B, lim) in R.TABLE]
+    halo = [c + (0, 0) for c in table + grids] + [c + vf for c in table + [(3, 32, 32, 8)] for vf in _NO_HALF if vf != (0, 0)]
+    stable = [(B, H, W, lim) for (H, W, B, lim) in R.SLOT_TABLE]
+    slot = [(B, H, W, 256, ktot, s2, lim, 1) for (B, H, W, lim) in stable + grids for ktot in (256, 512) for s2 in (0, 1)]
+    # the XCD rounding over every split count a CU limit can give (128 x 64: up to 128 splits; `& ~7` and `& ~3` part ways from 68 on)
+    slot += [(9, 16, 16, 128, 64, s2, lim, 1) for lim in range(8, 257) for s2 in (0, 1)]
+    slot += [(B, H, W, 256, ktot, s2, lim, 0) for (B, H, W, lim) in stable for ktot in (256, 512) for s2 in (0, 1)]
+    return halo, slot
 
 
 def test_planner_mirrors_restate_the_library():
-    """halo_plan / slot_plan restate a few lines of host code that no call can observe without a GPU (and whose effect on a GPU is a
-    schedule, not a value: whole and half jobs give the same bits).  These are the lines; whoever changes one changes the mirror with it."""
-    halo = _source("conv_halo.hip")
-    for line in ("const int R = 256 / W;",
-                 "const int crossings = H % R == 0 ? 0 : (R - 1 + H - 1) / H;",
-                 "const int ner = R + 2 + 2 * crossings;",
-                 "if (ner * (W + 2) > kHaloSlots) return 0;",
-                 "constexpr int kHaloSlots = %d;" % R.HALO_SLOTS,
-                 "dim3 grid((unsigned)(ntiles < ncu ? ntiles : ncu), cout / 128);",
-                 "const int G = (int)grid.x, rem = (int)(ntiles % G);",
-                 "if (ntiles > G && rem > 0 && 2 * rem <= G && p.variant != 4 && p.variant != 6) { p.nfull = (int)ntiles - rem; p.nhalf = 2 * rem; }",
-                 "else if (2 * ntiles <= ncu && p.variant != 4 && p.variant != 6 && p.variant != 8) { p.nfull = 0; p.nhalf = 2 * (int)ntiles; grid.x = (unsigned)p.nhalf; }"):
-        assert line in halo, line
-    slots = _source("conv_wgrad_slots.hip")
-    for line in ("const int tiles = (cout / 128) * (ktot / 64); int ns = gmk_cu_limit() / tiles;",
-                 "const bool wide = WE + 1 > 64;",
-                 "const int64_t total = (int64_t)B * RE * WE;",
-                 "if (nchunks < 8 * ns) {",
-                 "const int ytiles = (stride2 ? 4 : 1) * (ktot / 64); int ns3 = gmk_cu_limit() / ((cout / 64) * ytiles);",
-                 "const int all8 = ns3 & ~7, two = ns3 & ~3;",
-                 "ns3 = all8 * 16 < ns3 * 15 ? two : all8;",
-                 "if (nchunks < 8 * ns3) ns3 = nchunks / 8 > 0 ? nchunks / 8 : 1;",
-                 "dim3 grid3(ns3, ytiles, cout / 64);"):
-        assert line in slots, line
+    """halo_plan / slot_plan against the planners of csrc/conv_plan.h themselves (tools/conv_launch_trace.cpp `plans`, the host objects of the
+    tree without a GPU): every field both sides have, over a set that holds both sides of every rule the mirrors restate."""
+    halo, slot = _planner_cases()
+    # the set itself, on the mirror alone: both sides of the halo-slot capacity edge (ner * (W + 2) = 448 at 7 x 6, 496 at 5 x 6), the
+    # `2 rem == G` edge of the tail rule, all four schedules; both windows, both answers of the automatic choice, the XCD rounding
+    assert (1, 7, 6, 8, 0, 0) in halo and (1, 5, 6, 8, 0, 0) in halo
+    assert R.halo_plan(1, 7, 6, 8)["eligible"] and not R.halo_plan(1, 5, 6, 8)["eligible"]
+    assert 256 // 6 + 2 + 2 * R.halo_plan(1, 7, 6, 8)["crossings"] == R.HALO_SLOTS // 8 and (256 // 6 + 2 + 2 * R.halo_plan(1, 5, 6, 8)["crossings"]) * 8 == 496
+    mirrors = [R.halo_plan(*c[:4], *_NO_HALF[c[4:]]) for c in halo]
+    ok = [p for p in mirrors if p["eligible"]]
+    for vf, flags in _NO_HALF.items():          # every exclusion changes some schedule of the set
+        assert not any(flags) or any(R.halo_plan(*c[:4], *flags) != R.halo_plan(*c[:4]) for c in halo if c[4:] == vf), vf
+    assert {p["schedule"] for p in ok} == {"all_half", "whole_rounds", "half_tail", "whole_partial"}
+    assert any(p["schedule"] == "half_tail" and 2 * (p["ntiles"] % p["grid"]) == p["grid"] for p in ok)
+    assert any(2 * p["ntiles"] == lim for p, (_, _, _, lim, _, _) in zip(mirrors, halo) if p["eligible"])          # the `<=` of the all-half rule
+    assert any(not p["eligible"] and "R" in p for p in mirrors) and any("R" not in p for p in mirrors)
+    smirrors = [R.slot_plan(B, H, W, cout, ktot, stride2=bool(s2), cu_limit=lim) for (B, H, W, cout, ktot, s2, lim, _) in slot]
+    sok = [p for p in smirrors if p["eligible"]]
+    assert {p["wide"] for p in sok} == {False, True} and {p["auto"] for p in sok} == {False, True}
+    assert {1, 7, 8, 12, 16, 64, 68, 72} <= {p["ns3_plan"] for p in sok} and any(p["ns3"] < p["ns3_plan"] for p in sok)
+    assert any(p["nchunks"] == 8 * (248 // 8) for p in sok)                                                # the `<` of the automatic choice, at 31 splits
+
+    import launch_trace
+    run = launch_trace.build("conv_launch_trace", launch_trace.CONV_SOURCES)
+    text = "".join("halo %d %d %d %d %d %d\n" % c for c in halo) + "".join("slot %d %d %d %d %d %d %d %d\n" % c for c in slot)
+    lines = run("plans", stdin=text)
+    assert len(lines) == len(halo) + len(slot)
+    fields = lambda line: {k: v for k, v in (kv.split("=", 1) for kv in line.split()[1:])}
+    for case, want, line in zip(halo, mirrors, lines):
+        got = fields(line)
+        assert line.startswith("halo ") and tuple(int(got[k]) for k in ("B", "H", "W", "cu", "variant", "fold")) == case
+        assert bool(int(got["eligible"])) == want["eligible"], (case, line)
+        if want["eligible"]:
+            mine = (want["R"], want["ntiles"], want["rows"], want["nfull"], want["nhalf"], want["grid"])
+            assert tuple(int(got[k]) for k in ("R", "ntiles", "rows", "nfull", "nhalf", "grid")) == mine, (case, want, line)
+    for case, want, line in zip(slot, smirrors, lines[len(halo):]):
+        got = fields(line)
+        assert line.startswith("slot ") and tuple(int(got[k]) for k in ("B", "H", "W", "cout", "ktot", "stride2", "cu", "forced")) == case
+        assert bool(int(got["eligible"])) == (want["eligible"] and (case[-1] != 0 or want["auto"])), (case, line)      # forced 0: the work floor decides too
+        if int(got["eligible"]):
+            mine = (want["wide"], want["nchunks"], want["auto"], want["ns3_plan"], want["ns3"], want["grid"])
+            theirs = (bool(int(got["wide"])), int(got["nchunks"]), bool(int(got["auto"])), int(got["ns_cu"]), int(got["ns"]), tuple(int(v) for v in got["grid"].split(",")))
+            assert theirs == mine, (case, want, line)
 
 
 def test_halo_plan_by_hand():

@@ -12,6 +12,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import launch_trace  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -913,42 +916,14 @@ def test_counter_records_are_keyed_per_template_instantiation():
 
 @pytest.fixture(scope="module")
 def gn_launch_trace():
-    """tools/gn_launch_trace.cpp built against the tree's gn_silu.hip (host objects + a stand-in HIP runtime, no GPU, about half a minute):
-    returns run(which) -> the trace lines."""
-    import shutil
-    import tempfile
-    csrc = os.path.join(ROOT, "generative_models_amd", "csrc")
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not found")
-    rocm = Path(os.path.realpath(hipcc)).parent.parent
-    llvm = next((d for d in (rocm / "llvm" / "bin", rocm / "lib" / "llvm" / "bin") if (d / "clang++").exists()), None)
-    if llvm is None:
-        pytest.skip("clang++ of the ROCm toolchain not found")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    with tempfile.TemporaryDirectory() as tmp:
-        jobs = [[hipcc] + flags + ["-c", os.path.join(csrc, src + ".hip"), "-o", os.path.join(tmp, src + ".o")] for src in ("gn_silu", "gmk_common")]
-        jobs.append([hipcc] + flags + ["--cuda-device-only", "--no-gpu-bundle-output", "-c", os.path.join(csrc, "gn_silu.hip"), "-o", os.path.join(tmp, "gn_silu.co")])
-        procs = [subprocess.Popen(j, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for j in jobs]
-        for pr in procs:
-            out = pr.communicate(timeout=900)[0]
-            assert pr.returncode == 0, out[-2000:]
-        notes = os.path.join(tmp, "notes.txt")
-        with open(notes, "w") as f:
-            subprocess.run([str(llvm / "llvm-readelf"), "--notes", os.path.join(tmp, "gn_silu.co")], stdout=f, check=True, timeout=120)
-        exe = os.path.join(tmp, "gn_launch_trace")
-        r = subprocess.run([str(llvm / "clang++"), "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I" + str(rocm / "include"),
-                            os.path.join(ROOT, "tools", "gn_launch_trace.cpp"), os.path.join(ROOT, "tools", "launch_trace_stub.cpp"),
-                            os.path.join(tmp, "gn_silu.o"), os.path.join(tmp, "gmk_common.o"), "-o", exe], capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
+    """tools/gn_launch_trace.cpp against the tree's gn_silu.hip (about half a minute)"""
+    return launch_trace.build("gn_launch_trace", ("gn_silu", "gmk_common"))
 
-        def run(which):
-            env = {k: v for k, v in os.environ.items() if k != "GMK_GN_KERNEL"}
-            r = subprocess.run([exe, which], capture_output=True, text=True, timeout=600, env=dict(env, LAUNCH_TRACE_NOTES=notes))
-            assert r.returncode == 0, r.stderr[-2000:]
-            return r.stdout.splitlines()
-        yield run
+
+@pytest.fixture(scope="module")
+def conv_launch_trace():
+    """tools/conv_launch_trace.cpp against the tree's six convolution sources (a minute or two)"""
+    return launch_trace.build("conv_launch_trace", launch_trace.CONV_SOURCES)
 
 
 def test_groupnorm_dispatch_landmarks(gn_launch_trace):
@@ -989,3 +964,83 @@ def test_groupnorm_dispatch_landmarks(gn_launch_trace):
         assert rows[("gn_pair_fwd_ok", F16, -1, HW)]["rc"] == ("1" if HW == 256 else "0")
         assert rows[("gn_pair_ok", BF16, F16, HW)]["rc"] == ("1" if HW in (256, 1024) else "0")
         assert rows[("gn_pair_ok", F16, F16, HW)]["rc"] == "0"      # fp16 gradients: never
+
+
+def test_conv_dispatch_landmarks(conv_launch_trace):
+    """The routes that the comments of the convolution sources and DESIGN.md quote, read off the host dispatch itself (C = 128, B = 2048, fp16
+    activations beside bf16 gradients, and the fp32 twin, at the U-Net's 8 x 8 ... 64 x 64): which kernel and instantiation, the id
+    gmk_last_kernel reports, and that the three predicates answer 1 exactly where the matching launch takes that route."""
+    rows = {}
+    for line in conv_launch_trace("landmarks"):
+        assert "no-metadata" not in line
+        head, _, tail = line.partition(" -> ")
+        words = head.split()
+        call = dict(kv.split("=", 1) for kv in words[1:] if "=" in kv)
+        f = dict(kv.split("=", 1) for kv in re.sub(r'err="[^"]*"', "", tail).split() if "=" in kv)      # rc, kernel, and the last launch's grid / block
+        f["launches"] = re.findall(r"launch=(\S+)", tail)
+        tag = words[1] if "=" not in words[1] else ""
+        rows[(words[0], tag, int(call.get("dtype", -1)), call["grid"])] = f
+    F32, BF16, F16 = 0, 1, 2
+    # template arguments after the type: conv3x3_halo_ws_kernel<T, prefetch, shape, fuse, skip, stamp, merge, res, ring4>
+    targs = lambda name: [int(v.replace("n", "-")) for v in re.findall(r"L[ib](n?\d+)E", name)]
+    for S in (8, 16, 32, 64):
+        g, half = "%dx%d" % (S, S), "%dx%d" % (S // 2, S // 2)
+        ring4 = S < 64                                   # a tile's halo within 384 slots
+        for dt, ty in ((F16, "DF16_"), (BF16, "DF16b")):
+            for tag, want in (("plain", [1, 16, 0, 0, 0, 0, 0, int(ring4)]), ("two-sources", [1, 16, 0, 0, 0, 0, 0, int(ring4)]), ("residual", [1, 16, 0, 0, 0, 0, 1, 0]),
+                              ("upsample", [1, 16, 0, 0, 0, 0, 0, int(ring4)])):
+                r = rows[("conv_igemm", tag, dt, g)]
+                assert (r["rc"], r["kernel"], r["block"]) == ("0", "4", "512,1,1") and len(r["launches"]) == 1, (tag, dt, S, r)
+                assert "conv3x3_halo_ws_kernelI" + ty in r["launches"][0] and targs(r["launches"][0]) == want, (tag, dt, S, r["launches"])
+            # the stride-2 convolution: im2col (LDS-DMA from 256 x 512 rows)
+            r = rows[("conv_igemm", "stride2", dt, half)]
+            assert (r["kernel"], "conv_igemm_dma_kernelI" + ty in r["launches"][0]) == (("2", True) if S > 8 else ("1", False)), (dt, S, r)
+            # its data gradient: the sub-pixel kernel where the low-resolution grid fits a halo tile, else the halo kernel on the zero-stuffed source;
+            # under GMK_CONV_KERNEL=2 four parity phases of the LDS-DMA kernel
+            r = rows[("conv_igemm", "transposed", dt, g)]
+            if S > 8:
+                assert r["kernel"] == "9" and r["launches"] == [next(n for n in r["launches"] if "conv_subpixel_ws_kernelI" + ty + "Li1E" in n)], (dt, S, r)
+            else:
+                assert r["kernel"] == "5" and "conv3x3_halo_ws_kernelI" + ty in r["launches"][0] and targs(r["launches"][0])[6] == 1, (dt, S, r)
+            r = rows[("conv_igemm", "transposed-choice2", dt, g)]
+            assert r["kernel"] == "6" and len(r["launches"]) == 4 and all("conv_igemm_dma_kernelI" + ty in n for n in r["launches"]), (dt, S, r)
+            # Upsample in its sub-pixel form, and the predicate that offers it
+            r, ok = rows[("conv_subpixel", "", dt, g)], rows[("conv_subpixel_ok", "", dt, g)]["rc"]
+            assert ok == ("1" if S > 8 else "0") and (r["rc"] == "0") == (ok == "1"), (dt, S, r, ok)
+            if ok == "1":
+                assert r["kernel"] == "8" and "conv_subpixel_ws_kernelI" + ty + "Li0E" in r["launches"][0], (dt, S, r)
+            # conv2 with the folded 1x1 skip: +skip, merged sub-phases up to 32 x 32
+            r, ok = rows[("conv3x3_skipfold", "", dt, g)], rows[("conv3x3_skipfold_ok", "", -1, g)]["rc"]
+            assert ok == "1" and r["rc"] == "0" and r["kernel"] == "7", (dt, S, r)
+            assert "conv3x3_halo_ws_kernelI" + ty in r["launches"][0] and targs(r["launches"][0]) == [1, 16, 0, 1, 0, int(S < 64), 0, 0], (dt, S, r["launches"])
+            r = rows[("conv1x1_pair", "", dt, g)]
+            assert r["kernel"] == "14" and "conv1x1_pair_stream_kernelI" + ty in r["launches"][0] and r["grid"] == "256,1,1", (dt, S, r)
+        # the fused GroupNorm-apply and its predicate
+        r, ok = rows[("conv_igemm", "gn", F16, g)], rows[("conv_gn_fusable", "", -1, g)]["rc"]
+        assert ok == ("1" if S > 8 else "0") and (r["rc"] == "0") == (ok == "1"), (S, r, ok)
+        if ok == "1":
+            assert r["kernel"] == "4" and targs(r["launches"][0]) == [1, 16, 1, 0, 0, 0, -1, 0], (S, r)
+        # weight gradients, bf16 beside fp16 activations: slots for the 3x3 forms (the 128-slot window at 64 x 64, four planes for stride 2), a stream for the skip
+        slot = lambda look, share, s2: "conv_wgrad_slots_ws_kernelILi%dELb1ELb%dELb%dEE" % (look, share, s2)
+        look = 2 if S == 64 else 1
+        for tag, grid, kernel, name in (("3x3", g, "13", slot(look, 1, 0)), ("3x3-two-sources", g, "13", slot(look, 1, 0)), ("upsample", g, "13", slot(look, 0, 0)),
+                                        ("stride2", half, "17" if S > 8 else "11", slot(1, 1, 1) if S > 8 else "conv_wgrad_kernelIDF16bDF16_Lb0EE"),
+                                        ("skip-1x1", g, "15", "conv1x1_wgrad_stream_kernelIDF16_E")):
+            r = rows[("conv_wgrad", tag, BF16, grid)]
+            assert r["rc"] == "0" and r["kernel"] == kernel and name in r["launches"][0] and "wgrad_reduce_kernel" in r["launches"][1], (tag, S, r)
+        assert rows[("conv_wgrad_subpixel_ok", "", -1, g)]["rc"] == "1"
+        r = rows[("conv_wgrad_subpixel", "", -1, g)]
+        assert r["kernel"] == "16" and "conv_wgrad_subpixel_ws_kernelILb1EE" in r["launches"][0] and len(r["launches"]) == 3, (S, r)
+        # the fp32 twin: im2col everywhere (the register-staged kernel where a buffer passes 2^32 bytes), phases for the transposed form, no halo family
+        big = S == 64
+        for tag in ("plain", "residual", "two-sources", "upsample"):
+            r = rows[("conv_igemm", tag, F32, g)]
+            assert r["kernel"] == ("1" if big else "2") and ("conv_igemm_kernelIfLb0E" if big else "conv_igemm_dma_kernelIfLb0E") in r["launches"][0], (tag, S, r)
+        r = rows[("conv_igemm", "transposed", F32, g)]
+        assert (r["kernel"], len(r["launches"])) == (("1", 1) if big else ("6", 4)), (S, r)
+        assert rows[("conv_subpixel", "", F32, g)]["rc"] == "-1" and rows[("conv_subpixel_ok", "", F32, g)]["rc"] == "0"
+        assert rows[("conv3x3_skipfold", "", F32, g)]["rc"] == "-1"
+        assert rows[("conv1x1_pair", "", F32, g)]["kernel"] == ("1" if big else "2")
+        for tag, grid in (("3x3", g), ("stride2", half), ("upsample", g), ("skip-1x1", g)):
+            r = rows[("conv_wgrad", tag, F32, grid)]
+            assert r["kernel"] == "11" and "conv_wgrad_kernelIffLb0E" in r["launches"][0], (tag, S, r)

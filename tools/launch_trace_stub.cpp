@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <map>
 #include <string>
@@ -40,11 +41,11 @@ const std::vector<Arg>* args_of(const std::string& kernel) {
     return it == table.end() ? nullptr : &it->second;
 }
 std::string g_log;
-struct Pad { size_t arg_size, offset, len; };
+struct Pad { std::string kernel_part; size_t arg_size, offset, len; };
 std::vector<Pad> g_pads;
-bool is_padding(size_t arg_size, size_t b) {
+bool is_padding(const char* kernel, size_t arg_size, size_t b) {
     for (const Pad& p : g_pads)
-        if (p.arg_size == arg_size && b >= p.offset && b < p.offset + p.len) return true;
+        if (p.arg_size == arg_size && b >= p.offset && b < p.offset + p.len && strstr(kernel, p.kernel_part.c_str())) return true;
     return false;
 }
 struct { dim3 grid, block; size_t lds; hipStream_t stream; } g_cfg;
@@ -65,7 +66,13 @@ const char* name_of(const void* f) {
 // what the stand-in saw since the last call (declared by the tracing program)
 std::string launch_trace_take() { std::string s; s.swap(g_log); return s; }
 // padding bytes of a struct passed by value (indeterminate on the host): printed as "--" in every by-value argument of that size
-void launch_trace_padding(size_t arg_size, size_t offset, size_t len) { g_pads.push_back({arg_size, offset, len}); }
+void launch_trace_padding(size_t arg_size, size_t offset, size_t len) { g_pads.push_back({"", arg_size, offset, len}); }
+// the same for bytes a launch leaves unset, in the kernels whose name contains kernel_part only; launch_trace_unmask drops that part's ranges
+void launch_trace_mask(const char* kernel_part, size_t arg_size, size_t offset, size_t len) { g_pads.push_back({kernel_part, arg_size, offset, len}); }
+void launch_trace_unmask(const char* kernel_part) {
+    for (size_t i = g_pads.size(); i-- > 0;)
+        if (g_pads[i].kernel_part == kernel_part) g_pads.erase(g_pads.begin() + i);
+}
 
 extern "C" {
 void** __hipRegisterFatBinary(const void*) { static void* handle; return &handle; }
@@ -85,7 +92,7 @@ hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, si
     for (size_t i = 0; i < layout->size(); ++i) {
         logf("%s%zu:", i ? "," : "", (*layout)[i].offset);
         for (size_t b = 0; b < (*layout)[i].size; ++b) {
-            if (is_padding((*layout)[i].size, b)) { g_log += "--"; continue; }
+            if (is_padding(name, (*layout)[i].size, b)) { g_log += "--"; continue; }
             const unsigned char v = ((const unsigned char*)args[i])[b];
             g_log += "0123456789abcdef"[v >> 4];
             g_log += "0123456789abcdef"[v & 15];
