@@ -1,12 +1,14 @@
 """ctypes binding of libgmk.so, generated from include/gmk.h at import time.
 
-The prototypes are parsed from the header the library was compiled against, so the Python side can never
-drift from the C ABI.  There is no fallback: if the shared library is missing or a symbol is absent the
-import fails loudly (the product path must not silently run on anything else).
+The prototypes, the integer `#define GMK_*` constants and the kernel table are parsed from the header the library
+was compiled against, so the Python side can never drift from the C ABI.  There is no fallback: if the shared
+library is missing or a symbol is absent the import fails loudly (the product path must not silently run on
+anything else).
 """
 import ctypes
 import os
 import re
+import types
 
 import torch  # noqa: F401  (FIRST: libgmk.so must bind to the HIP runtime torch has loaded - two libamdhip64 copies in one process
 #                      do not share a device: a library loaded before torch reports "no ROCm-capable device" at its first launch)
@@ -33,10 +35,26 @@ def _ctype(decl):
     return _CTYPES[base]
 
 
+def _code(path):
+    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+
+
+def parse_constants(path=HEADER):
+    """-> {name: value} for every `#define GMK_<NAME> <integer>` of the header."""
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"^[ \t]*#define[ \t]+(GMK_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", _code(path), flags=re.M)}
+
+
+def parse_kernel_table(path=HEADER):
+    """-> [(symbol, id, profile name)], the rows of GMK_KERNEL_TABLE in the header's order."""
+    body = re.search(r"#define[ \t]+GMK_KERNEL_TABLE\(X\)((?:[^\n]*\\\n)*[^\n]*)", _code(path)).group(1)
+    rows = [(m.group(1), int(m.group(2)), m.group(3)) for m in re.finditer(r'X\(\s*(\w+)\s*,\s*(\d+)\s*,\s*"([^"]*)"\s*\)', body)]
+    assert rows and len({i for _, i, _ in rows}) == len({s for s, _, _ in rows}) == len(rows), "GMK_KERNEL_TABLE: no rows, or an id or symbol twice"
+    return rows
+
+
 def parse_header(path=HEADER):
     """-> {name: (restype, [argtypes], [argnames])} for every prototype in the header."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = _code(path)
     protos = {}
     for m in re.finditer(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(gmk_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.M | re.S):
         ret, name, args = m.group(1), m.group(2), m.group(3)
@@ -71,6 +89,15 @@ def _load():
 
 
 lib, PROTOS = _load()
+C = parse_constants()                                                   # C["GMK_BF16"] == 1 ...: a missing name is a KeyError at import
+_KERNELS = parse_kernel_table()
+K = types.SimpleNamespace(**{sym: kid for sym, kid, _ in _KERNELS})     # K.CONV_HALO_WS == 4 ...: the GMK_K_* ids
+_KERNEL_NAMES = {kid: name for _, kid, name in _KERNELS}
+
+
+def kernel_name(kid):
+    """Profile name of a kernel id (gmk_last_kernel), None for 0 or an id outside the table: gmk_kernel_name without the call."""
+    return _KERNEL_NAMES.get(kid)
 
 
 def check(rc, what=""):

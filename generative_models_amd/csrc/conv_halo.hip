@@ -1988,6 +1988,6 @@ extern "C" int gmk_conv3x3_skipfold(const void* src, int c0, int B, int H, int W
     };
     if (dtype == GMK_F16) launch(f16_t{});
     else launch(bf16_t{});
-    gmk_note_kernel(7);
+    gmk_note_kernel(GMK_K_CONV_HALO_SKIPFOLD);
     return gmk_check_launch("gmk_conv3x3_skipfold");
 }

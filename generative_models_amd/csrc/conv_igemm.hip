@@ -1182,11 +1182,11 @@ static int conv_igemm_impl(const void* src0, const void* src1, int c0, int c1, i
     if (r.route == GMK_ROUTE_HALO) {
         const int rc = gmk_conv3x3_halo_try(src0, src1, c0, c1, B, ho, wo, w, w_rows, n0, cout, bias, emb, emb_stride, residual, out, out_cstride,
                                             r.halo_min_tiles, r.halo_upsample, gn_stats, gn_stats_bytes, gn_scale, gn_shift, gn_stride, dtype, stream);
-        gmk_note_kernel(r.stuffed ? 5 : rc == 2 ? 4 : 3);       // 5: a halo kernel on the zero-stuffed source (transposed conv)
+        gmk_note_kernel(r.stuffed ? GMK_K_CONV_HALO_STUFFED : rc == 2 ? GMK_K_CONV_HALO_WS : GMK_K_CONV_HALO);
         return gmk_check_launch("gmk_conv_igemm(halo)");
     }
     if (r.route == GMK_ROUTE_PHASES) {
-        gmk_note_kernel(6);
+        gmk_note_kernel(GMK_K_CONV_DMA_PHASES);
         for (int ph = 0; ph < 4; ++ph) {
             ConvParams q = p;
             make_phase_gather(ph >> 1, ph & 1, hs, ws, ho, wo, &q.g);
@@ -1204,7 +1204,7 @@ static int conv_igemm_impl(const void* src0, const void* src1, int c0, int c1, i
         return conv_igemm_impl(src0, src1, c0, c1, B, hs, ws, ho, wo, ksize, mode, w, w_rows, n0 + cout, cout, bias, emb, emb_stride,
                                residual, out2, nullptr, out_cstride, nullptr, 0, nullptr, nullptr, 0, dtype, stream);
     }
-    gmk_note_kernel(r.route == GMK_ROUTE_DMA ? 2 : 1);
+    gmk_note_kernel(r.route == GMK_ROUTE_DMA ? GMK_K_CONV_IGEMM_DMA : GMK_K_CONV_IGEMM);
     if (r.route == GMK_ROUTE_DMA) launch_conv_dma(p, r, cout, dtype, stream);
     else {
         const dim3 grid((p.M + kBM - 1) / kBM, cout / kBN);
@@ -1232,7 +1232,7 @@ extern "C" int gmk_conv1x1_pair(const void* src, int c, int B, int H, int W, con
     if (c == 128 && B > 0 && H > 0 && W > 0) {             // the streaming form for the train step's sizes (conv1x1_stream.hip)
         const size_t es = 2;
         if (gmk_conv1x1_pair_stream_try(src, (int64_t)B * H * W, (const char*)w + (size_t)n0 * 128 * es, out_a, out_b, dtype, stream)) {
-            gmk_note_kernel(14);
+            gmk_note_kernel(GMK_K_CONV1X1_PAIR_STREAM);
             return gmk_check_launch("gmk_conv1x1_pair(stream)");
         }
     }
@@ -1280,7 +1280,7 @@ extern "C" int gmk_conv_wgrad(const void* dy, int dy_cstride, const void* src0, 
         // the skip convolution over the concatenated input at the train step's sizes: one workgroup per pixel range owns both input blocks
         const int ns1 = gmk_conv1x1_wgrad_stream_try(dy, dy_cstride, src0, src1, (int64_t)B * ho * wo, (float*)workspace, workspace_bytes, xf16, stream);
         if (ns1 > 0) {
-            gmk_note_kernel(15);
+            gmk_note_kernel(GMK_K_CONV1X1_WGRAD_STREAM);
             return wgrad_reduce("gmk_conv_wgrad(1x1 stream)", (const float*)workspace, dw, ns1, 1, cout, 256, stream);
         }
     }
@@ -1291,7 +1291,7 @@ extern "C" int gmk_conv_wgrad(const void* dy, int dy_cstride, const void* src0, 
     GMK_REQUIRE(workspace_bytes >= need, "gmk_conv_wgrad: workspace %lld < %lld bytes", (long long)workspace_bytes,
                 (long long)need);
     p.slab = (float*)workspace;
-    gmk_note_kernel(11);
+    gmk_note_kernel(GMK_K_CONV_WGRAD);
     p.ns = ns; p.taps = taps; p.order = (gmk_kernel_choice(3, "GMK_DEV_VARIANT") & 0xFF) == 61;
     dim3 grid((ns + 7) / 8 * 8 * taps * (cout / 128) * (p.ktot / 128));
     if (dtype == GMK_BF16 && xf16) conv_wgrad_kernel<bf16_t, f16_t><<<grid, 256, 0, gmk_stream(stream)>>>(p);

@@ -2,13 +2,7 @@
 // planners here take shapes, storage types, the kernel-choice switches and the CU limit, touch no pointer and launch nothing, so
 // tools/conv_launch_trace.cpp can print what they return on a machine without a GPU.  The .hip file named beside each one defines it and
 // launches from it.  (The halo and 1x1-stream launchers pick their instantiation themselves, from the geometry and schedule below.)
-//
-// Kernel ids the launchers pass to gmk_note_kernel (gmk_last_kernel reports them):
-//   1 conv_igemm_kernel, 2 conv_igemm_dma_kernel, 3 conv3x3_halo_kernel, 4 conv3x3_halo_ws_kernel, 5 a halo kernel on a zero-stuffed
-//   source, 6 stride-2 dgrad as four phase launches of the LDS-DMA kernel, 7 halo kernel with the folded 1x1 skip convolution,
-//   8 / 9 / 10 conv_subpixel_ws_kernel (upsample / transposed / upsample data gradient), 11 conv_wgrad_kernel,
-//   12 conv_wgrad_slots_kernel, 13 conv_wgrad_slots_ws_kernel, 14 / 15 conv1x1_pair_stream_kernel / conv1x1_wgrad_stream_kernel,
-//   16 conv_wgrad_subpixel_ws_kernel, 17 conv_wgrad_slots_ws_kernel in its stride-2 four-plane form
+// The kernel ids the launchers report (GMK_K_*) are those of include/gmk.h's GMK_KERNEL_TABLE.
 #pragma once
 #include <stdint.h>
 
@@ -79,7 +73,7 @@ ConvRoutePlan gmk_conv_route(const ConvCall& c, int conv_choice, bool subpixel_o
 // ---- weight gradients ---------------------------------------------------------------------------------------------------------------------
 // Common shape: ok, the kernel id, the split count (= slabs written), its grid and the slab bytes the launch needs
 struct SlotPlan {      // conv_wgrad_slots.hip: 3x3 bf16 weight gradient over padded slots
-    int kernel;                 // 12 the 8-compute-wave kernel, 13 the wave-specialised one, 17 its stride-2 four-plane form
+    int kernel;                 // GMK_K_CONV_WGRAD_SLOTS (8 compute waves), ..._SLOTS_WS (wave-specialised) or ..._SLOTS_S2 (its stride-2 four-plane form)
     bool wide, share;           // 128-slot window (rows beyond 62 pixels); dY slot and X slot are the same pixel
     bool auto_ok;               // enough chunks per split for the automatic choice (else the im2col kernel unless forced)
     int WE, RE, nchunks;
@@ -96,10 +90,10 @@ int gmk_conv_wgrad_slots_try(const void* dy, int dy_cstride, const void* src0, c
                              int W, int cout, float* slab, int64_t slab_bytes, int forced, int upsample, bool x_f16,
                              void* stream, int stride2 = 0);
 
-struct SubWgradPlan { int ns, cps, nchunks; int grid[3]; int64_t slab_bytes; };      // conv_wgrad_subpixel.hip (kernel 16)
+struct SubWgradPlan { int ns, cps, nchunks; int grid[3]; int64_t slab_bytes; };      // conv_wgrad_subpixel.hip (GMK_K_CONV_WGRAD_SUBPIXEL)
 int gmk_wgrad_subpixel_plan(int B, int H, int W, int cin, int cout, int dy_cstride, int cu_limit, SubWgradPlan* plan);
 
-// conv1x1_stream.hip: the skip convolution's pair of outputs (kernel 14) and its weight gradient (kernel 15) at the train step's sizes
+// conv1x1_stream.hip: the skip convolution's pair of outputs (GMK_K_CONV1X1_PAIR_STREAM) and its weight gradient (GMK_K_CONV1X1_WGRAD_STREAM) at the train step's sizes
 int gmk_conv1x1_pair_stream_try(const void* src, int64_t npix, const void* w_rows256, void* out_a, void* out_b, int dtype, void* stream);      // 1 if launched
 int gmk_conv1x1_wgrad_stream_try(const void* dy, int dy_cstride, const void* src0, const void* src1, int64_t npix, float* slab, int64_t slab_bytes,
                                  bool x_f16, void* stream);        // > 0 = slabs written

@@ -548,6 +548,6 @@ extern "C" int gmk_conv_subpixel(const void* src, int B, int H, int W, int cin, 
     if (mode == GMK_SUBPIXEL_UPSAMPLE) launch(IntTag<0>{});
     else if (mode == GMK_SUBPIXEL_TRANSPOSED) launch(IntTag<1>{});
     else launch(IntTag<2>{});
-    gmk_note_kernel(mode == GMK_SUBPIXEL_UPSAMPLE ? 8 : mode == GMK_SUBPIXEL_TRANSPOSED ? 9 : 10);
+    gmk_note_kernel(mode == GMK_SUBPIXEL_UPSAMPLE ? GMK_K_CONV_SUBPIXEL_UPSAMPLE : mode == GMK_SUBPIXEL_TRANSPOSED ? GMK_K_CONV_SUBPIXEL_TRANSPOSED : GMK_K_CONV_SUBPIXEL_UPSAMPLE_DGRAD);
     return gmk_check_launch("gmk_conv_subpixel");
 }

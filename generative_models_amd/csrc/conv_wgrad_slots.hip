@@ -690,7 +690,7 @@ int gmk_wgrad_slot_plan(int B, int H, int W, int c0, int c1, int cout, int dy_cs
     // forced: 0 automatic = 3 the wave-specialised kernel (1.37 - 1.58 x the 8-compute-wave kernel at every shape of the train step:
     // docs/EXPERIMENTS.md 7b.11); 2 the 8-compute-wave kernel (A/B)
     if (forced == 2) {
-        plan->kernel = 12; plan->ns_cu = plan->ns = ns; plan->cps = cps; plan->slab_bytes = slab8;
+        plan->kernel = GMK_K_CONV_WGRAD_SLOTS; plan->ns_cu = plan->ns = ns; plan->cps = cps; plan->slab_bytes = slab8;
         plan->grid[0] = ns; plan->grid[1] = ktot / 64; plan->grid[2] = cout / 128;
         return 1;
     }
@@ -701,7 +701,7 @@ int gmk_wgrad_slot_plan(int B, int H, int W, int c0, int c1, int cout, int dy_cs
     plan->ns = ns3 = (nchunks + plan->cps - 1) / plan->cps;
     const int64_t slab3 = (int64_t)ns3 * 9 * cout * ktot * 4;
     plan->slab_bytes = slab3 > slab8 ? slab3 : slab8;      // (the 8-compute-wave kernel's slabs are asked for as well: gmk_conv_wgrad_workspace_bytes covers both)
-    plan->kernel = stride2 ? 17 : 13;
+    plan->kernel = stride2 ? GMK_K_CONV_WGRAD_SLOTS_S2 : GMK_K_CONV_WGRAD_SLOTS_WS;
     plan->share = !upsample;          // dY slot S and X slot S are the same pixel: decode once (kShare)
     plan->grid[0] = ns3; plan->grid[1] = ytiles; plan->grid[2] = cout / 64;
     return 1;
@@ -727,9 +727,9 @@ int gmk_conv_wgrad_slots_try(const void* dy, int dy_cstride, const void* src0, c
     const bool f = x_f16, s = pl.share;
 #define GMK_SLOT_WS conv_wgrad_slots_ws_kernel
     void (*const k)(const SlotParams) =
-        pl.kernel == 17 ? (f ? GMK_SLOT_WS<1, true, true, true> : GMK_SLOT_WS<1, false, true, true>)
-        : pl.kernel == 13 && pl.wide ? (f ? (s ? GMK_SLOT_WS<2, true, true> : GMK_SLOT_WS<2, true, false>) : (s ? GMK_SLOT_WS<2, false, true> : GMK_SLOT_WS<2, false, false>))
-        : pl.kernel == 13 ? (f ? (s ? GMK_SLOT_WS<1, true, true> : GMK_SLOT_WS<1, true, false>) : (s ? GMK_SLOT_WS<1, false, true> : GMK_SLOT_WS<1, false, false>))
+        pl.kernel == GMK_K_CONV_WGRAD_SLOTS_S2 ? (f ? GMK_SLOT_WS<1, true, true, true> : GMK_SLOT_WS<1, false, true, true>)
+        : pl.kernel == GMK_K_CONV_WGRAD_SLOTS_WS && pl.wide ? (f ? (s ? GMK_SLOT_WS<2, true, true> : GMK_SLOT_WS<2, true, false>) : (s ? GMK_SLOT_WS<2, false, true> : GMK_SLOT_WS<2, false, false>))
+        : pl.kernel == GMK_K_CONV_WGRAD_SLOTS_WS ? (f ? (s ? GMK_SLOT_WS<1, true, true> : GMK_SLOT_WS<1, true, false>) : (s ? GMK_SLOT_WS<1, false, true> : GMK_SLOT_WS<1, false, false>))
         : pl.wide ? conv_wgrad_slots_kernel<2> : conv_wgrad_slots_kernel<1>;      // 12
 #undef GMK_SLOT_WS
     k<<<grid, 512, 0, st>>>(p);

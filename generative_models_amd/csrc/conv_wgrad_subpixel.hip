@@ -361,6 +361,6 @@ extern "C" int gmk_conv_wgrad_subpixel(const void* dy, int dy_cstride, const voi
     float* G = p.slab + (int64_t)2 * pl.ns * per;
     subpixel_split_reduce_kernel<<<dim3((unsigned)((per / 4 + 255) / 256), 2), 256, 0, st>>>(p.slab, G, pl.ns, (int)per);
     subpixel_taps_kernel<<<(cout * cin + 255) / 256, 256, 0, st>>>(G, dw, cout * cin);
-    gmk_note_kernel(16);
+    gmk_note_kernel(GMK_K_CONV_WGRAD_SUBPIXEL);
     return gmk_check_launch("gmk_conv_wgrad_subpixel");
 }

@@ -16,7 +16,7 @@
 
 #include "gmk_common.h"
 
-#define GMK_REQUIRE_MEAN_TYPE(mt, who) GMK_REQUIRE((mt) >= 0 && (mt) <= 2, who ": mean_type must be 0 (v), 1 (eps) or 2 (x)")
+#define GMK_REQUIRE_MEAN_TYPE(mt, who) GMK_REQUIRE((mt) >= GMK_MEAN_V && (mt) <= GMK_MEAN_X, who ": mean_type must be 0 (v), 1 (eps) or 2 (x)")
 
 namespace {
 
@@ -82,9 +82,9 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
 // the network output parametrises x (gaussian_diffusion.py:58-73): mean_type 0 'v' (predict_x_from_v), 1 'eps'
 // (predict_x_from_eps), 2 'x'; d x / d out is the second function
 __device__ __forceinline__ float x_from_out(float out, float zz, const LogsnrCoef& c, int mt) {
-    return mt == 0 ? c.alpha * zz - c.sigma * out : (mt == 1 ? c.d1 * (zz - out * c.d2) : out);
+    return mt == GMK_MEAN_V ? c.alpha * zz - c.sigma * out : (mt == GMK_MEAN_EPS ? c.d1 * (zz - out * c.d2) : out);
 }
-__device__ __forceinline__ float dx_dout(const LogsnrCoef& c, int mt) { return mt == 0 ? -c.sigma : (mt == 1 ? -c.d1 * c.d2 : 1.0f); }
+__device__ __forceinline__ float dx_dout(const LogsnrCoef& c, int mt) { return mt == GMK_MEAN_V ? -c.sigma : (mt == GMK_MEAN_EPS ? -c.d1 * c.d2 : 1.0f); }
 
 // one block per sample: loss and (optionally) d loss / d (network output)
 __global__ __launch_bounds__(256) void v_loss_kernel(const float* __restrict__ v, const float* __restrict__ z,
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void v_loss_kernel(const float* __restrict__ v
 // re-reads the residuals it wrote itself and zeroes those whose raw prediction left [-1, 1] (one bit per element, at most 48, in a register
 // pair).  Larger images are read again.  LDS: 4 min(n, kXLossKeep) bytes (12 KiB at 3 x 32 x 32, 48 KiB at the capacity) + 16 for block_sum,
 // all of it dynamic so that the 16-byte accesses stay aligned.
-constexpr int kXLossKeep = 12288;    // kDynKeys: covers 3 x 64 x 64
+constexpr int kXLossKeep = GMK_X_LOSS_KEEP;    // kDynKeys: covers 3 x 64 x 64
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void x_loss_w_kernel(const float* __restrict__ v, const float* __restrict__ z, const float* __restrict__ x,
@@ -586,7 +586,7 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* __res
 // when hi == lo or at least k_lo + 2 keys are <= a[lo], else the smallest key above a[lo] (one more pass, an integer LDS min).  No floating-
 // point atomics; every loop's trip count depends on n alone, whatever the values (NaNs and infinities are keys like any other).
 // LDS: 48 KiB of keys + 4 KiB of histograms + 84 B = 53,332 B per workgroup, so three workgroups (12 waves) share a CU's 160 KiB.
-constexpr int kDynKeys = 12288;      // LDS-resident keys per image: covers 3 x 64 x 64
+constexpr int kDynKeys = GMK_DYN_THRESHOLD_KEYS;      // LDS-resident keys per image: covers 3 x 64 x 64
 
 // inclusive sum over the 16 lanes of a DPP row (row_shr:1, 2, 4, 8; a lane the shift leaves without a source adds 0)
 __device__ __forceinline__ uint32_t row_scan16(uint32_t v) {
@@ -789,7 +789,7 @@ __global__ __launch_bounds__(256) void q_sample_logsnr_kernel(const float* __res
 
 // the network's noise prediction, UNCLIPPED: 'v' sigma z + alpha out, 'eps' out, 'x' (z - alpha out) / sigma in predict_eps_from_x's form
 __device__ __forceinline__ float eps_from_out(float out, float zz, const LogsnrCoef& c, int mt) {
-    return mt == 0 ? c.sigma * zz + c.alpha * out : (mt == 1 ? out : c.c1 * (zz - out * c.c2));
+    return mt == GMK_MEAN_V ? c.sigma * zz + c.alpha * out : (mt == GMK_MEAN_EPS ? out : c.c1 * (zz - out * c.c2));
 }
 
 // one block per sample: acc[b] += weight[b] * sum_i (eps - eps_hat)^2 (one read pass, v_loss_kernel's reduction: a fixed order, so
@@ -940,8 +940,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                   float* __restrict__ v, float* __restrict__ ema, const float* __restrict__ state,
                                                   int64_t n, float step_size, float beta1, float beta2, float eps, float inv_bc2_sqrt,
                                                   float grad_scale, float ema_w) {
-    if (CTL && state[2] == 0.0f) return;
-    const float coef = CTL ? state[1] : 1.0f;
+    if (CTL && state[GMK_APPLY] == 0.0f) return;
+    const float coef = CTL ? state[GMK_CLIP_COEF] : 1.0f;
     auto elem = [&](float& pp, float gk, float& mm, float& vv) {
         adam_elem(pp, CTL ? (gk * grad_scale) * coef : gk, mm, vv, step_size, beta1, beta2, eps, inv_bc2_sqrt, CTL ? 1.0f : grad_scale);
     };
@@ -1015,10 +1015,10 @@ __global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* __res
     if (threadIdx.x == 0) {
         const float total = grad_scale * sqrtf(s);
         const bool finite = isfinite(total);
-        state[0] = total;
-        state[1] = max_norm > 0.0f ? fminf(1.0f, max_norm / (total + 1e-6f)) : 1.0f;
-        state[2] = finite ? 1.0f : 0.0f;
-        state[3] = state[3] + (finite ? 0.0f : 1.0f);
+        state[GMK_GRAD_NORM] = total;
+        state[GMK_CLIP_COEF] = max_norm > 0.0f ? fminf(1.0f, max_norm / (total + 1e-6f)) : 1.0f;
+        state[GMK_APPLY] = finite ? 1.0f : 0.0f;
+        state[GMK_SKIPPED] = state[GMK_SKIPPED] + (finite ? 0.0f : 1.0f);
     }
 }
 
@@ -1131,7 +1131,7 @@ __global__ __launch_bounds__(256) void pf_ode_step_kernel(const float* __restric
 // values of a and of b per thread: 96 of the kernel's 114 registers at the capacity kSlerpKeep = 1024 x 12, four waves per SIMD, no scratch), so
 // a and b come from HBM once.  GROUPS == 0: any n, a and b are read again for every k.  (A second resident instantiation with GROUPS = 4 for
 // n <= 4096, 74 registers, measured 37.7 - 37.9 us against this one's 38.6 at B = 2048, n = 3072, K = 8: not kept.)
-constexpr int kSlerpKeep = 12288;    // kDynKeys, kXLossKeep: covers 3 x 64 x 64
+constexpr int kSlerpKeep = GMK_SLERP_KEEP;    // kDynKeys, kXLossKeep: covers 3 x 64 x 64
 
 template <int GROUPS>
 __global__ __launch_bounds__(256) void slerp_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ t,
@@ -1296,7 +1296,7 @@ extern "C" int gmk_u_importance(const float* state, const float* u0, float* u, f
 
 // The checks every entry that forms the (guided) prediction shares: the four gmk_*_step* entries, gmk_ddim_step_vec and gmk_dyn_threshold
 static int step_args_check(const char* who, int mean_type, const float* v_uncond, const float* cond_w, int B, int64_t n) {
-    GMK_REQUIRE(mean_type >= 0 && mean_type <= 2, "%s: mean_type must be 0 (v), 1 (eps) or 2 (x)", who);
+    GMK_REQUIRE(mean_type >= GMK_MEAN_V && mean_type <= GMK_MEAN_X, "%s: mean_type must be 0 (v), 1 (eps) or 2 (x)", who);
     GMK_REQUIRE((v_uncond == nullptr) == (cond_w == nullptr), "%s: v_uncond and cond_w go together", who);
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "%s: bad shape", who);
     return 0;

@@ -28,8 +28,7 @@ int gmk_check_launch(const char* what);   // returns 0 or the positive hipError_
 int gmk_kernel_choice(int which, const char* env);   // 0 conv (GMK_CONV_KERNEL), 1 wgrad (GMK_WGRAD_KERNEL), 2 GN
 bool fp32_split(void);                // fp32 mode: exact fp32 MFMA chains (default) or operands as bf16 hi + lo on the bf16 matrix cores (GMK_FP32_SPLIT=1 / gmk_set_fp32_exact(0))
 int gmk_cu_limit(void);                   // workgroups a persistent kernel may occupy (gmk_set_cu_limit / GMK_CU_LIMIT, default 256)
-void gmk_note_kernel(int id);             // 1 .. 17 the convolution kernels (listed in conv_plan.h),
-                                          // 21 gn_silu_fwd_reg_kernel, 22 gn_silu_fwd_kernel, 23 gn_silu_bwd_hybrid_kernel, 24 gn_silu_bwd_kernel, 25 gn_silu_bwd_pair_kernel, 26 gn_silu_fwd_pair_kernel
+void gmk_note_kernel(int id);             // a GMK_K_* of include/gmk.h's GMK_KERNEL_TABLE
 
 #define GMK_REQUIRE(cond, ...)                 \
     do {                                       \

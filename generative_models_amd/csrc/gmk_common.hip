@@ -26,10 +26,18 @@ int gmk_check_launch(const char* what) {
 extern "C" int gmk_version(void) { return 1; }
 extern "C" const char* gmk_last_error(void) { return g_err; }
 
-// which kernel the last gmk_conv_igemm / gmk_conv_wgrad call of this thread launched (profiling aid, see bench.py)
+// which kernel of GMK_KERNEL_TABLE this thread's last launcher reported (profiling aid, see bench.py)
 static thread_local int g_last_kernel = 0;
 void gmk_note_kernel(int id) { g_last_kernel = id; }
 extern "C" int gmk_last_kernel(void) { return g_last_kernel; }
+extern "C" const char* gmk_kernel_name(int id) {
+    switch (id) {
+#define GMK_K_CASE(symbol, num, name) case num: return name;
+        GMK_KERNEL_TABLE(GMK_K_CASE)
+#undef GMK_K_CASE
+    }
+    return nullptr;
+}
 
 // kernel-selection overrides (development / A-B measurement): -1 = unset (environment variable, then automatic)
 static int g_choice[4] = {-1, -1, -1, -1};

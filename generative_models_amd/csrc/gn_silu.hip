@@ -1205,7 +1205,7 @@ struct GnFwdPlan {
 };
 // mode: the forced kernel form (0 automatic); pow2_iter: mode 6's power-of-two pixels per thread, which gmk_gn_stats follows too
 GnFwdPlan gn_fwd_plan(int mode, bool pow2_iter, int dtype, int B, int HW, int C, int G, bool producer_stats) {
-    GnFwdPlan p = {GnFwdPlan::kStream, 0, 0, 0, kThreads, B, C, 22};
+    GnFwdPlan p = {GnFwdPlan::kStream, 0, 0, 0, kThreads, B, C, GMK_K_GN_FWD};
     if (gn_narrow(C, G)) { p.form = GnFwdPlan::kNarrow; return p; }
     const bool slabs = gmk_is16(dtype) && !producer_stats && 32 % (C / G) == 0;
     // 64 x 64 (HW up to 4096): a 32-channel slab of a sample is 256 KiB - the registers of ONE 1024-thread workgroup (16 pixels x 16 B per
@@ -1216,7 +1216,7 @@ GnFwdPlan gn_fwd_plan(int mode, bool pow2_iter, int dtype, int B, int HW, int C,
     const bool reg = slabs && (mode == 5 || mode == 6 || (mode == 0 && HW > 64)) && C % 64 == 0 && gn_reg_iter(pow2_iter, HW, 8) > 0;
     if (big || reg) {
         p.form = GnFwdPlan::kReg;
-        p.kernel = 21;
+        p.kernel = GMK_K_GN_FWD_REG;
         p.nvec = (big || mode == 5) ? 4 : 8;        // 32- or 64-channel slabs (64 = whole 128-B lines)
         p.it = big ? 16 : gn_reg_iter(pow2_iter, HW, p.nvec);
         p.planes = (HW + p.it - 1) / p.it;
@@ -1287,7 +1287,7 @@ GnBwdPlan gn_bwd_plan(int mode, int dtype, int B, int HW, int C, int G, bool dro
     const int cpg = narrow ? 1 : C / G;
     const bool slab32 = hybrid && C % 32 == 0 && 32 % cpg == 0;
     auto hyb = [&](GnBwdPlan::Row row, int threads, int CS, size_t lds, size_t lds_limit) {
-        return GnBwdPlan{row, threads, B * (C / CS), CS, lds, lds_limit, 23};
+        return GnBwdPlan{row, threads, B * (C / CS), CS, lds, lds_limit, GMK_K_GN_BWD_HYBRID};
     };
     if (slab32 && (mode == 0 || mode == 7) && HW > (mode == 7 ? 511 : 64) && HW <= 1024) {      // x parked in LDS: 64 B per pixel of a 32-channel slab
         const size_t lds = (size_t)HW * 64;
@@ -1304,7 +1304,7 @@ GnBwdPlan gn_bwd_plan(int mode, int dtype, int B, int HW, int C, int G, bool dro
     if (hybrid && (mode == 0 || mode == 7) && C % 16 == 0 && 16 % cpg == 0 && HW > 1024 && HW <= 4096)
         return hyb(GnBwdPlan::kHyb64Slab16, 1024, 16, (size_t)HW * 32, 4096 * 32);
     const int CS = gn_slab_channels(mode, C, G, HW, gmk_esize(dtype), true);
-    return GnBwdPlan{GnBwdPlan::kStream, kThreads, B * (C / CS), CS, 0, 0, 24};
+    return GnBwdPlan{GnBwdPlan::kStream, kThreads, B * (C / CS), CS, 0, 0, GMK_K_GN_BWD};
 }
 
 }  // namespace
@@ -1440,7 +1440,7 @@ extern "C" int gmk_gn_silu_fwd_pair(const void* x, void* y_a, void* y_b, const f
                 "gmk_gn_silu_fwd_pair: unsupported shape B=%d HW=%d C=%d G=%d,%d dtype=%d (gmk_gn_pair_fwd_ok)", B, HW, C, groups_a, groups_b, dtype);
     const GnFwdPlan p = gn_fwd_plan(0, false, dtype, B, HW, C, groups_a, false);      // the plan gmk_gn_pair_fwd_ok asked: <4, 8>, 512 threads
     const GnFwdSide sa = {y_a, gamma_a, beta_a, mean_a, rstd_a, groups_a}, sb = {y_b, gamma_b, beta_b, mean_b, rstd_b, groups_b};
-    gmk_note_kernel(26);
+    gmk_note_kernel(GMK_K_GN_FWD_PAIR);
     gmk_with_type<f16_t, bf16_t>(dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
         gn_silu_fwd_pair_kernel<T, 4, 8><<<p.nblk, p.threads, 0, gmk_stream(stream)>>>((const T*)x, sa, sb, HW, C, eps, B, p.planes, xadd, xadd_stride);
@@ -1464,7 +1464,7 @@ extern "C" int gmk_gn_silu_bwd_pair(const void* x, const void* dy_up, const void
     const GnBwdSide up = {(const bf16_t*)dy_up, (const bf16_t*)dadd_up, gamma_up, beta_up, mean_up, rstd_up, dgamma_part_up, dbeta_part_up, groups_up};
     const GnBwdSide dn = {(const bf16_t*)dy_dn, (const bf16_t*)dadd_dn, gamma_dn, beta_dn, mean_dn, rstd_dn, dgamma_part_dn, dbeta_part_dn, groups_dn};
     const GnBwdPlan p = gn_bwd_plan(0, GMK_BF16, B, HW, C, groups_dn, false);      // the row gmk_gn_pair_ok asked: its block, grid and LDS bytes
-    gmk_note_kernel(25);
+    gmk_note_kernel(GMK_K_GN_BWD_PAIR);
     gmk_with_type<f16_t, bf16_t>(x_dtype, [&](auto tag) {
         using TX = typename decltype(tag)::type;
         auto launch = [&](auto kernel) {

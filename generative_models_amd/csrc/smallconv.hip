@@ -912,6 +912,7 @@ static void launch_expand(const float* in, const float* w, const float* bias, T*
                 const int tps = (H * W + 127) / 128;
                 const unsigned ntiles = (unsigned)B * (unsigned)tps;
                 const unsigned grid16 = ntiles < resident ? ntiles : resident;
+                gmk_note_kernel(GMK_K_EXPAND_TILE16);
 #define GMK_EXPAND_T16(CSN) expand3x3_tile16_kernel<T, CSN, FLIP><<<grid16, 256, 0, stream>>>(in, w, bias, out, H, W, C, tps, ntiles, (unsigned)in_bytes, (unsigned)out_bytes)
                 if (cs == 1) GMK_EXPAND_T16(1);
                 else if (cs == 2) GMK_EXPAND_T16(2);
@@ -920,6 +921,7 @@ static void launch_expand(const float* in, const float* w, const float* bias, T*
                 return;
             }
         }
+        gmk_note_kernel(GMK_K_EXPAND_MFMA);
 #define GMK_EXPAND_M(CSN) expand3x3_mfma_kernel<T, CSN, FLIP><<<grid, 256, 0, stream>>>(in, w, bias, out, H, W, C, (unsigned)npix, nblocks, (unsigned)in_bytes, (unsigned)out_bytes)
         if (cs == 1) GMK_EXPAND_M(1);
         else if (cs == 2) GMK_EXPAND_M(2);
@@ -928,6 +930,7 @@ static void launch_expand(const float* in, const float* w, const float* bias, T*
 #undef GMK_EXPAND_M
         return;
     }
+    gmk_note_kernel(GMK_K_EXPAND);
 #define GMK_EXPAND(CSN, VW) expand3x3_kernel<T, CSN, VW, FLIP><<<nb, 256, 0, stream>>>(in, w, bias, out, H, W, C, inv_w, (unsigned)npix, ppb)
     if (cs == 1) GMK_EXPAND(1, 8);
     else if (cs == 2) GMK_EXPAND(2, 8);
@@ -973,6 +976,7 @@ static void launch_wgrad(const float* small, const T* big, float* part, int B, i
             if (W <= 128 && small_bytes < 0xFFFFFF00ull && gmk_kernel_choice(3, "GMK_DEV_VARIANT") != 42) {
                 const int tps = (H * W + 127) / 128;
                 const unsigned ntiles = (unsigned)B * (unsigned)tps;
+                gmk_note_kernel(GMK_K_WGRAD3_TILE16);
 #define GMK_WGRAD_T16(CSN) wgrad3x3_tile16_kernel<T, CSN, FLIP><<<nb, 256, 0, stream>>>(small, big, part, H, W, C, tps, ntiles, (unsigned)small_bytes, (unsigned)big_bytes)
                 if (cs == 1) GMK_WGRAD_T16(1);
                 else if (cs == 2) GMK_WGRAD_T16(2);
@@ -981,6 +985,7 @@ static void launch_wgrad(const float* small, const T* big, float* part, int B, i
                 return;
             }
         }
+        gmk_note_kernel(GMK_K_WGRAD3_MFMA);
 #define GMK_WGRAD_M(CSN) wgrad3x3_mfma_kernel<T, CSN, FLIP><<<nb, 256, 0, stream>>>(small, big, part, H, W, C, (unsigned)npix, (unsigned)small_bytes, (unsigned)big_bytes, ppw)
         if (cs == 1) GMK_WGRAD_M(1);
         else if (cs == 2) GMK_WGRAD_M(2);
@@ -990,6 +995,7 @@ static void launch_wgrad(const float* small, const T* big, float* part, int B, i
     }
     // VALU fallback.  Measured (B=1024, 28x28, 3 image channels): one launch per image channel with 8-channel vectors (the C-channel
     // tensor is read cs times, 204 us) beats all channels at once with 4-channel vectors (one read, but 27 reduction rounds per block: 279 us)
+    gmk_note_kernel(GMK_K_WGRAD3);
     for (int s0 = 0; s0 < cs; ++s0)
         wgrad3x3_kernel<T, 1, 8, FLIP><<<nb, 256, 0, stream>>>(small, big, part, H, W, C, inv_w, (unsigned)npix, ppb, cs, s0);
 }
@@ -1019,6 +1025,7 @@ extern "C" int gmk_head_wgrad(const float* dout, const void* a, float* dw_part, 
 template <typename T, bool STEM_DGRAD>
 static void launch_mfma_band(const T* a, const float* w, const float* bias, float* out, int B, int cs, int H, int W, int mb, int nb2,
                              size_t lds, unsigned a_bytes, hipStream_t stream) {
+    gmk_note_kernel(STEM_DGRAD ? GMK_K_STEM_DGRAD_MFMA : GMK_K_HEAD_FWD_MFMA);
     if constexpr (STEM_DGRAD) {
         static const hipError_t attr = hipFuncSetAttribute((const void*)stem_dgrad_mfma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                            131072);
@@ -1035,6 +1042,7 @@ static void launch_mfma_band(const T* a, const float* w, const float* bias, floa
 template <typename T, bool STEM_DGRAD>
 static void launch_valu_band(const T* a, const float* w, const float* bias, float* out, int B, int cs, int H, int W, int C, float inv_w,
                              int band, int nbands, size_t lds, hipStream_t stream) {
+    gmk_note_kernel(STEM_DGRAD ? GMK_K_STEM_DGRAD : GMK_K_HEAD_FWD);
     if constexpr (STEM_DGRAD)
         stem_dgrad_kernel<T><<<B * nbands, 256, lds, stream>>>(a, w, out, cs, H, W, C, inv_w, band, nbands);
     else

@@ -9,13 +9,13 @@ import os
 
 import torch
 
-from ._lib import check, lib
+from ._lib import C, K, check, kernel_name, lib
 
-F32, BF16, F16 = 0, 1, 2
+F32, BF16, F16 = C["GMK_F32"], C["GMK_BF16"], C["GMK_F16"]      # these and every other GMK_* integer below: read from include/gmk.h
 # fp16 = forward activations / forward weight packs of the 16-bit mode; bf16 = gradients (and the all-bf16 A/B mode)
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 _HALF = (torch.bfloat16, torch.float16)
-NORMAL, STRIDE2, UPSAMPLE2, TRANSPOSED2 = 0, 1, 2, 3
+NORMAL, STRIDE2, UPSAMPLE2, TRANSPOSED2 = C["GMK_CONV_NORMAL"], C["GMK_CONV_STRIDE2"], C["GMK_CONV_UPSAMPLE2"], C["GMK_CONV_TRANSPOSED2"]
 
 # bench.py sets this to a list to collect (kernel name, start event, end event, algorithmic FLOPs, algorithmic HBM bytes, multiplied FLOPs) per
 # launch of the convolution, weight-gradient, GroupNorm and stem / head kernels; events are recorded on the stream the kernel is launched on.
@@ -23,23 +23,6 @@ NORMAL, STRIDE2, UPSAMPLE2, TRANSPOSED2 = 0, 1, 2, 3
 # differ for the sub-pixel forms (16 tap-products per low-resolution pixel where the reference op counts 36), and only the multiplied
 # count may be set against the MFMA peak.
 PROFILE = None
-
-
-KERNEL_NAMES = {1: "conv_igemm_kernel", 2: "conv_igemm_dma_kernel", 3: "conv3x3_halo_kernel", 4: "conv3x3_halo_ws_kernel", 11: "conv_wgrad_kernel",
-                12: "conv_wgrad_slots_kernel", 13: "conv_wgrad_slots_ws_kernel", 16: "conv_wgrad_subpixel_ws_kernel", 14: "conv1x1_pair_stream_kernel", 15: "conv1x1_wgrad_stream_kernel",
-                # same binary as 4, launched on the zero-stuffed gradient of a stride-2 conv: 4x the algorithmic MFMA work by
-                # construction, so the profile keeps it apart from the plain 3x3 convolutions
-                5: "conv3x3_halo_ws_kernel[zero-stuffed transposed conv]",
-                # conv2 of an up-path ResBlock with its 1x1 skip convolution folded in (K = 9 x 128 + 256): its own line in the profile
-                7: "conv3x3_halo_ws_kernel[+1x1 skip]",
-                # stride-2 data gradient where the halo kernel declines (fp32, small problems): four output-parity phase launches of the LDS-DMA kernel
-                6: "conv_igemm_dma_kernel[stride-2 dgrad phases]",
-                # sub-pixel (output-parity) forms: `Upsample` as four 2x2-tap parities on pre-summed weights, the stride-2 data gradient as 1 / 2 / 2 / 4 taps
-                # the slot weight-gradient kernel on the four parity planes of a stride-2 convolution's input (round 6): its own line (4 - 16 MFMAs per step, not 36)
-                17: "conv_wgrad_slots_ws_kernel[stride-2 planes]",
-                8: "conv_subpixel_ws_kernel[upsample]", 9: "conv_subpixel_ws_kernel[transposed]", 10: "conv_subpixel_ws_kernel[upsample dgrad]",
-                21: "gn_silu_fwd_reg_kernel", 22: "gn_silu_fwd_kernel", 23: "gn_silu_bwd_hybrid_kernel", 24: "gn_silu_bwd_kernel",
-                25: "gn_silu_bwd_pair_kernel", 26: "gn_silu_fwd_pair_kernel"}
 
 
 def instantiation_key(name, dtype):
@@ -69,7 +52,8 @@ def _nbytes(*tensors):
 
 class _Timed:
     """flops / nbytes: ALGORITHMIC work of the launch (DESIGN.md section 4: each operand tensor read once, each result written once);
-    fixed=True: `name` is the kernel's own name (no gmk_last_kernel lookup)."""
+    fixed=True: `name` is the kernel's own name; otherwise the launcher's report is asked (gmk_last_kernel: every C entry point behind such
+    a block notes an id of include/gmk.h's kernel table on every path that launches) and `name` only labels a call that has reported nothing."""
 
     def __init__(self, name, flops, nbytes=0.0, fixed=False, multiplied=None, dtype=None):
         self.on = PROFILE is not None
@@ -87,7 +71,7 @@ class _Timed:
     def __exit__(self, *exc):
         if self.on:
             self.e.record()
-            name = self.name if self.fixed else KERNEL_NAMES.get(lib.gmk_last_kernel(), self.name)
+            name = self.name if self.fixed else kernel_name(lib.gmk_last_kernel()) or self.name
             PROFILE.append((name, self.s, self.e, self.flops, self.nbytes, self.multiplied, instantiation_key(name, self.dtype)))
 
 
@@ -495,12 +479,12 @@ def conv_igemm(srcs, w, w_rows, ksize, mode, out_hw, n0=0, cout=128, bias=None, 
                                  _p(bias), _p(emb), emb_stride, _p(residual), _p(out), cout, _p(part),
                                  part.numel() * 4 if part is not None else 0, _p(gsc), _p(gsh), gstride, _DT[s0.dtype], _s()),
               "conv_igemm")
-    if part is not None and lib.gmk_last_kernel() == 3 and ho * wo >= 32:      # only the 8-compute-wave halo kernel emits statistics
+    if part is not None and lib.gmk_last_kernel() == K.CONV_HALO and ho * wo >= 32:      # only the 8-compute-wave halo kernel emits statistics
         out._gn_stats = (part, tp, nt)     # consumed by gn_silu_fwd(out, ...)
     return out
 
 
-SUBPIXEL_UPSAMPLE, SUBPIXEL_TRANSPOSED, SUBPIXEL_UPSAMPLE_DGRAD = 0, 1, 2
+SUBPIXEL_UPSAMPLE, SUBPIXEL_TRANSPOSED, SUBPIXEL_UPSAMPLE_DGRAD = C["GMK_SUBPIXEL_UPSAMPLE"], C["GMK_SUBPIXEL_TRANSPOSED"], C["GMK_SUBPIXEL_UPSAMPLE_DGRAD"]
 
 
 def conv_subpixel_ok(B, H, W, c, dtype, cout=128):
@@ -648,22 +632,12 @@ def conv_wgrad_subpixel(dy, x, dw):
     return dw
 
 
-def _expand_name(dtype, cs, W):
-    """Profile label of the stem forward / head data gradient launch (smallconv.hip launch_expand: 16-bit results of <= 3 image channels run tiled)."""
-    return "expand3x3_tile16_kernel" if dtype in (torch.float16, torch.bfloat16) and cs <= 3 and W <= 128 else "expand3x3_mfma_kernel"
-
-
-def _wgrad3_name(dtype, cs, W):
-    """Profile label of the stem / head weight-gradient launch (smallconv.hip launch_wgrad: 16-bit tensors run tiled)."""
-    return "wgrad3x3_tile16_kernel" if dtype in (torch.float16, torch.bfloat16) and cs <= 3 and W <= 128 and W % 2 == 0 else "wgrad3x3_mfma_kernel"
-
-
 def stem_fwd(x, w, bias, C, dtype):
     _f32(x, "x"); _f32(w, "w"); _f32(bias, "bias")
     B, cin, H, W = x.shape
     assert w.shape == (C, cin, 3, 3)
     y = torch.empty((B, H, W, C), device=x.device, dtype=dtype)
-    with _Timed(_expand_name(dtype, cin, W), 2.0 * B * H * W * C * cin * 9, _nbytes(x, y), fixed=True):
+    with _Timed("stem_fwd", 2.0 * B * H * W * C * cin * 9, _nbytes(x, y)):
         check(lib.gmk_stem_fwd(_p(x), _p(w), _p(bias), _p(y), B, cin, H, W, C, _DT[dtype], _s()), "stem_fwd")
     return y
 
@@ -674,7 +648,7 @@ def stem_wgrad(x, dy, dw):
     C = dy.shape[3]
     nb = lib.gmk_stem_wgrad_blocks(B * H * W)
     part = torch.empty((nb, C * cin * 9), device=x.device, dtype=torch.float32)
-    with _Timed(_wgrad3_name(dy.dtype, cin, W), 2.0 * B * H * W * C * cin * 9, _nbytes(x, dy), fixed=True):
+    with _Timed("stem_wgrad", 2.0 * B * H * W * C * cin * 9, _nbytes(x, dy)):
         check(lib.gmk_stem_wgrad(_p(x), _p(dy), _p(part), B, cin, H, W, C, _DT[dy.dtype], _s()), "stem_wgrad")
     return colsum(part, dw)
 
@@ -685,7 +659,7 @@ def head_fwd(a, w, bias):
     cout = w.shape[0]
     assert w.shape == (cout, C, 3, 3)
     out = torch.empty((B, cout, H, W), device=a.device, dtype=torch.float32)
-    with _Timed("head_fwd_mfma_kernel", 2.0 * B * H * W * C * cout * 9, _nbytes(a, out), fixed=True):
+    with _Timed("head_fwd", 2.0 * B * H * W * C * cout * 9, _nbytes(a, out)):
         check(lib.gmk_head_fwd(_p(a), _p(w), _p(bias), _p(out), B, cout, H, W, C, _DT[a.dtype], _s()), "head_fwd")
     return out
 
@@ -695,7 +669,7 @@ def head_dgrad(dout, w, dtype):
     B, cout, H, W = dout.shape
     C = w.shape[1]
     da = torch.empty((B, H, W, C), device=dout.device, dtype=dtype)
-    with _Timed(_expand_name(dtype, cout, W), 2.0 * B * H * W * C * cout * 9, _nbytes(dout, da), fixed=True):
+    with _Timed("head_dgrad", 2.0 * B * H * W * C * cout * 9, _nbytes(dout, da)):
         check(lib.gmk_head_dgrad(_p(dout), _p(w), _p(da), B, cout, H, W, C, _DT[dtype], _s()), "head_dgrad")
     return da
 
@@ -709,7 +683,7 @@ def head_wgrad(dout, a, dwb):
     assert dwb.numel() == n
     nb = lib.gmk_head_wgrad_blocks(B * H * W)
     part = torch.empty((nb, n), device=a.device, dtype=torch.float32)
-    with _Timed(_wgrad3_name(a.dtype, cout, W), 2.0 * B * H * W * C * cout * 9, _nbytes(dout, a), fixed=True):
+    with _Timed("head_wgrad", 2.0 * B * H * W * C * cout * 9, _nbytes(dout, a)):
         check(lib.gmk_head_wgrad(_p(dout), _p(a), _p(part), B, cout, H, W, C, _DT[a.dtype], _s()), "head_wgrad")
     return colsum(part, dwb)
 
@@ -725,8 +699,7 @@ def stem_dgrad(dy, w):
     B, H, W, C = dy.shape
     cin = w.shape[1]
     dx = torch.empty((B, cin, H, W), device=dy.device, dtype=torch.float32)
-    name = "stem_dgrad_mfma_kernel" if dy.dtype in _HALF and C == 128 and cin <= 3 else "stem_dgrad_kernel"
-    with _Timed(name, 2.0 * B * H * W * C * cin * 9, _nbytes(dy, dx), fixed=True):
+    with _Timed("stem_dgrad", 2.0 * B * H * W * C * cin * 9, _nbytes(dy, dx)):
         check(lib.gmk_stem_dgrad(_p(dy), _p(w), _p(dx), B, cin, H, W, C, _DT[dy.dtype], _s()), "stem_dgrad")
     return dx
 
@@ -923,7 +896,7 @@ def q_sample(x, eps, u):
     return logsnr, z
 
 
-MEAN_TYPES = {"v": 0, "eps": 1, "x": 2}      # what the network output parametrises (gaussian_diffusion.py:58-73)
+MEAN_TYPES = {"v": C["GMK_MEAN_V"], "eps": C["GMK_MEAN_EPS"], "x": C["GMK_MEAN_X"]}      # what the network output parametrises (gaussian_diffusion.py:58-73)
 
 
 def v_loss(v, z, x, eps, logsnr, grad_scale=None, loss_type=0, mean_type="v"):
@@ -941,8 +914,8 @@ def v_loss(v, z, x, eps, logsnr, grad_scale=None, loss_type=0, mean_type="v"):
     return loss_b, xm, em, dv
 
 
-X_LOSS_WEIGHTS = {"snr_plus1": 0, "min_snr": 1}      # GMK_LOSS_W_* of include/gmk.h: the weightings gmk_x_loss_w evaluates
-X_LOSS_KEEP = 12288             # kXLossKeep of csrc/diffusion_ew.hip: images of up to this many values keep their residuals in LDS, larger ones are re-read
+X_LOSS_WEIGHTS = {"snr_plus1": C["GMK_LOSS_W_SNR_PLUS1"], "min_snr": C["GMK_LOSS_W_MIN_SNR"]}      # the weightings gmk_x_loss_w evaluates
+X_LOSS_KEEP = C["GMK_X_LOSS_KEEP"]      # images of up to this many values keep their residuals in LDS, larger ones are re-read
 
 
 def x_loss_w(v, z, x, logsnr, weight, gamma, grad_scale=None, mean_type="v"):
@@ -984,7 +957,7 @@ def u_stratified(u0, B):
     return u
 
 
-PROFILE_BINS = 64               # GMK_PROFILE_BINS of include/gmk.h: bins of equal width in u, one per lane of a wavefront
+PROFILE_BINS = C["GMK_PROFILE_BINS"]      # bins of equal width in u, one per lane of a wavefront
 
 
 def _profile_state(state):
@@ -1173,7 +1146,7 @@ def dpm_solver_step(v, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x, coef_prev,
     return ((z_next, z2) if dup else z_next), xp, ep
 
 
-DYN_THRESHOLD_KEYS = 12288      # kDynKeys of csrc/diffusion_ew.hip: images of up to this many values are selected from LDS, larger ones re-read
+DYN_THRESHOLD_KEYS = C["GMK_DYN_THRESHOLD_KEYS"]      # images of up to this many values are selected from LDS, larger ones re-read
 
 
 def dyn_threshold(v, z, logsnr_t, p, v_uncond=None, cond_w=None, mean_type="v", want_q=False):
@@ -1343,7 +1316,7 @@ def pf_ode_step(out, z, logsnr_i, logsnr_j=None, mean_type="v", r=None, g=None, 
     return z
 
 
-SLERP_KEEP = 12288              # kSlerpKeep of csrc/diffusion_ew.hip: images of up to this many values are read once, larger ones again for every t
+SLERP_KEEP = C["GMK_SLERP_KEEP"]      # images of up to this many values are read once, larger ones again for every t
 
 
 def slerp(a, b, t, want_cos=False):
@@ -1431,7 +1404,7 @@ def adam_ema_step(p, g, m, v, ema, lr, beta1, beta2, eps, step, decay_t, grad_sc
                                 1.0 - float(decay_t), _s()), "adam_ema_step")
 
 
-GRAD_NORM, CLIP_COEF, APPLY, SKIPPED = 0, 1, 2, 3       # slots of the 4-float state gmk_grad_norm writes
+GRAD_NORM, CLIP_COEF, APPLY, SKIPPED = C["GMK_GRAD_NORM"], C["GMK_CLIP_COEF"], C["GMK_APPLY"], C["GMK_SKIPPED"]       # slots of the 4-float state gmk_grad_norm writes
 
 
 def grad_norm_workspace(n, device):

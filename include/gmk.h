@@ -34,10 +34,57 @@ extern "C" {
 
 int gmk_version(void);
 const char* gmk_last_error(void);
-/* profiling aid: which kernel the calling thread's last gmk_conv_igemm / gmk_conv_wgrad / gmk_gn_* call launched
- * (1 conv_igemm_kernel, 2 conv_igemm_dma_kernel, 3 conv3x3_halo_kernel, 4 conv3x3_halo_ws_kernel, 7 conv3x3_halo_ws_kernel with the folded 1x1 skip convolution, 8 / 9 / 10 conv_subpixel_ws_kernel (upsample / transposed / upsample data gradient), 5 a halo kernel on the zero-stuffed source of GMK_CONV_TRANSPOSED2 (GMK_CONV_KERNEL=3), 6 the four parity-phase launches of the LDS-DMA kernel for GMK_CONV_TRANSPOSED2, 11 conv_wgrad_kernel,
- * 12 conv_wgrad_slots_kernel, 13 conv_wgrad_slots_ws_kernel, 17 its four-plane form for GMK_CONV_STRIDE2, 16 conv_wgrad_subpixel_ws_kernel, 14 conv1x1_pair_stream_kernel, 15 conv1x1_wgrad_stream_kernel, 21 gn_silu_fwd_reg_kernel, 22 gn_silu_fwd_kernel, 23 gn_silu_bwd_hybrid_kernel, 24 gn_silu_bwd_kernel, 25 gn_silu_bwd_pair_kernel, 26 gn_silu_fwd_pair_kernel) */
+/* The kernel table: X(symbol, id, profile name) for every kernel a launcher reports.  This list is the only place where an id or a profile
+ * name is written: the launchers pass GMK_K_<symbol>, the name lookup below is generated from it, and the Python binding parses it (K.<symbol>,
+ * kernel_name).  A name is the device function's; a bracketed suffix tells apart launches of one function that the profile keeps on lines of
+ * their own.  The stem / head kernels start at 31. */
+#define GMK_KERNEL_TABLE(X)                                                                                                               \
+    X(CONV_IGEMM, 1, "conv_igemm_kernel")                                                                                                 \
+    X(CONV_IGEMM_DMA, 2, "conv_igemm_dma_kernel")                                                                                         \
+    X(CONV_HALO, 3, "conv3x3_halo_kernel")                                                                                                \
+    X(CONV_HALO_WS, 4, "conv3x3_halo_ws_kernel")                                                                                          \
+    /* a halo kernel on the zero-stuffed source of GMK_CONV_TRANSPOSED2: 4x the algorithmic MFMA work by construction */                  \
+    X(CONV_HALO_STUFFED, 5, "conv3x3_halo_ws_kernel[zero-stuffed transposed conv]")                                                       \
+    /* GMK_CONV_TRANSPOSED2 where the halo family declines: four output-parity phase launches of the LDS-DMA kernel */                    \
+    X(CONV_DMA_PHASES, 6, "conv_igemm_dma_kernel[stride-2 dgrad phases]")                                                                 \
+    /* gmk_conv3x3_skipfold: conv2 of an up-path ResBlock with its 1x1 skip convolution folded in (K = 9 x 128 + 256) */                  \
+    X(CONV_HALO_SKIPFOLD, 7, "conv3x3_halo_ws_kernel[+1x1 skip]")                                                                         \
+    X(CONV_SUBPIXEL_UPSAMPLE, 8, "conv_subpixel_ws_kernel[upsample]")                                                                     \
+    X(CONV_SUBPIXEL_TRANSPOSED, 9, "conv_subpixel_ws_kernel[transposed]")                                                                 \
+    X(CONV_SUBPIXEL_UPSAMPLE_DGRAD, 10, "conv_subpixel_ws_kernel[upsample dgrad]")                                                        \
+    X(CONV_WGRAD, 11, "conv_wgrad_kernel")                                                                                                \
+    X(CONV_WGRAD_SLOTS, 12, "conv_wgrad_slots_kernel")                                                                                    \
+    X(CONV_WGRAD_SLOTS_WS, 13, "conv_wgrad_slots_ws_kernel")                                                                              \
+    X(CONV1X1_PAIR_STREAM, 14, "conv1x1_pair_stream_kernel")                                                                              \
+    X(CONV1X1_WGRAD_STREAM, 15, "conv1x1_wgrad_stream_kernel")                                                                            \
+    X(CONV_WGRAD_SUBPIXEL, 16, "conv_wgrad_subpixel_ws_kernel")                                                                           \
+    /* the slot kernel on the four parity planes of a stride-2 convolution's input (4 - 16 MFMAs per step, not 36) */                    \
+    X(CONV_WGRAD_SLOTS_S2, 17, "conv_wgrad_slots_ws_kernel[stride-2 planes]")                                                             \
+    X(GN_FWD_REG, 21, "gn_silu_fwd_reg_kernel")                                                                                           \
+    X(GN_FWD, 22, "gn_silu_fwd_kernel")                                                                                                   \
+    X(GN_BWD_HYBRID, 23, "gn_silu_bwd_hybrid_kernel")                                                                                     \
+    X(GN_BWD, 24, "gn_silu_bwd_kernel")                                                                                                   \
+    X(GN_BWD_PAIR, 25, "gn_silu_bwd_pair_kernel")                                                                                         \
+    X(GN_FWD_PAIR, 26, "gn_silu_fwd_pair_kernel")                                                                                         \
+    X(EXPAND, 31, "expand3x3_kernel")                                                                                                     \
+    X(EXPAND_MFMA, 32, "expand3x3_mfma_kernel")                                                                                           \
+    X(EXPAND_TILE16, 33, "expand3x3_tile16_kernel")                                                                                       \
+    X(WGRAD3, 34, "wgrad3x3_kernel")                                                                                                      \
+    X(WGRAD3_MFMA, 35, "wgrad3x3_mfma_kernel")                                                                                            \
+    X(WGRAD3_TILE16, 36, "wgrad3x3_tile16_kernel")                                                                                        \
+    X(HEAD_FWD, 37, "head_fwd_kernel")                                                                                                    \
+    X(HEAD_FWD_MFMA, 38, "head_fwd_mfma_kernel")                                                                                          \
+    X(STEM_DGRAD, 39, "stem_dgrad_kernel")                                                                                                \
+    X(STEM_DGRAD_MFMA, 40, "stem_dgrad_mfma_kernel")
+enum {
+#define GMK_K_ENUM(symbol, id, name) GMK_K_##symbol = id,
+    GMK_KERNEL_TABLE(GMK_K_ENUM)
+#undef GMK_K_ENUM
+};
+/* profiling aid: the table id of the kernel that the calling thread's last convolution, weight-gradient, GroupNorm or stem / head call
+ * launched (per thread and sticky: a call that launches nothing leaves it); its profile name, NULL for 0 or an id outside the table */
 int gmk_last_kernel(void);
+const char* gmk_kernel_name(int id);
 /* development aid: force kernel variants (0 = automatic; see GMK_CONV_KERNEL / GMK_WGRAD_KERNEL / GMK_GN_KERNEL); -1 = unset */
 int gmk_set_kernel_choice(int conv, int wgrad, int gn);
 /* development aid: a free integer (GMK_DEV_VARIANT) that experimental code paths may read for in-process A/B runs
@@ -317,8 +364,11 @@ int gmk_q_sample(const float* x, const float* eps, const float* u, float* logsnr
 /* gaussian_diffusion.py:58-77,165-169 and their backward in one pass over each sample:
  * x_hat = clip(x_from_output(v)); eps_hat = eps_from_x; loss_b = max(mean (x_hat-x)^2, mean (eps_hat-eps)^2);
  * dv (optional) = d(grad_scale * sum_b loss_b)/dv.  loss_b/x_mse/eps_mse: fp32 [B].
- * mean_type (the reference's `mean_type`, :58-73) says what the network output v is: 0 'v' (x = alpha z - sigma v),
- * 1 'eps' (x = (z - sigma v)/alpha), 2 'x' (x = v).  ('both' splits a 1-channel output along W in the reference — dead.) */
+ * mean_type (the reference's `mean_type`, :58-73) says what the network output v is: GMK_MEAN_V 'v' (x = alpha z - sigma v),
+ * GMK_MEAN_EPS 'eps' (x = (z - sigma v)/alpha), GMK_MEAN_X 'x' (x = v).  ('both' splits a 1-channel output along W in the reference — dead.) */
+#define GMK_MEAN_V 0
+#define GMK_MEAN_EPS 1
+#define GMK_MEAN_X 2
 int gmk_v_loss(const float* v, const float* z, const float* x, const float* eps, const float* logsnr, float* loss_b,
                float* x_mse, float* eps_mse, float* dv, float grad_scale, int loss_type, int mean_type, int B, int64_t n,
                void* stream);
@@ -338,6 +388,7 @@ int gmk_v_loss(const float* v, const float* z, const float* x, const float* eps,
  * (checked for either weight_type).  loss_b, x_mse: fp32 [B], both required. */
 #define GMK_LOSS_W_SNR_PLUS1 0
 #define GMK_LOSS_W_MIN_SNR 1
+#define GMK_X_LOSS_KEEP 12288      /* the "12,288 values" above (covers 3 x 64 x 64) */
 int gmk_x_loss_w(const float* v, const float* z, const float* x, const float* logsnr, float* loss_b, float* x_mse, float* dv,
                  float grad_scale, int weight_type, float gamma, int mean_type, int B, int64_t n, void* stream);
 /* low-discrepancy training times (Kingma et al. 2021, "Variational Diffusion Models", App. I.1); an extension: u[b] = frac(u0[0] + b / B) as
@@ -405,6 +456,7 @@ int gmk_dpm_solver_step(const float* v, const float* v_uncond, const float* cond
  *     division) in place of the clipped prediction; eps_hat = eps(z, x_hat) and everything after it (the update, x_hist, the is_last select, z_dup,
  *     logsnr_next) unchanged.  thr: B floats, required (gmk_dyn_threshold's s_out).  With thr = 1 and no guidance they give the bits of the entries
  *     without _dt: the same kernels, instantiated a second time. */
+#define GMK_DYN_THRESHOLD_KEYS 12288      /* the "12,288 values" of gmk_dyn_threshold */
 int gmk_dyn_threshold(const float* v, const float* v_uncond, const float* cond_w, const float* z, float logsnr_t, int k_lo, float frac,
                       float* s_out, float* q_out, int mean_type, int B, int64_t n, void* stream);
 int gmk_sampler_step_dt(const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z, const float* noise,
@@ -493,6 +545,7 @@ int gmk_pf_ode_step(const float* out, float* z, const float* r, const float* g, 
  * a fixed order without floating-point atomics, so the same call gives the same bits.  Images of up to 12,288 values stay in registers between
  * the reduction and the K output passes (a and b are read once), larger ones are read again per k.  B, K >= 1, n >= 4, n % 4 == 0; a, b and
  * out 16-byte aligned (16-byte loads and stores). */
+#define GMK_SLERP_KEEP 12288      /* the "12,288 values" above; a multiple of 1024 */
 int gmk_slerp(const float* a, const float* b, const float* t, float* out, float* cos_out, int B, int64_t n, int K, void* stream);
 
 /* ---- self-attention core (north_star "optional self-attention block", BASELINE config 5) -------------
@@ -546,13 +599,17 @@ int gmk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
 int gmk_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
                       float eps, int step, float grad_scale, float ema_w, void* stream);
 /* Global L2 norm of the gradient arena and this step's decision, on the device (no host sync).  No reference call site for the clipping; the
- * guard is what GradScaler.step does in the reference's train step (diffusion_model.py:71).  Writes state[0..3]:
- *   [0] total_norm = grad_scale sqrt(sum g^2)                       the norm of the gradient Adam consumes
- *   [1] coef       = min(1, max_norm / (total_norm + 1e-6))         torch.nn.utils.clip_grad_norm_; max_norm <= 0: no clipping, 1
- *   [2] apply      = 1 if total_norm is finite, else 0              (an overflowing sum of squares counts as non-finite)
- *   [3] skipped    += 1 - apply                                     a running count: zero it once, before the first call
+ * guard is what GradScaler.step does in the reference's train step (diffusion_model.py:71).  Writes the four floats of `state`:
+ *   [GMK_GRAD_NORM]  total_norm = grad_scale sqrt(sum g^2)                 the norm of the gradient Adam consumes
+ *   [GMK_CLIP_COEF]  coef       = min(1, max_norm / (total_norm + 1e-6))   torch.nn.utils.clip_grad_norm_; max_norm <= 0: no clipping, 1
+ *   [GMK_APPLY]      apply      = 1 if total_norm is finite, else 0        (an overflowing sum of squares counts as non-finite)
+ *   [GMK_SKIPPED]    skipped    += 1 - apply                               a running count: zero it once, before the first call
  * Two launches: one partial sum of squares per workgroup into `workspace` (gmk_grad_norm_workspace_bytes(n) bytes; the grid depends on n
  * alone, not on gmk_set_cu_limit), then one workgroup adds the partials in a fixed order.  No atomics: the same bits on every call. */
+#define GMK_GRAD_NORM 0
+#define GMK_CLIP_COEF 1
+#define GMK_APPLY 2
+#define GMK_SKIPPED 3
 int64_t gmk_grad_norm_workspace_bytes(int64_t n);
 int gmk_grad_norm(const float* g, int64_t n, float grad_scale, float max_norm, float* workspace, int64_t workspace_bytes, float* state,
                   void* stream);

@@ -130,7 +130,7 @@ def test_halo_forward_wide(ops, lib, dtype, two, C, case):
     rd, bd = nhwc(res, dtype), bias.cuda()
     ops.set_cu_limit(lim)
     outs = {}
-    for name, force, variant, kid in (("ws", 3, 0, 4), ("8wave", 3, 3, 3), ("auto", -1, 0, 4)):
+    for name, force, variant, kid in (("ws", 3, 0, ops.K.CONV_HALO_WS), ("8wave", 3, 3, ops.K.CONV_HALO), ("auto", -1, 0, ops.K.CONV_HALO_WS)):
         lib.gmk_set_kernel_choice(force, -1, -1)
         lib.gmk_set_dev_variant(variant)
         outs[name] = ops.conv_igemm(sd, wf, C, 3, ops.NORMAL, (H, W), cout=C, bias=bd, residual=rd)
@@ -140,7 +140,7 @@ def test_halo_forward_wide(ops, lib, dtype, two, C, case):
     embd = torch.zeros((B, 3 * C), device="cuda")
     embd[:, C:2 * C] = emb.cuda()
     out_e = ops.conv_igemm(sd, wf, C, 3, ops.NORMAL, (H, W), cout=C, bias=bd, emb=embd[:, C:2 * C], residual=rd)
-    assert lib.gmk_last_kernel() == 3
+    assert lib.gmk_last_kernel() == ops.K.CONV_HALO
     tag = f"{plan['schedule']} c{C} {ident(case)} {dtype} srcs={n}"
     check_a(outs["ws"], ref, dtype, lim, f"wave-specialised {tag}")
     assert torch.equal(outs["ws"], outs["8wave"]), "8-compute-wave kernel differs: " + R.worst(nchw(outs["8wave"]), nchw(outs["ws"]), cu_limit=lim)["text"]
@@ -164,7 +164,7 @@ def test_halo_dgrad_offset_rows(ops, lib, C, case):
     ops.set_cu_limit(lim)
     for i in range(2):
         outs = {}
-        for name, force, variant, kid in (("ws", 3, 0, 4), ("8wave", 3, 3, 3), ("auto", -1, 0, 4)):
+        for name, force, variant, kid in (("ws", 3, 0, ops.K.CONV_HALO_WS), ("8wave", 3, 3, ops.K.CONV_HALO), ("auto", -1, 0, ops.K.CONV_HALO_WS)):
             lib.gmk_set_kernel_choice(force, -1, -1)
             lib.gmk_set_dev_variant(variant)
             outs[name] = ops.conv_igemm([dyd], wd, 2 * C, 3, ops.NORMAL, (H, W), n0=i * C, cout=C)
@@ -198,7 +198,7 @@ def test_halo_upsample_and_transposed_wide(ops, lib, res, case):
             lib.gmk_set_kernel_choice(force, -1, -1)
             lib.gmk_set_dev_variant(variant)
             outs.append(ops.conv_igemm([xd], wf, C, 3, ops.UPSAMPLE2, (H, W), cout=C, residual=rd))
-            assert lib.gmk_last_kernel() == 4
+            assert lib.gmk_last_kernel() == ops.K.CONV_HALO_WS
         check_a(outs[0], ref, dtype, lim, f"nearest-x2 forward {ident(case)} {dtype}")
         assert torch.equal(outs[0], outs[1])
     # transposed: dy is the gradient of a stride-2 convolution's (hs x ws) output, w that convolution's weight
@@ -213,7 +213,7 @@ def test_halo_upsample_and_transposed_wide(ops, lib, res, case):
         lib.gmk_set_kernel_choice(-1, -1, -1)
         lib.gmk_set_dev_variant(0)
         dx = ops.conv_igemm([dyd], wd, C, 3, ops.TRANSPOSED2, (H, W), cout=C, residual=rd)
-        assert lib.gmk_last_kernel() == 6                      # fewer than 32 tiles, or fp32: four phases
+        assert lib.gmk_last_kernel() == ops.K.CONV_DMA_PHASES                      # fewer than 32 tiles, or fp32: four phases
         check_a(dx, ref, dtype, lim, f"transposed, four phases {ident(case)} {dtype}")
         if dtype == BF16:
             outs = []
@@ -221,7 +221,7 @@ def test_halo_upsample_and_transposed_wide(ops, lib, res, case):
                 lib.gmk_set_kernel_choice(3, -1, -1)
                 lib.gmk_set_dev_variant(variant)
                 outs.append(ops.conv_igemm([dyd], wd, C, 3, ops.TRANSPOSED2, (H, W), cout=C, residual=rd))
-                assert lib.gmk_last_kernel() == 5
+                assert lib.gmk_last_kernel() == ops.K.CONV_HALO_STUFFED
             check_a(outs[0], ref, dtype, lim, f"transposed, zero-stuffed halo {ident(case)}")
             assert torch.equal(outs[0], outs[1])
 
@@ -262,8 +262,8 @@ def test_im2col_kernels_wide(ops, lib, mode, what, geom):
             runs.append((f"n0={i * C}", [dy], wd, 2 * C, 1, ops.NORMAL, i * C, dsrcs[i]))
     for name, srcs, wp, w_rows, ks, cmode, n0, ref in runs:
         sd = [nhwc(s, dtype) for s in srcs]
-        for kid in (1, 2):
-            lib.gmk_set_kernel_choice(kid, -1, -1)
+        for force, kid in ((1, ops.K.CONV_IGEMM), (2, ops.K.CONV_IGEMM_DMA)):
+            lib.gmk_set_kernel_choice(force, -1, -1)
             out = ops.conv_igemm(sd, wp, w_rows, ks, cmode, (H, W), n0=n0, cout=C)
             assert lib.gmk_last_kernel() == kid
             check_a(out, ref, dtype, lim, f"kernel {kid} {what} {name} {mode} {ident(geom)}")
@@ -326,13 +326,13 @@ def test_slot_wgrad_wide(ops, lib, C, cmode, n, xdt, case):
         return a, kid
 
     base, kid = run(1)
-    assert kid == 11
+    assert kid == ops.K.CONV_WGRAD
     tag = f"c{C} mode {cmode} srcs={n} x={xdt} {ident(case)} plan={plan}"
-    check_b(base, ref, f"im2col (11) {tag}")
-    slot = 17 if s2 else 13
-    todo = [(3, slot), (-1, slot if plan["auto"] else 11)]
+    check_b(base, ref, f"im2col {tag}")
+    slot = ops.K.CONV_WGRAD_SLOTS_S2 if s2 else ops.K.CONV_WGRAD_SLOTS_WS
+    todo = [(3, slot), (-1, slot if plan["auto"] else ops.K.CONV_WGRAD)]
     if xdt == BF16 and not s2:
-        todo.insert(0, (2, 12))
+        todo.insert(0, (2, ops.K.CONV_WGRAD_SLOTS))
     for force, want in todo:
         dw, kid = run(force)
         assert kid == want, (force, kid, want, plan)
@@ -353,7 +353,7 @@ def test_skip_wgrad_wide(ops, lib, xdt, case):
     ops.set_cu_limit(lim)
     dw = torch.empty((C, 2 * C, 1, 1), device="cuda"); dw2 = torch.empty_like(dw)
     ops.conv_wgrad(nhwc(dy, BF16), [nhwc(x, xdt) for x in xs], 1, ops.NORMAL, dw)
-    assert lib.gmk_last_kernel() == 11
+    assert lib.gmk_last_kernel() == ops.K.CONV_WGRAD
     ops.conv_wgrad(nhwc(dy, BF16), [nhwc(x, xdt) for x in xs], 1, ops.NORMAL, dw2)
     assert torch.equal(dw, dw2)
     check_b(dw, ref, f"1x1 ktot=512 {xdt} {ident(case)}")

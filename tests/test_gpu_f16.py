@@ -79,7 +79,7 @@ def test_conv_forward_with_fp16_operands(ops, lib, B, S, two, up, force, variant
         lib.gmk_set_kernel_choice(-1, -1, -1)
         lib.gmk_set_dev_variant(0)
     assert out.dtype == H
-    assert kid == {1: 1, 2: 2}.get(force, 3 if variant == 3 else 4), kid
+    assert kid == {1: ops.K.CONV_IGEMM, 2: ops.K.CONV_IGEMM_DMA}.get(force, ops.K.CONV_HALO if variant == 3 else ops.K.CONV_HALO_WS), kid
     assert rel_err(nchw(out), ref) < 2e-3
 
 
@@ -119,7 +119,7 @@ def test_conv_output_saturates_instead_of_overflowing(ops, lib, kernel, residual
             wsf = torch.empty(wsk.numel(), device="cuda", dtype=H)
             ops.pack_conv_weight(wsk.cuda(), wsf, None)
             out = ops.conv3x3_skipfold(x, wf, torch.zeros(C, device="cuda"), sk, wsf, torch.zeros(C, device="cuda"))
-            assert lib.gmk_last_kernel() == 7
+            assert lib.gmk_last_kernel() == ops.K.CONV_HALO_SKIPFOLD
         elif kernel == "halo-fused-gn":
             # raw source 1.0 with scale / shift tables that make silu(x * scale + shift) = silu(60000) = 60000: the producers' own fp16 store
             xr = torch.ones((B, S, S, C), device="cuda", dtype=H)
@@ -128,7 +128,8 @@ def test_conv_output_saturates_instead_of_overflowing(ops, lib, kernel, residual
             out = ops.conv_igemm([xr], wf, C, 3, ops.NORMAL, (S, S), residual=res, gn=(tsc, tsh))
         else:
             out = ops.conv_igemm([x], wf, C, 3, ops.NORMAL, (S, S), residual=res)
-            want = {"auto-small": 4, "im2col-reg": 1, "im2col-dma": 2, "halo-ws": 4, "halo-ws-32x32": 4, "halo-8wave": 3}[kernel]
+            want = {"auto-small": ops.K.CONV_HALO_WS, "im2col-reg": ops.K.CONV_IGEMM, "im2col-dma": ops.K.CONV_IGEMM_DMA, "halo-ws": ops.K.CONV_HALO_WS, "halo-ws-32x32": ops.K.CONV_HALO_WS,
+                    "halo-8wave": ops.K.CONV_HALO}[kernel]
             assert lib.gmk_last_kernel() == want, lib.gmk_last_kernel()
     finally:
         lib.gmk_set_kernel_choice(-1, -1, -1)
@@ -157,7 +158,7 @@ def test_fused_groupnorm_conv_fp16_is_bit_identical(ops, lib, B, S, two):
         ops.gn_stats(s, gamma[sl], beta[sl], gpc, tsc[:, sl], tsh[:, sl], xadd=xadd)
         ys.append(ops.gn_silu_fwd(s, gamma[sl], beta[sl], gpc, xadd=xadd)[0])
     fused = ops.conv_igemm(srcs, wf, C, 3, ops.NORMAL, (S, S), gn=(tsc, tsh))
-    assert lib.gmk_last_kernel() == 4
+    assert lib.gmk_last_kernel() == ops.K.CONV_HALO_WS
     plain = ops.conv_igemm(ys, wf, C, 3, ops.NORMAL, (S, S))
     assert torch.equal(fused, plain)
 
@@ -199,7 +200,7 @@ def test_groupnorm_statistics_agree_across_the_forward_entry_points(ops, lib, S,
     x = (rnd(B, S, S, C, seed=31) * 1.4 + 0.25).to(dtype).cuda()
     gamma = (1 + 0.1 * rnd(C, seed=32)).cuda(); beta = (0.1 * rnd(C, seed=33)).cuda()
     xadd = (0.3 * rnd(B, C, seed=34)).cuda() if with_xadd else None
-    want = 22 if S == 8 else 21
+    want = ops.K.GN_FWD if S == 8 else ops.K.GN_FWD_REG
     _, mean, rstd = ops.gn_silu_fwd(x, gamma, beta, G, xadd=xadd)
     assert lib.gmk_last_kernel() == want
     tsc = torch.empty((B, C), device="cuda"); tsh = torch.empty_like(tsc)
@@ -210,7 +211,7 @@ def test_groupnorm_statistics_agree_across_the_forward_entry_points(ops, lib, S,
     assert ops.gn_pair_fwd_ok(x, G, G) == (S == 16)
     if S == 16:
         sides = ops.gn_silu_fwd_pair(x, (gamma, beta, G), (gamma, beta, G), xadd=xadd)
-        assert lib.gmk_last_kernel() == 26
+        assert lib.gmk_last_kernel() == ops.K.GN_FWD_PAIR
         for _, m, r in sides:
             assert torch.equal(m, mean) and torch.equal(r, rstd)
 
@@ -238,7 +239,7 @@ def test_weight_gradient_with_fp16_activations(ops, lib, B, S, two, mode, ks, fo
             outs[tag] = (dw, lib.gmk_last_kernel())
     finally:
         lib.gmk_set_kernel_choice(-1, -1, -1)
-    assert outs["bf16"][1] == outs["f16"][1] == (11 if force == 1 else 13)
+    assert outs["bf16"][1] == outs["f16"][1] == (ops.K.CONV_WGRAD if force == 1 else ops.K.CONV_WGRAD_SLOTS_WS)
     assert torch.equal(outs["bf16"][0], outs["f16 exact"][0])
     xr = torch.cat([x.to(H).to(BF).float().permute(0, 3, 1, 2) for x in xs], 1).requires_grad_(False)
     w = torch.zeros(C, cin, ks, ks, requires_grad=True)

@@ -37,7 +37,7 @@ def _check_backward(B, hw, C, groups, x_dtype, with_xadd, with_dxsum):
     sum_pair = torch.empty((B, C), device="cuda") if with_dxsum else None
     dx2, (p_gu, p_bu), (p_gd, p_bd) = ops.gn_silu_bwd_pair(x, (dy_u, dadd_u, gam_u, bet_u, *stats[0]), (dy_d, dadd_d, gam_d, bet_d, *stats[1]),
                                                             dxsum=sum_pair, xadd=xadd)
-    assert ops.lib.gmk_last_kernel() == 25
+    assert ops.lib.gmk_last_kernel() == ops.K.GN_BWD_PAIR
     torch.cuda.synchronize()
     pairs = [("dx", dx, dx2), ("dgp_up", dgp_u, p_gu), ("dbp_up", dbp_u, p_bu), ("dgp_dn", dgp_d, p_gd), ("dbp_dn", dbp_d, p_bd)]
     if with_dxsum:
@@ -72,7 +72,7 @@ def test_pair_forward_bit_identical(x_dtype, with_xadd, C, groups):
     assert ops.gn_pair_fwd_ok(x, ga, gb)
     ref = [ops.gn_silu_fwd(x, gam, bet, G, xadd=xadd) for G, gam, bet, _, _ in sides]
     got = ops.gn_silu_fwd_pair(x, (gam_a, bet_a, ga), (gam_b, bet_b, gb), xadd=xadd)
-    assert ops.lib.gmk_last_kernel() == 26
+    assert ops.lib.gmk_last_kernel() == ops.K.GN_FWD_PAIR
     torch.cuda.synchronize()
     for side, (r, p) in enumerate(zip(ref, got)):
         for name, a, b in zip(("y", "mean", "rstd"), r, p):

@@ -339,7 +339,7 @@ def test_rng_and_adam(ops):
 def test_forced_kernel_variants_agree_with_torch(ops, two, S, B, mode):
     """Small problems pick the im2col kernels automatically: force the slot weight-gradient kernel (both window widths: W <= 61
     and the wide one for 64-pixel rows) and both LDS-halo convolution kernels on them and hold them to the same parity bar."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     dtype, C = torch.bfloat16, 128
     cin = 2 * C if two else C
     srcs = [q(rnd(B, C, S, S, seed=110 + i), dtype).requires_grad_(True) for i in range(2 if two else 1)]
@@ -355,9 +355,9 @@ def test_forced_kernel_variants_agree_with_torch(ops, two, S, B, mode):
         lib.gmk_set_kernel_choice(-1, 2, -1)                       # slot weight-gradient kernel
         dw = torch.empty_like(w.detach()).cuda()
         ops.conv_wgrad(nhwc(dy, dtype), sd, 3, mode, dw)
-        assert lib.gmk_last_kernel() == 12
+        assert lib.gmk_last_kernel() == K.CONV_WGRAD_SLOTS
         assert rel_err(dw, w.grad) < TOL[dtype], "slot wgrad"
-        for variant, kid in ((0, 4), (3, 3)):                      # wave-specialised / 8-compute-wave halo kernel
+        for variant, kid in ((0, K.CONV_HALO_WS), (3, K.CONV_HALO)):                      # wave-specialised / 8-compute-wave halo kernel
             lib.gmk_set_kernel_choice(3, -1, -1)
             lib.gmk_set_dev_variant(variant)
             out = ops.conv_igemm(sd, wf, C, 3, mode, (ho, wo))
@@ -376,7 +376,7 @@ def test_stride2_wgrad_on_parity_planes(ops, xdt, S, B, C):
     the input's parity planes against the low-resolution gradient's slots, every tap a constant slot offset into one plane.  Against autograd in
     fp32 on the rounded operands, against the im2col kernel it replaces (the same bf16 x bf16 products, fp32 sums in another order),
     bit-reproducible; small problems take it only when forced, the train step's sizes automatically; odd input sizes keep the im2col kernel."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     x = q(rnd(B, C, S, S, seed=340), xdt)
     w = (rnd(C, C, 3, 3, seed=341) / math.sqrt(C * 9)).requires_grad_(True)
     out = F.conv2d(q(x, torch.bfloat16), w, None, stride=2, padding=1)               # the kernels multiply bf16(x)
@@ -388,10 +388,10 @@ def test_stride2_wgrad_on_parity_planes(ops, xdt, S, B, C):
     try:
         if not big:
             ops.conv_wgrad(dyd, [xd], 3, ops.STRIDE2, dw)
-            assert lib.gmk_last_kernel() == 11              # automatic: the im2col kernel
+            assert lib.gmk_last_kernel() == K.CONV_WGRAD              # automatic: the im2col kernel
             lib.gmk_set_kernel_choice(-1, 3, -1)
         ops.conv_wgrad(dyd, [xd], 3, ops.STRIDE2, dw)
-        assert lib.gmk_last_kernel() == 17
+        assert lib.gmk_last_kernel() == K.CONV_WGRAD_SLOTS_S2
         e = rel_err(dw, w.grad)
         assert e < TOL[torch.bfloat16], e
         dw2 = torch.empty_like(dw)
@@ -400,7 +400,7 @@ def test_stride2_wgrad_on_parity_planes(ops, xdt, S, B, C):
         lib.gmk_set_kernel_choice(-1, 1, -1)
         dw_old = torch.empty_like(dw)
         ops.conv_wgrad(dyd, [xd], 3, ops.STRIDE2, dw_old)
-        assert lib.gmk_last_kernel() == 11
+        assert lib.gmk_last_kernel() == K.CONV_WGRAD
         assert rel_err(dw, dw_old) < 1e-4, rel_err(dw, dw_old)
         assert e <= rel_err(dw_old, w.grad) + 1e-4
     finally:
@@ -411,7 +411,7 @@ def test_stride2_wgrad_on_parity_planes(ops, xdt, S, B, C):
         lib.gmk_set_kernel_choice(-1, 3, -1)
         try:
             ops.conv_wgrad(dyo, [xo], 3, ops.STRIDE2, dw2)
-            assert lib.gmk_last_kernel() == 11
+            assert lib.gmk_last_kernel() == K.CONV_WGRAD
         finally:
             lib.gmk_set_kernel_choice(-1, -1, -1)
 
@@ -421,7 +421,7 @@ def test_transposed_dgrad_on_halo_kernels(ops, S, B):
     """Data gradient of the stride-2 conv, the older form (GMK_CONV_KERNEL=3): on the halo kernels as a 3x3 conv of the zero-stuffed gradient
     (kernel id 5).  Force that path on small problems (tiles spanning several images at 8x8 / 14x14) and compare with autograd
     and with the im2col gather it replaces."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     dtype, C = torch.bfloat16, 128
     x = q(rnd(B, C, S, S, seed=140), dtype).requires_grad_(True)
     w = q(rnd(C, C, 3, 3, seed=141) / math.sqrt(C * 9), dtype).requires_grad_(True)
@@ -434,12 +434,12 @@ def test_transposed_dgrad_on_halo_kernels(ops, S, B):
     try:
         lib.gmk_set_kernel_choice(1, -1, -1)                        # im2col gather (register-staged)
         dx_im2col = ops.conv_igemm([dyd], wd, C, 3, ops.TRANSPOSED2, (S, S))
-        assert lib.gmk_last_kernel() == 1
+        assert lib.gmk_last_kernel() == K.CONV_IGEMM
         for variant in (0, 3):                                      # wave-specialised / 8-compute-wave halo kernel
             lib.gmk_set_kernel_choice(3, -1, -1)
             lib.gmk_set_dev_variant(variant)
             dx = ops.conv_igemm([dyd], wd, C, 3, ops.TRANSPOSED2, (S, S))
-            assert lib.gmk_last_kernel() == 5
+            assert lib.gmk_last_kernel() == K.CONV_HALO_STUFFED
             assert rel_err(nchw(dx), x.grad) < TOL[dtype], f"variant {variant} vs autograd"
             assert rel_err(nchw(dx), nchw(dx_im2col).cpu()) < 8e-3, f"variant {variant} vs im2col"   # same products, other summation order: <= 2 bf16 ulps
     finally:
@@ -454,7 +454,7 @@ def test_transposed_dgrad_as_four_phases(ops, dtype, S, B, res):
     problems the halo kernel declines; GMK_CONV_KERNEL=2 elsewhere) - 1 / 2 / 2 / 4 taps over the gradient's own grid, rows scattered with
     stride 2 - with and without the residual the net adds there (the skip path's gradient).  Against autograd, against the zero-stuffed
     halo form (same products, other summation order), in fp32 and bf16."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     x = q(rnd(B, C, S, S, seed=150), dtype).requires_grad_(True)
     w = q(rnd(C, C, 3, 3, seed=151) / math.sqrt(C * 9), dtype).requires_grad_(True)
@@ -468,17 +468,17 @@ def test_transposed_dgrad_as_four_phases(ops, dtype, S, B, res):
     rd = nhwc(r, dtype) if res else None
     ref = x.grad + (r if res else 0)
     dx0 = ops.conv_igemm([dyd], wd, C, 3, ops.TRANSPOSED2, (S, S), residual=rd)       # automatic choice
-    assert lib.gmk_last_kernel() == 6 if dtype == torch.float32 else lib.gmk_last_kernel() in (5, 6, 9)      # (9: the sub-pixel form, round 5)
+    assert lib.gmk_last_kernel() == K.CONV_DMA_PHASES if dtype == torch.float32 else lib.gmk_last_kernel() in (K.CONV_HALO_STUFFED, K.CONV_DMA_PHASES, K.CONV_SUBPIXEL_TRANSPOSED)      # (the sub-pixel form: round 5)
     assert rel_err(nchw(dx0), ref) < TOL[dtype]
     try:
         lib.gmk_set_kernel_choice(2, -1, -1)
         dx = ops.conv_igemm([dyd], wd, C, 3, ops.TRANSPOSED2, (S, S), residual=rd)
-        assert lib.gmk_last_kernel() == 6
+        assert lib.gmk_last_kernel() == K.CONV_DMA_PHASES
         assert rel_err(nchw(dx), ref) < TOL[dtype]
         if dtype == torch.bfloat16 and S >= 8:
             lib.gmk_set_kernel_choice(3, -1, -1)
             dx_h = ops.conv_igemm([dyd], wd, C, 3, ops.TRANSPOSED2, (S, S), residual=rd)
-            assert lib.gmk_last_kernel() == 5
+            assert lib.gmk_last_kernel() == K.CONV_HALO_STUFFED
             assert rel_err(nchw(dx), nchw(dx_h).cpu()) < 8e-3
     finally:
         lib.gmk_set_kernel_choice(-1, -1, -1)
@@ -489,7 +489,7 @@ def test_halo_tail_runs_as_half_jobs(ops, S, B, two, mode):
     """More tiles than CUs with a last round of <= 128 tiles: the wave-specialised kernel runs that round as half-channel jobs
     (64 pixels x 64 channels per consumer wave).  Same dot products in the same order as whole jobs, so the result must equal
     the 8-compute-wave kernel's (which has no such split) bit for bit, and agree with a float32 torch convolution."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     dtype, C = torch.bfloat16, 128
     cin = 2 * C if two else C
     hs = S // 2 if mode in (2, 3) else S
@@ -509,7 +509,7 @@ def test_halo_tail_runs_as_half_jobs(ops, S, B, two, mode):
             lib.gmk_set_kernel_choice(3, -1, -1)
             lib.gmk_set_dev_variant(variant)
             outs[variant] = ops.conv_igemm(srcs, wf, C, 3, mode, (S, S), bias=bias, residual=res)
-            assert lib.gmk_last_kernel() == (5 if mode == 3 else 4 if variant == 0 else 3)
+            assert lib.gmk_last_kernel() == (K.CONV_HALO_STUFFED if mode == 3 else K.CONV_HALO_WS if variant == 0 else K.CONV_HALO)
     finally:
         lib.gmk_set_kernel_choice(-1, -1, -1)
         lib.gmk_set_dev_variant(0)
@@ -662,7 +662,7 @@ def test_conv1x1_pair_equals_two_launches(ops, dtype, B, S):
     """gmk_conv1x1_pair (both halves of the skip connection's data gradient from one read of the output gradient) against two
     gmk_conv_igemm launches with n0 = 0 / 128: the same bits.  (160, 32) runs on the streaming kernel in the 16-bit modes and on the LDS-DMA
     kernel (two output blocks per pixel tile) in fp32, (3, 8) takes the two-launch route inside the library, (85, 28) ends in a partial tile."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     dy = q(rnd(B, S, S, C, seed=70), dtype).cuda().to(dtype)
     w = (rnd(2 * C, C, seed=71) / 11).cuda().to(dtype)          # packed [1 tap][256 rows][128]
@@ -672,7 +672,7 @@ def test_conv1x1_pair_equals_two_launches(ops, dtype, B, S):
     rb = ops.conv_igemm([dy], w, 2 * C, 1, ops.NORMAL, (S, S), n0=C)
     assert torch.equal(a, ra) and torch.equal(b, rb)
     # 16-bit problems of at least two 128-pixel tiles per CU: the streaming kernel (weights resident in LDS; conv1x1_stream.hip) - the same bits
-    assert kernel == (14 if dtype != torch.float32 and B * S * S >= 128 * 512 else 2 if B * S * S >= 256 * 512 else 1)
+    assert kernel == (K.CONV1X1_PAIR_STREAM if dtype != torch.float32 and B * S * S >= 128 * 512 else K.CONV_IGEMM_DMA if B * S * S >= 256 * 512 else K.CONV_IGEMM)
     ref = dy.float().reshape(-1, C) @ w.float().t()
     assert rel_err(torch.cat([a, b], -1).reshape(-1, 2 * C), ref.cpu()) < TOL[dtype]
 
@@ -683,7 +683,7 @@ def test_skip_conv_weight_gradient_streaming_kernel(ops, xdt, B, S):
     """Weight gradient of the 1x1 skip convolution over a concatenated input at sizes where the streaming kernel takes it (conv1x1_stream.hip: one
     workgroup per pixel range owns both 128-channel input blocks): the same bits as the im2col kernel (GMK_DEV_VARIANT=47: same split of the pixels,
     same order inside the MFMA), and autograd's values.  (171, 28): a pixel count that is no multiple of the 64-pixel step."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     g = torch.Generator().manual_seed(B + S)
     xs = [torch.randn((B, S, S, C), generator=g).to(xdt).cuda() for _ in range(2)]
@@ -697,7 +697,7 @@ def test_skip_conv_weight_gradient_streaming_kernel(ops, xdt, B, S):
             out[variant] = (dw.clone(), lib.gmk_last_kernel())
         finally:
             lib.gmk_set_dev_variant(0)
-    assert out[0][1] == 15 and out[47][1] == 11
+    assert out[0][1] == K.CONV1X1_WGRAD_STREAM and out[47][1] == K.CONV_WGRAD
     assert torch.equal(out[0][0], out[47][0])
     # fp16 activations are re-rounded to bf16 on their way to the MFMA (as in every weight-gradient kernel): the reference uses the same values
     xr = torch.cat([x.float().bfloat16().double() for x in xs], -1).reshape(-1, 2 * C)
@@ -757,7 +757,7 @@ def test_skip_convolution_folded_into_conv2(ops, dtype, S, B):
     products and ONE rounding) and against the two-launch path it replaces (1x1 convolution -> 16-bit tensor -> residual of conv2), which
     differs only by that intermediate rounding.  Shapes: tiles inside one image (32, 64), tiles spanning images with a ragged last tile
     (28: 252 of 256 pixels per tile; 14, 7, 8), more tiles than CUs (several jobs per workgroup: 16 x 70, 32 x 80)."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     a2 = q(rnd(B, C, S, S, seed=210), dtype)
     xs = [q(rnd(B, C, S, S, seed=211 + i) * (1.0 + i), dtype) for i in range(2)]
@@ -773,7 +773,7 @@ def test_skip_convolution_folded_into_conv2(ops, dtype, S, B):
         lib.gmk_set_kernel_choice(3, -1, -1)                      # small problems too (the dispatcher asks for 32 tiles)
         assert ops.conv_skipfold_ok(ad, xd)
         out = ops.conv3x3_skipfold(ad, wf, bias.cuda(), xd, wsf, bias_sk.cuda())
-        assert lib.gmk_last_kernel() == 7
+        assert lib.gmk_last_kernel() == K.CONV_HALO_SKIPFOLD
         res = ops.conv_igemm(xd, wsf, C, 1, ops.NORMAL, (S, S), bias=bias_sk.cuda())
         two = ops.conv_igemm([ad], wf, C, 3, ops.NORMAL, (S, S), bias=bias.cuda(), residual=res)
         out2 = ops.conv3x3_skipfold(ad, wf, bias.cuda(), xd, wsf, bias_sk.cuda())
@@ -793,7 +793,7 @@ def test_merged_skip_schedule_is_bit_identical_to_the_thirteen_step_one(ops, dty
     tap steps (kMerge: 9 barriers per phase, dense weights in the free seventh piece of the half-buffers, fragment sets swapping roles).  Same products in
     the same order as the 13-step schedule (GMK_DEV_VARIANT=12 keeps it): the same bits - a dense piece overwritten too early, a stale weight tile or
     a missed wait would show here.  Whole and half jobs, several jobs per workgroup, tails."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     g = torch.Generator().manual_seed(S * 1000 + B)
     ad = torch.randn((B, S, S, C), generator=g).to(dtype).cuda()
@@ -809,7 +809,7 @@ def test_merged_skip_schedule_is_bit_identical_to_the_thirteen_step_one(ops, dty
         for variant in (0, 12, 0):
             lib.gmk_set_dev_variant(variant)
             outs.setdefault(variant, []).append(ops.conv3x3_skipfold(ad, wf, bias, xd, wsf, bias_sk))
-            assert lib.gmk_last_kernel() == 7
+            assert lib.gmk_last_kernel() == K.CONV_HALO_SKIPFOLD
     finally:
         lib.gmk_set_kernel_choice(-1, -1, -1)
         lib.gmk_set_dev_variant(0)
@@ -824,7 +824,7 @@ def test_four_slot_weight_ring_is_bit_identical_to_the_three_slot_one(ops, dtype
     """Round 6: the plain 3x3 halo kernel without a residual runs with 6-piece halos and a FOURTH weight-ring slot where a tile fits 384 slots
     (one pad column per row: 32 x 32, 28 x 28, 16 x 16, 14 x 14, 8 x 8; kRing4: the weight tile of step q + 3 is issued in step q).  Same products, same order as the three-slot ring
     (GMK_DEV_VARIANT=13 keeps it): the same bits.  One and two sources (K = 1152 / 2304), whole and half jobs, tails, several jobs per workgroup."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     g = torch.Generator().manual_seed(S * 1000 + B + 7)
     srcs = [torch.randn((B, S, S, C), generator=g).to(dtype).cuda() for _ in range(2 if two else 1)]
@@ -838,7 +838,7 @@ def test_four_slot_weight_ring_is_bit_identical_to_the_three_slot_one(ops, dtype
         for variant in (0, 13, 0):
             lib.gmk_set_dev_variant(variant)
             outs.setdefault(variant, []).append(ops.conv_igemm(srcs, wf, C, 3, ops.NORMAL, (S, S), bias=bias))
-            assert lib.gmk_last_kernel() == 4
+            assert lib.gmk_last_kernel() == K.CONV_HALO_WS
     finally:
         lib.gmk_set_kernel_choice(-1, -1, -1)
         lib.gmk_set_dev_variant(0)
@@ -861,7 +861,7 @@ def test_upsample_conv_subpixel(ops, dtype, S, B):
     (measured far below it), against the nearest-x2 form of the halo kernel it replaces (the same sum, other rounding order), bit-reproducible.
     Shapes: 7 -> 14 ... 32 -> 64; tiles spanning images with ragged tiles (7, 14), one image per tile (16), several tiles per image (32), more
     tiles than CUs (several jobs per workgroup), fewer tiles than XCDs (16 x 16, B = 3)."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     x = q(rnd(B, C, S, S, seed=300), dtype)
     w = rnd(C, C, 3, 3, seed=301) / math.sqrt(C * 9)             # fp32 master weights: the pack sums them before rounding
@@ -883,7 +883,7 @@ def test_upsample_conv_subpixel(ops, dtype, S, B):
                     assert torch.equal(pk[a, b, ty, tx], q(want, dtype))
                     assert torch.equal(wsub_d.float().cpu().view(2, 2, 2, 2, C, C)[a, b, ty, tx], q(want, torch.bfloat16).t())
     out = ops.conv_subpixel(xd, wsub, C, ops.SUBPIXEL_UPSAMPLE, bias=bias.cuda())
-    assert lib.gmk_last_kernel() == 8 and out.shape == (B, 2 * S, 2 * S, C)
+    assert lib.gmk_last_kernel() == K.CONV_SUBPIXEL_UPSAMPLE and out.shape == (B, 2 * S, 2 * S, C)
     e = rel_err(nchw(out), ref)
     assert e < TOL[torch.bfloat16], e
     wf = torch.empty(w.numel(), device="cuda", dtype=dtype)
@@ -902,7 +902,7 @@ def test_transposed_dgrad_subpixel(ops, dtype, res, S, B):
     meet 1 / 2 / 2 / 4 taps of the ordinary data-gradient pack over the gradient's own grid - the products of the zero-stuffed halo form without
     its multiplications by zero.  Against autograd, with and without the residual the net adds there (the skip path's gradient), and against the
     zero-stuffed form: the same products accumulated in fp32, so the two differ by summation order only (<= 1 ulp of the 16-bit output)."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     x = q(rnd(B, C, 2 * S, 2 * S, seed=310), dtype).requires_grad_(True)
     w = q(rnd(C, C, 3, 3, seed=311) / math.sqrt(C * 9), dtype).requires_grad_(True)
@@ -917,19 +917,19 @@ def test_transposed_dgrad_subpixel(ops, dtype, res, S, B):
     rd = nhwc(r, dtype) if res else None
     assert ops.conv_subpixel_ok(B, S, S, C, dtype)
     dx = ops.conv_subpixel(dyd, wd, C, ops.SUBPIXEL_TRANSPOSED, residual=rd)
-    assert lib.gmk_last_kernel() == 9
+    assert lib.gmk_last_kernel() == K.CONV_SUBPIXEL_TRANSPOSED
     assert rel_err(nchw(dx), ref) < TOL[torch.bfloat16]
     try:
         lib.gmk_set_kernel_choice(2, -1, -1)                        # the four phase launches of the LDS-DMA kernel: the same products per output
         dx_p = ops.conv_igemm([dyd], wd, C, 3, ops.TRANSPOSED2, (2 * S, 2 * S), residual=rd)
-        assert lib.gmk_last_kernel() == 6
+        assert lib.gmk_last_kernel() == K.CONV_DMA_PHASES
     finally:
         lib.gmk_set_kernel_choice(-1, -1, -1)
     ulp = 2.0 ** (-10 if dtype == torch.float16 else -7)
     assert rel_err(nchw(dx), nchw(dx_p)) < 1.5 * ulp
     # through the dispatcher: gmk_conv_igemm(GMK_CONV_TRANSPOSED2) takes the sub-pixel form where it is eligible
     dx_auto = ops.conv_igemm([dyd], wd, C, 3, ops.TRANSPOSED2, (2 * S, 2 * S), residual=rd)
-    assert lib.gmk_last_kernel() == 9 and torch.equal(dx_auto, dx)
+    assert lib.gmk_last_kernel() == K.CONV_SUBPIXEL_TRANSPOSED and torch.equal(dx_auto, dx)
 
 
 @pytest.mark.parametrize("dtype,S,B", [(torch.bfloat16, s, b) for s, b in SUBPIXEL_SHAPES] + [(torch.float16, 7, 9), (torch.float16, 16, 3)])
@@ -938,7 +938,7 @@ def test_upsample_dgrad_subpixel(ops, dtype, S, B):
     sum-pool that is the backward of F.interpolate(nearest)) as ONE launch: the transpose of the sub-pixel forward - the four parity views of the
     output gradient, 2x2 taps each on the transposed pre-summed matrices, accumulated in fp32 and rounded once.  Against autograd in fp32 on the rounded
     gradient and fp32 weights, and against the two launches it replaces (which round the high-resolution intermediate to 16 bits before the pool)."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     x = rnd(B, C, S, S, seed=320).requires_grad_(True)
     w = rnd(C, C, 3, 3, seed=321) / math.sqrt(C * 9)
@@ -950,7 +950,7 @@ def test_upsample_dgrad_subpixel(ops, dtype, S, B):
     ops.pack_upsample_weight(w.cuda(), None, wsub_d)
     assert ops.conv_subpixel_ok(B, S, S, C, dtype)
     dx = ops.conv_subpixel(dyd, wsub_d, C, ops.SUBPIXEL_UPSAMPLE_DGRAD)
-    assert lib.gmk_last_kernel() == 10 and dx.shape == (B, S, S, C)
+    assert lib.gmk_last_kernel() == K.CONV_SUBPIXEL_UPSAMPLE_DGRAD and dx.shape == (B, S, S, C)
     e = rel_err(nchw(dx), x.grad)
     assert e < TOL[torch.bfloat16], e
     if dtype == torch.bfloat16:            # (gradients are bf16 in the product; the pooling kernel has no fp16 form)
@@ -971,7 +971,7 @@ def test_upsample_wgrad_subpixel(ops, xdt, S, B):
     matrices accumulated over the LOW-resolution slots (two dY parity streams and eight accumulators per workgroup), folded onto the 9 taps by a
     deterministic reduce.  Against autograd in fp32 on the rounded operands, against the nearest-x2 slot kernel it replaces (the same products,
     other summation order), bit-reproducible; small problems (too few slot chunks per split) are declined."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     C = 128
     x = q(rnd(B, C, S, S, seed=330), xdt)
     w = (rnd(C, C, 3, 3, seed=331) / math.sqrt(C * 9)).requires_grad_(True)
@@ -986,7 +986,7 @@ def test_upsample_wgrad_subpixel(ops, xdt, S, B):
     assert ok
     dw = torch.empty((C, C, 3, 3), device="cuda")
     ops.conv_wgrad_subpixel(dyd, xd, dw)
-    assert lib.gmk_last_kernel() == 16
+    assert lib.gmk_last_kernel() == K.CONV_WGRAD_SUBPIXEL
     e = rel_err(dw, w.grad)
     assert e < TOL[torch.bfloat16], e
     dw_old = torch.empty_like(dw)

@@ -155,12 +155,12 @@ def test_inpaint_merge_draws(ops, seed, off):
     assert d1 <= NORMAL_TOL and d2 <= NORMAL_TOL
 
 
-# GroupNorm dropout: one shape per forward kernel that can apply the mask.  (H = W, dtype, groups, kernel id of gmk_last_kernel)
-GN_CASES = [(8, torch.bfloat16, 32, 22),       # streaming gn_silu_fwd_kernel
-            (16, torch.bfloat16, 32, 21),      # gn_silu_fwd_reg_kernel, 64-channel slabs
-            (64, torch.bfloat16, 32, 21),      # the 1024-thread 32-channel-slab form
-            (8, torch.float32, 32, 22),
-            (12, torch.bfloat16, 64, 22)]      # the narrow branch (2 channels per group)
+# GroupNorm dropout: one shape per forward kernel that can apply the mask.  (H = W, dtype, groups, K symbol of the kernel gmk_last_kernel reports)
+GN_CASES = [(8, torch.bfloat16, 32, "GN_FWD"),          # streaming gn_silu_fwd_kernel
+            (16, torch.bfloat16, 32, "GN_FWD_REG"),      # gn_silu_fwd_reg_kernel, 64-channel slabs
+            (64, torch.bfloat16, 32, "GN_FWD_REG"),      # the 1024-thread 32-channel-slab form
+            (8, torch.float32, 32, "GN_FWD"),
+            (12, torch.bfloat16, 64, "GN_FWD")]         # the narrow branch (2 channels per group)
 GN_SEED, GN_OFF = (1 << 63) + 12345, (1 << 33) - 4096      # the 8 x 8 case ends on a multiple of 2^32, the larger ones cross it
 GN_P = 0.25
 
@@ -177,7 +177,7 @@ def test_groupnorm_dropout_mask_forward(ops):
     """Dropped elements are exactly zero; kept ones are the undropped output over 1 - p: within 2^-7 relative for bf16 (two half-ulp roundings
     of 2^-9 each - the undropped output's and the scaled one's - doubled for margin), 2^-22 for fp32 in the same way.  One loop over the
     shapes, so that the kernels that ran can be counted: the three bf16 shapes with 32 groups cover both forward kernels."""
-    from generative_models_amd._lib import lib
+    from generative_models_amd._lib import K, lib
     ran = []
     for S, dtype, G, kernel in GN_CASES:
         case = f"{S}x{S} {dtype} groups {G}"
@@ -186,7 +186,7 @@ def test_groupnorm_dropout_mask_forward(ops):
         y0, _, _ = ops.gn_silu_fwd(xd, gd, bd, G)
         y, _, _ = ops.gn_silu_fwd(xd, gd, bd, G, dropout=(GN_P, GN_SEED, GN_OFF))
         ran.append(lib.gmk_last_kernel())
-        assert ran[-1] == kernel, f"{case}: kernel {ran[-1]} ran, expected {kernel}"
+        assert ran[-1] == getattr(K, kernel), f"{case}: kernel {ran[-1]} ran, expected {kernel}"
         y0, y = y0.cpu().double(), y.cpu().double()
         keep = t(philox_ref.keep_mask(GN_SEED, GN_OFF, x.numel(), GN_P)).reshape(x.shape)      # NHWC element order
         assert 0.70 < float(keep.double().mean()) < 0.80
@@ -196,7 +196,7 @@ def test_groupnorm_dropout_mask_forward(ops):
         excess = (y[keep] - want).abs() - tol * want.abs()
         assert float(excess.max()) <= 0, f"{case}: {int((excess > 0).sum())} kept elements differ from y0 / (1 - p)"
         assert int((y[keep] != 0).sum()) > 0.99 * int(keep.sum()), case                         # kept elements are not zeroed
-    assert set(ran[:3]) == {21, 22}
+    assert set(ran[:3]) == {K.GN_FWD_REG, K.GN_FWD}
 
 
 @pytest.mark.parametrize("S", [8, 16])

@@ -81,8 +81,8 @@ def test_rank_is_the_literal_rule_on_the_gpu_tests_grid():
 def test_lds_capacity_constant_matches_the_kernel():
     from generative_models_amd import ops
     src = open(os.path.join(ROOT, "generative_models_amd", "csrc", "diffusion_ew.hip")).read()
-    m = re.search(r"constexpr int kDynKeys = (\d+);", src)
-    assert m and int(m.group(1)) == ops.DYN_THRESHOLD_KEYS >= 12288
+    m = re.search(r"#define GMK_DYN_THRESHOLD_KEYS (\d+)\b", open(os.path.join(ROOT, "include", "gmk.h")).read())      # the kernel's constant is the header's
+    assert "constexpr int kDynKeys = GMK_DYN_THRESHOLD_KEYS;" in src and m and int(m.group(1)) == ops.DYN_THRESHOLD_KEYS >= 12288
 
 
 @pytest.mark.parametrize("bad", [-0.1, 1.0001, float("nan"), "x"])

@@ -228,9 +228,9 @@ def test_entries_reject_bad_arguments_before_any_launch():
 def test_constants_match_the_kernel_and_wrappers_check_first():
     from generative_models_amd import ops
     src = open(os.path.join(ROOT, "generative_models_amd", "csrc", "diffusion_ew.hip")).read()
-    m = re.search(r"constexpr int kXLossKeep = (\d+);", src)
-    assert m and int(m.group(1)) == ops.X_LOSS_KEEP == ops.DYN_THRESHOLD_KEYS and ops.X_LOSS_KEEP % 256 == 0
     hdr = open(os.path.join(ROOT, "include", "gmk.h")).read()
+    m = re.search(r"#define GMK_X_LOSS_KEEP (\d+)\b", hdr)      # the kernel's constant is the header's
+    assert "constexpr int kXLossKeep = GMK_X_LOSS_KEEP;" in src and m and int(m.group(1)) == ops.X_LOSS_KEEP == ops.DYN_THRESHOLD_KEYS and ops.X_LOSS_KEEP % 256 == 0
     for name, code in ops.X_LOSS_WEIGHTS.items():
         assert re.search(rf"#define GMK_LOSS_W_{name.upper()} {code}\b", hdr)
     t = torch.zeros(2, 8)
