@@ -128,7 +128,14 @@ int gmk_pack_conv_weights_multi(const float* arena, void* packs, int count, cons
  * two calls of 16 groups each, simple_unet.py:150,161); mean/rstd: fp32 [B][groups] (written).
  * groups < 0: -groups channels per group (1..16, any size: nn.GroupNorm(32, 96) has 3), ceil(C / -groups) groups whose last one may be
  * partial - for zero-padded widths, where it lies in the padding; mean/rstd then have ceil(C / -groups) columns.  Same convention in
- * gmk_gn_silu_bwd. */
+ * gmk_gn_silu_bwd.
+ * Precision of the statistics: ONE pass of fp32 sums over the group's n = HW * C / groups values (sum and sum of squares, biased
+ * var = E[x^2] - mean^2 clamped at 0, rstd = 1 / sqrt(var + eps)), for every storage type.  With m and sigma the group's exact mean and
+ * standard deviation the results lie within
+ *     |rstd - exact| / exact <= 4 * 2^-24 * log2(n) * (1 + m^2 / sigma^2)        |mean - exact| <= 4 * 2^-24 * log2(n) * sqrt(m^2 + sigma^2)
+ * (measured: a tenth to a fifth of that).  The subtraction E[x^2] - mean^2 is where the m^2 / sigma^2 comes from: centred activations
+ * give rstd to 1e-7, a group whose mean lies 8 sigma from zero to 1e-5 against a bound of 1.7e-4 - the size of fp16's rounding.
+ * tests/test_gpu_gn_conformance.py holds every kernel form to this bound. */
 int gmk_gn_silu_fwd(const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd,
                     int B, int HW, int C, int groups, float eps, const float* stats_part, int tile_pixels, int ntiles,
                     float drop_p, uint64_t drop_seed, uint64_t drop_offset, const float* xadd, int xadd_stride, int dtype,

@@ -1,5 +1,5 @@
 """Builds the host-dispatch trace tools of tools/ (gn_launch_trace.cpp, conv_launch_trace.cpp, smallconv_launch_trace.cpp) against the tree's
-csrc/ without a GPU; used by tests/test_host_logic.py and tests/test_host_conv_ref.py."""
+csrc/ without a GPU; used by tests/test_host_logic.py, tests/test_host_conv_ref.py and tests/test_host_gn_ref.py."""
 import os
 import re
 import subprocess
@@ -14,7 +14,7 @@ _TRACE_TOOLS = {}
 
 def build(tool, sources):
     """tools/<tool>.cpp built against the tree's csrc/<sources>.hip (host objects + tools/launch_trace_stub.cpp as the HIP runtime, no GPU):
-    returns run(which, stdin=None, env=None) -> the trace lines.  One hipcc job per source, at most 16 at a time; the kernel-argument
+    returns run(which, stdin=None, env=None) -> the trace lines (run.notes: the file of the code objects' kernel metadata).  One hipcc job per source, at most 16 at a time; the kernel-argument
     layout is read from the code object inside each host object.  Built once per session (shared by the test modules)."""
     import atexit
     import shutil
@@ -63,6 +63,7 @@ def build(tool, sources):
         r = subprocess.run([exe, which], input=stdin, capture_output=True, text=True, timeout=600, env=dict(base, LAUNCH_TRACE_NOTES=notes, **(env or {})))
         assert r.returncode == 0, r.stderr[-2000:]
         return r.stdout.splitlines()
+    run.notes = notes          # the code objects' kernel metadata as text: every kernel symbol the sources instantiate
     _TRACE_TOOLS[tool] = run
     return run
 

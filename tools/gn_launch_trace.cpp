@@ -7,9 +7,12 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -c csrc/gn_silu.hip csrc/gmk_common.hip        (the Makefile's flags)
 //   clang++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I<rocm>/include tools/gn_launch_trace.cpp tools/launch_trace_stub.cpp gn_silu.o gmk_common.o
 //   llvm-readelf --notes <code object: the hipcc line with --cuda-device-only --no-gpu-bundle-output> > notes.txt
-//   LAUNCH_TRACE_NOTES=notes.txt ./a.out <entry point | all | landmarks>
+//   LAUNCH_TRACE_NOTES=notes.txt ./a.out <entry point | all | landmarks | cases>
 //
 // `landmarks` prints the handful of rows tests/test_host_logic.py asserts (C = 128, 32 groups, the five sizes of the U-Net levels).
+// `cases` reads one call per line from stdin (the case tables of tests/gn_ref.py) and prints its row:
+//   <entry> <mode | -1> <dtype> <x_dtype> <HW> <C> <groups> <groups_b> <dropout p> <xadd> <dxsum> <producer stats> <B>
+// entry: gn_silu_fwd, gn_stats, gn_silu_bwd, gn_silu_fwd_pair (groups, groups_b = the two consumers) or gn_silu_bwd_pair (up, down).
 // A stand-alone CPU program: not part of the library build, not a shared library.
 #include <cstdio>
 #include <cstdlib>
@@ -176,6 +179,48 @@ void sweep_small(const Axes& a, const char* which) {
         ROW("sumpool2x2", gmk_sumpool2x2(ptr(61), nullptr, 1, 4, 4, 8, GMK_BF16, kStream), "null y");
     }
 }
+
+// one call per stdin line; the three flags are 0 / 1 (absent / present with a row stride of C + 24)
+int sweep_cases() {
+    char line[512], entry[64];
+    while (fgets(line, sizeof(line), stdin)) {
+        int m, dt, xdt, HW, C, G, G2, xa, ds, st, B;
+        float p;
+        if (line[0] == '\n' || line[0] == '#') continue;
+        if (sscanf(line, "%63s %d %d %d %d %d %d %d %f %d %d %d %d", entry, &m, &dt, &xdt, &HW, &C, &G, &G2, &p, &xa, &ds, &st, &B) != 13) {
+            fprintf(stderr, "cases: cannot read \"%s\"\n", line);
+            return 2;
+        }
+        xa = xa ? 2 : 0; ds = ds ? 2 : 0; st = st ? 2 : 0;
+        set_mode(m);
+        char what[256];
+        snprintf(what, sizeof(what), "mode=%d dtype=%d x_dtype=%d HW=%d C=%d G=%d,%d drop=%g xadd=%d dxsum=%d stats=%d B=%d", m, dt, xdt, HW, C, G, G2, (double)p,
+                 xa, ds, st, B);
+        if (!strcmp(entry, "gn_silu_fwd"))
+            row(entry, what, gmk_gn_silu_fwd(ptr(1), ptr(2), ptr<float>(3), ptr<float>(4), ptr<float>(5), ptr<float>(6), B, HW, C, G, kEps, opt_ptr(st, 7), 32, 11, p,
+                                             kSeed, kOffset, opt_ptr(xa, 8), opt_stride(xa, C), dt, kStream));
+        else if (!strcmp(entry, "gn_stats"))
+            row(entry, what, gmk_gn_stats(ptr(1), ptr<float>(3), ptr<float>(4), ptr<float>(5), ptr<float>(6), ptr<float>(12), ptr<float>(13), C + 40, B, HW, C, G, kEps,
+                                          opt_ptr(xa, 8), opt_stride(xa, C), dt, kStream));
+        else if (!strcmp(entry, "gn_silu_bwd"))
+            row(entry, what, gmk_gn_silu_bwd(ptr(21), ptr(1), ptr<float>(3), ptr<float>(4), ptr<float>(5), ptr<float>(6), ptr(22), ptr(23), ptr(24), ptr<float>(25),
+                                             ptr<float>(26), const_cast<float*>(opt_ptr(ds, 27)), opt_stride(ds, C), B, HW, C, G, p, kSeed, kOffset, opt_ptr(xa, 8),
+                                             opt_stride(xa, C), dt, xdt, kStream));
+        else if (!strcmp(entry, "gn_silu_fwd_pair"))
+            row(entry, what, gmk_gn_silu_fwd_pair(ptr(1), ptr(31), ptr(32), ptr<float>(33), ptr<float>(34), ptr<float>(35), ptr<float>(36), ptr<float>(37), ptr<float>(38),
+                                                  ptr<float>(39), ptr<float>(40), B, HW, C, G, G2, kEps, opt_ptr(xa, 8), opt_stride(xa, C), dt, kStream));
+        else if (!strcmp(entry, "gn_silu_bwd_pair"))
+            row(entry, what, gmk_gn_silu_bwd_pair(ptr(1), ptr(41), ptr(42), ptr<float>(43), ptr<float>(44), ptr<float>(45), ptr<float>(46), ptr<float>(47), ptr<float>(48),
+                                                  G, ptr(51), ptr(52), ptr<float>(53), ptr<float>(54), ptr<float>(55), ptr<float>(56), ptr<float>(57), ptr<float>(58), G2,
+                                                  ptr(24), const_cast<float*>(opt_ptr(ds, 27)), opt_stride(ds, C), B, HW, C, opt_ptr(xa, 8), opt_stride(xa, C), xdt,
+                                                  kStream));
+        else {
+            fprintf(stderr, "cases: unknown entry point \"%s\"\n", entry);
+            return 2;
+        }
+    }
+    return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -183,6 +228,7 @@ int main(int argc, char** argv) {
     launch_trace_padding(48, 44, 4);      // GnFwdSide: five pointers and an int
     launch_trace_padding(72, 68, 4);      // GnBwdSide: eight pointers and an int
     const bool landmarks = !strcmp(which, "landmarks"), all = !strcmp(which, "all");
+    if (!strcmp(which, "cases")) return sweep_cases();
     if (landmarks) {
         Axes a = kLandmarks, grads = kLandmarks, mixed = kLandmarks;
         grads.dtype = {GMK_F32};                    // same-typed x
