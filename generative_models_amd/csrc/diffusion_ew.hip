@@ -53,18 +53,49 @@ __device__ __forceinline__ float block_sum(float v, float* red) {   // 256 threa
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// grid (ceil(n/1024), B): z = x*alpha + eps*sigma with logsnr = schedule(u[b])
+// ---- the reference's closed-form log-SNR schedules (diffusion_utils.py:169-201) with the range as arguments; GaussianDiffusion there picks
+// 'cosine', -20, 20 (gaussian_diffusion.py:33-34): kSchedA / kSchedB, which gmk_q_sample and gmk_logsnr_schedule pass.
+//   GMK_SCHED_COSINE       -2 log(tan(a u + b))        b = atan(exp(-lmax / 2)), a = atan(exp(-lmin / 2)) - b
+//   GMK_SCHED_UNIFORM      lmin u + lmax (1 - u)
+//   GMK_SCHED_BETA_CONST   -log(expm1(a u + b))        b = softplus(-lmax),      a = softplus(-lmin) - b
+//   GMK_SCHED_BETA_LINEAR  -log(expm1(a (u u) + b))    as beta_const
+// then + shift (skipped when shift == 0, so that no bit moves; the additive shift of Hoogeboom et al. 2023, an extension).  a, b come from the
+// host (float64, rounded to fp32 the way torch applies a double scalar to an fp32 tensor); every operation here is one correctly rounded fp32
+// operation in the reference's order - the products and sums through __fmul_rn / __fadd_rn, which the compiler may not contract - so numpy
+// float32 restates the argument bit for bit.
+// The kind is a run-time value, the same in every thread of a launch: one instantiation.  As a template argument it measured no faster
+// (15.3-15.6 us per launch at 3 x 32 x 32, B = 2048, against 15.0-15.3 with the run-time switch).
+__device__ __forceinline__ float sched_logsnr(int kind, float a, float b, float lmin, float lmax, float shift, float u) {
+    float l;
+    if (kind == GMK_SCHED_UNIFORM) {
+        l = __fadd_rn(__fmul_rn(lmin, u), __fmul_rn(lmax, __fsub_rn(1.0f, u)));
+    } else {
+        const float t = __fadd_rn(__fmul_rn(a, kind == GMK_SCHED_BETA_LINEAR ? __fmul_rn(u, u) : u), b);
+        l = kind == GMK_SCHED_COSINE ? -2.0f * logf(tanf(t)) : -logf(expm1f(t));
+    }
+    return shift != 0.0f ? __fadd_rn(l, shift) : l;
+}
+
+// grid (ceil(n/1024), B), 256 threads: z = x*alpha + eps*sigma with logsnr = schedule(u[b]), the schedule once per workgroup (every thread of
+// it ahead of its loop).  Any n: image b starts at element b n, which is 16-byte aligned only when b n % 4 == 0, so the first `head` =
+// (-b n) mod 4 elements of the image go one by one (the first `head` threads of workgroup 0), the 16-byte loads and stores start behind them -
+// x, eps and z share the offset, hence the alignment - and the last (n - head) % 4 elements go one by one again.  With n % 4 == 0 (all
+// gmk_q_sample takes) head is 0.  Each element is the same three operations on either path.
 __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                                       const float* __restrict__ u, float* __restrict__ logsnr,
-                                                      float* __restrict__ z, int64_t n) {
+                                                      float* __restrict__ z, int64_t n, int kind, float a, float sb, float lmin,
+                                                      float lmax, float shift) {
     const int b = blockIdx.y;
-    const float t = __fadd_rn(__fmul_rn(kSchedA, u[b]), kSchedB);
-    const float l = -2.0f * logf(tanf(t));
+    const float l = sched_logsnr(kind, a, sb, lmin, lmax, shift, u[b]);
     if (blockIdx.x == 0 && threadIdx.x == 0) logsnr[b] = l;
     const float alpha = sqrtf(1.0f / (1.0f + expf(-l)));
     const float sigma = sqrtf(1.0f / (1.0f + expf(l)));
     const int64_t base = (int64_t)b * n;
-    for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+    const int64_t pad = (4 - (base & 3)) & 3;
+    const int64_t head = pad < n ? pad : n;
+    if (blockIdx.x == 0 && threadIdx.x < head)
+        z[base + threadIdx.x] = __fadd_rn(__fmul_rn(x[base + threadIdx.x], alpha), __fmul_rn(sigma, eps[base + threadIdx.x]));
+    for (int64_t i = head + (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
         if (i + 3 < n) {
             float xv[4], ev[4], o[4];
             load4(x + base + i, xv);
@@ -1235,8 +1266,25 @@ extern "C" int gmk_q_sample(const float* x, const float* eps, const float* u, fl
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0 && n % 4 == 0, "gmk_q_sample: bad shape B=%d n=%lld (n %% 4 == 0 required)", B,
                 (long long)n);
     const int gx = row_grid(n, 1024);
-    q_sample_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(x, eps, u, logsnr, z, n);
+    q_sample_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(x, eps, u, logsnr, z, n, GMK_SCHED_COSINE, kSchedA, kSchedB, 0.f, 0.f, 0.f);
     return gmk_check_launch("gmk_q_sample");
+}
+
+#define GMK_REQUIRE_SCHED(kind, a, b, lmin, lmax, shift, who)                                                                      \
+    do {                                                                                                                           \
+        GMK_REQUIRE((kind) >= GMK_SCHED_COSINE && (kind) <= GMK_SCHED_BETA_LINEAR,                                                 \
+                    who ": kind = %d, must be 0 (cosine), 1 (uniform), 2 (beta_const) or 3 (beta_linear)", (int)(kind));           \
+        GMK_REQUIRE(isfinite(a) && isfinite(b) && isfinite(lmin) && isfinite(lmax) && isfinite(shift), who ": non-finite schedule argument"); \
+    } while (0)
+
+extern "C" int gmk_q_sample_sched(const float* x, const float* eps, const float* u, float* logsnr, float* z, int B, int64_t n, int kind,
+                                  float a, float b, float lmin, float lmax, float shift, void* stream) {
+    GMK_REQUIRE(x && eps && u && logsnr && z, "gmk_q_sample_sched: null pointer");
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_q_sample_sched: bad shape B=%d n=%lld", B, (long long)n);
+    GMK_REQUIRE_SCHED(kind, a, b, lmin, lmax, shift, "gmk_q_sample_sched");
+    const int gx = row_grid(n, 1024);
+    q_sample_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(x, eps, u, logsnr, z, n, kind, a, b, lmin, lmax, shift);
+    return gmk_check_launch("gmk_q_sample_sched");
 }
 
 extern "C" int gmk_v_loss(const float* v, const float* z, const float* x, const float* eps, const float* logsnr,
@@ -1513,16 +1561,16 @@ extern "C" int gmk_ddim_step_vec(const float* v, const float* v_uncond, const fl
 }
 
 namespace {
-// u -> logsnr (diffusion_utils.py:198-201); optionally u = (i + 1) / T - shift from integer times (gaussian_diffusion.py:90-91)
-__global__ void schedule_kernel(const float* __restrict__ u, const int64_t* __restrict__ ti, float T, float shift,
-                                float* __restrict__ u_out, float* __restrict__ logsnr, int B) {
+// u -> logsnr = sched_logsnr(u) (diffusion_utils.py:169-201); optionally u = (i + 1) / T - u_shift from integer times (gaussian_diffusion.py:90-91)
+__global__ void schedule_kernel(const float* __restrict__ u, const int64_t* __restrict__ ti, float T, float u_shift, int kind, float a,
+                                float sb, float lmin, float lmax, float shift, float* __restrict__ u_out, float* __restrict__ logsnr,
+                                int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     float uu = ti ? __fdiv_rn((float)(ti[b] + 1), T) : u[b];
-    uu = __fsub_rn(uu, shift);
+    uu = __fsub_rn(uu, u_shift);
     if (u_out) u_out[b] = uu;
-    const float t = __fadd_rn(__fmul_rn(kSchedA, uu), kSchedB);
-    logsnr[b] = -2.0f * logf(tanf(t));
+    logsnr[b] = sched_logsnr(kind, a, sb, lmin, lmax, shift, uu);
 }
 
 // gaussian_diffusion.py:147-154: x-target implied by two teacher DDIM steps, its i == 0 select, and the eps-target
@@ -1556,8 +1604,19 @@ extern "C" int gmk_logsnr_schedule(const float* u, const int64_t* i_times, int n
                                    float* logsnr, int B, void* stream) {
     GMK_REQUIRE((u != nullptr) != (i_times != nullptr) && logsnr && B > 0, "gmk_logsnr_schedule: give exactly one of u / i_times");
     GMK_REQUIRE(!i_times || num_steps >= 1, "gmk_logsnr_schedule: num_steps");
-    schedule_kernel<<<(B + 255) / 256, 256, 0, gmk_stream(stream)>>>(u, i_times, (float)num_steps, shift, u_out, logsnr, B);
+    schedule_kernel<<<(B + 255) / 256, 256, 0, gmk_stream(stream)>>>(u, i_times, (float)num_steps, shift, GMK_SCHED_COSINE, kSchedA, kSchedB,
+                                                                     0.f, 0.f, 0.f, u_out, logsnr, B);
     return gmk_check_launch("gmk_logsnr_schedule");
+}
+
+extern "C" int gmk_logsnr_schedule_sched(const float* u, const int64_t* i_times, int num_steps, float u_shift, int kind, float a, float b,
+                                         float lmin, float lmax, float shift, float* u_out, float* logsnr, int B, void* stream) {
+    GMK_REQUIRE((u != nullptr) != (i_times != nullptr) && logsnr && B > 0, "gmk_logsnr_schedule_sched: give exactly one of u / i_times");
+    GMK_REQUIRE(!i_times || num_steps >= 1, "gmk_logsnr_schedule_sched: num_steps");
+    GMK_REQUIRE_SCHED(kind, a, b, lmin, lmax, shift, "gmk_logsnr_schedule_sched");
+    schedule_kernel<<<(B + 255) / 256, 256, 0, gmk_stream(stream)>>>(u, i_times, (float)num_steps, u_shift, kind, a, b, lmin, lmax, shift, u_out,
+                                                                     logsnr, B);
+    return gmk_check_launch("gmk_logsnr_schedule_sched");
 }
 
 extern "C" int gmk_distill_target(const float* z_teacher, const float* z_t, const float* x_pred_teacher, const float* logsnr,

@@ -23,7 +23,8 @@ import os
 import torch
 
 from .. import checkpoint, common, ops, parallel
-from .gaussian_diffusion import GaussianDiffusion, PhiloxStream, dyn_threshold_check, edit_start, loss_weight_check, restore_operator, time_importance_check
+from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, dyn_threshold_check, edit_start, loss_weight_check, restore_operator,
+                                 schedule_check, time_importance_check)
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -92,6 +93,13 @@ def make_plugin(GMBase, AttrDict):
         DG.importance_floor = 0.01     # the uniform share of the sampling distribution, in (0, 1] (untuned)
         DG.loss_profile = 0            # 1: keep the per-time profile of the train and test losses (gmk_loss_profile) and write it to
                                        # <logdir>/loss_profile.csv after every evaluation; nothing is sampled from it; not with teacher_path
+        DG.logsnr_schedule = "cosine"  # the noise schedule u -> logsnr of training: 'cosine' (reference) | 'uniform' | 'beta_const' | 'beta_linear', the closed-form
+                                       # schedules of the reference's registry (diffusion_utils.py:169-201); other than the defaults: not in the reference's plugin
+        DG.logsnr_min = -20.0          # its range, -20 <= logsnr_min < logsnr_max <= 20 (the reference's pick: -20, 20); the likelihoods (nlogp_samples,
+        DG.logsnr_max = 20.0           # ode_nlogp_steps) are integrated over [-20, 20] and refuse another range or a shift
+        DG.logsnr_shift = 0.0          # added to the log-SNR, |shift| <= 10: 2 log(32 / d) for d x d images (Hoogeboom et al. 2023), -1.386 at 64 x 64
+        DG.sample_logsnr_schedule = "" # the curve the samplers walk (sample, evaluate, inpaint, edit, restore, encode / decode): '' the training one, else a
+                                       # kind as above on the same range and shift ('uniform' is DPM-Solver++'s grid for few steps)
         DG.image_size = 0              # S > 0: images are S x S (CIFAR-10: 32 with in_channels 3); 0: the reference's 28, or 32 with pad32
 
         def __init__(self, G):
@@ -158,13 +166,25 @@ def make_plugin(GMBase, AttrDict):
                 get("time_importance"), get("importance_decay"), get("importance_warmup"), get("importance_floor"), get("loss_profile"),
                 self.teacher_net is not None, parallel.world())
             self.loss_profile = loss_profile
+            schedule, sample_schedule = schedule_check(get("logsnr_schedule"), get("logsnr_min"), get("logsnr_max"), get("logsnr_shift"),
+                                                       get("sample_logsnr_schedule"))
+            for name in ("nlogp_samples", "ode_nlogp_steps"):
+                if getattr(self, name) > 0 and not schedule.full_range:
+                    raise ValueError(f"{name} > 0 with logsnr_min = {schedule.logsnr_min:g}, logsnr_max = {schedule.logsnr_max:g}, logsnr_shift = "
+                                     f"{schedule.shift:g}: the likelihoods are integrated over logsnr in [-20, 20]; leave the three at -20, 20, 0")
+            # the defaults are the reference's pick, which the original entries hold as constants: None keeps a default run on them
+            # (a sampling schedule of None would mean the training one, so it is only dropped together with it)
+            if schedule == Schedule():
+                sample_schedule = None if sample_schedule == schedule else sample_schedule
+                schedule = None
             seed = int(get("seed")) * 1000 + parallel.rank()
             self.diffusion = GaussianDiffusion(mean_type=get("mean_type"), num_steps=int(get("timesteps")),
                                                sampler=get("sampler"), teacher_net=self.teacher_net,
                                                teacher_mode=get("teacher_mode"), sample_cond_w=get("sample_cond_w"),
                                                seed=seed, dyn_threshold=dyn_threshold, loss_weight=loss_weight, loss_gamma=loss_gamma,
                                                time_sampler=time_sampler, time_importance=time_importance, importance_decay=importance_decay,
-                                               importance_warmup=importance_warmup, importance_floor=importance_floor, loss_profile=loss_profile)
+                                               importance_warmup=importance_warmup, importance_floor=importance_floor, loss_profile=loss_profile,
+                                               schedule=schedule, sample_schedule=sample_schedule)
             self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
             # EMA of the weights (an extension): a second SimpleUnet of the same arena layout, so one fused launch updates both.  It is seeded
             # from `net` at the first optimiser step (after a data-parallel broadcast of the initial weights) or by a checkpoint load.

@@ -5,6 +5,10 @@ return structure; `net` is the HIP `SimpleUnet` or a `functools.partial` of it c
 as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in libgmk.so:
 
 * q_sample + log-SNR schedule          gmk_q_sample     (:94-100, diffusion_utils.py:65-73,198-201)
+* other schedules (`schedule=`, `sample_schedule=`)  `Schedule`: the reference's closed-form family (diffusion_utils.py:169-201: cosine, uniform, beta_const,
+                                        beta_linear with logsnr_min / logsnr_max) plus an additive shift, through gmk_q_sample_sched /
+                                        gmk_logsnr_schedule_sched for training and `Schedule.host` for every sampler grid; None is the reference's pick
+                                        ('cosine', -20, 20, :33-34) through the entries above
 * v -> x_hat/eps_hat, clip, loss, dL/dv gmk_v_loss       (:61-77,:165-169 and their backward)
 * DDIM / ancestral / guidance update   gmk_sampler_step (:174-243,:292)
 * DPM-Solver++(2M) update              gmk_dpm_solver_step (sampler='dpmpp_2m': an extension, no reference call site)
@@ -30,7 +34,7 @@ distillation (:87-91,:105-154) is supported: `teacher_net` is a 
 steps run through gmk_ddim_step_vec / gmk_distill_target, the student is conditioned on the guidance weight.
 """
 from collections import namedtuple
-from functools import partial
+from functools import lru_cache, partial
 
 import math
 import os
@@ -56,10 +60,111 @@ def logsnr_schedule_cosine_host(u):
     return np.float32(-2.0) * np.log(np.tan(SCHED_A * u + SCHED_B, dtype=np.float32), dtype=np.float32)
 
 
-def sampler_grid(num_steps):
+SCHEDULE_KINDS = ("cosine", "uniform", "beta_const", "beta_linear")
+SCHEDULE_LOGSNR_BOUND = 20.0            # beyond +-20 the cosine form loses its argument to fp32 rounding (at -20 it is already 1e-3 off its float64 value)
+SCHEDULE_SHIFT_BOUND = 10.0
+
+
+def _softplus64(x):
+    return np.logaddexp(np.float64(x), 0.0)                   # diffusion_utils.py:173-174
+
+
+@lru_cache(maxsize=64)
+def _schedule_coefs(kind, lmin, lmax):
+    """(a, b) of `Schedule`, formed in float64 and rounded to fp32; kept, because a train step asks for them at every launch."""
+    if kind == "cosine":
+        b = np.arctan(np.exp(-0.5 * lmax))
+        a = np.arctan(np.exp(-0.5 * lmin)) - b
+    elif kind in ("beta_const", "beta_linear"):
+        b = _softplus64(-lmax)
+        a = _softplus64(-lmin) - b
+    elif kind == "uniform":
+        a = b = 0.0
+    else:
+        raise ValueError(f"schedule kind {kind!r}: one of {', '.join(SCHEDULE_KINDS)}")
+    return np.float32(a), np.float32(b)
+
+
+class Schedule(namedtuple("Schedule", "kind logsnr_min logsnr_max shift", defaults=("cosine", -20.0, 20.0, 0.0))):
+    """One of the reference's closed-form log-SNR schedules u in [0, 1] -> logsnr (diffusion_utils.py:169-201; u = 0 is logsnr_max, u = 1
+    logsnr_min), plus an additive `shift` (Hoogeboom et al. 2023, "simple diffusion": 2 log(32 / d) for d x d images; an extension):
+      'cosine'       -2 log(tan(a u + b))        b = atan(exp(-logsnr_max / 2)), a = atan(exp(-logsnr_min / 2)) - b
+      'uniform'      logsnr_min u + logsnr_max (1 - u)
+      'beta_const'   -log(expm1(a u + b))        b = softplus(-logsnr_max),      a = softplus(-logsnr_min) - b
+      'beta_linear'  -log(expm1(a u^2 + b))      as beta_const
+    a, b are formed in float64 and rounded to fp32 (how torch applies a double scalar to an fp32 tensor); `host` is then one fp32 operation
+    after another, the arithmetic of gmk_q_sample_sched.  `Schedule()` is what `GaussianDiffusion` picks in the reference (:33-34) and what
+    `logsnr_schedule_cosine_host` / gmk_q_sample hold as constants.  The interpolated (table) schedules of the reference are not here."""
+    __slots__ = ()
+
+    @property
+    def a(self):
+        return _schedule_coefs(self.kind, float(self.logsnr_min), float(self.logsnr_max))[0]
+
+    @property
+    def b(self):
+        return _schedule_coefs(self.kind, float(self.logsnr_min), float(self.logsnr_max))[1]
+
+    @property
+    def full_range(self):
+        """Does the schedule run over exactly [-20, 20], the range the likelihood kernels hold as constants?"""
+        return float(self.shift) == 0.0 and float(self.logsnr_min) == VLB_LOGSNR_MIN and float(self.logsnr_max) == VLB_LOGSNR_MAX
+
+    def host(self, u):
+        """logsnr(u) for a host scalar (or array), all in fp32 -> np.float32."""
+        u = np.float32(u)
+        a, b = self.a, self.b
+        if self.kind == "cosine":
+            l = np.float32(-2.0) * np.log(np.tan(a * u + b, dtype=np.float32), dtype=np.float32)
+        elif self.kind == "uniform":
+            l = np.float32(self.logsnr_min) * u + np.float32(self.logsnr_max) * (np.float32(1.0) - u)
+        else:
+            t = a * (u * u if self.kind == "beta_linear" else u) + b
+            l = -np.log(np.expm1(t, dtype=np.float32), dtype=np.float32)
+        return l + np.float32(self.shift) if float(self.shift) != 0.0 else l
+
+
+def schedule_check(logsnr_schedule, logsnr_min, logsnr_max, logsnr_shift, sample_logsnr_schedule=""):
+    """The noise-schedule options: logsnr_schedule one of SCHEDULE_KINDS, -20 <= logsnr_min < logsnr_max <= 20, |logsnr_shift| <= 10, and
+    sample_logsnr_schedule the samplers' kind ('' or None: the training one; it shares the range and the shift).
+    -> (training Schedule, sampling Schedule), or ValueError naming the flag."""
+    if logsnr_schedule not in SCHEDULE_KINDS:
+        raise ValueError(f"logsnr_schedule = {logsnr_schedule!r}: one of {', '.join(SCHEDULE_KINDS)}")
+    sample_kind = logsnr_schedule if sample_logsnr_schedule in ("", None) else sample_logsnr_schedule
+    if sample_kind not in SCHEDULE_KINDS:
+        raise ValueError(f"sample_logsnr_schedule = {sample_logsnr_schedule!r}: '' (the training schedule) or one of {', '.join(SCHEDULE_KINDS)}")
+    nums = {}
+    for name, val in (("logsnr_min", logsnr_min), ("logsnr_max", logsnr_max), ("logsnr_shift", logsnr_shift)):
+        try:
+            nums[name] = float(val)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} = {val!r}: a finite number") from None
+        if isinstance(val, bool) or not math.isfinite(nums[name]):
+            raise ValueError(f"{name} = {val!r}: a finite number")
+    lmin, lmax, shift = nums["logsnr_min"], nums["logsnr_max"], nums["logsnr_shift"]
+    bound = SCHEDULE_LOGSNR_BOUND
+    rule = f"-{bound:g} <= logsnr_min < logsnr_max <= {bound:g}"
+    if not -bound <= lmin:
+        raise ValueError(f"logsnr_min = {lmin}: below -{bound:g} the cosine form loses its argument to fp32 rounding; {rule}")
+    if not lmax <= bound:
+        raise ValueError(f"logsnr_max = {lmax}: above {bound:g} the cosine form loses its argument to fp32 rounding; {rule}")
+    if not lmin < lmax:
+        raise ValueError(f"logsnr_min = {lmin}, logsnr_max = {lmax}: {rule}")
+    if abs(shift) > SCHEDULE_SHIFT_BOUND:
+        raise ValueError(f"logsnr_shift = {shift}: |logsnr_shift| <= {SCHEDULE_SHIFT_BOUND:g} (2 log(32 / d) is -1.386 at 64 x 64, -4.16 at 256 x 256)")
+    return Schedule(logsnr_schedule, lmin, lmax, shift), Schedule(sample_kind, lmin, lmax, shift)
+
+
+def _schedule_host(schedule):
+    """u -> fp32 logsnr on the host: `schedule.host`, or for None the function every default path has always called."""
+    return logsnr_schedule_cosine_host if schedule is None else schedule.host
+
+
+def sampler_grid(num_steps, schedule=None):
     """The samplers' time grid: one row (i, logsnr_t, logsnr_s) per loop iteration i = T-1 ... 0, fp32 host scalars.  The one place that forms
-    it; the update kernels, `dpm_solver_coefs` and `inpaint_coefs` all read these values."""
-    return [(i, *map(logsnr_schedule_cosine_host, sampler_times(i, num_steps))) for i in range(num_steps)[::-1]]
+    it; the update kernels, `dpm_solver_coefs` and `inpaint_coefs` all read these values.  schedule: the `Schedule` the samplers walk
+    (None: the reference's cosine on [-20, 20])."""
+    return [(i, *map(_schedule_host(schedule), sampler_times(i, num_steps))) for i in range(num_steps)[::-1]]
 
 
 DpmCoef = namedtuple("DpmCoef", "i lt ls h coef_z coef_x coef_prev")
@@ -89,7 +194,7 @@ def edit_start(strength, num_steps):
     return min(T, max(1, int(math.floor(s * T + 0.5))))
 
 
-def dpm_solver_coefs(num_steps, start=None):
+def dpm_solver_coefs(num_steps, start=None, schedule=None):
     """Per-step coefficients of sampler='dpmpp_2m' (DPM-Solver++(2M), Lu et al. 2022, Algorithm 2, data prediction; an extension with no
     reference call site), one row per loop iteration i = T-1 ... 0 on DDIM's time grid.  lt / ls are the fp32 log-SNRs the DDIM path uses;
     with lambda = logsnr / 2, alpha = sqrt(sigmoid(logsnr)), sigma = sqrt(sigmoid(-logsnr)) and h = lambda_s - lambda_t:
@@ -97,12 +202,12 @@ def dpm_solver_coefs(num_steps, start=None):
     so that z_s = coef_z z_t + coef_x ((1 + coef_prev) x_hat - coef_prev x_hat_prev).  coef_prev is 0 on the first step (first order: DDIM's
     update) and on the last (i == 0 returns x_hat itself, gaussian_diffusion.py:292), so T <= 2 is DDIM.  All in float64 from the fp32 log-SNRs.
     start = k (`sampler_start`) keeps the rows i = k-1 ... 0; the first of them has no history either, so its coef_prev is 0, and every later
-    row is the full list's."""
+    row is the full list's.  schedule: `sampler_grid`'s."""
     k_start = sampler_start(start, num_steps)
     sigma = lambda l: math.sqrt(1.0 / (1.0 + math.exp(l)))
     alpha = lambda l: math.sqrt(1.0 / (1.0 + math.exp(-l)))
     rows, h_prev = [], None
-    for i, lt, ls in sampler_grid(num_steps):
+    for i, lt, ls in sampler_grid(num_steps, schedule):
         lt, ls = float(lt), float(ls)
         h = 0.5 * (ls - lt)
         # a zero-length previous step (coincident fp32 log-SNRs, only at extreme T) leaves no slope to extrapolate: first order again
@@ -198,22 +303,24 @@ def time_importance_check(time_importance, importance_decay, importance_warmup, 
     return flags["time_importance"], decay, warmup, floor, flags["loss_profile"]
 
 
-def profile_bin_edges():
+def profile_bin_edges(schedule=None):
     """The 64 bins of the loss profile on the host: (u_lo, u_hi, logsnr_hi, logsnr_lo), fp32 [64] each - bin k is [k / 64, (k + 1) / 64) in u,
-    and its log-SNR range follows from the schedule (`logsnr_schedule_cosine_host`; the schedule falls, so u_lo carries the high end)."""
+    and its log-SNR range follows from the training schedule (a `Schedule`'s host, None: `logsnr_schedule_cosine_host`; the schedule falls, so
+    u_lo carries the high end)."""
     n = ops.PROFILE_BINS
     u_lo = np.arange(n, dtype=np.float32) / np.float32(n)
     u_hi = np.arange(1, n + 1, dtype=np.float32) / np.float32(n)
-    return u_lo, u_hi, logsnr_schedule_cosine_host(u_lo), logsnr_schedule_cosine_host(u_hi)
+    host = _schedule_host(schedule)
+    return u_lo, u_hi, host(u_lo), host(u_hi)
 
 
-def profile_rows(state, p=None):
-    """Host view of a profile state (fp32 [5, 64] array): dict of [64] arrays - u_lo, u_hi, logsnr_hi, logsnr_lo (`profile_bin_edges`), weight = W,
+def profile_rows(state, p=None, schedule=None):
+    """Host view of a profile state (fp32 [5, 64] array): dict of [64] arrays - u_lo, u_hi, logsnr_hi, logsnr_lo (`profile_bin_edges(schedule)`), weight = W,
     loss_mean = S1_0 / W, loss_rms = sqrt(S2_0 / W), x_mse_mean = S1_1 / W (NaN where W = 0), and p: the sampling probabilities given, or None."""
     s = np.asarray(state, dtype=np.float64)
     if s.shape != (5, ops.PROFILE_BINS):
         raise ValueError(f"profile state of shape {s.shape}, expected (5, {ops.PROFILE_BINS})")
-    u_lo, u_hi, l_hi, l_lo = profile_bin_edges()
+    u_lo, u_hi, l_hi, l_lo = profile_bin_edges(schedule)
     with np.errstate(divide="ignore", invalid="ignore"):
         W = s[0]
         rows = {"u_lo": u_lo, "u_hi": u_hi, "logsnr_hi": l_hi, "logsnr_lo": l_lo, "weight": W, "loss_mean": s[1] / W, "loss_rms": np.sqrt(s[2] / W),
@@ -244,17 +351,17 @@ def dyn_threshold_rank(p, n):
 InpaintCoef = namedtuple("InpaintCoef", "i lt ls alpha_s sigma_s a b is_last")
 
 
-def inpaint_coefs(num_steps):
+def inpaint_coefs(num_steps, schedule=None):
     """Per-step coefficients of `GaussianDiffusion.inpaint` (RePaint, Lugmayr et al. 2022, Algorithm 1), one row per loop iteration
     i = T-1 ... 0 on DDIM's time grid; lt / ls are the fp32 log-SNRs the sampler uses.  With alpha^2 = sigmoid(l), sigma^2 = sigmoid(-l):
       alpha_s, sigma_s  the known region's noisy copy alpha_s x0 + sigma_s eps at time s
       a, b              the forward transition q(z_t | z_s) = N(a z_s, b^2), a = alpha_t / alpha_s, b^2 = 1 - alpha_t^2 / alpha_s^2,
                         formed as b^2 = -expm1(lt - ls) sigma_t^2 (no cancellation), so that a^2 sigma_s^2 + b^2 = sigma_t^2
       is_last           i == 0: the known region is x0 itself and the step never re-noises.
-    All in float64 from the fp32 log-SNRs."""
+    All in float64 from the fp32 log-SNRs.  schedule: `sampler_grid`'s."""
     sig = lambda l: 1.0 / (1.0 + math.exp(-l))
     rows = []
-    for i, lt, ls in sampler_grid(num_steps):
+    for i, lt, ls in sampler_grid(num_steps, schedule):
         lt, ls = float(lt), float(ls)
         a = math.sqrt(sig(lt) / sig(ls))
         b = math.sqrt(-math.expm1(lt - ls) * sig(-lt))
@@ -300,17 +407,17 @@ def restore_operator(shape, factor=1, gray=False):
     return cf, N, (B, C // cf, H // N, W // N)
 
 
-def sampler_plan(num_steps, sampler="ddim", resample=None, start=None):
+def sampler_plan(num_steps, sampler="ddim", resample=None, start=None, schedule=None):
     """One row per sampler iteration i = T-1 ... 0: the grid's (i, lt, ls), is_last, the network evaluations of the step (`resample`: the
     inpainting loop's, None outside it) and the step's DpmCoef (sampler 'dpmpp_2m') / InpaintCoef (inpainting) rows, else None.  The loop
     reserves its Philox counters and every chunk spends them by walking the same plan.  start = k (`sampler_start`): a chain that begins
-    part-way, from z at plan[0].lt = logsnr(k / T) - the rows i = k-1 ... 0 of the same grid (None: all T of them)."""
+    part-way, from z at plan[0].lt = logsnr(k / T) - the rows i = k-1 ... 0 of the same grid (None: all T of them).  schedule: `sampler_grid`'s."""
     k = sampler_start(start, num_steps)
     skip = num_steps - k
-    dpm = dpm_solver_coefs(num_steps, start) if sampler == "dpmpp_2m" else [None] * k
-    inp = inpaint_coefs(num_steps)[skip:] if resample is not None else [None] * k
+    dpm = dpm_solver_coefs(num_steps, start, schedule) if sampler == "dpmpp_2m" else [None] * k
+    inp = inpaint_coefs(num_steps, schedule)[skip:] if resample is not None else [None] * k
     return [SamplerStep(i, lt, ls, i == 0, 1 if resample is None else inpaint_passes(i, resample), d, c)
-            for (i, lt, ls), d, c in zip(sampler_grid(num_steps)[skip:], dpm, inp)]
+            for (i, lt, ls), d, c in zip(sampler_grid(num_steps, schedule)[skip:], dpm, inp)]
 
 
 # the variational bound's log-SNR range: the schedule's truncation (diffusion_utils.py:199-200)
@@ -326,11 +433,12 @@ def stratified_logsnr(u0, K):
     return (VLB_LOGSNR_MAX - (VLB_LOGSNR_MAX - VLB_LOGSNR_MIN) * frac).float()
 
 
-def ode_logsnr_grid(num_steps):
-    """The probability-flow ODE's time grid, the samplers' own: lambda_i = logsnr_schedule_cosine(i / N) in fp32 for i = 0 ... N (lambda_0 = 20,
-    the data end; lambda_N = -20, the prior end), as Python floats."""
+def ode_logsnr_grid(num_steps, schedule=None):
+    """The probability-flow ODE's time grid, the samplers' own: lambda_i = schedule(i / N) in fp32 for i = 0 ... N (lambda_0 = 20, the data end;
+    lambda_N = -20, the prior end, under the default schedule, None: the reference's cosine on [-20, 20]), as Python floats."""
     N = int(num_steps)
-    return [float(logsnr_schedule_cosine_host(np.float32(np.float32(i) / np.float32(N)))) for i in range(N + 1)]
+    host = _schedule_host(schedule)
+    return [float(host(np.float32(np.float32(i) / np.float32(N)))) for i in range(N + 1)]
 
 
 def ode_trapezoid_weights(lam):
@@ -474,9 +582,20 @@ class _XLossW(torch.autograd.Function):
 class GaussianDiffusion:
     def __init__(self, *, mean_type, num_steps, teacher_net=None, teacher_mode=None, sampler="ddim", sample_cond_w=None,
                  seed=0, dyn_threshold=0.0, loss_weight="snr_trunc", loss_gamma=5.0, time_sampler="uniform", time_importance=0,
-                 importance_decay=0.9, importance_warmup=5, importance_floor=0.01, loss_profile=0):
+                 importance_decay=0.9, importance_warmup=5, importance_floor=0.01, loss_profile=0, schedule=None, sample_schedule=None):
         if mean_type not in ops.MEAN_TYPES:                     # :70-71
             raise NotImplementedError(mean_type)
+        # the noise schedule (`Schedule`; the reference's registry, diffusion_utils.py:228-239, of which it picks 'cosine', -20, 20 at :33-34):
+        # `schedule` maps the training times to log-SNRs (q_sample, the distillation targets, the loss profile's bin edges), `sample_schedule`
+        # is the curve every sampler, edit, restore and the ODE walk (None: the training one) - the network is conditioned on the log-SNR
+        # itself, so the two may differ.  None is that pick through the entries that hold it as constants: the same launches as ever.
+        for name, s in (("schedule", schedule), ("sample_schedule", sample_schedule)):
+            if s is not None and not isinstance(s, Schedule):
+                raise ValueError(f"{name} = {s!r}: None or a Schedule")
+            if s is not None:
+                schedule_check(s.kind, s.logsnr_min, s.logsnr_max, s.shift)
+        self.schedule = schedule
+        self.sample_schedule = schedule if sample_schedule is None else sample_schedule
         # dynamic thresholding of the samplers' x-hat (Saharia et al. 2022, section 2.3; an extension, no reference call site): 0 is off (the
         # reference's static clip, the same launches as ever), else each image's x-hat is the unclipped (guided) prediction clamped to its own
         # p-th percentile s of |x| (s >= 1) and divided by s.  sample() and inpaint() only: the ODE is unclipped by definition and the
@@ -601,7 +720,7 @@ class GaussianDiffusion:
         p = None
         if split == "train" and self.time_importance:
             p = ops.u_importance(t, torch.zeros((1,), device=t.device), self.importance_warmup, self.importance_floor, want_table=True)[2].cpu().numpy()
-        rows = profile_rows(t.cpu().numpy(), p)
+        rows = profile_rows(t.cpu().numpy(), p, self.schedule)
         if reset:
             t.zero_()
         return rows
@@ -620,25 +739,25 @@ class GaussianDiffusion:
             if i_times is None:
                 i_times = (self.rng.uniform((B,), dev) * self.num_steps).long().clamp_(max=self.num_steps - 1)
             i_times = ops.aligned(i_times.long())
-            _, u = ops.logsnr_schedule(B, dev, i_times=i_times, num_steps=self.num_steps, want_u=True)
+            _, u = ops.logsnr_schedule(B, dev, i_times=i_times, num_steps=self.num_steps, want_u=True, schedule=self.schedule)
         else:
             if u is None:
                 u = self.draw_u(B, dev)                                           # :94 continuous time
             u = ops.aligned(u.float())
-        logsnr, z_t = ops.q_sample(x, eps, u)                                     # :95-100
+        logsnr, z_t = ops.q_sample(x, eps, u, self.schedule)                      # :95-100
         if not distill:
             return module, guide, None, z_t, logsnr, x, eps, 1 if self.loss_weight_type == "snr" else 0
         if cond_w is None:
             cond_w = 4.0 * self.rng.uniform((B,), dev)                            # :107
         cond_w = ops.aligned(cond_w.float())
         with torch.no_grad():
-            logsnr_s = ops.logsnr_schedule(B, dev, u=u, shift=1.0 / self.num_steps)           # :118-119
+            logsnr_s = ops.logsnr_schedule(B, dev, u=u, shift=1.0 / self.num_steps, schedule=self.schedule)      # :118-119
             if self.teacher_mode == "step1":                                      # :121-126 one guided teacher step
                 v, vu = self._teacher_eval(z_t, logsnr, guide, None, guided=True)
                 _, x_target, eps_target = ops.ddim_step_vec(v, z_t, logsnr, logsnr_s, v_uncond=vu, cond_w=cond_w, mean_type=self.mean_type)
                 loss_type = 1
             else:                                                                 # :128-154 two w-conditioned teacher steps
-                logsnr_mid = ops.logsnr_schedule(B, dev, u=u, shift=0.5 / self.num_steps)
+                logsnr_mid = ops.logsnr_schedule(B, dev, u=u, shift=0.5 / self.num_steps, schedule=self.schedule)
                 v1, _ = self._teacher_eval(z_t, logsnr, guide, cond_w, guided=False)
                 z_mid, _, _ = ops.ddim_step_vec(v1, z_t, logsnr, logsnr_mid, mean_type=self.mean_type)
                 v2, _ = self._teacher_eval(z_mid, logsnr_mid, guide, cond_w, guided=False)
@@ -714,10 +833,20 @@ class GaussianDiffusion:
         return out
 
     # ---- likelihood: the continuous-time variational bound (an extension, no reference call site) ------------------------------------------
+    @staticmethod
+    def _full_range(what, schedule):
+        """`nll` and `ode_nll` integrate between the schedule's end points, which gmk_vlb_endpoints (and the ODE's standard-normal prior) hold
+        as -20 and 20: any kind of schedule over exactly that range passes, another range or a shift raises."""
+        if schedule is not None and not schedule.full_range:
+            raise ValueError(f"{what}: the likelihood is integrated over logsnr in [{VLB_LOGSNR_MIN:g}, {VLB_LOGSNR_MAX:g}], this schedule has logsnr_min = "
+                             f"{schedule.logsnr_min:g}, logsnr_max = {schedule.logsnr_max:g}, logsnr_shift = {schedule.shift:g}: leave them at "
+                             f"{VLB_LOGSNR_MIN:g}, {VLB_LOGSNR_MAX:g}, 0 (a likelihood over another range is not implemented)")
+
     @torch.no_grad()
     def nll(self, *, net, x, num_samples, seed=0, delta=1.0 / 255):
-        """Per-image variational bound on -log p(x) of Kingma et al. 2021 (VDM) for this schedule (cosine log-SNR truncated to [-20, 20]), in nats
-        per dimension.  x [B, C, H, W], D = C H W, lambda = logsnr, alpha^2 = sigmoid(lambda), sigma^2 = sigmoid(-lambda), Delta = 40:
+        """Per-image variational bound on -log p(x) of Kingma et al. 2021 (VDM) for a schedule over [-20, 20] (any kind: the bound is an integral over
+        the log-SNR; another logsnr_min / logsnr_max / logsnr_shift raises, `_full_range`), in nats per dimension.
+        x [B, C, H, W], D = C H W, lambda = logsnr, alpha^2 = sigmoid(lambda), sigma^2 = sigmoid(-lambda), Delta = 40:
           diffusion  1/2 int_{-20}^{20} E_eps |eps - eps_hat(z_lambda, lambda)|^2 d lambda  (VDM eq. 17 with lambda as the variable), estimated with
                      K = num_samples stratified draws per image, lambda_{b,k} = 20 - Delta frac(u0_b + k / K): mean_k 1/2 Delta |eps_k - eps_hat_k|^2
           prior      sum_i KL(N(alpha_1 x_i, sigma_1^2) || N(0, 1)) at lambda = -20
@@ -732,6 +861,7 @@ class GaussianDiffusion:
         module, guide, kw_cond_w = _unwrap(net)
         if self.teacher_net is not None or kw_cond_w is not None:
             raise ValueError("nll: a distilled student is conditioned on cond_w; its variational bound is not defined")
+        self._full_range("nll", self.schedule)
         K = int(num_samples)
         if K < 1:
             raise ValueError(f"nll: num_samples = {num_samples}, need at least 1")
@@ -775,7 +905,7 @@ class GaussianDiffusion:
             raise ValueError(f"{what}: num_steps = {num_steps}, need an integer >= 1")
         if x.dim() != 4 or x.shape[0] == 0 or x.shape[1] != getattr(module, "in_channels", x.shape[1]):
             raise ValueError(f"{what}: x has shape {tuple(x.shape)}, expected [B, {getattr(module, 'in_channels', 'C')}, H, W] with B > 0")
-        lam = ode_logsnr_grid(N)
+        lam = ode_logsnr_grid(N, self.sample_schedule)
         B = x.shape[0]
         times = torch.tensor(lam, dtype=torch.float32)[:, None].expand(len(lam), (B + 3) // 4 * 4).contiguous().to(x.device)
         return module, guide, N, lam, times[:, :B]
@@ -826,6 +956,7 @@ class GaussianDiffusion:
         evaluation (ode_draw_counters).  Runs without dropout.
         -> dict of fp32 [B]: nlogp = -log p(y) / D - log(2 delta) (by Jensen an upper bound on -log P(x's bin) / D, up to the estimator's
         noise), prior = -log N(z_N; 0, I) / D, divergence = the trapezoid sum / D."""
+        self._full_range("ode_nll", self.sample_schedule)
         module, guide, N, lam, times = self._ode_setup("ode_nll", net, x, num_steps)
         delta = float(delta)
         if not 0.0 < delta <= 0.5:
@@ -955,7 +1086,7 @@ class GaussianDiffusion:
         x = ops.aligned(x.float())
         rng = PhiloxStream(seed)
         eps = rng.normal(shape, dev)
-        lt_k = logsnr_schedule_cosine_host(sampler_times(k - 1, self.num_steps)[0])      # the grid's logsnr_t of iteration k-1
+        lt_k = _schedule_host(self.sample_schedule)(sampler_times(k - 1, self.num_steps)[0])      # the grid's logsnr_t of iteration k-1
         z_k = ops.q_sample_logsnr(x, eps, torch.full((shape[0],), float(lt_k), device=dev))
         inp = None if m is None else InpaintState(x, m, rng, 1, shape[0], [])
         return self._sample(net=net, init_x=z_k, cond_w=cond_w, record=record, inp=inp, start=k)
@@ -1026,7 +1157,7 @@ class GaussianDiffusion:
             not self._graph_path(module, nb_half, init_x.shape[2], init_x.shape[3])
         K = 2 if two else 1
         cut = lambda t, a, b_: None if t is None else ops.aligned(t[a:b_])
-        plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample, start)
+        plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample, start, self.sample_schedule)
         # Philox counter of each network evaluation's noise draw for the WHOLE batch (ancestral sampler), and (inp.moffs) of each inpainting
         # merge's known-region draws: chunks take their slice of them
         offs = []

@@ -3,6 +3,7 @@
 Every wrapper checks shapes/dtypes/contiguity on the host before launching (a kernel fault on this hardware can
 take the whole node down) and enqueues on torch's current HIP stream.
 """
+import functools
 import math
 
 import os
@@ -885,14 +886,33 @@ def rng_uniform(shape, seed, offset, device):
     return out
 
 
-def q_sample(x, eps, u):
+SCHEDULES = {"cosine": C["GMK_SCHED_COSINE"], "uniform": C["GMK_SCHED_UNIFORM"], "beta_const": C["GMK_SCHED_BETA_CONST"],
+             "beta_linear": C["GMK_SCHED_BETA_LINEAR"]}       # the closed-form log-SNR schedules (diffusion_utils.py:169-201)
+
+
+@functools.lru_cache(maxsize=64)
+def _sched_args(schedule):
+    """The (kind, a, b, lmin, lmax, shift) arguments of the gmk_*_sched entries from a `gaussian_diffusion.Schedule` (its kind, the fp32
+    coefficients a, b it derived, its range and shift); kept per schedule (an immutable tuple): this sits on every training launch's path."""
+    if schedule.kind not in SCHEDULES:
+        raise ValueError(f"schedule kind {schedule.kind!r}: one of {', '.join(SCHEDULES)}")
+    return (SCHEDULES[schedule.kind], float(schedule.a), float(schedule.b), float(schedule.logsnr_min), float(schedule.logsnr_max),
+            float(schedule.shift))
+
+
+def q_sample(x, eps, u, schedule=None):
+    """-> (logsnr, z): logsnr = schedule(u), z = alpha x + sigma eps.  schedule: a `gaussian_diffusion.Schedule` (gmk_q_sample_sched, any
+    image size), None: the reference's cosine schedule on [-20, 20] (gmk_q_sample, as ever)."""
     _f32(x, "x"); _f32(eps, "eps"); _f32(u, "u")
     B = x.shape[0]
     n = x.numel() // B
     assert eps.shape == x.shape and u.numel() == B
     logsnr = torch.empty((B,), device=x.device, dtype=torch.float32)
     z = torch.empty_like(x)
-    check(lib.gmk_q_sample(_p(x), _p(eps), _p(u), _p(logsnr), _p(z), B, n, _s()), "q_sample")
+    if schedule is None:
+        check(lib.gmk_q_sample(_p(x), _p(eps), _p(u), _p(logsnr), _p(z), B, n, _s()), "q_sample")
+    else:
+        check(lib.gmk_q_sample_sched(_p(x), _p(eps), _p(u), _p(logsnr), _p(z), B, n, *_sched_args(schedule), _s()), "q_sample_sched")
     return logsnr, z
 
 
@@ -1346,16 +1366,23 @@ def slerp(a, b, t, want_cos=False):
     return (out, cos) if want_cos else out
 
 
-def logsnr_schedule(B, device, u=None, i_times=None, num_steps=1, shift=0.0, want_u=False):
-    """logsnr = schedule(u - shift), u given or (i_times + 1) / num_steps.  -> logsnr (, u_shifted)"""
+def logsnr_schedule(B, device, u=None, i_times=None, num_steps=1, shift=0.0, want_u=False, schedule=None):
+    """logsnr = schedule(u - shift), u given or (i_times + 1) / num_steps.  schedule: as in `q_sample` (`shift` here moves u, the schedule's
+    own shift the log-SNR).  -> logsnr (, u_shifted)"""
     if u is not None:
         _f32(u, "u")
+        assert u.numel() == B
     if i_times is not None:
         _chk(i_times, torch.int64, "i_times")
+        assert i_times.numel() == B
     logsnr = torch.empty((B,), device=device, dtype=torch.float32)
     uo = torch.empty((B,), device=device, dtype=torch.float32) if want_u else None
-    check(lib.gmk_logsnr_schedule(_p(u), _p(i_times), int(num_steps), float(shift), _p(uo), _p(logsnr), B, _s()),
-          "logsnr_schedule")
+    if schedule is None:
+        check(lib.gmk_logsnr_schedule(_p(u), _p(i_times), int(num_steps), float(shift), _p(uo), _p(logsnr), B, _s()),
+              "logsnr_schedule")
+    else:
+        check(lib.gmk_logsnr_schedule_sched(_p(u), _p(i_times), int(num_steps), float(shift), *_sched_args(schedule), _p(uo), _p(logsnr), B,
+                                            _s()), "logsnr_schedule_sched")
     return (logsnr, uo) if want_u else logsnr
 
 

@@ -368,6 +368,21 @@ int gmk_rng_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, void*
  * (gaussian_diffusion.py:95-100, diffusion_utils.py:65-73) */
 int gmk_q_sample(const float* x, const float* eps, const float* u, float* logsnr, float* z, int B, int64_t n,
                  void* stream);
+/* gmk_q_sample under any of the reference's closed-form log-SNR schedules (diffusion_utils.py:169-201; its GaussianDiffusion picks
+ * 'cosine', -20, 20, gaussian_diffusion.py:33-34, which gmk_q_sample holds as constants), logsnr(u) =
+ *   GMK_SCHED_COSINE       -2 log(tan(a u + b))       b = atan(exp(-lmax / 2)), a = atan(exp(-lmin / 2)) - b
+ *   GMK_SCHED_UNIFORM      lmin u + lmax (1 - u)      (the only kind that reads lmin / lmax; the others take their range through a, b)
+ *   GMK_SCHED_BETA_CONST   -log(expm1(a u + b))       b = softplus(-lmax), a = softplus(-lmin) - b
+ *   GMK_SCHED_BETA_LINEAR  -log(expm1(a u^2 + b))     as beta_const
+ * then + shift unless shift == 0 (an additive log-SNR shift, Hoogeboom et al. 2023; no reference call site).  a, b: float64 on the host,
+ * rounded to fp32; every operation on the device is one fp32 operation in the reference's order.  With (GMK_SCHED_COSINE, the two
+ * constants, shift 0) the bits of gmk_q_sample.  Any n > 0 (gmk_q_sample asks n % 4 == 0).  An unknown kind is GMK_ERR_ARG. */
+#define GMK_SCHED_COSINE 0
+#define GMK_SCHED_UNIFORM 1
+#define GMK_SCHED_BETA_CONST 2
+#define GMK_SCHED_BETA_LINEAR 3
+int gmk_q_sample_sched(const float* x, const float* eps, const float* u, float* logsnr, float* z, int B, int64_t n, int kind, float a,
+                       float b, float lmin, float lmax, float shift, void* stream);
 /* gaussian_diffusion.py:58-77,165-169 and their backward in one pass over each sample:
  * x_hat = clip(x_from_output(v)); eps_hat = eps_from_x; loss_b = max(mean (x_hat-x)^2, mean (eps_hat-eps)^2);
  * dv (optional) = d(grad_scale * sum_b loss_b)/dv.  loss_b/x_mse/eps_mse: fp32 [B].
@@ -586,6 +601,9 @@ int gmk_softmax_bwd(const void* P, const float* dP, void* dS, int64_t rows, int 
  * u_out (optional) receives the shifted u */
 int gmk_logsnr_schedule(const float* u, const int64_t* i_times, int num_steps, float shift, float* u_out, float* logsnr,
                         int B, void* stream);
+/* the same under a schedule of gmk_q_sample_sched (diffusion_utils.py:169-201): logsnr[b] = schedule(u[b] - u_shift) + shift */
+int gmk_logsnr_schedule_sched(const float* u, const int64_t* i_times, int num_steps, float u_shift, int kind, float a, float b, float lmin,
+                              float lmax, float shift, float* u_out, float* logsnr, int B, void* stream);
 /* one DDIM step with per-sample times logsnr_t[b] -> logsnr_s[b] (teacher steps inside the loss, :116,:129-144) */
 int gmk_ddim_step_vec(const float* v, const float* v_uncond, const float* cond_w, const float* z, const float* logsnr_t,
                       const float* logsnr_s, float* z_next, float* x_pred, float* eps_pred, int mean_type, int B, int64_t n,
