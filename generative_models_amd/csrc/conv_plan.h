@@ -97,3 +97,17 @@ int gmk_wgrad_subpixel_plan(int B, int H, int W, int cin, int cout, int dy_cstri
 int gmk_conv1x1_pair_stream_try(const void* src, int64_t npix, const void* w_rows256, void* out_a, void* out_b, int dtype, void* stream);      // 1 if launched
 int gmk_conv1x1_wgrad_stream_try(const void* dy, int dy_cstride, const void* src0, const void* src1, int64_t npix, float* slab, int64_t slab_bytes,
                                  bool x_f16, void* stream);        // > 0 = slabs written
+
+// ---- the stem / head kernels (smallconv.hip) ------------------------------------------------------------------------------------------------
+// One launch of the six entry points: the kernel id, its geometry, and the scalars that kernel takes (the others stay 0).  cs: image channels.
+struct SmallPlan {
+    int kernel, launches;              // launches: cs for the VALU weight gradient (one per image channel), else 1
+    unsigned grid, block, lds;
+    int ppb, tps, band, nbands, rows;  // rows: the weight gradients' partial rows (= grid = gmk_stem_wgrad_blocks / gmk_head_wgrad_blocks)
+    unsigned nblocks, ntiles, ppw;
+};
+// variant: GMK_DEV_VARIANT (41 keeps the VALU kernels, 42 the exact-fp32 chains); each returns 0 for a shape the entry points refuse
+int gmk_expand_plan(int B, int cs, int H, int W, int C, int dtype, int variant, int cu_limit, SmallPlan* p);      // gmk_stem_fwd, gmk_head_dgrad
+int gmk_wgrad3_plan(int B, int cs, int H, int W, int C, int dtype, int variant, int cu_limit, SmallPlan* p);      // gmk_stem_wgrad, gmk_head_wgrad
+// gmk_head_fwd (stem_dgrad = false), gmk_stem_dgrad: the kernel ids differ.  band < 1 (kernel 0): the image is too wide for the VALU kernel's LDS
+int gmk_head_plan(int B, int cs, int H, int W, int C, int dtype, int variant, int cu_limit, bool stem_dgrad, SmallPlan* p);

@@ -51,6 +51,10 @@ template <typename T> constexpr int gmk_dtype_of = std::is_same<T, float>::value
 template <typename... Ts, typename F> static inline bool gmk_with_type(int dtype, F&& f) {
     return ((dtype == gmk_dtype_of<Ts> ? (f(gmk_tag<Ts>{}), true) : false) || ...);
 }
+// The same for a small integer template parameter: calls f(std::integral_constant<int, N>{}) for the N among Ns that equals n
+template <int... Ns, typename F> static inline bool gmk_with_count(int n, F&& f) {
+    return ((n == Ns ? (f(std::integral_constant<int, Ns>{}), true) : false) || ...);
+}
 
 // ---- device helpers ---------------------------------------------------------------------------
 template <typename T> struct Vec8;   // 8 activation elements as the natural 16/32-byte vector

@@ -1,18 +1,27 @@
 // Stem (C_in <= 4 -> C) and head (C -> C_out <= 4) 3x3 convolutions with their backward passes.
 // Reference: gms/diffusion/simple_unet.py:92-94 (Downsample(1, channels, 1)) and :41 (Conv2d(channels, 1, 3, padding=1)).
-// Degenerate GEMM shapes (K = 9 or N = 1): HBM-bound streaming kernels, no MFMA.  Image-side tensors are NCHW
-// fp32 as the reference passes them; the network side is NHWC in `dtype`.
-//
-// All five kernels move the C-channel tensor exactly once (16 B per lane, a wave covers whole 256-B pixel rows) and
-// take the 1-channel image through L1/L2; a thread is (8-channel vector, pixel lane) and walks the flat pixel range of
-// its block with 32-bit counters (one division per thread, then increments — per-pixel 64-bit div/mod had made the
-// first version of these kernels 5x slower than their HBM time).  A thread's weights / accumulators for ALL image channels live in
-// registers: 8 network channels per thread for 1-2 image channels, 4 for 3-4 (CIFAR-shape configs).
+// Degenerate GEMM shapes (K = 9 x image channels, or N = image channels).  Image-side tensors are NCHW fp32 as the reference passes
+// them; the network side is NHWC in `dtype`.  Three operations, six entry points, ten kernels:
+//   expand (image -> C): gmk_stem_fwd, gmk_head_dgrad      expand3x3_kernel, expand3x3_mfma_kernel, expand3x3_tile16_kernel
+//   weight gradient:     gmk_stem_wgrad, gmk_head_wgrad    wgrad3x3_kernel, wgrad3x3_mfma_kernel, wgrad3x3_tile16_kernel
+//   contract (C -> image): gmk_head_fwd, gmk_stem_dgrad    head_fwd_kernel, stem_dgrad_kernel, head_fwd_mfma_kernel, stem_dgrad_mfma_kernel
+// The four VALU kernels (the first of each group) take every shape: C = 128 or 256, 1 - 4 image channels, any storage type.  They move the
+// C-channel tensor exactly once (16 B per lane, a wave covers whole 256-B pixel rows) and take the image through L1/L2; a thread is
+// (channel vector, pixel lane) and walks the flat pixel range of its block with 32-bit counters (one division per thread, then increments
+// - per-pixel 64-bit div/mod had made the first version of these kernels 5x slower than their HBM time).  A thread's weights /
+// accumulators for ALL image channels live in registers: 8 network channels per thread for 1-2 image channels, 4 for 3-4 (CIFAR-shape
+// configs).  The six matrix-core kernels serve C = 128 with up to 3 image channels (the fp32 expand chain: 4): *_mfma_kernel of the
+// expand and weight-gradient groups are exact fp32 chains for every storage type, *_tile16_kernel their tiled forms for 16-bit tensors
+// and rows of up to 128 pixels, and the contraction's matrix-core pair takes 16-bit activations.  Which call gets which, and with what
+// grid, is decided once by the planners below the kernels (declared in conv_plan.h) and only executed by the launchers.
+#include "conv_plan.h"
 #include "gmk_common.h"
 
 namespace {
 
 constexpr int kMaxSmall = 4;   // max image channels handled (1 in the reference, 3 for the CIFAR-shape configs)
+// A buffer addressed with 32-bit byte offsets ends below this: the kernels (each restates it) turn a masked lane's offset into it, which the buffer bounds check drops
+constexpr unsigned kBadOff = 0xFFFFFF00u;
 
 __device__ __forceinline__ int div_small(int a, float inv) { return (int)(((float)a + 0.5f) * inv); }
 
@@ -868,236 +877,224 @@ __global__ __launch_bounds__(512) void stem_dgrad_mfma_kernel(const T* __restric
     head_fwd_mfma_body<T, true>(dy, w, nullptr, dx, cs, H, W, band, nbands, dy_bytes, tapl);
 }
 
-int small_ppb(int64_t npix) {          // pixels per workgroup of the streaming kernels
-    return npix > 4096 * 256 ? 1024 : 512;
+// ---- the planners (conv_plan.h): plain arithmetic, no pointer, nothing launched ----------------------------------------------------------
+constexpr int kVariantValu = 41, kVariantFp32Chain = 42;      // GMK_DEV_VARIANT: keep the VALU kernels / keep the exact-fp32 chains (A/B)
+// LDS of a contraction workgroup: 9 fp32 planes per image channel of (band + 2) rows.  Matrix-core kernel: all cs channels in <= 124 KiB;
+// VALU kernel: one channel at a time in 48 KiB
+constexpr size_t kMfmaBandLds = 126976, kValuBandLds = 49152;
+
+int small_ppb(int64_t npix) { return npix > 4096 * 256 ? 1024 : 512; }      // pixels per workgroup of the streaming kernels
+
+// rows of the weight-gradient partials: one per workgroup of the matrix-core kernels, whose grid is the resident set (2 per CU);
+// the VALU kernel accepts any row count (its pixels per workgroup follow from it)
+int wgrad_rows(int64_t npix, int cu_limit) {
+    const int ppb = small_ppb(npix), nb = (int)((npix + ppb - 1) / ppb);
+    return nb < 2 * cu_limit ? nb : 2 * cu_limit;
 }
 
-int small_blocks(int64_t npix) {
-    const int ppb = small_ppb(npix);
-    return (int)((npix + ppb - 1) / ppb);
-}
-
-// rows of the weight-gradient partials: one per workgroup of the matrix-core kernel, whose grid is the resident set (2 per CU);
-// the VALU kernels accept any row count (their pixels per workgroup follow from it)
-int wgrad_rows(int64_t npix) {
-    const int nb = small_blocks(npix), resident = 2 * gmk_cu_limit();
-    return nb < resident ? nb : resident;
-}
-
-bool small_shape_ok(int B, int cs, int H, int W, int C) {
+// what every entry point accepts; *p starts as no kernel, one launch, no grid, 256 threads, every scalar 0
+bool small_plan_begin(int B, int cs, int H, int W, int C, SmallPlan* p) {
+    *p = SmallPlan{0, 1, 0, 256};
     return B > 0 && cs >= 1 && cs <= kMaxSmall && H > 0 && W > 0 && (C == 128 || C == 256) && (int64_t)B * H * W < (1ll << 24) &&
            H * W >= 32;
 }
 
 }  // namespace
 
-extern "C" int gmk_stem_wgrad_blocks(int64_t n_pixels) { return wgrad_rows(n_pixels); }
-extern "C" int gmk_head_wgrad_blocks(int64_t n_pixels) { return wgrad_rows(n_pixels); }
-
-template <typename T, bool FLIP>
-static void launch_expand(const float* in, const float* w, const float* bias, T* out, int B, int cs, int H, int W, int C,
-                          hipStream_t stream) {
+int gmk_expand_plan(int B, int cs, int H, int W, int C, int dtype, int variant, int cu_limit, SmallPlan* p) {
+    if (!small_plan_begin(B, cs, H, W, C, p)) return 0;
     const int64_t npix = (int64_t)B * H * W;
-    const int ppb = small_ppb(npix), nb = small_blocks(npix);
-    const float inv_w = 1.0f / (float)W;
-    // the matrix-core form (exact fp32, bit-identical sums) for 128-channel nets; GMK_DEV_VARIANT 41 keeps the VALU kernel (A/B)
-    const size_t in_bytes = (size_t)npix * cs * 4, out_bytes = (size_t)npix * C * sizeof(T);
-    if (C == 128 && out_bytes < 0xFFFFFF00ull && gmk_kernel_choice(3, "GMK_DEV_VARIANT") != 41) {
-        const unsigned nblocks = (unsigned)((npix + 31) / 32);
-        // persistent: exactly the resident set (2 workgroups per CU at <= 256 registers), so the per-wave operand setup runs once
-        const unsigned resident = 2u * (unsigned)gmk_cu_limit();
-        const unsigned grid = (nblocks + 3) / 4 < resident ? (nblocks + 3) / 4 : resident;
-        if constexpr (sizeof(T) == 2) {          // 16-bit results: tiles with the image window in LDS and bf16 hi / lo operands (GMK_DEV_VARIANT 42 keeps the exact-fp32 chain: A/B)
-            if (W <= 128 && cs <= 3 && gmk_kernel_choice(3, "GMK_DEV_VARIANT") != 42) {
-                const int tps = (H * W + 127) / 128;
-                const unsigned ntiles = (unsigned)B * (unsigned)tps;
-                const unsigned grid16 = ntiles < resident ? ntiles : resident;
-                gmk_note_kernel(GMK_K_EXPAND_TILE16);
-#define GMK_EXPAND_T16(CSN) expand3x3_tile16_kernel<T, CSN, FLIP><<<grid16, 256, 0, stream>>>(in, w, bias, out, H, W, C, tps, ntiles, (unsigned)in_bytes, (unsigned)out_bytes)
-                if (cs == 1) GMK_EXPAND_T16(1);
-                else if (cs == 2) GMK_EXPAND_T16(2);
-                else GMK_EXPAND_T16(3);
-#undef GMK_EXPAND_T16
-                return;
-            }
+    // persistent matrix-core grids: exactly the resident set (2 workgroups per CU at <= 256 registers), so the per-wave operand setup runs once
+    const unsigned resident = 2u * (unsigned)cu_limit;
+    if (C == 128 && (size_t)npix * C * gmk_esize(dtype) < kBadOff && variant != kVariantValu) {
+        // 16-bit results: tiles with the image window in LDS and bf16 hi / lo operands; else the exact fp32 chain (bit-identical sums)
+        if (gmk_is16(dtype) && W <= 128 && cs <= 3 && variant != kVariantFp32Chain) {
+            p->kernel = GMK_K_EXPAND_TILE16;
+            p->tps = (H * W + 127) / 128;
+            p->ntiles = (unsigned)B * (unsigned)p->tps;
+            p->grid = p->ntiles < resident ? p->ntiles : resident;
+        } else {
+            p->kernel = GMK_K_EXPAND_MFMA;
+            p->nblocks = (unsigned)((npix + 31) / 32);
+            p->grid = (p->nblocks + 3) / 4 < resident ? (p->nblocks + 3) / 4 : resident;
         }
-        gmk_note_kernel(GMK_K_EXPAND_MFMA);
-#define GMK_EXPAND_M(CSN) expand3x3_mfma_kernel<T, CSN, FLIP><<<grid, 256, 0, stream>>>(in, w, bias, out, H, W, C, (unsigned)npix, nblocks, (unsigned)in_bytes, (unsigned)out_bytes)
-        if (cs == 1) GMK_EXPAND_M(1);
-        else if (cs == 2) GMK_EXPAND_M(2);
-        else if (cs == 3) GMK_EXPAND_M(3);
-        else GMK_EXPAND_M(4);
-#undef GMK_EXPAND_M
-        return;
-    }
-    gmk_note_kernel(GMK_K_EXPAND);
-#define GMK_EXPAND(CSN, VW) expand3x3_kernel<T, CSN, VW, FLIP><<<nb, 256, 0, stream>>>(in, w, bias, out, H, W, C, inv_w, (unsigned)npix, ppb)
-    if (cs == 1) GMK_EXPAND(1, 8);
-    else if (cs == 2) GMK_EXPAND(2, 8);
-    else if (cs == 3) GMK_EXPAND(3, 4);
-    else GMK_EXPAND(4, 4);
-#undef GMK_EXPAND
-}
-
-extern "C" int gmk_stem_fwd(const float* x, const float* w, const float* bias, void* y, int B, int cin, int H, int W, int C,
-                            int dtype, void* stream) {
-    GMK_REQUIRE(x && w && bias && y, "gmk_stem_fwd: null pointer");
-    GMK_REQUIRE(small_shape_ok(B, cin, H, W, C), "gmk_stem_fwd: unsupported shape B=%d cin=%d %dx%d C=%d", B, cin, H, W, C);
-    if (dtype == GMK_BF16) launch_expand<bf16_t, false>(x, w, bias, (bf16_t*)y, B, cin, H, W, C, gmk_stream(stream));
-    else if (dtype == GMK_F16) launch_expand<f16_t, false>(x, w, bias, (f16_t*)y, B, cin, H, W, C, gmk_stream(stream));
-    else if (dtype == GMK_F32) launch_expand<float, false>(x, w, bias, (float*)y, B, cin, H, W, C, gmk_stream(stream));
-    else GMK_REQUIRE(false, "gmk_stem_fwd: bad dtype %d", dtype);
-    return gmk_check_launch("gmk_stem_fwd");
-}
-
-extern "C" int gmk_head_dgrad(const float* dout, const float* w, void* da, int B, int cout, int H, int W, int C, int dtype,
-                              void* stream) {
-    GMK_REQUIRE(dout && w && da, "gmk_head_dgrad: null pointer");
-    GMK_REQUIRE(small_shape_ok(B, cout, H, W, C), "gmk_head_dgrad: unsupported shape");
-    if (dtype == GMK_BF16) launch_expand<bf16_t, true>(dout, w, nullptr, (bf16_t*)da, B, cout, H, W, C, gmk_stream(stream));
-    else if (dtype == GMK_F32) launch_expand<float, true>(dout, w, nullptr, (float*)da, B, cout, H, W, C, gmk_stream(stream));
-    else GMK_REQUIRE(false, "gmk_head_dgrad: bad dtype %d", dtype);
-    return gmk_check_launch("gmk_head_dgrad");
-}
-
-template <typename T, bool FLIP>
-static void launch_wgrad(const float* small, const T* big, float* part, int B, int cs, int H, int W, int C, hipStream_t stream) {
-    const int64_t npix = (int64_t)B * H * W;
-    const int nb = wgrad_rows(npix);
-    int ppb = (int)((npix + nb - 1) / nb);
-    ppb = (ppb + 31) & ~31;
-    const float inv_w = 1.0f / (float)W;
-    const size_t small_bytes = (size_t)npix * cs * 4, big_bytes = (size_t)npix * C * sizeof(T);
-    if (C == 128 && cs <= 3 && W % 2 == 0 && big_bytes < 0xFFFFFF00ull && gmk_kernel_choice(3, "GMK_DEV_VARIANT") != 41) {
-        const unsigned npairs = (unsigned)((npix + 1) / 2);
-        unsigned ppw = (npairs + (unsigned)nb * 4 - 1) / ((unsigned)nb * 4);
-        ppw = (ppw + 7) & ~7u;                                         // whole groups of 8 pairs
-        if constexpr (sizeof(T) == 2) {          // 16-bit tensors: tiles through LDS, 16-bit matrix cores (GMK_DEV_VARIANT 42 keeps the fp32 chain: A/B)
-            if (W <= 128 && small_bytes < 0xFFFFFF00ull && gmk_kernel_choice(3, "GMK_DEV_VARIANT") != 42) {
-                const int tps = (H * W + 127) / 128;
-                const unsigned ntiles = (unsigned)B * (unsigned)tps;
-                gmk_note_kernel(GMK_K_WGRAD3_TILE16);
-#define GMK_WGRAD_T16(CSN) wgrad3x3_tile16_kernel<T, CSN, FLIP><<<nb, 256, 0, stream>>>(small, big, part, H, W, C, tps, ntiles, (unsigned)small_bytes, (unsigned)big_bytes)
-                if (cs == 1) GMK_WGRAD_T16(1);
-                else if (cs == 2) GMK_WGRAD_T16(2);
-                else GMK_WGRAD_T16(3);
-#undef GMK_WGRAD_T16
-                return;
-            }
-        }
-        gmk_note_kernel(GMK_K_WGRAD3_MFMA);
-#define GMK_WGRAD_M(CSN) wgrad3x3_mfma_kernel<T, CSN, FLIP><<<nb, 256, 0, stream>>>(small, big, part, H, W, C, (unsigned)npix, (unsigned)small_bytes, (unsigned)big_bytes, ppw)
-        if (cs == 1) GMK_WGRAD_M(1);
-        else if (cs == 2) GMK_WGRAD_M(2);
-        else GMK_WGRAD_M(3);
-#undef GMK_WGRAD_M
-        return;
-    }
-    // VALU fallback.  Measured (B=1024, 28x28, 3 image channels): one launch per image channel with 8-channel vectors (the C-channel
-    // tensor is read cs times, 204 us) beats all channels at once with 4-channel vectors (one read, but 27 reduction rounds per block: 279 us)
-    gmk_note_kernel(GMK_K_WGRAD3);
-    for (int s0 = 0; s0 < cs; ++s0)
-        wgrad3x3_kernel<T, 1, 8, FLIP><<<nb, 256, 0, stream>>>(small, big, part, H, W, C, inv_w, (unsigned)npix, ppb, cs, s0);
-}
-
-extern "C" int gmk_stem_wgrad(const float* x, const void* dy, float* dw_part, int B, int cin, int H, int W, int C, int dtype,
-                              void* stream) {
-    GMK_REQUIRE(x && dy && dw_part, "gmk_stem_wgrad: null pointer");
-    GMK_REQUIRE(small_shape_ok(B, cin, H, W, C), "gmk_stem_wgrad: unsupported shape");
-    if (dtype == GMK_BF16) launch_wgrad<bf16_t, false>(x, (const bf16_t*)dy, dw_part, B, cin, H, W, C, gmk_stream(stream));
-    else if (dtype == GMK_F32) launch_wgrad<float, false>(x, (const float*)dy, dw_part, B, cin, H, W, C, gmk_stream(stream));
-    else GMK_REQUIRE(false, "gmk_stem_wgrad: bad dtype %d", dtype);
-    return gmk_check_launch("gmk_stem_wgrad");
-}
-
-extern "C" int gmk_head_wgrad(const float* dout, const void* a, float* dw_part, int B, int cout, int H, int W, int C,
-                              int dtype, void* stream) {
-    GMK_REQUIRE(dout && a && dw_part, "gmk_head_wgrad: null pointer");
-    GMK_REQUIRE(small_shape_ok(B, cout, H, W, C), "gmk_head_wgrad: unsupported shape");
-    if (dtype == GMK_BF16) launch_wgrad<bf16_t, true>(dout, (const bf16_t*)a, dw_part, B, cout, H, W, C, gmk_stream(stream));
-    else if (dtype == GMK_F16) launch_wgrad<f16_t, true>(dout, (const f16_t*)a, dw_part, B, cout, H, W, C, gmk_stream(stream));
-    else if (dtype == GMK_F32) launch_wgrad<float, true>(dout, (const float*)a, dw_part, B, cout, H, W, C, gmk_stream(stream));
-    else GMK_REQUIRE(false, "gmk_head_wgrad: bad dtype %d", dtype);
-    return gmk_check_launch("gmk_head_wgrad");
-}
-
-// The head forward and the stem data gradient: one C -> cs contraction over 3x3 taps (head_fwd_body / head_fwd_mfma_body)
-template <typename T, bool STEM_DGRAD>
-static void launch_mfma_band(const T* a, const float* w, const float* bias, float* out, int B, int cs, int H, int W, int mb, int nb2,
-                             size_t lds, unsigned a_bytes, hipStream_t stream) {
-    gmk_note_kernel(STEM_DGRAD ? GMK_K_STEM_DGRAD_MFMA : GMK_K_HEAD_FWD_MFMA);
-    if constexpr (STEM_DGRAD) {
-        static const hipError_t attr = hipFuncSetAttribute((const void*)stem_dgrad_mfma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                           131072);
-        (void)attr;
-        stem_dgrad_mfma_kernel<T><<<B * nb2, 512, lds, stream>>>(a, w, out, cs, H, W, mb, nb2, a_bytes);
     } else {
-        static const hipError_t attr = hipFuncSetAttribute((const void*)head_fwd_mfma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                           131072);
-        (void)attr;
-        head_fwd_mfma_kernel<T><<<B * nb2, 512, lds, stream>>>(a, w, bias, out, cs, H, W, mb, nb2, a_bytes);
+        p->kernel = GMK_K_EXPAND;
+        p->ppb = small_ppb(npix);
+        p->grid = (unsigned)((npix + p->ppb - 1) / p->ppb);
     }
+    return 1;
 }
 
-template <typename T, bool STEM_DGRAD>
-static void launch_valu_band(const T* a, const float* w, const float* bias, float* out, int B, int cs, int H, int W, int C, float inv_w,
-                             int band, int nbands, size_t lds, hipStream_t stream) {
-    gmk_note_kernel(STEM_DGRAD ? GMK_K_STEM_DGRAD : GMK_K_HEAD_FWD);
-    if constexpr (STEM_DGRAD)
-        stem_dgrad_kernel<T><<<B * nbands, 256, lds, stream>>>(a, w, out, cs, H, W, C, inv_w, band, nbands);
-    else
-        head_fwd_kernel<T><<<B * nbands, 256, lds, stream>>>(a, w, bias, out, cs, H, W, C, inv_w, band, nbands);
-}
-
-template <bool STEM_DGRAD>
-static int launch_head_contraction(const void* a, const float* w, const float* bias, float* out, int B, int cs, int H, int W, int C,
-                                   int dtype, hipStream_t stream, const char* name) {
-    const size_t a_bytes = (size_t)B * H * W * C * 2;
-    if (gmk_is16(dtype) && C == 128 && cs <= 3 && a_bytes < 0xFFFFFF00ull && gmk_kernel_choice(3, "GMK_DEV_VARIANT") != 41) {
-        // matrix-core kernel: all image channels from one read; 9 * cs fp32 planes of (band + 2) rows in <= 124 KiB of LDS
-        int mb = (int)(126976 / ((size_t)36 * cs * W)) - 2;
-        if (mb >= 1) {
-            if (mb >= H) mb = H;
-            else {                       // equal bands
-                const int n = (H + mb - 1) / mb;
-                mb = (H + n - 1) / n;
-            }
-            const int nb2 = (H + mb - 1) / mb;
-            const size_t lds2 = (size_t)9 * cs * (mb + 2) * W * 4;
-            if (dtype == GMK_F16)
-                launch_mfma_band<f16_t, STEM_DGRAD>((const f16_t*)a, w, bias, out, B, cs, H, W, mb, nb2, lds2, (unsigned)a_bytes, stream);
-            else
-                launch_mfma_band<bf16_t, STEM_DGRAD>((const bf16_t*)a, w, bias, out, B, cs, H, W, mb, nb2, lds2, (unsigned)a_bytes, stream);
-            return gmk_check_launch(name);
+int gmk_wgrad3_plan(int B, int cs, int H, int W, int C, int dtype, int variant, int cu_limit, SmallPlan* p) {
+    if (!small_plan_begin(B, cs, H, W, C, p)) return 0;
+    const int64_t npix = (int64_t)B * H * W;
+    p->grid = p->rows = wgrad_rows(npix, cu_limit);
+    if (C == 128 && cs <= 3 && W % 2 == 0 && (size_t)npix * C * gmk_esize(dtype) < kBadOff && variant != kVariantValu) {
+        // 16-bit tensors: tiles through LDS, 16-bit matrix cores; else the fp32 chain over pixel pairs
+        if (gmk_is16(dtype) && W <= 128 && (size_t)npix * cs * 4 < kBadOff && variant != kVariantFp32Chain) {
+            p->kernel = GMK_K_WGRAD3_TILE16;
+            p->tps = (H * W + 127) / 128;
+            p->ntiles = (unsigned)B * (unsigned)p->tps;
+        } else {
+            p->kernel = GMK_K_WGRAD3_MFMA;
+            const unsigned npairs = (unsigned)((npix + 1) / 2);
+            p->ppw = (npairs + p->grid * 4 - 1) / (p->grid * 4);
+            p->ppw = (p->ppw + 7) & ~7u;                                         // whole groups of 8 pairs
         }
+    } else {
+        // VALU fallback.  Measured (B=1024, 28x28, 3 image channels): one launch per image channel with 8-channel vectors (the C-channel
+        // tensor is read cs times, 204 us) beats all channels at once with 4-channel vectors (one read, but 27 reduction rounds per block: 279 us)
+        p->kernel = GMK_K_WGRAD3;
+        p->launches = cs;
+        p->ppb = ((int)((npix + p->rows - 1) / p->rows) + 31) & ~31;
     }
-    // band of rows per workgroup: 9 fp32 planes of (band + 2) rows within 48 KiB of LDS, at least 4 workgroups per CU's worth of bands
-    int band = 49152 / (36 * W) - 2;
-    GMK_REQUIRE(band >= 1, "%s: image too wide (W=%d)", name, W);
-    if (band > H) band = H;
-    const int nbands = (H + band - 1) / band;
-    const size_t lds = (size_t)9 * (band + 2) * W * 4;
-    const float inv_w = 1.0f / (float)W;
-    if (dtype == GMK_BF16)
-        launch_valu_band<bf16_t, STEM_DGRAD>((const bf16_t*)a, w, bias, out, B, cs, H, W, C, inv_w, band, nbands, lds, stream);
-    else if (dtype == GMK_F16)
-        launch_valu_band<f16_t, STEM_DGRAD>((const f16_t*)a, w, bias, out, B, cs, H, W, C, inv_w, band, nbands, lds, stream);
-    else if (dtype == GMK_F32)
-        launch_valu_band<float, STEM_DGRAD>((const float*)a, w, bias, out, B, cs, H, W, C, inv_w, band, nbands, lds, stream);
-    else
-        GMK_REQUIRE(false, "%s: bad dtype %d", name, dtype);
+    return 1;
+}
+
+int gmk_head_plan(int B, int cs, int H, int W, int C, int dtype, int variant, int, bool stem_dgrad, SmallPlan* p) {
+    if (!small_plan_begin(B, cs, H, W, C, p)) return 0;
+    // matrix-core kernel: all image channels from one read of 16-bit activations, if one band row of them fits its LDS
+    const int mb = (int)(kMfmaBandLds / ((size_t)36 * cs * W)) - 2;
+    const bool mfma = gmk_is16(dtype) && C == 128 && cs <= 3 && (size_t)B * H * W * C * 2 < kBadOff && variant != kVariantValu && mb >= 1;
+    p->band = mfma ? mb : (int)(kValuBandLds / ((size_t)36 * W)) - 2;
+    if (p->band < 1) return 1;           // kernel 0: too wide
+    if (p->band > H) p->band = H;
+    p->nbands = (H + p->band - 1) / p->band;
+    if (mfma) {                          // equal bands
+        p->band = (H + p->nbands - 1) / p->nbands;
+        p->nbands = (H + p->band - 1) / p->band;
+    }
+    p->kernel = mfma ? (stem_dgrad ? GMK_K_STEM_DGRAD_MFMA : GMK_K_HEAD_FWD_MFMA) : (stem_dgrad ? GMK_K_STEM_DGRAD : GMK_K_HEAD_FWD);
+    p->block = mfma ? 512 : 256;
+    p->lds = (unsigned)((size_t)9 * (mfma ? cs : 1) * (p->band + 2) * W * 4);
+    p->grid = (unsigned)(B * p->nbands);
+    return 1;
+}
+
+extern "C" int gmk_stem_wgrad_blocks(int64_t n_pixels) { return wgrad_rows(n_pixels, gmk_cu_limit()); }
+extern "C" int gmk_head_wgrad_blocks(int64_t n_pixels) { return wgrad_rows(n_pixels, gmk_cu_limit()); }
+
+// ---- the launchers: each executes one plan.  The order of the cases and the type and count lists fix the kernels' addresses (see gmk_with_type):
+// a list is instantiated last to first, so each is written backwards to keep every kernel where it has always been - per storage type bf16, fp16,
+// fp32, in it tiled, matrix-core, VALU, in each 1 .. 4 image channels; the contraction's matrix-core kernels fp16 first (`nm -n` shows it) ------
+template <bool FLIP, typename... Ts>
+static int launch_expand(const char* name, const SmallPlan& p, const float* in, const float* w, const float* bias, void* out, int B, int cs,
+                         int H, int W, int C, int dtype, hipStream_t s) {
+    const unsigned npix = (unsigned)(B * H * W), in_bytes = npix * cs * 4, out_bytes = (unsigned)((size_t)npix * C * gmk_esize(dtype));
+    const bool ok = gmk_with_type<Ts...>(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        gmk_note_kernel(p.kernel);
+        switch (p.kernel) {
+        case GMK_K_EXPAND_TILE16:
+            if constexpr (sizeof(T) == 2)
+                gmk_with_count<3, 2, 1>(cs, [&](auto n) { expand3x3_tile16_kernel<T, decltype(n)::value, FLIP><<<p.grid, p.block, 0, s>>>(in, w, bias, (T*)out, H, W, C, p.tps, p.ntiles, in_bytes, out_bytes); });
+            break;
+        case GMK_K_EXPAND_MFMA:
+            gmk_with_count<4, 3, 2, 1>(cs, [&](auto n) { expand3x3_mfma_kernel<T, decltype(n)::value, FLIP><<<p.grid, p.block, 0, s>>>(in, w, bias, (T*)out, H, W, C, npix, p.nblocks, in_bytes, out_bytes); });
+            break;
+        default:
+            gmk_with_count<4, 3, 2, 1>(cs, [&](auto n) {
+                constexpr int CSN = decltype(n)::value;
+                expand3x3_kernel<T, CSN, CSN <= 2 ? 8 : 4, FLIP><<<p.grid, p.block, 0, s>>>(in, w, bias, (T*)out, H, W, C, 1.0f / (float)W, npix, p.ppb);
+            });
+        }
+    });
+    GMK_REQUIRE(ok, "%s: bad dtype %d", name, dtype);
     return gmk_check_launch(name);
 }
 
-extern "C" int gmk_head_fwd(const void* a, const float* w, const float* bias, float* out, int B, int cout, int H, int W,
-                            int C, int dtype, void* stream) {
+template <bool FLIP, typename... Ts>
+static int launch_wgrad(const char* name, const SmallPlan& p, const float* small, const void* big, float* part, int B, int cs, int H, int W,
+                        int C, int dtype, hipStream_t s) {
+    const unsigned npix = (unsigned)(B * H * W), small_bytes = npix * cs * 4, big_bytes = (unsigned)((size_t)npix * C * gmk_esize(dtype));
+    const bool ok = gmk_with_type<Ts...>(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        gmk_note_kernel(p.kernel);
+        switch (p.kernel) {
+        case GMK_K_WGRAD3_TILE16:
+            if constexpr (sizeof(T) == 2)
+                gmk_with_count<3, 2, 1>(cs, [&](auto n) { wgrad3x3_tile16_kernel<T, decltype(n)::value, FLIP><<<p.grid, p.block, 0, s>>>(small, (const T*)big, part, H, W, C, p.tps, p.ntiles, small_bytes, big_bytes); });
+            break;
+        case GMK_K_WGRAD3_MFMA:
+            gmk_with_count<3, 2, 1>(cs, [&](auto n) { wgrad3x3_mfma_kernel<T, decltype(n)::value, FLIP><<<p.grid, p.block, 0, s>>>(small, (const T*)big, part, H, W, C, npix, small_bytes, big_bytes, p.ppw); });
+            break;
+        default:      // only ever <T, 1, 8, FLIP>, one image channel per launch: dropping the kernel's unused generality would rename its symbols, left for another day
+            for (int s0 = 0; s0 < p.launches; ++s0)
+                wgrad3x3_kernel<T, 1, 8, FLIP><<<p.grid, p.block, 0, s>>>(small, (const T*)big, part, H, W, C, 1.0f / (float)W, npix, p.ppb, cs, s0);
+        }
+    });
+    GMK_REQUIRE(ok, "%s: bad dtype %d", name, dtype);
+    return gmk_check_launch(name);
+}
+
+// The head forward and the stem data gradient: one C -> cs contraction over 3x3 taps (head_fwd_body / head_fwd_mfma_body)
+template <bool STEM_DGRAD>
+static int launch_head(const char* name, const SmallPlan& p, const void* a, const float* w, const float* bias, float* out, int B, int cs, int H,
+                       int W, int C, int dtype, hipStream_t s) {
+    GMK_REQUIRE(p.kernel, "%s: image too wide (W=%d)", name, W);
+    bool ok;
+    if (p.kernel == GMK_K_HEAD_FWD_MFMA || p.kernel == GMK_K_STEM_DGRAD_MFMA)
+        ok = gmk_with_type<bf16_t, f16_t>(dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            const unsigned a_bytes = (unsigned)((size_t)B * H * W * C * 2);
+            constexpr auto kernel = [] { if constexpr (STEM_DGRAD) return stem_dgrad_mfma_kernel<T>; else return head_fwd_mfma_kernel<T>; }();
+            [[maybe_unused]] static const hipError_t attr = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+            if constexpr (STEM_DGRAD) kernel<<<p.grid, p.block, p.lds, s>>>((const T*)a, w, out, cs, H, W, p.band, p.nbands, a_bytes);
+            else kernel<<<p.grid, p.block, p.lds, s>>>((const T*)a, w, bias, out, cs, H, W, p.band, p.nbands, a_bytes);
+        });
+    else
+        ok = gmk_with_type<float, f16_t, bf16_t>(dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            if constexpr (STEM_DGRAD) stem_dgrad_kernel<T><<<p.grid, p.block, p.lds, s>>>((const T*)a, w, out, cs, H, W, C, 1.0f / (float)W, p.band, p.nbands);
+            else head_fwd_kernel<T><<<p.grid, p.block, p.lds, s>>>((const T*)a, w, bias, out, cs, H, W, C, 1.0f / (float)W, p.band, p.nbands);
+        });
+    GMK_REQUIRE(ok, "%s: bad dtype %d", name, dtype);
+    gmk_note_kernel(p.kernel);
+    return gmk_check_launch(name);
+}
+
+// ---- the six entry points: pointers, the plan (0: the shape is refused), its launch -------------------------------------------------------------
+static int dev_variant(void) { return gmk_kernel_choice(3, "GMK_DEV_VARIANT"); }      // read once per call
+
+extern "C" int gmk_stem_fwd(const float* x, const float* w, const float* bias, void* y, int B, int cin, int H, int W, int C, int dtype, void* stream) {
+    SmallPlan p;
+    GMK_REQUIRE(x && w && bias && y, "gmk_stem_fwd: null pointer");
+    GMK_REQUIRE(gmk_expand_plan(B, cin, H, W, C, dtype, dev_variant(), gmk_cu_limit(), &p), "gmk_stem_fwd: unsupported shape B=%d cin=%d %dx%d C=%d", B, cin, H, W, C);
+    return launch_expand<false, float, f16_t, bf16_t>("gmk_stem_fwd", p, x, w, bias, y, B, cin, H, W, C, dtype, gmk_stream(stream));
+}
+
+extern "C" int gmk_head_dgrad(const float* dout, const float* w, void* da, int B, int cout, int H, int W, int C, int dtype, void* stream) {
+    SmallPlan p;
+    GMK_REQUIRE(dout && w && da, "gmk_head_dgrad: null pointer");
+    GMK_REQUIRE(gmk_expand_plan(B, cout, H, W, C, dtype, dev_variant(), gmk_cu_limit(), &p), "gmk_head_dgrad: unsupported shape");
+    return launch_expand<true, float, bf16_t>("gmk_head_dgrad", p, dout, w, nullptr, da, B, cout, H, W, C, dtype, gmk_stream(stream));
+}
+
+extern "C" int gmk_stem_wgrad(const float* x, const void* dy, float* dw_part, int B, int cin, int H, int W, int C, int dtype, void* stream) {
+    SmallPlan p;
+    GMK_REQUIRE(x && dy && dw_part, "gmk_stem_wgrad: null pointer");
+    GMK_REQUIRE(gmk_wgrad3_plan(B, cin, H, W, C, dtype, dev_variant(), gmk_cu_limit(), &p), "gmk_stem_wgrad: unsupported shape");
+    return launch_wgrad<false, float, bf16_t>("gmk_stem_wgrad", p, x, dy, dw_part, B, cin, H, W, C, dtype, gmk_stream(stream));
+}
+
+extern "C" int gmk_head_wgrad(const float* dout, const void* a, float* dw_part, int B, int cout, int H, int W, int C, int dtype, void* stream) {
+    SmallPlan p;
+    GMK_REQUIRE(dout && a && dw_part, "gmk_head_wgrad: null pointer");
+    GMK_REQUIRE(gmk_wgrad3_plan(B, cout, H, W, C, dtype, dev_variant(), gmk_cu_limit(), &p), "gmk_head_wgrad: unsupported shape");
+    return launch_wgrad<true, float, f16_t, bf16_t>("gmk_head_wgrad", p, dout, a, dw_part, B, cout, H, W, C, dtype, gmk_stream(stream));
+}
+
+extern "C" int gmk_head_fwd(const void* a, const float* w, const float* bias, float* out, int B, int cout, int H, int W, int C, int dtype, void* stream) {
+    SmallPlan p;
     GMK_REQUIRE(a && w && bias && out, "gmk_head_fwd: null pointer");
-    GMK_REQUIRE(small_shape_ok(B, cout, H, W, C), "gmk_head_fwd: unsupported shape");
-    return launch_head_contraction<false>(a, w, bias, out, B, cout, H, W, C, dtype, gmk_stream(stream), "gmk_head_fwd");
+    GMK_REQUIRE(gmk_head_plan(B, cout, H, W, C, dtype, dev_variant(), gmk_cu_limit(), false, &p), "gmk_head_fwd: unsupported shape");
+    return launch_head<false>("gmk_head_fwd", p, a, w, bias, out, B, cout, H, W, C, dtype, gmk_stream(stream));
 }
 
 extern "C" int gmk_stem_dgrad(const void* dy, const float* w, float* dx, int B, int cin, int H, int W, int C, int dtype, void* stream) {
+    SmallPlan p;
     GMK_REQUIRE(dy && w && dx, "gmk_stem_dgrad: null pointer");
-    GMK_REQUIRE(small_shape_ok(B, cin, H, W, C), "gmk_stem_dgrad: unsupported shape B=%d cin=%d %dx%d C=%d", B, cin, H, W, C);
-    return launch_head_contraction<true>(dy, w, nullptr, dx, B, cin, H, W, C, dtype, gmk_stream(stream), "gmk_stem_dgrad");
+    GMK_REQUIRE(gmk_head_plan(B, cin, H, W, C, dtype, dev_variant(), gmk_cu_limit(), true, &p), "gmk_stem_dgrad: unsupported shape B=%d cin=%d %dx%d C=%d", B, cin, H, W, C);
+    return launch_head<true>("gmk_stem_dgrad", p, dy, w, nullptr, dx, B, cin, H, W, C, dtype, gmk_stream(stream));
 }

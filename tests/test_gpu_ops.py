@@ -175,6 +175,50 @@ def test_stem_head(ops, dtype, cs, S, B):
     assert rel_err(dwb[cs * C * 9:], bh.grad) < 1e-3
 
 
+@pytest.mark.parametrize("C,dtype", [(128, torch.float32), (128, torch.bfloat16), (128, torch.float16), (256, torch.bfloat16)])
+def test_stem_head_under_a_cu_limit(ops, C, dtype):
+    """The five launches of test_stem_head and the stem's data gradient with every persistent grid on its clamped side: under a CU limit of 8,
+    B = 9 at 32 x 32 with 3 image channels is 72 tiles on a 16-workgroup tiled grid, 72 block groups on a 16-workgroup matrix-core grid and 18
+    streaming blocks onto 16 partial rows.  C = 128: the matrix-core kernels of each storage type (fp16 = the 16-bit mode: fp16 activations
+    beside bf16 gradients, as the two gradient-typed entries take no fp16); C = 256: the VALU kernels.  Against F.conv2d and autograd on the
+    same rounded operands, at test_stem_head's bars; an fp16 result gets 2e-3, test_gpu_f16's bar for the stem (4 ulp of 2^-11 at the
+    output's scale), below the bf16 one."""
+    cs, S, B = 3, 32, 9
+    gdtype = torch.bfloat16 if dtype == torch.float16 else dtype          # the type of the gradient tensors
+    tol = {**TOL, torch.float16: 2e-3}
+    x = rnd(B, cs, S, S, seed=40).clamp(-1, 1).requires_grad_(True)
+    w = (rnd(C, cs, 3, 3, seed=41) / 3).requires_grad_(True)
+    b = 0.1 * rnd(C, seed=42)
+    a = q(rnd(B, C, S, S, seed=44), dtype).requires_grad_(True)
+    wh = (rnd(cs, C, 3, 3, seed=45) / math.sqrt(9 * C)).requires_grad_(True)
+    bh = (0.1 * rnd(cs, seed=46)).requires_grad_(True)
+    dy, do = q(rnd(B, C, S, S, seed=43), gdtype), rnd(B, cs, S, S, seed=47)
+    y_ref, o_ref = F.conv2d(x, w, b, padding=1), F.conv2d(a, wh, bh, padding=1)
+    y_ref.backward(dy)
+    o_ref.backward(do)
+    before = ops.get_cu_limit()
+    ops.set_cu_limit(8)
+    try:
+        y = ops.stem_fwd(x.detach().cuda(), w.detach().cuda(), b.cuda(), C, dtype)
+        dw = torch.empty_like(w.detach()).cuda()
+        ops.stem_wgrad(x.detach().cuda(), nhwc(dy, gdtype), dw)
+        dx = ops.stem_dgrad(nhwc(dy, gdtype), w.detach().cuda())
+        o = ops.head_fwd(nhwc(a.detach(), dtype), wh.detach().cuda(), bh.detach().cuda())
+        da = ops.head_dgrad(do.cuda(), wh.detach().cuda(), gdtype)
+        dwb = torch.empty(cs * C * 9 + cs, device="cuda")
+        ops.head_wgrad(do.cuda(), nhwc(a.detach(), dtype), dwb)
+        torch.cuda.synchronize()
+    finally:
+        ops.set_cu_limit(before)
+    assert rel_err(nchw(y), y_ref) < tol[dtype]
+    assert rel_err(dw, w.grad) < tol[gdtype]
+    assert rel_err(dx, x.grad) < tol[gdtype]
+    assert rel_err(o, o_ref) < tol[dtype]
+    assert rel_err(nchw(da), a.grad) < tol[gdtype]
+    assert rel_err(dwb[:cs * C * 9].view_as(wh), wh.grad) < tol[dtype]
+    assert rel_err(dwb[cs * C * 9:], bh.grad) < 1e-3
+
+
 def test_stem_head_random_shapes(ops):
     """The four stem / head launches of the 16-bit mode on 24 random shapes (non-square, rows that fill no 64- or 128-pixel tile, widths on
     both sides of the tiled kernels' W <= 128, 1 - 3 image channels, batches of 1 - 6) against autograd on the same rounded operands."""

@@ -1120,3 +1120,95 @@ def test_smallconv_reports_what_it_launches(smallconv_launch_trace):
     assert len(got) == 1920 and set(got.values()) == set(_SMALLCONV_KERNELS)
     for case, name in launch_trace.SMALLCONV_LANDMARKS.items():
         assert got[case] == name, (case, got[case], name)
+
+
+def _smallconv_rows(lines):
+    """trace lines -> [(entry, call fields, rc, error text, kernel id, [launch fields: name, grid, block, lds, args (explicit arguments as little-endian ints)])]"""
+    rows = []
+    for line in lines:
+        head, _, tail = line.partition(" -> ")
+        f = dict(kv.split("=", 1) for kv in head.split()[1:])
+        launches = []
+        for text in tail.split(" launch=")[1:]:
+            w = dict(kv.split("=", 1) for kv in ("name=" + text).split())
+            w["args"] = [int.from_bytes(bytes.fromhex(a.split(":")[1]), "little") for a in w["args"].split(",")]
+            launches.append(w)
+        rc, err, kid = re.match(r'rc=(-?\d+) err="(.*)" kernel=(-?\d+)', tail).groups()
+        rows.append((head.split()[0], f, int(rc), err, int(kid), launches))
+    return rows
+
+
+def test_smallconv_sweeps_launch_every_instantiation(smallconv_launch_trace):
+    """Every expand3x3_*, wgrad3x3_*, head_fwd* and stem_dgrad* kernel in the code object of smallconv.hip is launched by at least one line of
+    the tool's two sweeps (`all` + `limits`): no instantiation that no call reaches, none that only an untraced call reaches."""
+    notes = open(smallconv_launch_trace.notes).read()
+    symbols = {s for s in re.findall(r"\.name:\s+(\S+)", notes) if re.search(r"\d+(expand3x3_|wgrad3x3_|head_fwd|stem_dgrad)\w*kernelI", s) and not s.endswith(".kd")}
+    assert len(symbols) == 88
+    launched = set()
+    for mode in ("all", "limits"):
+        for line in smallconv_launch_trace(mode):
+            launched.update(re.findall(r" launch=(\S+)", line))
+    assert not symbols - launched, sorted(symbols - launched)
+    assert launched <= symbols
+
+
+def test_smallconv_plans_at_their_clamps(smallconv_launch_trace):
+    """The `limits` sweep of the stem / head entry points: the persistent grids under the CU limits 256 / 248 / 8, the byte limit that demotes a
+    C = 128 call to the VALU kernel, the contraction's bands, the refusal at 2^24 pixels - values worked out by hand from the launchers as they
+    stood before the planners and confirmed on their trace - and, on every line, gmk_*_wgrad_blocks(B H W) = the grid of the weight-gradient
+    launch = the rows ops sizes the partials with.  The byte limit is one number in the source: every kBadOff is the file-scope one."""
+    from generative_models_amd._lib import K
+    F32, BF16, F16 = 0, 1, 2
+    lines = smallconv_launch_trace("limits")
+    assert len(lines) == 3 * 2 * 4 * 13 * (3 * 16 + 6) + 36 and all("no-metadata" not in line for line in lines)
+    rows = _smallconv_rows(lines)
+    at = {(e, int(f["cu"]), int(f["variant"]), int(f["C"]), int(f["cs"]), int(f["B"]), f["grid"], int(f["dtype"])): (rc, kid, ls)
+          for e, f, rc, _, kid, ls in rows if "cu" in f}
+    # (c) the partial rows
+    n = 0
+    for e, f, rc, _, kid, ls in rows:
+        if e in ("stem_wgrad", "head_wgrad") and rc == 0 and "blocks" in f:
+            blocks = int(f["blocks"].split(",")[e == "head_wgrad"])
+            assert ls and all(w["grid"] == "%d,1,1" % blocks for w in ls) and len(ls) == (int(f["cs"]) if kid == K.WGRAD3 else 1), (f, ls)
+            n += 1
+    assert n == 3 * 3 * 2 * 4 * (13 - 2) * (2 + 3)          # every accepted size (two of the 13 are 2^24 pixels), the five weight-gradient lines
+    # (b) B = 2048 at 32 x 32, 3 image channels, C = 128
+    for L in (256, 248, 8):
+        rc, kid, (w,) = at[("stem_fwd", L, 0, 128, 3, 2048, "32x32", BF16)]
+        assert (rc, kid, w["grid"], w["block"]) == (0, K.EXPAND_TILE16, "%d,1,1" % min(2048 * 8, 2 * L), "256,1,1") and "expand3x3_tile16_kernel" in w["name"]
+        assert {256: 512, 248: 496, 8: 16}[L] == min(2048 * 8, 2 * L) and w["args"][-4:-2] == [8, 2048 * 8]          # tps, ntiles
+        rc, kid, (w,) = at[("stem_wgrad", L, 0, 128, 3, 2048, "32x32", F32)]
+        assert (rc, kid, w["grid"]) == (0, K.WGRAD3_MFMA, "%d,1,1" % min(2048, 2 * L)) and "wgrad3x3_mfma_kernel" in w["name"]      # 1024 pixels per block: 2048 blocks
+        assert w["args"][-1] == (-(-2 ** 20 // (4 * min(2048, 2 * L))) + 7) // 8 * 8 and (L != 256 or w["args"][-1] == 512)      # ppw: pairs per wave, groups of 8
+    rc, kid, (w,) = at[("head_fwd", 256, 0, 128, 3, 2048, "32x32", F16)]
+    assert (rc, kid, w["grid"], w["block"], w["lds"]) == (0, K.HEAD_FWD_MFMA, "2048,1,1", "512,1,1", str(27 * 34 * 32 * 4)) and 27 * 34 * 32 * 4 == 117504
+    assert w["args"][-3:-1] == [32, 1] and "head_fwd_mfma_kernel" in w["name"]          # band, nbands
+    rc, kid, (w,) = at[("head_fwd", 256, 0, 128, 3, 1024, "64x64", F16)]
+    assert (rc, kid, w["grid"], w["lds"], w["args"][-3:-1]) == (0, K.HEAD_FWD_MFMA, "4096,1,1", "124416", [16, 4])
+    # B = 8192 at 32 x 32: the fp32 output is exactly 4 GiB - the VALU kernel, 1024 pixels per block; the bf16 one stays tiled
+    rc, kid, (w,) = at[("stem_fwd", 256, 0, 128, 3, 8192, "32x32", F32)]
+    assert (rc, kid, w["grid"], w["args"][-1]) == (0, K.EXPAND, "8192,1,1", 1024) and "expand3x3_kernel" in w["name"]
+    rc, kid, (w,) = at[("stem_fwd", 256, 0, 128, 3, 8192, "32x32", BF16)]
+    assert (rc, kid, w["grid"]) == (0, K.EXPAND_TILE16, "512,1,1")
+    # exactly 2^20 pixels: still 512 per block; a 16-bit tensor of exactly the byte limit: the VALU kernels
+    assert at[("stem_fwd", 256, 0, 256, 3, 1024, "32x32", BF16)][2][0]["grid"] == "2048,1,1"
+    for e, kid in (("stem_fwd", K.EXPAND), ("head_fwd", K.HEAD_FWD), ("stem_dgrad", K.STEM_DGRAD)):
+        assert at[(e, 256, 0, 128, 3, 479349, "5x7", BF16)][:2] == (0, kid)
+    # rows of exactly 128 pixels are the last the tiled kernels take; 2 image channels there: 11 band rows fit the contraction's LDS, so 12 rows are 2 bands of 6
+    assert at[("stem_fwd", 256, 0, 128, 2, 2, "12x128", BF16)][:2] == (0, K.EXPAND_TILE16) and at[("stem_wgrad", 256, 0, 128, 2, 2, "12x128", BF16)][:2] == (0, K.WGRAD3_TILE16)
+    rc, kid, (w,) = at[("head_fwd", 256, 0, 128, 2, 2, "12x128", BF16)]
+    assert (rc, kid, w["grid"], w["lds"], w["args"][-3:-1]) == (0, K.HEAD_FWD_MFMA, "4,1,1", str(18 * 8 * 128 * 4), [6, 2])
+    # 2^24 pixels: every entry refuses, with the texts it has always had
+    texts = {"stem_fwd": "gmk_stem_fwd: unsupported shape B=16384 cin=3 32x32 C=128", "stem_dgrad": "gmk_stem_dgrad: unsupported shape B=16384 cin=3 32x32 C=128"}
+    for e, f, rc, err, kid, ls in rows:
+        if f.get("B") == "16384" and f["cs"] == "3" and f["C"] == "128":
+            assert rc == -1 and not ls and err == texts.get(e, "gmk_%s: unsupported shape" % e), (e, f, err)
+    assert all(rc == 0 for (e, L, v, C, cs, B, g, dt), (rc, _, _) in at.items() if B == 16383 and dt != 7)
+    # an illegal storage type, a null pointer, an image too wide for any kernel
+    assert all(rc == -1 and not ls for (e, L, v, C, cs, B, g, dt), (rc, _, ls) in at.items() if dt == 7)
+    nulls = [(e, f, rc, err) for e, f, rc, err, _, ls in rows if "null" in f]
+    order = ["stem_fwd", "stem_wgrad", "head_fwd", "head_dgrad", "head_wgrad", "stem_dgrad"]
+    assert len(nulls) == 36 and all((rc, err) == (-1, "gmk_%s: null pointer" % e) if order[int(f["null"])] == e else rc == 0 for e, f, rc, err in nulls)
+    assert at[("head_fwd", 256, 0, 128, 3, 2, "1x2048", BF16)][0] == -1 and at[("head_fwd", 256, 0, 128, 3, 2, "2x400", BF16)][:2] == (0, K.HEAD_FWD)
+    src = open(os.path.join(ROOT, "generative_models_amd", "csrc", "smallconv.hip")).read()
+    assert set(re.findall(r"kBadOff = (\w+);", src)) == {"0xFFFFFF00u"} and "0xFFFFFF00ull" not in src
