@@ -11,7 +11,8 @@
 // gmk_x_loss_w (the SNR+1 weighting of Salimans & Ho 2022 and Min-SNR-gamma, Hang et al. 2023, as w(logsnr) x_mse) and gmk_u_stratified
 // (low-discrepancy training times, Kingma et al. 2021) are extensions too.  gmk_slerp (spherical interpolation of latent codes) is an extension as well.
 // gmk_box_mean / gmk_box_residual / gmk_sampler_step_ns / gmk_dpm_solver_step_ns (DDNM's range-null-space projection of x-hat for box-mean
-// operators: Wang, Yu & Zhang 2023) are extensions too.
+// operators: Wang, Yu & Zhang 2023) are extensions too.  gmk_consistency_target / gmk_x_loss_huber / gmk_consistency_step (consistency distillation and
+// multistep consistency sampling: Song et al. 2023, Algorithms 1 and 2; the pseudo-Huber metric of Song & Dhariwal 2023) are extensions as well.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -173,9 +174,12 @@ __global__ __launch_bounds__(256) void v_loss_kernel(const float* __restrict__ v
 // re-reads the residuals it wrote itself and zeroes those whose raw prediction left [-1, 1] (one bit per element, at most 48, in a register
 // pair).  Larger images are read again.  LDS: 4 min(n, kXLossKeep) bytes (12 KiB at 3 x 32 x 32, 48 KiB at the capacity) + 16 for block_sum,
 // all of it dynamic so that the 16-byte accesses stay aligned.
+// HUBER (gmk_x_loss_huber; the pseudo-Huber metric of Song & Dhariwal 2023, "Improved Techniques for Training Consistency Models", with
+// c_paper = c sqrt(n), scaled by 1 / sqrt(n)): the same passes and the same x_mse bits; loss_b = r - c with r = sqrt(x_mse + c^2) and the
+// gradient's factor grad_scale / (n r) in place of grad_scale w 2 / n.  `gamma` carries c; weight_type is not read.
 constexpr int kXLossKeep = GMK_X_LOSS_KEEP;    // kDynKeys: covers 3 x 64 x 64
 
-template <bool VEC>
+template <bool VEC, bool HUBER = false>
 __global__ __launch_bounds__(256) void x_loss_w_kernel(const float* __restrict__ v, const float* __restrict__ z, const float* __restrict__ x,
                                                       const float* __restrict__ logsnr, float* __restrict__ loss_b,
                                                       float* __restrict__ x_mse_o, float* __restrict__ dv, float grad_scale, int weight_type,
@@ -218,15 +222,20 @@ __global__ __launch_bounds__(256) void x_loss_w_kernel(const float* __restrict__
     }
     sx = block_sum(sx, red);
     const float xm = sx / (float)n;
-    const float el = expf(l);
-    const float w = weight_type == GMK_LOSS_W_SNR_PLUS1 ? 1.0f + el : fminf(el, gamma);
-    if (tid == 0) {
-        loss_b[b] = w * xm;
-        x_mse_o[b] = xm;
+    float w, kx;
+    if constexpr (HUBER) {
+        w = sqrtf(xm + gamma * gamma);       // r: sqrt(c c) is c itself, so a zero residual is a zero loss
+        kx = grad_scale / ((float)n * w);
+        if (tid == 0) loss_b[b] = w - gamma;
+    } else {
+        const float el = expf(l);
+        w = weight_type == GMK_LOSS_W_SNR_PLUS1 ? 1.0f + el : fminf(el, gamma);
+        kx = grad_scale * w * 2.f / (float)n;
+        if (tid == 0) loss_b[b] = w * xm;
     }
+    if (tid == 0) x_mse_o[b] = xm;
     if (!dv) return;
     // torch.clip passes the gradient inside [-1, 1], ends included (v_loss_kernel's rule); w depends on l alone
-    const float kx = grad_scale * w * 2.f / (float)n;
     const float dxo = dx_dout(c, mt);
     if (keep) {
         int bit = 0;
@@ -793,6 +802,46 @@ __global__ __launch_bounds__(256) void inpaint_merge_kernel(float* __restrict__ 
     }
 }
 
+// ---- multistep consistency sampling (Song et al. 2023, "Consistency Models", Algorithm 1); an extension, no reference call site.
+// grid (ceil(n/1024), B): x-hat / eps-hat and the guidance exactly as sampler_step_kernel forms them (predict_x_eps), then
+//   z_next = is_last ? x-hat : alpha_s x-hat + sigma_s eps      (a product, a product, a sum: nothing contracted)
+// eps are Philox normals drawn here and never stored: element j of this chunk (j = b n + i) takes counter ctr + j / 4, component j % 4 - what
+// gmk_rng_normal(seed, ctr) would store at j.  Not drawn when is_last.  n % 4 == 0: every group of four lies in one row and starts 16-byte
+// aligned.  alpha_s, sigma_s come from the host (double, rounded to fp32).
+__global__ __launch_bounds__(256) void consistency_step_kernel(const float* __restrict__ v, const float* __restrict__ vu,
+                                                              const float* __restrict__ cond_w, const float* __restrict__ z, float lt, float ls,
+                                                              float alpha_s, float sigma_s, int is_last, uint64_t seed, uint64_t ctr,
+                                                              float* __restrict__ z_next, float* __restrict__ x_pred,
+                                                              float* __restrict__ eps_pred, float* __restrict__ z_dup,
+                                                              float* __restrict__ logsnr_next, int64_t n, int mt) {
+    const int b = blockIdx.y;
+    write_logsnr_next(logsnr_next, z_dup, b, ls);
+    const LogsnrCoef c = logsnr_coef(lt);
+    const float w = cond_w ? cond_w[b] : 0.f;
+    const int64_t base = (int64_t)b * n;
+    for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+        const int64_t j = base + i;
+        float vv[4], zv[4], xh[4], eh[4], zs[4];
+        load4(v + j, vv);
+        load4(z + j, zv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) predict_x_eps<false>(vv[k], vu, j + k, w, zv[k], c, mt, 1.0f, xh[k], eh[k]);
+        if (is_last) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zs[k] = xh[k];
+        } else {
+            float e[4];
+            philox_normal4(ctr + (uint64_t)(j >> 2), seed, e);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zs[k] = __fadd_rn(__fmul_rn(alpha_s, xh[k]), __fmul_rn(sigma_s, e[k]));
+        }
+        store4(z_next + j, zs);
+        if (z_dup) store4(z_dup + j, zs);
+        if (x_pred) store4(x_pred + j, xh);
+        if (eps_pred) store4(eps_pred + j, eh);
+    }
+}
+
 // ---- continuous-time variational bound (Kingma et al. 2021, VDM eq. 17 with lambda as the variable); an extension, no reference call site.
 // Every kernel below takes any n: 16-byte vector accesses when n % 4 == 0 (every row then starts 16-byte aligned), element by element otherwise.
 
@@ -1317,6 +1366,22 @@ extern "C" int gmk_x_loss_w(const float* v, const float* z, const float* x, cons
     return gmk_check_launch("gmk_x_loss_w");
 }
 
+extern "C" int gmk_x_loss_huber(const float* v, const float* z, const float* x, const float* logsnr, float* loss_b, float* x_mse, float* dv,
+                                float grad_scale, float c, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && z && x && logsnr && loss_b && x_mse, "gmk_x_loss_huber: null pointer");
+    GMK_REQUIRE(B > 0 && n > 0, "gmk_x_loss_huber: bad shape B=%d n=%lld", B, (long long)n);
+    GMK_REQUIRE(isfinite(c) && c > 0.0f, "gmk_x_loss_huber: c = %g, need a finite value > 0", (double)c);
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_x_loss_huber");
+    const int64_t m = n < kXLossKeep ? n : kXLossKeep;
+    const int lds_floats = (int)((m + 3) / 4 * 4);
+    const size_t lds = (size_t)(lds_floats + 4) * sizeof(float);
+    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(x) |
+                                     reinterpret_cast<uintptr_t>(dv)) & 15) == 0;       // gmk_x_loss_w's rule
+    if (vec) x_loss_w_kernel<true, true><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, 0, c, n, mean_type, lds_floats);
+    else x_loss_w_kernel<false, true><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, 0, c, n, mean_type, lds_floats);
+    return gmk_check_launch("gmk_x_loss_huber");
+}
+
 extern "C" int gmk_u_stratified(const float* u0, float* u, int B, void* stream) {
     GMK_REQUIRE(u0 && u, "gmk_u_stratified: null pointer");
     GMK_REQUIRE(B > 0 && B <= (1 << 24), "gmk_u_stratified: B = %d outside [1, 2^24] (b and B must be exact in fp32)", B);
@@ -1515,6 +1580,22 @@ extern "C" int gmk_inpaint_merge(float* z, const float* x0, const uint8_t* mask,
     return gmk_check_launch("gmk_inpaint_merge");
 }
 
+extern "C" int gmk_consistency_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float logsnr_t, float logsnr_s,
+                                    int is_last, uint64_t seed, uint64_t offset, uint64_t q0, float* z_next, float* x_pred, float* eps_pred,
+                                    float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && z && z_next, "gmk_consistency_step: null pointer");
+    if (const int err = step_args_check("gmk_consistency_step", mean_type, v_uncond, cond_w, B, n)) return err;
+    GMK_REQUIRE(n % 4 == 0, "gmk_consistency_step: n = %lld (n %% 4 == 0 required)", (long long)n);
+    GMK_REQUIRE(isfinite(logsnr_t) && isfinite(logsnr_s), "gmk_consistency_step: non-finite time");
+    // alpha_s^2 = sigmoid(logsnr_s), sigma_s^2 = sigmoid(-logsnr_s), in double from the fp32 log-SNR
+    const double ls = (double)logsnr_s;
+    const float alpha_s = (float)sqrt(1.0 / (1.0 + exp(-ls))), sigma_s = (float)sqrt(1.0 / (1.0 + exp(ls)));
+    const int gx = row_grid(n, 1024);
+    consistency_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, logsnr_t, logsnr_s, alpha_s, sigma_s, is_last, seed,
+                                                                        offset + q0, z_next, x_pred, eps_pred, z_dup, logsnr_next, n, mean_type);
+    return gmk_check_launch("gmk_consistency_step");
+}
+
 extern "C" int gmk_q_sample_logsnr(const float* x, const float* eps, const float* logsnr, float* z, int B, int64_t n, void* stream) {
     GMK_REQUIRE(x && eps && logsnr && z, "gmk_q_sample_logsnr: null pointer");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_q_sample_logsnr: bad shape B=%d n=%lld", B, (long long)n);
@@ -1598,6 +1679,41 @@ __global__ __launch_bounds__(256) void distill_target_kernel(const float* __rest
         eps_target[base + i] = c1 * (zt - xt * c2);
     }
 }
+
+// consistency distillation (Song et al. 2023, "Consistency Models", Algorithm 2): the target net's clipped data prediction at (z_s, logsnr_s) -
+// predict_x_eps, sampler_step_kernel's own x-hat - with the boundary condition f(., t_min) = identity as the i == 0 select of the teacher's final
+// prediction, and the eps-target distill_target_kernel ends with.  grid (gx, B); VEC: 16-byte accesses (n % 4 == 0, aligned tensors), else one by
+// one - the same operations per element.  Rows with i == 0 read neither v_tgt nor z_s.
+template <bool VEC>
+__global__ __launch_bounds__(256) void consistency_target_kernel(const float* __restrict__ v_tgt, const float* __restrict__ z_s,
+                                                                const float* __restrict__ x_pred_teacher, const float* __restrict__ z_t,
+                                                                const float* __restrict__ logsnr_t, const float* __restrict__ logsnr_s,
+                                                                const int64_t* __restrict__ ti, float* __restrict__ x_target,
+                                                                float* __restrict__ eps_target, int64_t n, int mt) {
+    constexpr int STEP = VEC ? 4 : 1;
+    const int b = blockIdx.y;
+    const float l = logsnr_t[b];
+    const LogsnrCoef cs = logsnr_coef(logsnr_s[b]);
+    const float c1 = sqrtf(1.0f + expf(l)), c2 = 1.0f / sqrtf(1.0f + expf(-l));
+    const bool first = ti[b] == 0;
+    const int64_t base = (int64_t)b * n;
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * STEP; i < n; i += (int64_t)gridDim.x * 256 * STEP) {
+        const int64_t j = base + i;
+        float zt[STEP], xt[STEP], et[STEP];
+        if constexpr (VEC) load4(z_t + j, zt); else zt[0] = z_t[j];
+        if (first) {
+            if constexpr (VEC) load4(x_pred_teacher + j, xt); else xt[0] = x_pred_teacher[j];
+        } else {
+            float vv[STEP], zs[STEP], eh;
+            if constexpr (VEC) { load4(v_tgt + j, vv); load4(z_s + j, zs); } else { vv[0] = v_tgt[j]; zs[0] = z_s[j]; }
+#pragma unroll
+            for (int k = 0; k < STEP; ++k) predict_x_eps<false>(vv[k], nullptr, j + k, 0.f, zs[k], cs, mt, 1.0f, xt[k], eh);
+        }
+#pragma unroll
+        for (int k = 0; k < STEP; ++k) et[k] = c1 * (zt[k] - xt[k] * c2);
+        if constexpr (VEC) { store4(x_target + j, xt); store4(eps_target + j, et); } else { x_target[j] = xt[0]; eps_target[j] = et[0]; }
+    }
+}
 }  // namespace
 
 extern "C" int gmk_logsnr_schedule(const float* u, const int64_t* i_times, int num_steps, float shift, float* u_out,
@@ -1629,6 +1745,20 @@ extern "C" int gmk_distill_target(const float* z_teacher, const float* z_t, cons
     distill_target_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(z_teacher, z_t, x_pred_teacher, logsnr, logsnr_s, i_times,
                                                                        x_target, eps_target, n);
     return gmk_check_launch("gmk_distill_target");
+}
+
+extern "C" int gmk_consistency_target(const float* v_tgt, const float* z_s, const float* x_pred_teacher, const float* z_t, const float* logsnr_t,
+                                      const float* logsnr_s, const int64_t* i_times, float* x_target, float* eps_target, int mean_type, int B,
+                                      int64_t n, void* stream) {
+    GMK_REQUIRE(v_tgt && z_s && x_pred_teacher && z_t && logsnr_t && logsnr_s && i_times && x_target && eps_target,
+                "gmk_consistency_target: null pointer");
+    GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_consistency_target: bad shape B=%d n=%lld", B, (long long)n);
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_consistency_target");
+    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(v_tgt) | reinterpret_cast<uintptr_t>(z_s) | reinterpret_cast<uintptr_t>(x_pred_teacher) |
+                                     reinterpret_cast<uintptr_t>(z_t) | reinterpret_cast<uintptr_t>(x_target) | reinterpret_cast<uintptr_t>(eps_target)) & 15) == 0;
+    if (vec) consistency_target_kernel<true><<<dim3(row_grid(n, 1024), B), 256, 0, gmk_stream(stream)>>>(v_tgt, z_s, x_pred_teacher, z_t, logsnr_t, logsnr_s, i_times, x_target, eps_target, n, mean_type);
+    else consistency_target_kernel<false><<<dim3(row_grid(n, 256), B), 256, 0, gmk_stream(stream)>>>(v_tgt, z_s, x_pred_teacher, z_t, logsnr_t, logsnr_s, i_times, x_target, eps_target, n, mean_type);
+    return gmk_check_launch("gmk_consistency_target");
 }
 
 // scalar prologue in double, as torch.optim.adam._single_tensor_adam does on the host, then the one launch of an Adam step

@@ -23,8 +23,8 @@ import os
 import torch
 
 from .. import checkpoint, common, ops, parallel
-from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, dyn_threshold_check, edit_start, loss_weight_check, restore_operator,
-                                 schedule_check, time_importance_check)
+from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, consistency_check, dyn_threshold_check, edit_start, loss_weight_check,
+                                 restore_operator, schedule_check, time_importance_check)
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -39,13 +39,15 @@ def make_plugin(GMBase, AttrDict):
         DG.hidden_size = 128
         DG.dropout = 0.0
         DG.sampler = "ddim"            # 'ddim' | 'noisy' | 'teacher_test' (reference) | 'dpmpp_2m' (extension: DPM-Solver++(2M), second order, no training)
+                                       # | 'consistency' (extension: multistep consistency sampling, for a net trained with teacher_mode 'consistency')
         DG.mean_type = "v"
         DG.eval_heavy = 1
         DG.class_cond = 1
         DG.sample_cond_w = -1.0
         DG.cf_drop_prob = 0.1
         DG.teacher_path = Path(".")
-        DG.teacher_mode = "step1"
+        DG.teacher_mode = "step1"        # 'step1' | 'step2' (reference: progressive distillation) | 'consistency' (extension: consistency distillation,
+                                       # Song et al. 2023, Algorithm 2: one training run for 1-4 step sampling; needs teacher_path)
         DG.lr_scheduler = "none"         # 'none' (reference: nothing reads it there) | 'cosine' (extension: FusedAdam.lr_at)
         # additions of the HIP path
         DG.compute_dtype = "bf16"      # 'bf16' (16-bit MFMA mode: bf16 gradients) or 'fp32' (exact-fp32 MFMA, 1e-3 parity mode)
@@ -100,6 +102,11 @@ def make_plugin(GMBase, AttrDict):
         DG.logsnr_shift = 0.0          # added to the log-SNR, |shift| <= 10: 2 log(32 / d) for d x d images (Hoogeboom et al. 2023), -1.386 at 64 x 64
         DG.sample_logsnr_schedule = "" # the curve the samplers walk (sample, evaluate, inpaint, edit, restore, encode / decode): '' the training one, else a
                                        # kind as above on the same range and shift ('uniform' is DPM-Solver++'s grid for few steps)
+        DG.consistency_grid = 0        # teacher_mode 'consistency': the number N >= 1 of training time points (0: timesteps), so that a run can train on
+                                       # a 256-point grid while --timesteps 2 --sampler consistency evaluates in two steps
+        DG.consistency_loss = "l2"     # teacher_mode 'consistency': 'l2' (the truncated-SNR loss of step2, against the consistency target) | 'huber'
+                                       # (pseudo-Huber on x, Song & Dhariwal 2023; gmk_x_loss_huber)
+        DG.consistency_huber_c = 0.00054  # its c, finite and > 0: the paper's 0.00054 sqrt(d) per dimension
         DG.image_size = 0              # S > 0: images are S x S (CIFAR-10: 32 with in_channels 3); 0: the reference's 28, or 32 with pad32
 
         def __init__(self, G):
@@ -121,6 +128,8 @@ def make_plugin(GMBase, AttrDict):
                     param.requires_grad = False
             else:
                 self.teacher_net = None
+            consistency, consistency_grid, consistency_loss, consistency_huber_c = consistency_check(
+                get("teacher_mode"), self.teacher_net is not None, get("consistency_grid"), get("consistency_loss"), get("consistency_huber_c"))
             self.nlogp_samples = int(get("nlogp_samples"))
             if self.nlogp_samples < 0:
                 raise ValueError(f"nlogp_samples = {self.nlogp_samples}: 0 (off) or the number of draws per image")
@@ -160,6 +169,12 @@ def make_plugin(GMBase, AttrDict):
                 raise ValueError("restore_eval / restore_gray with dyn_threshold: restoration together with dynamic thresholding is out of scope")
             self.binarize = int(get("binarize"))
             dyn_threshold = dyn_threshold_check(get("dyn_threshold"))
+            if get("sampler") == "consistency":
+                for name, on in (("dyn_threshold", dyn_threshold > 0), ("inpaint_eval", self.inpaint_eval > 0),
+                                 ("restore_eval / restore_gray", bool(self.restore_eval or self.restore_gray))):
+                    if on:
+                        raise ValueError(f"sampler = 'consistency' with {name}: multistep consistency sampling together with dynamic thresholding, "
+                                         f"inpainting or restoration is out of scope")
             loss_weight, loss_gamma, time_sampler = loss_weight_check(get("loss_weight"), get("loss_gamma"), get("time_sampler"),
                                                                       self.teacher_net is not None)
             time_importance, importance_decay, importance_warmup, importance_floor, loss_profile = time_importance_check(
@@ -178,16 +193,9 @@ def make_plugin(GMBase, AttrDict):
                 sample_schedule = None if sample_schedule == schedule else sample_schedule
                 schedule = None
             seed = int(get("seed")) * 1000 + parallel.rank()
-            self.diffusion = GaussianDiffusion(mean_type=get("mean_type"), num_steps=int(get("timesteps")),
-                                               sampler=get("sampler"), teacher_net=self.teacher_net,
-                                               teacher_mode=get("teacher_mode"), sample_cond_w=get("sample_cond_w"),
-                                               seed=seed, dyn_threshold=dyn_threshold, loss_weight=loss_weight, loss_gamma=loss_gamma,
-                                               time_sampler=time_sampler, time_importance=time_importance, importance_decay=importance_decay,
-                                               importance_warmup=importance_warmup, importance_floor=importance_floor, loss_profile=loss_profile,
-                                               schedule=schedule, sample_schedule=sample_schedule)
-            self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
             # EMA of the weights (an extension): a second SimpleUnet of the same arena layout, so one fused launch updates both.  It is seeded
-            # from `net` at the first optimiser step (after a data-parallel broadcast of the initial weights) or by a checkpoint load.
+            # from `net` at the first optimiser step (after a data-parallel broadcast of the initial weights) or by a checkpoint load; under
+            # teacher_mode 'consistency' it is also the method's target network and is seeded ahead of the first forward (`_seed_target`).
             self.ema_decay = float(get("ema_decay"))
             self.ema_net = None
             if self.ema_decay > 0:
@@ -196,6 +204,16 @@ def make_plugin(GMBase, AttrDict):
                 for param in self.ema_net.parameters():
                     param.requires_grad = False
                 self.ema_net.eval()
+            self.diffusion = GaussianDiffusion(mean_type=get("mean_type"), num_steps=int(get("timesteps")),
+                                               sampler=get("sampler"), teacher_net=self.teacher_net,
+                                               teacher_mode=get("teacher_mode"), sample_cond_w=get("sample_cond_w"),
+                                               seed=seed, dyn_threshold=dyn_threshold, loss_weight=loss_weight, loss_gamma=loss_gamma,
+                                               time_sampler=time_sampler, time_importance=time_importance, importance_decay=importance_decay,
+                                               importance_warmup=importance_warmup, importance_floor=importance_floor, loss_profile=loss_profile,
+                                               schedule=schedule, sample_schedule=sample_schedule,
+                                               target_net=self.ema_net if consistency else None, consistency_grid=consistency_grid,
+                                               consistency_loss=consistency_loss, consistency_huber_c=consistency_huber_c)
+            self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
             grad_clip, lr_min_ratio = float(get("grad_clip")), float(get("lr_min_ratio"))
             lr_warmup, lr_decay_steps = int(get("lr_warmup")), int(get("lr_decay_steps"))
             if not grad_clip >= 0.0:
@@ -295,6 +313,13 @@ def make_plugin(GMBase, AttrDict):
                 self.optimizer.seed_ema()
             return self.ema_net
 
+        def _seed_target(self):
+            """Consistency distillation's target network is the weight average: it has to hold the student's weights BEFORE the first target
+            forward, which comes ahead of the first optimiser step (where the average is seeded otherwise).  Called at the top of train_step
+            and loss(): after the constructor's teacher load, a weights_from load and a data-parallel broadcast of the initial weights."""
+            if self.diffusion.target_net is not None and not self.optimizer.ema_seeded:
+                self.optimizer.seed_ema()
+
         def _step_metrics(self, loss):
             """What train_step returns: the reference's two keys; with clipping or the guard on also `grad_norm` and `skipped_steps` (device
             scalars copied from the optimiser's state: no host sync), with a schedule on also `lr`."""
@@ -319,6 +344,7 @@ def make_plugin(GMBase, AttrDict):
         # -- training (diffusion_model.py:63-74)
         def train_step(self, x, y):
             self._check_image(x)
+            self._seed_target()
             B = x.shape[0]
             # classifier-free label drop (:67): mutates the caller's y in place like the reference, but the mask comes from the
             # device RNG inside one small kernel (the reference's CPU-generated mask forces a host sync every step)
@@ -401,6 +427,7 @@ def make_plugin(GMBase, AttrDict):
         # -- loss (:76-80): differentiable through torch.autograd; used by the driver's test-set pass
         def loss(self, x, y):
             self._check_image(x)
+            self._seed_target()
             metrics = self.diffusion.training_losses(net=partial(self.net, guide=y), x=x)
             metrics = {key: val.mean() for key, val in metrics.items()}
             if self.nlogp_samples > 0:              # the unconditional bound, nats/dim; the driver logs `nlogp` as eval/nlogp (gms/main.py:170-174)

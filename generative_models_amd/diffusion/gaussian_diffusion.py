@@ -26,6 +26,9 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
                                         between two latent codes (SDEdit, Meng et al. 2022; DDIM's interpolation, Song et al. 2021; extensions, no reference call site)
 * restoration (`restore`)               gmk_box_residual, then gmk_sampler_step_ns / gmk_dpm_solver_step_ns: DDNM's projection of x-hat onto the images that
                                         agree with a low-resolution and / or grey observation (Wang, Yu & Zhang 2023; an extension, no reference call site)
+* consistency distillation (`teacher_mode='consistency'`) and sampling (`sampler='consistency'`)  gmk_consistency_target (and, with
+                                        `consistency_loss='huber'`, gmk_x_loss_huber) for the training target, gmk_consistency_step for the multistep
+                                        sampler (Song et al. 2023, Algorithms 2 and 1; an extension, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -303,6 +306,42 @@ def time_importance_check(time_importance, importance_decay, importance_warmup, 
     return flags["time_importance"], decay, warmup, floor, flags["loss_profile"]
 
 
+TEACHER_MODES = ("step1", "step2", "consistency")
+CONSISTENCY_LOSSES = ("l2", "huber")
+
+
+def consistency_check(teacher_mode, has_teacher, consistency_grid=0, consistency_loss="l2", consistency_huber_c=0.00054):
+    """The consistency-distillation options (Song et al. 2023, Algorithm 2): teacher_mode 'consistency' needs a teacher (teacher_path);
+    consistency_grid N >= 0, the training discretisation (0: `timesteps`); consistency_loss 'l2' (the truncated-SNR loss of distillation step 2
+    against the consistency target) or 'huber' (pseudo-Huber on x, Song & Dhariwal 2023) with consistency_huber_c finite and > 0.  The grid and
+    'huber' belong to teacher_mode 'consistency' alone.  -> (on, int(grid), loss, float(c)), or ValueError naming the flags."""
+    on = teacher_mode == "consistency"
+    if on and not has_teacher:
+        raise ValueError("teacher_mode = 'consistency' without teacher_path: consistency distillation needs a frozen teacher")
+    try:
+        ok = not isinstance(consistency_grid, bool) and int(consistency_grid) == float(consistency_grid)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"consistency_grid = {consistency_grid!r}: 0 (timesteps) or the number of training time points N >= 1")
+    grid = int(consistency_grid)
+    if grid < 0:
+        raise ValueError(f"consistency_grid = {grid}: 0 (timesteps) or the number of training time points N >= 1")
+    if consistency_loss not in CONSISTENCY_LOSSES:
+        raise ValueError(f"consistency_loss = {consistency_loss!r}: one of {', '.join(CONSISTENCY_LOSSES)}")
+    try:
+        c = float(consistency_huber_c)
+    except (TypeError, ValueError):
+        raise ValueError(f"consistency_huber_c = {consistency_huber_c!r}: a finite number > 0") from None
+    if isinstance(consistency_huber_c, bool) or not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"consistency_huber_c = {consistency_huber_c!r}: a finite number > 0")
+    if not on and consistency_loss != "l2":
+        raise ValueError(f"consistency_loss = {consistency_loss!r} without teacher_mode = 'consistency': the loss of consistency distillation only")
+    if not on and grid > 0:
+        raise ValueError(f"consistency_grid = {grid} without teacher_mode = 'consistency': the time grid of consistency distillation only")
+    return on, grid, consistency_loss, c
+
+
 def profile_bin_edges(schedule=None):
     """The 64 bins of the loss profile on the host: (u_lo, u_hi, logsnr_hi, logsnr_lo), fp32 [64] each - bin k is [k / 64, (k + 1) / 64) in u,
     and its log-SNR range follows from the training schedule (a `Schedule`'s host, None: `logsnr_schedule_cosine_host`; the schedule falls, so
@@ -409,7 +448,8 @@ def restore_operator(shape, factor=1, gray=False):
 
 def sampler_plan(num_steps, sampler="ddim", resample=None, start=None, schedule=None):
     """One row per sampler iteration i = T-1 ... 0: the grid's (i, lt, ls), is_last, the network evaluations of the step (`resample`: the
-    inpainting loop's, None outside it) and the step's DpmCoef (sampler 'dpmpp_2m') / InpaintCoef (inpainting) rows, else None.  The loop
+    inpainting loop's, None outside it) and the step's DpmCoef (sampler 'dpmpp_2m') / InpaintCoef (inpainting) rows, else None ('consistency':
+    DDIM's rows - gmk_consistency_step forms its two coefficients from ls itself).  The loop
     reserves its Philox counters and every chunk spends them by walking the same plan.  start = k (`sampler_start`): a chain that begins
     part-way, from z at plan[0].lt = logsnr(k / T) - the rows i = k-1 ... 0 of the same grid (None: all T of them).  schedule: `sampler_grid`'s."""
     k = sampler_start(start, num_steps)
@@ -579,10 +619,29 @@ class _XLossW(torch.autograd.Function):
         return out, None, None, None, None, None, None
 
 
+class _XLossHuber(torch.autograd.Function):
+    """(loss_b, x_mse) of `ops.x_loss_huber`, loss_b = sqrt(x_mse + c^2) - c differentiable w.r.t. v; x_mse is a reported number only."""
+
+    @staticmethod
+    def forward(ctx, v, z, x, logsnr, c, mean_type="v"):
+        loss_b, x_mse, dv = ops.x_loss_huber(v.contiguous(), z, x, logsnr, c, grad_scale=1.0, mean_type=mean_type)
+        ctx.save_for_backward(dv)
+        ctx.mark_non_differentiable(x_mse)
+        return loss_b, x_mse
+
+    @staticmethod
+    def backward(ctx, g, _g_x_mse):
+        (dv,) = ctx.saved_tensors
+        B = dv.shape[0]
+        out = ops.scale_rows(dv.view(B, -1), g.contiguous().float()).view_as(dv)
+        return out, None, None, None, None, None
+
+
 class GaussianDiffusion:
     def __init__(self, *, mean_type, num_steps, teacher_net=None, teacher_mode=None, sampler="ddim", sample_cond_w=None,
                  seed=0, dyn_threshold=0.0, loss_weight="snr_trunc", loss_gamma=5.0, time_sampler="uniform", time_importance=0,
-                 importance_decay=0.9, importance_warmup=5, importance_floor=0.01, loss_profile=0, schedule=None, sample_schedule=None):
+                 importance_decay=0.9, importance_warmup=5, importance_floor=0.01, loss_profile=0, schedule=None, sample_schedule=None,
+                 target_net=None, consistency_grid=0, consistency_loss="l2", consistency_huber_c=0.00054):
         if mean_type not in ops.MEAN_TYPES:                     # :70-71
             raise NotImplementedError(mean_type)
         # the noise schedule (`Schedule`; the reference's registry, diffusion_utils.py:228-239, of which it picks 'cosine', -20, 20 at :33-34):
@@ -610,11 +669,19 @@ class GaussianDiffusion:
         # how a batch's times are drawn (`loss_weight_check`); `loss_weight` is the caller's choice, `loss_weight_type` what a step applies
         self.loss_weight, self.loss_gamma, self.time_sampler = loss_weight_check(loss_weight, loss_gamma, time_sampler, teacher_net is not None)
         self.loss_weight_type = self.loss_weight
+        # consistency distillation (`consistency_check`; an extension): a third teacher mode beside the reference's two.  `target_net` is the
+        # method's target network (the weight average; None: the student itself under stop-gradient), `train_grid` the N of its time grid
+        self.consistency, grid, self.consistency_loss, self.consistency_huber_c = consistency_check(
+            teacher_mode, teacher_net is not None, consistency_grid, consistency_loss, consistency_huber_c)
+        self.target_net = target_net if self.consistency else None
+        self.train_grid = grid if grid > 0 else num_steps
         if self.teacher_net is not None:                      # :39-43
-            assert teacher_mode in ["step1", "step2"]
+            assert teacher_mode in TEACHER_MODES
             self.teacher_mode = teacher_mode
             if self.teacher_mode == "step1":
                 self.loss_weight_type = "snr"
+            if self.consistency and self.consistency_loss == "huber":
+                self.loss_weight_type = "huber"
         # the loss profile (extensions, off by default; `time_importance_check`): with either flag the fused train pass keeps `time_profile`, the
         # fp32 [5, 64] device state of gmk_loss_profile over its own (u, loss_b, x_mse), and with `time_importance` it draws its times from it
         # (gmk_u_importance); with `loss_profile` the test pass (`training_losses`) sums into a state of its own.  Allocated on first use, zeros.
@@ -692,6 +759,13 @@ class GaussianDiffusion:
         v2 = t.forward_hip(torch.cat([z, z]), torch.cat([logsnr, logsnr]), torch.cat([guide, -torch.ones_like(guide)]), None)
         return v2[:B], v2[B:]
 
+    def _target_eval(self, module, z, logsnr, guide, cond_w_net):
+        """The target network's forward of consistency distillation (no grad, never with dropout): `target_net`, or without one the student
+        `module` itself under stop-gradient - no ctx, and with dropout off its counter does not move, so the student's own pass sees nothing of it."""
+        target = module if self.target_net is None else self.target_net
+        with _EvalForward(target):
+            return target.forward_hip(z, logsnr, guide, cond_w_net)
+
     def draw_u(self, B, dev):
         """The continuous times of one batch from self.rng, fp32 [B] in [0, 1): 'uniform' B independent draws (:94); 'stratified' ONE draw
         (one Philox counter) expanded to u0 + b / B mod 1 by gmk_u_stratified.  `_prepare` and the graphed train step both draw here."""
@@ -735,11 +809,13 @@ class GaussianDiffusion:
         if eps is None:
             eps = self.rng.normal(x.shape, dev)                                   # :83
         eps = ops.aligned(eps.float())
-        if distill and self.teacher_mode == "step2":                              # :87-91 discrete time
+        # the discretisation of the discrete-time modes: `timesteps`, or consistency distillation's own grid
+        T = self.train_grid if self.consistency else self.num_steps
+        if distill and self.teacher_mode in ("step2", "consistency"):             # :87-91 discrete time
             if i_times is None:
-                i_times = (self.rng.uniform((B,), dev) * self.num_steps).long().clamp_(max=self.num_steps - 1)
+                i_times = (self.rng.uniform((B,), dev) * T).long().clamp_(max=T - 1)
             i_times = ops.aligned(i_times.long())
-            _, u = ops.logsnr_schedule(B, dev, i_times=i_times, num_steps=self.num_steps, want_u=True, schedule=self.schedule)
+            _, u = ops.logsnr_schedule(B, dev, i_times=i_times, num_steps=T, want_u=True, schedule=self.schedule)
         else:
             if u is None:
                 u = self.draw_u(B, dev)                                           # :94 continuous time
@@ -751,11 +827,17 @@ class GaussianDiffusion:
             cond_w = 4.0 * self.rng.uniform((B,), dev)                            # :107
         cond_w = ops.aligned(cond_w.float())
         with torch.no_grad():
-            logsnr_s = ops.logsnr_schedule(B, dev, u=u, shift=1.0 / self.num_steps, schedule=self.schedule)      # :118-119
+            logsnr_s = ops.logsnr_schedule(B, dev, u=u, shift=1.0 / T, schedule=self.schedule)      # :118-119
             if self.teacher_mode == "step1":                                      # :121-126 one guided teacher step
                 v, vu = self._teacher_eval(z_t, logsnr, guide, None, guided=True)
                 _, x_target, eps_target = ops.ddim_step_vec(v, z_t, logsnr, logsnr_s, v_uncond=vu, cond_w=cond_w, mean_type=self.mean_type)
                 loss_type = 1
+            elif self.consistency:          # Song et al. 2023, Algorithm 2: one teacher step t -> s, then the target net at (z_s, s)
+                v_t, _ = self._teacher_eval(z_t, logsnr, guide, cond_w, guided=False)
+                z_s, x_pred_teacher, _ = ops.ddim_step_vec(v_t, z_t, logsnr, logsnr_s, mean_type=self.mean_type)
+                v_tgt = self._target_eval(module, z_s, logsnr_s, guide, cond_w)
+                x_target, eps_target = ops.consistency_target(v_tgt, z_s, x_pred_teacher, z_t, logsnr, logsnr_s, i_times, mean_type=self.mean_type)
+                loss_type = 0
             else:                                                                 # :128-154 two w-conditioned teacher steps
                 logsnr_mid = ops.logsnr_schedule(B, dev, u=u, shift=0.5 / self.num_steps, schedule=self.schedule)
                 v1, _ = self._teacher_eval(z_t, logsnr, guide, cond_w, guided=False)
@@ -783,6 +865,13 @@ class GaussianDiffusion:
             """loss_profile: the batch into the test profile at decay 1 (plain sums; x_mse where the branch has it)."""
             if self.loss_profile:
                 ops.loss_profile(u, loss.detach(), x_mse, self.profile_state("test", u.device), 1.0)
+        if self.loss_weight_type == "huber":                      # consistency distillation's pseudo-Huber loss on x
+            if grad:
+                loss, x_mse = _XLossHuber.apply(v, z_t, x_t, logsnr, self.consistency_huber_c, self.mean_type)
+            else:
+                loss, x_mse, _ = ops.x_loss_huber(v, z_t, x_t, logsnr, self.consistency_huber_c, mean_type=self.mean_type)
+            note(loss, x_mse)
+            return {"loss": loss, "x_mse": x_mse}
         if self.loss_weight_type in ops.X_LOSS_WEIGHTS:           # 'snr_plus1' / 'min_snr': w(logsnr) x_mse, no eps anywhere
             if grad:
                 loss, x_mse = _XLossW.apply(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, self.mean_type)
@@ -816,7 +905,10 @@ class GaussianDiffusion:
         module, guide, w, z_t, logsnr, x_t, eps_t, loss_type = self._prepare(net, x, u, eps, i_times, cond_w)
         ctx = {}
         v = module.forward_hip(z_t, logsnr, guide, w, ctx=ctx)
-        if self.loss_weight_type in ops.X_LOSS_WEIGHTS:
+        if self.loss_weight_type == "huber":
+            loss_b, x_mse, dv = ops.x_loss_huber(v, z_t, x_t, logsnr, self.consistency_huber_c, grad_scale=grad_scale, mean_type=self.mean_type)
+            out = {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
+        elif self.loss_weight_type in ops.X_LOSS_WEIGHTS:
             loss_b, x_mse, dv = ops.x_loss_w(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, grad_scale=grad_scale, mean_type=self.mean_type)
             out = {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
         else:
@@ -1130,8 +1222,16 @@ class GaussianDiffusion:
         dev = init_x.device
         if cond_w is not None and net_cond_w is None:
             net_cond_w = 4.0 * self.rng.uniform((B,), dev)           # :247-251
-        if self.sampler not in ("ddim", "noisy", "teacher_test", "dpmpp_2m"):
+        if self.sampler not in ("ddim", "noisy", "teacher_test", "dpmpp_2m", "consistency"):
             raise NotImplementedError(self.sampler)
+        if self.sampler == "consistency":       # multistep consistency sampling: fresh noise at every step but the last, drawn in the update kernel
+            for what, on in (("inpainting", inp is not None), ("restoration", rst is not None), ("dyn_threshold", bool(self.dyn_threshold))):
+                if on:
+                    raise ValueError(f"sampler 'consistency' together with {what} is out of scope")
+            if noises is not None:
+                raise ValueError("sampler 'consistency' draws its noise in the update kernel (self.rng's Philox stream): noises cannot be injected")
+            if int(np.prod(init_x.shape[1:])) % 4:
+                raise ValueError(f"sampler 'consistency': {int(np.prod(init_x.shape[1:]))} values per image, a multiple of 4 is required")
         student_w, w, use_teacher = resolve_guidance(sample_cond_w=self.sample_cond_w, net_cond_w=net_cond_w, kw_cond_w=kw_cond_w,
                                                      has_teacher=self.teacher_net is not None, sampler=self.sampler)
         if use_teacher:
@@ -1187,7 +1287,7 @@ class GaussianDiffusion:
             return outs
         for step in plan:
             for _ in range(step.passes):
-                if self.sampler == "noisy" and noises is None:
+                if self.sampler in ("noisy", "consistency") and noises is None:
                     offs.append(self.rng._take(B * n1))
                 if inp is not None:
                     inp.moffs.append(inp.rng._take(2 * B * n1))     # eps1 and eps2 of one merge, used or not
@@ -1250,7 +1350,10 @@ class GaussianDiffusion:
                 # restoration: one residual launch per network evaluation (per image, so a half-batch gives the whole batch's bits)
                 ns = None if rst is None else (ops.box_residual(v, z_t, rst.obs, lt, rst.cf, rst.N, v_uncond=vu, cond_w=w, mean_type=self.mean_type),
                                                rst.cf, rst.N)
-                if dpm is not None:
+                if self.sampler == "consistency":
+                    z_t, xp, ep = ops.consistency_step(v, z_t, lt, ls, step.is_last, self.rng.seed, offs[f], q0=q0, v_uncond=vu, cond_w=w,
+                                                       want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
+                elif dpm is not None:
                     z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, dpm.coef_z, dpm.coef_x, dpm.coef_prev, step.is_last, v_uncond=vu, cond_w=w,
                                                       want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr, ns=ns)
                 else:

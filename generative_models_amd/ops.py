@@ -1410,6 +1410,90 @@ def distill_target(z_teacher, z_t, x_pred_teacher, logsnr, logsnr_s, i_times):
     return xt, et
 
 
+# ---- consistency distillation and multistep consistency sampling (extensions; Song et al. 2023, "Consistency Models") ------------------
+def _images(tensors, vectors=(), what="consistency"):
+    """tensors: (tensor, name) pairs of one fp32 image shape [B, ...]; vectors: (tensor, name, dtype) triples of B values each; all contiguous
+    device tensors (named for what is wrong before anything is launched).  -> (B, values per image)"""
+    shape = tuple(tensors[0][0].shape)
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f"{what}: {tensors[0][1]} has shape {shape}, expected [B, ...] with B and every image dimension > 0")
+    for t, nm in tensors:
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{nm}: shape {tuple(t.shape)}, expected {shape}")
+    for t, nm, dtype in vectors:
+        if t.dim() != 1 or t.numel() != shape[0]:
+            raise ValueError(f"{nm}: shape {tuple(t.shape)}, expected ({shape[0]},)")
+    for t, nm, dtype in tuple((t, nm, torch.float32) for t, nm in tensors) + tuple(vectors):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == dtype):
+            raise ValueError(f"{nm}: expected a contiguous {dtype} device tensor")
+    return shape[0], math.prod(shape[1:])
+
+
+def consistency_target(v_tgt, z_s, x_pred_teacher, z_t, logsnr_t, logsnr_s, i_times, mean_type="v"):
+    """The target of consistency distillation (gmk_consistency_target; Song et al. 2023, Algorithm 2): x_target = the clipped data prediction
+    of the target network's output v_tgt at (z_s, logsnr_s) - `ddim_step_vec`'s x_pred, bit for bit - with the i_times == 0 rows taking
+    x_pred_teacher (the boundary condition), and eps_target = eps_from_x(z_t, x_target, logsnr_t), `distill_target`'s closing expression.
+    Images: fp32 [B, ...], contiguous (16-byte aligned tensors with n % 4 == 0 take the 16-byte path, anything else the scalar one);
+    logsnr_t, logsnr_s: fp32 [B]; i_times: int64 [B].  -> (x_target, eps_target)"""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    B, n = _images(((z_t, "z_t"), (v_tgt, "v_tgt"), (z_s, "z_s"), (x_pred_teacher, "x_pred_teacher")),
+                   ((logsnr_t, "logsnr_t", torch.float32), (logsnr_s, "logsnr_s", torch.float32), (i_times, "i_times", torch.int64)),
+                   "consistency_target")
+    if B >= 65536:
+        raise ValueError(f"consistency_target: B = {B}, need < 65536")
+    xt, et = torch.empty_like(z_t), torch.empty_like(z_t)
+    check(lib.gmk_consistency_target(_p(v_tgt), _p(z_s), _p(x_pred_teacher), _p(z_t), _p(logsnr_t), _p(logsnr_s), _p(i_times), _p(xt), _p(et),
+                                     MEAN_TYPES[mean_type], B, n, _s()), "consistency_target")
+    return xt, et
+
+
+def x_loss_huber(v, z, x, logsnr, c, grad_scale=None, mean_type="v"):
+    """Pseudo-Huber x-space loss (gmk_x_loss_huber; Song & Dhariwal 2023; an extension): loss_b = sqrt(x_mse + c^2) - c, x_mse = mean (x_hat - x)^2
+    of the clipped prediction - the bits of `x_loss_w`'s x_mse.  c = c_paper / sqrt(n), finite and > 0.  Tensors as in `x_loss_w`.
+    -> (loss_b, x_mse, dv or None), dv = d(grad_scale sum_b loss_b)/dv when grad_scale is given."""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    c = float(c)
+    if not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"c = {c}: need a finite value > 0")
+    B, n = _images(((x, "x"), (v, "v"), (z, "z")), ((logsnr, "logsnr", torch.float32),), "x_loss_huber")
+    loss_b = torch.empty((B,), device=x.device, dtype=torch.float32)
+    xm = torch.empty_like(loss_b)
+    dv = torch.empty_like(v) if grad_scale is not None else None
+    check(lib.gmk_x_loss_huber(_p(v), _p(z), _p(x), _p(logsnr), _p(loss_b), _p(xm), _p(dv), float(grad_scale or 0.0), c, MEAN_TYPES[mean_type],
+                               B, n, _s()), "x_loss_huber")
+    return loss_b, xm, dv
+
+
+def consistency_step(v, z, logsnr_t, logsnr_s, is_last, seed, offset, q0=0, v_uncond=None, cond_w=None, want_pred=False, mean_type="v",
+                     dup=False, logsnr_next=None):
+    """One step of multistep consistency sampling (gmk_consistency_step; Song et al. 2023, Algorithm 1): x-hat as `sampler_step` forms it
+    (guidance included), z_next = x-hat when is_last, else alpha_s x-hat + sigma_s eps with eps the Philox normals of
+    gmk_rng_normal(seed, offset + q0), drawn in the kernel: q0 = a n / 4 places a chunk that starts at row a of a batch.  n % 4 == 0.
+    Arguments and returns otherwise as `sampler_step`."""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    shape = tuple(z.shape)
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f"z: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
+    if math.prod(shape[1:]) % 4:
+        raise ValueError(f"z: {math.prod(shape[1:])} values per image, a multiple of 4 is required")
+    if not (math.isfinite(float(logsnr_t)) and math.isfinite(float(logsnr_s))):
+        raise ValueError(f"consistency_step: non-finite time ({logsnr_t}, {logsnr_s})")
+    seed, offset = check_stream(seed, offset)
+    q0 = int(q0)
+    if not 0 <= q0 < 1 << 64:
+        raise ValueError(f"q0 = {q0}: an unsigned 64-bit Philox counter offset")
+    if (v_uncond is None) != (cond_w is None):
+        raise ValueError("consistency_step: v_uncond and cond_w go together")
+    B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((v_uncond, "v_uncond"),), cond_w, want_pred, dup, logsnr_next)
+    check(lib.gmk_consistency_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), float(logsnr_t), float(logsnr_s), int(bool(is_last)), seed, offset, q0,
+                                   _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()),
+          "consistency_step")
+    return ((z_next, z2) if dup else z_next), xp, ep
+
+
 def _adam_arenas(p, g, m, v, ema=None):
     """The tensor checks of the three Adam ops: fp32 device arenas of one size (ema when given)."""
     arenas = ((p, "p"), (g, "g"), (m, "m"), (v, "v")) + (() if ema is None else ((ema, "ema"),))

@@ -614,6 +614,41 @@ int gmk_distill_target(const float* z_teacher, const float* z_t, const float* x_
                        const float* logsnr_s, const int64_t* i_times, float* x_target, float* eps_target, int B, int64_t n,
                        void* stream);
 
+/* ---- consistency distillation and multistep consistency sampling (Song, Dhariwal, Chen & Sutskever 2023, "Consistency Models", Algorithms 2
+ * and 1); extensions, no reference call site.  alpha(l) = sqrt(sigmoid(l)), sigma(l) = sqrt(sigmoid(-l)); x_hat(out, z, l) is the CLIPPED data
+ * prediction of gmk_sampler_step / gmk_v_loss for the three mean_types; eps_from_x(z, x, l) = (z - alpha x) / sigma in gmk_distill_target's form
+ * sqrt(1 + e^l) (z - x / sqrt(1 + e^-l)).  All three work on fp32 images as flat [B][n], without floating-point atomics (the same call gives
+ * the same bits); no row of GMK_KERNEL_TABLE: they carry no profile label.
+ *   gmk_consistency_target: the distillation target of one batch.  z_s = the teacher's DDIM step from z_t (gmk_ddim_step_vec), x_pred_teacher its
+ *     x_pred, v_tgt the target network's output at (z_s, logsnr_s):
+ *       x_target[b] = i_times[b] == 0 ? x_pred_teacher[b] : x_hat(v_tgt[b], z_s[b], logsnr_s[b])
+ *       eps_target[b] = eps_from_x(z_t[b], x_target[b], logsnr_t[b])
+ *     The i == 0 rows are the boundary condition f(., t_min) = identity on the teacher's final prediction (v_tgt and z_s are not read there).
+ *     x_hat is the device function behind gmk_ddim_step_vec's x_pred, eps_target the expression gmk_distill_target ends with: their bits.
+ *     Any n: 16-byte accesses when n % 4 == 0 and the six image tensors are 16-byte aligned, else element by element.  B < 65536.
+ *   gmk_x_loss_huber: the pseudo-Huber metric of Song & Dhariwal 2023, "Improved Techniques for Training Consistency Models", on x_hat:
+ *       m_b = mean_j (x_hat_j - x_j)^2, loss_b[b] = sqrt(m_b + c^2) - c, x_mse[b] = m_b
+ *     - the paper's sqrt(|d|^2 + c_paper^2) - c_paper with c_paper = c sqrt(n), scaled by 1 / sqrt(n) (its default 0.00054 sqrt(n) is c = 0.00054).
+ *     dv (optional) = d(grad_scale sum_b loss_b)/dv: dv_j = grad_scale (x_hat_j - x_j) / (n sqrt(m_b + c^2)) dx_hat/dout where the raw prediction
+ *     lies in [-1, 1] (ends included), else 0 - gmk_v_loss's clip rule.  gmk_x_loss_w's kernel, instantiated once more: one workgroup per image,
+ *     residuals in LDS up to GMK_X_LOSS_KEEP values (larger images are read again), the same 16-byte / scalar rule, and x_mse carries the bits
+ *     gmk_x_loss_w writes for the same inputs.  c: finite, > 0.  loss_b, x_mse: fp32 [B], both required.
+ *   gmk_consistency_step: one step t -> s of multistep consistency sampling on the samplers' grid.  x_hat / eps_hat exactly as gmk_sampler_step
+ *     forms them (v_uncond / cond_w: classifier-free guidance), then
+ *       z_next = is_last ? x_hat : fadd(fmul(alpha_s, x_hat), fmul(sigma_s, eps))     (nothing contracted)
+ *     alpha_s, sigma_s computed by the entry in double from the fp32 logsnr_s and rounded to fp32.  eps are Philox normals drawn in the kernel
+ *     and never stored: element j of this chunk is element j of gmk_rng_normal(seed, offset + q0) - so rows [a, b) of a batch called with
+ *     q0 = a n / 4 draw exactly what the whole batch would (gmk_inpaint_merge's convention).  Nothing is drawn when is_last.  n % 4 == 0.
+ *     x_pred / eps_pred / z_dup / logsnr_next: gmk_sampler_step's conventions. */
+int gmk_consistency_target(const float* v_tgt, const float* z_s, const float* x_pred_teacher, const float* z_t, const float* logsnr_t,
+                           const float* logsnr_s, const int64_t* i_times, float* x_target, float* eps_target, int mean_type, int B, int64_t n,
+                           void* stream);
+int gmk_x_loss_huber(const float* v, const float* z, const float* x, const float* logsnr, float* loss_b, float* x_mse, float* dv,
+                     float grad_scale, float c, int mean_type, int B, int64_t n, void* stream);
+int gmk_consistency_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float logsnr_t, float logsnr_s, int is_last,
+                         uint64_t seed, uint64_t offset, uint64_t q0, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
+                         float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+
 /* ---- optimiser (torch.optim.Adam defaults as diffusion_model.py:56 uses it), flat fp32 arena ------------- */
 int gmk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, int step, float grad_scale, void* stream);
