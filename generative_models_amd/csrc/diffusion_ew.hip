@@ -13,6 +13,9 @@
 // gmk_box_mean / gmk_box_residual / gmk_sampler_step_ns / gmk_dpm_solver_step_ns (DDNM's range-null-space projection of x-hat for box-mean
 // operators: Wang, Yu & Zhang 2023) are extensions too.  gmk_consistency_target / gmk_x_loss_huber / gmk_consistency_step (consistency distillation and
 // multistep consistency sampling: Song et al. 2023, Algorithms 1 and 2; the pseudo-Huber metric of Song & Dhariwal 2023) are extensions as well.
+// gmk_cfg_rescale (the rescale factor of classifier-free guidance: Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are
+// Flawed", section 3.4; the samplers apply it inside the guidance interval of Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval
+// Improves Sample and Distribution Quality in Diffusion Models") is an extension, no reference call site.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -1284,6 +1287,122 @@ __global__ __launch_bounds__(256) void slerp_kernel(const float* __restrict__ a,
     }
 }
 
+// ---- the rescale factor of classifier-free guidance (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", section
+// 3.4), which the samplers apply on the steps inside the guidance interval (Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval
+// Improves Sample and Distribution Quality in Diffusion Models"); an extension, no reference call site.  Per image b, in fp32, with
+// x_c = x_raw_from_out(unguided) and x_raw = x_raw_from_out(guided, w_b) - dyn_threshold_kernel's device function, hence its bits, no clip:
+//   m_c = (sum x_c) / n, m_r = (sum x_raw) / n;  q_c = sum (x_c - m_c)^2, q_r = sum (x_raw - m_r)^2      (two passes, centred squares)
+//   ratio = sqrtf(q_c / q_r) = std(x_c) / std(x_raw);  f = fadd(1, fmul(phi, fsub(ratio, 1)));  thr = 1 / f (a true division)
+//   thr = 1 where q_r == 0, f is not finite or f <= 0.
+// threshold_x(x, thr) = clamp(x, -thr, thr) / thr = clip(f x, -1, 1) for f > 0, so the _dt update kernels called with this thr are the rescaled update.
+// One workgroup of 256 threads per image.  Every one of the four sums is accumulated with ONE element-to-thread assignment and order: thread t
+// takes the elements t, t + 256, ... ascending (a plain add for the means, d d + q as fmaf for the squares), then block_sum: per chain
+// ceil(n / 256) additions + 6 (wave_sum) + 2.  No floating-point atomics, a fixed order: the same call gives the same bits, a row depends on its
+// own image alone, and w_b = 0 (x_raw = 1 x_c + (-0) x_u: x_c's value) gives q_r == q_c bit for bit, hence ratio = 1, f = 1, thr = 1 exactly.
+// VEC: the loads are 16 bytes wide - thread t forms x_c and x_raw of the elements 4t .. 4t + 3 of a chunk of 1024 and stores them to LDS (8 KiB
+// of staging), then reads the chunk's elements t + 256 k (k < 4) back: the assignment above.  Without VEC thread t loads those elements itself.
+// KEEP: the image has at most kRescaleKeep = 12 x 1024 values and both predictions stay in registers between the passes (48 + 48 values per
+// thread), so v, v_uncond and z come from HBM once: 12 n bytes per image.  Without KEEP any n: the second pass forms them again (24 n bytes).
+constexpr int kRescaleKeep = GMK_CFG_RESCALE_KEEP;    // kDynKeys, kXLossKeep, kSlerpKeep: covers 3 x 64 x 64
+static_assert(kRescaleKeep % 1024 == 0, "whole chunks of 1024");
+
+template <bool VEC, bool KEEP>
+__global__ __launch_bounds__(256) void cfg_rescale_kernel(const float* __restrict__ v, const float* __restrict__ vu,
+                                                         const float* __restrict__ cond_w, const float* __restrict__ z, float lt, float phi,
+                                                         float* __restrict__ thr_out, float* __restrict__ ratio_out, int64_t n, int mt) {
+    __shared__ __attribute__((aligned(16))) float stage_c[1024];
+    __shared__ __attribute__((aligned(16))) float stage_r[1024];
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const LogsnrCoef c = logsnr_coef(lt);
+    const float w = cond_w[b];
+    const int64_t base = (int64_t)b * n;
+    constexpr int CH = KEEP ? kRescaleKeep / 1024 : 1;
+    float xc[CH][4], xr[CH][4];
+    // x_c and x_raw of the elements c0 + tid + 256 k (k < 4) of the image; an entry whose element lies beyond n is not written (or holds stale
+    // LDS) and is never read.  c0 < n is the same in every thread, so the barriers are reached by all of them.
+    auto chunk = [&](int64_t c0, float (&oc)[4], float (&orw)[4]) {
+        if constexpr (VEC) {
+            __syncthreads();             // the staging's last values have been read
+            const int64_t i = c0 + tid * 4;
+            if (i < n) {                 // n % 4 == 0: the whole group lies inside the image
+                float ov[4], uv[4], zv[4], a[4], r[4];
+                load4(v + base + i, ov);
+                load4(vu + base + i, uv);
+                load4(z + base + i, zv);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    a[k] = x_raw_from_out(ov[k], 0.f, false, w, zv[k], c, mt);
+                    r[k] = x_raw_from_out(ov[k], uv[k], true, w, zv[k], c, mt);
+                }
+                store4(stage_c + tid * 4, a);
+                store4(stage_r + tid * 4, r);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                oc[k] = stage_c[tid + 256 * k];
+                orw[k] = stage_r[tid + 256 * k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = c0 + tid + 256 * k;
+                if (i < n) {
+                    const float o = v[base + i], zz = z[base + i];
+                    oc[k] = x_raw_from_out(o, 0.f, false, w, zz, c, mt);
+                    orw[k] = x_raw_from_out(o, vu[base + i], true, w, zz, c, mt);
+                }
+            }
+        }
+    };
+    // f(x_c, x_raw) for every element of this thread, in ascending order; `load`: form the chunk (else: it is in the registers)
+    auto for_elements = [&](bool load, auto&& f) {
+        if constexpr (KEEP) {
+#pragma unroll
+            for (int ch = 0; ch < CH; ++ch) {
+                const int64_t c0 = (int64_t)ch * 1024;
+                if (c0 < n) {
+                    if (load) chunk(c0, xc[ch], xr[ch]);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (c0 + tid + 256 * k < n) f(xc[ch][k], xr[ch][k]);
+                }
+            }
+        } else {
+            for (int64_t c0 = 0; c0 < n; c0 += 1024) {
+                chunk(c0, xc[0], xr[0]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (c0 + tid + 256 * k < n) f(xc[0][k], xr[0][k]);
+            }
+        }
+    };
+    float sc = 0.f, sr = 0.f;
+    for_elements(true, [&](float a, float r) {
+        sc = __fadd_rn(sc, a);
+        sr = __fadd_rn(sr, r);
+    });
+    sc = block_sum(sc, red);
+    sr = block_sum(sr, red);
+    const float mc = __fdiv_rn(sc, (float)n), mr = __fdiv_rn(sr, (float)n);
+    float qc = 0.f, qr = 0.f;
+    for_elements(!KEEP, [&](float a, float r) {
+        const float dc = __fsub_rn(a, mc), dr = __fsub_rn(r, mr);
+        qc = fmaf(dc, dc, qc);
+        qr = fmaf(dr, dr, qr);
+    });
+    qc = block_sum(qc, red);
+    qr = block_sum(qr, red);
+    if (tid == 0) {
+        const float ratio = sqrtf(__fdiv_rn(qc, qr));
+        const float f = __fadd_rn(1.0f, __fmul_rn(phi, __fsub_rn(ratio, 1.0f)));
+        thr_out[b] = (qr == 0.0f || !isfinite(f) || f <= 0.0f) ? 1.0f : __fdiv_rn(1.0f, f);
+        if (ratio_out) ratio_out[b] = ratio;
+    }
+}
+
 // blocks per row of a (gx, B) grid whose blocks take `per_block` elements per pass: enough for the row, at most 64
 int row_grid(int64_t n, int per_block) {
     const int64_t g = (n + per_block - 1) / per_block;
@@ -1857,4 +1976,22 @@ extern "C" int gmk_slerp(const float* a, const float* b, const float* t, float* 
     if (n <= kSlerpKeep) slerp_kernel<kSlerpKeep / 1024><<<B, 256, 0, st>>>(a, b, t, out, cos_out, B, n, K);
     else slerp_kernel<0><<<B, 256, 0, st>>>(a, b, t, out, cos_out, B, n, K);
     return gmk_check_launch("gmk_slerp");
+}
+
+extern "C" int gmk_cfg_rescale(const float* v, const float* v_uncond, const float* cond_w, const float* z, float logsnr_t, float phi,
+                               float* thr_out, float* ratio_out, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && v_uncond && cond_w && z && thr_out, "gmk_cfg_rescale: null pointer (v, v_uncond, cond_w, z and thr_out are required)");
+    GMK_REQUIRE(isfinite(phi) && phi >= 0.0f && phi <= 1.0f, "gmk_cfg_rescale: phi = %g outside [0, 1]", (double)phi);
+    GMK_REQUIRE(mean_type >= GMK_MEAN_V && mean_type <= GMK_MEAN_X, "gmk_cfg_rescale: mean_type must be 0 (v), 1 (eps) or 2 (x)");
+    GMK_REQUIRE(B >= 1 && n >= 1, "gmk_cfg_rescale: bad shape B=%d n=%lld (B, n >= 1 required)", B, (long long)n);
+    GMK_REQUIRE(isfinite(logsnr_t), "gmk_cfg_rescale: non-finite time");
+    const bool vec = n % 4 == 0 &&
+        ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(v_uncond) | reinterpret_cast<uintptr_t>(z)) & 15) == 0;
+    const bool keep = n <= kRescaleKeep;
+    hipStream_t st = gmk_stream(stream);
+    if (vec && keep) cfg_rescale_kernel<true, true><<<B, 256, 0, st>>>(v, v_uncond, cond_w, z, logsnr_t, phi, thr_out, ratio_out, n, mean_type);
+    else if (vec) cfg_rescale_kernel<true, false><<<B, 256, 0, st>>>(v, v_uncond, cond_w, z, logsnr_t, phi, thr_out, ratio_out, n, mean_type);
+    else if (keep) cfg_rescale_kernel<false, true><<<B, 256, 0, st>>>(v, v_uncond, cond_w, z, logsnr_t, phi, thr_out, ratio_out, n, mean_type);
+    else cfg_rescale_kernel<false, false><<<B, 256, 0, st>>>(v, v_uncond, cond_w, z, logsnr_t, phi, thr_out, ratio_out, n, mean_type);
+    return gmk_check_launch("gmk_cfg_rescale");
 }

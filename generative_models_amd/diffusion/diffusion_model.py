@@ -23,8 +23,8 @@ import os
 import torch
 
 from .. import checkpoint, common, ops, parallel
-from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, consistency_check, dyn_threshold_check, edit_start, loss_weight_check,
-                                 restore_operator, schedule_check, time_importance_check)
+from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, consistency_check, dyn_threshold_check, edit_start, guidance_check,
+                                 loss_weight_check, restore_operator, schedule_check, time_importance_check)
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -75,6 +75,12 @@ def make_plugin(GMBase, AttrDict):
         DG.restore_gray = 0            # 1: that restoration also (or, with restore_eval = 0, only) starts from the channel mean (colourisation)
         DG.dyn_threshold = 0.0         # p in (0, 1]: sample() / evaluate() / inpaint() clamp each image's x-hat to its own p-th percentile of |x| and rescale
                                        # (dynamic thresholding, Saharia et al. 2022; e.g. 0.995) instead of the clip at 1; not in the reference, off by default
+        DG.guidance_lo = float("-inf") # the guidance interval (Kynkaanniemi et al. 2024): a guided sampler step whose log-SNR lies outside [guidance_lo, guidance_hi]
+        DG.guidance_hi = float("inf")  # evaluates the conditional batch alone (B images forwarded instead of 2 B); both infinite: off (guidance at every step);
+                                       # e.g. -3, 3; not in the reference
+        DG.cfg_rescale = 0.0           # phi in (0, 1]: on guided steps x-hat is the guided prediction scaled by 1 + phi (std(x_cond) / std(x_guided) - 1) per image,
+                                       # then clipped (Lin et al. 2023, section 3.4; e.g. 0.7); not with dyn_threshold, restore_eval / restore_gray or
+                                       # sampler 'consistency'; not in the reference, off by default
         DG.grad_clip = 0.0             # c > 0: clip the global gradient norm to c inside the optimiser step (torch.nn.utils.clip_grad_norm_'s rule) and
                                        # report train/grad_norm, train/skipped_steps; implies skip_nonfinite; not in the reference, off by default
         DG.skip_nonfinite = 0          # 1: a step whose gradients hold an inf or a NaN changes nothing (the guard of the reference's GradScaler.step)
@@ -175,6 +181,10 @@ def make_plugin(GMBase, AttrDict):
                     if on:
                         raise ValueError(f"sampler = 'consistency' with {name}: multistep consistency sampling together with dynamic thresholding, "
                                          f"inpainting or restoration is out of scope")
+            guidance_interval, cfg_rescale = guidance_check((get("guidance_lo"), get("guidance_hi")), get("cfg_rescale"), get("sampler"),
+                                                            dyn_threshold)
+            if (self.restore_eval or self.restore_gray) and cfg_rescale > 0:
+                raise ValueError("restore_eval / restore_gray with cfg_rescale: restoration together with the rescaled guided prediction is out of scope")
             loss_weight, loss_gamma, time_sampler = loss_weight_check(get("loss_weight"), get("loss_gamma"), get("time_sampler"),
                                                                       self.teacher_net is not None)
             time_importance, importance_decay, importance_warmup, importance_floor, loss_profile = time_importance_check(
@@ -212,7 +222,8 @@ def make_plugin(GMBase, AttrDict):
                                                importance_warmup=importance_warmup, importance_floor=importance_floor, loss_profile=loss_profile,
                                                schedule=schedule, sample_schedule=sample_schedule,
                                                target_net=self.ema_net if consistency else None, consistency_grid=consistency_grid,
-                                               consistency_loss=consistency_loss, consistency_huber_c=consistency_huber_c)
+                                               consistency_loss=consistency_loss, consistency_huber_c=consistency_huber_c,
+                                               guidance_interval=guidance_interval, cfg_rescale=cfg_rescale)
             self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
             grad_clip, lr_min_ratio = float(get("grad_clip")), float(get("lr_min_ratio"))
             lr_warmup, lr_decay_steps = int(get("lr_warmup")), int(get("lr_decay_steps"))

@@ -29,6 +29,9 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
 * consistency distillation (`teacher_mode='consistency'`) and sampling (`sampler='consistency'`)  gmk_consistency_target (and, with
                                         `consistency_loss='huber'`, gmk_x_loss_huber) for the training target, gmk_consistency_step for the multistep
                                         sampler (Song et al. 2023, Algorithms 2 and 1; an extension, no reference call site)
+* guidance interval and rescale (`guidance_interval=(lo, hi)`, `cfg_rescale=phi`)  host logic over the sampler loop - outside the interval a step
+                                        forwards B images, not 2B (Kynkaanniemi et al. 2024) - and gmk_cfg_rescale ahead of the thresholded update
+                                        kernels (Lin et al. 2023, section 3.4; extensions, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -231,6 +234,49 @@ def dyn_threshold_check(p):
     if not 0.0 <= p <= 1.0:
         raise ValueError(f"dyn_threshold = {p}: 0 (off) or a percentile in (0, 1]")
     return p
+
+
+def guidance_check(interval, phi, sampler="ddim", dyn_threshold=0.0):
+    """The options of the guided samplers beyond the weight: `interval` None (guidance at every step) or (lo, hi), lo <= hi, the band of
+    log-SNRs in which a step is guided (Kynkaanniemi et al. 2024; either end may be infinite, (-inf, inf) is None); `phi` the rescale of the
+    guided prediction (Lin et al. 2023, section 3.4): 0 is off, else in (0, 1].  phi > 0 does not go with dyn_threshold (both set the update's
+    threshold) nor with sampler 'consistency' (its update has no thresholded form).  -> (interval as None or a pair of floats, float(phi)), or
+    ValueError naming the option (NaNs included)."""
+    if interval is not None:
+        try:
+            lo, hi = interval
+            lo, hi = float(lo), float(hi)
+        except (TypeError, ValueError):
+            raise ValueError(f"guidance_interval = {interval!r}: None or a pair (lo, hi) of log-SNRs, lo <= hi") from None
+        if not lo <= hi:                            # a NaN fails this too
+            raise ValueError(f"guidance_interval = ({lo}, {hi}): None or a pair (lo, hi) of log-SNRs, lo <= hi")
+        interval = None if (lo == -math.inf and hi == math.inf) else (lo, hi)
+    try:
+        phi = float(phi)
+    except (TypeError, ValueError):
+        raise ValueError(f"cfg_rescale = {phi!r}: 0 (off) or a factor in (0, 1]") from None
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"cfg_rescale = {phi}: 0 (off) or a factor in (0, 1]")
+    if phi > 0.0 and dyn_threshold:
+        raise ValueError(f"cfg_rescale = {phi} together with dyn_threshold = {dyn_threshold}: both set the threshold of the update; choose one")
+    if phi > 0.0 and sampler == "consistency":
+        raise ValueError(f"cfg_rescale = {phi} with sampler 'consistency': its update has no thresholded form; leave cfg_rescale at 0")
+    return interval, phi
+
+
+def guidance_mask(plan, interval):
+    """One bool per row of a `sampler_plan`: is the step guided?  lo <= lt <= hi on the row's fp32 network time lt as a Python float;
+    interval None: every row."""
+    if interval is None:
+        return [True] * len(plan)
+    lo, hi = interval
+    return [lo <= float(step.lt) <= hi for step in plan]
+
+
+def guidance_evals(plan, mask, B):
+    """Images forwarded by a guided call of B images over `plan`: a guided row costs 2 B per network evaluation (the conditional and the
+    unconditional batch), another B."""
+    return sum(step.passes * (2 * B if g else B) for step, g in zip(plan, mask))
 
 
 LOSS_WEIGHTS = ("snr_trunc", "snr", "snr_plus1", "min_snr")
@@ -641,7 +687,7 @@ class GaussianDiffusion:
     def __init__(self, *, mean_type, num_steps, teacher_net=None, teacher_mode=None, sampler="ddim", sample_cond_w=None,
                  seed=0, dyn_threshold=0.0, loss_weight="snr_trunc", loss_gamma=5.0, time_sampler="uniform", time_importance=0,
                  importance_decay=0.9, importance_warmup=5, importance_floor=0.01, loss_profile=0, schedule=None, sample_schedule=None,
-                 target_net=None, consistency_grid=0, consistency_loss="l2", consistency_huber_c=0.00054):
+                 target_net=None, consistency_grid=0, consistency_loss="l2", consistency_huber_c=0.00054, guidance_interval=None, cfg_rescale=0.0):
         if mean_type not in ops.MEAN_TYPES:                     # :70-71
             raise NotImplementedError(mean_type)
         # the noise schedule (`Schedule`; the reference's registry, diffusion_utils.py:228-239, of which it picks 'cosine', -20, 20 at :33-34):
@@ -660,6 +706,12 @@ class GaussianDiffusion:
         # p-th percentile s of |x| (s >= 1) and divided by s.  sample() and inpaint() only: the ODE is unclipped by definition and the
         # training loss keeps the reference's clip.
         self.dyn_threshold = dyn_threshold_check(dyn_threshold)
+        # the guided samplers' two options (`guidance_check`; extensions, no reference call site, off by default: the same launches as ever).
+        # `guidance_interval` (Kynkaanniemi et al. 2024): a step whose network time lies outside (lo, hi) evaluates the B-image conditional batch
+        # alone and updates without guidance - one forward of B images instead of 2 B.  `cfg_rescale` = phi (Lin et al. 2023, section 3.4): on
+        # the guided steps x-hat is clip(f x_raw, -1, 1), f = 1 + phi (std(x_c) / std(x_raw) - 1) per image, through gmk_cfg_rescale and the
+        # thresholded update kernels.
+        self.guidance_interval, self.cfg_rescale = guidance_check(guidance_interval, cfg_rescale, sampler, self.dyn_threshold)
         self.mean_type = mean_type
         self.num_steps = num_steps
         self.teacher_net = teacher_net
@@ -705,13 +757,14 @@ class GaussianDiffusion:
         """Does a forward of `nb` images of H x W replay a captured graph in the sampler loop?"""
         return 0 < nb * H * W <= self.GRAPH_MAX_PIXELS and self.num_steps >= 16 and not (module.training and module.dropout > 0.0)
 
-    def _forward_runner(self, module, z, guide, student_w):
+    def _forward_runner(self, module, z, guide, student_w, nb_decide=None):
         """-> (run(z_t) -> v, lvec): the forward of `module` on a [nb, C, H, W] batch conditioned on `guide` / `student_w`, and the fp32 [nb]
-        log-SNR vector it reads (the caller fills it before the first step, the sampler-update kernel writes it afterwards)."""
+        log-SNR vector it reads (the caller fills it before the first step, the sampler-update kernel writes it afterwards).  nb_decide: the
+        batch the captured-graph decision is taken for (a guidance interval runs a B and a 2B forward in one chain: both follow the larger)."""
         nb = z.shape[0]
         dev = z.device
         # (a captured forward would replay ONE dropout mask: training-mode dropout keeps the kernel-by-kernel path)
-        small = self._graph_path(module, nb, z.shape[2], z.shape[3])
+        small = self._graph_path(module, nb if nb_decide is None else nb_decide, z.shape[2], z.shape[3])
         if not small:
             lvecs = [torch.empty((nb,), device=dev), torch.empty((nb,), device=dev)]      # two buffers alternate (see `sample`)
             return None, lvecs
@@ -1217,6 +1270,10 @@ class GaussianDiffusion:
         None, or the whole batch's RestoreState)."""
         if rst is not None and (inp is not None or self.dyn_threshold):
             raise ValueError("restore: restoration together with inpainting or dynamic thresholding is out of scope")
+        if rst is not None and self.cfg_rescale:
+            raise ValueError("restore: cfg_rescale is set: restoration together with cfg_rescale is out of scope - the projected x-hat must not "
+                             "be rescaled")
+        guidance_check(self.guidance_interval, self.cfg_rescale, self.sampler, self.dyn_threshold)      # the attributes may have been set since
         module, guide, kw_cond_w = _unwrap(net)
         B = init_x.shape[0]
         dev = init_x.device
@@ -1242,6 +1299,9 @@ class GaussianDiffusion:
         w = ops.aligned(as_vec(w)) if w is not None else None
         if w is not None and guide is None:
             raise ValueError("classifier-free guidance needs class labels (net must carry guide=)")
+        plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample, start, self.sample_schedule)
+        if w is not None and not any(guidance_mask(plan, self.guidance_interval)):
+            w = None                            # no step of this chain lies inside the guidance interval: the conditional model alone
         z_all = ops.aligned(init_x.float())
         n1 = int(np.prod(init_x.shape[1:]))
         # Large batches run as TWO half-batches on two HIP streams (round 5): the chains of different samples never meet (GroupNorm is per
@@ -1257,7 +1317,6 @@ class GaussianDiffusion:
             not self._graph_path(module, nb_half, init_x.shape[2], init_x.shape[3])
         K = 2 if two else 1
         cut = lambda t, a, b_: None if t is None else ops.aligned(t[a:b_])
-        plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample, start, self.sample_schedule)
         # Philox counter of each network evaluation's noise draw for the WHOLE batch (ancestral sampler), and (inp.moffs) of each inpainting
         # merge's known-region draws: chunks take their slice of them
         offs = []
@@ -1319,51 +1378,68 @@ class GaussianDiffusion:
         whole-batch Philox counter of evaluation f's merge.  rst (restoration): None, or the RestoreState with this chunk's rows of obs."""
         B = z_t.shape[0]
         zs, xs, es = [], [], []
-        guided = w is not None
-        if guided:       # conditional + unconditional evaluations share one 2B-image forward (:176-177)
-            guide = torch.cat([guide, -torch.ones_like(guide)])
-            student_w = None if student_w is None else torch.cat([student_w, student_w])
+        # the mode of every network evaluation: guided (the 2B-image batch) or not (the B-image batch with the caller's labels alone).  Without a
+        # guidance interval all of them share the chain's mode, and one runner issues the launches it always has; with one, the steps whose
+        # network time lies outside it are unguided (w = 0: the conditional model), a re-noising inpainting pass staying in its step's mode.
+        mask = guidance_mask(plan, self.guidance_interval) if w is not None else [False] * len(plan)
+        modes = [g for step, g in zip(plan, mask) for _ in range(step.passes)]
+        nb_max = 2 * B if True in modes else B          # the captured-graph decision is taken for the larger of the two forwards
+        # per mode: the forward's runner (small batches replay a captured forward: one static log-SNR buffer, safe by stream order; large ones
+        # launch it kernel by kernel), its log-SNR buffers and its conditioning
+        runners = {}
+        if False in modes:
+            runners[False] = self._forward_runner(module, z_t, guide, student_w, nb_max) + (guide, student_w)
+        if True in modes:       # conditional + unconditional evaluations share one 2B-image forward (:176-177)
+            guide2 = torch.cat([guide, -torch.ones_like(guide)])
+            student_w2 = None if student_w is None else torch.cat([student_w, student_w])
             z2 = torch.cat([z_t, z_t])      # once: afterwards the update kernel writes both halves of the next 2B batch itself
-        # small batches replay a captured forward (one static log-SNR buffer, safe by stream order); large ones launch it kernel by kernel
-        graphed, lvecs = self._forward_runner(module, z2 if guided else z_t, guide, student_w)
+            runners[True] = self._forward_runner(module, z2, guide2, student_w2, nb_max) + (guide2, student_w2)
         # the network's time vector: filled once here, then by the update kernel (the next logsnr_t is this step's logsnr_s);
         # two buffers alternate so that a forward still queued on the GPU never sees its input overwritten
-        lvecs[0].fill_(float(plan[0].lt))
+        runners[modes[0]][1][0].fill_(float(plan[0].lt))
 
-        def evaluate(z_in, lvec):
-            """One network evaluation -> (v, vu): the conditional output and, guided, the unconditional one (else None)."""
-            out = graphed(z_in) if graphed else module.forward_hip(z_in, lvec, guide, student_w)
-            return (out[:B], out[B:]) if guided else (out, None)
+        def evaluate(g, z_in, f):
+            """Network evaluation f in mode g -> (v, vu): the conditional output and, guided, the unconditional one (else None)."""
+            graphed, lvecs, gd, sw = runners[g]
+            out = graphed(z_in) if graphed else module.forward_hip(z_in, lvecs[f & 1], gd, sw)
+            return (out[:B], out[B:]) if g else (out, None)
         # dpmpp_2m: the previous step's x-hat, [B, ...] also when guided (the kernel reads and rewrites it in place; the first step does not read it)
         x_hist = torch.empty_like(z_t) if self.sampler == "dpmpp_2m" else None
         f = 0                                   # network evaluations so far (one per step unless inpainting resamples)
         for step in plan:
             i, lt, ls, dpm, mrg = step.i, step.lt, step.ls, step.dpm, step.inp
             for p in range(step.passes):
-                lvec, lnext = lvecs[f & 1], lvecs[(f + 1) & 1]
-                v, vu = evaluate(z2 if guided else z_t, lvec)
+                # this evaluation's mode and the next one's: every launch that writes the next batch and its time vector (the update, the
+                # inpainting merge) does so in the form the NEXT evaluation needs - the duplicate and the 2B vector iff that one is guided
+                g, g_next = modes[f], modes[min(f + 1, len(modes) - 1)]
+                lnext = runners[g_next][1][(f + 1) & 1]
+                v, vu = evaluate(g, z2 if g else z_t, f)
+                wg = w if g else None
                 noise = None
                 if self.sampler == "noisy":                 # :241
                     noise = ops.aligned(noises[i]) if noises is not None else ops.rng_normal(tuple(z_t.shape), self.rng.seed, offs[f] + q0, z_t.device)
                 # dynamic thresholding: one select launch per network evaluation (per image, so a half-batch gives the whole batch's bits)
-                thr = ops.dyn_threshold(v, z_t, lt, self.dyn_threshold, v_uncond=vu, cond_w=w, mean_type=self.mean_type) if self.dyn_threshold else None
+                thr = ops.dyn_threshold(v, z_t, lt, self.dyn_threshold, v_uncond=vu, cond_w=wg, mean_type=self.mean_type) if self.dyn_threshold else None
+                # the rescaled guided prediction: one reduction launch per guided evaluation (per image too); an unguided one has factor 1
+                if self.cfg_rescale and g:
+                    thr = ops.cfg_rescale(v, z_t, lt, self.cfg_rescale, vu, wg, mean_type=self.mean_type)
                 # restoration: one residual launch per network evaluation (per image, so a half-batch gives the whole batch's bits)
-                ns = None if rst is None else (ops.box_residual(v, z_t, rst.obs, lt, rst.cf, rst.N, v_uncond=vu, cond_w=w, mean_type=self.mean_type),
+                ns = None if rst is None else (ops.box_residual(v, z_t, rst.obs, lt, rst.cf, rst.N, v_uncond=vu, cond_w=wg, mean_type=self.mean_type),
                                                rst.cf, rst.N)
                 if self.sampler == "consistency":
-                    z_t, xp, ep = ops.consistency_step(v, z_t, lt, ls, step.is_last, self.rng.seed, offs[f], q0=q0, v_uncond=vu, cond_w=w,
-                                                       want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext)
+                    z_t, xp, ep = ops.consistency_step(v, z_t, lt, ls, step.is_last, self.rng.seed, offs[f], q0=q0, v_uncond=vu, cond_w=wg,
+                                                       want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext)
                 elif dpm is not None:
-                    z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, dpm.coef_z, dpm.coef_x, dpm.coef_prev, step.is_last, v_uncond=vu, cond_w=w,
-                                                      want_pred=record, mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr, ns=ns)
+                    z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, dpm.coef_z, dpm.coef_x, dpm.coef_prev, step.is_last, v_uncond=vu, cond_w=wg,
+                                                      want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext, thr=thr, ns=ns)
                 else:
-                    z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, step.is_last, v_uncond=vu, cond_w=w, noise=noise, want_pred=record,
-                                                   mean_type=self.mean_type, dup=guided, logsnr_next=lnext, thr=thr, ns=ns)
-                if guided:
+                    z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, step.is_last, v_uncond=vu, cond_w=wg, noise=noise, want_pred=record,
+                                                   mean_type=self.mean_type, dup=g_next, logsnr_next=lnext, thr=thr, ns=ns)
+                if g_next:
                     z_t, z2 = z_t
                 if inp is not None:             # the known region, then (all passes but the step's last) the jump back to time t
                     ops.inpaint_merge(z_t, inp.x0, inp.mask, mrg.alpha_s, mrg.sigma_s, mrg.a, mrg.b, mrg.is_last, p < step.passes - 1, lt, ls, inp.rng.seed,
-                                      inp.moffs[f], q0=q0, B_total=inp.B_total, z_dup=z2[B:] if guided else None, logsnr_next=lnext)
+                                      inp.moffs[f], q0=q0, B_total=inp.B_total, z_dup=z2[B:] if g_next else None, logsnr_next=lnext)
                 f += 1
             if record:
                 zs.append(z_t); xs.append(xp); es.append(ep)

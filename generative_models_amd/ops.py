@@ -1184,6 +1184,28 @@ def dyn_threshold(v, z, logsnr_t, p, v_uncond=None, cond_w=None, mean_type="v", 
     return (s, q) if want_q else s
 
 
+CFG_RESCALE_KEEP = C["GMK_CFG_RESCALE_KEEP"]      # images of up to this many values are read once and kept in registers, larger ones re-read
+
+
+def cfg_rescale(v, z, logsnr_t, phi, v_uncond, cond_w, mean_type="v", want_ratio=False):
+    """The rescale factor of classifier-free guidance as a threshold (Lin et al. 2023, section 3.4; gmk_cfg_rescale; an extension):
+    thr[b] = 1 / f[b], f = 1 + phi (ratio - 1), ratio[b] = std(x_c[b]) / std(x_raw[b]) - x_c the conditional data prediction of the network
+    output v at (z, logsnr_t), x_raw the guided one, both UNCLIPPED as `dyn_threshold` forms them.  clamp(x, -thr, thr) / thr = clip(f x, -1, 1),
+    so thr is the `thr=` of `sampler_step` / `dpm_solver_step`.  v, z, v_uncond: fp32 [B, ...]; cond_w: fp32 [B]; 0 <= phi <= 1.
+    -> thr (fp32 [B]), or (thr, ratio) with want_ratio."""
+    if v_uncond is None or cond_w is None:
+        raise ValueError("cfg_rescale: v_uncond and cond_w are required (the factor compares the guided prediction with the conditional one)")
+    phi = float(phi)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"cfg_rescale: phi = {phi} outside [0, 1]")
+    B, n = _sampler_check(v, z, ((v_uncond, "v_uncond"),), cond_w)
+    thr = torch.empty((B,), device=z.device, dtype=torch.float32)
+    ratio = torch.empty_like(thr) if want_ratio else None
+    check(lib.gmk_cfg_rescale(_p(v), _p(v_uncond), _p(cond_w), _p(z), float(logsnr_t), phi, _p(thr), _p(ratio), MEAN_TYPES[mean_type], B, n,
+                              _s()), "cfg_rescale")
+    return (thr, ratio) if want_ratio else thr
+
+
 def inpaint_merge(z, x0, mask, alpha_s, sigma_s, a, b, is_last, renoise, logsnr_t, logsnr_s, seed, offset, q0=0, B_total=None, z_dup=None,
                   logsnr_next=None):
     """RePaint's merge of the known region (gmk_inpaint_merge), in place on z (fp32 [B, ...], the sampler update's output):

@@ -487,6 +487,24 @@ int gmk_sampler_step_dt(const float* v, const float* v_uncond, const float* cond
 int gmk_dpm_solver_step_dt(const float* v, const float* v_uncond, const float* cond_w, const float* thr, const float* z, float* x_hist,
                            float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last, float* z_next,
                            float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+/* the rescale factor of classifier-free guidance (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4:
+ * the guided prediction scaled back towards the conditional prediction's standard deviation), which the samplers apply on the steps inside the
+ * guidance interval (Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval Improves Sample and Distribution Quality in Diffusion
+ * Models"); an extension, no reference call site.  Per image b, in fp32, with x_c = x(v) and x_raw = (1 + w_b) x_c + (-w_b) x(v_uncond) exactly
+ * as gmk_dyn_threshold forms them (the same device function, the same bits, no clip anywhere):
+ *   m_c = (sum x_c) / n, m_r = (sum x_raw) / n;  q_c = sum (x_c - m_c)^2, q_r = sum (x_raw - m_r)^2   (two passes with centred squares)
+ *   ratio = sqrtf(q_c / q_r) = std(x_c) / std(x_raw);  f = fadd(1, fmul(phi, fsub(ratio, 1)));  thr_out[b] = 1 / f, a true division;
+ *   thr_out[b] = 1 where q_r == 0, f is not finite or f <= 0.  ratio_out (optional, B floats) receives ratio (NaN where q_c = q_r = 0).
+ * clamp(x, -thr, thr) / thr = clip(f x, -1, 1) for thr = 1 / f > 0, so gmk_sampler_step_dt / gmk_dpm_solver_step_dt called with thr_out ARE the
+ * rescaled update; ratio == 1 or phi == 0 gives thr = 1 exactly.  One workgroup of 256 threads per image; every sum runs in one order (thread t
+ * adds the elements t, t + 256, ... ascending, then the workgroup's tree: ceil(n / 256) + 8 additions per chain) without floating-point atomics, so
+ * the same call gives the same bits, a half-batch gives the whole batch's rows, and w_b = 0 gives q_r == q_c bit for bit (thr = ratio = 1).
+ * Images of up to 12,288 values are read once (12 bytes per value) and kept in registers between the passes, larger ones are read again.
+ * 16-byte loads when n % 4 == 0 and v, v_uncond, z are 16-byte aligned, else element by element.  v, v_uncond, cond_w, z, thr_out required;
+ * 0 <= phi <= 1; B, n >= 1; logsnr_t finite.  Non-finite inputs give thr = 1 or unspecified values, nothing else. */
+#define GMK_CFG_RESCALE_KEEP 12288      /* the "12,288 values" of gmk_cfg_rescale; a multiple of 1024 */
+int gmk_cfg_rescale(const float* v, const float* v_uncond, const float* cond_w, const float* z, float logsnr_t, float phi, float* thr_out,
+                    float* ratio_out, int mean_type, int B, int64_t n, void* stream);
 /* DDNM restoration for box-mean operators (Wang, Yu & Zhang 2023, "Zero-Shot Image Restoration Using Denoising Diffusion Null-Space Model",
  * eq. 13-14, noise-free); an extension, no reference call site.  Images are NCHW fp32, n = C H W.  The operator A has parameters (cf, N):
  * cf in {1, C} channels are averaged together (cf = C: colourisation), N >= 1 is the side of the spatial box (H % N == 0, W % N == 0), k = cf N^2.
