@@ -15,7 +15,9 @@
 // multistep consistency sampling: Song et al. 2023, Algorithms 1 and 2; the pseudo-Huber metric of Song & Dhariwal 2023) are extensions as well.
 // gmk_cfg_rescale (the rescale factor of classifier-free guidance: Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are
 // Flawed", section 3.4; the samplers apply it inside the guidance interval of Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval
-// Improves Sample and Distribution Quality in Diffusion Models") is an extension, no reference call site.
+// Improves Sample and Distribution Quality in Diffusion Models") is an extension, no reference call site.  gmk_stochastic_step is the ancestral
+// posterior of diffusion_reverse (diffusion_utils.py:34-62) with all three of its x_logvar forms, of which the reference's sampler calls 'large'
+// alone; DDIM with eta > 0 (Song et al. 2021) and SDE-DPM-Solver++(2M) (Lu et al. 2022) through the same entry are extensions.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -838,6 +840,66 @@ __global__ __launch_bounds__(256) void consistency_step_kernel(const float* __re
 #pragma unroll
             for (int k = 0; k < 4; ++k) zs[k] = __fadd_rn(__fmul_rn(alpha_s, xh[k]), __fmul_rn(sigma_s, e[k]));
         }
+        store4(z_next + j, zs);
+        if (z_dup) store4(z_dup + j, zs);
+        if (x_pred) store4(x_pred + j, xh);
+        if (eps_pred) store4(eps_pred + j, eh);
+    }
+}
+
+// ---- the stochastic samplers (gmk_stochastic_step): the ancestral posterior of diffusion_utils.py:34-62 with x_logvar 'small' / 'large' /
+// 'medium:<frac>', DDIM with eta > 0 (Song et al. 2021, eq. 12 and 16) and SDE-DPM-Solver++(2M) (Lu et al. 2022) are one update, linear in what
+// the step kernels already hold; the host (`stochastic_coefs`) forms the four coefficients in double.
+// grid (ceil(n/1024), B), consistency_step_kernel's shape: x-hat / eps-hat and the guidance exactly as sampler_step_kernel forms them
+// (predict_x_eps<DT>; DT: the row's threshold thr[b]), then
+//   d      = k != 0 ? fsub(fmul(1 + k, x-hat), fmul(k, x_prev)) : x-hat                  (x_prev = x_hist on entry; not read when k == 0)
+//   z_next = is_last ? x-hat : fadd(fadd(fmul(c_z, z), fmul(c_x, d)), fmul(c_n, xi))     (every operation singly rounded)
+// xi are Philox normals drawn here and never stored, by consistency_step_kernel's convention: element j = b n + i takes counter ctr + j / 4,
+// component j % 4.  Not drawn when is_last or c_n == 0 (xi = 0 then).  x_hist (nullable) takes this step's x-hat from the thread that read it.
+template <bool DT>
+__global__ __launch_bounds__(256) void stochastic_step_kernel(const float* __restrict__ v, const float* __restrict__ vu,
+                                                             const float* __restrict__ cond_w, const float* __restrict__ z,
+                                                             float* __restrict__ x_hist, const float* __restrict__ thr, float lt, float ls,
+                                                             float c_z, float c_x, float c_n, float k_prev, int is_last, uint64_t seed,
+                                                             uint64_t ctr, float* __restrict__ z_next, float* __restrict__ x_pred,
+                                                             float* __restrict__ eps_pred, float* __restrict__ z_dup,
+                                                             float* __restrict__ logsnr_next, int64_t n, int mt) {
+    const int b = blockIdx.y;
+    write_logsnr_next(logsnr_next, z_dup, b, ls);
+    const LogsnrCoef c = logsnr_coef(lt);
+    const float w = cond_w ? cond_w[b] : 0.f;
+    const float s = DT ? thr[b] : 1.0f;
+    const bool second_order = k_prev != 0.0f;            // uniform across the launch, and then x_hist is there (the entry checks)
+    const bool draw = !is_last && c_n != 0.0f;
+    const float k1 = 1.0f + k_prev;
+    const int64_t base = (int64_t)b * n;
+    for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+        const int64_t j = base + i;
+        float vv[4], zv[4], xh[4], eh[4], d[4], zs[4];
+        load4(v + j, vv);
+        load4(z + j, zv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) predict_x_eps<DT>(vv[k], vu, j + k, w, zv[k], c, mt, s, xh[k], eh[k]);
+        if (second_order) {
+            float xp[4];
+            load4(x_hist + j, xp);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d[k] = __fsub_rn(__fmul_rn(k1, xh[k]), __fmul_rn(k_prev, xp[k]));
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d[k] = xh[k];
+        }
+        if (is_last) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zs[k] = xh[k];
+        } else {
+            float e[4] = {0.f, 0.f, 0.f, 0.f};
+            if (draw) philox_normal4(ctr + (uint64_t)(j >> 2), seed, e);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                zs[k] = __fadd_rn(__fadd_rn(__fmul_rn(c_z, zv[k]), __fmul_rn(c_x, d[k])), __fmul_rn(c_n, e[k]));
+        }
+        if (x_hist) store4(x_hist + j, xh);
         store4(z_next + j, zs);
         if (z_dup) store4(z_dup + j, zs);
         if (x_pred) store4(x_pred + j, xh);
@@ -1713,6 +1775,29 @@ extern "C" int gmk_consistency_step(const float* v, const float* v_uncond, const
     consistency_step_kernel<<<dim3(gx, B), 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, logsnr_t, logsnr_s, alpha_s, sigma_s, is_last, seed,
                                                                         offset + q0, z_next, x_pred, eps_pred, z_dup, logsnr_next, n, mean_type);
     return gmk_check_launch("gmk_consistency_step");
+}
+
+extern "C" int gmk_stochastic_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float* x_hist, const float* thr,
+                                   float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_noise, float coef_prev, int is_last,
+                                   uint64_t seed, uint64_t offset, uint64_t q0, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
+                                   float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && z && z_next, "gmk_stochastic_step: null pointer");
+    if (const int err = step_args_check("gmk_stochastic_step", mean_type, v_uncond, cond_w, B, n)) return err;
+    GMK_REQUIRE(n % 4 == 0, "gmk_stochastic_step: n = %lld (n %% 4 == 0 required)", (long long)n);
+    GMK_REQUIRE(isfinite(logsnr_t) && isfinite(logsnr_s) && isfinite(coef_z) && isfinite(coef_x) && isfinite(coef_noise) && isfinite(coef_prev),
+                "gmk_stochastic_step: non-finite time or coefficient");
+    GMK_REQUIRE(coef_noise >= 0.0f, "gmk_stochastic_step: coef_noise = %g, a standard deviation: need >= 0", (double)coef_noise);
+    GMK_REQUIRE(coef_prev == 0.0f || x_hist, "gmk_stochastic_step: coef_prev = %g without x_hist", (double)coef_prev);
+    const dim3 grid(row_grid(n, 1024), B);
+    if (thr)
+        stochastic_step_kernel<true><<<grid, 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, x_hist, thr, logsnr_t, logsnr_s, coef_z, coef_x,
+                                                                          coef_noise, coef_prev, is_last, seed, offset + q0, z_next, x_pred,
+                                                                          eps_pred, z_dup, logsnr_next, n, mean_type);
+    else
+        stochastic_step_kernel<false><<<grid, 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, x_hist, nullptr, logsnr_t, logsnr_s, coef_z,
+                                                                           coef_x, coef_noise, coef_prev, is_last, seed, offset + q0, z_next,
+                                                                           x_pred, eps_pred, z_dup, logsnr_next, n, mean_type);
+    return gmk_check_launch("gmk_stochastic_step");
 }
 
 extern "C" int gmk_q_sample_logsnr(const float* x, const float* eps, const float* logsnr, float* z, int B, int64_t n, void* stream) {

@@ -24,7 +24,7 @@ import torch
 
 from .. import checkpoint, common, ops, parallel
 from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, consistency_check, dyn_threshold_check, edit_start, guidance_check,
-                                 loss_weight_check, restore_operator, schedule_check, time_importance_check)
+                                 loss_weight_check, restore_operator, schedule_check, stochastic_check, time_importance_check)
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -40,6 +40,11 @@ def make_plugin(GMBase, AttrDict):
         DG.dropout = 0.0
         DG.sampler = "ddim"            # 'ddim' | 'noisy' | 'teacher_test' (reference) | 'dpmpp_2m' (extension: DPM-Solver++(2M), second order, no training)
                                        # | 'consistency' (extension: multistep consistency sampling, for a net trained with teacher_mode 'consistency')
+                                       # | 'ancestral' ('noisy' with the variance of posterior_var, its noise drawn in the update kernel)
+                                       # | 'sde_dpmpp_2m' (extension: SDE-DPM-Solver++(2M), Lu et al. 2022: second order, stochastic)
+        DG.posterior_var = "large"     # sampler 'ancestral': the reference's x_logvar (diffusion_utils.py:44-61), 'small' | 'large' (what 'noisy' hard-codes)
+                                       # | 'medium:<frac>', frac in [0, 1] the log-domain weight of 'large'
+        DG.ddim_eta = 0.0              # sampler 'ddim': eta in (0, 1], the noise share of Song et al. 2021 (1: ancestral 'small'); 0: deterministic DDIM, as ever
         DG.mean_type = "v"
         DG.eval_heavy = 1
         DG.class_cond = 1
@@ -181,6 +186,12 @@ def make_plugin(GMBase, AttrDict):
                     if on:
                         raise ValueError(f"sampler = 'consistency' with {name}: multistep consistency sampling together with dynamic thresholding, "
                                          f"inpainting or restoration is out of scope")
+            stochastic, posterior_var, ddim_eta = stochastic_check(get("sampler"), get("posterior_var"), get("ddim_eta"))
+            if stochastic:
+                for name, on in (("inpaint_eval", self.inpaint_eval > 0), ("restore_eval / restore_gray", bool(self.restore_eval or self.restore_gray))):
+                    if on:
+                        raise ValueError(f"sampler = {get('sampler')!r}, ddim_eta = {ddim_eta} with {name}: the stochastic samplers together with "
+                                         f"inpainting or restoration are out of scope")
             guidance_interval, cfg_rescale = guidance_check((get("guidance_lo"), get("guidance_hi")), get("cfg_rescale"), get("sampler"),
                                                             dyn_threshold)
             if (self.restore_eval or self.restore_gray) and cfg_rescale > 0:
@@ -223,7 +234,8 @@ def make_plugin(GMBase, AttrDict):
                                                schedule=schedule, sample_schedule=sample_schedule,
                                                target_net=self.ema_net if consistency else None, consistency_grid=consistency_grid,
                                                consistency_loss=consistency_loss, consistency_huber_c=consistency_huber_c,
-                                               guidance_interval=guidance_interval, cfg_rescale=cfg_rescale)
+                                               guidance_interval=guidance_interval, cfg_rescale=cfg_rescale,
+                                               posterior_var=posterior_var, ddim_eta=ddim_eta)
             self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
             grad_clip, lr_min_ratio = float(get("grad_clip")), float(get("lr_min_ratio"))
             lr_warmup, lr_decay_steps = int(get("lr_warmup")), int(get("lr_decay_steps"))

@@ -32,6 +32,9 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
 * guidance interval and rescale (`guidance_interval=(lo, hi)`, `cfg_rescale=phi`)  host logic over the sampler loop - outside the interval a step
                                         forwards B images, not 2B (Kynkaanniemi et al. 2024) - and gmk_cfg_rescale ahead of the thresholded update
                                         kernels (Lin et al. 2023, section 3.4; extensions, no reference call site)
+* stochastic samplers (`sampler='ancestral'` with `posterior_var`, `sampler='ddim'` with `ddim_eta > 0`, `sampler='sde_dpmpp_2m'`)
+                                        gmk_stochastic_step on `stochastic_coefs`' rows: the reference's posterior (diffusion_utils.py:34-62)
+                                        with each of its three variances; DDIM's eta and SDE-DPM-Solver++(2M) are extensions
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -223,6 +226,106 @@ def dpm_solver_coefs(num_steps, start=None, schedule=None):
     rows = rows[len(rows) - k_start:]
     rows[0] = rows[0]._replace(coef_prev=0.0)
     return rows
+
+
+StochCoef = namedtuple("StochCoef", "i lt ls coef_z coef_x coef_noise coef_prev")
+STOCHASTIC_KINDS = ("ancestral", "ddim_eta", "sde_dpmpp_2m")
+STOCHASTIC_SAMPLERS = ("ancestral", "sde_dpmpp_2m")      # the sampler names gmk_stochastic_step adds ('ddim' with ddim_eta > 0 runs on it too)
+
+
+def posterior_var_frac(posterior_var):
+    """The ancestral sampler's variance choice as the reference's diffusion_reverse takes it (x_logvar, diffusion_utils.py:44-61): 'small'
+    (the posterior's own variance), 'large' (the forward process's) or 'medium:<frac>' (the geometric interpolation, frac in [0, 1] the weight
+    of 'large').  -> frac in [0, 1] (0 small, 1 large), or ValueError naming the option."""
+    what = f"posterior_var = {posterior_var!r}: 'small', 'large' or 'medium:<frac>' with frac in [0, 1]"
+    if posterior_var == "small":
+        return 0.0
+    if posterior_var == "large":
+        return 1.0
+    if not isinstance(posterior_var, str) or not posterior_var.startswith("medium:"):
+        raise ValueError(what)
+    try:
+        frac = float(posterior_var.split(":", 1)[1])
+    except ValueError:
+        raise ValueError(what) from None
+    if not 0.0 <= frac <= 1.0:              # a NaN fails this too
+        raise ValueError(what)
+    return frac
+
+
+def stochastic_check(sampler, posterior_var="large", ddim_eta=0.0):
+    """The options of the stochastic samplers: `posterior_var` (`posterior_var_frac`) is read by sampler 'ancestral' alone, `ddim_eta` in
+    [0, 1] (Song et al. 2021: 0 the deterministic DDIM, 1 the ancestral 'small') by sampler 'ddim' alone; a value other than the default with
+    another sampler is refused.  -> (kind, posterior_var, float(ddim_eta)), kind the `stochastic_coefs` family the sampler loop runs through
+    gmk_stochastic_step or None for the loops that have always been there, or ValueError naming the option (NaNs included)."""
+    posterior_var_frac(posterior_var)
+    try:
+        eta = float(ddim_eta)
+    except (TypeError, ValueError):
+        raise ValueError(f"ddim_eta = {ddim_eta!r}: a number in [0, 1] (0: deterministic DDIM)") from None
+    if isinstance(ddim_eta, bool) or not 0.0 <= eta <= 1.0:
+        raise ValueError(f"ddim_eta = {ddim_eta!r}: a number in [0, 1] (0: deterministic DDIM)")
+    if posterior_var != "large" and sampler != "ancestral":
+        raise ValueError(f"posterior_var = {posterior_var!r} with sampler {sampler!r}: the variance of sampler 'ancestral' only")
+    if eta > 0.0 and sampler != "ddim":
+        raise ValueError(f"ddim_eta = {eta} with sampler {sampler!r}: the noise share of sampler 'ddim' only")
+    kind = sampler if sampler in STOCHASTIC_SAMPLERS else ("ddim_eta" if eta > 0.0 else None)
+    return kind, posterior_var, eta
+
+
+def stochastic_coefs(num_steps, kind, posterior_var="large", ddim_eta=0.0, start=None, schedule=None):
+    """Per-step coefficients of gmk_stochastic_step, one row per loop iteration i = T-1 ... 0 on the samplers' grid, so that
+      z_s = coef_z z_t + coef_x ((1 + coef_prev) x_hat - coef_prev x_hat_prev) + coef_noise xi,   xi ~ N(0, I).
+    With alpha = sqrt(sigmoid(l)), sigma = sqrt(sigmoid(-l)), r = exp(lt - ls), omr = -expm1(lt - ls) and h = (ls - lt) / 2:
+      'ancestral'     the posterior q(z_s | z_t, x_hat) of the reference's diffusion_reverse (diffusion_utils.py:34-62):
+                      coef_z = r sqrt((1 + e^-lt) / (1 + e^-ls)), coef_x = omr alpha_s, coef_noise = exp(logvar / 2) with
+                      logvar = log(omr) + f logsigmoid(-lt) + (1 - f) logsigmoid(-ls), f = `posterior_var_frac(posterior_var)`
+      'ddim_eta'      DDIM with noise share eta (Song et al. 2021, eq. 12 and 16): z_s = alpha_s x_hat + sqrt(sigma_s^2 - c_n^2) eps_hat + c_n xi,
+                      eps_hat = (z_t - alpha_t x_hat) / sigma_t:  coef_noise = eta sigma_s sqrt(omr),
+                      coef_z = (sigma_s / sigma_t) sqrt((1 - eta^2) + eta^2 r) - this form: sqrt(1 - eta^2 omr) cancels to 0 at eta = 1 on the
+                      one-step grid - and coef_x = alpha_s - alpha_t coef_z.  eta = 0 gives DDIM's own update.
+      'sde_dpmpp_2m'  SDE-DPM-Solver++(2M) (Lu et al. 2022): coef_z = (sigma_s / sigma_t) e^-h, coef_x = -alpha_s expm1(-2 h),
+                      coef_noise = sigma_s sqrt(-expm1(-2 h)), coef_prev = `dpm_solver_coefs`' (0 on the first row, on the last and after a
+                      zero-length step).
+    coef_prev is 0 for the first two kinds.  A zero-length step (coincident fp32 log-SNRs) is the identity: coef_z = 1, coef_x = coef_noise = 0.
+    On the last row (i == 0) the kernel returns x_hat and draws nothing.  All in float64 from the fp32 log-SNRs of `sampler_grid`; start = k
+    (`sampler_start`) keeps the rows i = k-1 ... 0, as `dpm_solver_coefs` does."""
+    if kind not in STOCHASTIC_KINDS:
+        raise ValueError(f"kind = {kind!r}: one of {', '.join(STOCHASTIC_KINDS)}")
+    frac = posterior_var_frac(posterior_var)
+    eta = float(ddim_eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"ddim_eta = {ddim_eta!r}: a number in [0, 1]")
+    k_start = sampler_start(start, num_steps)
+    prev = [d.coef_prev for d in dpm_solver_coefs(num_steps, start, schedule)] if kind == "sde_dpmpp_2m" else [0.0] * k_start
+    return [StochCoef(i, float(lt), float(ls), *stochastic_row(kind, lt, ls, frac, eta), k)
+            for (i, lt, ls), k in zip(sampler_grid(num_steps, schedule)[num_steps - k_start:], prev)]
+
+
+def stochastic_row(kind, lt, ls, frac=1.0, eta=0.0):
+    """(coef_z, coef_x, coef_noise) of one step lt -> ls of `stochastic_coefs` (its closed forms; frac: `posterior_var_frac`'s), Python floats
+    in float64 from the two log-SNRs as given."""
+    lt, ls = float(lt), float(ls)
+    if lt == ls:                                # a zero-length step: the identity, and no log(0)
+        return 1.0, 0.0, 0.0
+    sig = lambda l: 1.0 / (1.0 + math.exp(-l))
+    logsig = lambda l: -float(_softplus64(-l))
+    alpha_t, alpha_s, sigma_t, sigma_s = math.sqrt(sig(lt)), math.sqrt(sig(ls)), math.sqrt(sig(-lt)), math.sqrt(sig(-ls))
+    r, omr = math.exp(lt - ls), -math.expm1(lt - ls)
+    if kind == "ancestral":
+        c_z = r * math.sqrt((1.0 + math.exp(-lt)) / (1.0 + math.exp(-ls)))
+        c_x = omr * alpha_s
+        c_n = math.exp(0.5 * (math.log(omr) + frac * logsig(-lt) + (1.0 - frac) * logsig(-ls)))
+    elif kind == "ddim_eta":
+        c_n = eta * sigma_s * math.sqrt(omr)
+        c_z = (sigma_s / sigma_t) * math.sqrt((1.0 - eta * eta) + eta * eta * r)
+        c_x = alpha_s - alpha_t * c_z
+    else:
+        h = 0.5 * (ls - lt)
+        c_z = (sigma_s / sigma_t) * math.exp(-h)
+        c_x = -alpha_s * math.expm1(-2.0 * h)
+        c_n = sigma_s * math.sqrt(-math.expm1(-2.0 * h))
+    return c_z, c_x, c_n
 
 
 def dyn_threshold_check(p):
@@ -460,7 +563,38 @@ def inpaint_passes(i, resample):
     return 1 if i == 0 else int(resample)
 
 
-SamplerStep = namedtuple("SamplerStep", "i lt ls is_last passes dpm inp")
+class SamplerStep(namedtuple("SamplerStep", "i lt ls is_last passes dpm inp")):
+    """One row of `sampler_plan`.  The seven tuple fields are what they have always been (plans are compared, sliced and unpacked as tuples);
+    `sto`, the stochastic samplers' StochCoef row, trails them as an eighth constructor argument that defaults to None and rides as an
+    attribute, so a plan without it is the tuple it always was.  Two rows are equal when their tuples and their `sto` are."""
+
+    sto = None                              # (what `_make` leaves: it builds the tuple without the constructor)
+
+    def __new__(cls, i, lt, ls, is_last, passes, dpm, inp, sto=None):
+        self = super().__new__(cls, i, lt, ls, is_last, passes, dpm, inp)
+        self.sto = sto
+        return self
+
+    def __getnewargs__(self):               # copy and pickle keep the row
+        return (*self, self.sto)
+
+    def _replace(self, **kwargs):
+        sto = kwargs.pop("sto", self.sto)
+        return type(self)(*super()._replace(**kwargs), sto)
+
+    def __eq__(self, other):
+        return tuple.__eq__(self, other) is True and getattr(other, "sto", None) == self.sto
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple(self), self.sto))
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", sto={self.sto!r})"
+
+
 # what inpainting adds to the sampler loop: x0 and the uint8 mask [B, n] (of the whole batch, or of a chunk's rows), the known-region
 # PhiloxStream, resample, and the whole-batch Philox counter of each network evaluation's merge (filled as the loop reserves them)
 InpaintState = namedtuple("InpaintState", "x0 mask rng resample B_total moffs")
@@ -492,18 +626,21 @@ def restore_operator(shape, factor=1, gray=False):
     return cf, N, (B, C // cf, H // N, W // N)
 
 
-def sampler_plan(num_steps, sampler="ddim", resample=None, start=None, schedule=None):
+def sampler_plan(num_steps, sampler="ddim", resample=None, start=None, schedule=None, posterior_var="large", ddim_eta=0.0):
     """One row per sampler iteration i = T-1 ... 0: the grid's (i, lt, ls), is_last, the network evaluations of the step (`resample`: the
     inpainting loop's, None outside it) and the step's DpmCoef (sampler 'dpmpp_2m') / InpaintCoef (inpainting) rows, else None ('consistency':
-    DDIM's rows - gmk_consistency_step forms its two coefficients from ls itself).  The loop
+    DDIM's rows - gmk_consistency_step forms its two coefficients from ls itself); `sto`: the step's StochCoef row when `stochastic_check`
+    (sampler, posterior_var, ddim_eta) names a kind - samplers 'ancestral', 'sde_dpmpp_2m' and 'ddim' with ddim_eta > 0 - else None.  The loop
     reserves its Philox counters and every chunk spends them by walking the same plan.  start = k (`sampler_start`): a chain that begins
     part-way, from z at plan[0].lt = logsnr(k / T) - the rows i = k-1 ... 0 of the same grid (None: all T of them).  schedule: `sampler_grid`'s."""
     k = sampler_start(start, num_steps)
     skip = num_steps - k
     dpm = dpm_solver_coefs(num_steps, start, schedule) if sampler == "dpmpp_2m" else [None] * k
     inp = inpaint_coefs(num_steps, schedule)[skip:] if resample is not None else [None] * k
-    return [SamplerStep(i, lt, ls, i == 0, 1 if resample is None else inpaint_passes(i, resample), d, c)
-            for (i, lt, ls), d, c in zip(sampler_grid(num_steps, schedule)[skip:], dpm, inp)]
+    kind, posterior_var, ddim_eta = stochastic_check(sampler, posterior_var, ddim_eta)
+    sto = stochastic_coefs(num_steps, kind, posterior_var, ddim_eta, start, schedule) if kind else [None] * k
+    return [SamplerStep(i, lt, ls, i == 0, 1 if resample is None else inpaint_passes(i, resample), d, c, e)
+            for (i, lt, ls), d, c, e in zip(sampler_grid(num_steps, schedule)[skip:], dpm, inp, sto)]
 
 
 # the variational bound's log-SNR range: the schedule's truncation (diffusion_utils.py:199-200)
@@ -687,9 +824,13 @@ class GaussianDiffusion:
     def __init__(self, *, mean_type, num_steps, teacher_net=None, teacher_mode=None, sampler="ddim", sample_cond_w=None,
                  seed=0, dyn_threshold=0.0, loss_weight="snr_trunc", loss_gamma=5.0, time_sampler="uniform", time_importance=0,
                  importance_decay=0.9, importance_warmup=5, importance_floor=0.01, loss_profile=0, schedule=None, sample_schedule=None,
-                 target_net=None, consistency_grid=0, consistency_loss="l2", consistency_huber_c=0.00054, guidance_interval=None, cfg_rescale=0.0):
+                 target_net=None, consistency_grid=0, consistency_loss="l2", consistency_huber_c=0.00054, guidance_interval=None, cfg_rescale=0.0,
+                 posterior_var="large", ddim_eta=0.0):
         if mean_type not in ops.MEAN_TYPES:                     # :70-71
             raise NotImplementedError(mean_type)
+        # the stochastic samplers' options (`stochastic_check`; off by default: the same launches as ever): `posterior_var`, the variance of
+        # sampler 'ancestral' (the reference's x_logvar, diffusion_utils.py:44-61), and `ddim_eta`, the noise share of sampler 'ddim'
+        _, self.posterior_var, self.ddim_eta = stochastic_check(sampler, posterior_var, ddim_eta)
         # the noise schedule (`Schedule`; the reference's registry, diffusion_utils.py:228-239, of which it picks 'cosine', -20, 20 at :33-34):
         # `schedule` maps the training times to log-SNRs (q_sample, the distillation targets, the loss profile's bin edges), `sample_schedule`
         # is the curve every sampler, edit, restore and the ODE walk (None: the training one) - the network is conditioned on the log-SNR
@@ -1279,8 +1420,18 @@ class GaussianDiffusion:
         dev = init_x.device
         if cond_w is not None and net_cond_w is None:
             net_cond_w = 4.0 * self.rng.uniform((B,), dev)           # :247-251
-        if self.sampler not in ("ddim", "noisy", "teacher_test", "dpmpp_2m", "consistency"):
+        if self.sampler not in ("ddim", "noisy", "teacher_test", "dpmpp_2m", "consistency") + STOCHASTIC_SAMPLERS:
             raise NotImplementedError(self.sampler)
+        stochastic, _, _ = stochastic_check(self.sampler, self.posterior_var, self.ddim_eta)      # the attributes may have been set since
+        if stochastic:      # gmk_stochastic_step: fresh noise at every step but the last, drawn in the update kernel
+            name = f"sampler {self.sampler!r}" + (f" with ddim_eta = {self.ddim_eta}" if stochastic == "ddim_eta" else "")
+            for what, on in (("inpainting", inp is not None), ("restoration", rst is not None)):
+                if on:
+                    raise ValueError(f"{name} together with {what} is out of scope")
+            if noises is not None:
+                raise ValueError(f"{name} draws its noise in the update kernel (self.rng's Philox stream): noises cannot be injected")
+            if int(np.prod(init_x.shape[1:])) % 4:
+                raise ValueError(f"{name}: {int(np.prod(init_x.shape[1:]))} values per image, a multiple of 4 is required")
         if self.sampler == "consistency":       # multistep consistency sampling: fresh noise at every step but the last, drawn in the update kernel
             for what, on in (("inpainting", inp is not None), ("restoration", rst is not None), ("dyn_threshold", bool(self.dyn_threshold))):
                 if on:
@@ -1299,7 +1450,8 @@ class GaussianDiffusion:
         w = ops.aligned(as_vec(w)) if w is not None else None
         if w is not None and guide is None:
             raise ValueError("classifier-free guidance needs class labels (net must carry guide=)")
-        plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample, start, self.sample_schedule)
+        plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample, start, self.sample_schedule,
+                            self.posterior_var, self.ddim_eta)
         if w is not None and not any(guidance_mask(plan, self.guidance_interval)):
             w = None                            # no step of this chain lies inside the guidance interval: the conditional model alone
         z_all = ops.aligned(init_x.float())
@@ -1346,7 +1498,7 @@ class GaussianDiffusion:
             return outs
         for step in plan:
             for _ in range(step.passes):
-                if self.sampler in ("noisy", "consistency") and noises is None:
+                if (self.sampler in ("noisy", "consistency") or stochastic) and noises is None:
                     offs.append(self.rng._take(B * n1))
                 if inp is not None:
                     inp.moffs.append(inp.rng._take(2 * B * n1))     # eps1 and eps2 of one merge, used or not
@@ -1404,10 +1556,10 @@ class GaussianDiffusion:
             out = graphed(z_in) if graphed else module.forward_hip(z_in, lvecs[f & 1], gd, sw)
             return (out[:B], out[B:]) if g else (out, None)
         # dpmpp_2m: the previous step's x-hat, [B, ...] also when guided (the kernel reads and rewrites it in place; the first step does not read it)
-        x_hist = torch.empty_like(z_t) if self.sampler == "dpmpp_2m" else None
+        x_hist = torch.empty_like(z_t) if self.sampler in ("dpmpp_2m", "sde_dpmpp_2m") else None
         f = 0                                   # network evaluations so far (one per step unless inpainting resamples)
         for step in plan:
-            i, lt, ls, dpm, mrg = step.i, step.lt, step.ls, step.dpm, step.inp
+            i, lt, ls, dpm, mrg, sto = step.i, step.lt, step.ls, step.dpm, step.inp, step.sto
             for p in range(step.passes):
                 # this evaluation's mode and the next one's: every launch that writes the next batch and its time vector (the update, the
                 # inpainting merge) does so in the form the NEXT evaluation needs - the duplicate and the 2B vector iff that one is guided
@@ -1429,6 +1581,10 @@ class GaussianDiffusion:
                 if self.sampler == "consistency":
                     z_t, xp, ep = ops.consistency_step(v, z_t, lt, ls, step.is_last, self.rng.seed, offs[f], q0=q0, v_uncond=vu, cond_w=wg,
                                                        want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext)
+                elif sto is not None:       # 'ancestral', 'sde_dpmpp_2m', 'ddim' with ddim_eta > 0: one launch, the noise drawn in it
+                    z_t, xp, ep = ops.stochastic_step(v, z_t, lt, ls, sto.coef_z, sto.coef_x, sto.coef_noise, sto.coef_prev, step.is_last,
+                                                      self.rng.seed, offs[f], q0=q0, x_hist=x_hist, thr=thr, v_uncond=vu, cond_w=wg,
+                                                      want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext)
                 elif dpm is not None:
                     z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, dpm.coef_z, dpm.coef_x, dpm.coef_prev, step.is_last, v_uncond=vu, cond_w=wg,
                                                       want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext, thr=thr, ns=ns)

@@ -1516,6 +1516,41 @@ def consistency_step(v, z, logsnr_t, logsnr_s, is_last, seed, offset, q0=0, v_un
     return ((z_next, z2) if dup else z_next), xp, ep
 
 
+def stochastic_step(v, z, logsnr_t, logsnr_s, coef_z, coef_x, coef_noise, coef_prev, is_last, seed, offset, q0=0, x_hist=None, thr=None,
+                    v_uncond=None, cond_w=None, want_pred=False, mean_type="v", dup=False, logsnr_next=None):
+    """One step of a stochastic sampler (gmk_stochastic_step): x-hat as `sampler_step` forms it (guidance included; with thr, fp32 [B], as its
+    thresholded form), D = (1 + coef_prev) x-hat - coef_prev x_hist when coef_prev != 0, else x-hat, and z_next = x-hat when is_last, else
+    coef_z z + coef_x D + coef_noise xi with xi the Philox normals of gmk_rng_normal(seed, offset + q0), drawn in the kernel (none when
+    coef_noise == 0): q0 = a n / 4 places a chunk that starts at row a of a batch.  The coefficients are a row of
+    `gaussian_diffusion.stochastic_coefs` ('ancestral', 'ddim_eta', 'sde_dpmpp_2m').  x_hist: None, or fp32 [B, ...] - the previous x-hat,
+    overwritten with this step's; required when coef_prev != 0.  n % 4 == 0.  Arguments and returns otherwise as `sampler_step`."""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    shape = tuple(z.shape)
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f"z: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
+    if math.prod(shape[1:]) % 4:
+        raise ValueError(f"z: {math.prod(shape[1:])} values per image, a multiple of 4 is required")
+    scalars = tuple(float(s) for s in (logsnr_t, logsnr_s, coef_z, coef_x, coef_noise, coef_prev))
+    if not all(math.isfinite(s) for s in scalars):
+        raise ValueError(f"stochastic_step: non-finite time or coefficient {scalars}")
+    if scalars[4] < 0.0:
+        raise ValueError(f"coef_noise = {scalars[4]}: a standard deviation, need >= 0")
+    if scalars[5] != 0.0 and x_hist is None:
+        raise ValueError(f"coef_prev = {scalars[5]} without x_hist: the second-order step needs the previous x-hat")
+    seed, offset = check_stream(seed, offset)
+    q0 = int(q0)
+    if not 0 <= q0 < 1 << 64:
+        raise ValueError(f"q0 = {q0}: an unsigned 64-bit Philox counter offset")
+    if (v_uncond is None) != (cond_w is None):
+        raise ValueError("stochastic_step: v_uncond and cond_w go together")
+    B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((x_hist, "x_hist"), (v_uncond, "v_uncond")), cond_w, want_pred, dup, logsnr_next)
+    check(lib.gmk_stochastic_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(x_hist), None if thr is None else _p(_thr_check(thr, B)), *scalars,
+                                  int(bool(is_last)), seed, offset, q0, _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None,
+                                  _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()), "stochastic_step")
+    return ((z_next, z2) if dup else z_next), xp, ep
+
+
 def _adam_arenas(p, g, m, v, ema=None):
     """The tensor checks of the three Adam ops: fp32 device arenas of one size (ema when given)."""
     arenas = ((p, "p"), (g, "g"), (m, "m"), (v, "v")) + (() if ema is None else ((ema, "ema"),))

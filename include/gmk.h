@@ -667,6 +667,27 @@ int gmk_consistency_step(const float* v, const float* v_uncond, const float* con
                          uint64_t seed, uint64_t offset, uint64_t q0, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
                          float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
 
+/* ---- the stochastic samplers: one step t -> s on the samplers' grid, one launch, for three families that are the same linear update.
+ *   'ancestral'    the posterior q(z_s | z_t, x_hat) of the reference's diffusion_reverse (gms/diffusion/diffusion_utils.py:34-62) with x_logvar
+ *                  'small', 'large' (what gmk_sampler_step's noise path hard-codes) or 'medium:<frac>'
+ *   'ddim_eta'     DDIM with eta in (0, 1] (Song, Meng & Ermon 2021, eq. 12 and 16); an extension, no reference call site
+ *   'sde_dpmpp_2m' SDE-DPM-Solver++(2M) (Lu et al. 2022, "DPM-Solver++", the SDE solver of its appendix); an extension, no reference call site
+ * x_hat / eps_hat exactly as gmk_sampler_step forms them (v_uncond / cond_w: classifier-free guidance), or with thr (fp32 [B], nullable) as
+ * gmk_sampler_step_dt forms them: one device function, the same bits.  Then, every operation singly rounded and nothing contracted,
+ *     d      = coef_prev != 0 ? fsub(fmul(1 + coef_prev, x_hat), fmul(coef_prev, x_prev)) : x_hat
+ *     z_next = is_last ? x_hat : fadd(fadd(fmul(coef_z, z), fmul(coef_x, d)), fmul(coef_noise, xi))
+ * with the four coefficients from the host (gaussian_diffusion.stochastic_coefs, in double, rounded to fp32).  x_hist (nullable; required when
+ * coef_prev != 0) holds x_prev, the previous step's x_hat, on entry - read only when coef_prev != 0 - and this step's x_hat on exit (same
+ * element, same thread).  xi are Philox normals drawn in the kernel and never stored: element j of this chunk is element j of
+ * gmk_rng_normal(seed, offset + q0), so rows [a, b) of a batch called with q0 = a n / 4 draw exactly what the whole batch would
+ * (gmk_consistency_step's convention).  Nothing is drawn when is_last or when coef_noise == 0.  n % 4 == 0; times and coefficients finite;
+ * coef_noise >= 0.  x_pred / eps_pred / z_dup / logsnr_next: gmk_sampler_step's conventions.  No floating-point atomics; no row of
+ * GMK_KERNEL_TABLE. */
+int gmk_stochastic_step(const float* v, const float* v_uncond, const float* cond_w, const float* z, float* x_hist, const float* thr,
+                        float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_noise, float coef_prev, int is_last,
+                        uint64_t seed, uint64_t offset, uint64_t q0, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
+                        float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+
 /* ---- optimiser (torch.optim.Adam defaults as diffusion_model.py:56 uses it), flat fp32 arena ------------- */
 int gmk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, int step, float grad_scale, void* stream);
