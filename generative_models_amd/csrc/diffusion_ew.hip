@@ -18,6 +18,9 @@
 // Improves Sample and Distribution Quality in Diffusion Models") is an extension, no reference call site.  gmk_stochastic_step is the ancestral
 // posterior of diffusion_reverse (diffusion_utils.py:34-62) with all three of its x_logvar forms, of which the reference's sampler calls 'large'
 // alone; DDIM with eta > 0 (Song et al. 2021) and SDE-DPM-Solver++(2M) (Lu et al. 2022) through the same entry are extensions.
+// gmk_hybrid_loss / gmk_stochastic_step_lv / gmk_add_into (a learned reverse-process variance: Nichol & Dhariwal 2021, "Improved Denoising
+// Diffusion Probabilistic Models", section 3.1 - the bound term is normal_kl of diffusion_utils.py:138-163 on diffusion_reverse's variances) are
+// extensions, no reference call site.
 #include <math.h>
 
 #include "gmk_common.h"
@@ -266,6 +269,140 @@ __global__ __launch_bounds__(256) void x_loss_w_kernel(const float* __restrict__
             d[k] = (raw >= -1.0f && raw <= 1.0f) ? dxo * (kx * (clip1(raw) - xv[k])) : 0.f;
         }
         if constexpr (VEC) store4(dv + base + i, d); else dv[base + i] = d[0];
+    }
+}
+
+// ---- the hybrid loss of a learned reverse-process variance (gmk_hybrid_loss; Nichol & Dhariwal 2021, "Improved DDPM", section 3.1); an
+// extension, no reference call site.  The simple loss, x_mse, eps_mse and dv are v_loss_kernel's: the same expressions, the same
+// element-to-thread assignment and summation order (thread t adds elements t, t + 256, ... in ascending order with fmaf, then block_sum), so the
+// same bits.  The bound term is the KL divergence of the posterior q(z_s | z_t, x) (diffusion_reverse's 'small' variance) from the model's
+// p(z_s | z_t) - the same mean at x_hat (a constant: stop-gradient) and the 'medium' interpolation with the per-element fraction
+// f = (nu + 1) / 2 - in the closed form of gmk.h: with D = softplus(ls) - softplus(lt) and g = -expm1(lt - ls) e^ls per image,
+//   KL_i = (f D + expm1(-f D) + e^(-f D) g d_i^2) / 2,   d nu_i = grad_scale lambda / n  D / 4  (1 - e^(-f D) (1 + g d_i^2)).
+// d nu needs no reduction, so it is written in the first pass: nu is read once whatever n.
+// One workgroup of 256 threads per image, x_loss_w_kernel's shape: the residuals d_i = x_hat_i - x_i and eps_hat_i - eps_i go through LDS
+// in chunks of kXLossKeep values (16-byte loads where VEC allows; the strided sums read them back), and an image of n <= kXLossKeep values
+// is one chunk whose gradient pass reads LDS instead of global memory (v, nu, z, x, eps are read once).  Larger images read v, z, x, eps again.
+// LDS: 8 min(n, kXLossKeep) + 16 bytes, dynamic (24 KiB at 3 x 32 x 32, 96 KiB at the capacity).  No atomics.
+__device__ __forceinline__ float softplus_f(float l) { return fmaxf(l, 0.0f) + log1pf(expf(-fabsf(l))); }
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void hybrid_loss_kernel(const float* __restrict__ v, const float* __restrict__ nu, const float* __restrict__ z,
+                                                         const float* __restrict__ x, const float* __restrict__ eps,
+                                                         const float* __restrict__ logsnr, const float* __restrict__ logsnr_s,
+                                                         float* __restrict__ loss_b, float* __restrict__ vlb_b, float* __restrict__ frac_b,
+                                                         float* __restrict__ x_mse_o, float* __restrict__ eps_mse_o, float* __restrict__ dv,
+                                                         float* __restrict__ dnu, float grad_scale, float lambda, int64_t n, int loss_type,
+                                                         int mt, int lds_floats) {
+    extern __shared__ __attribute__((aligned(16))) float hres[];     // lds_floats x residuals, lds_floats eps residuals, block_sum's four partials
+    float* resx = hres;
+    float* rese = hres + lds_floats;
+    float* red = rese + lds_floats;
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float lt = logsnr[b], ls = logsnr_s[b];
+    const LogsnrCoef c = logsnr_coef(lt);
+    const float delta = softplus_f(ls) - softplus_f(lt);            // logvar_large - logvar_small
+    const float g = -expm1f(lt - ls) * expf(ls);
+    const float knu = grad_scale * lambda / (float)n * (0.25f * delta);
+    const int64_t base = (int64_t)b * n;
+    const bool keep = dv && n <= kXLossKeep;
+    constexpr int STEP = VEC ? 4 : 1;
+    uint64_t clipped = 0;                    // keep: bit (STEP g + k) for element k of this thread's g-th group
+    float sx = 0.f, se = 0.f, skl = 0.f, sf = 0.f;
+    for (int64_t c0 = 0; c0 < n; c0 += kXLossKeep) {
+        const int m = (int)(n - c0 < kXLossKeep ? n - c0 : kXLossKeep);
+        if (c0) __syncthreads();             // the last chunk's residuals have been summed
+        int bit = 0;
+        for (int i = tid * STEP; i < m; i += 256 * STEP, bit += STEP) {
+            float vv[STEP], nv[STEP], zv[STEP], xv[STEP], ev[STEP], dx[STEP], de[STEP], dn[STEP];
+            if constexpr (VEC) {
+                load4(v + base + c0 + i, vv); load4(nu + base + c0 + i, nv); load4(z + base + c0 + i, zv);
+                load4(x + base + c0 + i, xv); load4(eps + base + c0 + i, ev);
+            } else {
+                vv[0] = v[base + c0 + i]; nv[0] = nu[base + c0 + i]; zv[0] = z[base + c0 + i];
+                xv[0] = x[base + c0 + i]; ev[0] = eps[base + c0 + i];
+            }
+#pragma unroll
+            for (int k = 0; k < STEP; ++k) {
+                const float raw = x_from_out(vv[k], zv[k], c, mt);
+                const float xh = clip1(raw);
+                const float eh = c.c1 * (zv[k] - xh * c.c2);
+                dx[k] = xh - xv[k];
+                de[k] = eh - ev[k];
+                if (keep && !(raw >= -1.0f && raw <= 1.0f)) clipped |= (uint64_t)1 << (bit + k);
+                const float f = 0.5f * (nv[k] + 1.0f);
+                const float a = f * delta;
+                const float ema = expf(-a);
+                const float q = g * (dx[k] * dx[k]);
+                skl += 0.5f * (a + expm1f(-a) + ema * q);
+                sf += f;
+                dn[k] = knu * (1.0f - ema * (1.0f + q));
+            }
+            if constexpr (VEC) {
+                store4(resx + i, dx); store4(rese + i, de);
+                if (dnu) store4(dnu + base + c0 + i, dn);
+            } else {
+                resx[i] = dx[0]; rese[i] = de[0];
+                if (dnu) dnu[base + c0 + i] = dn[0];
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < m; i += 256) {
+            const float dx = resx[i], de = rese[i];
+            sx = fmaf(dx, dx, sx);
+            se = fmaf(de, de, se);
+        }
+    }
+    sx = block_sum(sx, red);
+    se = block_sum(se, red);
+    skl = block_sum(skl, red);
+    sf = block_sum(sf, red);
+    const float xm = sx / (float)n, em = se / (float)n;
+    if (tid == 0) {
+        const float vlb = skl / (float)n;
+        loss_b[b] = (loss_type == 1 ? em : fmaxf(xm, em)) + lambda * vlb;
+        vlb_b[b] = vlb;
+        frac_b[b] = sf / (float)n;
+        x_mse_o[b] = xm;
+        eps_mse_o[b] = em;
+    }
+    if (!dv) return;
+    // v_loss_kernel's gradient of the simple loss: the bound's mean is a constant, so dv has no other term
+    const float gx = loss_type == 1 ? 0.f : (xm > em ? 1.f : (xm == em ? 0.5f : 0.f));
+    const float ge = 1.f - gx;
+    const float kx = grad_scale * gx * 2.f / (float)n;
+    const float ke = grad_scale * ge * 2.f / (float)n * (-c.c1 * c.c2);
+    if (keep) {
+        int bit = 0;
+        for (int i = tid * STEP; i < (int)n; i += 256 * STEP, bit += STEP) {
+            float dx[STEP], de[STEP], o[STEP];
+            if constexpr (VEC) { load4(resx + i, dx); load4(rese + i, de); } else { dx[0] = resx[i]; de[0] = rese[i]; }
+#pragma unroll
+            for (int k = 0; k < STEP; ++k) {
+                const float dxh = kx * dx[k] + ke * de[k];
+                o[k] = ((clipped >> (bit + k)) & 1) ? 0.f : dx_dout(c, mt) * dxh;
+            }
+            if constexpr (VEC) store4(dv + base + i, o); else dv[base + i] = o[0];
+        }
+        return;
+    }
+    for (int64_t i = (int64_t)tid * STEP; i < n; i += 256 * STEP) {
+        float vv[STEP], zv[STEP], xv[STEP], ev[STEP], o[STEP];
+        if constexpr (VEC) {
+            load4(v + base + i, vv); load4(z + base + i, zv); load4(x + base + i, xv); load4(eps + base + i, ev);
+        } else {
+            vv[0] = v[base + i]; zv[0] = z[base + i]; xv[0] = x[base + i]; ev[0] = eps[base + i];
+        }
+#pragma unroll
+        for (int k = 0; k < STEP; ++k) {
+            const float raw = x_from_out(vv[k], zv[k], c, mt);
+            const float xh = clip1(raw);
+            const float eh = c.c1 * (zv[k] - xh * c.c2);
+            const float dxh = kx * (xh - xv[k]) + ke * (eh - ev[k]);
+            o[k] = (raw >= -1.0f && raw <= 1.0f) ? dx_dout(c, mt) * dxh : 0.f;
+        }
+        if constexpr (VEC) store4(dv + base + i, o); else dv[base + i] = o[0];
     }
 }
 
@@ -907,6 +1044,55 @@ __global__ __launch_bounds__(256) void stochastic_step_kernel(const float* __res
     }
 }
 
+// ---- the ancestral step under a learned variance (gmk_stochastic_step_lv; Nichol & Dhariwal 2021, section 3.1): stochastic_step_kernel for kind
+// 'ancestral' (k_prev = 0, no x_hist) with a noise multiplier per element,
+//   c_n_i = fmul(c_n_small, exp(fmul(f_i, half_delta))),  f_i = fmul(0.5, fadd(nu_i, 1)),
+// 'medium:f_i' of diffusion_reverse in the form coef_noise_small e^(f D / 2).  nu = -1 gives f = 0, exp(0) = 1 and c_n_i = c_n_small: the
+// bits of stochastic_step_kernel under 'small'.  Same grid, same x-hat, same Philox counters; nu is not read on the last step.
+template <bool DT>
+__global__ __launch_bounds__(256) void stochastic_step_lv_kernel(const float* __restrict__ v, const float* __restrict__ vu,
+                                                                const float* __restrict__ cond_w, const float* __restrict__ z,
+                                                                const float* __restrict__ nu, const float* __restrict__ thr, float lt, float ls,
+                                                                float c_z, float c_x, float c_n_small, float half_delta, int is_last,
+                                                                uint64_t seed, uint64_t ctr, float* __restrict__ z_next,
+                                                                float* __restrict__ x_pred, float* __restrict__ eps_pred,
+                                                                float* __restrict__ z_dup, float* __restrict__ logsnr_next, int64_t n, int mt) {
+    const int b = blockIdx.y;
+    write_logsnr_next(logsnr_next, z_dup, b, ls);
+    const LogsnrCoef c = logsnr_coef(lt);
+    const float w = cond_w ? cond_w[b] : 0.f;
+    const float s = DT ? thr[b] : 1.0f;
+    const bool draw = !is_last && c_n_small != 0.0f;
+    const int64_t base = (int64_t)b * n;
+    for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+        const int64_t j = base + i;
+        float vv[4], zv[4], xh[4], eh[4], zs[4];
+        load4(v + j, vv);
+        load4(z + j, zv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) predict_x_eps<DT>(vv[k], vu, j + k, w, zv[k], c, mt, s, xh[k], eh[k]);
+        if (is_last) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zs[k] = xh[k];
+        } else {
+            float e[4] = {0.f, 0.f, 0.f, 0.f}, nv[4] = {-1.f, -1.f, -1.f, -1.f};
+            if (draw) {
+                philox_normal4(ctr + (uint64_t)(j >> 2), seed, e);
+                load4(nu + j, nv);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float cn = __fmul_rn(c_n_small, expf(__fmul_rn(__fmul_rn(0.5f, __fadd_rn(nv[k], 1.0f)), half_delta)));
+                zs[k] = __fadd_rn(__fadd_rn(__fmul_rn(c_z, zv[k]), __fmul_rn(c_x, xh[k])), __fmul_rn(cn, e[k]));
+            }
+        }
+        store4(z_next + j, zs);
+        if (z_dup) store4(z_dup + j, zs);
+        if (x_pred) store4(x_pred + j, xh);
+        if (eps_pred) store4(eps_pred + j, eh);
+    }
+}
+
 // ---- continuous-time variational bound (Kingma et al. 2021, VDM eq. 17 with lambda as the variable); an extension, no reference call site.
 // Every kernel below takes any n: 16-byte vector accesses when n % 4 == 0 (every row then starts 16-byte aligned), element by element otherwise.
 
@@ -1476,7 +1662,30 @@ int stream_grid(int64_t work_items) {
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
+// a[i] += b[i] over n elements, n % 8 == 0, 16-byte (bf16) / 32-byte (fp32) accesses: the sum of the two heads' data gradients (gmk_add_into)
+template <typename T>
+__global__ __launch_bounds__(256) void add_into_kernel(T* __restrict__ a, const T* __restrict__ b, int64_t n) {
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < n; i += (int64_t)gridDim.x * 2048) {
+        float x[8], y[8];
+        load8(a + i, x);
+        load8(b + i, y);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] += y[k];
+        store8(a + i, x);
+    }
+}
+
 }  // namespace
+
+extern "C" int gmk_add_into(void* a, const void* b, int64_t n, int dtype, void* stream) {
+    GMK_REQUIRE(a && b, "gmk_add_into: null pointer");
+    GMK_REQUIRE(n > 0 && n % 8 == 0, "gmk_add_into: n = %lld (a positive multiple of 8 required)", (long long)n);
+    GMK_REQUIRE(dtype == GMK_F32 || dtype == GMK_BF16, "gmk_add_into: dtype must be GMK_F32 or GMK_BF16 (the gradient types)");
+    const int grid = stream_grid(n / 8);
+    if (dtype == GMK_F32) add_into_kernel<float><<<grid, 256, 0, gmk_stream(stream)>>>((float*)a, (const float*)b, n);
+    else add_into_kernel<bf16_t><<<grid, 256, 0, gmk_stream(stream)>>>((bf16_t*)a, (const bf16_t*)b, n);
+    return gmk_check_launch("gmk_add_into");
+}
 
 extern "C" int gmk_rng_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
     GMK_REQUIRE(out && n > 0, "gmk_rng_normal: bad arguments");
@@ -1561,6 +1770,41 @@ extern "C" int gmk_x_loss_huber(const float* v, const float* z, const float* x, 
     if (vec) x_loss_w_kernel<true, true><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, 0, c, n, mean_type, lds_floats);
     else x_loss_w_kernel<false, true><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, 0, c, n, mean_type, lds_floats);
     return gmk_check_launch("gmk_x_loss_huber");
+}
+
+extern "C" int gmk_hybrid_loss(const float* v, const float* nu, const float* z, const float* x, const float* eps, const float* logsnr,
+                               const float* logsnr_s, float* loss_b, float* vlb_b, float* frac_b, float* x_mse, float* eps_mse, float* dv,
+                               float* dnu, float grad_scale, float lambda, int loss_type, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && nu && z && x && eps && logsnr && logsnr_s && loss_b && vlb_b && frac_b && x_mse && eps_mse, "gmk_hybrid_loss: null pointer");
+    GMK_REQUIRE(B > 0 && n > 0, "gmk_hybrid_loss: bad shape B=%d n=%lld", B, (long long)n);
+    GMK_REQUIRE(loss_type == 0 || loss_type == 1, "gmk_hybrid_loss: loss_type must be 0 (snr_trunc) or 1 (snr)");
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_hybrid_loss");
+    GMK_REQUIRE(isfinite(lambda) && lambda >= 0.0f, "gmk_hybrid_loss: lambda = %g, need a finite value >= 0", (double)lambda);
+    GMK_REQUIRE(!dv == !dnu, "gmk_hybrid_loss: dv and dnu go together");
+    const int64_t m = n < kXLossKeep ? n : kXLossKeep;
+    const int lds_floats = (int)((m + 3) / 4 * 4);
+    const size_t lds = (size_t)(2 * lds_floats + 4) * sizeof(float);
+    if (lds > 64 * 1024) {      // above what a launch gets unasked: raise the kernels' limit (96 KiB + 16) once on every device that launches them
+        constexpr int kLdsMax = (2 * kXLossKeep + 4) * (int)sizeof(float);
+        constexpr int kMaxDevices = 64;
+        static bool raised[kMaxDevices] = {};
+        int device = -1;
+        GMK_REQUIRE(hipGetDevice(&device) == hipSuccess && device >= 0 && device < kMaxDevices, "gmk_hybrid_loss: no current device (%d)", device);
+        if (!raised[device]) {
+            const hipError_t ev = hipFuncSetAttribute((const void*)hybrid_loss_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
+            const hipError_t es = hipFuncSetAttribute((const void*)hybrid_loss_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
+            GMK_REQUIRE(ev == hipSuccess && es == hipSuccess, "gmk_hybrid_loss: cannot raise the dynamic LDS limit to %d bytes on device %d: %s", kLdsMax,
+                        device, hipGetErrorString(ev != hipSuccess ? ev : es));
+            raised[device] = true;
+        }
+    }
+    // 16-byte accesses need every row to start on a 16-byte boundary: n a multiple of 4 and aligned tensors (gmk_x_loss_w's rule)
+    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(nu) | reinterpret_cast<uintptr_t>(z) |
+                                     reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(dv) |
+                                     reinterpret_cast<uintptr_t>(dnu)) & 15) == 0;
+    if (vec) hybrid_loss_kernel<true><<<B, 256, lds, gmk_stream(stream)>>>(v, nu, z, x, eps, logsnr, logsnr_s, loss_b, vlb_b, frac_b, x_mse, eps_mse, dv, dnu, grad_scale, lambda, n, loss_type, mean_type, lds_floats);
+    else hybrid_loss_kernel<false><<<B, 256, lds, gmk_stream(stream)>>>(v, nu, z, x, eps, logsnr, logsnr_s, loss_b, vlb_b, frac_b, x_mse, eps_mse, dv, dnu, grad_scale, lambda, n, loss_type, mean_type, lds_floats);
+    return gmk_check_launch("gmk_hybrid_loss");
 }
 
 extern "C" int gmk_u_stratified(const float* u0, float* u, int B, void* stream) {
@@ -1798,6 +2042,29 @@ extern "C" int gmk_stochastic_step(const float* v, const float* v_uncond, const 
                                                                            coef_x, coef_noise, coef_prev, is_last, seed, offset + q0, z_next,
                                                                            x_pred, eps_pred, z_dup, logsnr_next, n, mean_type);
     return gmk_check_launch("gmk_stochastic_step");
+}
+
+extern "C" int gmk_stochastic_step_lv(const float* v, const float* v_uncond, const float* cond_w, const float* z, const float* nu,
+                                      const float* thr, float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_noise_small,
+                                      float half_delta, int is_last, uint64_t seed, uint64_t offset, uint64_t q0, float* z_next, float* x_pred,
+                                      float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, void* stream) {
+    GMK_REQUIRE(v && z && nu && z_next, "gmk_stochastic_step_lv: null pointer");
+    if (const int err = step_args_check("gmk_stochastic_step_lv", mean_type, v_uncond, cond_w, B, n)) return err;
+    GMK_REQUIRE(n % 4 == 0, "gmk_stochastic_step_lv: n = %lld (n %% 4 == 0 required)", (long long)n);
+    GMK_REQUIRE(isfinite(logsnr_t) && isfinite(logsnr_s) && isfinite(coef_z) && isfinite(coef_x) && isfinite(coef_noise_small) && isfinite(half_delta),
+                "gmk_stochastic_step_lv: non-finite time or coefficient");
+    GMK_REQUIRE(coef_noise_small >= 0.0f, "gmk_stochastic_step_lv: coef_noise_small = %g, a standard deviation: need >= 0", (double)coef_noise_small);
+    GMK_REQUIRE(half_delta >= 0.0f, "gmk_stochastic_step_lv: half_delta = %g, half of logvar_large - logvar_small: need >= 0", (double)half_delta);
+    const dim3 grid(row_grid(n, 1024), B);
+    if (thr)
+        stochastic_step_lv_kernel<true><<<grid, 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, nu, thr, logsnr_t, logsnr_s, coef_z, coef_x,
+                                                                             coef_noise_small, half_delta, is_last, seed, offset + q0, z_next,
+                                                                             x_pred, eps_pred, z_dup, logsnr_next, n, mean_type);
+    else
+        stochastic_step_lv_kernel<false><<<grid, 256, 0, gmk_stream(stream)>>>(v, v_uncond, cond_w, z, nu, nullptr, logsnr_t, logsnr_s, coef_z,
+                                                                              coef_x, coef_noise_small, half_delta, is_last, seed, offset + q0,
+                                                                              z_next, x_pred, eps_pred, z_dup, logsnr_next, n, mean_type);
+    return gmk_check_launch("gmk_stochastic_step_lv");
 }
 
 extern "C" int gmk_q_sample_logsnr(const float* x, const float* eps, const float* logsnr, float* z, int B, int64_t n, void* stream) {

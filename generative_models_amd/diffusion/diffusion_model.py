@@ -24,7 +24,7 @@ import torch
 
 from .. import checkpoint, common, ops, parallel
 from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, consistency_check, dyn_threshold_check, edit_start, guidance_check,
-                                 loss_weight_check, restore_operator, schedule_check, stochastic_check, time_importance_check)
+                                 loss_weight_check, restore_operator, schedule_check, stochastic_check, time_importance_check, learned_var_check)
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -43,7 +43,8 @@ def make_plugin(GMBase, AttrDict):
                                        # | 'ancestral' ('noisy' with the variance of posterior_var, its noise drawn in the update kernel)
                                        # | 'sde_dpmpp_2m' (extension: SDE-DPM-Solver++(2M), Lu et al. 2022: second order, stochastic)
         DG.posterior_var = "large"     # sampler 'ancestral': the reference's x_logvar (diffusion_utils.py:44-61), 'small' | 'large' (what 'noisy' hard-codes)
-                                       # | 'medium:<frac>', frac in [0, 1] the log-domain weight of 'large'
+                                       # | 'medium:<frac>', frac in [0, 1] the log-domain weight of 'large' | 'learned' (the network's own, per element
+                                       # and per step: needs learn_var = 1)
         DG.ddim_eta = 0.0              # sampler 'ddim': eta in (0, 1], the noise share of Song et al. 2021 (1: ancestral 'small'); 0: deterministic DDIM, as ever
         DG.mean_type = "v"
         DG.eval_heavy = 1
@@ -118,6 +119,11 @@ def make_plugin(GMBase, AttrDict):
         DG.consistency_loss = "l2"     # teacher_mode 'consistency': 'l2' (the truncated-SNR loss of step2, against the consistency target) | 'huber'
                                        # (pseudo-Huber on x, Song & Dhariwal 2023; gmk_x_loss_huber)
         DG.consistency_huber_c = 0.00054  # its c, finite and > 0: the paper's 0.00054 sqrt(d) per dimension
+        DG.learn_var = 0               # 1: the network gets a second head `out_var` whose output nu sets the reverse-process variance per element, and trains on
+                                       # the hybrid loss simple + vlb_lambda vlb (Nichol & Dhariwal 2021, section 3.1; gmk_hybrid_loss); loss() also reports
+                                       # `vlb` and `var_frac`; not with teacher_path, loss_weight 'snr_trunc' / 'snr' only; not in the reference, off by default
+        DG.vlb_lambda = 0.001          # the weight of the bound term, finite and >= 0 (the paper's value)
+        DG.vlb_steps = 1000            # T >= 1: the bound term compares the times u and max(u - 1 / T, 0)
         DG.image_size = 0              # S > 0: images are S x S (CIFAR-10: 32 with in_channels 3); 0: the reference's 28, or 32 with pad32
 
         def __init__(self, G):
@@ -125,8 +131,10 @@ def make_plugin(GMBase, AttrDict):
             get = lambda k: G[k] if k in G else self.DG[k]
             cdt = _DTYPES[get("compute_dtype")]
             adt = cdt if cdt == torch.float32 else {"fp16": torch.float16, "bf16": torch.bfloat16}[get("act_dtype")]
+            if get("learn_var") not in (0, 1):
+                raise ValueError(f"learn_var = {get('learn_var')!r}: 0 (off) or 1")
             self.net = SimpleUnet(get("hidden_size"), get("dropout"), in_channels=get("in_channels"),
-                                  compute_dtype=cdt, attention=int(get("attention")), act_dtype=adt)
+                                  compute_dtype=cdt, attention=int(get("attention")), act_dtype=adt, learn_var=bool(get("learn_var")))
             weights_from = Path(G["weights_from"]) if "weights_from" in G else Path(".")
             if Path(get("teacher_path")) != Path(".") and weights_from == Path("."):      # diffusion_model.py:34-43
                 print("Loading teacher model")
@@ -186,7 +194,9 @@ def make_plugin(GMBase, AttrDict):
                     if on:
                         raise ValueError(f"sampler = 'consistency' with {name}: multistep consistency sampling together with dynamic thresholding, "
                                          f"inpainting or restoration is out of scope")
-            stochastic, posterior_var, ddim_eta = stochastic_check(get("sampler"), get("posterior_var"), get("ddim_eta"))
+            learn_var, vlb_lambda, vlb_steps = learned_var_check(get("learn_var"), get("vlb_lambda"), get("vlb_steps"), self.teacher_net is not None,
+                                                                 get("loss_weight"))
+            stochastic, posterior_var, ddim_eta = stochastic_check(get("sampler"), get("posterior_var"), get("ddim_eta"), learn_var)
             if stochastic:
                 for name, on in (("inpaint_eval", self.inpaint_eval > 0), ("restore_eval / restore_gray", bool(self.restore_eval or self.restore_gray))):
                     if on:
@@ -221,7 +231,7 @@ def make_plugin(GMBase, AttrDict):
             self.ema_net = None
             if self.ema_decay > 0:
                 self.ema_net = SimpleUnet(get("hidden_size"), get("dropout"), in_channels=get("in_channels"),
-                                          compute_dtype=cdt, attention=int(get("attention")), act_dtype=adt)
+                                          compute_dtype=cdt, attention=int(get("attention")), act_dtype=adt, learn_var=learn_var)
                 for param in self.ema_net.parameters():
                     param.requires_grad = False
                 self.ema_net.eval()
@@ -235,7 +245,8 @@ def make_plugin(GMBase, AttrDict):
                                                target_net=self.ema_net if consistency else None, consistency_grid=consistency_grid,
                                                consistency_loss=consistency_loss, consistency_huber_c=consistency_huber_c,
                                                guidance_interval=guidance_interval, cfg_rescale=cfg_rescale,
-                                               posterior_var=posterior_var, ddim_eta=ddim_eta)
+                                               posterior_var=posterior_var, ddim_eta=ddim_eta, learn_var=int(learn_var), vlb_lambda=vlb_lambda,
+                                               vlb_steps=vlb_steps)
             self.net.drop_seed = seed + 104729              # per-rank dropout masks (only used when dropout > 0)
             grad_clip, lr_min_ratio = float(get("grad_clip")), float(get("lr_min_ratio"))
             lr_warmup, lr_decay_steps = int(get("lr_warmup")), int(get("lr_decay_steps"))
@@ -270,6 +281,17 @@ def make_plugin(GMBase, AttrDict):
             return self
 
         def load_state_dict(self, state_dict, strict=True, assign=False):
+            # weights saved without the variance head, loaded into a learn_var model: the head keeps its fresh initialisation (the average's
+            # head follows the net's), so that a variance head can be fine-tuned onto a trained model
+            if getattr(self.net, "learn_var", False) and not any(k.startswith("net.out_var.") for k in state_dict):
+                print("Loaded weights have no out_var.* keys: the variance head starts from its initialisation")
+                state_dict = dict(state_dict)
+                head = {k: v.detach().clone() for k, v in self.net.state_dict().items() if k.startswith("out_var.")}
+                has_ema = any(k.startswith("ema_net.") for k in state_dict)
+                for k, v in head.items():
+                    state_dict["net." + k] = v
+                    if has_ema:
+                        state_dict["ema_net." + k] = v
             if getattr(self, "ema_net", None) is None:          # EMA off (or the teacher load inside __init__, before the EMA net exists)
                 return super().load_state_dict(state_dict, strict=strict, assign=assign)
             if not any(k.startswith("ema_net.") for k in state_dict):      # an ordinary checkpoint: the average restarts from the loaded weights

@@ -35,6 +35,10 @@ as the reference passes it (diffusion_model.py:77,85).  All arithmetic is in lib
 * stochastic samplers (`sampler='ancestral'` with `posterior_var`, `sampler='ddim'` with `ddim_eta > 0`, `sampler='sde_dpmpp_2m'`)
                                         gmk_stochastic_step on `stochastic_coefs`' rows: the reference's posterior (diffusion_utils.py:34-62)
                                         with each of its three variances; DDIM's eta and SDE-DPM-Solver++(2M) are extensions
+* learned variance (`learn_var=1`, `posterior_var='learned'`)  the network's second output nu as the per-element weight of 'large' in the 'medium'
+                                        variance (Nichol & Dhariwal 2021, section 3.1): the hybrid loss through gmk_hybrid_loss (the simple loss
+                                        with gmk_v_loss's bits plus vlb_lambda times the bound term), sampler 'ancestral' through
+                                        gmk_stochastic_step_lv on the 'small' rows (an extension, no reference call site)
 * RNG                                   counter-based Philox streams (gmk_rng_*), keyed (seed, rank, draw index)
 
 `mean_type` 'v' (the reference default, diffusion_model.py:21), 'eps' and 'x' (:58-63) are kernel arguments; 'both'
@@ -253,12 +257,17 @@ def posterior_var_frac(posterior_var):
     return frac
 
 
-def stochastic_check(sampler, posterior_var="large", ddim_eta=0.0):
+def stochastic_check(sampler, posterior_var="large", ddim_eta=0.0, learn_var=False):
     """The options of the stochastic samplers: `posterior_var` (`posterior_var_frac`) is read by sampler 'ancestral' alone, `ddim_eta` in
     [0, 1] (Song et al. 2021: 0 the deterministic DDIM, 1 the ancestral 'small') by sampler 'ddim' alone; a value other than the default with
-    another sampler is refused.  -> (kind, posterior_var, float(ddim_eta)), kind the `stochastic_coefs` family the sampler loop runs through
-    gmk_stochastic_step or None for the loops that have always been there, or ValueError naming the option (NaNs included)."""
-    posterior_var_frac(posterior_var)
+    another sampler is refused.  posterior_var 'learned' (the network's own per-element variance, gmk_stochastic_step_lv) goes with sampler
+    'ancestral' on a `learn_var` network alone.  -> (kind, posterior_var, float(ddim_eta)), kind the `stochastic_coefs` family the sampler loop
+    runs through gmk_stochastic_step or None for the loops that have always been there, or ValueError naming the option (NaNs included)."""
+    if posterior_var == "learned":
+        if not learn_var:
+            raise ValueError("posterior_var = 'learned' without learn_var: the network has no variance head (train it with learn_var = 1)")
+    else:
+        posterior_var_frac(posterior_var)
     try:
         eta = float(ddim_eta)
     except (TypeError, ValueError):
@@ -292,7 +301,7 @@ def stochastic_coefs(num_steps, kind, posterior_var="large", ddim_eta=0.0, start
     (`sampler_start`) keeps the rows i = k-1 ... 0, as `dpm_solver_coefs` does."""
     if kind not in STOCHASTIC_KINDS:
         raise ValueError(f"kind = {kind!r}: one of {', '.join(STOCHASTIC_KINDS)}")
-    frac = posterior_var_frac(posterior_var)
+    frac = 0.0 if posterior_var == "learned" else posterior_var_frac(posterior_var)      # 'learned': the 'small' rows, scaled per element in the kernel
     eta = float(ddim_eta)
     if not 0.0 <= eta <= 1.0:
         raise ValueError(f"ddim_eta = {ddim_eta!r}: a number in [0, 1]")
@@ -326,6 +335,46 @@ def stochastic_row(kind, lt, ls, frac=1.0, eta=0.0):
         c_x = -alpha_s * math.expm1(-2.0 * h)
         c_n = sigma_s * math.sqrt(-math.expm1(-2.0 * h))
     return c_z, c_x, c_n
+
+
+def learned_half_delta(lt, ls):
+    """half_delta of gmk_stochastic_step_lv for one step lt -> ls: (softplus(ls) - softplus(lt)) / 2 = (logvar_large - logvar_small) / 2 of
+    diffusion_reverse, in float64, so that `stochastic_row`'s 'small' coef_noise times exp(f half_delta) is its 'medium:f' coef_noise."""
+    return 0.5 * (float(_softplus64(float(ls))) - float(_softplus64(float(lt))))
+
+
+VLB_LAMBDA = 0.001          # the weight of the bound term in the hybrid loss (Nichol & Dhariwal 2021, section 3.1)
+VLB_STEPS = 1000            # T of the bound's time pairs (u, max(u - 1 / T, 0))
+
+
+def learned_var_check(learn_var, vlb_lambda=VLB_LAMBDA, vlb_steps=VLB_STEPS, has_teacher=False, loss_weight="snr_trunc"):
+    """The options of a learned reverse-process variance (Nichol & Dhariwal 2021, section 3.1; an extension, off by default): `learn_var` 0 / 1
+    - the network carries the variance head and trains on the hybrid loss (gmk_hybrid_loss) simple + vlb_lambda vlb; `vlb_lambda` finite and
+    >= 0; `vlb_steps` = T >= 1, the grid of the bound's time pairs.  Not with a teacher (teacher_mode step1 / step2 / consistency) and with
+    loss_weight 'snr_trunc' or 'snr' only (the two objectives gmk_v_loss forms).  -> (bool(learn_var), float(vlb_lambda), int(vlb_steps)), or
+    ValueError naming the option (NaNs included)."""
+    if isinstance(learn_var, str) or learn_var not in (0, 1):
+        raise ValueError(f"learn_var = {learn_var!r}: 0 (off) or 1")
+    try:
+        lam = float(vlb_lambda)
+    except (TypeError, ValueError):
+        raise ValueError(f"vlb_lambda = {vlb_lambda!r}: a finite number >= 0") from None
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"vlb_lambda = {vlb_lambda!r}: a finite number >= 0")
+    try:
+        T = int(vlb_steps)
+        whole = T == float(vlb_steps)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"vlb_steps = {vlb_steps!r}: an integer >= 1") from None
+    if not whole or T < 1:
+        raise ValueError(f"vlb_steps = {vlb_steps!r}: an integer >= 1")
+    if learn_var:
+        if has_teacher:
+            raise ValueError("learn_var = 1 with teacher_path (teacher_mode step1 / step2 / consistency): a learned variance for the distillation "
+                             "modes is out of scope")
+        if loss_weight not in ("snr_trunc", "snr"):
+            raise ValueError(f"learn_var = 1 with loss_weight = {loss_weight!r}: the hybrid loss adds the bound to 'snr_trunc' or 'snr' only")
+    return bool(learn_var), lam, T
 
 
 def dyn_threshold_check(p):
@@ -626,7 +675,7 @@ def restore_operator(shape, factor=1, gray=False):
     return cf, N, (B, C // cf, H // N, W // N)
 
 
-def sampler_plan(num_steps, sampler="ddim", resample=None, start=None, schedule=None, posterior_var="large", ddim_eta=0.0):
+def sampler_plan(num_steps, sampler="ddim", resample=None, start=None, schedule=None, posterior_var="large", ddim_eta=0.0, learn_var=False):
     """One row per sampler iteration i = T-1 ... 0: the grid's (i, lt, ls), is_last, the network evaluations of the step (`resample`: the
     inpainting loop's, None outside it) and the step's DpmCoef (sampler 'dpmpp_2m') / InpaintCoef (inpainting) rows, else None ('consistency':
     DDIM's rows - gmk_consistency_step forms its two coefficients from ls itself); `sto`: the step's StochCoef row when `stochastic_check`
@@ -637,7 +686,7 @@ def sampler_plan(num_steps, sampler="ddim", resample=None, start=None, schedule=
     skip = num_steps - k
     dpm = dpm_solver_coefs(num_steps, start, schedule) if sampler == "dpmpp_2m" else [None] * k
     inp = inpaint_coefs(num_steps, schedule)[skip:] if resample is not None else [None] * k
-    kind, posterior_var, ddim_eta = stochastic_check(sampler, posterior_var, ddim_eta)
+    kind, posterior_var, ddim_eta = stochastic_check(sampler, posterior_var, ddim_eta, learn_var)
     sto = stochastic_coefs(num_steps, kind, posterior_var, ddim_eta, start, schedule) if kind else [None] * k
     return [SamplerStep(i, lt, ls, i == 0, 1 if resample is None else inpaint_passes(i, resample), d, c, e)
             for (i, lt, ls), d, c, e in zip(sampler_grid(num_steps, schedule)[skip:], dpm, inp, sto)]
@@ -784,6 +833,26 @@ class _VLoss(torch.autograd.Function):
         return out, None, None, None, None, None, None
 
 
+class _HybridLoss(torch.autograd.Function):
+    """(loss_b, vlb_b, frac_b, x_mse) of `ops.hybrid_loss`, loss_b = simple + vlb_lambda vlb differentiable w.r.t. v (the simple loss alone:
+    the bound's mean is a constant) and nu; the other three are reported numbers only."""
+
+    @staticmethod
+    def forward(ctx, v, nu, z, x, eps, logsnr, logsnr_s, vlb_lambda, loss_type=0, mean_type="v"):
+        loss_b, vlb, frac, x_mse, _, dv, dnu = ops.hybrid_loss(v.contiguous(), nu.contiguous(), z, x, eps, logsnr, logsnr_s, vlb_lambda,
+                                                               grad_scale=1.0, loss_type=loss_type, mean_type=mean_type)
+        ctx.save_for_backward(dv, dnu)
+        ctx.mark_non_differentiable(vlb, frac, x_mse)
+        return loss_b, vlb, frac, x_mse
+
+    @staticmethod
+    def backward(ctx, g, _g_vlb, _g_frac, _g_x_mse):
+        dv, dnu = ctx.saved_tensors
+        B = dv.shape[0]
+        g = g.contiguous().float()
+        return (ops.scale_rows(dv.view(B, -1), g).view_as(dv), ops.scale_rows(dnu.view(B, -1), g).view_as(dnu)) + (None,) * 8
+
+
 class _XLossW(torch.autograd.Function):
     """(loss_b, x_mse) of `ops.x_loss_w`, loss_b = w(logsnr) x_mse differentiable w.r.t. v; x_mse is a reported number only."""
 
@@ -825,12 +894,16 @@ class GaussianDiffusion:
                  seed=0, dyn_threshold=0.0, loss_weight="snr_trunc", loss_gamma=5.0, time_sampler="uniform", time_importance=0,
                  importance_decay=0.9, importance_warmup=5, importance_floor=0.01, loss_profile=0, schedule=None, sample_schedule=None,
                  target_net=None, consistency_grid=0, consistency_loss="l2", consistency_huber_c=0.00054, guidance_interval=None, cfg_rescale=0.0,
-                 posterior_var="large", ddim_eta=0.0):
+                 posterior_var="large", ddim_eta=0.0, learn_var=0, vlb_lambda=VLB_LAMBDA, vlb_steps=VLB_STEPS):
         if mean_type not in ops.MEAN_TYPES:                     # :70-71
             raise NotImplementedError(mean_type)
+        # a learned reverse-process variance (`learned_var_check`; Nichol & Dhariwal 2021, section 3.1; an extension, off by default: the same
+        # launches as ever): the network's second head gives nu, training adds vlb_lambda times the bound term of the time pair
+        # (u, max(u - 1 / vlb_steps, 0)) to the simple loss (gmk_hybrid_loss), and sampler 'ancestral' with posterior_var 'learned' draws with it
+        self.learn_var, self.vlb_lambda, self.vlb_steps = learned_var_check(learn_var, vlb_lambda, vlb_steps, teacher_net is not None, loss_weight)
         # the stochastic samplers' options (`stochastic_check`; off by default: the same launches as ever): `posterior_var`, the variance of
         # sampler 'ancestral' (the reference's x_logvar, diffusion_utils.py:44-61), and `ddim_eta`, the noise share of sampler 'ddim'
-        _, self.posterior_var, self.ddim_eta = stochastic_check(sampler, posterior_var, ddim_eta)
+        _, self.posterior_var, self.ddim_eta = stochastic_check(sampler, posterior_var, ddim_eta, self.learn_var)
         # the noise schedule (`Schedule`; the reference's registry, diffusion_utils.py:228-239, of which it picks 'cosine', -20, 20 at :33-34):
         # `schedule` maps the training times to log-SNRs (q_sample, the distillation targets, the loss profile's bin edges), `sample_schedule`
         # is the curve every sampler, edit, restore and the ODE walk (None: the training one) - the network is conditioned on the log-SNR
@@ -898,8 +971,9 @@ class GaussianDiffusion:
         """Does a forward of `nb` images of H x W replay a captured graph in the sampler loop?"""
         return 0 < nb * H * W <= self.GRAPH_MAX_PIXELS and self.num_steps >= 16 and not (module.training and module.dropout > 0.0)
 
-    def _forward_runner(self, module, z, guide, student_w, nb_decide=None):
-        """-> (run(z_t) -> v, lvec): the forward of `module` on a [nb, C, H, W] batch conditioned on `guide` / `student_w`, and the fp32 [nb]
+    def _forward_runner(self, module, z, guide, student_w, nb_decide=None, want_nu=0):
+        """want_nu: 0, or the number of leading rows whose variance output the forward also returns (run(z_t) -> (v, nu) then).
+        -> (run(z_t) -> v, lvec): the forward of `module` on a [nb, C, H, W] batch conditioned on `guide` / `student_w`, and the fp32 [nb]
         log-SNR vector it reads (the caller fills it before the first step, the sampler-update kernel writes it afterwards).  nb_decide: the
         batch the captured-graph decision is taken for (a guidance interval runs a B and a 2B forward in one chain: both follow the larger)."""
         nb = z.shape[0]
@@ -912,7 +986,7 @@ class GaussianDiffusion:
         # the host-side freshness check of the packed convolution weights runs at capture time only: do it here, before every replay loop
         # (the pack buffer keeps its address, so a re-pack is seen by the captured kernels)
         module.prepare_forward(dev)
-        key = (id(module), module.flat_params.data_ptr(), module._pack_buf.data_ptr(), tuple(z.shape), guide is not None, student_w is not None)
+        key = (id(module), module.flat_params.data_ptr(), module._pack_buf.data_ptr(), tuple(z.shape), guide is not None, student_w is not None, want_nu)
         ent = self._graphs.get(key)
         if ent is None:
             zs, ls = torch.empty_like(z), torch.zeros((nb,), device=dev)
@@ -923,11 +997,11 @@ class GaussianDiffusion:
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for _ in range(2):
-                    module.forward_hip(zs, ls, gs, ws)
+                    module.forward_hip(zs, ls, gs, ws, want_nu=want_nu)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out = module.forward_hip(zs, ls, gs, ws)
+                out = module.forward_hip(zs, ls, gs, ws, want_nu=want_nu)
             ent = self._graphs[key] = (graph, zs, ls, gs, ws, out)
             if len(self._graphs) > 8:                             # a handful of shapes at most: drop the oldest capture
                 self._graphs.pop(next(iter(self._graphs)))
@@ -1042,16 +1116,35 @@ class GaussianDiffusion:
                 loss_type = 0
         return module, guide, cond_w, z_t, logsnr, x_target, eps_target, loss_type
 
+    def _logsnr_prev(self, u):
+        """The log-SNR one step of the bound's grid earlier, schedule(max(u - 1 / vlb_steps, 0)): the clamp is made here because the schedule
+        kernel does not clamp and the cosine curve is NaN below u = 0."""
+        u_s = ops.aligned((u - 1.0 / self.vlb_steps).clamp_(min=0.0))
+        return ops.logsnr_schedule(u.numel(), u.device, u=u_s, schedule=self.schedule)
+
     def training_losses(self, *, net, x, u=None, eps=None, i_times=None, cond_w=None):
-        """Reference call shape (:81).  Differentiable through torch.autograd when grad mode is on."""
+        """Reference call shape (:81).  Differentiable through torch.autograd when grad mode is on.  learn_var: the hybrid loss, with `vlb`
+        (the bound term, nats per dimension) and `var_frac` (the mean interpolation weight) beside it."""
         assert x.dtype in [torch.float32, torch.float64]
-        if self.loss_profile:                                     # the same draws in the same order (`_prepare`: eps, then u), made here to keep u
+        if self.loss_profile or self.learn_var:                                     # the same draws in the same order (`_prepare`: eps, then u), made here to keep u
             if eps is None:
                 eps = self.rng.normal(x.shape, x.device)
             if u is None:
                 u = self.draw_u(x.shape[0], x.device)
             u = ops.aligned(u.float())
         module, guide, w, z_t, logsnr, x_t, eps_t, loss_type = self._prepare(net, x, u, eps, i_times, cond_w)
+        if self.learn_var:                                        # the hybrid loss on the network's (v, nu) pair
+            if not getattr(module, "learn_var", False):
+                raise ValueError("learn_var = 1 with a network that has no variance head (SimpleUnet(learn_var=True))")
+            v, nu = module(z_t, logsnr, guide=guide, cond_w=w, want_nu=True)
+            args = (v, nu, z_t, x_t, eps_t, logsnr, self._logsnr_prev(u), self.vlb_lambda)
+            if torch.is_grad_enabled() and v.requires_grad:
+                loss, vlb, frac, x_mse = _HybridLoss.apply(*args, loss_type, self.mean_type)
+            else:
+                loss, vlb, frac, x_mse = ops.hybrid_loss(*args, loss_type=loss_type, mean_type=self.mean_type)[:4]
+            if self.loss_profile:
+                ops.loss_profile(u, loss.detach(), x_mse, self.profile_state("test", u.device), 1.0)
+            return {"loss": loss, "vlb": vlb, "var_frac": frac}
         v = module(z_t, logsnr, guide=guide, cond_w=w)
         grad = torch.is_grad_enabled() and v.requires_grad
 
@@ -1090,6 +1183,12 @@ class GaussianDiffusion:
         # time_importance it goes through the profile's inverse CDF, and every image's gradient and loss take the importance weight 1 / (64 p).
         profiled = (self.time_importance or self.loss_profile) and u is None
         time_w = None
+        if self.learn_var and not profiled:     # the bound's time pair needs u: `_prepare`'s draws in its order (eps, then u), made here
+            if eps is None:
+                eps = self.rng.normal(x.shape, x.device)
+            if u is None:
+                u = self.draw_u(x.shape[0], x.device)
+            u = ops.aligned(u.float())
         if profiled:
             if eps is None:
                 eps = self.rng.normal(x.shape, x.device)
@@ -1098,19 +1197,31 @@ class GaussianDiffusion:
                 u, time_w = ops.u_importance(self.profile_state("train", x.device), u, self.importance_warmup, self.importance_floor)
         module, guide, w, z_t, logsnr, x_t, eps_t, loss_type = self._prepare(net, x, u, eps, i_times, cond_w)
         ctx = {}
-        v = module.forward_hip(z_t, logsnr, guide, w, ctx=ctx)
-        if self.loss_weight_type == "huber":
-            loss_b, x_mse, dv = ops.x_loss_huber(v, z_t, x_t, logsnr, self.consistency_huber_c, grad_scale=grad_scale, mean_type=self.mean_type)
-            out = {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
-        elif self.loss_weight_type in ops.X_LOSS_WEIGHTS:
-            loss_b, x_mse, dv = ops.x_loss_w(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, grad_scale=grad_scale, mean_type=self.mean_type)
-            out = {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
+        dnu = None
+        if self.learn_var:                      # the hybrid loss: the simple loss's dv (gmk_v_loss's bits) and the bound's dnu, one launch
+            if not getattr(module, "learn_var", False):
+                raise ValueError("learn_var = 1 with a network that has no variance head (SimpleUnet(learn_var=True))")
+            v, nu = module.forward_hip(z_t, logsnr, guide, w, ctx=ctx, want_nu=True)
+            loss_b, vlb, frac, x_mse, eps_mse, dv, dnu = ops.hybrid_loss(v, nu, z_t, x_t, eps_t, logsnr, self._logsnr_prev(u), self.vlb_lambda,
+                                                                        grad_scale=grad_scale, loss_type=loss_type, mean_type=self.mean_type)
+            out = {"loss": loss_b, "x_mse": x_mse, "eps_mse": eps_mse, "logsnr": logsnr, "vlb": vlb, "var_frac": frac}
         else:
-            loss_b, x_mse, eps_mse, dv = ops.v_loss(v, z_t, x_t, eps_t, logsnr, grad_scale=grad_scale, loss_type=loss_type, mean_type=self.mean_type)
-            out = {"loss": loss_b, "x_mse": x_mse, "eps_mse": eps_mse, "logsnr": logsnr}
-        if time_w is not None:
+            v = module.forward_hip(z_t, logsnr, guide, w, ctx=ctx)
+            if self.loss_weight_type == "huber":
+                loss_b, x_mse, dv = ops.x_loss_huber(v, z_t, x_t, logsnr, self.consistency_huber_c, grad_scale=grad_scale, mean_type=self.mean_type)
+                out = {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
+            elif self.loss_weight_type in ops.X_LOSS_WEIGHTS:
+                loss_b, x_mse, dv = ops.x_loss_w(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, grad_scale=grad_scale,
+                                                 mean_type=self.mean_type)
+                out = {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
+            else:
+                loss_b, x_mse, eps_mse, dv = ops.v_loss(v, z_t, x_t, eps_t, logsnr, grad_scale=grad_scale, loss_type=loss_type, mean_type=self.mean_type)
+                out = {"loss": loss_b, "x_mse": x_mse, "eps_mse": eps_mse, "logsnr": logsnr}
+        if time_w is not None:                  # the importance weights scale every row of the output gradients
             dv = ops.scale_rows(dv.view(dv.shape[0], -1), time_w).view_as(dv)
-        module.backward_hip(ctx, dv, on_grads_ready=on_grads_ready, join_side_before_ready=join_side_before_ready)
+            if dnu is not None:
+                dnu = ops.scale_rows(dnu.view(dnu.shape[0], -1), time_w).view_as(dnu)
+        module.backward_hip(ctx, dv, on_grads_ready=on_grads_ready, join_side_before_ready=join_side_before_ready, dnu=dnu)
         if profiled:                    # the UNWEIGHTED loss enters the profile: p must follow the loss itself, not the loss it reweighted
             ops.loss_profile(u, loss_b, x_mse, self.profile_state("train", u.device), self.importance_decay)
             out["u"] = u
@@ -1422,7 +1533,8 @@ class GaussianDiffusion:
             net_cond_w = 4.0 * self.rng.uniform((B,), dev)           # :247-251
         if self.sampler not in ("ddim", "noisy", "teacher_test", "dpmpp_2m", "consistency") + STOCHASTIC_SAMPLERS:
             raise NotImplementedError(self.sampler)
-        stochastic, _, _ = stochastic_check(self.sampler, self.posterior_var, self.ddim_eta)      # the attributes may have been set since
+        # (the attributes may have been set since; the variance head is the sampling network's own)
+        stochastic, _, _ = stochastic_check(self.sampler, self.posterior_var, self.ddim_eta, getattr(module, "learn_var", False))
         if stochastic:      # gmk_stochastic_step: fresh noise at every step but the last, drawn in the update kernel
             name = f"sampler {self.sampler!r}" + (f" with ddim_eta = {self.ddim_eta}" if stochastic == "ddim_eta" else "")
             for what, on in (("inpainting", inp is not None), ("restoration", rst is not None)):
@@ -1451,7 +1563,7 @@ class GaussianDiffusion:
         if w is not None and guide is None:
             raise ValueError("classifier-free guidance needs class labels (net must carry guide=)")
         plan = sampler_plan(self.num_steps, self.sampler, None if inp is None else inp.resample, start, self.sample_schedule,
-                            self.posterior_var, self.ddim_eta)
+                            self.posterior_var, self.ddim_eta, getattr(module, "learn_var", False))
         if w is not None and not any(guidance_mask(plan, self.guidance_interval)):
             w = None                            # no step of this chain lies inside the guidance interval: the conditional model alone
         z_all = ops.aligned(init_x.float())
@@ -1539,22 +1651,26 @@ class GaussianDiffusion:
         # per mode: the forward's runner (small batches replay a captured forward: one static log-SNR buffer, safe by stream order; large ones
         # launch it kernel by kernel), its log-SNR buffers and its conditioning
         runners = {}
+        # posterior_var 'learned': every forward also runs the variance head, over the conditional rows alone (the first B of a guided 2B batch)
+        want_nu = B if self.posterior_var == "learned" and self.sampler == "ancestral" else 0
         if False in modes:
-            runners[False] = self._forward_runner(module, z_t, guide, student_w, nb_max) + (guide, student_w)
+            runners[False] = self._forward_runner(module, z_t, guide, student_w, nb_max, want_nu) + (guide, student_w)
         if True in modes:       # conditional + unconditional evaluations share one 2B-image forward (:176-177)
             guide2 = torch.cat([guide, -torch.ones_like(guide)])
             student_w2 = None if student_w is None else torch.cat([student_w, student_w])
             z2 = torch.cat([z_t, z_t])      # once: afterwards the update kernel writes both halves of the next 2B batch itself
-            runners[True] = self._forward_runner(module, z2, guide2, student_w2, nb_max) + (guide2, student_w2)
+            runners[True] = self._forward_runner(module, z2, guide2, student_w2, nb_max, want_nu) + (guide2, student_w2)
         # the network's time vector: filled once here, then by the update kernel (the next logsnr_t is this step's logsnr_s);
         # two buffers alternate so that a forward still queued on the GPU never sees its input overwritten
         runners[modes[0]][1][0].fill_(float(plan[0].lt))
 
         def evaluate(g, z_in, f):
-            """Network evaluation f in mode g -> (v, vu): the conditional output and, guided, the unconditional one (else None)."""
+            """Network evaluation f in mode g -> (v, vu, nu): the conditional output, guided the unconditional one (else None), and under
+            posterior_var 'learned' the conditional rows' variance output (else None)."""
             graphed, lvecs, gd, sw = runners[g]
-            out = graphed(z_in) if graphed else module.forward_hip(z_in, lvecs[f & 1], gd, sw)
-            return (out[:B], out[B:]) if g else (out, None)
+            out = graphed(z_in) if graphed else module.forward_hip(z_in, lvecs[f & 1], gd, sw, want_nu=want_nu)
+            out, nu = out if want_nu else (out, None)
+            return (out[:B], out[B:], nu) if g else (out, None, nu)
         # dpmpp_2m: the previous step's x-hat, [B, ...] also when guided (the kernel reads and rewrites it in place; the first step does not read it)
         x_hist = torch.empty_like(z_t) if self.sampler in ("dpmpp_2m", "sde_dpmpp_2m") else None
         f = 0                                   # network evaluations so far (one per step unless inpainting resamples)
@@ -1565,7 +1681,7 @@ class GaussianDiffusion:
                 # inpainting merge) does so in the form the NEXT evaluation needs - the duplicate and the 2B vector iff that one is guided
                 g, g_next = modes[f], modes[min(f + 1, len(modes) - 1)]
                 lnext = runners[g_next][1][(f + 1) & 1]
-                v, vu = evaluate(g, z2 if g else z_t, f)
+                v, vu, nu = evaluate(g, z2 if g else z_t, f)
                 wg = w if g else None
                 noise = None
                 if self.sampler == "noisy":                 # :241
@@ -1581,6 +1697,10 @@ class GaussianDiffusion:
                 if self.sampler == "consistency":
                     z_t, xp, ep = ops.consistency_step(v, z_t, lt, ls, step.is_last, self.rng.seed, offs[f], q0=q0, v_uncond=vu, cond_w=wg,
                                                        want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext)
+                elif sto is not None and nu is not None:      # 'ancestral' under the learned variance: the 'small' row, scaled per element
+                    z_t, xp, ep = ops.stochastic_step_lv(v, z_t, nu, lt, ls, sto.coef_z, sto.coef_x, sto.coef_noise, learned_half_delta(lt, ls),
+                                                         step.is_last, self.rng.seed, offs[f], q0=q0, thr=thr, v_uncond=vu, cond_w=wg,
+                                                         want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext)
                 elif sto is not None:       # 'ancestral', 'sde_dpmpp_2m', 'ddim' with ddim_eta > 0: one launch, the noise drawn in it
                     z_t, xp, ep = ops.stochastic_step(v, z_t, lt, ls, sto.coef_z, sto.coef_x, sto.coef_noise, sto.coef_prev, step.is_last,
                                                       self.rng.seed, offs[f], q0=q0, x_hist=x_hist, thr=thr, v_uncond=vu, cond_w=wg,

@@ -54,7 +54,7 @@ RES_BLOCKS = ["down.seq.1", "down.seq.2", "down.seq.4", "down.seq.5", "turn", "u
               "up.seq.3.0", "up.seq.4", "up.seq.5", "up.seq.6"]
 
 
-def param_inventory(C, in_channels=1, attention=False):
+def param_inventory(C, in_channels=1, attention=False, learn_var=False):
     E = 2 * C
     inv = []
     for name, fan_in in (("time_embed", 64), ("cond_w_embed", 64), ("guide_embed", 10)):
@@ -77,6 +77,8 @@ def param_inventory(C, in_channels=1, attention=False):
             inv += _res_names(f"up.seq.{i}", 2 * C, C, E)
     inv += [("out.0.weight", (C,)), ("out.0.bias", (C,)), ("out.2.weight", (in_channels, C, 3, 3)),
             ("out.2.bias", (in_channels,))]
+    if learn_var:        # the variance head (Nichol & Dhariwal 2021: the second half of a 2 C-channel output layer, kept as a tensor pair of its own)
+        inv += [("out_var.weight", (in_channels, C, 3, 3)), ("out_var.bias", (in_channels,))]
     return inv
 
 
@@ -128,7 +130,7 @@ class _DeferredGN:
 
 
 class SimpleUnet(nn.Module):
-    def __init__(self, channels, dropout=0.0, in_channels=1, compute_dtype=torch.bfloat16, attention=False, act_dtype=None):
+    def __init__(self, channels, dropout=0.0, in_channels=1, compute_dtype=torch.bfloat16, attention=False, act_dtype=None, learn_var=False):
         super().__init__()
         if channels % 32 or not 32 <= channels <= 256:
             raise ValueError(f"the HIP path is built for hidden_size 128 (DiffusionModel's default, every BASELINE config) and 256 (the default of "
@@ -158,14 +160,17 @@ class SimpleUnet(nn.Module):
         cpg1, cpg2 = channels // 32, 2 * channels // 32
         self._g1 = padded // cpg1 if padded % cpg1 == 0 and cpg1 in (1, 2, 4, 8, 16) else -cpg1
         self._g2 = padded // cpg2 if padded % cpg2 == 0 and cpg2 in (1, 2, 4, 8, 16) else -cpg2
-        self._real_inventory = param_inventory(channels, in_channels, bool(attention))
+        # learn_var: a second 3x3 head `out_var` on the activation `out.2` reads; its output nu sets the reverse-process variance per element
+        # (Nichol & Dhariwal 2021, section 3.1; an extension).  Off: the inventory, the arena and every launch are the reference's.
+        self.learn_var = bool(learn_var)
+        self._real_inventory = param_inventory(channels, in_channels, bool(attention), self.learn_var)
         channels = padded
         self.channels, self.in_channels, self.compute_dtype, self.act_dtype = channels, in_channels, compute_dtype, act_dtype
         self.dropout = float(dropout)      # nn.Dropout(p) of every ResBlock's out_layers (simple_unet.py:171); training mode only
         self.drop_seed, self._drop_counter = 0x5EEDD0, 0
         self.attention = bool(attention)
         self.attention_fp8 = int(attention) == 2      # attention=2: QK^T / PV on the fp8 matrix cores (BASELINE config 5)
-        self._inventory = param_inventory(channels, in_channels, self.attention)
+        self._inventory = param_inventory(channels, in_channels, self.attention, self.learn_var)
         # arena order: the 12 emb_layers Linear weights, their biases, the 12 conv1 biases (one batched GEMM with two bias
         # tables serves all 12 ResBlocks), then everything else in reference order; every tensor starts on a 16-byte boundary.
         emb_w = [f"{b}.emb_layers.1.weight" for b in RES_BLOCKS]
@@ -756,8 +761,12 @@ class SimpleUnet(nn.Module):
         self._freq_table(MAX_TIMESTEPS, dev)
         self._freq_table(4, dev)
 
-    def forward_hip(self, x, logsnr, guide=None, cond_w=None, ctx=None):
-        """x: NCHW fp32 [B, in_channels, H, W]; returns NCHW fp32.  ctx: dict receiving what backward needs."""
+    def forward_hip(self, x, logsnr, guide=None, cond_w=None, ctx=None, want_nu=False):
+        """x: NCHW fp32 [B, in_channels, H, W]; returns NCHW fp32.  ctx: dict receiving what backward needs.
+        want_nu (a learn_var network only): True, or the number of leading batch rows - also run the variance head, a second gmk_head_fwd on the
+        same stream, and return (v, nu), nu NCHW fp32 [rows, in_channels, H, W] (a guided 2 B batch needs nu of its conditional half alone)."""
+        if want_nu and not self.learn_var:
+            raise ValueError("forward_hip: want_nu on a network without the variance head (learn_var)")
         if self._packs_stale or self._packed_version != self._version_sum():
             self._repack()
         P, C, T = self._pv, self.channels, self.act_dtype
@@ -802,6 +811,11 @@ class SimpleUnet(nn.Module):
         if ctx is not None:
             ctx["net"] = (x, t2, t5, u0r, u3r, u6, ao, mo, ro)
             ctx["dims"] = (B, H, W)
+        if want_nu:
+            rows = B if want_nu is True else int(want_nu)
+            if not 1 <= rows <= B:
+                raise ValueError(f"forward_hip: want_nu = {want_nu} rows of a batch of {B}")
+            return out, ops.head_fwd(ao if rows == B else ao[:rows], P["out_var.weight"], P["out_var.bias"])
         return out
 
     def grad_buckets(self):
@@ -810,7 +824,7 @@ class SimpleUnet(nn.Module):
         names = [n for n, _ in self._inventory]
         def rng(pred):
             return self.arena_range([n for n in names if pred(n)])
-        late = ("up.seq.4", "up.seq.5", "up.seq.6", "out.")
+        late = ("up.seq.4", "up.seq.5", "up.seq.6", "out.", "out_var.")
         mid = ("up.seq.0", "up.seq.1", "up.seq.2", "up.seq.3")
         emb = ("time_embed", "cond_w_embed", "guide_embed")
         is_emb = lambda n: n.startswith(emb) or ".emb_layers." in n or n.endswith(".in_layers.2.bias")   # the arena's front block
@@ -824,8 +838,11 @@ class SimpleUnet(nn.Module):
         assert all(srt[i][1] == srt[i + 1][0] for i in range(3)), "gradient buckets must tile the arena"
         return buckets
 
-    def backward_hip(self, ctx, dout, on_grads_ready=None, join_side_before_ready=True, want_dx=False):
-        """dout: NCHW fp32 gradient of the network output.  Fills `flat_grads` (overwrites every touched slice); want_dx: also returns the
+    def backward_hip(self, ctx, dout, on_grads_ready=None, join_side_before_ready=True, want_dx=False, dnu=None):
+        """dout: NCHW fp32 gradient of the network output; dnu (a learn_var network only): the gradient of the variance
+        head's output nu, dout's shape - its weight gradient runs on the side stream like out.2's, its data gradient is added to out.2's;
+        None there: nu took no part, the out_var gradients are zeroed and nothing else is launched.
+        Fills `flat_grads` (overwrites every touched slice); want_dx: also returns the
         gradient of the input x (NCHW fp32, the stem's data gradient gmk_stem_dgrad), else None.
         on_grads_ready(k): called as soon as every kernel that writes bucket k of grad_buckets() has been ENQUEUED (overlapped gradient
         all-reduce).  A bucket is final only when the side stream's weight gradients are: with join_side_before_ready the current stream
@@ -842,12 +859,17 @@ class SimpleUnet(nn.Module):
             self._cu_part = (full, min(ops.WGRAD_CUS, full - 8))
             ops.set_cu_limit(full - self._cu_part[1])
             try:
-                return self.backward_hip(ctx, dout, on_grads_ready, join_side_before_ready, want_dx)
+                return self.backward_hip(ctx, dout, on_grads_ready, join_side_before_ready, want_dx, dnu)
             finally:
                 ops.set_cu_limit(full)
                 self._cu_part = None
+        if dnu is not None and not self.learn_var:
+            raise ValueError("backward_hip: dnu on a network without the variance head (learn_var)")
+        if dnu is not None and tuple(dnu.shape) != tuple(dout.shape):
+            raise ValueError(f"backward_hip: dnu has shape {tuple(dnu.shape)}, dout {tuple(dout.shape)}")
         join = self._join_side if (on_grads_ready is not None and join_side_before_ready) else None
-        dt0 = self._backward_schedule(ctx, ops.aligned(dout.float()), True, on_grads_ready, join)
+        dt0 = self._backward_schedule(ctx, ops.aligned(dout.float()), True, on_grads_ready, join,
+                                      dnu=None if dnu is None else ops.aligned(dnu.float()))
         return ops.stem_dgrad(dt0, self._pv["down.seq.0.conv.weight"]) if want_dx else None
 
     def input_vjp_hip(self, ctx, r):
@@ -861,7 +883,7 @@ class SimpleUnet(nn.Module):
         dt0 = self._backward_schedule(ctx, ops.aligned(r.float()), False)
         return ops.stem_dgrad(dt0, self._pv["down.seq.0.conv.weight"])
 
-    def _backward_schedule(self, ctx, dout, grads, ready=None, join=None):
+    def _backward_schedule(self, ctx, dout, grads, ready=None, join=None, dnu=None):
         """The one backward schedule: the order of the blocks and the wiring of the seven skip gradients.  dout: aligned NCHW fp32.
         grads=True (backward_hip): the data-gradient chain plus every weight, bias and embedding gradient into `flat_grads`, with join() /
         ready(k) once bucket k of grad_buckets() is enqueued.  grads=False (input_vjp_hip): the data-gradient chain alone.
@@ -907,6 +929,14 @@ class SimpleUnet(nn.Module):
             assert self._offsets["out.2.bias"] == o + (nhead + 3) // 4 * 4 == o + nhead
             self._on_side(lambda: ops.head_wgrad(dout, ao, self.flat_grads[o:o + nhead + self.in_channels]), (dout, ao))
         dao = ops.head_dgrad(dout, P["out.2.weight"], T)
+        if dnu is None and grads and self.learn_var:      # nu took no part: this pass still writes every gradient slice
+            self.flat_grads[self._offsets["out_var.weight"]:].zero_()      # (the arena's last two tensors)
+        if dnu is not None:                          # the variance head: the same two kernels once more, the data gradients summed
+            if grads:
+                ov = self._offsets["out_var.weight"]
+                assert self._offsets["out_var.bias"] == ov + nhead
+                self._on_side(lambda: ops.head_wgrad(dnu, ao, self.flat_grads[ov:ov + nhead + self.in_channels]), (dnu, ao))
+            ops.add_into(dao, ops.head_dgrad(dnu, P["out_var.weight"], T))
         s6 = torch.empty((B, C), device=dev, dtype=torch.float32) if grads else None
         du6, dgp, dbp = ops.gn_silu_bwd(dao, u6, P["out.0.weight"], P["out.0.bias"], mo, ro, dxsum=s6)
         if grads:
@@ -945,12 +975,15 @@ class SimpleUnet(nn.Module):
     def zero_grad_arena(self):
         self.flat_grads.zero_()
 
-    def forward(self, x, timesteps, guide=None, cond_w=None):
+    def forward(self, x, timesteps, guide=None, cond_w=None, want_nu=False):
         """Reference signature (simple_unet.py:44).  Differentiable through SimpleUnetFunction when grad is enabled and the parameters or
-        x require it (x: torch.autograd.grad(net(x, ...).sum(), x) works with frozen parameters too)."""
+        x require it (x: torch.autograd.grad(net(x, ...).sum(), x) works with frozen parameters too).  want_nu (a learn_var network):
+        -> (v, nu), both differentiable with respect to the parameters (SimpleUnetVarFunction)."""
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if want_nu:
+                return SimpleUnetVarFunction.apply(self, x, timesteps, guide, cond_w, *self.parameters())
             return SimpleUnetFunction.apply(self, x, timesteps, guide, cond_w, *self.parameters())
-        return self.forward_hip(x, timesteps, guide, cond_w)
+        return self.forward_hip(x, timesteps, guide, cond_w, want_nu=bool(want_nu))
 
 
 class SimpleUnetFunction(torch.autograd.Function):
@@ -979,3 +1012,26 @@ class SimpleUnetFunction(torch.autograd.Function):
             dx = net.input_vjp_hip(ctx.store, dout)
         # parameter gradients were written in place into p.grad (views of the arena): None for every parameter
         return (None, dx) + (None,) * (3 + len(list(net.parameters())))
+
+
+class SimpleUnetVarFunction(torch.autograd.Function):
+    """SimpleUnetFunction for both outputs (v, nu) of a learn_var network: backward_hip with the two output gradients.  Parameter gradients
+    only: the input gradient of a network whose variance output is in use is not implemented (input_vjp_hip follows v alone)."""
+
+    @staticmethod
+    def forward(ctx, net, x, timesteps, guide, cond_w, *params):
+        store = {}
+        v, nu = net.forward_hip(x, timesteps, guide, cond_w, ctx=store, want_nu=True)
+        ctx.net, ctx.store = net, store
+        return v, nu
+
+    @staticmethod
+    def backward(ctx, dv, dnu):
+        net = ctx.net
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("the input gradient of a learn_var network's (v, nu) pair is not implemented")
+        if any(ctx.needs_input_grad[5:]):
+            prev = net.flat_grads.clone()
+            net.backward_hip(ctx.store, dv, dnu=dnu)
+            net.flat_grads.add_(prev)
+        return (None,) * (5 + len(list(net.parameters())))

@@ -689,6 +689,15 @@ def head_wgrad(dout, a, dwb):
     return colsum(part, dwb)
 
 
+def add_into(a, b):
+    """a += b in place (gmk_add_into): two gradient tensors of one shape and type (fp32 or bf16), a multiple of 8 elements.  -> a"""
+    _chk(a, name="a"); _chk(b, a.dtype, "b")
+    if a.shape != b.shape or a.numel() % 8 or a.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"add_into: shapes {tuple(a.shape)} and {tuple(b.shape)} of {a.dtype}: one shape, a multiple of 8 elements, fp32 or bf16")
+    check(lib.gmk_add_into(_p(a), _p(b), a.numel(), _DT[a.dtype], _s()), "add_into")
+    return a
+
+
 def stem_dgrad(dy, w):
     """The network's input gradient through the stem: dy NHWC [B, H, W, C] (compute dtype) -> dx NCHW fp32 [B, cin, H, W], the transposed 3x3
     convolution with the stem weight w [C, cin, 3, 3] (gmk_stem_dgrad; an extension)."""
@@ -932,6 +941,31 @@ def v_loss(v, z, x, eps, logsnr, grad_scale=None, loss_type=0, mean_type="v"):
     check(lib.gmk_v_loss(_p(v), _p(z), _p(x), _p(eps), _p(logsnr), _p(loss_b), _p(xm), _p(em), _p(dv),
                          float(grad_scale or 0.0), loss_type, MEAN_TYPES[mean_type], B, n, _s()), "v_loss")
     return loss_b, xm, em, dv
+
+
+def hybrid_loss(v, nu, z, x, eps, logsnr, logsnr_s, vlb_lambda, grad_scale=None, loss_type=0, mean_type="v"):
+    """The hybrid loss of a learned reverse-process variance (gmk_hybrid_loss; Nichol & Dhariwal 2021, section 3.1; an extension): `v_loss`'s simple
+    loss (its x_mse, eps_mse and dv bits) plus vlb_lambda times the bound term vlb_b = mean_i KL(q(z_s | z_t, x) || p(z_s | z_t)) in nats per
+    dimension, p with the per-element 'medium' fraction f = (nu + 1) / 2 and the mean held constant.  v, nu, z, x, eps: fp32 [B, ...], contiguous
+    (16-byte aligned tensors with n % 4 == 0 take the 16-byte path, anything else the scalar one); logsnr, logsnr_s: fp32 [B], logsnr_s >= logsnr
+    the log-SNR one step of the bound's grid earlier.  -> (loss_b, vlb_b, frac_b, x_mse, eps_mse, dv or None, dnu or None), the gradients of
+    grad_scale sum_b loss_b when grad_scale is given."""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    if loss_type not in (0, 1):
+        raise ValueError(f"loss_type {loss_type!r}: 0 (snr_trunc) or 1 (snr)")
+    lam = float(vlb_lambda)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"vlb_lambda = {lam}: need a finite value >= 0")
+    B, n = _images(((x, "x"), (v, "v"), (nu, "nu"), (z, "z"), (eps, "eps")),
+                   ((logsnr, "logsnr", torch.float32), (logsnr_s, "logsnr_s", torch.float32)), "hybrid_loss")
+    loss_b = torch.empty((B,), device=x.device, dtype=torch.float32)
+    vlb, frac, xm, em = (torch.empty_like(loss_b) for _ in range(4))
+    dv = torch.empty_like(v) if grad_scale is not None else None
+    dnu = torch.empty_like(nu) if grad_scale is not None else None
+    check(lib.gmk_hybrid_loss(_p(v), _p(nu), _p(z), _p(x), _p(eps), _p(logsnr), _p(logsnr_s), _p(loss_b), _p(vlb), _p(frac), _p(xm), _p(em),
+                              _p(dv), _p(dnu), float(grad_scale or 0.0), lam, loss_type, MEAN_TYPES[mean_type], B, n, _s()), "hybrid_loss")
+    return loss_b, vlb, frac, xm, em, dv, dnu
 
 
 X_LOSS_WEIGHTS = {"snr_plus1": C["GMK_LOSS_W_SNR_PLUS1"], "min_snr": C["GMK_LOSS_W_MIN_SNR"]}      # the weightings gmk_x_loss_w evaluates
@@ -1548,6 +1582,42 @@ def stochastic_step(v, z, logsnr_t, logsnr_s, coef_z, coef_x, coef_noise, coef_p
     check(lib.gmk_stochastic_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(x_hist), None if thr is None else _p(_thr_check(thr, B)), *scalars,
                                   int(bool(is_last)), seed, offset, q0, _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None,
                                   _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()), "stochastic_step")
+    return ((z_next, z2) if dup else z_next), xp, ep
+
+
+def stochastic_step_lv(v, z, nu, logsnr_t, logsnr_s, coef_z, coef_x, coef_noise_small, half_delta, is_last, seed, offset, q0=0, thr=None,
+                       v_uncond=None, cond_w=None, want_pred=False, mean_type="v", dup=False, logsnr_next=None):
+    """One 'ancestral' step under a learned variance (gmk_stochastic_step_lv; Nichol & Dhariwal 2021): `stochastic_step` with coef_prev = 0 and the
+    noise multiplier coef_noise_small exp(f half_delta) per element, f = (nu + 1) / 2 - nu: fp32 of z's shape, the network's second output (the
+    conditional half's under guidance); coef_noise_small: the 'small' row of `gaussian_diffusion.stochastic_row`; half_delta =
+    (softplus(logsnr_s) - softplus(logsnr_t)) / 2 >= 0.  nu = -1 everywhere gives the bits of `stochastic_step` under 'small'.  Arguments and
+    returns otherwise as `stochastic_step`."""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    shape = tuple(z.shape)
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f"z: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
+    if math.prod(shape[1:]) % 4:
+        raise ValueError(f"z: {math.prod(shape[1:])} values per image, a multiple of 4 is required")
+    scalars = tuple(float(s) for s in (logsnr_t, logsnr_s, coef_z, coef_x, coef_noise_small, half_delta))
+    if not all(math.isfinite(s) for s in scalars):
+        raise ValueError(f"stochastic_step_lv: non-finite time or coefficient {scalars}")
+    if scalars[4] < 0.0:
+        raise ValueError(f"coef_noise_small = {scalars[4]}: a standard deviation, need >= 0")
+    if scalars[5] < 0.0:
+        raise ValueError(f"half_delta = {scalars[5]}: half of logvar_large - logvar_small, need >= 0")
+    seed, offset = check_stream(seed, offset)
+    q0 = int(q0)
+    if not 0 <= q0 < 1 << 64:
+        raise ValueError(f"q0 = {q0}: an unsigned 64-bit Philox counter offset")
+    if (v_uncond is None) != (cond_w is None):
+        raise ValueError("stochastic_step_lv: v_uncond and cond_w go together")
+    if nu is None:
+        raise ValueError("stochastic_step_lv: nu is required (the network's variance output)")
+    B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((nu, "nu"), (v_uncond, "v_uncond")), cond_w, want_pred, dup, logsnr_next)
+    check(lib.gmk_stochastic_step_lv(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(nu), None if thr is None else _p(_thr_check(thr, B)), *scalars,
+                                     int(bool(is_last)), seed, offset, q0, _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None,
+                                     _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()), "stochastic_step_lv")
     return ((z_next, z2) if dup else z_next), xp, ep
 
 

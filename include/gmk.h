@@ -688,6 +688,39 @@ int gmk_stochastic_step(const float* v, const float* v_uncond, const float* cond
                         uint64_t seed, uint64_t offset, uint64_t q0, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
                         float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
 
+/* ---- a learned reverse-process variance (Nichol & Dhariwal 2021, "Improved Denoising Diffusion Probabilistic Models", section 3.1); extensions,
+ * no reference call site.  The network's second head gives nu, fp32 [B][n] beside v; f_i = (nu_i + 1) / 2 (unclamped, as in the paper) is the
+ * weight of diffusion_reverse's 'large' log-variance in its 'medium' interpolation, per element.
+ * gmk_hybrid_loss: per image b with lt = logsnr[b], ls = logsnr_s[b] >= lt (the time one step of the bound's grid earlier),
+ *   x_hat, eps_hat, x_mse, eps_mse, simple_b (by loss_type, mean_type) and dv: gmk_v_loss's, from the same device functions in the same order -
+ *   x_mse, eps_mse and dv carry gmk_v_loss's bits for the same (v, z, x, eps, logsnr).
+ *   D    = softplus(ls) - softplus(lt)                       (logvar_large - logvar_small)
+ *   g    = -expm1(lt - ls) e^ls
+ *   d_i  = x_hat_i - x_i                                     (the clipped prediction; the mean is a constant: stop-gradient)
+ *   KL_i = (f_i D + expm1(-f_i D) + e^(-f_i D) g d_i^2) / 2  = normal_kl(q(z_s | z_t, x), p(z_s | z_t)) with diffusion_reverse's variances
+ *   vlb_b[b] = mean_i KL_i (nats per dimension),  frac_b[b] = mean_i f_i,  loss_b[b] = simple_b + lambda vlb_b[b]
+ *   dnu_i = grad_scale lambda / n  D / 4  (1 - e^(-f_i D) (1 + g d_i^2))        (dv, dnu: both or neither)
+ * ls == lt gives KL = 0 and dnu = 0 from the formulas.  One workgroup per image; v, nu, z, x, eps are read once for images of up to
+ * GMK_X_LOSS_KEEP values (larger ones read v, z, x, eps twice, nu once); 16-byte accesses when n % 4 == 0 and every tensor is 16-byte aligned,
+ * scalar ones otherwise; any n.  lambda: finite, >= 0.  No floating-point atomics: the same call gives the same bits.  No row of GMK_KERNEL_TABLE. */
+int gmk_hybrid_loss(const float* v, const float* nu, const float* z, const float* x, const float* eps, const float* logsnr,
+                    const float* logsnr_s, float* loss_b, float* vlb_b, float* frac_b, float* x_mse, float* eps_mse, float* dv, float* dnu,
+                    float grad_scale, float lambda, int loss_type, int mean_type, int B, int64_t n, void* stream);
+/* gmk_stochastic_step for kind 'ancestral' (coef_prev = 0, no x_hist) with a noise multiplier per element:
+ *     c_i    = fmul(coef_noise_small, exp(fmul(fmul(0.5, fadd(nu_i, 1)), half_delta)))
+ *     z_next = is_last ? x_hat : fadd(fadd(fmul(coef_z, z), fmul(coef_x, x_hat)), fmul(c_i, xi))
+ * coef_noise_small: the 'small' row of gaussian_diffusion.stochastic_row; half_delta = (softplus(ls) - softplus(lt)) / 2 >= 0, both from the host
+ * in double, rounded to fp32.  nu: fp32 [B][n] (under guidance the conditional half's).  With nu = -1 everywhere z_next carries the bits of
+ * gmk_stochastic_step under 'small'.  x_hat, thr, guidance, the Philox draw at (seed, offset + q0), is_last, x_pred / eps_pred / z_dup /
+ * logsnr_next, n % 4 == 0: gmk_stochastic_step's.  No row of GMK_KERNEL_TABLE. */
+int gmk_stochastic_step_lv(const float* v, const float* v_uncond, const float* cond_w, const float* z, const float* nu, const float* thr,
+                           float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_noise_small, float half_delta, int is_last,
+                           uint64_t seed, uint64_t offset, uint64_t q0, float* z_next, float* x_pred, float* eps_pred, float* z_dup,
+                           float* logsnr_next, int mean_type, int B, int64_t n, void* stream);
+/* a[i] += b[i] (rounded once to dtype, GMK_F32 or GMK_BF16; n % 8 == 0, 16-byte aligned): the sum of the two heads' data gradients of a
+ * learn_var network ahead of the last GroupNorm's backward. */
+int gmk_add_into(void* a, const void* b, int64_t n, int dtype, void* stream);
+
 /* ---- optimiser (torch.optim.Adam defaults as diffusion_model.py:56 uses it), flat fp32 arena ------------- */
 int gmk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, int step, float grad_scale, void* stream);

@@ -1,0 +1,616 @@
+"""GPU tests of the learned reverse-process variance (Nichol & Dhariwal 2021, section 3.1): gmk_hybrid_loss bit for bit against gmk_v_loss
+(x_mse, eps_mse, dv) and against the float64 restatement (tests/learned_var_ref.py; vlb_b, dnu), gmk_stochastic_step_lv bit for bit against
+gmk_stochastic_step under 'small' and against the restatement's per-element noise scale, the network's second head forward and backward
+against oracle/unet_ref.py in float64, and the model end to end (training, sampling, resuming).
+
+The error rule of the two kernels' float comparisons (`within`): the device may be off from the float64 value by four times what the same
+closed form is off when torch evaluates it in fp32 on the CPU on the same inputs (the factor covers the device's exp / expm1 differing from
+the host's by a few ulp), plus 1e-6 of the largest entry of the float64 value.  Both errors are printed.
+"""
+import math
+import os
+import sys
+from functools import partial
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import learned_var_ref as R  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MEAN_TYPES = ("v", "eps", "x")
+VLB_T = 1000
+U24 = 2.0 ** -24
+
+
+def f64(t):
+    return t.detach().double().cpu()
+
+
+def within(dev, cpu32, ref64, what):
+    """The error rule of the module docstring.  -> (device error, CPU fp32 error), largest absolute entries; prints both."""
+    e_dev = float((f64(dev) - ref64).abs().max())
+    e_cpu = float((cpu32.double() - ref64).abs().max())
+    top = float(ref64.abs().max())
+    print(f"{what}: device error {e_dev:.3e}, CPU fp32 error {e_cpu:.3e}, largest entry {top:.3e}")
+    assert e_dev <= 4.0 * e_cpu + 1e-6 * top, (what, e_dev, e_cpu, top)
+    return e_dev, e_cpu
+
+
+# ---- the loss kernel ----------------------------------------------------------------------------------------------------------------------------
+# per case: the ends of the schedule with a zero-length pair (u = 0: u - 1 / T clamps to 0, so ls == lt; u = 1 / T: ls = logsnr_max; u = 1:
+# lt = logsnr_min), and three times in between
+TIME_SETS = ((0.0, 1.0 / VLB_T, 1.0), (0.3, 0.6, 0.97))
+
+
+def _loss_case(n, mean_type, u, seed):
+    """fp32 device inputs of one loss call: a prediction near the target (so that some raw x-hats clip and some do not) and a spread-out nu."""
+    from generative_models_amd import ops
+    g = torch.Generator().manual_seed(seed)
+    B = len(u)
+    x = (torch.rand((B, n), generator=g) * 2.4 - 1.2).clamp_(-1, 1)
+    eps = torch.randn((B, n), generator=g)
+    u = torch.tensor(u, dtype=torch.float32).cuda()
+    lt = ops.logsnr_schedule(B, "cuda", u=u)
+    ls = ops.logsnr_schedule(B, "cuda", u=ops.aligned((u - 1.0 / VLB_T).clamp_(min=0.0)))
+    al, si = torch.sqrt(torch.sigmoid(lt.cpu()))[:, None], torch.sqrt(torch.sigmoid(-lt.cpu()))[:, None]
+    z = al * x + si * eps
+    target = {"v": al * eps - si * x, "eps": eps, "x": x}[mean_type]
+    v = target + 0.4 * torch.randn((B, n), generator=g)
+    nu = 0.8 * torch.randn((B, n), generator=g)
+    return tuple(t.contiguous().cuda() for t in (v, nu, z, x, eps)) + (lt, ls)
+
+
+@pytest.mark.parametrize("loss_type", [0, 1], ids=["snr_trunc", "snr"])
+@pytest.mark.parametrize("mean_type", MEAN_TYPES)
+@pytest.mark.parametrize("n", [64, 432, 49, 12300, 12291])      # 49, 12291: the scalar path; 12300, 12291: above the 12,288 values kept in LDS
+def test_hybrid_loss(n, mean_type, loss_type):
+    from generative_models_amd import ops
+    assert ops.X_LOSS_KEEP == 12288
+    lam, gs = 0.001, 1.0 / 3
+    for k, u in enumerate(TIME_SETS):
+        v, nu, z, x, eps, lt, ls = _loss_case(n, mean_type, u, 100 * n + k)
+        assert bool((ls >= lt).all())
+        if k == 0:      # the zero-length pair, the first step below logsnr_max and the last one down to logsnr_min
+            assert float(ls[0]) == float(lt[0]) == float(ls[1]) and abs(float(ls[1]) - 20.0) <= 1e-4 and abs(float(lt[2]) + 20.0) <= 1e-2
+        got = ops.hybrid_loss(v, nu, z, x, eps, lt, ls, lam, grad_scale=gs, loss_type=loss_type, mean_type=mean_type)
+        loss_b, vlb, frac, xm, em, dv, dnu = got
+        # the simple loss: gmk_v_loss's bits
+        loss_v, xm_v, em_v, dv_v = ops.v_loss(v, z, x, eps, lt, grad_scale=gs, loss_type=loss_type, mean_type=mean_type)
+        assert torch.equal(xm, xm_v) and torch.equal(em, em_v) and torch.equal(dv, dv_v), (n, mean_type, loss_type, k)
+        assert bool((dv == 0).any()) and bool((dv != 0).any())          # clipped and unclipped predictions both occur
+        # the bound: the float64 restatement on the same fp32 inputs, and the same closed form in fp32 on the CPU
+        args64 = tuple(f64(t) for t in (v, nu, z, x, eps, lt, ls))
+        args32 = tuple(t.detach().cpu() for t in (v, nu, z, x, eps, lt, ls))
+        ref = R.hybrid_loss(*args64, lam, gs, loss_type, mean_type)
+        cpu = R.hybrid_loss(*args32, lam, gs, loss_type, mean_type)
+        tag = f"n = {n}, {mean_type}, loss_type {loss_type}, times {k}"
+        within(vlb, cpu["vlb"], ref["vlb"], tag + ", vlb_b")
+        within(dnu, cpu["dnu"], ref["dnu"], tag + ", dnu")
+        within(loss_b, cpu["loss"], ref["loss"], tag + ", loss_b")
+        assert float((f64(frac) - ref["frac"]).abs().max()) <= 1e-6
+        assert torch.equal(loss_b, loss_v + lam * vlb) or float((f64(loss_b) - f64(loss_v) - lam * f64(vlb)).abs().max()) <= 2 * U24 * float(f64(loss_b).abs().max())
+        if k == 0:      # the zero-length pair: KL = 0 and dnu = 0 from the formula itself
+            assert float(vlb[0]) == 0.0 and float(dnu[0].abs().max()) == 0.0 and float(loss_b[0]) == float(loss_v[0])
+            assert float(vlb[1]) > 0.0 and float(dnu[1].abs().max()) > 0.0
+        # without gradients: the same numbers; and twice the same call, the same bits
+        plain = ops.hybrid_loss(v, nu, z, x, eps, lt, ls, lam, loss_type=loss_type, mean_type=mean_type)
+        assert plain[5] is None and plain[6] is None and all(torch.equal(a, b) for a, b in zip(plain[:5], got[:5]))
+        again = ops.hybrid_loss(v, nu, z, x, eps, lt, ls, lam, grad_scale=gs, loss_type=loss_type, mean_type=mean_type)
+        assert all(torch.equal(a, b) for a, b in zip(again, got))
+        # lambda = 0: the simple loss alone, and no gradient to nu
+        zero = ops.hybrid_loss(v, nu, z, x, eps, lt, ls, 0.0, grad_scale=gs, loss_type=loss_type, mean_type=mean_type)
+        assert torch.equal(zero[0], loss_v) and torch.equal(zero[1], vlb) and torch.equal(zero[5], dv_v) and float(zero[6].abs().max()) == 0.0
+
+
+def test_hybrid_loss_unaligned_tensors_take_the_scalar_path():
+    """n % 4 == 0 but a tensor that starts 4 bytes past a 16-byte boundary: x_mse, eps_mse and both gradients carry the aligned call's bits."""
+    from generative_models_amd import ops
+    v, nu, z, x, eps, lt, ls = _loss_case(64, "v", TIME_SETS[1], 7)
+    want = ops.hybrid_loss(v, nu, z, x, eps, lt, ls, 0.001, grad_scale=0.5)
+    buf = torch.empty(nu.numel() + 1, device="cuda")
+    off = buf[1:].view_as(nu)
+    off.copy_(nu)
+    assert off.data_ptr() % 16 == 4 and off.is_contiguous()
+    got = ops.hybrid_loss(v, off, z, x, eps, lt, ls, 0.001, grad_scale=0.5)
+    for a, b in zip(got[3:], want[3:]):
+        assert torch.equal(a, b)                         # x_mse, eps_mse, dv: one order of summation on either path; dnu: elementwise
+    # vlb_b and frac_b are per-thread sums over the elements a thread loads, which the two paths deal out differently: equal to rounding
+    assert torch.allclose(got[1], want[1], rtol=1e-5, atol=0.0) and torch.allclose(got[2], want[2], rtol=0.0, atol=1e-6)
+    assert torch.allclose(got[0], want[0], rtol=1e-5, atol=0.0)
+
+
+def test_hybrid_loss_refuses_bad_arguments():
+    from generative_models_amd import ops
+    v, nu, z, x, eps, lt, ls = _loss_case(64, "v", TIME_SETS[1], 8)
+    for lam in (-1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="vlb_lambda"):
+            ops.hybrid_loss(v, nu, z, x, eps, lt, ls, lam)
+    with pytest.raises(ValueError, match="mean_type"):
+        ops.hybrid_loss(v, nu, z, x, eps, lt, ls, 0.001, mean_type="both")
+    with pytest.raises(ValueError, match="nu"):
+        ops.hybrid_loss(v, nu[:, :32].contiguous(), z, x, eps, lt, ls, 0.001)
+
+
+# ---- the sampler kernel -------------------------------------------------------------------------------------------------------------------------
+def _cpu_step32(z, xh, xi, c_z, c_x, cn_small, hd, nu):
+    """The update in fp32 on the CPU, the kernel's order: every coefficient rounded to fp32, every operation rounded once."""
+    f32 = lambda c: torch.tensor(c, dtype=torch.float32)
+    cn = f32(cn_small) * torch.exp((0.5 * (nu + 1.0)) * f32(hd))
+    return (f32(c_z) * z + f32(c_x) * xh) + cn * xi
+
+
+@pytest.mark.parametrize("guided", [False, True], ids=["unguided", "guided"])
+@pytest.mark.parametrize("mt", MEAN_TYPES)
+@pytest.mark.parametrize("n", [64, 432])
+def test_step_lv_kernel(n, mt, guided):
+    from generative_models_amd import ops
+    from generative_models_amd.diffusion.gaussian_diffusion import learned_half_delta, stochastic_row
+    B, seed, offset = 4, 91, 2000
+    g = torch.Generator().manual_seed(n + 7 * guided)
+    rnd = lambda *s: torch.randn(*s, generator=g).cuda()
+    for lt, ls in ((-15.0, -2.5), (-2.5, 3.0), (3.0, 15.0)):
+        v, z = rnd(B, n), rnd(B, n)
+        kw = dict(v_uncond=rnd(B, n), cond_w=(4.0 * torch.rand(B, generator=g)).cuda(), mean_type=mt) if guided else dict(mean_type=mt)
+        thr = (1.0 + torch.rand(B, generator=g)).cuda()
+        c_z, c_x, cn_small = stochastic_row("ancestral", lt, ls, 0.0)
+        hd = learned_half_delta(lt, ls)
+        lv = lambda nu, **more: ops.stochastic_step_lv(v, z, nu, lt, ls, c_z, c_x, cn_small, hd, False, seed, offset, **{**kw, **more})
+        # nu = -1: gmk_stochastic_step under 'small', bit for bit; with thr too
+        minus = torch.full((B, n), -1.0, device="cuda")
+        small = ops.stochastic_step(v, z, lt, ls, c_z, c_x, cn_small, 0.0, False, seed, offset, want_pred=True, **kw)
+        got = lv(minus, want_pred=True)
+        assert torch.equal(got[0], small[0]) and torch.equal(got[1], small[1]) and torch.equal(got[2], small[2]), (lt, ls)
+        small_t = ops.stochastic_step(v, z, lt, ls, c_z, c_x, cn_small, 0.0, False, seed, offset, thr=thr, want_pred=True, **kw)
+        got_t = lv(minus, thr=thr, want_pred=True)
+        assert all(torch.equal(a, b) for a, b in zip(got_t, small_t))
+        xh, xi = got[1], ops.rng_normal((B, n), seed, offset, "cuda")
+        # nu = +1 and nu = -0.4: 'large' and 'medium:0.3'
+        for nu_val, frac in ((1.0, 1.0), (-0.4, 0.3)):
+            nu = torch.full((B, n), nu_val, device="cuda")
+            row = stochastic_row("ancestral", lt, ls, frac)
+            assert row[:2] == (c_z, c_x)
+            ref = c_z * f64(z) + c_x * f64(xh) + row[2] * f64(xi)
+            cpu = _cpu_step32(z.cpu(), xh.cpu(), xi.cpu(), c_z, c_x, cn_small, hd, nu.cpu())
+            within(lv(nu)[0], cpu, ref, f"n = {n}, {mt}, step {lt} -> {ls}, nu = {nu_val}")
+        # a random nu: (z_next - deterministic part) / xi is the restatement's per-element scale.  The deterministic part is two products and
+        # a sum, each rounded once: torch's fp32 on the device restates it bit for bit.  What is left is fl(det + fl(c_i xi)) - det: the sum's
+        # rounding, at most 2^-24 |z_next| (2^-23 allowed), plus the error of c_i xi: coef_noise_small and half_delta rounded from double, nu + 1,
+        # the halving (exact), f half_delta =: a, the last product (u = 2^-24 each), exp within a few ulp, and the argument's error, which exp
+        # turns into a relative error of about 2 u |a|: (8 + 4 |a|) u |c_i xi| allowed
+        nu = (0.9 * rnd(B, n)).contiguous()
+        z_next, xp, _ = lv(nu, want_pred=True)
+        assert torch.equal(xp, xh)
+        f32c = lambda c: torch.tensor(c, dtype=torch.float32, device="cuda")
+        det = f32c(c_z) * z + f32c(c_x) * xh
+        scale = R.noise_scale(f64(nu), cn_small, hd)
+        a = (0.5 * (f64(nu) + 1.0) * hd).abs()
+        err = ((f64(z_next) - f64(det)) - scale * f64(xi)).abs()
+        bound = 2.0 ** -23 * f64(z_next).abs() + (8.0 + 4.0 * a) * U24 * (scale * f64(xi)).abs()
+        assert bool((err <= bound).all()), (lt, ls, float((err / bound).max()))
+        drawn = f64(xi) != 0                           # the same comparison as a quotient: (z_next - det) / xi against the scale
+        ratio = (f64(z_next) - f64(det))[drawn] / f64(xi)[drawn]
+        assert bool(((ratio - scale[drawn]).abs() <= (bound[drawn] / f64(xi)[drawn].abs())).all())
+        assert float(scale.max()) > float(scale.min()) and not torch.equal(z_next, small[0])      # nu does change the scale
+        # rows [a, b) at q0 = a n / 4 draw what the whole batch draws
+        for lo, hi in ((0, 1), (1, 4)):
+            cut = lambda t: None if t is None else ops.aligned(t[lo:hi])
+            part = ops.stochastic_step_lv(cut(v), cut(z), cut(nu), lt, ls, c_z, c_x, cn_small, hd, False, seed, offset, q0=lo * n // 4,
+                                          v_uncond=cut(kw.get("v_uncond")), cond_w=cut(kw.get("cond_w")), mean_type=mt)[0]
+            assert torch.equal(part, z_next[lo:hi]), (lo, hi)
+        # the last step returns x-hat and draws nothing: any counter, any nu, the same
+        last = ops.stochastic_step_lv(v, z, nu, lt, ls, c_z, c_x, cn_small, hd, True, seed + 1, offset + 64, want_pred=True, **kw)
+        assert torch.equal(last[0], xh) and torch.equal(last[1], xh)
+        assert torch.equal(ops.stochastic_step_lv(v, z, torch.full_like(nu, float("nan")), lt, ls, c_z, c_x, cn_small, hd, True, 5, 0, **kw)[0], xh)
+        # z_dup and logsnr_next: gmk_stochastic_step's conventions
+        lnext = torch.zeros((2 * B,), device="cuda")
+        (zn, z2), _, _ = lv(nu, dup=True, logsnr_next=lnext)
+        assert torch.equal(zn, z_next) and torch.equal(z2[:B], z_next) and torch.equal(z2[B:], z_next)
+        assert torch.equal(lnext, torch.full((2 * B,), float(np.float32(ls)), device="cuda"))
+        offset += 4096
+    with pytest.raises(ValueError, match="multiple of 4"):
+        ops.stochastic_step_lv(torch.zeros((B, 25), device="cuda"), torch.zeros((B, 25), device="cuda"), torch.zeros((B, 25), device="cuda"),
+                               0.0, 1.0, 0.5, 0.5, 0.1, 0.2, False, seed, 0)
+    with pytest.raises(ValueError, match="half_delta"):
+        ops.stochastic_step_lv(v, z, nu, 0.0, 1.0, 0.5, 0.5, 0.1, -0.2, False, seed, 0)
+
+
+# ---- the network ----------------------------------------------------------------------------------------------------------------------------------
+C, S = 128, 8
+TOL32 = 1e-3
+GRAD16 = {"cosine": 0.9999, "rel_l2": 1.5e-2}          # the README's whole-gradient statement for the 16-bit mode
+
+
+def _params(in_channels, seed=3):
+    """Default-init-scale weights of the reference's inventory (every convolution live) plus a variance head of the same scale."""
+    from oracle import unet_ref as U
+    p = U.reference_init_params(C, in_channels, zero_out_layers=False)
+    g = torch.Generator().manual_seed(seed)
+    bound = 1.0 / math.sqrt(C * 9)
+    head = {"out_var.weight": (torch.rand((in_channels, C, 3, 3), generator=g) * 2 - 1) * bound,
+            "out_var.bias": (torch.rand((in_channels,), generator=g) * 2 - 1) * bound}
+    return p, head
+
+
+def _nets(in_channels, dtype):
+    from generative_models_amd.diffusion.simple_unet import SimpleUnet
+    p, head = _params(in_channels)
+    plain = SimpleUnet(C, 0.0, in_channels=in_channels, compute_dtype=dtype)
+    plain.load_state_dict(p, strict=True)
+    lv = SimpleUnet(C, 0.0, in_channels=in_channels, compute_dtype=dtype, learn_var=True)
+    lv.load_state_dict({**p, **head}, strict=True)
+    return plain.cuda(), lv.cuda(), p, head
+
+
+def _batch(in_channels, B=2, seed=13):
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.rand((B, in_channels, S, S), generator=g) * 2 - 1)
+    return x.cuda(), torch.randn((B, in_channels, S, S), generator=g).cuda(), torch.tensor([0.35, 0.7][:B]).cuda(), torch.tensor([4, -1][:B]).cuda()
+
+
+def rel_err(a, b):
+    a, b = f64(a), f64(b)
+    return float((a - b).abs().max() / max(1e-6, float(b.abs().max())))
+
+
+@pytest.mark.parametrize("in_channels", [1, 3])
+def test_forward_with_the_variance_head(in_channels):
+    plain, lv, p, head = _nets(in_channels, torch.float32)
+    x, eps, u, y = _batch(in_channels)
+    l = torch.tensor([-2.0, 4.0]).cuda()
+    v0 = lv.forward_hip(x, l, y, None)
+    ctx = {}
+    v, nu = lv.forward_hip(x, l, y, None, ctx=ctx, want_nu=True)
+    assert torch.equal(v, v0) and torch.equal(v, plain.forward_hip(x, l, y, None))          # the same launches for v
+    assert nu.shape == v.shape and nu.dtype == torch.float32 and nu.is_contiguous()
+    ao = ctx["net"][6]                                                                    # NHWC, what out.2 reads
+    want = F.conv2d(f64(ao).permute(0, 3, 1, 2), head["out_var.weight"].double(), head["out_var.bias"].double(), padding=1)
+    assert rel_err(nu, want) <= TOL32
+    # the conditional half alone: the first rows of the whole batch's nu
+    v1, nu1 = lv.forward_hip(x, l, y, None, want_nu=1)
+    assert torch.equal(v1, v) and torch.equal(nu1, nu[:1])
+    with pytest.raises(ValueError, match="want_nu"):
+        lv.forward_hip(x, l, y, None, want_nu=3)
+    with pytest.raises(ValueError, match="learn_var"):
+        plain.forward_hip(x, l, y, None, want_nu=True)
+
+
+def _train_pass(net, in_channels, **kw):
+    from generative_models_amd.diffusion.gaussian_diffusion import GaussianDiffusion
+    x, eps, u, y = _batch(in_channels)
+    d = GaussianDiffusion(mean_type="v", num_steps=4, vlb_steps=100, **kw)
+    net.zero_grad_arena()
+    out = d.train_forward_backward(net=partial(net, guide=y), x=x, grad_scale=0.5, u=u, eps=eps)
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("in_channels", [1, 3])
+def test_lambda_zero_is_the_plain_models_gradient(in_channels):
+    """vlb_lambda = 0: dnu is zero, so every gradient the two models share is the plain model's, and the head's own gradient is exactly zero."""
+    plain, lv, _, _ = _nets(in_channels, torch.float32)
+    a = _train_pass(plain, in_channels)
+    b = _train_pass(lv, in_channels, learn_var=1, vlb_lambda=0.0)
+    assert torch.equal(a["loss"], b["loss"]) and torch.equal(a["x_mse"], b["x_mse"]) and float(b["vlb"].min()) > 0.0
+    n0 = plain._arena_size
+    assert lv._arena_size > n0 and all(lv._offsets[k] == o for k, o in plain._offsets.items())
+    assert torch.equal(lv.flat_grads[:n0], plain.flat_grads) and float(plain.flat_grads.abs().max()) > 0.0
+    assert float(lv.flat_grads[n0:].abs().max()) == 0.0
+    assert float(lv.grad("out_var.weight").abs().max()) == 0.0 and float(lv.grad("out_var.bias").abs().max()) == 0.0
+
+
+@pytest.fixture
+def oracle64(monkeypatch):
+    """oracle/unet_ref.py for float64 weights -> forward(P, z, lt, y) -> (v, nu), nu a torch convolution of the activation out.2 reads.
+    The oracle forms its sinusoidal and one-hot features in fp32 (`.float()`, as the reference does) INSIDE unet_forward and hands them to
+    F.linear with the caller's weights, so float64 weights raise a dtype error there, and nothing passed in at the call can widen a tensor that
+    is made between two uses of the same parameter dict.  The one route without touching the module would be fp32 weights for the whole
+    embedding path, which makes the reference fp32 exactly where the new head's gradient flows back into shared weights.  So, for the duration
+    of a test, `_mlp` casts its input to the dtype of its weights: the features keep their fp32 values, every product is float64, and the file
+    itself is as committed."""
+    from oracle import unet_ref as U
+    mlp = U._mlp
+    monkeypatch.setattr(U, "_mlp", lambda p, prefix, x: mlp(p, prefix, x.to(p[f"{prefix}.0.weight"].dtype)))
+
+    def forward(P, z, lt, y):
+        taps = {}
+        v = U.unet_forward(P, z, lt, guide=y, taps=taps)
+        ao = U.gn_silu(taps["up.6"], P["out.0.weight"], P["out.0.bias"])
+        return v, F.conv2d(ao, P["out_var.weight"], P["out_var.bias"], padding=1)
+    return forward
+
+
+def _grad_errors(net, P, names=None):
+    """The device gradient against the float64 one over `names` (default: every parameter with a gradient).  -> (relative L2, cosine)"""
+    names = [k for k in P if P[k].grad is not None] if names is None else names
+    want = torch.cat([P[k].grad.reshape(-1) for k in names])
+    got = torch.cat([f64(net.grad(k)).reshape(-1) for k in names])
+    return float((got - want).norm() / want.norm()), float((got @ want) / (got.norm() * want.norm()))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "16bit"])
+@pytest.mark.parametrize("in_channels", [1, 3])
+def test_backward_with_a_variance_gradient_of_dvs_size(in_channels, dtype, oracle64):
+    """backward_hip with a random dnu of dout's magnitude against float64 autograd of (v . dout + nu . dnu): the shared gradients (everything
+    but out_var.*) and the whole gradient, at the bars of the whole-gradient test - fp32 mode 1e-3 relative L2, 16-bit mode cosine >= 0.9999 and
+    relative L2 <= 1.5e-2.  Here the second head's data gradient is half of what flows back (the control below measures its share), so a wrong
+    or missing head_dgrad / gmk_add_into fails.  dnu = None on the same network: nu took no part - the plain model's shared gradients, zeros
+    for out_var.*."""
+    plain, lv, p, head = _nets(in_channels, dtype)
+    x, eps, u, y = _batch(in_channels)
+    B = x.shape[0]
+    l = torch.tensor([-2.0, 4.0]).cuda()
+    g = torch.Generator().manual_seed(31)
+    dout = (torch.randn(x.shape, generator=g) / x[0].numel()).cuda()
+    dnu = (torch.randn(x.shape, generator=g) / x[0].numel()).cuda()
+    ctx = {}
+    v_dev, nu_dev = lv.forward_hip(x, l, y, None, ctx=ctx, want_nu=True)
+    lv.zero_grad_arena()
+    lv.backward_hip(ctx, dout, dnu=dnu)
+    torch.cuda.synchronize()
+    both = lv.flat_grads.clone()
+    P = {k: t.double().clone().requires_grad_(True) for k, t in {**p, **head}.items()}
+    v, nu = oracle64(P, f64(x), f64(l), y.cpu())
+    assert rel_err(v_dev, v) <= (TOL32 if dtype == torch.float32 else 1e-2) and rel_err(nu_dev, nu) <= (TOL32 if dtype == torch.float32 else 1e-2)
+    ((v * f64(dout)).sum() + (nu * f64(dnu)).sum()).backward()
+    names = [k for k in P if P[k].grad is not None]
+    shared = [k for k in names if not k.startswith("out_var.")]
+    assert len(shared) == len(names) - 2 and bool(torch.isfinite(torch.cat([lv.grad(k).reshape(-1) for k in names])).all())
+    whole_l2, whole_cos = _grad_errors(lv, P)
+    shared_l2, shared_cos = _grad_errors(lv, P, shared)
+    head_l2, _ = _grad_errors(lv, P, ["out_var.weight", "out_var.bias"])
+    # the control: the same pass without dnu, against the same float64 gradient - how much of the shared gradient the second head carries
+    ctx = {}
+    lv.forward_hip(x, l, y, None, ctx=ctx, want_nu=True)
+    lv.zero_grad_arena()
+    lv.flat_grads[plain._arena_size:].fill_(float("nan"))   # the head's slice: the pass has to write it
+    lv.backward_hip(ctx, dout)
+    torch.cuda.synchronize()
+    without_l2, _ = _grad_errors(lv, P, shared)
+    print(f"in_channels {in_channels}, {dtype}: random dnu: whole gradient relative L2 {whole_l2:.3e}, cosine {whole_cos:.7f}; shared {shared_l2:.3e}, "
+          f"{shared_cos:.7f}; out_var.* {head_l2:.3e}; shared without the second head's data gradient {without_l2:.3e}")
+    assert without_l2 >= 0.2                                # dropping the second head's data gradient is a first-order error
+    if dtype == torch.float32:
+        assert whole_l2 <= TOL32 and shared_l2 <= TOL32 and head_l2 <= TOL32
+    else:
+        assert whole_cos >= GRAD16["cosine"] and whole_l2 <= GRAD16["rel_l2"] and shared_cos >= GRAD16["cosine"] and shared_l2 <= GRAD16["rel_l2"]
+    # dnu = None: the plain model's gradients for everything shared, zeros for the head
+    n0 = plain._arena_size
+    ctx = {}
+    plain.forward_hip(x, l, y, None, ctx=ctx)
+    plain.backward_hip(ctx, dout)
+    torch.cuda.synchronize()
+    assert torch.equal(lv.flat_grads[:n0], plain.flat_grads) and float(lv.flat_grads[n0:].abs().max()) == 0.0
+    assert not torch.equal(both[:n0], plain.flat_grads)
+    with pytest.raises(ValueError, match="learn_var"):
+        plain.backward_hip(ctx, dout, dnu=dnu)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_add_into(dtype):
+    """gmk_add_into against torch: a + b rounded once to the type, so the same bits - at one vector per thread, at sizes that are no multiple
+    of a block's 2048 elements, and past the grid's 4096 blocks (the grid-stride loop)."""
+    from generative_models_amd import ops
+    g = torch.Generator().manual_seed(5)
+    for n in (8, 2048 * 3 + 8, 4096 * 2048 + 2048 * 3 + 40):
+        a = torch.randn(n, generator=g).cuda().to(dtype)
+        b = (torch.randn(n, generator=g) * 3).cuda().to(dtype)
+        want = (a.float() + b.float()).to(dtype)
+        keep_b = b.clone()
+        out = ops.add_into(a, b)
+        assert out is a and torch.equal(a, want) and torch.equal(b, keep_b), (dtype, n)
+    nhwc = torch.randn((2, 8, 8, 128), generator=g).cuda().to(dtype)
+    other = torch.randn((2, 8, 8, 128), generator=g).cuda().to(dtype)
+    want = (nhwc.float() + other.float()).to(dtype)
+    assert torch.equal(ops.add_into(nhwc, other), want)
+    with pytest.raises(ValueError, match="add_into"):
+        ops.add_into(torch.zeros(12, device="cuda", dtype=dtype), torch.zeros(12, device="cuda", dtype=dtype))
+    with pytest.raises(ValueError):
+        ops.add_into(torch.zeros(16, device="cuda", dtype=dtype), torch.zeros(16, device="cuda", dtype=torch.float16))
+
+
+def test_importance_weights_scale_both_output_gradients():
+    """time_importance with a hand-set steep ready profile: the (dv, dnu) handed to backward_hip are those of a pass without the flag at the
+    returned times, each row scaled once by its weight - bit for bit - and the weights are not 1; the profile takes the unweighted loss."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import time_importance_ref as TI
+    from generative_models_amd.diffusion.gaussian_diffusion import GaussianDiffusion
+    _, lv, _, _ = _nets(1, torch.float32)
+    g = torch.Generator().manual_seed(17)
+    B = 4
+    x = (torch.rand((B, 1, S, S), generator=g) * 2 - 1).cuda()
+    eps = torch.randn((B, 1, S, S), generator=g).cuda()
+    y = torch.tensor([4, -1, 0, 7]).cuda()
+    seen = []
+    backward = lv.backward_hip
+    lv.backward_hip = lambda ctx, dv, **kw: seen.append((dv.clone(), kw["dnu"].clone())) or backward(ctx, dv, **kw)
+    steep = TI.steep_state(14.0)
+    d = GaussianDiffusion(mean_type="v", num_steps=8, seed=13, time_importance=1, importance_floor=0.5, learn_var=1, vlb_lambda=0.05, vlb_steps=100)
+    d.time_profile = torch.from_numpy(steep).cuda()
+    out = d.train_forward_backward(net=partial(lv, guide=y), x=x, grad_scale=1.0 / B, eps=eps)
+    tw = out["time_w"]
+    assert not bool((tw == 1.0).any()) and float(tw.max() / tw.min()) > 1.5 and torch.equal(out["loss"], tw * out["loss_b"])
+    want_state = TI.loss_profile(steep, out["u"].cpu().numpy(), out["loss_b"].cpu().numpy(), out["x_mse"].cpu().numpy(), 0.9)
+    assert np.array_equal(d.time_profile.cpu().numpy().view(np.uint32), want_state.view(np.uint32))
+    plain = GaussianDiffusion(mean_type="v", num_steps=8, learn_var=1, vlb_lambda=0.05, vlb_steps=100)
+    base = plain.train_forward_backward(net=partial(lv, guide=y), x=x, grad_scale=1.0 / B, u=out["u"], eps=eps)
+    assert torch.equal(base["loss"], out["loss_b"]) and torch.equal(base["vlb"], out["vlb"])
+    (dv_w, dnu_w), (dv_0, dnu_0) = seen
+    rows = tw.view(B, 1, 1, 1)
+    assert float(dnu_0.abs().max()) > 0.0 and float(dv_0.abs().max()) > 0.0
+    assert torch.equal(dv_w, dv_0 * rows) and torch.equal(dnu_w, dnu_0 * rows)
+    assert not torch.equal(dnu_w, dnu_0)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "16bit"])
+@pytest.mark.parametrize("in_channels", [1, 3])
+def test_whole_gradient_vs_float64_autograd(in_channels, dtype, oracle64):
+    """vlb_lambda = 0.001: the whole gradient against float64 autograd through oracle/unet_ref.py (`oracle64`), a torch convolution for the
+    second head and the restatement's hybrid loss.  fp32 mode: 1e-3 relative L2; 16-bit mode: cosine >= 0.9999 and relative L2 <= 1.5e-2.
+    At this lambda and these times dnu is about 1e-6 of dv: the test bounds the loss path and out_var.weight's own gradient; the second
+    head's share of the shared gradients is test_backward_with_a_variance_gradient_of_dvs_size's."""
+    _, lv, p, head = _nets(in_channels, dtype)
+    lam, gs = 0.001, 0.5
+    out = _train_pass(lv, in_channels, learn_var=1, vlb_lambda=lam)
+    x, eps, u, y = _batch(in_channels)
+    B = x.shape[0]
+    P = {k: t.double().clone().requires_grad_(True) for k, t in {**p, **head}.items()}
+    lt = f64(out["logsnr"])
+    sched = lambda t: -2.0 * torch.log(torch.tan(1.5707055269354342 * t + 4.539992973129278e-05))
+    assert float((sched(f64(u)) - lt).abs().max()) <= 1e-5
+    ls = sched((f64(u) - 1.0 / 100).clamp(min=0.0))
+    al, si = torch.sqrt(torch.sigmoid(lt)).view(B, 1, 1, 1), torch.sqrt(torch.sigmoid(-lt)).view(B, 1, 1, 1)
+    z = al * f64(x) + si * f64(eps)
+    v, nu = oracle64(P, z, lt, y.cpu())
+    flat = lambda t: t.reshape(B, -1)
+    ref = R.hybrid_loss(flat(v), flat(nu), flat(z), flat(f64(x)), flat(f64(eps)), lt, ls, lam, gs)
+    (gs * ref["loss"].sum()).backward()
+    assert rel_err(out["loss"], ref["loss"]) <= (TOL32 if dtype == torch.float32 else 1e-2)
+    names = [k for k in P if P[k].grad is not None]
+    assert "out_var.weight" in names and "out_var.bias" in names and "out.2.weight" in names
+    want = torch.cat([P[k].grad.reshape(-1) for k in names])
+    got = torch.cat([f64(lv.grad(k)).reshape(-1) for k in names])
+    rel_l2 = float((got - want).norm() / want.norm())
+    cosine = float((got @ want) / (got.norm() * want.norm()))
+    head_l2 = float((f64(lv.grad("out_var.weight")) - P["out_var.weight"].grad).norm() / P["out_var.weight"].grad.norm())
+    print(f"in_channels {in_channels}, {dtype}: whole gradient relative L2 {rel_l2:.3e}, cosine {cosine:.7f}; out_var.weight relative L2 {head_l2:.3e}, "
+          f"its share of the norm {float(P['out_var.weight'].grad.norm() / want.norm()):.3e}")
+    assert float(P["out_var.weight"].grad.norm()) > 0.0
+    if dtype == torch.float32:
+        assert rel_l2 <= TOL32 and head_l2 <= TOL32
+    else:
+        assert cosine >= GRAD16["cosine"] and rel_l2 <= GRAD16["rel_l2"]
+
+
+def test_autograd_bridge_matches_the_fused_pass():
+    """training_losses through torch.autograd (SimpleUnetVarFunction, _HybridLoss) leaves the fused pass's gradient arena."""
+    from generative_models_amd.diffusion.gaussian_diffusion import GaussianDiffusion
+    _, lv, _, _ = _nets(1, torch.float32)
+    out = _train_pass(lv, 1, learn_var=1, vlb_lambda=0.001)
+    fused = lv.flat_grads.clone()
+    x, eps, u, y = _batch(1)
+    d = GaussianDiffusion(mean_type="v", num_steps=4, vlb_steps=100, learn_var=1, vlb_lambda=0.001)
+    lv.zero_grad_arena()
+    m = d.training_losses(net=partial(lv, guide=y), x=x, u=u, eps=eps)
+    assert set(m) == {"loss", "vlb", "var_frac"} and torch.equal(m["loss"], out["loss"]) and torch.equal(m["vlb"], out["vlb"])
+    (0.5 * m["loss"].sum()).backward()
+    torch.cuda.synchronize()
+    assert float((lv.flat_grads - fused).abs().max()) <= 1e-6 * float(fused.abs().max())
+    with torch.no_grad():
+        m2 = d.training_losses(net=partial(lv, guide=y), x=x, u=u, eps=eps)
+    assert torch.equal(m2["loss"], m["loss"]) and torch.equal(m2["var_frac"], out["var_frac"])
+
+
+# ---- end to end -----------------------------------------------------------------------------------------------------------------------------------
+def _model(seed=0, **flags):
+    from generative_models_amd import common
+    Model = common.discover_models()["diffusion_model"]
+    G = common.AttrDict(dict(Model.DG))
+    G.update(lr=1e-3, pad32=0, device="cuda", bs=8, seed=3, hidden_size=C, in_channels=1, image_size=S, timesteps=4, learn_var=1, grad_clip=1.0,
+             time_importance=1, sampler="ancestral", posterior_var="learned", **flags)
+    torch.manual_seed(seed)
+    return Model(G).cuda().train()
+
+
+def _batches(k):
+    g = torch.Generator().manual_seed(11)
+    return [((torch.rand((8, 1, S, S), generator=g) * 2 - 1).cuda(), torch.randint(0, 10, (8,), generator=g).cuda()) for _ in range(k)]
+
+
+def _steps(model, batches):
+    out = []
+    for x, y in batches:
+        metrics = model.train_step(x, y.clone())
+        out.append({k: metrics[k].detach().cpu().clone() for k in ("loss", "grad_norm", "skipped_steps")})
+    torch.cuda.synchronize()
+    return out
+
+
+def _run_five_steps_and_sample():
+    m = _model()
+    assert m.net.learn_var and m.diffusion.learn_var and "out_var.weight" in m.net._offsets
+    before = m.net.param("out_var.weight").clone()
+    metrics = _steps(m, _batches(5))
+    assert all(bool(torch.isfinite(s["loss"])) and bool(torch.isfinite(s["grad_norm"])) for s in metrics)
+    assert bool(torch.isfinite(m.net.flat_params).all()) and int(metrics[-1]["skipped_steps"]) == 0
+    assert not torch.equal(m.net.param("out_var.weight"), before)                        # the head trains
+    loss, test = m.loss(*_batches(1)[0])
+    assert {"loss", "vlb", "var_frac"} <= set(test) and all(bool(torch.isfinite(test[k])) for k in ("loss", "vlb", "var_frac"))
+    m.eval()
+    guided = m.sample(8, torch.tensor([1, 2, 3, 4, 5, 6, 7, 8]).cuda())
+    plain = m.sample(8)
+    for out in (guided, plain):
+        assert out.shape == (8, 1, S, S) and bool(torch.isfinite(out).all()) and float(out.abs().max()) <= 1.0
+    assert m.diffusion.rng.counter > 0 and not torch.equal(guided, plain)
+    return metrics, guided, plain
+
+
+def test_training_and_sampling_end_to_end():
+    """Five Adam steps under learn_var 1, grad_clip 1, time_importance 1, then sampler 'ancestral' with posterior_var 'learned' on 4 steps,
+    guided and unguided; the whole sequence again from the same seeds gives the same numbers and the same images."""
+    a, b = _run_five_steps_and_sample(), _run_five_steps_and_sample()
+    for sa, sb in zip(a[0], b[0]):
+        assert all(torch.equal(sa[k], sb[k]) for k in sa)
+    assert torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
+
+
+def test_learned_differs_from_the_fixed_variances_and_runs_the_options():
+    """The same trained-from-init model under posterior_var 'learned', 'small' and 'large': three different chains from one seed; and 'learned'
+    with the guidance interval, cfg_rescale and dyn_threshold."""
+    from generative_models_amd.diffusion.gaussian_diffusion import GaussianDiffusion
+    _, lv, _, _ = _nets(1, torch.float32)
+    lv.eval()
+    g = torch.Generator().manual_seed(21)
+    init, y = torch.randn((4, 1, S, S), generator=g).cuda(), torch.tensor([3, -1, 0, 9]).cuda()
+    run = lambda d, **kw: d.sample(net=partial(lv, guide=y), init_x=init, record=False, **kw)[0][-1]
+    make = lambda pv, **kw: GaussianDiffusion(mean_type="v", num_steps=4, seed=5, sampler="ancestral", learn_var=1, posterior_var=pv, **kw)
+    outs = {pv: run(make(pv)) for pv in ("learned", "small", "large")}
+    assert all(bool(torch.isfinite(o).all()) for o in outs.values())
+    assert not torch.equal(outs["learned"], outs["small"]) and not torch.equal(outs["learned"], outs["large"])
+    assert torch.equal(outs["learned"], run(make("learned")))
+    d = make("learned")
+    run(d)
+    assert d.rng.counter == 4 * (4 * S * S // 4)            # the noise budget of 'ancestral': one block per step
+    guided = dict(cond_w=0.5, net_cond_w=torch.tensor([0.5, 1.0, 2.0, 3.5]).cuda())
+    for extra, kw in ((dict(guidance_interval=(-3.0, 30.0)), guided), (dict(cfg_rescale=0.7), guided), (dict(dyn_threshold=0.9), {}), ({}, guided)):
+        out = run(make("learned", **extra), **kw)
+        assert bool(torch.isfinite(out).all()) and float(out.abs().max()) <= 1.0, extra
+    # a graph-replayed chain (16 steps, small batch) and the kernel-by-kernel one: the same bits
+    graphed, plain = (GaussianDiffusion(mean_type="v", num_steps=16, seed=5, sampler="ancestral", learn_var=1, posterior_var="learned")
+                      for _ in range(2))
+    plain.GRAPH_MAX_PIXELS = 0
+    assert torch.equal(run(graphed), run(plain)) and len(graphed._graphs) == 1 and not plain._graphs
+    # a network without the head is refused by name
+    plain_net = _nets(1, torch.float32)[0]
+    with pytest.raises(ValueError, match="posterior_var.*learn_var"):
+        make("learned").sample(net=partial(plain_net, guide=y), init_x=init)
+
+
+def test_a_resumed_run_reaches_the_bits_of_the_one_that_never_stopped(tmp_path):
+    """What --save_state writes and --resume reads (state_dict + train_state), across step 3 of 6."""
+    batches = _batches(6)
+    A = _model(0, ema_decay=0.999)
+    mA = _steps(A, batches)
+    B = _model(0, ema_decay=0.999)
+    _steps(B, batches[:3])
+    torch.save(B.state_dict(), tmp_path / "model.pt")
+    torch.save(B.train_state(), tmp_path / "state.pt")
+    del B
+    Cm = _model(1, ema_decay=0.999)
+    assert not torch.equal(Cm.net.flat_params, A.net.flat_params)
+    sd = torch.load(tmp_path / "model.pt", map_location="cuda")
+    assert "net.out_var.weight" in sd and "ema_net.out_var.weight" in sd
+    Cm.load_state_dict(sd)
+    Cm.load_train_state(torch.load(tmp_path / "state.pt", map_location="cpu"))
+    mC = _steps(Cm, batches[3:])
+    for name, a, c in (("flat_params", A.net.flat_params, Cm.net.flat_params), ("m", A.optimizer.m, Cm.optimizer.m),
+                       ("v", A.optimizer.v, Cm.optimizer.v), ("ema", A.ema_net.flat_params, Cm.ema_net.flat_params)):
+        assert torch.equal(a, c), name
+    assert A.arena_digests() == Cm.arena_digests() and A.optimizer.m.numel() == A.net._arena_size
+    for step, (a, c) in enumerate(zip(mA[3:], mC)):
+        assert all(torch.equal(a[k], c[k]) for k in a), step
