@@ -11,7 +11,8 @@ serialise host and GPU every step), rank-aware logging and checkpointing for one
 Environment differences (no network, no tensorboard / ignite in the image): `--data synthetic` (default) is an MNIST-shaped
 generator, `--data mnist` reads the IDX files if they are present; the writer is `common.NullWriter`, or with `--save_images 1`
 `common.ImageWriter` (PNG / APNG files under <logdir>/images; `--dump_samples N` writes samples as an `npy` dataset).  `--data_device 1` keeps
-`mnist`, `cifar10` or an `npy` array on the GPU and assembles every batch there (data.DeviceDataset).
+`mnist`, `cifar10` or an `npy` array on the GPU and assembles every batch there (data.DeviceDataset); with it,
+`--nn_eval Q` reports after every checkpoint how close Q samples lie to their nearest training images (neighbours.py).
 
     python -m generative_models_amd.main --model=diffusion --epochs=1 --bs 32
     torchrun --nproc-per-node 8 -m generative_models_amd.main --model=diffusion      (one process per GPU, RCCL)
@@ -63,6 +64,9 @@ DG.image_frames = 60       # most frames an APNG keeps of a sampling trajectory 
 DG.save_state = 0          # 1: every checkpoint also writes <logdir>/train_state.pt, what --resume needs beside model.pt (checkpoint.py)
 DG.resume = Path(".")      # <dir>: continue the run that wrote <dir>/model.pt + train_state.pt, with its hps.yaml under the command line
 DG.dump_samples = 0        # N > 0: after every checkpoint, N samples as <logdir>/samples_{images,labels}.npy (data.load_npy's format)
+DG.nn_eval = 0             # Q > 0: after every checkpoint, Q samples beside their nearest training images in pixel space (neighbours.py;
+                           # data_device 1 and binarize 0 only): eval/nn_dist, eval/nn_dist_test, eval/nn_closer, <logdir>/nearest_neighbours.npz
+DG.nn_k = 3                # neighbours kept per sample (1 .. 8)
 
 SyntheticMNIST = datasets.SyntheticMNIST       # kept importable from here
 
@@ -145,6 +149,8 @@ class EpochLog:
 
 
 LOSS_PROFILE_FILE = "loss_profile.csv"
+NN_FILE = "nearest_neighbours.npz"
+NN_PICTURE_ROWS = 10
 LOSS_PROFILE_COLUMNS = ("epoch", "split", "bin", "u_lo", "u_hi", "logsnr_hi", "logsnr_lo", "weight", "loss_mean", "loss_rms", "x_mse_mean", "p")
 
 
@@ -174,6 +180,7 @@ class Session:
         self.device = getattr(model, "run_device", G.device)
         self.lead = parallel.rank() == 0                               # rank 0 prints, writes hps.yaml and checkpoints
         self.writer = common.ImageWriter(G.logdir, G.get("image_frames", 60)) if G.get("save_images", 0) else common.NullWriter(G.logdir)
+        self.nn_index = None                                           # neighbours.NeighbourIndex of the training set, built at the first report
 
     def _batches(self, ds):
         for batch in ds:
@@ -214,15 +221,15 @@ class Session:
 
     def checkpoint(self, log, last_batch, epoch=0):
         if self.lead:
-            self._write_checkpoint(log, last_batch)
-        # last: the heavy evaluation and dump_samples draw from the model's streams and advance the test loader.  Every rank enters (the
-        # replica check of a data-parallel run is a collective), rank 0 writes
+            self._write_checkpoint(log, last_batch, epoch)
+        # last: the heavy evaluation and dump_samples draw from the model's streams and advance the test loader, and the neighbour report
+        # draws from the streams too.  Every rank enters (the replica check of a data-parallel run is a collective), rank 0 writes
         if self.G.get("save_state", 0):
             train_state.save(Path(self.G.logdir), self.model, self.train_ds, self.test_ds, epoch)
             if self.lead:
                 print("SAVED TRAIN STATE", self.G.logdir)
 
-    def _write_checkpoint(self, log, last_batch):
+    def _write_checkpoint(self, log, last_batch, epoch=0):
         Path(self.G.logdir).mkdir(parents=True, exist_ok=True)
         self.model.save(Path(self.G.logdir), *last_batch)
         print("SAVED MODEL", self.G.logdir)
@@ -237,11 +244,12 @@ class Session:
             print("DONE HEAVY EVAL")
         if self.G.get("dump_samples", 0) > 0:
             self.dump_samples(int(self.G.dump_samples))
+        if self.G.get("nn_eval", 0) > 0:
+            self.nn_eval(log, int(self.G.nn_eval), int(self.G.nn_k), epoch)
 
-    def dump_samples(self, n):
-        """n samples of the model as a dataset: <logdir>/samples_images.npy (uint8 [n, C, H, W]) and samples_labels.npy (uint8 [n]), the
-        format of data.load_npy - renamed to train_* / test_*, a set `--data npy --data_device 1` trains on.  Drawn in batches of `bs`; with
-        class_cond the labels are arange(n) % 10 and the draw is guided as `sample(n, y)` is, else unconditional with labels 0."""
+    def draw_uint8(self, n):
+        """-> (samples uint8 [n, C, H, W] on the device, labels int64 [n]): drawn in batches of `bs`; with class_cond the labels are
+        arange(n) % 10 and the draw is guided as `sample(n, y)` is, else unconditional with labels 0."""
         cond = bool(self.G.get("class_cond", 0))
         labels = torch.arange(n, dtype=torch.long, device=self.device) % 10 if cond else torch.zeros(n, dtype=torch.long, device=self.device)
         was_training = self.model.training
@@ -251,10 +259,42 @@ class Session:
             y = labels[lo:lo + int(self.G.bs)]
             parts.append(self.model.sample_uint8(y.numel(), y.clone() if cond else None))
         self.model.train(was_training)
+        return torch.cat(parts), labels
+
+    def dump_samples(self, n):
+        """n samples of the model as a dataset: <logdir>/samples_images.npy (uint8 [n, C, H, W]) and samples_labels.npy (uint8 [n]), the
+        format of data.load_npy - renamed to train_* / test_*, a set `--data npy --data_device 1` trains on.  The draw: draw_uint8."""
+        samples, labels = self.draw_uint8(n)
         logdir = Path(self.G.logdir)
-        np.save(logdir / "samples_images.npy", torch.cat(parts).cpu().numpy())
+        np.save(logdir / "samples_images.npy", samples.cpu().numpy())
         np.save(logdir / "samples_labels.npy", labels.cpu().numpy().astype(np.uint8))
         print("DUMPED", n, "SAMPLES", logdir)
+
+    def nn_eval(self, log, n, k, epoch):
+        """n samples (draw_uint8) and the first min(n, N_test) images of the test split, each beside its k nearest training images in pixel
+        space (neighbours.nn_report; mirrored matches count when the train split flips): logs eval/nn_dist, eval/nn_dist_test, eval/nn_closer
+        and dt/nn_eval, writes <logdir>/nearest_neighbours.npz (samples, index, dist2, mirrored, test_dist2, epoch) and, with save_images, the
+        picture `nearest`: one line per sample for the first 10, the sample and then its neighbours as the dataset stores them.  The test
+        loader is not advanced; the training set's norms are computed at the first report of the run."""
+        from . import neighbours
+        started = time.time()
+        if self.nn_index is None:
+            self.nn_index = neighbours.NeighbourIndex(self.train_ds.images)
+        samples, _ = self.draw_uint8(n)
+        holdout = self.test_ds.images[:min(n, self.test_ds.images.shape[0])]
+        report = neighbours.nn_report(self.nn_index, samples, holdout, k, mirror=self.G.get("flip_p", 0.0) > 0)
+        for key in ("nn_dist", "nn_dist_test", "nn_closer"):
+            log.set(f"eval/{key}", report[key])
+        np.savez(Path(self.G.logdir) / NN_FILE, samples=samples.cpu().numpy(), index=report["index"], dist2=report["dist2"],
+                 mirrored=report["mirrored"], test_dist2=report["test_dist2"], epoch=np.int64(epoch))
+        if self.G.get("save_images", 0) and samples.shape[1] in (1, 3):
+            rows = min(NN_PICTURE_ROWS, n)
+            found = self.train_ds.images[torch.from_numpy(report["index"][:rows]).to(self.device)]          # [rows, k, C, H, W]
+            tiles = torch.cat((samples[:rows, None], found), 1).flatten(0, 1)
+            # byte b as the float whose quantisation (ops.to_uint8's rule, trunc((x + 1) 127.5)) is b again: the middle of b's interval
+            self.writer.write_frames("nearest", (tiles.float() + 0.5) / 127.5 - 1.0, epoch, ncol=k + 1)
+        log.set("dt/nn_eval", time.time() - started)
+        print("NEAREST NEIGHBOURS OF", n, "SAMPLES", {key: round(report[key], 6) for key in ("nn_dist", "nn_dist_test", "nn_closer")})
 
     def train_epoch(self, log):
         self.model.train()
@@ -372,6 +412,24 @@ def _check_image_flags(G):
         raise ValueError(f"--dump_samples {G.dump_samples}: 0 (off) or the number of samples to write after a checkpoint")
 
 
+def _check_nn_flags(G, n_train=None):
+    """The flags of the nearest-neighbour report, named before any model is built; with n_train (once the data is loaded) also against the
+    training set's size."""
+    if G.nn_eval < 0:
+        raise ValueError(f"--nn_eval {G.nn_eval}: 0 (off) or the number Q >= 1 of samples to search neighbours for after a checkpoint")
+    if not G.nn_eval:
+        return
+    if not 1 <= G.nn_k <= 8:
+        raise ValueError(f"--nn_k {G.nn_k}: 1 .. 8 neighbours per sample")
+    if not G.data_device:
+        raise ValueError(f"--nn_eval {G.nn_eval} needs --data_device 1 (the search runs against the training set held on the GPU as bytes)")
+    if G.binarize:
+        raise ValueError(f"--nn_eval {G.nn_eval} needs --binarize 0 (samples and dataset bytes are compared as grey levels; a binarized model "
+                         f"draws 0 / 1 images)")
+    if n_train is not None and G.nn_k > n_train:
+        raise ValueError(f"--nn_k {G.nn_k}: the training set has {n_train} images")
+
+
 def _device_datasets(G, device, rank, world):
     root = str(G.data_root)
     if G.data == "mnist":
@@ -402,6 +460,7 @@ def load_model_and_data(argv=None):
     G, Model = FlagSpace(DG).resolve(argv)
     _check_data_flags(G)
     _check_image_flags(G)
+    _check_nn_flags(G)
     init_distributed()
     _check_resume_flags(G, Model)                                      # after init_distributed: the state file names its world size
     device = _run_device(G.device)
@@ -413,6 +472,8 @@ def load_model_and_data(argv=None):
     if parallel.world() > 1 and hasattr(model, "net"):
         parallel.GradSync(model.net).broadcast_params(0)
     train_ds, test_ds = _datasets(G, device)
+    if G.nn_eval:
+        _check_nn_flags(G, int(train_ds.images.shape[0]))
     if parallel.rank() == 0:
         print("num_vars", common.count_vars(model))
     autoencoder, classifier = _feature_extractors(G, device, test_ds)

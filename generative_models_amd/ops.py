@@ -1684,6 +1684,72 @@ def arena_digest(t):
     return int(out.item()) & 0xFFFFFFFFFFFFFFFF
 
 
+# ---- exact nearest neighbours of byte rows (an extension; no reference call site) --------------------------------
+NN_SLAB, NN_MAX_K, NN_MAX_D = C["GMK_NN_SLAB"], C["GMK_NN_MAX_K"], C["GMK_NN_MAX_D"]
+NN_WORKSPACE_CAP = 64 << 20          # bytes of partial lists one launch may leave: nn_search_u8 takes the queries in blocks that stay below it
+
+
+def _byte_rows(t, name):
+    """uint8 device tensor of rank >= 2 -> its contiguous [rows, D] view (everything behind dimension 0 flattened; a copy only of a
+    non-contiguous view), with the ranges of include/gmk.h checked."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise ValueError(f"{name}: dtype {getattr(t, 'dtype', type(t))}, expected {torch.uint8}")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: expected a device tensor (the HIP path has no CPU fallback)")
+    if t.dim() < 2 or t.shape[0] < 1:
+        raise ValueError(f"{name}: shape {tuple(t.shape)} (want [rows, ...] of rank >= 2 with at least one row)")
+    rows = t.reshape(t.shape[0], -1).contiguous()
+    if not 1 <= rows.shape[1] <= NN_MAX_D:
+        raise ValueError(f"{name}: rows of D = {rows.shape[1]} bytes (1 .. {NN_MAX_D}: beyond it a squared distance leaves int32)")
+    if rows.shape[0] >= 1 << 31:
+        raise ValueError(f"{name}: {rows.shape[0]} rows (below 2^31)")
+    return rows
+
+
+def u8_sqnorm(rows):
+    """-> int32 [N]: sum_i (rows[j][i] - 128)^2 of a uint8 device tensor [N, ...] (gmk_u8_sqnorm): the norms nn_search_u8 wants of its database."""
+    rows = _byte_rows(rows, "u8_sqnorm: rows")
+    out = torch.empty((rows.shape[0],), device=rows.device, dtype=torch.int32)
+    with _Timed("u8_sqnorm_kernel", 0.0, _nbytes(rows, out), fixed=True):
+        check(lib.gmk_u8_sqnorm(_p(rows), rows.shape[0], rows.shape[1], _p(out), _s()), "u8_sqnorm")
+    return out
+
+
+def nn_search_u8(queries, database, k=1, db_sqnorm=None):
+    """-> (dist2 int32 [Q, k], index int64 [Q, k]): per query the k smallest pairs (d2, j) in lexicographic order, d2 the exact squared
+    Euclidean distance between the bytes of queries[q] and database[j] (include/gmk.h: gmk_nn_search_u8).  queries [Q, ...] and database
+    [N, ...]: uint8 device tensors of rank >= 2 with the same number of bytes per row; db_sqnorm: u8_sqnorm(database), computed here when
+    None.  The queries are taken in blocks whose workspace stays under NN_WORKSPACE_CAP."""
+    queries, database = _byte_rows(queries, "nn_search_u8: queries"), _byte_rows(database, "nn_search_u8: database")
+    if queries.device != database.device:
+        raise ValueError(f"nn_search_u8: queries on {queries.device}, database on {database.device}")
+    (Q, D), N = queries.shape, database.shape[0]
+    if database.shape[1] != D:
+        raise ValueError(f"nn_search_u8: queries of D = {D} bytes, database rows of D = {database.shape[1]}")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= NN_MAX_K or k > N:
+        raise ValueError(f"nn_search_u8: k = {k!r} with N = {N} (an integer in 1 .. {NN_MAX_K}, at most N)")
+    if db_sqnorm is None:
+        db_sqnorm = u8_sqnorm(database)
+    elif (not isinstance(db_sqnorm, torch.Tensor) or db_sqnorm.dtype != torch.int32 or db_sqnorm.device != database.device
+          or tuple(db_sqnorm.shape) != (N,) or not db_sqnorm.is_contiguous()):
+        raise ValueError(f"nn_search_u8: db_sqnorm {getattr(db_sqnorm, 'dtype', type(db_sqnorm))} {tuple(getattr(db_sqnorm, 'shape', ()))}, "
+                         f"expected contiguous {torch.int32} [{N}] on {database.device} (u8_sqnorm(database))")
+    per_query = lib.gmk_nn_search_workspace(2, N, k) - lib.gmk_nn_search_workspace(1, N, k)      # the partial lists of one query
+    block = max(1, NN_WORKSPACE_CAP // per_query)
+    block = Q if block >= Q else max(block // 16 * 16, 1)          # whole 16-row groups: a later block starts 16-byte aligned when the first does
+    need = lib.gmk_nn_search_workspace(block, N, k)
+    workspace = torch.empty((need,), device=queries.device, dtype=torch.uint8)
+    dist2 = torch.empty((Q, k), device=queries.device, dtype=torch.int32)
+    index = torch.empty((Q, k), device=queries.device, dtype=torch.int32)
+    for lo in range(0, Q, block):
+        n = min(block, Q - lo)
+        with _Timed("nn_search_kernel", 2.0 * n * N * D, _nbytes(database, queries[lo:lo + n], db_sqnorm) + 8.0 * n * k, fixed=True,
+                    multiplied=2.0 * n * N * D):
+            check(lib.gmk_nn_search_u8(_p(queries[lo:lo + n]), n, _p(database), N, D, _p(db_sqnorm), k, _p(workspace), need,
+                                       _p(dist2[lo:lo + n]), _p(index[lo:lo + n]), _s()), "nn_search_u8")
+    return dist2, index.long()
+
+
 # ---- self-attention core (north_star extension; no reference call site) -----------------------------------------
 def bgemm_nt(A, B, out=None, alpha=1.0, out_dtype=None):
     """C[b] = alpha * A[b] @ B[b]^T for batches of K-contiguous matrices (row / batch strides free): A [batch, M, K],

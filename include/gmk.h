@@ -759,6 +759,28 @@ int gmk_adam_step_ctl(float* p, const float* g, float* m, float* v, float* ema, 
  * and then added to by one 64-bit atomic per workgroup. */
 int gmk_arena_digest(const void* data, int64_t n_words, uint64_t* out, void* stream);
 
+/* ---- exact nearest neighbours of byte rows (no reference call site: neighbours.py's report of samples beside their nearest training images) ----
+ * d2(q, j) = sum_i (queries[q][i] - database[j][i])^2, an exact integer.  Row q of dist2_out / index_out holds the k smallest pairs (d2, j) in
+ * lexicographic order: the smaller distance first and, among equal distances, the smaller index (identical database rows come lowest index
+ * first).  A function of the inputs alone - integer arithmetic, no atomics, no merge that depends on an order of arrival: two calls give the
+ * same bytes.
+ *   queries [Q][D] uint8, database [N][D] uint8, row-contiguous, any alignment (D % 16 == 0 on 16-byte aligned bases takes 16-byte loads,
+ *   everything else a per-byte staging path);  db_sqnorm [N] int32 = gmk_u8_sqnorm(database), so that a caller can keep it per dataset;
+ *   dist2_out, index_out [Q][k] int32;  workspace: gmk_nn_search_workspace(Q, N, k) bytes, 16-byte aligned (-1 for arguments out of range)
+ *   1 <= k <= GMK_NN_MAX_K and k <= N;  1 <= Q, N < 2^31;  1 <= D <= GMK_NN_MAX_D - there d2 <= 32768 * 255^2 = 2 130 739 200 < 2^31.
+ * Bytes are taken as b ^ 0x80 = b - 128 (the differences do not change) and d2 = |q'|^2 + |x'|^2 - 2 q'.x' with the dot product on
+ * v_mfma_i32_32x32x32_i8 (int32 accumulation, |q'.x'| <= 2^29: exact).  Three launches: the queries' norms, one workgroup per GMK_NN_SLAB
+ * database rows that loops over the query tiles and leaves two lists of k keys (d2 << 32 | j) per query and slab in the workspace, and a
+ * merge of those lists per query (csrc/nn_search.hip).  The database is read from HBM once per call.
+ * gmk_u8_sqnorm: out[j] = sum_i (rows[j][i] - 128)^2 as int32 (<= 2^29), the same ranges of N and D.  No rows of GMK_KERNEL_TABLE. */
+#define GMK_NN_SLAB 128
+#define GMK_NN_MAX_K 8
+#define GMK_NN_MAX_D 32768
+int gmk_u8_sqnorm(const uint8_t* rows, int64_t N, int D, int* out, void* stream);
+int64_t gmk_nn_search_workspace(int64_t Q, int64_t N, int k);
+int gmk_nn_search_u8(const uint8_t* queries, int64_t Q, const uint8_t* database, int64_t N, int D, const int* db_sqnorm, int k,
+                     void* workspace, int64_t workspace_bytes, int* dist2_out, int* index_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
