@@ -3,7 +3,8 @@
 // ddim_step :189-213, reverse_dpm_step :215-243, sample :292) and gms/diffusion/diffusion_utils.py
 // (diffusion_forward :65-73, diffusion_reverse :34-62, predict_* :76-105, _logsnr_schedule_cosine :198-201);
 // torch.optim.Adam as diffusion_model.py:56 constructs it.  gmk_adam_ema_step's weight average has no reference call site (the
-// reference keeps no EMA): an extension, defined by torch.lerp.  gmk_dpm_solver_step (DPM-Solver++(2M)) is an extension too, and so are
+// reference keeps no EMA): an extension, defined by torch.lerp; so are gmk_adam_pema_step / gmk_arena_combine (the power-function averages
+// of post-hoc EMA and their reconstruction: Karras et al. 2024, section 3.2 and appendix C).  gmk_dpm_solver_step (DPM-Solver++(2M)) is an extension too, and so are
 // the variational-bound kernels gmk_q_sample_logsnr / gmk_vlb_term / gmk_vlb_endpoints (Kingma et al. 2021, continuous-time VDM bound) and
 // the inpainting merge gmk_inpaint_merge (RePaint, Lugmayr et al. 2022) and dynamic thresholding (gmk_dyn_threshold, gmk_sampler_step_dt,
 // gmk_dpm_solver_step_dt; Saharia et al. 2022).  gmk_grad_norm / gmk_adam_step_ctl (global-norm clipping by
@@ -1261,16 +1262,24 @@ __device__ __forceinline__ float lerp_to(float start, float end, float w) {
     return w < 0.5f ? fmaf(w, diff, start) : fmaf(-diff, 1.0f - w, end);
 }
 
-// The Adam step behind gmk_adam_step, gmk_adam_ema_step and gmk_adam_step_ctl.
+// The Adam step behind gmk_adam_step, gmk_adam_ema_step, gmk_adam_step_ctl and gmk_adam_pema_step.
 // EMA: Adam, then the EMA of the updated weights in the same pass: ema = lerp(ema, p_new, ema_w).  p is read once, so the EMA costs its own
 // read and write only (36 B / parameter against Adam's 28).
 // CTL: steered by gmk_grad_norm's state (below): gg = (g grad_scale) coef (adam_elem then multiplies by 1: exact), and no memory is touched
 // when apply == 0.  Both values are uniform across the launch.  Without CTL adam_elem forms g grad_scale itself and `state` is not read.
-template <bool EMA, bool CTL>
+// NP > 0 (gmk_adam_pema_step): NP more averages of the updated weights, the rows of one [NP][stride] arena, row r = lerp(row r, p_new, w[r]):
+// 8 B / parameter each, the row loop unrolled.  PVEC: the rows take 16-byte accesses (base aligned, stride % 4 == 0), else scalar ones.
+struct PemaArgs {
+    float* rows;
+    int64_t stride;
+    float w[3];
+};
+
+template <bool EMA, bool CTL, int NP = 0, bool PVEC = true>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                   float* __restrict__ v, float* __restrict__ ema, const float* __restrict__ state,
                                                   int64_t n, float step_size, float beta1, float beta2, float eps, float inv_bc2_sqrt,
-                                                  float grad_scale, float ema_w) {
+                                                  float grad_scale, float ema_w, PemaArgs pa) {
     if (CTL && state[GMK_APPLY] == 0.0f) return;
     const float coef = CTL ? state[GMK_CLIP_COEF] : 1.0f;
     auto elem = [&](float& pp, float gk, float& mm, float& vv) {
@@ -1278,16 +1287,36 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     };
     const int64_t nq = n / 4;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
-        float pv[4], gv[4], mv[4], vv[4], ev[4];
+        float pv[4], gv[4], mv[4], vv[4], ev[4], rv[NP ? NP : 1][4];
         load4(p + q * 4, pv); load4(g + q * 4, gv); load4(m + q * 4, mv); load4(v + q * 4, vv);
         if (EMA) load4(ema + q * 4, ev);
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+            float* row = pa.rows + r * pa.stride + q * 4;
+            if (PVEC) load4(row, rv[r]);
+            else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rv[r][k] = row[k];
+            }
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             elem(pv[k], gv[k], mv[k], vv[k]);
             if (EMA) ev[k] = lerp_to(ev[k], pv[k], ema_w);
+#pragma unroll
+            for (int r = 0; r < NP; ++r) rv[r][k] = lerp_to(rv[r][k], pv[k], pa.w[r]);
         }
         store4(p + q * 4, pv); store4(m + q * 4, mv); store4(v + q * 4, vv);
         if (EMA) store4(ema + q * 4, ev);
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+            float* row = pa.rows + r * pa.stride + q * 4;
+            if (PVEC) store4(row, rv[r]);
+            else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) row[k] = rv[r][k];
+            }
+        }
     }
     // tail (n not a multiple of 4)
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
@@ -1296,7 +1325,47 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         elem(pp, g[i], mm, vv);
         m[i] = mm; v[i] = vv; p[i] = pp;
         if (EMA) ema[i] = lerp_to(ema[i], pp, ema_w);
+#pragma unroll
+        for (int r = 0; r < NP; ++r) pa.rows[r * pa.stride + i] = lerp_to(pa.rows[r * pa.stride + i], pp, pa.w[r]);
     }
+}
+
+// out[i] = fp32(sum_k coef[k] src[k][i]) in double, k in index order, every product and every sum rounded on its own (gmk_arena_combine).
+// VEC: one float4 of each row per thread, 16-byte accesses (bases aligned, stride % 4 == 0) and a scalar tail; else one element per thread.
+// coef is uniform across the launch: scalar loads.
+template <bool VEC>
+__global__ __launch_bounds__(256) void arena_combine_kernel(const float* __restrict__ src, int64_t stride, const double* __restrict__ coef, int K,
+                                                           float* __restrict__ out, int64_t n) {
+    auto one = [&](int64_t i) {
+        double acc = __dmul_rn(coef[0], (double)src[i]);
+        for (int k = 1; k < K; ++k) acc = __dadd_rn(acc, __dmul_rn(coef[k], (double)src[k * stride + i]));
+        out[i] = (float)acc;
+    };
+    if (!VEC) {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) one(i);
+        return;
+    }
+    const int64_t nq = n / 4;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+        float xv[4];
+        double acc[4];
+        load4(src + q * 4, xv);
+        const double c0 = coef[0];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = __dmul_rn(c0, (double)xv[j]);
+#pragma unroll 4
+        for (int k = 1; k < K; ++k) {
+            load4(src + k * stride + q * 4, xv);
+            const double c = coef[k];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = __dadd_rn(acc[j], __dmul_rn(c, (double)xv[j]));
+        }
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (float)acc[j];
+        store4(out + q * 4, o);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) one(nq * 4 + threadIdx.x);
 }
 
 // ---- steered optimiser step: global gradient norm, clipping and the non-finite guard without a host sync; an extension (the reference's
@@ -2233,15 +2302,15 @@ extern "C" int gmk_consistency_target(const float* v_tgt, const float* z_s, cons
 }
 
 // scalar prologue in double, as torch.optim.adam._single_tensor_adam does on the host, then the one launch of an Adam step
-template <bool EMA, bool CTL>
+template <bool EMA, bool CTL, int NP = 0, bool PVEC = true>
 static int adam_launch(const char* who, float* p, const float* g, float* m, float* v, float* ema, const float* state, int64_t n, float lr,
-                       float beta1, float beta2, float eps, int step, float grad_scale, float ema_w, void* stream) {
+                       float beta1, float beta2, float eps, int step, float grad_scale, float ema_w, void* stream, PemaArgs pa = PemaArgs{}) {
     const double bc1 = 1.0 - pow((double)beta1, step);
     const double bc2 = 1.0 - pow((double)beta2, step);
     const float step_size = (float)((double)lr / bc1);
     const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    adam_kernel<EMA, CTL><<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, ema, state, n, step_size, beta1, beta2, eps,
-                                                                                  inv_bc2_sqrt, grad_scale, ema_w);
+    adam_kernel<EMA, CTL, NP, PVEC><<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(p, g, m, v, ema, state, n, step_size, beta1, beta2,
+                                                                                            eps, inv_bc2_sqrt, grad_scale, ema_w, pa);
     return gmk_check_launch(who);
 }
 
@@ -2286,7 +2355,54 @@ extern "C" int gmk_adam_step_ctl(float* p, const float* g, float* m, float* v, f
     GMK_REQUIRE(state, "gmk_adam_step_ctl: state is null");
     GMK_REQUIRE(!ema || (ema_w >= 0.0f && ema_w <= 1.0f), "gmk_adam_step_ctl: ema_w = %g outside [0, 1]", (double)ema_w);
     return (ema ? adam_launch<true, true> : adam_launch<false, true>)("gmk_adam_step_ctl", p, g, m, v, ema, state, n, lr, beta1, beta2, eps, step,
-                                                                      grad_scale, ema ? ema_w : 0.0f, stream);
+                                                                      grad_scale, ema ? ema_w : 0.0f, stream, PemaArgs{});
+}
+
+// gmk_adam_pema_step's instantiation: classic average or not, steered or not, for one row count and one row access width
+template <int NP, bool PVEC>
+static int adam_pema_launch(float* p, const float* g, float* m, float* v, float* ema, const float* state, int64_t n, float lr, float beta1,
+                            float beta2, float eps, int step, float grad_scale, float ema_w, void* stream, PemaArgs pa) {
+    auto launch = ema ? (state ? adam_launch<true, true, NP, PVEC> : adam_launch<true, false, NP, PVEC>)
+                      : (state ? adam_launch<false, true, NP, PVEC> : adam_launch<false, false, NP, PVEC>);
+    return launch("gmk_adam_pema_step", p, g, m, v, ema, state, n, lr, beta1, beta2, eps, step, grad_scale, ema ? ema_w : 0.0f, stream, pa);
+}
+
+extern "C" int gmk_adam_pema_step(float* p, const float* g, float* m, float* v, float* ema, float* pema, int64_t pema_stride, int n_pema,
+                                  int64_t n, float lr, float beta1, float beta2, float eps, int step, float grad_scale, float ema_w, float pw0,
+                                  float pw1, float pw2, const float* state, void* stream) {
+    GMK_REQUIRE(n_pema >= 1 && n_pema <= 3, "gmk_adam_pema_step: n_pema = %d outside 1 .. 3", n_pema);
+    GMK_REQUIRE(p && g && m && v && n > 0 && step >= 1, "gmk_adam_pema_step: bad arguments");
+    GMK_REQUIRE(pema, "gmk_adam_pema_step: pema is null");
+    GMK_REQUIRE(pema_stride >= n, "gmk_adam_pema_step: pema_stride = %lld below n = %lld", (long long)pema_stride, (long long)n);
+    GMK_REQUIRE(!ema || (ema_w >= 0.0f && ema_w <= 1.0f), "gmk_adam_pema_step: ema_w = %g outside [0, 1]", (double)ema_w);
+    const PemaArgs pa = {pema, pema_stride, {pw0, pw1, pw2}};
+    for (int r = 0; r < n_pema; ++r)
+        GMK_REQUIRE(pa.w[r] >= 0.0f && pa.w[r] <= 1.0f, "gmk_adam_pema_step: pw%d = %g outside [0, 1]", r, (double)pa.w[r]);
+    const bool pvec = reinterpret_cast<uintptr_t>(pema) % 16 == 0 && pema_stride % 4 == 0;
+#define GMK_PEMA_CASE(NP)                                                                                                                   \
+    case NP:                                                                                                                                \
+        return (pvec ? adam_pema_launch<NP, true> : adam_pema_launch<NP, false>)(p, g, m, v, ema, state, n, lr, beta1, beta2, eps, step,    \
+                                                                                 grad_scale, ema_w, stream, pa)
+    switch (n_pema) {
+        GMK_PEMA_CASE(1);
+        GMK_PEMA_CASE(2);
+        default: GMK_PEMA_CASE(3);
+    }
+#undef GMK_PEMA_CASE
+}
+
+extern "C" int gmk_arena_combine(const float* src, int64_t src_stride, const double* coef, int K, float* out, int64_t n, void* stream) {
+    GMK_REQUIRE(K >= 1 && K <= 64, "gmk_arena_combine: K = %d outside 1 .. 64", K);
+    GMK_REQUIRE(src && coef && out && n > 0, "gmk_arena_combine: bad arguments");
+    GMK_REQUIRE(src_stride >= n, "gmk_arena_combine: src_stride = %lld below n = %lld", (long long)src_stride, (long long)n);
+    const float* src_end = src + (int64_t)(K - 1) * src_stride + n;
+    GMK_REQUIRE(out + n <= src || out >= src_end, "gmk_arena_combine: out aliases src");
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out);
+    if (bases % 16 == 0 && src_stride % 4 == 0)
+        arena_combine_kernel<true><<<stream_grid(n / 4 + 1), 256, 0, gmk_stream(stream)>>>(src, src_stride, coef, K, out, n);
+    else
+        arena_combine_kernel<false><<<stream_grid(n), 256, 0, gmk_stream(stream)>>>(src, src_stride, coef, K, out, n);
+    return gmk_check_launch("gmk_arena_combine");
 }
 
 extern "C" int gmk_rng_rademacher(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {

@@ -22,7 +22,7 @@ import os
 
 import torch
 
-from .. import checkpoint, common, ops, parallel
+from .. import checkpoint, common, ops, parallel, posthoc_ema
 from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, consistency_check, dyn_threshold_check, edit_start, guidance_check,
                                  loss_weight_check, restore_operator, schedule_check, stochastic_check, time_importance_check, learned_var_check)
 from .optim import FusedAdam
@@ -124,11 +124,19 @@ def make_plugin(GMBase, AttrDict):
                                        # `vlb` and `var_frac`; not with teacher_path, loss_weight 'snr_trunc' / 'snr' only; not in the reference, off by default
         DG.vlb_lambda = 0.001          # the weight of the bound term, finite and >= 0 (the paper's value)
         DG.vlb_steps = 1000            # T >= 1: the bound term compares the times u and max(u - 1 / T, 0)
+        DG.ema_sigma_rel = ""          # 's1[,s2[,s3]]': keep a power-function average of the weights per relative width (strictly increasing, each in
+                                       # [0.01, 0.25]) inside the fused Adam launch and snapshot them under <logdir>/ema_snapshots; the weights of any
+                                       # width in between are reconstructed after training (posthoc_ema.py; Karras et al. 2024); evaluate() and sample()
+                                       # keep using the online or the ema_decay net; not in the reference, off by default
+        DG.ema_snapshot_every = 0      # optimiser steps between those snapshots (needs logdir); 0: one at every save() only
         DG.image_size = 0              # S > 0: images are S x S (CIFAR-10: 32 with in_channels 3); 0: the reference's 28, or 32 with pad32
 
         def __init__(self, G):
             super().__init__(G)
             get = lambda k: G[k] if k in G else self.DG[k]
+            self.ema_sigma_rel, self.ema_snapshot_every = posthoc_ema.check_flags(get("ema_sigma_rel"), get("ema_snapshot_every"))
+            if self.ema_snapshot_every > 0 and "logdir" not in G:
+                raise ValueError(f"ema_snapshot_every = {self.ema_snapshot_every} without logdir: the snapshots go to <logdir>/ema_snapshots")
             cdt = _DTYPES[get("compute_dtype")]
             adt = cdt if cdt == torch.float32 else {"fp16": torch.float16, "bf16": torch.bfloat16}[get("act_dtype")]
             if get("learn_var") not in (0, 1):
@@ -264,7 +272,8 @@ def make_plugin(GMBase, AttrDict):
                 raise ValueError("lr_scheduler = 'cosine' with lr_decay_steps = 0: give the number of steps of the decay")
             self.optimizer = FusedAdam(self.net, lr=G.lr if "lr" in G else 3e-4, ema_net=self.ema_net, ema_decay=self.ema_decay,
                                        grad_clip=grad_clip, skip_nonfinite=bool(int(get("skip_nonfinite"))), lr_scheduler=get("lr_scheduler"),
-                                       lr_warmup=lr_warmup, lr_decay_steps=lr_decay_steps, lr_min_ratio=lr_min_ratio)
+                                       lr_warmup=lr_warmup, lr_decay_steps=lr_decay_steps, lr_min_ratio=lr_min_ratio,
+                                       ema_sigma_rel=self.ema_sigma_rel)
             self.size = 32 if ("pad32" in G and G.pad32) else 28
             if int(get("image_size")) < 0:
                 raise ValueError(f"image_size = {get('image_size')}: 0 (28, or 32 with pad32) or the side of the square images")
@@ -306,11 +315,30 @@ def make_plugin(GMBase, AttrDict):
             self.optimizer.ema_seeded = True
             return out
 
+        # -- power-function averages (an extension, ema_sigma_rel): snapshots for the reconstruction of posthoc_ema.py
+        def save(self, path, test_x=None, test_y=None):
+            super().save(path, test_x, test_y)
+            self.write_ema_snapshot(path)
+
+        def write_ema_snapshot(self, logdir=None):
+            """The power-function arenas as they stand, to <logdir>/ema_snapshots/step_<t>.pt (rank 0; reads the device: a host sync).
+            Nothing before the first optimiser step, and nothing without ema_sigma_rel.  -> the path, or None"""
+            opt = self.optimizer
+            if not opt.gamma or opt.pema is None or opt.step_count < 1 or parallel.rank() != 0:
+                return None
+            return posthoc_ema.write_snapshot(self.G.logdir if logdir is None else logdir, opt.step_count, opt.sigma_rel, opt.gamma, opt.pema)
+
+        def _after_step(self):
+            if self.ema_snapshot_every > 0 and self.optimizer.step_count % self.ema_snapshot_every == 0:
+                self.write_ema_snapshot()
+
         # -- the state of a resumable run (an extension; checkpoint.py writes it beside model.pt as train_state.pt)
         def arena_digests(self):
             """64-bit digests (ops.arena_digest) of the four arenas a resumed run must find again; None for one that does not exist (yet)."""
             opt = self.optimizer
             arenas = {"params": self.net.flat_params, "ema": None if self.ema_net is None else self.ema_net.flat_params, "m": opt.m, "v": opt.v}
+            if opt.gamma:                           # with ema_sigma_rel only: one digest per power-function arena
+                arenas.update({f"pema{k}": None if opt.pema is None else opt.pema[k] for k in range(len(opt.gamma))})
             return {name: None if t is None else checkpoint.arena_digest(t) for name, t in arenas.items()}
 
         def train_state(self):
@@ -349,6 +377,9 @@ def make_plugin(GMBase, AttrDict):
             for name in ("m", "v"):
                 if want[name] != have[name]:
                     raise RuntimeError(f"optimizer moment '{name}' does not carry the digest recorded with it: train_state.pt is damaged")
+            for name in (k for k in have if k.startswith("pema")):
+                if want.get(name) != have[name]:
+                    raise RuntimeError(f"power-function arena '{name}' does not carry the digest recorded with it: train_state.pt is damaged")
 
         def _sampling_net(self):
             """The network sample() and evaluate() run: the weight average when EMA is on."""
@@ -411,6 +442,7 @@ def make_plugin(GMBase, AttrDict):
                 raise
             self._sync.finish()
             self.optimizer.step(grad_scale=1.0 / world)
+            self._after_step()
             metrics = self._step_metrics(ops.mean(out["loss"]))
             ops.throttle()                          # at most two steps queued on the GPU (see ops.throttle)
             return metrics
@@ -465,6 +497,7 @@ def make_plugin(GMBase, AttrDict):
             xs.copy_(x); ys.copy_(y); es.copy_(eps); us.copy_(u)
             graph.replay()
             self.optimizer.step(grad_scale=1.0)
+            self._after_step()
             metrics = self._step_metrics(loss.clone())
             ops.throttle()
             return metrics

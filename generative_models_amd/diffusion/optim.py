@@ -16,12 +16,20 @@ Three more extensions, all off by default (step() then makes exactly the calls a
   * a learning-rate schedule on the host, `lr_at`.
 The norm and the decision are formed on the device (ops.grad_norm) and read by the Adam launch (ops.adam_step_ctl): no host sync.  A skipped
 step therefore STILL advances `step_count`, and with it the bias correction, the schedule and the EMA warm-up; GradScaler does not advance the
-optimiser on a skipped step.  The count of skipped steps lives on the device (`ctl_state[ops.SKIPPED]`)."""
+optimiser on a skipped step.  The count of skipped steps lives on the device (`ctl_state[ops.SKIPPED]`).
+
+With `ema_sigma_rel` (one to three relative widths, an extension, off by default) the same launch also keeps one power-function average of
+the updated weights per width (posthoc_ema.py; Karras et al. 2024): the rows of `pema`, an fp32 [K][n] arena this optimiser owns - no network
+is built for them.  Row k after step t is lerp(row k, p_new, w_k(t)), w_k(t) = posthoc_ema.power_weight(gamma_k, t) from the host in double,
+the way the EMA's decay travels; w_k(1) = 1, so the rows are zero until step 1 overwrites them with the first updated weights and need no
+seeding.  One launch per step in every combination (steered or not, `ema_decay` on or off): ops.adam_pema_step, 28 + 8 (averages) B per
+parameter.  A step the non-finite guard skips on the device still advances t (as it does for the bias correction and the EMA warm-up): the
+rows keep their bits and the profile a reconstruction assumes is then off by the skipped steps."""
 import math
 
 import torch
 
-from .. import ops
+from .. import ops, posthoc_ema
 
 
 def ema_decay_at(decay, t):
@@ -32,7 +40,7 @@ def ema_decay_at(decay, t):
 
 class FusedAdam:
     def __init__(self, net, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, ema_net=None, ema_decay=0.0, grad_clip=0.0, skip_nonfinite=False,
-                 lr_scheduler="none", lr_warmup=0, lr_decay_steps=0, lr_min_ratio=0.1):
+                 lr_scheduler="none", lr_warmup=0, lr_decay_steps=0, lr_min_ratio=0.1, ema_sigma_rel=()):
         self.net, self.lr, self.betas, self.eps = net, float(lr), betas, float(eps)
         self.step_count = 0
         self.m = self.v = None
@@ -61,6 +69,9 @@ class FusedAdam:
         self.ctl_state = self._ctl_ws = None                              # device: [grad_norm, clip coefficient, apply, skipped steps]
         self._skipped0 = 0.0                                              # the count a loaded state dict carries, until ctl_state exists
         self.last_lr = self.lr
+        self.sigma_rel = posthoc_ema.parse_sigma_rel(ema_sigma_rel)       # () : off, step() makes the calls it always made
+        self.gamma = tuple(posthoc_ema.gamma_from_sigma_rel(s) for s in self.sigma_rel)
+        self.pema = self._pema_store = None                               # device fp32 [K][n] (a view of rows padded to 16 bytes), from the first step on
 
     def lr_at(self, t):
         """Learning rate of the step taken after `t` earlier ones, in double.  Warm-up: times min(1, (t + 1) / lr_warmup).  'cosine': from lr
@@ -84,6 +95,21 @@ class FusedAdam:
         self.ema_net.mark_params_changed()
         self.ema_seeded = True
 
+    def _ensure_pema(self):
+        """The power-function arena on the parameters' device: zeros (step 1 overwrites them), or what it held on another device."""
+        p = self.net.flat_params
+        if self.pema is None or self.pema.device != p.device:
+            n = p.numel()
+            store = torch.zeros((len(self.gamma), (n + 3) // 4 * 4), dtype=torch.float32, device=p.device)
+            if self.pema is not None:
+                store[:, :n].copy_(self.pema)
+            self._pema_store, self.pema = store, store[:, :n]
+        return self.pema
+
+    def power_weights(self, t):
+        """The K lerp weights of the update after optimiser step t (doubles; the launch rounds each once to fp32)."""
+        return [posthoc_ema.power_weight(gamma, t) for gamma in self.gamma]
+
     def step(self, grad_scale=1.0):
         p, g = self.net.flat_params, self.net.flat_grads
         if self.m is None or self.m.device != p.device:
@@ -102,7 +128,10 @@ class FusedAdam:
             ema, decay_t = self.ema_net.flat_params, ema_decay_at(self.ema_decay, self.step_count)
         self.step_count += 1                        # also when the device skips a steered step: the host never learns of it
         adam = (lr, self.betas[0], self.betas[1], self.eps, self.step_count)
-        if self.steered:
+        if self.gamma:
+            ops.adam_pema_step(p, g, self.m, self.v, self._ensure_pema(), self.power_weights(self.step_count), *adam, grad_scale, ema=ema,
+                               decay_t=decay_t, state=self.ctl_state if self.steered else None)
+        elif self.steered:
             ops.adam_step_ctl(p, g, self.m, self.v, self.ctl_state, *adam, grad_scale, ema=ema, decay_t=decay_t)
         elif ema is not None:
             ops.adam_ema_step(p, g, self.m, self.v, ema, *adam, decay_t, grad_scale)
@@ -118,8 +147,12 @@ class FusedAdam:
 
     def state_dict(self):
         """`m` and `v` are None before the first step (a checkpoint taken at epoch 0)."""
-        return {"step": self.step_count, "m": self.m, "v": self.v, "lr": self.lr, "skipped": self.skipped_steps(),
-                "ema_seeded": self.ema_seeded}
+        sd = {"step": self.step_count, "m": self.m, "v": self.v, "lr": self.lr, "skipped": self.skipped_steps(),
+              "ema_seeded": self.ema_seeded}
+        if self.gamma:                  # with ema_sigma_rel only: without it the dictionary has the keys it always had
+            sd["pema"] = None if self.pema is None else self.pema.contiguous()
+            sd["pema_sigma_rel"] = list(self.sigma_rel)
+        return sd
 
     def load_state_dict(self, sd):
         """The moments move to the arena's device; one of another size (another hidden_size, in_channels or attention flag) is refused."""
@@ -135,7 +168,22 @@ class FusedAdam:
             moments[name] = t
         if (moments["m"] is None) != (moments["v"] is None):
             raise ValueError("optimizer state holds one of 'm' and 'v' only: both, or neither (a state saved before the first step)")
+        pema = None
+        if self.gamma:
+            if "pema" not in sd or [float(s) for s in sd.get("pema_sigma_rel", ())] != list(self.sigma_rel):
+                raise ValueError(f"optimizer state tracks the power-function averages {sd.get('pema_sigma_rel', [])}, this run ema_sigma_rel = "
+                                 f"{list(self.sigma_rel)}: resume with the widths the state was saved with")
+            pema = sd["pema"]
+            if pema is not None and (pema.dtype != p.dtype or tuple(pema.shape) != (len(self.gamma), p.numel())):
+                raise ValueError(f"optimizer state 'pema' holds {pema.dtype} {tuple(pema.shape)}, this run needs {p.dtype} "
+                                 f"{(len(self.gamma), p.numel())}: the state was saved by a model of another shape")
+            if (pema is None) != (moments["m"] is None):
+                raise ValueError("optimizer state holds one of 'pema' and the moments only: both, or neither (a state saved before the first step)")
         self.step_count, self.m, self.v, self.lr = int(sd["step"]), moments["m"], moments["v"], sd["lr"]
+        if self.gamma:
+            self.pema = self._pema_store = None
+            if pema is not None:
+                self._ensure_pema().copy_(pema.detach())
         self.ema_seeded = bool(sd.get("ema_seeded", self.ema_seeded))
         self._skipped0 = float(sd.get("skipped", 0))
         if self.ctl_state is not None:

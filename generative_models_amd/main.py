@@ -430,6 +430,13 @@ def _check_nn_flags(G, n_train=None):
         raise ValueError(f"--nn_k {G.nn_k}: the training set has {n_train} images")
 
 
+def _check_posthoc_flags(G):
+    """The flags of the power-function averages (models that have them), named before any model is built."""
+    if "ema_sigma_rel" in G or "ema_snapshot_every" in G:
+        from . import posthoc_ema
+        posthoc_ema.check_flags(G.get("ema_sigma_rel", ""), G.get("ema_snapshot_every", 0))
+
+
 def _device_datasets(G, device, rank, world):
     root = str(G.data_root)
     if G.data == "mnist":
@@ -461,6 +468,7 @@ def load_model_and_data(argv=None):
     _check_data_flags(G)
     _check_image_flags(G)
     _check_nn_flags(G)
+    _check_posthoc_flags(G)
     init_distributed()
     _check_resume_flags(G, Model)                                      # after init_distributed: the state file names its world size
     device = _run_device(G.device)

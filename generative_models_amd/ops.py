@@ -1674,6 +1674,55 @@ def adam_step_ctl(p, g, m, v, state, lr, beta1, beta2, eps, step, grad_scale=1.0
                                 1.0 - float(decay_t), _p(state), _s()), "adam_step_ctl")
 
 
+def _row_arena(t, n, name):
+    """-> (tensor, row stride) of an fp32 [K][>= n] device arena whose rows are contiguous (a [:, :n] view of padded storage is one).  Rows
+    narrower than n are reported as that width, which the library refuses by name."""
+    if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{name}: expected an fp32 device tensor [K][stride] with contiguous rows, got {t.dtype} {tuple(t.shape)} strides "
+                         f"{tuple(t.stride())}")
+    if t.shape[1] < n or t.shape[0] < 2:
+        return t, t.shape[1]
+    if t.stride(0) < t.shape[1]:
+        raise ValueError(f"{name}: rows overlap (strides {tuple(t.stride())})")
+    return t, t.stride(0)
+
+
+def adam_pema_step(p, g, m, v, pema, weights, lr, beta1, beta2, eps, step, grad_scale=1.0, ema=None, decay_t=0.0, state=None):
+    """adam_step (state None) or adam_step_ctl (state: grad_norm's record), then the classic average when `ema` is given (adam_ema_step's bits),
+    then row k of `pema` (fp32 [K][stride >= n], K = 1 .. 3) = lerp(row k, p_new, weights[k]) - one launch, every arena read and written once
+    (gmk_adam_pema_step).  weights: K floats in [0, 1]."""
+    _adam_arenas(p, g, m, v, ema)
+    n = p.numel()
+    pema, stride = _row_arena(pema, n, "pema")
+    weights = [float(w) for w in weights]
+    if len(weights) != pema.shape[0]:
+        raise ValueError(f"pema has {pema.shape[0]} rows, {len(weights)} weights given")
+    if state is not None:
+        _f32(state, "state")
+        assert state.numel() == 4
+    pw = (weights + [0.0, 0.0, 0.0])[:3]
+    check(lib.gmk_adam_pema_step(_p(p), _p(g), _p(m), _p(v), _p(ema), _p(pema), stride, pema.shape[0], n, lr, beta1, beta2, eps, step,
+                                 grad_scale, 1.0 - float(decay_t), *pw, _p(state), _s()), "adam_pema_step")
+
+
+def arena_combine(src, coef, out=None, n=None):
+    """out[i] = fp32(sum_k coef[k] src[k][i]) accumulated in double in index order, each product and sum rounded on its own (gmk_arena_combine):
+    src fp32 [K][stride >= n] on the device with contiguous rows, K = 1 .. 64; coef: K float64 values (any sequence, or a device tensor); n:
+    columns combined (default: all of them).  -> out, fp32 [n] (must not overlap src)"""
+    n = src.shape[1] if n is None else int(n)
+    src, stride = _row_arena(src, n, "src")
+    if not (isinstance(coef, torch.Tensor) and coef.is_cuda):
+        coef = torch.as_tensor(coef, dtype=torch.float64).to(src.device)
+    if coef.dtype != torch.float64 or not coef.is_contiguous() or coef.dim() != 1 or coef.numel() != src.shape[0]:
+        raise ValueError(f"coef: expected {src.shape[0]} contiguous float64 values, got {coef.dtype} {tuple(coef.shape)}")
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float32, device=src.device)
+    if not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n:
+        raise ValueError(f"out: expected {n} contiguous fp32 values on the device, got {out.dtype} {tuple(out.shape)}")
+    check(lib.gmk_arena_combine(_p(src), stride, _p(coef), src.shape[0], _p(out), n, _s()), "arena_combine")
+    return out
+
+
 def arena_digest(t):
     """64-bit digest of a tensor's bytes read as 4-byte words (gmk_arena_digest; checkpoint.digest_host is the same function in numpy):
     any contiguous CUDA tensor whose byte size is a positive multiple of 4.  -> an unsigned Python int (reads the device: a host sync)"""

@@ -750,6 +750,25 @@ int gmk_grad_norm(const float* g, int64_t n, float grad_scale, float max_norm, f
  * launch returns before it touches p, m, v or ema. */
 int gmk_adam_step_ctl(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2, float eps,
                       int step, float grad_scale, float ema_w, const float* state, void* stream);
+/* The Adam step of gmk_adam_step (state NULL) or gmk_adam_step_ctl (state: gmk_grad_norm's record, same semantics: when apply is 0 the launch
+ * returns before it touches any memory), then optionally the classic average (ema may be NULL; else gmk_adam_ema_step's bits), then n_pema
+ * more averages of the updated weights, 1 <= n_pema <= 3: the rows of one fp32 [n_pema][pema_stride] arena,
+ *     row_k = lerp(row_k, p_new, pw_k),   k < n_pema,   pw_k in [0, 1]   (pw_k with k >= n_pema is not read)
+ * each row the bits gmk_adam_ema_step would write into it under ema_w = pw_k.  No reference call site: the power-function averages of Karras
+ * et al. 2024 (post-hoc EMA), whose weights pw_k = 1 - (1 - 1/t)^(gamma_k + 1) come from the host every step (an extension, off by default,
+ * DG.ema_sigma_rel).  pema_stride >= n; columns >= n of a row are never touched; rows take 16-byte accesses when pema is 16-byte aligned and
+ * pema_stride % 4 == 0, scalar ones otherwise.  Everything is read once and written once: 28 + 8 (averages) B / parameter.  Any n.  No row of
+ * GMK_KERNEL_TABLE. */
+int gmk_adam_pema_step(float* p, const float* g, float* m, float* v, float* ema, float* pema, int64_t pema_stride, int n_pema, int64_t n,
+                       float lr, float beta1, float beta2, float eps, int step, float grad_scale, float ema_w, float pw0, float pw1, float pw2,
+                       const float* state, void* stream);
+/* out[i] = fp32(sum_k coef[k] src[k][i]), i < n: src fp32 [K][src_stride] (src_stride >= n), coef K doubles on the device, 1 <= K <= 64.  In
+ * double: acc = coef[0] row_0, then acc = acc + coef[k] row_k for k = 1 .. K - 1 in index order, every product and every sum rounded on its
+ * own (no contraction), acc rounded once to fp32 - a function of the inputs alone, which a float64 loop on the host reproduces bit for bit.
+ * out must not overlap src.  16-byte loads when src and out are 16-byte aligned and src_stride % 4 == 0, scalar ones otherwise and for the
+ * n & 3 tail.  4 K + 4 B / element.  No reference call site: the reconstruction step of post-hoc EMA (posthoc_ema.py).  No row of
+ * GMK_KERNEL_TABLE. */
+int gmk_arena_combine(const float* src, int64_t src_stride, const double* coef, int K, float* out, int64_t n, void* stream);
 /* 64-bit digest of a device buffer of n_words 4-byte words (no reference call site: checkpoint.py ties model.pt to train_state.pt with it,
  * compares data-parallel replicas and arenas without a host copy).  In uint64 arithmetic mod 2^64, w_i the raw bits of word i (from 0):
  *   digest = sum_i mix(w_i + (i + 1) 0x9E3779B97F4A7C15),   mix = splitmix64's finaliser (x ^= x >> 30; x *= 0xBF58476D1CE4E5B9;
