@@ -208,6 +208,12 @@ __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d
     return (unsigned)v;
 }
 
+// q, k and v saturate to +-448, the largest e4m3 magnitude, before the rounding (the contract in gmk.h; NaN stays NaN).  P needs none: p <= 1.
+__device__ __forceinline__ float sat_e4m3(float x) { return x > 448.f ? 448.f : (x < -448.f ? -448.f : x); }
+__device__ __forceinline__ unsigned pack4_fp8_sat(float a, float b, float c, float d) {
+    return pack4_fp8(sat_e4m3(a), sat_e4m3(b), sat_e4m3(c), sat_e4m3(d));
+}
+
 template <bool kFp8>
 __global__ __launch_bounds__(512, 2) void attn_fused_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o,
                                                                bf16_t* __restrict__ pout, int N, float c_log2e) {
@@ -231,15 +237,15 @@ __global__ __launch_bounds__(512, 2) void attn_fused_fwd_kernel(const bf16_t* __
             *reinterpret_cast<bf16x8*>(Ks + row * 256 + ((ch ^ (row & 15)) << 4)) = kv;
             *reinterpret_cast<bf16x8*>(Vs + row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4)) = vv;
         } else {
-            u32x2a k8 = {pack4_fp8((float)kv[0], (float)kv[1], (float)kv[2], (float)kv[3]),
-                         pack4_fp8((float)kv[4], (float)kv[5], (float)kv[6], (float)kv[7])};
+            u32x2a k8 = {pack4_fp8_sat((float)kv[0], (float)kv[1], (float)kv[2], (float)kv[3]),
+                         pack4_fp8_sat((float)kv[4], (float)kv[5], (float)kv[6], (float)kv[7])};
             *reinterpret_cast<u32x2a*>(Ks + row * 128 + ((ch ^ ((row >> 1) & 15)) << 3)) = k8;
             // V^T image: byte (d, pos), pos = the key's place in the k order of the P^T operand: key = 32 kb + 16 s + 8 g + 4 hh + jj
             // sits at pos = 32 kb + 16 s + 8 hh + 4 g + jj
             const int kin = row & 31;
             const int pos = (row & ~31) | (kin & 16) | (((kin >> 2) & 1) << 3) | (((kin >> 3) & 1) << 2) | (kin & 3);
-            const unsigned lo = pack4_fp8((float)vv[0], (float)vv[1], (float)vv[2], (float)vv[3]);
-            const unsigned hi = pack4_fp8((float)vv[4], (float)vv[5], (float)vv[6], (float)vv[7]);
+            const unsigned lo = pack4_fp8_sat((float)vv[0], (float)vv[1], (float)vv[2], (float)vv[3]);
+            const unsigned hi = pack4_fp8_sat((float)vv[4], (float)vv[5], (float)vv[6], (float)vv[7]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int d = ch * 8 + e;
@@ -260,8 +266,8 @@ __global__ __launch_bounds__(512, 2) void attn_fused_fwd_kernel(const bf16_t* __
     if (kFp8) {
 #pragma unroll
         for (int kg = 0; kg < 8; ++kg) {
-            const u32x2a v = {pack4_fp8((float)qf[kg][0], (float)qf[kg][1], (float)qf[kg][2], (float)qf[kg][3]),
-                              pack4_fp8((float)qf[kg][4], (float)qf[kg][5], (float)qf[kg][6], (float)qf[kg][7])};
+            const u32x2a v = {pack4_fp8_sat((float)qf[kg][0], (float)qf[kg][1], (float)qf[kg][2], (float)qf[kg][3]),
+                              pack4_fp8_sat((float)qf[kg][4], (float)qf[kg][5], (float)qf[kg][6], (float)qf[kg][7])};
             q8[kg] = __builtin_bit_cast(long, v);
         }
     }

@@ -1818,7 +1818,8 @@ def bgemm_nt(A, B, out=None, alpha=1.0, out_dtype=None):
 
 def attention_fwd(qkv, scale, want_p=False, fp8=False):
     """Fused softmax(scale * q k^T) v for qkv [B, N, 3C] (bf16, C = 128, N in {64, 128, 256}) -> (o [B, N, C], P [B, N, N] or None).
-    fp8: both contractions on the fp8 (e4m3) matrix cores."""
+    fp8: both contractions on the fp8 (e4m3) matrix cores; q, k and v saturate to +-448, the largest e4m3 magnitude, before the e4m3
+    rounding (round to nearest even; NaN stays NaN)."""
     _chk(qkv, torch.bfloat16, "qkv")
     B, N, C3 = qkv.shape
     C = C3 // 3

@@ -605,7 +605,8 @@ int gmk_softmax_fwd(const float* S, void* P, int64_t rows, int N, float scale, i
 /* fused forward of the block's core: o[b] = softmax(scale * q[b] k[b]^T) v[b] with q, k, v the three C-column blocks of qkv
  * [B][N][3C] (bf16), one workgroup per sample, K / V resident in LDS, no N x N matrix in HBM unless p_out (bf16 [B][N][N], the
  * probabilities the backward pass needs) is given.  fp8 != 0: both contractions on the fp8 (OCP e4m3) matrix cores with fp32
- * accumulation - BASELINE config 5's "fp8 MFMA".  C = 128, N in {64, 128, 256}. */
+ * accumulation - BASELINE config 5's "fp8 MFMA".  With fp8, q, k and v saturate to +-448, the largest e4m3 magnitude, before the e4m3
+ * rounding (round to nearest even; NaN stays NaN).  C = 128, N in {64, 128, 256}. */
 int gmk_attention_fwd(const void* qkv, void* o, void* p_out, int B, int N, int C, float scale, int fp8, void* stream);
 /* fused backward of the same core (round 5): dqkv [B][N][3C] (bf16) = (dq | dk | dv) given d_o [B][N][C] (bf16), the forward's inputs qkv and output o.
  * P is recomputed block by block in registers: no N x N matrix in HBM (the three-kernel path kept P [B][N][N] and a fp32 dP of that shape).  stats:
