@@ -24,7 +24,8 @@ import torch
 
 from .. import checkpoint, common, ops, parallel, posthoc_ema
 from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, consistency_check, dyn_threshold_check, edit_start, guidance_check,
-                                 loss_weight_check, restore_operator, schedule_check, stochastic_check, time_importance_check, learned_var_check)
+                                 loss_weight_check, restore_operator, schedule_check, stochastic_check, time_importance_check, learned_var_check,
+                                 FLAG_WORDS, sampler_caps, sampler_compat_check)
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -192,28 +193,16 @@ def make_plugin(GMBase, AttrDict):
             self.restore_gray = int(get("restore_gray"))
             if self.restore_gray and int(get("in_channels")) == 1:
                 raise ValueError("restore_gray = 1 with in_channels = 1: there is no colour to restore")
-            if (self.restore_eval or self.restore_gray) and float(get("dyn_threshold")) > 0:
-                raise ValueError("restore_eval / restore_gray with dyn_threshold: restoration together with dynamic thresholding is out of scope")
             self.binarize = int(get("binarize"))
             dyn_threshold = dyn_threshold_check(get("dyn_threshold"))
-            if get("sampler") == "consistency":
-                for name, on in (("dyn_threshold", dyn_threshold > 0), ("inpaint_eval", self.inpaint_eval > 0),
-                                 ("restore_eval / restore_gray", bool(self.restore_eval or self.restore_gray))):
-                    if on:
-                        raise ValueError(f"sampler = 'consistency' with {name}: multistep consistency sampling together with dynamic thresholding, "
-                                         f"inpainting or restoration is out of scope")
             learn_var, vlb_lambda, vlb_steps = learned_var_check(get("learn_var"), get("vlb_lambda"), get("vlb_steps"), self.teacher_net is not None,
                                                                  get("loss_weight"))
-            stochastic, posterior_var, ddim_eta = stochastic_check(get("sampler"), get("posterior_var"), get("ddim_eta"), learn_var)
-            if stochastic:
-                for name, on in (("inpaint_eval", self.inpaint_eval > 0), ("restore_eval / restore_gray", bool(self.restore_eval or self.restore_gray))):
-                    if on:
-                        raise ValueError(f"sampler = {get('sampler')!r}, ddim_eta = {ddim_eta} with {name}: the stochastic samplers together with "
-                                         f"inpainting or restoration are out of scope")
+            _, posterior_var, ddim_eta = stochastic_check(get("sampler"), get("posterior_var"), get("ddim_eta"), learn_var)
             guidance_interval, cfg_rescale = guidance_check((get("guidance_lo"), get("guidance_hi")), get("cfg_rescale"), get("sampler"),
                                                             dyn_threshold)
-            if (self.restore_eval or self.restore_gray) and cfg_rescale > 0:
-                raise ValueError("restore_eval / restore_gray with cfg_rescale: restoration together with the rescaled guided prediction is out of scope")
+            # what goes with the sampler, by the loop's own table: asked once per evaluation extra (each is a sampler run of its own at evaluate())
+            for one in (dict(inpaint=min(self.inpaint_eval, 1)), dict(restore=self.restore_eval or self.restore_gray)):
+                sampler_compat_check(sampler_caps(get("sampler"), ddim_eta), dyn_threshold=dyn_threshold, cfg_rescale=cfg_rescale, words=FLAG_WORDS, **one)
             loss_weight, loss_gamma, time_sampler = loss_weight_check(get("loss_weight"), get("loss_gamma"), get("time_sampler"),
                                                                       self.teacher_net is not None)
             time_importance, importance_decay, importance_warmup, importance_floor, loss_profile = time_importance_check(

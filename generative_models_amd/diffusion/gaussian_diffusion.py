@@ -234,7 +234,55 @@ def dpm_solver_coefs(num_steps, start=None, schedule=None):
 
 StochCoef = namedtuple("StochCoef", "i lt ls coef_z coef_x coef_noise coef_prev")
 STOCHASTIC_KINDS = ("ancestral", "ddim_eta", "sde_dpmpp_2m")
-STOCHASTIC_SAMPLERS = ("ancestral", "sde_dpmpp_2m")      # the sampler names gmk_stochastic_step adds ('ddim' with ddim_eta > 0 runs on it too)
+
+# What the sampler loop and every option check know about a sampler, one row per name.  tag: how an error message names it; update: the `ops`
+# wrapper of its update ('stochastic_step' is 'stochastic_step_lv' under posterior_var 'learned'); noise: "" - none, "arg" - one draw per network
+# evaluation, made by ops.rng_normal or injected (`noises`) and handed to the update, "kernel" - one draw per evaluation made inside the update (no
+# injected noises, n % 4 == 0); thr: the update has the thresholded form (dyn_threshold, cfg_rescale); x_hist: it keeps the previous x-hat;
+# inpaint: the largest `resample` it inpaints with (0: it does not inpaint); restore: it restores (the update's ns form)
+SamplerCaps = namedtuple("SamplerCaps", "tag update noise thr x_hist inpaint restore")
+SAMPLER_CAPS = {
+    "ddim":         SamplerCaps("sampler 'ddim'",         "sampler_step",     "",       True,  False, math.inf, True),
+    "noisy":        SamplerCaps("sampler 'noisy'",        "sampler_step",     "arg",    True,  False, math.inf, True),
+    "teacher_test": SamplerCaps("sampler 'teacher_test'", "sampler_step",     "",       True,  False, math.inf, False),
+    "dpmpp_2m":     SamplerCaps("sampler 'dpmpp_2m'",     "dpm_solver_step",  "",       True,  True,  1,        True),
+    "consistency":  SamplerCaps("sampler 'consistency'",  "consistency_step", "kernel", False, False, 0,        False),
+    "ancestral":    SamplerCaps("sampler 'ancestral'",    "stochastic_step",  "kernel", True,  False, 0,        False),
+    "sde_dpmpp_2m": SamplerCaps("sampler 'sde_dpmpp_2m'", "stochastic_step",  "kernel", True,  True,  0,        False),
+}
+DDIM_ETA_CAPS = SAMPLER_CAPS["ancestral"]._replace(tag="sampler 'ddim' with ddim_eta > 0")      # the row 'ddim' takes when ddim_eta > 0
+STOCHASTIC_SAMPLERS = tuple(name for name, caps in SAMPLER_CAPS.items() if caps.update == "stochastic_step")      # the names gmk_stochastic_step adds
+
+
+def sampler_caps(sampler, ddim_eta=0.0):
+    """The `SAMPLER_CAPS` row of a sampler name under `ddim_eta`; None for a name the loop does not know (`sample` raises NotImplementedError)."""
+    return DDIM_ETA_CAPS if sampler == "ddim" and float(ddim_eta) > 0.0 else SAMPLER_CAPS.get(sampler)
+
+
+# how a caller names the features in `sampler_compat_check`'s messages: a method of `GaussianDiffusion`, or the model's flags
+FEATURE_WORDS = {"inpaint": "inpainting", "restore": "restoration", "dyn_threshold": "dyn_threshold", "cfg_rescale": "cfg_rescale"}
+FLAG_WORDS = {**FEATURE_WORDS, "inpaint": "inpaint_eval", "restore": "restore_eval / restore_gray"}
+
+
+def sampler_compat_check(caps, *, inpaint=0, restore=False, dyn_threshold=False, cfg_rescale=False, noises=False, n1=4, words=FEATURE_WORDS):
+    """Does the sampler of row `caps` (`sampler_caps`; None, an unknown name, passes: the loop refuses it) go with what a call wants?  inpaint:
+    0, or the `resample` count of inpainting; restore, dyn_threshold, cfg_rescale, noises (injected): is the feature asked for; n1: the values
+    per image.  Every caller passes what it knows of, and names the features by `words`.  Restoration goes with none of inpainting,
+    dyn_threshold and cfg_rescale (the projected x-hat must not be rescaled), whatever the sampler.  -> None, or ValueError naming both sides."""
+    asked = {"inpaint": inpaint > 0, "dyn_threshold": bool(dyn_threshold), "cfg_rescale": bool(cfg_rescale), "restore": bool(restore)}
+    able = caps and {"inpaint": caps.inpaint > 0, "dyn_threshold": caps.thr, "cfg_rescale": caps.thr, "restore": caps.restore}
+    for feature, on in asked.items():
+        if on and asked["restore"] and feature != "restore":
+            raise ValueError(f"{words['restore']} together with {words[feature]} is out of scope")
+        if on and caps is not None and not able[feature]:
+            raise ValueError(f"{caps.tag} together with {words[feature]} is out of scope")
+    drawn = caps is not None and caps.noise == "kernel"
+    if caps is not None and inpaint > caps.inpaint:
+        raise ValueError(f"{caps.tag} takes resample <= {caps.inpaint} only (its x-hat history has no meaning across a jump back)")
+    if drawn and noises:
+        raise ValueError(f"{caps.tag} draws its noise in the update kernel (self.rng's Philox stream): noises cannot be injected")
+    if drawn and n1 % 4:
+        raise ValueError(f"{caps.tag}: {n1} values per image, a multiple of 4 is required")
 
 
 def posterior_var_frac(posterior_var):
@@ -392,8 +440,8 @@ def guidance_check(interval, phi, sampler="ddim", dyn_threshold=0.0):
     """The options of the guided samplers beyond the weight: `interval` None (guidance at every step) or (lo, hi), lo <= hi, the band of
     log-SNRs in which a step is guided (Kynkaanniemi et al. 2024; either end may be infinite, (-inf, inf) is None); `phi` the rescale of the
     guided prediction (Lin et al. 2023, section 3.4): 0 is off, else in (0, 1].  phi > 0 does not go with dyn_threshold (both set the update's
-    threshold) nor with sampler 'consistency' (its update has no thresholded form).  -> (interval as None or a pair of floats, float(phi)), or
-    ValueError naming the option (NaNs included)."""
+    threshold) nor with a sampler whose update has no thresholded form (`sampler_compat_check`).  -> (interval as None or a pair of floats,
+    float(phi)), or ValueError naming the option (NaNs included)."""
     if interval is not None:
         try:
             lo, hi = interval
@@ -411,8 +459,7 @@ def guidance_check(interval, phi, sampler="ddim", dyn_threshold=0.0):
         raise ValueError(f"cfg_rescale = {phi}: 0 (off) or a factor in (0, 1]")
     if phi > 0.0 and dyn_threshold:
         raise ValueError(f"cfg_rescale = {phi} together with dyn_threshold = {dyn_threshold}: both set the threshold of the update; choose one")
-    if phi > 0.0 and sampler == "consistency":
-        raise ValueError(f"cfg_rescale = {phi} with sampler 'consistency': its update has no thresholded form; leave cfg_rescale at 0")
+    sampler_compat_check(sampler_caps(sampler), cfg_rescale=phi > 0.0)
     return interval, phi
 
 
@@ -1406,8 +1453,7 @@ class GaussianDiffusion:
         if isinstance(r, bool) or int(r) != r or r < 1:
             raise ValueError(f"inpaint: resample = {resample}, need an integer >= 1")
         r = int(r)
-        if self.sampler == "dpmpp_2m" and r > 1:
-            raise ValueError("inpaint: sampler 'dpmpp_2m' takes resample = 1 only (its x-hat history has no meaning across a jump back)")
+        sampler_compat_check(sampler_caps(self.sampler, self.ddim_eta), inpaint=r)
         shape = tuple(init_x.shape)
         if tuple(x0.shape) != shape:
             raise ValueError(f"inpaint: x0 shape {tuple(x0.shape)} differs from init_x shape {shape}")
@@ -1425,11 +1471,7 @@ class GaussianDiffusion:
         noise.  Two extra launches per network evaluation: gmk_box_residual, then the *_ns update.  Samplers 'ddim', 'noisy', 'dpmpp_2m'; `net`
         / `cond_w` (guidance) and the noise of 'noisy' as in `sample`.  Out of scope, and a ValueError: noisy observations (DDNM+), time
         travel, and restoration together with dynamic thresholding or inpainting.  -> sample()'s triple."""
-        if self.sampler == "teacher_test":
-            raise ValueError("restore: sampler 'teacher_test' is not supported (samplers 'ddim', 'noisy', 'dpmpp_2m')")
-        if self.dyn_threshold:
-            raise ValueError("restore: dyn_threshold is set: restoration together with dynamic thresholding (or inpainting) is out of scope - "
-                             "the projected x-hat must not be rescaled")
+        sampler_compat_check(sampler_caps(self.sampler, self.ddim_eta), restore=True, dyn_threshold=self.dyn_threshold)
         shape = tuple(init_x.shape)
         cf, N, low = restore_operator(shape, factor, gray)
         if not isinstance(obs, torch.Tensor) or tuple(obs.shape) != low:
@@ -1520,38 +1562,19 @@ class GaussianDiffusion:
     def _sample(self, *, net, init_x, cond_w=None, record=True, noises=None, net_cond_w=None, inp=None, start=None, rst=None):
         """The loop behind `sample`, `inpaint`, `edit` and `restore` (inp: None, or the whole batch's InpaintState; start: `sampler_plan`'s; rst:
         None, or the whole batch's RestoreState)."""
-        if rst is not None and (inp is not None or self.dyn_threshold):
-            raise ValueError("restore: restoration together with inpainting or dynamic thresholding is out of scope")
-        if rst is not None and self.cfg_rescale:
-            raise ValueError("restore: cfg_rescale is set: restoration together with cfg_rescale is out of scope - the projected x-hat must not "
-                             "be rescaled")
         guidance_check(self.guidance_interval, self.cfg_rescale, self.sampler, self.dyn_threshold)      # the attributes may have been set since
         module, guide, kw_cond_w = _unwrap(net)
         B = init_x.shape[0]
         dev = init_x.device
-        if cond_w is not None and net_cond_w is None:
-            net_cond_w = 4.0 * self.rng.uniform((B,), dev)           # :247-251
-        if self.sampler not in ("ddim", "noisy", "teacher_test", "dpmpp_2m", "consistency") + STOCHASTIC_SAMPLERS:
+        if self.sampler not in SAMPLER_CAPS:
             raise NotImplementedError(self.sampler)
         # (the attributes may have been set since; the variance head is the sampling network's own)
-        stochastic, _, _ = stochastic_check(self.sampler, self.posterior_var, self.ddim_eta, getattr(module, "learn_var", False))
-        if stochastic:      # gmk_stochastic_step: fresh noise at every step but the last, drawn in the update kernel
-            name = f"sampler {self.sampler!r}" + (f" with ddim_eta = {self.ddim_eta}" if stochastic == "ddim_eta" else "")
-            for what, on in (("inpainting", inp is not None), ("restoration", rst is not None)):
-                if on:
-                    raise ValueError(f"{name} together with {what} is out of scope")
-            if noises is not None:
-                raise ValueError(f"{name} draws its noise in the update kernel (self.rng's Philox stream): noises cannot be injected")
-            if int(np.prod(init_x.shape[1:])) % 4:
-                raise ValueError(f"{name}: {int(np.prod(init_x.shape[1:]))} values per image, a multiple of 4 is required")
-        if self.sampler == "consistency":       # multistep consistency sampling: fresh noise at every step but the last, drawn in the update kernel
-            for what, on in (("inpainting", inp is not None), ("restoration", rst is not None), ("dyn_threshold", bool(self.dyn_threshold))):
-                if on:
-                    raise ValueError(f"sampler 'consistency' together with {what} is out of scope")
-            if noises is not None:
-                raise ValueError("sampler 'consistency' draws its noise in the update kernel (self.rng's Philox stream): noises cannot be injected")
-            if int(np.prod(init_x.shape[1:])) % 4:
-                raise ValueError(f"sampler 'consistency': {int(np.prod(init_x.shape[1:]))} values per image, a multiple of 4 is required")
+        stochastic_check(self.sampler, self.posterior_var, self.ddim_eta, getattr(module, "learn_var", False))
+        caps = sampler_caps(self.sampler, self.ddim_eta)
+        sampler_compat_check(caps, inpaint=0 if inp is None else inp.resample, restore=rst is not None, dyn_threshold=self.dyn_threshold,
+                             cfg_rescale=self.cfg_rescale, noises=noises is not None, n1=int(np.prod(init_x.shape[1:])))
+        if cond_w is not None and net_cond_w is None:
+            net_cond_w = 4.0 * self.rng.uniform((B,), dev)           # :247-251
         student_w, w, use_teacher = resolve_guidance(sample_cond_w=self.sample_cond_w, net_cond_w=net_cond_w, kw_cond_w=kw_cond_w,
                                                      has_teacher=self.teacher_net is not None, sampler=self.sampler)
         if use_teacher:
@@ -1591,7 +1614,7 @@ class GaussianDiffusion:
             inp_k = None if inp is None else inp._replace(x0=cut(inp.x0, a, b_), mask=cut(inp.mask, a, b_))
             rst_k = None if rst is None else rst._replace(obs=cut(rst.obs, a, b_))
             gens.append(self._sample_chunk(plan, module, cut(guide, a, b_), cut(student_w, a, b_), cut(w, a, b_), cut(z_all, a, b_),
-                                           noises if (noises is None or K == 1) else torch.as_tensor(noises)[:, a:b_], record, offs, a * n1 // 4, inp_k, rst_k))
+                                           noises if (noises is None or K == 1) else torch.as_tensor(noises)[:, a:b_], record, offs, a * n1 // 4, caps, inp_k, rst_k))
         if K > 1:
             # what a forward builds lazily after a weight update (packed weights, frequency tables) is enqueued HERE, on the stream both chunk
             # streams wait for: the first chunk's forward would otherwise re-pack on ITS stream and clear the host flag, and the second chunk's
@@ -1610,7 +1633,7 @@ class GaussianDiffusion:
             return outs
         for step in plan:
             for _ in range(step.passes):
-                if (self.sampler in ("noisy", "consistency") or stochastic) and noises is None:
+                if caps.noise and noises is None:
                     offs.append(self.rng._take(B * n1))
                 if inp is not None:
                     inp.moffs.append(inp.rng._take(2 * B * n1))     # eps1 and eps2 of one merge, used or not
@@ -1635,11 +1658,11 @@ class GaussianDiffusion:
             self._streams = [torch.cuda.Stream(device=dev) for _ in range(K)]
         return self._streams[:K]
 
-    def _sample_chunk(self, plan, module, guide, student_w, w, z_t, noises, record, offs, q0, inp=None, rst=None):
+    def _sample_chunk(self, plan, module, guide, student_w, w, z_t, noises, record, offs, q0, caps, inp=None, rst=None):
         """The sampler loop over one (chunk of a) batch as a generator: one `next` per step of `plan` (everything it launches goes to the stream
         current at that call), then one more for the result.  offs[f] / q0: Philox counter of network evaluation `f`'s whole-batch noise draw /
-        this chunk's offset in it.  inp (inpainting): None, or the InpaintState with this chunk's rows of x0 and mask - inp.moffs[f] is the
-        whole-batch Philox counter of evaluation f's merge.  rst (restoration): None, or the RestoreState with this chunk's rows of obs."""
+        this chunk's offset in it; caps: `sampler_caps`' row.  inp: None, or the InpaintState with this chunk's rows of x0 and mask - inp.moffs[f]
+        is the whole-batch Philox counter of evaluation f's merge.  rst: None, or the RestoreState with this chunk's rows of obs."""
         B = z_t.shape[0]
         zs, xs, es = [], [], []
         # the mode of every network evaluation: guided (the 2B-image batch) or not (the B-image batch with the caller's labels alone).  Without a
@@ -1652,7 +1675,7 @@ class GaussianDiffusion:
         # launch it kernel by kernel), its log-SNR buffers and its conditioning
         runners = {}
         # posterior_var 'learned': every forward also runs the variance head, over the conditional rows alone (the first B of a guided 2B batch)
-        want_nu = B if self.posterior_var == "learned" and self.sampler == "ancestral" else 0
+        want_nu = B if self.posterior_var == "learned" and caps.update == "stochastic_step" else 0
         if False in modes:
             runners[False] = self._forward_runner(module, z_t, guide, student_w, nb_max, want_nu) + (guide, student_w)
         if True in modes:       # conditional + unconditional evaluations share one 2B-image forward (:176-177)
@@ -1672,10 +1695,26 @@ class GaussianDiffusion:
             out, nu = out if want_nu else (out, None)
             return (out[:B], out[B:], nu) if g else (out, None, nu)
         # dpmpp_2m: the previous step's x-hat, [B, ...] also when guided (the kernel reads and rewrites it in place; the first step does not read it)
-        x_hist = torch.empty_like(z_t) if self.sampler in ("dpmpp_2m", "sde_dpmpp_2m") else None
+        x_hist = torch.empty_like(z_t) if caps.x_hist else None
+        # the update, chosen once: the wrapper's own leading arguments (s: the step, f: the evaluation) and, where it has the form, thr / ns; the
+        # keywords all five share come as `kw`, stated once at the call ('_lv': 'ancestral' under the learned variance, the 'small' row scaled per element)
+        seed, name = self.rng.seed, caps.update + ("_lv" if want_nu else "")
+        if name == "sampler_step":
+            update = lambda s, f, v, z, nu, noise, thr, ns, kw: ops.sampler_step(v, z, s.lt, s.ls, s.is_last, noise=noise, thr=thr, ns=ns, **kw)
+        elif name == "dpm_solver_step":
+            update = lambda s, f, v, z, nu, noise, thr, ns, kw: ops.dpm_solver_step(
+                v, z, x_hist, s.lt, s.ls, s.dpm.coef_z, s.dpm.coef_x, s.dpm.coef_prev, s.is_last, thr=thr, ns=ns, **kw)
+        elif name == "consistency_step":
+            update = lambda s, f, v, z, nu, noise, thr, ns, kw: ops.consistency_step(v, z, s.lt, s.ls, s.is_last, seed, offs[f], q0=q0, **kw)
+        elif name == "stochastic_step":
+            update = lambda s, f, v, z, nu, noise, thr, ns, kw: ops.stochastic_step(v, z, s.lt, s.ls,
+                s.sto.coef_z, s.sto.coef_x, s.sto.coef_noise, s.sto.coef_prev, s.is_last, seed, offs[f], q0=q0, x_hist=x_hist, thr=thr, **kw)
+        else:
+            update = lambda s, f, v, z, nu, noise, thr, ns, kw: ops.stochastic_step_lv(v, z, nu, s.lt, s.ls,
+                s.sto.coef_z, s.sto.coef_x, s.sto.coef_noise, learned_half_delta(s.lt, s.ls), s.is_last, seed, offs[f], q0=q0, thr=thr, **kw)
         f = 0                                   # network evaluations so far (one per step unless inpainting resamples)
         for step in plan:
-            i, lt, ls, dpm, mrg, sto = step.i, step.lt, step.ls, step.dpm, step.inp, step.sto
+            i, lt, ls, mrg = step.i, step.lt, step.ls, step.inp
             for p in range(step.passes):
                 # this evaluation's mode and the next one's: every launch that writes the next batch and its time vector (the update, the
                 # inpainting merge) does so in the form the NEXT evaluation needs - the duplicate and the 2B vector iff that one is guided
@@ -1684,7 +1723,7 @@ class GaussianDiffusion:
                 v, vu, nu = evaluate(g, z2 if g else z_t, f)
                 wg = w if g else None
                 noise = None
-                if self.sampler == "noisy":                 # :241
+                if caps.noise == "arg":                     # :241
                     noise = ops.aligned(noises[i]) if noises is not None else ops.rng_normal(tuple(z_t.shape), self.rng.seed, offs[f] + q0, z_t.device)
                 # dynamic thresholding: one select launch per network evaluation (per image, so a half-batch gives the whole batch's bits)
                 thr = ops.dyn_threshold(v, z_t, lt, self.dyn_threshold, v_uncond=vu, cond_w=wg, mean_type=self.mean_type) if self.dyn_threshold else None
@@ -1694,23 +1733,8 @@ class GaussianDiffusion:
                 # restoration: one residual launch per network evaluation (per image, so a half-batch gives the whole batch's bits)
                 ns = None if rst is None else (ops.box_residual(v, z_t, rst.obs, lt, rst.cf, rst.N, v_uncond=vu, cond_w=wg, mean_type=self.mean_type),
                                                rst.cf, rst.N)
-                if self.sampler == "consistency":
-                    z_t, xp, ep = ops.consistency_step(v, z_t, lt, ls, step.is_last, self.rng.seed, offs[f], q0=q0, v_uncond=vu, cond_w=wg,
-                                                       want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext)
-                elif sto is not None and nu is not None:      # 'ancestral' under the learned variance: the 'small' row, scaled per element
-                    z_t, xp, ep = ops.stochastic_step_lv(v, z_t, nu, lt, ls, sto.coef_z, sto.coef_x, sto.coef_noise, learned_half_delta(lt, ls),
-                                                         step.is_last, self.rng.seed, offs[f], q0=q0, thr=thr, v_uncond=vu, cond_w=wg,
-                                                         want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext)
-                elif sto is not None:       # 'ancestral', 'sde_dpmpp_2m', 'ddim' with ddim_eta > 0: one launch, the noise drawn in it
-                    z_t, xp, ep = ops.stochastic_step(v, z_t, lt, ls, sto.coef_z, sto.coef_x, sto.coef_noise, sto.coef_prev, step.is_last,
-                                                      self.rng.seed, offs[f], q0=q0, x_hist=x_hist, thr=thr, v_uncond=vu, cond_w=wg,
-                                                      want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext)
-                elif dpm is not None:
-                    z_t, xp, ep = ops.dpm_solver_step(v, z_t, x_hist, lt, ls, dpm.coef_z, dpm.coef_x, dpm.coef_prev, step.is_last, v_uncond=vu, cond_w=wg,
-                                                      want_pred=record, mean_type=self.mean_type, dup=g_next, logsnr_next=lnext, thr=thr, ns=ns)
-                else:
-                    z_t, xp, ep = ops.sampler_step(v, z_t, lt, ls, step.is_last, v_uncond=vu, cond_w=wg, noise=noise, want_pred=record,
-                                                   mean_type=self.mean_type, dup=g_next, logsnr_next=lnext, thr=thr, ns=ns)
+                z_t, xp, ep = update(step, f, v, z_t, nu, noise, thr, ns, dict(v_uncond=vu, cond_w=wg, want_pred=record, mean_type=self.mean_type,
+                                                                               dup=g_next, logsnr_next=lnext))
                 if g_next:
                     z_t, z2 = z_t
                 if inp is not None:             # the known region, then (all passes but the step's last) the jump back to time t

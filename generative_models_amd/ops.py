@@ -1093,6 +1093,38 @@ def _sampler_io(v, z, same_shape, cond_w, want_pred, dup, logsnr_next):
     return B, n, z_next, z2, xp, ep
 
 
+def _sampler_ret(z_next, z2, xp, ep):
+    """What every update wrapper returns from `_sampler_io`'s outputs: (z_next, or (z_next, z2) with dup), x_pred, eps_pred."""
+    return (z_next if z2 is None else (z_next, z2)), xp, ep
+
+
+def _drawn_scalars(name, z, mean_type, scalars):
+    """The first checks of the updates that draw their noise in the kernel (`consistency_step`, `stochastic_step`, `stochastic_step_lv`), ahead
+    of each wrapper's own sign rules: mean_type, z's shape [B, ...], n % 4, the scalars (times and coefficients) finite.  -> scalars as floats"""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    shape = tuple(z.shape)
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f"z: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
+    if math.prod(shape[1:]) % 4:
+        raise ValueError(f"z: {math.prod(shape[1:])} values per image, a multiple of 4 is required")
+    scalars = tuple(float(s) for s in scalars)
+    if not all(math.isfinite(s) for s in scalars):
+        raise ValueError(f"{name}: non-finite time or coefficient {scalars}")
+    return scalars
+
+
+def _drawn_stream(name, seed, offset, q0, v_uncond, cond_w):
+    """Their checks after the sign rules, before any device tensor is asked for: the Philox stream, q0, v_uncond with cond_w.  -> (seed, offset, q0)"""
+    seed, offset = check_stream(seed, offset)
+    q0 = int(q0)
+    if not 0 <= q0 < 1 << 64:
+        raise ValueError(f"q0 = {q0}: an unsigned 64-bit Philox counter offset")
+    if (v_uncond is None) != (cond_w is None):
+        raise ValueError(f"{name}: v_uncond and cond_w go together")
+    return seed, offset, q0
+
+
 def _thr_check(thr, B):
     """`thr` of the *_dt entries: fp32 [B], the per-image threshold `dyn_threshold` returns."""
     _f32(thr, "thr")
@@ -1155,6 +1187,20 @@ def box_residual(v, z, obs, logsnr_t, cf, N, v_uncond=None, cond_w=None, mean_ty
     return r
 
 
+def _step_forms(name, plain, dt, with_ns, head, rest, z, B, thr, ns):
+    """One launch of an update that has a thresholded and a restoring form: the entry `plain`, with thr (fp32 [B], dynamic thresholding) `dt`,
+    with ns ((r, cf, N), restoration) `with_ns`, never both.  The extra pointer follows `head`, the box geometry `rest`."""
+    if ns is not None:
+        if thr is not None:
+            raise ValueError(f"{name}: ns (restoration) together with thr (dynamic thresholding) is not supported")
+        r, *geom = _ns_check(ns, z)
+        check(with_ns(*head, _p(r), *rest, *geom, _s()), name + "_ns")
+    elif thr is not None:
+        check(dt(*head, _p(_thr_check(thr, B)), *rest, _s()), name + "_dt")
+    else:
+        check(plain(*head, *rest, _s()), name)
+
+
 def sampler_step(v, z, logsnr_t, logsnr_s, is_last, v_uncond=None, cond_w=None, noise=None, want_pred=False, mean_type="v",
                  dup=False, logsnr_next=None, thr=None, ns=None):
     """dup: z_next is returned as the first half of a [2B, ...] tensor whose second half holds the same values (z2 = returned[1]);
@@ -1162,20 +1208,11 @@ def sampler_step(v, z, logsnr_t, logsnr_s, is_last, v_uncond=None, cond_w=None, 
     x-hat is the unclipped (guided) prediction clamped to +-thr[b] and divided by thr[b] (`dyn_threshold` gives thr).  ns: None, or
     (r, cf, N) - DDNM's null-space projection (gmk_sampler_step_ns): x-hat + A+ r with r = `box_residual`'s output; not together with thr."""
     B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((v_uncond, "v_uncond"), (noise, "noise")), cond_w, want_pred, dup, logsnr_next)
-    tail = (float(logsnr_t), float(logsnr_s), int(is_last), _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next),
-            MEAN_TYPES[mean_type], B, n)
-    if ns is not None:
-        if thr is not None:
-            raise ValueError("sampler_step: ns (restoration) together with thr (dynamic thresholding) is not supported")
-        r, *geom = _ns_check(ns, z)
-        check(lib.gmk_sampler_step_ns(_p(v), _p(v_uncond), _p(cond_w), _p(r), _p(z), _p(noise), *tail, *geom, _s()), "sampler_step_ns")
-        return ((z_next, z2) if dup else z_next), xp, ep
-    tail += (_s(),)
-    if thr is None:
-        check(lib.gmk_sampler_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(noise), *tail), "sampler_step")
-    else:
-        check(lib.gmk_sampler_step_dt(_p(v), _p(v_uncond), _p(cond_w), _p(_thr_check(thr, B)), _p(z), _p(noise), *tail), "sampler_step_dt")
-    return ((z_next, z2) if dup else z_next), xp, ep
+    rest = (_p(z), _p(noise), float(logsnr_t), float(logsnr_s), int(is_last), _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None,
+            _p(logsnr_next), MEAN_TYPES[mean_type], B, n)
+    _step_forms("sampler_step", lib.gmk_sampler_step, lib.gmk_sampler_step_dt, lib.gmk_sampler_step_ns, (_p(v), _p(v_uncond), _p(cond_w)), rest,
+                z, B, thr, ns)
+    return _sampler_ret(z_next, z2, xp, ep)
 
 
 def dpm_solver_step(v, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x, coef_prev, is_last, v_uncond=None, cond_w=None, want_pred=False,
@@ -1184,20 +1221,11 @@ def dpm_solver_step(v, z, x_hist, logsnr_t, logsnr_s, coef_z, coef_x, coef_prev,
     when coef_prev == 0).  Arguments and returns otherwise as `sampler_step` (no noise: the solver is deterministic); thr as there
     (gmk_dpm_solver_step_dt), ns as there (gmk_dpm_solver_step_ns)."""
     B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((x_hist, "x_hist"), (v_uncond, "v_uncond")), cond_w, want_pred, dup, logsnr_next)
-    tail = (_p(x_hist), float(logsnr_t), float(logsnr_s), float(coef_z), float(coef_x), float(coef_prev), int(is_last), _p(z_next), _p(xp),
+    rest = (_p(z), _p(x_hist), float(logsnr_t), float(logsnr_s), float(coef_z), float(coef_x), float(coef_prev), int(is_last), _p(z_next), _p(xp),
             _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next), MEAN_TYPES[mean_type], B, n)
-    if ns is not None:
-        if thr is not None:
-            raise ValueError("dpm_solver_step: ns (restoration) together with thr (dynamic thresholding) is not supported")
-        r, *geom = _ns_check(ns, z)
-        check(lib.gmk_dpm_solver_step_ns(_p(v), _p(v_uncond), _p(cond_w), _p(r), _p(z), *tail, *geom, _s()), "dpm_solver_step_ns")
-        return ((z_next, z2) if dup else z_next), xp, ep
-    tail += (_s(),)
-    if thr is None:
-        check(lib.gmk_dpm_solver_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), *tail), "dpm_solver_step")
-    else:
-        check(lib.gmk_dpm_solver_step_dt(_p(v), _p(v_uncond), _p(cond_w), _p(_thr_check(thr, B)), _p(z), *tail), "dpm_solver_step_dt")
-    return ((z_next, z2) if dup else z_next), xp, ep
+    _step_forms("dpm_solver_step", lib.gmk_dpm_solver_step, lib.gmk_dpm_solver_step_dt, lib.gmk_dpm_solver_step_ns,
+                (_p(v), _p(v_uncond), _p(cond_w)), rest, z, B, thr, ns)
+    return _sampler_ret(z_next, z2, xp, ep)
 
 
 DYN_THRESHOLD_KEYS = C["GMK_DYN_THRESHOLD_KEYS"]      # images of up to this many values are selected from LDS, larger ones re-read
@@ -1528,26 +1556,13 @@ def consistency_step(v, z, logsnr_t, logsnr_s, is_last, seed, offset, q0=0, v_un
     (guidance included), z_next = x-hat when is_last, else alpha_s x-hat + sigma_s eps with eps the Philox normals of
     gmk_rng_normal(seed, offset + q0), drawn in the kernel: q0 = a n / 4 places a chunk that starts at row a of a batch.  n % 4 == 0.
     Arguments and returns otherwise as `sampler_step`."""
-    if mean_type not in MEAN_TYPES:
-        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
-    shape = tuple(z.shape)
-    if len(shape) < 2 or 0 in shape:
-        raise ValueError(f"z: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
-    if math.prod(shape[1:]) % 4:
-        raise ValueError(f"z: {math.prod(shape[1:])} values per image, a multiple of 4 is required")
-    if not (math.isfinite(float(logsnr_t)) and math.isfinite(float(logsnr_s))):
-        raise ValueError(f"consistency_step: non-finite time ({logsnr_t}, {logsnr_s})")
-    seed, offset = check_stream(seed, offset)
-    q0 = int(q0)
-    if not 0 <= q0 < 1 << 64:
-        raise ValueError(f"q0 = {q0}: an unsigned 64-bit Philox counter offset")
-    if (v_uncond is None) != (cond_w is None):
-        raise ValueError("consistency_step: v_uncond and cond_w go together")
+    scalars = _drawn_scalars("consistency_step", z, mean_type, (logsnr_t, logsnr_s))
+    seed, offset, q0 = _drawn_stream("consistency_step", seed, offset, q0, v_uncond, cond_w)
     B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((v_uncond, "v_uncond"),), cond_w, want_pred, dup, logsnr_next)
-    check(lib.gmk_consistency_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), float(logsnr_t), float(logsnr_s), int(bool(is_last)), seed, offset, q0,
+    check(lib.gmk_consistency_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), *scalars, int(bool(is_last)), seed, offset, q0,
                                    _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None, _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()),
           "consistency_step")
-    return ((z_next, z2) if dup else z_next), xp, ep
+    return _sampler_ret(z_next, z2, xp, ep)
 
 
 def stochastic_step(v, z, logsnr_t, logsnr_s, coef_z, coef_x, coef_noise, coef_prev, is_last, seed, offset, q0=0, x_hist=None, thr=None,
@@ -1558,31 +1573,17 @@ def stochastic_step(v, z, logsnr_t, logsnr_s, coef_z, coef_x, coef_noise, coef_p
     coef_noise == 0): q0 = a n / 4 places a chunk that starts at row a of a batch.  The coefficients are a row of
     `gaussian_diffusion.stochastic_coefs` ('ancestral', 'ddim_eta', 'sde_dpmpp_2m').  x_hist: None, or fp32 [B, ...] - the previous x-hat,
     overwritten with this step's; required when coef_prev != 0.  n % 4 == 0.  Arguments and returns otherwise as `sampler_step`."""
-    if mean_type not in MEAN_TYPES:
-        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
-    shape = tuple(z.shape)
-    if len(shape) < 2 or 0 in shape:
-        raise ValueError(f"z: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
-    if math.prod(shape[1:]) % 4:
-        raise ValueError(f"z: {math.prod(shape[1:])} values per image, a multiple of 4 is required")
-    scalars = tuple(float(s) for s in (logsnr_t, logsnr_s, coef_z, coef_x, coef_noise, coef_prev))
-    if not all(math.isfinite(s) for s in scalars):
-        raise ValueError(f"stochastic_step: non-finite time or coefficient {scalars}")
+    scalars = _drawn_scalars("stochastic_step", z, mean_type, (logsnr_t, logsnr_s, coef_z, coef_x, coef_noise, coef_prev))
     if scalars[4] < 0.0:
         raise ValueError(f"coef_noise = {scalars[4]}: a standard deviation, need >= 0")
     if scalars[5] != 0.0 and x_hist is None:
         raise ValueError(f"coef_prev = {scalars[5]} without x_hist: the second-order step needs the previous x-hat")
-    seed, offset = check_stream(seed, offset)
-    q0 = int(q0)
-    if not 0 <= q0 < 1 << 64:
-        raise ValueError(f"q0 = {q0}: an unsigned 64-bit Philox counter offset")
-    if (v_uncond is None) != (cond_w is None):
-        raise ValueError("stochastic_step: v_uncond and cond_w go together")
+    seed, offset, q0 = _drawn_stream("stochastic_step", seed, offset, q0, v_uncond, cond_w)
     B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((x_hist, "x_hist"), (v_uncond, "v_uncond")), cond_w, want_pred, dup, logsnr_next)
     check(lib.gmk_stochastic_step(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(x_hist), None if thr is None else _p(_thr_check(thr, B)), *scalars,
                                   int(bool(is_last)), seed, offset, q0, _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None,
                                   _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()), "stochastic_step")
-    return ((z_next, z2) if dup else z_next), xp, ep
+    return _sampler_ret(z_next, z2, xp, ep)
 
 
 def stochastic_step_lv(v, z, nu, logsnr_t, logsnr_s, coef_z, coef_x, coef_noise_small, half_delta, is_last, seed, offset, q0=0, thr=None,
@@ -1592,33 +1593,19 @@ def stochastic_step_lv(v, z, nu, logsnr_t, logsnr_s, coef_z, coef_x, coef_noise_
     conditional half's under guidance); coef_noise_small: the 'small' row of `gaussian_diffusion.stochastic_row`; half_delta =
     (softplus(logsnr_s) - softplus(logsnr_t)) / 2 >= 0.  nu = -1 everywhere gives the bits of `stochastic_step` under 'small'.  Arguments and
     returns otherwise as `stochastic_step`."""
-    if mean_type not in MEAN_TYPES:
-        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
-    shape = tuple(z.shape)
-    if len(shape) < 2 or 0 in shape:
-        raise ValueError(f"z: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
-    if math.prod(shape[1:]) % 4:
-        raise ValueError(f"z: {math.prod(shape[1:])} values per image, a multiple of 4 is required")
-    scalars = tuple(float(s) for s in (logsnr_t, logsnr_s, coef_z, coef_x, coef_noise_small, half_delta))
-    if not all(math.isfinite(s) for s in scalars):
-        raise ValueError(f"stochastic_step_lv: non-finite time or coefficient {scalars}")
+    scalars = _drawn_scalars("stochastic_step_lv", z, mean_type, (logsnr_t, logsnr_s, coef_z, coef_x, coef_noise_small, half_delta))
     if scalars[4] < 0.0:
         raise ValueError(f"coef_noise_small = {scalars[4]}: a standard deviation, need >= 0")
     if scalars[5] < 0.0:
         raise ValueError(f"half_delta = {scalars[5]}: half of logvar_large - logvar_small, need >= 0")
-    seed, offset = check_stream(seed, offset)
-    q0 = int(q0)
-    if not 0 <= q0 < 1 << 64:
-        raise ValueError(f"q0 = {q0}: an unsigned 64-bit Philox counter offset")
-    if (v_uncond is None) != (cond_w is None):
-        raise ValueError("stochastic_step_lv: v_uncond and cond_w go together")
+    seed, offset, q0 = _drawn_stream("stochastic_step_lv", seed, offset, q0, v_uncond, cond_w)
     if nu is None:
         raise ValueError("stochastic_step_lv: nu is required (the network's variance output)")
     B, n, z_next, z2, xp, ep = _sampler_io(v, z, ((nu, "nu"), (v_uncond, "v_uncond")), cond_w, want_pred, dup, logsnr_next)
     check(lib.gmk_stochastic_step_lv(_p(v), _p(v_uncond), _p(cond_w), _p(z), _p(nu), None if thr is None else _p(_thr_check(thr, B)), *scalars,
                                      int(bool(is_last)), seed, offset, q0, _p(z_next), _p(xp), _p(ep), _p(z2[B:]) if dup else None,
                                      _p(logsnr_next), MEAN_TYPES[mean_type], B, n, _s()), "stochastic_step_lv")
-    return ((z_next, z2) if dup else z_next), xp, ep
+    return _sampler_ret(z_next, z2, xp, ep)
 
 
 def _adam_arenas(p, g, m, v, ema=None):
