@@ -127,6 +127,22 @@ __device__ __forceinline__ float x_from_out(float out, float zz, const LogsnrCoe
 }
 __device__ __forceinline__ float dx_dout(const LogsnrCoef& c, int mt) { return mt == GMK_MEAN_V ? -c.sigma : (mt == GMK_MEAN_EPS ? -c.d1 * c.d2 : 1.0f); }
 
+// The three loss kernels' element and their simple loss's gradient, once (tests hold the kernels to one another's bits).  clipped_pred: x-hat, the
+// clipped prediction (:58-63, :73), eps-hat from it (:76), and whether the raw prediction lay inside [-1, 1], ends included - where torch.clip
+// passes the gradient (a NaN is outside).  simple_loss_grad: torch.maximum routes the gradient to the larger branch, ties split evenly.
+struct ClippedPred { float raw, xh, eh;  __device__ __forceinline__ bool inside() const { return raw >= -1.0f && raw <= 1.0f; } };
+__device__ __forceinline__ ClippedPred clipped_pred(float out, float zz, const LogsnrCoef& c, int mt) {
+    const float raw = x_from_out(out, zz, c, mt);
+    const float xh = clip1(raw);
+    return {raw, xh, c.c1 * (zz - xh * c.c2)};
+}
+struct SimpleLossGrad { float kx, ke; };      // d loss / d x-hat = kx (x-hat - x) + ke (eps-hat - eps)
+__device__ __forceinline__ SimpleLossGrad simple_loss_grad(float xm, float em, int loss_type, float grad_scale, int64_t n, const LogsnrCoef& c) {
+    const float gx = loss_type == 1 ? 0.f : (xm > em ? 1.f : (xm == em ? 0.5f : 0.f));
+    const float ge = 1.f - gx;
+    return {grad_scale * gx * 2.f / (float)n, grad_scale * ge * 2.f / (float)n * (-c.c1 * c.c2)};
+}
+
 // one block per sample: loss and (optionally) d loss / d (network output)
 __global__ __launch_bounds__(256) void v_loss_kernel(const float* __restrict__ v, const float* __restrict__ z,
                                                     const float* __restrict__ x, const float* __restrict__ eps,
@@ -140,9 +156,8 @@ __global__ __launch_bounds__(256) void v_loss_kernel(const float* __restrict__ v
     float sx = 0.f, se = 0.f;
     for (int64_t i = threadIdx.x; i < n; i += 256) {
         const float zz = z[base + i];
-        const float xh = clip1(x_from_out(v[base + i], zz, c, mt));        // :58-63, :73
-        const float eh = c.c1 * (zz - xh * c.c2);                          // :76
-        const float dx = xh - x[base + i], de = eh - eps[base + i];
+        const ClippedPred p = clipped_pred(v[base + i], zz, c, mt);
+        const float dx = p.xh - x[base + i], de = p.eh - eps[base + i];
         sx = fmaf(dx, dx, sx);
         se = fmaf(de, de, se);
     }
@@ -155,17 +170,13 @@ __global__ __launch_bounds__(256) void v_loss_kernel(const float* __restrict__ v
         if (eps_mse_o) eps_mse_o[b] = em;
     }
     if (!dv) return;
-    // torch.maximum routes the gradient to the larger branch, ties split evenly; torch.clip passes it inside [-1, 1]
-    const float gx = loss_type == 1 ? 0.f : (xm > em ? 1.f : (xm == em ? 0.5f : 0.f));
-    const float ge = 1.f - gx;
-    const float kx = grad_scale * gx * 2.f / (float)n;
-    const float ke = grad_scale * ge * 2.f / (float)n * (-c.c1 * c.c2);
+    const SimpleLossGrad sg = simple_loss_grad(xm, em, loss_type, grad_scale, n, c);
     for (int64_t i = threadIdx.x; i < n; i += 256) {
         const float zz = z[base + i];
-        const float raw = x_from_out(v[base + i], zz, c, mt);
+        const float raw = x_from_out(v[base + i], zz, c, mt);      // clipped_pred's lines (the first pass calls it: keep in step), spelled out: through the call this loop takes one more VGPR
         const float xh = clip1(raw);
         const float eh = c.c1 * (zz - xh * c.c2);
-        const float dxh = kx * (xh - x[base + i]) + ke * (eh - eps[base + i]);
+        const float dxh = sg.kx * (xh - x[base + i]) + sg.ke * (eh - eps[base + i]);
         dv[base + i] = (raw >= -1.0f && raw <= 1.0f) ? dx_dout(c, mt) * dxh : 0.f;
     }
 }
@@ -217,9 +228,9 @@ __global__ __launch_bounds__(256) void x_loss_w_kernel(const float* __restrict__
             }
 #pragma unroll
             for (int k = 0; k < STEP; ++k) {
-                const float raw = x_from_out(vv[k], zv[k], c, mt);
-                d[k] = clip1(raw) - xv[k];
-                if (keep && !(raw >= -1.0f && raw <= 1.0f)) clipped |= (uint64_t)1 << (bit + k);
+                const ClippedPred p = clipped_pred(vv[k], zv[k], c, mt);
+                d[k] = p.xh - xv[k];
+                if (keep && !p.inside()) clipped |= (uint64_t)1 << (bit + k);
             }
             if constexpr (VEC) store4(res + i, d); else res[i] = d[0];
         }
@@ -266,8 +277,8 @@ __global__ __launch_bounds__(256) void x_loss_w_kernel(const float* __restrict__
         }
 #pragma unroll
         for (int k = 0; k < STEP; ++k) {
-            const float raw = x_from_out(vv[k], zv[k], c, mt);
-            d[k] = (raw >= -1.0f && raw <= 1.0f) ? dxo * (kx * (clip1(raw) - xv[k])) : 0.f;
+            const ClippedPred p = clipped_pred(vv[k], zv[k], c, mt);
+            d[k] = p.inside() ? dxo * (kx * (p.xh - xv[k])) : 0.f;
         }
         if constexpr (VEC) store4(dv + base + i, d); else dv[base + i] = d[0];
     }
@@ -326,12 +337,10 @@ __global__ __launch_bounds__(256) void hybrid_loss_kernel(const float* __restric
             }
 #pragma unroll
             for (int k = 0; k < STEP; ++k) {
-                const float raw = x_from_out(vv[k], zv[k], c, mt);
-                const float xh = clip1(raw);
-                const float eh = c.c1 * (zv[k] - xh * c.c2);
-                dx[k] = xh - xv[k];
-                de[k] = eh - ev[k];
-                if (keep && !(raw >= -1.0f && raw <= 1.0f)) clipped |= (uint64_t)1 << (bit + k);
+                const ClippedPred p = clipped_pred(vv[k], zv[k], c, mt);
+                dx[k] = p.xh - xv[k];
+                de[k] = p.eh - ev[k];
+                if (keep && !p.inside()) clipped |= (uint64_t)1 << (bit + k);
                 const float f = 0.5f * (nv[k] + 1.0f);
                 const float a = f * delta;
                 const float ema = expf(-a);
@@ -370,10 +379,7 @@ __global__ __launch_bounds__(256) void hybrid_loss_kernel(const float* __restric
     }
     if (!dv) return;
     // v_loss_kernel's gradient of the simple loss: the bound's mean is a constant, so dv has no other term
-    const float gx = loss_type == 1 ? 0.f : (xm > em ? 1.f : (xm == em ? 0.5f : 0.f));
-    const float ge = 1.f - gx;
-    const float kx = grad_scale * gx * 2.f / (float)n;
-    const float ke = grad_scale * ge * 2.f / (float)n * (-c.c1 * c.c2);
+    const SimpleLossGrad sg = simple_loss_grad(xm, em, loss_type, grad_scale, n, c);
     if (keep) {
         int bit = 0;
         for (int i = tid * STEP; i < (int)n; i += 256 * STEP, bit += STEP) {
@@ -381,7 +387,7 @@ __global__ __launch_bounds__(256) void hybrid_loss_kernel(const float* __restric
             if constexpr (VEC) { load4(resx + i, dx); load4(rese + i, de); } else { dx[0] = resx[i]; de[0] = rese[i]; }
 #pragma unroll
             for (int k = 0; k < STEP; ++k) {
-                const float dxh = kx * dx[k] + ke * de[k];
+                const float dxh = sg.kx * dx[k] + sg.ke * de[k];
                 o[k] = ((clipped >> (bit + k)) & 1) ? 0.f : dx_dout(c, mt) * dxh;
             }
             if constexpr (VEC) store4(dv + base + i, o); else dv[base + i] = o[0];
@@ -397,11 +403,9 @@ __global__ __launch_bounds__(256) void hybrid_loss_kernel(const float* __restric
         }
 #pragma unroll
         for (int k = 0; k < STEP; ++k) {
-            const float raw = x_from_out(vv[k], zv[k], c, mt);
-            const float xh = clip1(raw);
-            const float eh = c.c1 * (zv[k] - xh * c.c2);
-            const float dxh = kx * (xh - xv[k]) + ke * (eh - ev[k]);
-            o[k] = (raw >= -1.0f && raw <= 1.0f) ? dx_dout(c, mt) * dxh : 0.f;
+            const ClippedPred p = clipped_pred(vv[k], zv[k], c, mt);
+            const float dxh = sg.kx * (p.xh - xv[k]) + sg.ke * (p.eh - ev[k]);
+            o[k] = p.inside() ? dx_dout(c, mt) * dxh : 0.f;
         }
         if constexpr (VEC) store4(dv + base + i, o); else dv[base + i] = o[0];
     }
@@ -1731,6 +1735,19 @@ int stream_grid(int64_t work_items) {
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
+// 16-byte accesses need every row to start on a 16-byte boundary: n a multiple of 4 and aligned tensors (a null pointer is not accessed)
+template <typename... T> static bool rows_aligned16(int64_t n, const T*... ptrs) {
+    return n % 4 == 0 && ((reinterpret_cast<uintptr_t>(ptrs) | ...) & 15) == 0;
+}
+
+// the dynamic LDS of a loss kernel that keeps `arrays` kinds of residual: each min(n, kXLossKeep) floats rounded up to 4, then block_sum's four partials
+struct LossLds { int floats; size_t bytes; };
+static LossLds loss_lds(int64_t n, int arrays) {
+    const int64_t m = n < kXLossKeep ? n : kXLossKeep;
+    const int floats = (int)((m + 3) / 4 * 4);
+    return {floats, (size_t)(arrays * floats + 4) * sizeof(float)};
+}
+
 // a[i] += b[i] over n elements, n % 8 == 0, 16-byte (bf16) / 32-byte (fp32) accesses: the sum of the two heads' data gradients (gmk_add_into)
 template <typename T>
 __global__ __launch_bounds__(256) void add_into_kernel(T* __restrict__ a, const T* __restrict__ b, int64_t n) {
@@ -1814,14 +1831,9 @@ extern "C" int gmk_x_loss_w(const float* v, const float* z, const float* x, cons
                 "gmk_x_loss_w: weight_type must be 0 (snr_plus1) or 1 (min_snr)");
     GMK_REQUIRE(isfinite(gamma) && gamma > 0.0f, "gmk_x_loss_w: gamma = %g, need a finite value > 0", (double)gamma);
     GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_x_loss_w");
-    const int64_t m = n < kXLossKeep ? n : kXLossKeep;
-    const int lds_floats = (int)((m + 3) / 4 * 4);
-    const size_t lds = (size_t)(lds_floats + 4) * sizeof(float);
-    // 16-byte accesses need every row to start on a 16-byte boundary: n a multiple of 4 and aligned tensors
-    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(x) |
-                                     reinterpret_cast<uintptr_t>(dv)) & 15) == 0;
-    if (vec) x_loss_w_kernel<true><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, weight_type, gamma, n, mean_type, lds_floats);
-    else x_loss_w_kernel<false><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, weight_type, gamma, n, mean_type, lds_floats);
+    const LossLds lds = loss_lds(n, 1);
+    if (rows_aligned16(n, v, z, x, dv)) x_loss_w_kernel<true><<<B, 256, lds.bytes, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, weight_type, gamma, n, mean_type, lds.floats);
+    else x_loss_w_kernel<false><<<B, 256, lds.bytes, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, weight_type, gamma, n, mean_type, lds.floats);
     return gmk_check_launch("gmk_x_loss_w");
 }
 
@@ -1831,13 +1843,9 @@ extern "C" int gmk_x_loss_huber(const float* v, const float* z, const float* x, 
     GMK_REQUIRE(B > 0 && n > 0, "gmk_x_loss_huber: bad shape B=%d n=%lld", B, (long long)n);
     GMK_REQUIRE(isfinite(c) && c > 0.0f, "gmk_x_loss_huber: c = %g, need a finite value > 0", (double)c);
     GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_x_loss_huber");
-    const int64_t m = n < kXLossKeep ? n : kXLossKeep;
-    const int lds_floats = (int)((m + 3) / 4 * 4);
-    const size_t lds = (size_t)(lds_floats + 4) * sizeof(float);
-    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(x) |
-                                     reinterpret_cast<uintptr_t>(dv)) & 15) == 0;       // gmk_x_loss_w's rule
-    if (vec) x_loss_w_kernel<true, true><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, 0, c, n, mean_type, lds_floats);
-    else x_loss_w_kernel<false, true><<<B, 256, lds, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, 0, c, n, mean_type, lds_floats);
+    const LossLds lds = loss_lds(n, 1);
+    if (rows_aligned16(n, v, z, x, dv)) x_loss_w_kernel<true, true><<<B, 256, lds.bytes, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, 0, c, n, mean_type, lds.floats);
+    else x_loss_w_kernel<false, true><<<B, 256, lds.bytes, gmk_stream(stream)>>>(v, z, x, logsnr, loss_b, x_mse, dv, grad_scale, 0, c, n, mean_type, lds.floats);
     return gmk_check_launch("gmk_x_loss_huber");
 }
 
@@ -1850,10 +1858,8 @@ extern "C" int gmk_hybrid_loss(const float* v, const float* nu, const float* z, 
     GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_hybrid_loss");
     GMK_REQUIRE(isfinite(lambda) && lambda >= 0.0f, "gmk_hybrid_loss: lambda = %g, need a finite value >= 0", (double)lambda);
     GMK_REQUIRE(!dv == !dnu, "gmk_hybrid_loss: dv and dnu go together");
-    const int64_t m = n < kXLossKeep ? n : kXLossKeep;
-    const int lds_floats = (int)((m + 3) / 4 * 4);
-    const size_t lds = (size_t)(2 * lds_floats + 4) * sizeof(float);
-    if (lds > 64 * 1024) {      // above what a launch gets unasked: raise the kernels' limit (96 KiB + 16) once on every device that launches them
+    const LossLds lds = loss_lds(n, 2);
+    if (lds.bytes > 64 * 1024) {      // above what a launch gets unasked: raise the kernels' limit (96 KiB + 16) once on every device that launches them
         constexpr int kLdsMax = (2 * kXLossKeep + 4) * (int)sizeof(float);
         constexpr int kMaxDevices = 64;
         static bool raised[kMaxDevices] = {};
@@ -1867,12 +1873,8 @@ extern "C" int gmk_hybrid_loss(const float* v, const float* nu, const float* z, 
             raised[device] = true;
         }
     }
-    // 16-byte accesses need every row to start on a 16-byte boundary: n a multiple of 4 and aligned tensors (gmk_x_loss_w's rule)
-    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(nu) | reinterpret_cast<uintptr_t>(z) |
-                                     reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(dv) |
-                                     reinterpret_cast<uintptr_t>(dnu)) & 15) == 0;
-    if (vec) hybrid_loss_kernel<true><<<B, 256, lds, gmk_stream(stream)>>>(v, nu, z, x, eps, logsnr, logsnr_s, loss_b, vlb_b, frac_b, x_mse, eps_mse, dv, dnu, grad_scale, lambda, n, loss_type, mean_type, lds_floats);
-    else hybrid_loss_kernel<false><<<B, 256, lds, gmk_stream(stream)>>>(v, nu, z, x, eps, logsnr, logsnr_s, loss_b, vlb_b, frac_b, x_mse, eps_mse, dv, dnu, grad_scale, lambda, n, loss_type, mean_type, lds_floats);
+    if (rows_aligned16(n, v, nu, z, x, eps, dv, dnu)) hybrid_loss_kernel<true><<<B, 256, lds.bytes, gmk_stream(stream)>>>(v, nu, z, x, eps, logsnr, logsnr_s, loss_b, vlb_b, frac_b, x_mse, eps_mse, dv, dnu, grad_scale, lambda, n, loss_type, mean_type, lds.floats);
+    else hybrid_loss_kernel<false><<<B, 256, lds.bytes, gmk_stream(stream)>>>(v, nu, z, x, eps, logsnr, logsnr_s, loss_b, vlb_b, frac_b, x_mse, eps_mse, dv, dnu, grad_scale, lambda, n, loss_type, mean_type, lds.floats);
     return gmk_check_launch("gmk_hybrid_loss");
 }
 
@@ -2294,9 +2296,7 @@ extern "C" int gmk_consistency_target(const float* v_tgt, const float* z_s, cons
                 "gmk_consistency_target: null pointer");
     GMK_REQUIRE(B > 0 && B < 65536 && n > 0, "gmk_consistency_target: bad shape B=%d n=%lld", B, (long long)n);
     GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_consistency_target");
-    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(v_tgt) | reinterpret_cast<uintptr_t>(z_s) | reinterpret_cast<uintptr_t>(x_pred_teacher) |
-                                     reinterpret_cast<uintptr_t>(z_t) | reinterpret_cast<uintptr_t>(x_target) | reinterpret_cast<uintptr_t>(eps_target)) & 15) == 0;
-    if (vec) consistency_target_kernel<true><<<dim3(row_grid(n, 1024), B), 256, 0, gmk_stream(stream)>>>(v_tgt, z_s, x_pred_teacher, z_t, logsnr_t, logsnr_s, i_times, x_target, eps_target, n, mean_type);
+    if (rows_aligned16(n, v_tgt, z_s, x_pred_teacher, z_t, x_target, eps_target)) consistency_target_kernel<true><<<dim3(row_grid(n, 1024), B), 256, 0, gmk_stream(stream)>>>(v_tgt, z_s, x_pred_teacher, z_t, logsnr_t, logsnr_s, i_times, x_target, eps_target, n, mean_type);
     else consistency_target_kernel<false><<<dim3(row_grid(n, 256), B), 256, 0, gmk_stream(stream)>>>(v_tgt, z_s, x_pred_teacher, z_t, logsnr_t, logsnr_s, i_times, x_target, eps_target, n, mean_type);
     return gmk_check_launch("gmk_consistency_target");
 }
@@ -2453,8 +2453,7 @@ extern "C" int gmk_cfg_rescale(const float* v, const float* v_uncond, const floa
     GMK_REQUIRE(mean_type >= GMK_MEAN_V && mean_type <= GMK_MEAN_X, "gmk_cfg_rescale: mean_type must be 0 (v), 1 (eps) or 2 (x)");
     GMK_REQUIRE(B >= 1 && n >= 1, "gmk_cfg_rescale: bad shape B=%d n=%lld (B, n >= 1 required)", B, (long long)n);
     GMK_REQUIRE(isfinite(logsnr_t), "gmk_cfg_rescale: non-finite time");
-    const bool vec = n % 4 == 0 &&
-        ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(v_uncond) | reinterpret_cast<uintptr_t>(z)) & 15) == 0;
+    const bool vec = rows_aligned16(n, v, v_uncond, z);
     const bool keep = n <= kRescaleKeep;
     hipStream_t st = gmk_stream(stream);
     if (vec && keep) cfg_rescale_kernel<true, true><<<B, 256, 0, st>>>(v, v_uncond, cond_w, z, logsnr_t, phi, thr_out, ratio_out, n, mean_type);

@@ -453,9 +453,7 @@ def make_plugin(GMBase, AttrDict):
 
         def _train_step_graphed(self, x, y):
             B, dev = x.shape[0], x.device
-            rng = self.diffusion.rng
-            eps = rng.normal(x.shape, dev)                      # the draw order of GaussianDiffusion._prepare: eps, then u
-            u = self.diffusion.draw_u(B, dev)                   # outside the capture, like every draw ('stratified': one draw + gmk_u_stratified)
+            u, eps = self.diffusion.draw_eps_u(x)               # outside the capture, like every draw ('stratified': one draw + gmk_u_stratified)
             key = (tuple(x.shape), y.dtype)
             graphs = self.__dict__.setdefault("_train_graphs", {})
             ent = graphs.get(key)

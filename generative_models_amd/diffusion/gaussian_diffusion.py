@@ -259,6 +259,32 @@ def sampler_caps(sampler, ddim_eta=0.0):
     return DDIM_ETA_CAPS if sampler == "ddim" and float(ddim_eta) > 0.0 else SAMPLER_CAPS.get(sampler)
 
 
+# What both training passes and the autograd bridge know about an objective, one row per objective a step can apply (`loss_weight_type`, or
+# 'hybrid' under learn_var).  op: the `ops` wrapper, called as op(v, [nu,] z, x, [eps,] logsnr, [logsnr_s,] grad_scale=, mean_type=, **scalars);
+# eps: it reads the target noise; nu: it reads the network's variance output (the forward's want_nu, backward_hip's dnu) and logsnr_s =
+# `_logsnr_prev(u)`; scalars: (wrapper keyword, attribute of the GaussianDiffusion) pairs, None for `_prepare`'s loss_type; outs: the wrapper's
+# return tuple by name; grads: the names among `outs` that are gradients (None without grad_scale).  A new objective is a row here.
+LossRow = namedtuple("LossRow", "op eps nu scalars outs grads")
+_V_ROW = LossRow("v_loss", True, False, (("loss_type", None),), ("loss", "x_mse", "eps_mse", "dv"), ("dv",))
+_XW_ROW = LossRow("x_loss_w", False, False, (("weight", "loss_weight_type"), ("gamma", "loss_gamma")), ("loss", "x_mse", "dv"), ("dv",))
+LOSS_TABLE = {
+    "snr_trunc": _V_ROW,
+    "snr":       _V_ROW,
+    "snr_plus1": _XW_ROW,
+    "min_snr":   _XW_ROW,
+    "huber":     LossRow("x_loss_huber", False, False, (("c", "consistency_huber_c"),), ("loss", "x_mse", "dv"), ("dv",)),
+    "hybrid":    LossRow("hybrid_loss", True, True, (("vlb_lambda", "vlb_lambda"), ("loss_type", None)),
+                         ("loss", "vlb", "var_frac", "x_mse", "eps_mse", "dv", "dnu"), ("dv", "dnu")),
+}
+TRAIN_KEYS = ("loss", "x_mse", "eps_mse", "logsnr", "vlb", "var_frac")      # what `train_forward_backward` reports of a row's outputs, in this order
+
+
+def loss_row(diffusion):
+    """The `LOSS_TABLE` row of a `GaussianDiffusion`: 'hybrid' under learn_var (which `learned_var_check` allows over 'snr_trunc' / 'snr'
+    only), else the row of its `loss_weight_type`."""
+    return LOSS_TABLE["hybrid" if diffusion.learn_var else diffusion.loss_weight_type]
+
+
 # how a caller names the features in `sampler_compat_check`'s messages: a method of `GaussianDiffusion`, or the model's flags
 FEATURE_WORDS = {"inpaint": "inpainting", "restore": "restoration", "dyn_threshold": "dyn_threshold", "cfg_rescale": "cfg_rescale"}
 FLAG_WORDS = {**FEATURE_WORDS, "inpaint": "inpaint_eval", "restore": "restore_eval / restore_gray"}
@@ -863,77 +889,26 @@ def resolve_guidance(*, sample_cond_w, net_cond_w, kw_cond_w, has_teacher, sampl
     return student_w, guidance_w, False
 
 
-class _VLoss(torch.autograd.Function):
-    """loss_b = max(mse_x, mse_eps) of the clipped v-parameterised prediction, differentiable w.r.t. v."""
+class _LossBridge(torch.autograd.Function):
+    """A `LOSS_TABLE` row's wrapper under torch.autograd: -> the row's per-image outputs without its gradients, `loss` first and differentiable
+    w.r.t. v (and nu where the row has dnu), the others reported numbers only.  tensors: the wrapper's tensor arguments, v (then nu) leading."""
 
     @staticmethod
-    def forward(ctx, v, z, x, eps, logsnr, loss_type=0, mean_type="v"):
-        loss_b, _, _, dv = ops.v_loss(v.contiguous(), z, x, eps, logsnr, grad_scale=1.0, loss_type=loss_type, mean_type=mean_type)
-        ctx.save_for_backward(dv)
-        return loss_b
+    def forward(ctx, row, kw, *tensors):
+        lead = len(row.grads)               # the differentiable inputs: one per gradient
+        vals = getattr(ops, row.op)(*(t.contiguous() for t in tensors[:lead]), *tensors[lead:], grad_scale=1.0, **kw)
+        outs = dict(zip(row.outs, vals))
+        ctx.save_for_backward(*(outs.pop(name) for name in row.grads))
+        ctx.constants = len(tensors) - lead
+        loss, *reported = outs.values()
+        ctx.mark_non_differentiable(*reported)
+        return (loss, *reported)
 
     @staticmethod
-    def backward(ctx, g):
-        (dv,) = ctx.saved_tensors
-        B = dv.shape[0]
-        out = ops.scale_rows(dv.view(B, -1), g.contiguous().float()).view_as(dv)
-        return out, None, None, None, None, None, None
-
-
-class _HybridLoss(torch.autograd.Function):
-    """(loss_b, vlb_b, frac_b, x_mse) of `ops.hybrid_loss`, loss_b = simple + vlb_lambda vlb differentiable w.r.t. v (the simple loss alone:
-    the bound's mean is a constant) and nu; the other three are reported numbers only."""
-
-    @staticmethod
-    def forward(ctx, v, nu, z, x, eps, logsnr, logsnr_s, vlb_lambda, loss_type=0, mean_type="v"):
-        loss_b, vlb, frac, x_mse, _, dv, dnu = ops.hybrid_loss(v.contiguous(), nu.contiguous(), z, x, eps, logsnr, logsnr_s, vlb_lambda,
-                                                               grad_scale=1.0, loss_type=loss_type, mean_type=mean_type)
-        ctx.save_for_backward(dv, dnu)
-        ctx.mark_non_differentiable(vlb, frac, x_mse)
-        return loss_b, vlb, frac, x_mse
-
-    @staticmethod
-    def backward(ctx, g, _g_vlb, _g_frac, _g_x_mse):
-        dv, dnu = ctx.saved_tensors
-        B = dv.shape[0]
+    def backward(ctx, g, *_):
         g = g.contiguous().float()
-        return (ops.scale_rows(dv.view(B, -1), g).view_as(dv), ops.scale_rows(dnu.view(B, -1), g).view_as(dnu)) + (None,) * 8
-
-
-class _XLossW(torch.autograd.Function):
-    """(loss_b, x_mse) of `ops.x_loss_w`, loss_b = w(logsnr) x_mse differentiable w.r.t. v; x_mse is a reported number only."""
-
-    @staticmethod
-    def forward(ctx, v, z, x, logsnr, weight, gamma, mean_type="v"):
-        loss_b, x_mse, dv = ops.x_loss_w(v.contiguous(), z, x, logsnr, weight, gamma, grad_scale=1.0, mean_type=mean_type)
-        ctx.save_for_backward(dv)
-        ctx.mark_non_differentiable(x_mse)
-        return loss_b, x_mse
-
-    @staticmethod
-    def backward(ctx, g, _g_x_mse):
-        (dv,) = ctx.saved_tensors
-        B = dv.shape[0]
-        out = ops.scale_rows(dv.view(B, -1), g.contiguous().float()).view_as(dv)
-        return out, None, None, None, None, None, None
-
-
-class _XLossHuber(torch.autograd.Function):
-    """(loss_b, x_mse) of `ops.x_loss_huber`, loss_b = sqrt(x_mse + c^2) - c differentiable w.r.t. v; x_mse is a reported number only."""
-
-    @staticmethod
-    def forward(ctx, v, z, x, logsnr, c, mean_type="v"):
-        loss_b, x_mse, dv = ops.x_loss_huber(v.contiguous(), z, x, logsnr, c, grad_scale=1.0, mean_type=mean_type)
-        ctx.save_for_backward(dv)
-        ctx.mark_non_differentiable(x_mse)
-        return loss_b, x_mse
-
-    @staticmethod
-    def backward(ctx, g, _g_x_mse):
-        (dv,) = ctx.saved_tensors
-        B = dv.shape[0]
-        out = ops.scale_rows(dv.view(B, -1), g.contiguous().float()).view_as(dv)
-        return out, None, None, None, None, None
+        grads = tuple(ops.scale_rows(d.view(d.shape[0], -1), g).view_as(d) for d in ctx.saved_tensors)
+        return (None, None) + grads + (None,) * ctx.constants
 
 
 class GaussianDiffusion:
@@ -1083,10 +1058,22 @@ class GaussianDiffusion:
 
     def draw_u(self, B, dev):
         """The continuous times of one batch from self.rng, fp32 [B] in [0, 1): 'uniform' B independent draws (:94); 'stratified' ONE draw
-        (one Philox counter) expanded to u0 + b / B mod 1 by gmk_u_stratified.  `_prepare` and the graphed train step both draw here."""
+        (one Philox counter) expanded to u0 + b / B mod 1 by gmk_u_stratified.  Every pass draws its times through `draw_eps_u`."""
         if self.time_sampler == "stratified":
             return ops.u_stratified(self.rng.uniform((1,), dev), B)
         return self.rng.uniform((B,), dev)
+
+    def draw_eps_u(self, x, u=None, eps=None, want_u=True):
+        """The first two draws of a step from self.rng, in the one order every pass and a resumed run share: eps where the caller gave none,
+        then (want_u) u where the caller gave none, as aligned fp32.  `_prepare` draws here, and so does a pass that needs u before `_prepare`
+        (the bound's time pair, the loss profile, the graphed step's static inputs) - `_prepare` then finds both given.  -> (u, eps)"""
+        if eps is None:
+            eps = self.rng.normal(x.shape, x.device)
+        if want_u:
+            if u is None:
+                u = self.draw_u(x.shape[0], x.device)
+            u = ops.aligned(u.float())
+        return u, eps
 
     # ---- the loss profile and the loss-aware time sampler (extensions, no reference call site) --------------------------------------------
     def profile_state(self, split, dev):
@@ -1121,20 +1108,16 @@ class GaussianDiffusion:
         x = ops.aligned(x.float())
         B, dev = x.shape[0], x.device
         distill = self.teacher_net is not None
-        if eps is None:
-            eps = self.rng.normal(x.shape, dev)                                   # :83
+        discrete = distill and self.teacher_mode in ("step2", "consistency")      # :87-91 discrete time
+        u, eps = self.draw_eps_u(x, u, eps, want_u=not discrete)                  # :83, :94 continuous time
         eps = ops.aligned(eps.float())
         # the discretisation of the discrete-time modes: `timesteps`, or consistency distillation's own grid
         T = self.train_grid if self.consistency else self.num_steps
-        if distill and self.teacher_mode in ("step2", "consistency"):             # :87-91 discrete time
+        if discrete:
             if i_times is None:
                 i_times = (self.rng.uniform((B,), dev) * T).long().clamp_(max=T - 1)
             i_times = ops.aligned(i_times.long())
             _, u = ops.logsnr_schedule(B, dev, i_times=i_times, num_steps=T, want_u=True, schedule=self.schedule)
-        else:
-            if u is None:
-                u = self.draw_u(B, dev)                                           # :94 continuous time
-            u = ops.aligned(u.float())
         logsnr, z_t = ops.q_sample(x, eps, u, self.schedule)                      # :95-100
         if not distill:
             return module, guide, None, z_t, logsnr, x, eps, 1 if self.loss_weight_type == "snr" else 0
@@ -1169,58 +1152,45 @@ class GaussianDiffusion:
         u_s = ops.aligned((u - 1.0 / self.vlb_steps).clamp_(min=0.0))
         return ops.logsnr_schedule(u.numel(), u.device, u=u_s, schedule=self.schedule)
 
+    def _loss_row(self, module):
+        """`loss_row(self)`, refused before the forward when the row needs a variance output that `module` does not have."""
+        row = loss_row(self)
+        if row.nu and not getattr(module, "learn_var", False):
+            raise ValueError("learn_var = 1 with a network that has no variance head (SimpleUnet(learn_var=True))")
+        return row
+
+    def _loss(self, row, v, nu, z_t, x_t, eps_t, logsnr, u, loss_type, grad_scale):
+        """The objective of `row` on the network's output, for both passes: grad_scale None is `training_losses` (through `_LossBridge` when
+        autograd follows v), a number `train_forward_backward`'s.  -> the wrapper's outputs by the row's names"""
+        tensors = (v,) + ((nu,) if row.nu else ()) + (z_t, x_t) + ((eps_t,) if row.eps else ()) + (logsnr,) + ((self._logsnr_prev(u),) if row.nu else ())
+        kw = {name: loss_type if attr is None else getattr(self, attr) for name, attr in row.scalars}
+        kw["mean_type"] = self.mean_type
+        if grad_scale is None and torch.is_grad_enabled() and v.requires_grad:
+            vals = _LossBridge.apply(row, kw, *tensors)
+            return dict(zip((name for name in row.outs if name not in row.grads), vals))
+        return dict(zip(row.outs, getattr(ops, row.op)(*tensors, grad_scale=grad_scale, **kw)))
+
     def training_losses(self, *, net, x, u=None, eps=None, i_times=None, cond_w=None):
         """Reference call shape (:81).  Differentiable through torch.autograd when grad mode is on.  learn_var: the hybrid loss, with `vlb`
         (the bound term, nats per dimension) and `var_frac` (the mean interpolation weight) beside it."""
         assert x.dtype in [torch.float32, torch.float64]
-        if self.loss_profile or self.learn_var:                                     # the same draws in the same order (`_prepare`: eps, then u), made here to keep u
-            if eps is None:
-                eps = self.rng.normal(x.shape, x.device)
-            if u is None:
-                u = self.draw_u(x.shape[0], x.device)
-            u = ops.aligned(u.float())
+        if self.loss_profile or self.learn_var:                   # both need u after `_prepare`, which does not return it
+            u, eps = self.draw_eps_u(x, u, eps)
         module, guide, w, z_t, logsnr, x_t, eps_t, loss_type = self._prepare(net, x, u, eps, i_times, cond_w)
-        if self.learn_var:                                        # the hybrid loss on the network's (v, nu) pair
-            if not getattr(module, "learn_var", False):
-                raise ValueError("learn_var = 1 with a network that has no variance head (SimpleUnet(learn_var=True))")
-            v, nu = module(z_t, logsnr, guide=guide, cond_w=w, want_nu=True)
-            args = (v, nu, z_t, x_t, eps_t, logsnr, self._logsnr_prev(u), self.vlb_lambda)
-            if torch.is_grad_enabled() and v.requires_grad:
-                loss, vlb, frac, x_mse = _HybridLoss.apply(*args, loss_type, self.mean_type)
-            else:
-                loss, vlb, frac, x_mse = ops.hybrid_loss(*args, loss_type=loss_type, mean_type=self.mean_type)[:4]
-            if self.loss_profile:
-                ops.loss_profile(u, loss.detach(), x_mse, self.profile_state("test", u.device), 1.0)
-            return {"loss": loss, "vlb": vlb, "var_frac": frac}
-        v = module(z_t, logsnr, guide=guide, cond_w=w)
-        grad = torch.is_grad_enabled() and v.requires_grad
-
-        def note(loss, x_mse):
-            """loss_profile: the batch into the test profile at decay 1 (plain sums; x_mse where the branch has it)."""
-            if self.loss_profile:
-                ops.loss_profile(u, loss.detach(), x_mse, self.profile_state("test", u.device), 1.0)
-        if self.loss_weight_type == "huber":                      # consistency distillation's pseudo-Huber loss on x
-            if grad:
-                loss, x_mse = _XLossHuber.apply(v, z_t, x_t, logsnr, self.consistency_huber_c, self.mean_type)
-            else:
-                loss, x_mse, _ = ops.x_loss_huber(v, z_t, x_t, logsnr, self.consistency_huber_c, mean_type=self.mean_type)
-            note(loss, x_mse)
-            return {"loss": loss, "x_mse": x_mse}
-        if self.loss_weight_type in ops.X_LOSS_WEIGHTS:           # 'snr_plus1' / 'min_snr': w(logsnr) x_mse, no eps anywhere
-            if grad:
-                loss, x_mse = _XLossW.apply(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, self.mean_type)
-            else:
-                loss, x_mse, _ = ops.x_loss_w(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, mean_type=self.mean_type)
-            note(loss, x_mse)
-            return {"loss": loss, "x_mse": x_mse}
-        if grad:
-            loss = _VLoss.apply(v, z_t, x_t, eps_t, logsnr, loss_type, self.mean_type)
-            note(loss, None)
-            return {"loss": loss}
-        loss, x_mse = ops.v_loss(v, z_t, x_t, eps_t, logsnr, loss_type=loss_type, mean_type=self.mean_type)[:2]
-        note(loss, x_mse)
-        # a weighting chosen by the caller also reports the unweighted x_mse: one number that compares runs under different weightings
-        return {"loss": loss, "x_mse": x_mse} if self.loss_weight != "snr_trunc" else {"loss": loss}
+        row = self._loss_row(module)
+        pred = module(z_t, logsnr, guide=guide, cond_w=w, **({"want_nu": True} if row.nu else {}))
+        v, nu = pred if row.nu else (pred, None)
+        v_grad = row.op == "v_loss" and torch.is_grad_enabled() and v.requires_grad
+        o = self._loss(row, v, nu, z_t, x_t, eps_t, logsnr, u, loss_type, None)
+        if self.loss_profile:                                     # the batch into the test profile at decay 1 (plain sums)
+            x_mse = None if v_grad else o["x_mse"]                # (kept as it was: under autograd the v-loss rows hand the profile no x_mse)
+            ops.loss_profile(u, o["loss"].detach(), x_mse, self.profile_state("test", u.device), 1.0)
+        if row.nu:
+            return {"loss": o["loss"], "vlb": o["vlb"], "var_frac": o["var_frac"]}
+        # the v-loss rows report the unweighted x_mse only under a weighting the caller chose: one number that compares runs across weightings
+        if v_grad or (row.op == "v_loss" and self.loss_weight == "snr_trunc"):      # (kept as it was: under autograd they never report it)
+            return {"loss": o["loss"]}
+        return {"loss": o["loss"], "x_mse": o["x_mse"]}
 
     def train_forward_backward(self, *, net, x, grad_scale, u=None, eps=None, i_times=None, cond_w=None,
                                on_grads_ready=None, join_side_before_ready=True):
@@ -1230,50 +1200,29 @@ class GaussianDiffusion:
         # time_importance it goes through the profile's inverse CDF, and every image's gradient and loss take the importance weight 1 / (64 p).
         profiled = (self.time_importance or self.loss_profile) and u is None
         time_w = None
-        if self.learn_var and not profiled:     # the bound's time pair needs u: `_prepare`'s draws in its order (eps, then u), made here
-            if eps is None:
-                eps = self.rng.normal(x.shape, x.device)
-            if u is None:
-                u = self.draw_u(x.shape[0], x.device)
-            u = ops.aligned(u.float())
-        if profiled:
-            if eps is None:
-                eps = self.rng.normal(x.shape, x.device)
-            u = self.draw_u(x.shape[0], x.device)
-            if self.time_importance:
-                u, time_w = ops.u_importance(self.profile_state("train", x.device), u, self.importance_warmup, self.importance_floor)
+        if self.learn_var or profiled:          # both need u after `_prepare` (the bound's time pair, the profile)
+            u, eps = self.draw_eps_u(x, u, eps)
+        if profiled and self.time_importance:
+            u, time_w = ops.u_importance(self.profile_state("train", x.device), u, self.importance_warmup, self.importance_floor)
         module, guide, w, z_t, logsnr, x_t, eps_t, loss_type = self._prepare(net, x, u, eps, i_times, cond_w)
+        row = self._loss_row(module)
         ctx = {}
-        dnu = None
-        if self.learn_var:                      # the hybrid loss: the simple loss's dv (gmk_v_loss's bits) and the bound's dnu, one launch
-            if not getattr(module, "learn_var", False):
-                raise ValueError("learn_var = 1 with a network that has no variance head (SimpleUnet(learn_var=True))")
-            v, nu = module.forward_hip(z_t, logsnr, guide, w, ctx=ctx, want_nu=True)
-            loss_b, vlb, frac, x_mse, eps_mse, dv, dnu = ops.hybrid_loss(v, nu, z_t, x_t, eps_t, logsnr, self._logsnr_prev(u), self.vlb_lambda,
-                                                                        grad_scale=grad_scale, loss_type=loss_type, mean_type=self.mean_type)
-            out = {"loss": loss_b, "x_mse": x_mse, "eps_mse": eps_mse, "logsnr": logsnr, "vlb": vlb, "var_frac": frac}
-        else:
-            v = module.forward_hip(z_t, logsnr, guide, w, ctx=ctx)
-            if self.loss_weight_type == "huber":
-                loss_b, x_mse, dv = ops.x_loss_huber(v, z_t, x_t, logsnr, self.consistency_huber_c, grad_scale=grad_scale, mean_type=self.mean_type)
-                out = {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
-            elif self.loss_weight_type in ops.X_LOSS_WEIGHTS:
-                loss_b, x_mse, dv = ops.x_loss_w(v, z_t, x_t, logsnr, self.loss_weight_type, self.loss_gamma, grad_scale=grad_scale,
-                                                 mean_type=self.mean_type)
-                out = {"loss": loss_b, "x_mse": x_mse, "logsnr": logsnr}
-            else:
-                loss_b, x_mse, eps_mse, dv = ops.v_loss(v, z_t, x_t, eps_t, logsnr, grad_scale=grad_scale, loss_type=loss_type, mean_type=self.mean_type)
-                out = {"loss": loss_b, "x_mse": x_mse, "eps_mse": eps_mse, "logsnr": logsnr}
+        pred = module.forward_hip(z_t, logsnr, guide, w, ctx=ctx, **({"want_nu": True} if row.nu else {}))
+        v, nu = pred if row.nu else (pred, None)
+        o = self._loss(row, v, nu, z_t, x_t, eps_t, logsnr, u, loss_type, grad_scale)
+        dv, dnu = o["dv"], o.get("dnu")
         if time_w is not None:                  # the importance weights scale every row of the output gradients
             dv = ops.scale_rows(dv.view(dv.shape[0], -1), time_w).view_as(dv)
             if dnu is not None:
                 dnu = ops.scale_rows(dnu.view(dnu.shape[0], -1), time_w).view_as(dnu)
         module.backward_hip(ctx, dv, on_grads_ready=on_grads_ready, join_side_before_ready=join_side_before_ready, dnu=dnu)
+        o["logsnr"] = logsnr
+        out = {key: o[key] for key in TRAIN_KEYS if key in o}
         if profiled:                    # the UNWEIGHTED loss enters the profile: p must follow the loss itself, not the loss it reweighted
-            ops.loss_profile(u, loss_b, x_mse, self.profile_state("train", u.device), self.importance_decay)
+            ops.loss_profile(u, out["loss"], out["x_mse"], self.profile_state("train", u.device), self.importance_decay)
             out["u"] = u
             if time_w is not None:      # loss: the unbiased estimate of the uniform-time loss
-                out.update(loss=time_w * loss_b, loss_b=loss_b, time_w=time_w)
+                out.update(loss=time_w * out["loss"], loss_b=out["loss"], time_w=time_w)
         return out
 
     # ---- likelihood: the continuous-time variational bound (an extension, no reference call site) ------------------------------------------

@@ -928,19 +928,32 @@ def q_sample(x, eps, u, schedule=None):
 MEAN_TYPES = {"v": C["GMK_MEAN_V"], "eps": C["GMK_MEAN_EPS"], "x": C["GMK_MEAN_X"]}      # what the network output parametrises (gaussian_diffusion.py:58-73)
 
 
+def _loss_front(what, images, vectors, mean_type, aligned16=False):
+    """What the four loss wrappers ask of their tensors, after their own scalars: a known mean type, then `_images` - images: (tensor, name)
+    pairs of one fp32 shape [B, ...], vectors: (tensor, name) pairs of fp32 [B], all contiguous device tensors; aligned16: also 16-byte
+    aligned (`v_loss`, as ever; its siblings take other tensors on their scalar path).  -> (B, values per image)"""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    B, n = _images(images, tuple((t, nm, torch.float32) for t, nm in vectors), what)
+    for t, nm in (images + vectors) if aligned16 else ():
+        if t.data_ptr() % 16:
+            raise ValueError(f"{nm}: data pointer not 16-byte aligned")
+    return B, n
+
+
+def _loss_call(what, inputs, n_out, wrt, grad_scale, scalars, mean_type, B, n):
+    """The four loss wrappers' tail: n_out per-image fp32 [B] outputs, a gradient like each tensor of `wrt` iff grad_scale is given, and the call
+    gmk_<what>(inputs, outputs, gradients, grad_scale, scalars, mean type, B, n, stream).  -> (outputs ..., gradients or Nones ...)"""
+    outs = tuple(torch.empty((B,), device=inputs[0].device, dtype=torch.float32) for _ in range(n_out))
+    grads = tuple(torch.empty_like(t) if grad_scale is not None else None for t in wrt)
+    check(getattr(lib, "gmk_" + what)(*map(_p, inputs + outs + grads), float(grad_scale or 0.0), *scalars, MEAN_TYPES[mean_type], B, n, _s()), what)
+    return outs + grads
+
+
 def v_loss(v, z, x, eps, logsnr, grad_scale=None, loss_type=0, mean_type="v"):
     """-> (loss_b, x_mse, eps_mse, dv or None).  loss_type 0 'snr_trunc', 1 'snr'."""
-    for t, nm in ((v, "v"), (z, "z"), (x, "x"), (eps, "eps"), (logsnr, "logsnr")):
-        _f32(t, nm)
-    B = x.shape[0]
-    n = x.numel() // B
-    assert v.shape == x.shape == z.shape == eps.shape and logsnr.numel() == B
-    loss_b = torch.empty((B,), device=x.device, dtype=torch.float32)
-    xm = torch.empty_like(loss_b); em = torch.empty_like(loss_b)
-    dv = torch.empty_like(v) if grad_scale is not None else None
-    check(lib.gmk_v_loss(_p(v), _p(z), _p(x), _p(eps), _p(logsnr), _p(loss_b), _p(xm), _p(em), _p(dv),
-                         float(grad_scale or 0.0), loss_type, MEAN_TYPES[mean_type], B, n, _s()), "v_loss")
-    return loss_b, xm, em, dv
+    B, n = _loss_front("v_loss", ((x, "x"), (v, "v"), (z, "z"), (eps, "eps")), ((logsnr, "logsnr"),), mean_type, aligned16=True)
+    return _loss_call("v_loss", (v, z, x, eps, logsnr), 3, (v,), grad_scale, (loss_type,), mean_type, B, n)
 
 
 def hybrid_loss(v, nu, z, x, eps, logsnr, logsnr_s, vlb_lambda, grad_scale=None, loss_type=0, mean_type="v"):
@@ -950,22 +963,13 @@ def hybrid_loss(v, nu, z, x, eps, logsnr, logsnr_s, vlb_lambda, grad_scale=None,
     (16-byte aligned tensors with n % 4 == 0 take the 16-byte path, anything else the scalar one); logsnr, logsnr_s: fp32 [B], logsnr_s >= logsnr
     the log-SNR one step of the bound's grid earlier.  -> (loss_b, vlb_b, frac_b, x_mse, eps_mse, dv or None, dnu or None), the gradients of
     grad_scale sum_b loss_b when grad_scale is given."""
-    if mean_type not in MEAN_TYPES:
-        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
     if loss_type not in (0, 1):
         raise ValueError(f"loss_type {loss_type!r}: 0 (snr_trunc) or 1 (snr)")
     lam = float(vlb_lambda)
     if not (math.isfinite(lam) and lam >= 0.0):
         raise ValueError(f"vlb_lambda = {lam}: need a finite value >= 0")
-    B, n = _images(((x, "x"), (v, "v"), (nu, "nu"), (z, "z"), (eps, "eps")),
-                   ((logsnr, "logsnr", torch.float32), (logsnr_s, "logsnr_s", torch.float32)), "hybrid_loss")
-    loss_b = torch.empty((B,), device=x.device, dtype=torch.float32)
-    vlb, frac, xm, em = (torch.empty_like(loss_b) for _ in range(4))
-    dv = torch.empty_like(v) if grad_scale is not None else None
-    dnu = torch.empty_like(nu) if grad_scale is not None else None
-    check(lib.gmk_hybrid_loss(_p(v), _p(nu), _p(z), _p(x), _p(eps), _p(logsnr), _p(logsnr_s), _p(loss_b), _p(vlb), _p(frac), _p(xm), _p(em),
-                              _p(dv), _p(dnu), float(grad_scale or 0.0), lam, loss_type, MEAN_TYPES[mean_type], B, n, _s()), "hybrid_loss")
-    return loss_b, vlb, frac, xm, em, dv, dnu
+    B, n = _loss_front("hybrid_loss", ((x, "x"), (v, "v"), (nu, "nu"), (z, "z"), (eps, "eps")), ((logsnr, "logsnr"), (logsnr_s, "logsnr_s")), mean_type)
+    return _loss_call("hybrid_loss", (v, nu, z, x, eps, logsnr, logsnr_s), 5, (v, nu), grad_scale, (lam, loss_type), mean_type, B, n)
 
 
 X_LOSS_WEIGHTS = {"snr_plus1": C["GMK_LOSS_W_SNR_PLUS1"], "min_snr": C["GMK_LOSS_W_MIN_SNR"]}      # the weightings gmk_x_loss_w evaluates
@@ -979,23 +983,11 @@ def x_loss_w(v, z, x, logsnr, weight, gamma, grad_scale=None, mean_type="v"):
     scalar one); logsnr: fp32 [B].  -> (loss_b, x_mse, dv or None), dv = d(grad_scale sum_b loss_b)/dv when grad_scale is given."""
     if weight not in X_LOSS_WEIGHTS:
         raise ValueError(f"weight {weight!r}: expected one of {sorted(X_LOSS_WEIGHTS)}")
-    if mean_type not in MEAN_TYPES:
-        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
     gamma = float(gamma)
     if not (math.isfinite(gamma) and gamma > 0.0):
         raise ValueError(f"gamma = {gamma}: need a finite value > 0")
-    for t, nm in ((v, "v"), (z, "z"), (x, "x"), (logsnr, "logsnr")):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-            raise ValueError(f"{nm}: expected a contiguous fp32 device tensor")
-    B = x.shape[0]
-    n = x.numel() // B
-    assert v.shape == x.shape == z.shape and logsnr.numel() == B
-    loss_b = torch.empty((B,), device=x.device, dtype=torch.float32)
-    xm = torch.empty_like(loss_b)
-    dv = torch.empty_like(v) if grad_scale is not None else None
-    check(lib.gmk_x_loss_w(_p(v), _p(z), _p(x), _p(logsnr), _p(loss_b), _p(xm), _p(dv), float(grad_scale or 0.0), X_LOSS_WEIGHTS[weight], gamma,
-                           MEAN_TYPES[mean_type], B, n, _s()), "x_loss_w")
-    return loss_b, xm, dv
+    B, n = _loss_front("x_loss_w", ((x, "x"), (v, "v"), (z, "z")), ((logsnr, "logsnr"),), mean_type)
+    return _loss_call("x_loss_w", (v, z, x, logsnr), 2, (v,), grad_scale, (X_LOSS_WEIGHTS[weight], gamma), mean_type, B, n)
 
 
 def u_stratified(u0, B):
@@ -1536,18 +1528,11 @@ def x_loss_huber(v, z, x, logsnr, c, grad_scale=None, mean_type="v"):
     """Pseudo-Huber x-space loss (gmk_x_loss_huber; Song & Dhariwal 2023; an extension): loss_b = sqrt(x_mse + c^2) - c, x_mse = mean (x_hat - x)^2
     of the clipped prediction - the bits of `x_loss_w`'s x_mse.  c = c_paper / sqrt(n), finite and > 0.  Tensors as in `x_loss_w`.
     -> (loss_b, x_mse, dv or None), dv = d(grad_scale sum_b loss_b)/dv when grad_scale is given."""
-    if mean_type not in MEAN_TYPES:
-        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
     c = float(c)
     if not (math.isfinite(c) and c > 0.0):
         raise ValueError(f"c = {c}: need a finite value > 0")
-    B, n = _images(((x, "x"), (v, "v"), (z, "z")), ((logsnr, "logsnr", torch.float32),), "x_loss_huber")
-    loss_b = torch.empty((B,), device=x.device, dtype=torch.float32)
-    xm = torch.empty_like(loss_b)
-    dv = torch.empty_like(v) if grad_scale is not None else None
-    check(lib.gmk_x_loss_huber(_p(v), _p(z), _p(x), _p(logsnr), _p(loss_b), _p(xm), _p(dv), float(grad_scale or 0.0), c, MEAN_TYPES[mean_type],
-                               B, n, _s()), "x_loss_huber")
-    return loss_b, xm, dv
+    B, n = _loss_front("x_loss_huber", ((x, "x"), (v, "v"), (z, "z")), ((logsnr, "logsnr"),), mean_type)
+    return _loss_call("x_loss_huber", (v, z, x, logsnr), 2, (v,), grad_scale, (c,), mean_type, B, n)
 
 
 def consistency_step(v, z, logsnr_t, logsnr_s, is_last, seed, offset, q0=0, v_uncond=None, cond_w=None, want_pred=False, mean_type="v",
