@@ -21,7 +21,9 @@
 // alone; DDIM with eta > 0 (Song et al. 2021) and SDE-DPM-Solver++(2M) (Lu et al. 2022) through the same entry are extensions.
 // gmk_hybrid_loss / gmk_stochastic_step_lv / gmk_add_into (a learned reverse-process variance: Nichol & Dhariwal 2021, "Improved Denoising
 // Diffusion Probabilistic Models", section 3.1 - the bound term is normal_kl of diffusion_utils.py:138-163 on diffusion_reverse's variances) are
-// extensions, no reference call site.
+// extensions, no reference call site.  gmk_gauss_blur / gmk_dps_backproject / gmk_dps_correct (diffusion posterior sampling: Chung et al. 2023,
+// Algorithm 1, for box-mean and Gaussian-blur measurements) are extensions as well; they stand at the end of the file.
+#include <float.h>
 #include <math.h>
 
 #include "gmk_common.h"
@@ -2461,4 +2463,189 @@ extern "C" int gmk_cfg_rescale(const float* v, const float* v_uncond, const floa
     else if (keep) cfg_rescale_kernel<false, true><<<B, 256, 0, st>>>(v, v_uncond, cond_w, z, logsnr_t, phi, thr_out, ratio_out, n, mean_type);
     else cfg_rescale_kernel<false, false><<<B, 256, 0, st>>>(v, v_uncond, cond_w, z, logsnr_t, phi, thr_out, ratio_out, n, mean_type);
     return gmk_check_launch("gmk_cfg_rescale");
+}
+
+// ---- Diffusion posterior sampling (DPS: Chung et al. 2023, "Diffusion Posterior Sampling for General Noisy Inverse Problems", Algorithm 1);
+// an extension, no reference call site.  Observation y = A x + noise; per sampler step, with the network output `out` at (z, lt):
+//   x-hat = x_from_out(out, z) (UNCLIPPED: a clip has zero gradient where early steps saturate), e = y - A x-hat, u = A^T e, |e|^2 per image
+//   (gmk_dps_backproject); g = (d out / d z)^T u (the network's input VJP); z_s += 2 zeta / max(|e|, FLT_MIN) (c_z u + c_o g) (gmk_dps_correct),
+//   (c_z, c_o) = d x-hat / d (z, out).  A is the box mean of DDNM (BoxGeom; A^T e = e / k replicated over the box) or a separable Gaussian
+//   blur with zero padding (symmetric: A^T = A).  Every sum is single rounded fp32 operations in a fixed order: the same call gives the same bits.
+namespace {
+
+constexpr int kBlurSide = GMK_BLUR_MAX_SIDE;        // a plane of at most 64 x 64 floats (16 KiB) is staged in LDS, with a second one for the row pass
+constexpr int kBlurTaps = 2 * GMK_BLUR_MAX_R + 1;
+
+struct BlurLds {
+    float a[kBlurSide * kBlurSide], t[kBlurSide * kBlurSide], taps[kBlurTaps];
+};
+
+// every thread of a 256-thread workgroup: the first 2 R + 1 stage the taps
+__device__ __forceinline__ void blur_stage_taps(BlurLds& s, const float* __restrict__ taps, int R) {
+    if ((int)threadIdx.x < 2 * R + 1) s.taps[threadIdx.x] = taps[threadIdx.x];
+}
+
+// The blur of the H x W plane staged in s.a, in place, by every thread of a 256-thread workgroup (barriers inside: one ahead of the first read of
+// s.a and s.taps, one behind the last write).  Rows first, s.t[y][x] = sum_k taps[k + R] a[y][x + k], then columns, a[y][x] = sum_k taps[k + R]
+// t[y + k][x]; each sum starts from 0 and adds fmul(tap, value) for k = -R ... R in that order, the terms outside the plane (zero padding) left
+// out.  Thread i % 256 writes element i in both passes.
+__device__ __forceinline__ void blur_plane(BlurLds& s, int R, int H, int W) {
+    const int n = H * W;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int y = i / W, x = i - y * W;
+        const int k0 = x < R ? -x : -R, k1 = W - 1 - x < R ? W - 1 - x : R;
+        float acc = 0.f;
+        for (int k = k0; k <= k1; ++k) acc = __fadd_rn(acc, __fmul_rn(s.taps[k + R], s.a[i + k]));
+        s.t[i] = acc;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int y = i / W;
+        const int k0 = y < R ? -y : -R, k1 = H - 1 - y < R ? H - 1 - y : R;
+        float acc = 0.f;
+        for (int k = k0; k <= k1; ++k) acc = __fadd_rn(acc, __fmul_rn(s.taps[k + R], s.t[i + k * W]));
+        s.a[i] = acc;
+    }
+    __syncthreads();
+}
+
+// grid B, one workgroup per image, which loops over the channels: out = A x
+__global__ __launch_bounds__(256) void gauss_blur_kernel(const float* __restrict__ x, float* __restrict__ out, const float* __restrict__ taps,
+                                                        int R, int C, int H, int W) {
+    __shared__ BlurLds s;
+    const int n = H * W;
+    blur_stage_taps(s, taps, R);
+    for (int ch = 0; ch < C; ++ch) {
+        const int64_t base = ((int64_t)blockIdx.x * C + ch) * n;
+        for (int i = threadIdx.x; i < n; i += 256) s.a[i] = x[base + i];
+        blur_plane(s, R, H, W);
+        for (int i = threadIdx.x; i < n; i += 256) out[base + i] = s.a[i];
+    }
+}
+
+// grid B, one workgroup per image.  x-hat = x_from_out(v, z) per element (v and z are read once), then
+//   BLUR: per channel, A x-hat by blur_plane (gauss_blur_kernel's function: its bits), e = fsub(obs, A x-hat) over the plane, u = blur_plane(e);
+//   box:  per box (one thread each, 256 at a time), box_kernel's sequential mean of x-hat, e = fsub(obs, mean), u = fdiv(e, (float)k) stored to
+//         the k members.
+// enorm2[b] = |e_b|^2: every thread adds fmul(e, e) of its elements to a partial in the order it visits them (from 0), the 256 partials are
+// summed by a binary tree in LDS (red[t] += red[t + s] for s = 128, 64 ... 1).  No atomics.
+template <bool BLUR>
+__global__ __launch_bounds__(256) void dps_backproject_kernel(const float* __restrict__ v, const float* __restrict__ z,
+                                                             const float* __restrict__ obs, float lt, int mt, const float* __restrict__ taps,
+                                                             int R, float* __restrict__ u, float* __restrict__ enorm2, BoxGeom g) {
+    __shared__ float red[256];
+    const int b = blockIdx.x;
+    const LogsnrCoef c = logsnr_coef(lt);
+    float part = 0.f;
+    if constexpr (BLUR) {
+        __shared__ BlurLds s;
+        const int n = g.HW;
+        blur_stage_taps(s, taps, R);
+        for (uint32_t ch = 0; ch < g.C; ++ch) {
+            const int64_t base = ((int64_t)b * g.C + ch) * n;
+            for (int i = threadIdx.x; i < n; i += 256) s.a[i] = x_from_out(v[base + i], z[base + i], c, mt);
+            blur_plane(s, R, g.H, g.W);
+            for (int i = threadIdx.x; i < n; i += 256) {
+                const float e = __fsub_rn(obs[base + i], s.a[i]);
+                part = __fadd_rn(part, __fmul_rn(e, e));
+                s.a[i] = e;
+            }
+            blur_plane(s, R, g.H, g.W);
+            for (int i = threadIdx.x; i < n; i += 256) u[base + i] = s.a[i];
+        }
+    } else {
+        const float k = (float)(g.cf * g.N * g.N);
+        const int64_t base = (int64_t)b * g.C * g.HW;
+        for (uint32_t box = threadIdx.x; box < g.n_box; box += 256) {
+            const uint32_t j = box % g.Wb, t = box / g.Wb, i = t % g.Hb, cp = t / g.Hb;
+            float sum = 0.f;
+            for (uint32_t dc = 0; dc < g.cf; ++dc)
+                for (uint32_t dy = 0; dy < g.N; ++dy) {
+                    const int64_t row = base + (int64_t)(cp * g.cf + dc) * g.HW + (i * g.N + dy) * g.W + j * g.N;
+                    for (uint32_t dx = 0; dx < g.N; ++dx) sum = __fadd_rn(sum, x_from_out(v[row + dx], z[row + dx], c, mt));
+                }
+            const float e = __fsub_rn(obs[(int64_t)b * g.n_box + box], __fdiv_rn(sum, k));
+            part = __fadd_rn(part, __fmul_rn(e, e));
+            const float ue = __fdiv_rn(e, k);
+            for (uint32_t dc = 0; dc < g.cf; ++dc)
+                for (uint32_t dy = 0; dy < g.N; ++dy) {
+                    const int64_t row = base + (int64_t)(cp * g.cf + dc) * g.HW + (i * g.N + dy) * g.W + j * g.N;
+                    for (uint32_t dx = 0; dx < g.N; ++dx) u[row + dx] = ue;
+                }
+        }
+    }
+    red[threadIdx.x] = part;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = __fadd_rn(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) enorm2[b] = red[0];
+}
+
+// grid (ceil(n / 1024), B), n % 4 == 0, in place: z = fadd(z, fmul(scale, fadd(fmul(c_z, u), fmul(c_o, g)))) with scale = min(fdiv(zeta2,
+// max(sqrt(enorm2[b]), FLT_MIN)), FLT_MAX), zeta2 = 2 zeta from the host (the min keeps 0 times the scale 0 when |e| = 0)
+__global__ __launch_bounds__(256) void dps_correct_kernel(float* __restrict__ z, const float* __restrict__ u, const float* __restrict__ g,
+                                                         const float* __restrict__ enorm2, float c_z, float c_o, float zeta2, int64_t n) {
+    const int b = blockIdx.y;
+    const float scale = fminf(__fdiv_rn(zeta2, fmaxf(sqrtf(enorm2[b]), FLT_MIN)), FLT_MAX);
+    const int64_t base = (int64_t)b * n;
+    for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+        float zv[4], uv[4], gv[4];
+        load4(z + base + i, zv);
+        load4(u + base + i, uv);
+        load4(g + base + i, gv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) zv[k] = __fadd_rn(zv[k], __fmul_rn(scale, __fadd_rn(__fmul_rn(c_z, uv[k]), __fmul_rn(c_o, gv[k]))));
+        store4(z + base + i, zv);
+    }
+}
+
+}  // namespace
+
+static int blur_args_check(const char* who, const float* taps, int R, int B, int C, int H, int W) {
+    GMK_REQUIRE(taps, "%s: null pointer (taps)", who);
+    GMK_REQUIRE(R >= 1 && R <= GMK_BLUR_MAX_R, "%s: R = %d outside [1, %d]", who, R, GMK_BLUR_MAX_R);
+    GMK_REQUIRE(B > 0 && B < 65536 && C > 0 && H > 0 && W > 0 && H <= GMK_BLUR_MAX_SIDE && W <= GMK_BLUR_MAX_SIDE,
+                "%s: bad shape B=%d C=%d H=%d W=%d (H, W <= %d: the plane is staged in LDS)", who, B, C, H, W, GMK_BLUR_MAX_SIDE);
+    return 0;
+}
+
+extern "C" int gmk_gauss_blur(const float* x, float* out, const float* taps, int R, int B, int C, int H, int W, void* stream) {
+    GMK_REQUIRE(x && out, "gmk_gauss_blur: null pointer");
+    if (const int err = blur_args_check("gmk_gauss_blur", taps, R, B, C, H, W)) return err;
+    gauss_blur_kernel<<<B, 256, 0, gmk_stream(stream)>>>(x, out, taps, R, C, H, W);
+    return gmk_check_launch("gmk_gauss_blur");
+}
+
+extern "C" int gmk_dps_backproject(const float* v, const float* z, const float* obs, float logsnr_t, int op, int cf, int N, const float* taps,
+                                   int R, float* u, float* enorm2, int mean_type, int B, int C, int H, int W, void* stream) {
+    GMK_REQUIRE(v && z && obs && u && enorm2, "gmk_dps_backproject: null pointer");
+    GMK_REQUIRE_MEAN_TYPE(mean_type, "gmk_dps_backproject");
+    GMK_REQUIRE(isfinite(logsnr_t), "gmk_dps_backproject: non-finite time");
+    GMK_REQUIRE(op == GMK_DPS_BOX || op == GMK_DPS_BLUR, "gmk_dps_backproject: op = %d, expected 0 (box) or 1 (blur)", op);
+    BoxGeom g;
+    if (op == GMK_DPS_BLUR) {
+        if (const int err = blur_args_check("gmk_dps_backproject", taps, R, B, C, H, W)) return err;
+        if (const int err = box_geom_check("gmk_dps_backproject", B, C, H, W, 1, 1, &g)) return err;      // (the shape fields alone are read)
+        dps_backproject_kernel<true><<<B, 256, 0, gmk_stream(stream)>>>(v, z, obs, logsnr_t, mean_type, taps, R, u, enorm2, g);
+    } else {
+        if (const int err = box_geom_check("gmk_dps_backproject", B, C, H, W, cf, N, &g)) return err;
+        dps_backproject_kernel<false><<<B, 256, 0, gmk_stream(stream)>>>(v, z, obs, logsnr_t, mean_type, nullptr, 0, u, enorm2, g);
+    }
+    return gmk_check_launch("gmk_dps_backproject");
+}
+
+extern "C" int gmk_dps_correct(float* z, const float* u, const float* g, const float* enorm2, float c_z, float c_o, float zeta, int B, int64_t n,
+                               void* stream) {
+    GMK_REQUIRE(z && u && g && enorm2, "gmk_dps_correct: null pointer");
+    GMK_REQUIRE(B > 0 && B < 65536 && n >= 4 && n % 4 == 0, "gmk_dps_correct: bad shape B=%d n=%lld (n %% 4 == 0 required)", B, (long long)n);
+    GMK_REQUIRE(((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(g)) & 15) == 0,
+                "gmk_dps_correct: z, u and g must be 16-byte aligned");
+    GMK_REQUIRE(isfinite(c_z) && isfinite(c_o) && isfinite(zeta) && zeta >= 0.0f && isfinite(2.0f * zeta),
+                "gmk_dps_correct: c_z = %g, c_o = %g, zeta = %g: finite, zeta >= 0", (double)c_z, (double)c_o, (double)zeta);
+    if (zeta == 0.0f) return 0;      // no guidance: nothing is launched, z keeps its bits (a sum z + 0 would turn -0 into +0)
+    dps_correct_kernel<<<dim3(row_grid(n, 1024), B), 256, 0, gmk_stream(stream)>>>(z, u, g, enorm2, c_z, c_o, 2.0f * zeta, n);
+    return gmk_check_launch("gmk_dps_correct");
 }

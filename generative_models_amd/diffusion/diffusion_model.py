@@ -25,7 +25,7 @@ import torch
 from .. import checkpoint, common, ops, parallel, posthoc_ema
 from .gaussian_diffusion import (GaussianDiffusion, PhiloxStream, Schedule, consistency_check, dyn_threshold_check, edit_start, guidance_check,
                                  loss_weight_check, restore_operator, schedule_check, stochastic_check, time_importance_check, learned_var_check,
-                                 FLAG_WORDS, sampler_caps, sampler_compat_check)
+                                 FLAG_WORDS, sampler_caps, sampler_compat_check, dps_check, dps_zeta_check, measurement_op)
 from .optim import FusedAdam
 from .simple_unet import SimpleUnet
 
@@ -80,6 +80,11 @@ def make_plugin(GMBase, AttrDict):
                                        # Wang, Yu & Zhang 2023) as last_eval['restore'] / frames 'restore', 'restore_input', with last_eval['restore_psnr'];
                                        # not in the reference, off by default
         DG.restore_gray = 0            # 1: that restoration also (or, with restore_eval = 0, only) starts from the channel mean (colourisation)
+        DG.dps_eval = ""               # 'box:N' | 'gray' | 'gray_box:N' | 'blur:SIGMA': evaluate() also restores the first 25 test images from that measurement
+                                       # plus noise by diffusion posterior sampling (DPS, Chung et al. 2023) as last_eval['dps'] / frames 'dps', 'dps_input',
+                                       # with last_eval['dps_psnr'], ['dps_input_psnr'] and ['dps_residual']; samplers 'ddim', 'noisy', 'ancestral'; '': off
+        DG.dps_noise = 0.05            # the standard deviation of that measurement's noise, >= 0 (dps_residual is comparable with it)
+        DG.dps_zeta = 1.0              # the DPS step size zeta >= 0 of evaluate() and posterior_sample(); untuned: the paper's values lie in 0.3 ... 1
         DG.dyn_threshold = 0.0         # p in (0, 1]: sample() / evaluate() / inpaint() clamp each image's x-hat to its own p-th percentile of |x| and rescale
                                        # (dynamic thresholding, Saharia et al. 2022; e.g. 0.995) instead of the clip at 1; not in the reference, off by default
         DG.guidance_lo = float("-inf") # the guidance interval (Kynkaanniemi et al. 2024): a guided sampler step whose log-SNR lies outside [guidance_lo, guidance_hi]
@@ -194,6 +199,16 @@ def make_plugin(GMBase, AttrDict):
             if self.restore_gray and int(get("in_channels")) == 1:
                 raise ValueError("restore_gray = 1 with in_channels = 1: there is no colour to restore")
             self.binarize = int(get("binarize"))
+            self.dps_eval = get("dps_eval")
+            if not isinstance(self.dps_eval, str):
+                raise ValueError(f"dps_eval = {self.dps_eval!r}: '' (off) or a measurement, 'box:N', 'gray', 'gray_box:N' or 'blur:SIGMA'")
+            self.dps_zeta = dps_zeta_check(get("dps_zeta"), "dps_zeta")
+            try:
+                self.dps_noise = float(get("dps_noise"))
+            except (TypeError, ValueError):
+                raise ValueError(f"dps_noise = {get('dps_noise')!r}: the noise's standard deviation, finite and >= 0") from None
+            if not (0.0 <= self.dps_noise < float("inf")):
+                raise ValueError(f"dps_noise = {self.dps_noise}: the noise's standard deviation, finite and >= 0")
             dyn_threshold = dyn_threshold_check(get("dyn_threshold"))
             learn_var, vlb_lambda, vlb_steps = learned_var_check(get("learn_var"), get("vlb_lambda"), get("vlb_steps"), self.teacher_net is not None,
                                                                  get("loss_weight"))
@@ -270,6 +285,11 @@ def make_plugin(GMBase, AttrDict):
             if self._size_declared:
                 self.size = int(get("image_size"))
             self._aux_rng = PhiloxStream(seed + 7919)
+            if self.dps_eval:               # the string against this model's images, the sampler and its options against what DPS runs with
+                measurement_op(self.dps_eval, (1, int(get("in_channels")), self.size, self.size))
+                fixed_w = get("sample_cond_w") is not None and float(get("sample_cond_w")) != -1.0
+                dps_check(sampler=get("sampler"), ddim_eta=ddim_eta, mean_type=get("mean_type"), cond_w=fixed_w, dyn_threshold=dyn_threshold,
+                          cfg_rescale=cfg_rescale, learned_var=posterior_var == "learned", student=self.teacher_net is not None, what="dps_eval")
             self._sync = None
 
         def train(self, mode=True):
@@ -589,6 +609,30 @@ def make_plugin(GMBase, AttrDict):
                 cond_w = 0.5 if y is not None else None
                 return self.diffusion.restore(net=net, obs=obs, factor=factor, gray=gray, init_x=noise, cond_w=cond_w)[0][-1]
 
+        # -- posterior sampling (an extension): DPS from a noisy box-mean or blurred observation on the net sample() uses
+        def measure(self, x, kind, *, noise_std=0.0, seed=0):
+            """The observation A x + noise_std n that `posterior_sample` starts from: kind 'box:N', 'gray', 'gray_box:N' (`degrade`'s
+            operators and format) or 'blur:SIGMA' (a Gaussian blur, x's shape); n standard normal from PhiloxStream(seed) through
+            `ops.rng_normal` (nothing is drawn with noise_std = 0).  -> fp32"""
+            x = ops.aligned(x.float().contiguous())
+            op, low = measurement_op(kind, tuple(x.shape))
+            noise_std = float(noise_std)
+            if not (0.0 <= noise_std < float("inf")):
+                raise ValueError(f"measure: noise_std = {noise_std}, need a finite standard deviation >= 0")
+            obs = ops.measure(x, op)
+            return obs if noise_std == 0.0 else obs + noise_std * PhiloxStream(seed).normal(low, x.device)
+
+        def posterior_sample(self, obs, kind, *, zeta=None, y=None, seed=0):
+            """An image of this model whose `measure(., kind)` agrees with obs up to the observation's noise, with
+            `GaussianDiffusion.posterior_sample` (DPS).  zeta: the step size (None: the dps_zeta flag); y: labels (no guidance: DPS runs
+            the conditional model alone).  The initial noise comes from PhiloxStream(seed).  -> [B, C, S, S]"""
+            with torch.no_grad():
+                shape = (obs.shape[0], self.net.in_channels, self.size, self.size)
+                op, _ = measurement_op(kind, shape)
+                noise = PhiloxStream(seed).normal(shape, obs.device)
+                return self.diffusion.posterior_sample(net=partial(self._sampling_net(), guide=y), obs=obs, op=op, init_x=noise,
+                                                       zeta=self.dps_zeta if zeta is None else zeta)[0][-1]
+
         # -- editing and interpolation (extensions): SDEdit and latent-code interpolation on the net sample() uses
         def edit(self, x, strength, y=None, mask=None, seed=0):
             """Edit x ([B, C, S, S] in [-1, 1]) with `GaussianDiffusion.edit`: noised up to step k = edit_start(strength, timesteps) of the
@@ -609,6 +653,7 @@ def make_plugin(GMBase, AttrDict):
 
         INPAINT_EVAL_SEED = 104723                  # evaluate()'s inpainting: initial noise from PhiloxStream(this), known-region noise from this + 1
         RESTORE_EVAL_SEED = 104759                  # evaluate()'s restoration: the initial noise (and nothing else) from PhiloxStream(this)
+        DPS_EVAL_SEED = 104773                      # evaluate()'s posterior sampling: the initial noise from PhiloxStream(this), the observation's from this + 1
         EDIT_EVAL_SEED = 104743                     # evaluate()'s editing: the forward noise (and nothing else) from PhiloxStream(this)
 
         # -- evaluate (:89-111): 25 class-conditional samples without guidance, trajectories as uint8
@@ -681,6 +726,26 @@ def make_plugin(GMBase, AttrDict):
                 if pictures:
                     writer.write_frames("restore", z, epoch, crop=crop)
                     writer.write_frames("restore_input", z_in, epoch, crop=crop)
+            if self.dps_eval:                                         # an extension, as above: its draws from PhiloxStream(DPS_EVAL_SEED) and the next
+                k = min(25, x.shape[0])
+                x0 = ops.aligned(x[:k].float().contiguous())
+                op, low = measurement_op(self.dps_eval, tuple(x0.shape))
+                obs = self.measure(x0, self.dps_eval, noise_std=self.dps_noise, seed=self.DPS_EVAL_SEED + 1)
+                init = PhiloxStream(self.DPS_EVAL_SEED).normal(tuple(x0.shape), x.device)
+                z = self.diffusion.posterior_sample(net=partial(self._sampling_net(), guide=None if y is None else y[:k]), obs=obs, op=op,
+                                                    init_x=init, zeta=self.dps_zeta)[0][-1]
+                # what a viewer would see without the model: the replicated box means, or the blurred image itself
+                z_in = obs if op.kind == "blur" else obs.repeat_interleave(op.N, dim=2).repeat_interleave(op.N, dim=3).repeat_interleave(op.cf, dim=1)
+                psnr = lambda t: 10.0 * torch.log10(4.0 / (t.double() - x0.double()).square().mean(dim=(1, 2, 3)))
+                m = math.prod(low[1:])                                # observation values per image
+                self.last_eval["dps"] = proc(z)
+                self.last_eval["dps_psnr"] = psnr(z).cpu()
+                self.last_eval["dps_input_psnr"] = psnr(z_in).cpu()
+                # the mean of |obs - A z| / sqrt(m) over the images: comparable with dps_noise
+                self.last_eval["dps_residual"] = float(((obs - ops.measure(z, op)).double().flatten(1).norm(dim=1) / math.sqrt(m)).mean())
+                if pictures:
+                    writer.write_frames("dps", z, epoch, crop=crop)
+                    writer.write_frames("dps_input", z_in, epoch, crop=crop)
             random.randint(0, 2 ** 32)                                # :111 keeps the host RNG consumption
 
     return DiffusionModel

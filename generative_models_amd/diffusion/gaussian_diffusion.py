@@ -748,6 +748,97 @@ def restore_operator(shape, factor=1, gray=False):
     return cf, N, (B, C // cf, H // N, W // N)
 
 
+# what diffusion posterior sampling (DPS) measures with: a linear operator A on [B, C, H, W] images.  kind 'box': `restore_operator`'s (cf, N)
+# box mean (sigma 0, no taps); kind 'blur': a separable Gaussian of width sigma with zero padding, taps = `blur_taps(sigma)` (cf = N = 1)
+MeasurementOp = namedtuple("MeasurementOp", "kind cf N sigma taps")
+BLUR_MAX_SIGMA = 5.0
+DPS_SAMPLERS = ("ddim", "noisy", "ancestral")       # the samplers `posterior_sample` runs ('ddim' also with ddim_eta > 0: ancestral's kernel)
+DPS_KINDS = "'box:N', 'gray', 'gray_box:N' or 'blur:SIGMA'"
+
+
+def blur_taps(sigma):
+    """The taps of the Gaussian blur: t_k = exp(-k^2 / (2 sigma^2)) for |k| <= R = min(ceil(3 sigma), 15), 0 < sigma <= 5, divided by their
+    full sum in float64 and rounded once to fp32.  -> tuple of 2 R + 1 floats (taps[k + R] weighs offset k), or ValueError."""
+    try:
+        sigma = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"blur: sigma = {sigma!r}, need a width in (0, {BLUR_MAX_SIGMA:g}]") from None
+    if not 0.0 < sigma <= BLUR_MAX_SIGMA:
+        raise ValueError(f"blur: sigma = {sigma}, need a width in (0, {BLUR_MAX_SIGMA:g}]")
+    R = min(int(math.ceil(3.0 * sigma)), 15)
+    t = np.exp(-np.arange(-R, R + 1, dtype=np.float64) ** 2 / (2.0 * sigma * sigma))
+    return tuple(float(v) for v in (t / t.sum()).astype(np.float32))
+
+
+def measurement_op(kind, shape):
+    """The `MeasurementOp` a string names on images of `shape` = [B, C, H, W], and its observation's shape: 'box:N' (N x N box means), 'gray'
+    (the channel mean), 'gray_box:N' (both) - `restore`'s operators and observation format - or 'blur:SIGMA' (the observation has the image's
+    shape; H, W <= 64).  -> (op, observation shape), or ValueError naming the string."""
+    bad = ValueError(f"measurement {kind!r}: expected {DPS_KINDS}")
+    if not isinstance(kind, str):
+        raise bad
+    name, sep, arg = kind.partition(":")
+    if name not in ("box", "gray", "gray_box", "blur") or (name == "gray") != (sep == "") or (sep and not arg):
+        raise bad
+    if name == "blur":
+        try:
+            sigma = float(arg)
+        except ValueError:
+            raise bad from None
+        taps = blur_taps(sigma)
+        if len(shape) != 4 or 0 in shape:
+            raise ValueError(f"measurement {kind!r}: shape {tuple(shape)}, expected [B, C, H, W] with every dimension > 0")
+        if max(int(shape[2]), int(shape[3])) > 64:
+            raise ValueError(f"measurement {kind!r}: H = {shape[2]}, W = {shape[3]}, the blur takes at most 64 x 64 images")
+        return MeasurementOp("blur", 1, 1, sigma, taps), tuple(int(d) for d in shape)
+    try:
+        N = int(arg) if sep else 1
+    except ValueError:
+        raise bad from None
+    cf, N, low = restore_operator(shape, N, name.startswith("gray"))
+    return MeasurementOp("box", cf, N, 0.0, ()), low
+
+
+def dps_check(*, sampler, ddim_eta=0.0, mean_type="v", cond_w=False, dyn_threshold=False, cfg_rescale=False, learned_var=False, student=False,
+              what="posterior_sample"):
+    """Does `posterior_sample` (DPS) go with the options?  sampler: one of `DPS_SAMPLERS`; cond_w (classifier-free guidance), dyn_threshold,
+    cfg_rescale, learned_var (posterior_var 'learned'), student (a distilled student): asked for or not; mean_type 'eps' is refused - its
+    c_z = 1 / alpha_t is about 2e4 at the first step.  `what` names the caller's side.  -> None, or ValueError naming both sides."""
+    if sampler not in DPS_SAMPLERS:
+        raise ValueError(f"{what} together with sampler {sampler!r} is out of scope (it runs {', '.join(map(repr, DPS_SAMPLERS))})")
+    for on, word in ((cond_w, "classifier-free guidance (cond_w)"), (dyn_threshold, "dyn_threshold"), (cfg_rescale, "cfg_rescale"),
+                     (learned_var, "a learned variance (learn_var, posterior_var 'learned')"), (student, "a distilled student (teacher_net)"),
+                     (mean_type == "eps", "mean_type 'eps' (c_z = 1 / alpha_t is about 2e4 at the first step)")):
+        if on:
+            raise ValueError(f"{what} together with {word} is out of scope")
+    stochastic_check(sampler, "large", ddim_eta, False)
+
+
+def dps_zeta_check(zeta, what="posterior_sample"):
+    """zeta, the DPS step size: finite, >= 0 (0: no guidance).  -> float, or ValueError"""
+    try:
+        z = float(zeta)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: zeta = {zeta!r}, need a finite step size >= 0") from None
+    if not (math.isfinite(z) and 0.0 <= z < 1e38):
+        raise ValueError(f"{what}: zeta = {zeta!r}, need a finite step size >= 0")
+    return z
+
+
+def dps_coefs(logsnr_t, mean_type):
+    """(c_z, c_o) = d x-hat / d (z, out) of the unclipped prediction at logsnr_t, in float64: 'v' (alpha_t, -sigma_t), 'eps' (1 / alpha_t,
+    -sigma_t / alpha_t), 'x' (0, 1)."""
+    l = float(logsnr_t)
+    alpha, sigma = math.sqrt(1.0 / (1.0 + math.exp(-l))), math.sqrt(1.0 / (1.0 + math.exp(l)))
+    if mean_type == "v":
+        return alpha, -sigma
+    if mean_type == "eps":
+        return 1.0 / alpha, -sigma / alpha
+    if mean_type == "x":
+        return 0.0, 1.0
+    raise ValueError(f"mean_type {mean_type!r}")
+
+
 def sampler_plan(num_steps, sampler="ddim", resample=None, start=None, schedule=None, posterior_var="large", ddim_eta=0.0, learn_var=False):
     """One row per sampler iteration i = T-1 ... 0: the grid's (i, lt, ls), is_last, the network evaluations of the step (`resample`: the
     inpainting loop's, None outside it) and the step's DpmCoef (sampler 'dpmpp_2m') / InpaintCoef (inpainting) rows, else None ('consistency':
@@ -1428,6 +1519,72 @@ class GaussianDiffusion:
                              f"init_x {shape}, factor = {N}, gray = {bool(gray)}")
         rst = RestoreState(ops.aligned(obs.to(init_x.device).float().contiguous()), cf, N)
         return self._sample(net=net, init_x=init_x, cond_w=cond_w, record=record, rst=rst)
+
+    # ---- sampling from a noisy or blurred observation (DPS, Chung et al. 2023, Algorithm 1; an extension, no reference call site) ----------
+    @torch.no_grad()
+    def posterior_sample(self, *, net, obs, op, init_x, zeta, record=False, noises=None):
+        """Sample an image whose measurement agrees with obs = A x + noise, A the linear `MeasurementOp` op (`measurement_op`: box means,
+        `restore`'s observation format, or a Gaussian blur), by diffusion posterior sampling: every step t -> s runs the sampler's own update
+        (its clipped x-hat, as in `sample`) and then moves z_s along the gradient of the measurement error of the UNCLIPPED, unguided
+        prediction x-hat(z_t) = c_z z_t + c_o out:
+            e = obs - A x-hat, u = A^T e, g = (d out / d z)^T u;  z_s += 2 zeta / max(|e_b|, FLT_MIN) (c_z u + c_o g)
+        - the paper's x' - zeta_i grad |y - A x-hat|^2 with zeta_i = zeta / |y - A x-hat| - at every step, the last one included.  Per step:
+        a forward that keeps its activations, gmk_dps_backproject, the network's input VJP, the update, gmk_dps_correct; one stream, kernel
+        by kernel, without dropout.  zeta >= 0 is the step size (untuned; 0 gives `sample`'s bits).  Samplers 'ddim' (also with ddim_eta > 0),
+        'noisy' and 'ancestral'; labels (`net` carrying guide=) are allowed, the noise of the stochastic samplers comes from self.rng as in
+        `sample` (`noises`: injected, 'noisy' only).  A ValueError: any other sampler, classifier-free guidance, dyn_threshold, cfg_rescale, a
+        learned variance, a distilled student, mean_type 'eps'.  -> sample()'s triple (with `record` the z after each step's correction and
+        the update's clipped x-hat / eps-hat)."""
+        module, guide, kw_cond_w = _unwrap(net)
+        fixed_w = self.sample_cond_w is not None and float(self.sample_cond_w) != -1.0
+        dps_check(sampler=self.sampler, ddim_eta=self.ddim_eta, mean_type=self.mean_type, cond_w=fixed_w or kw_cond_w is not None,
+                  dyn_threshold=self.dyn_threshold, cfg_rescale=self.cfg_rescale, learned_var=self.posterior_var == "learned",
+                  student=self.teacher_net is not None)
+        zeta = dps_zeta_check(zeta)
+        if not isinstance(op, MeasurementOp):
+            raise ValueError(f"posterior_sample: op = {op!r}, expected a MeasurementOp (measurement_op)")
+        shape = tuple(init_x.shape)
+        if len(shape) != 4 or 0 in shape:
+            raise ValueError(f"posterior_sample: init_x shape {shape}, expected [B, C, H, W] with every dimension > 0")
+        B, n1 = shape[0], math.prod(shape[1:])
+        caps = sampler_caps(self.sampler, self.ddim_eta)
+        sampler_compat_check(caps, noises=noises is not None, n1=n1)
+        if n1 % 4:
+            raise ValueError(f"posterior_sample: {n1} values per image, a multiple of 4 is required")
+        low = ops.box_geometry(shape, op.cf, op.N)[-1] if op.kind == "box" else shape
+        if not isinstance(obs, torch.Tensor) or tuple(obs.shape) != tuple(low):
+            raise ValueError(f"posterior_sample: obs shape {tuple(obs.shape) if isinstance(obs, torch.Tensor) else type(obs).__name__}, "
+                             f"expected {tuple(low)} for init_x {shape} and the {op.kind} operator")
+        dev = init_x.device
+        obs = ops.aligned(obs.to(dev).float().contiguous())
+        plan = sampler_plan(self.num_steps, self.sampler, None, None, self.sample_schedule, self.posterior_var, self.ddim_eta, False)
+        z_t = ops.aligned(init_x.float())
+        # the network's time vector, as in the sampler loop: two buffers alternate, the update kernel fills the next step's
+        lvecs = [torch.full((B,), float(plan[0].lt), device=dev), torch.empty((B,), device=dev)]
+        seed = self.rng.seed
+        zs, xs, es = [], [], []
+        with _EvalForward(module):
+            for f, s in enumerate(plan):
+                off = self.rng._take(B * n1) if caps.noise and noises is None else None
+                store = {}
+                out = module.forward_hip(z_t, lvecs[f & 1], guide, None, ctx=store)
+                u, enorm2 = ops.dps_backproject(out, z_t, obs, s.lt, op, mean_type=self.mean_type)
+                g = module.input_vjp_hip(store, u)
+                kw = dict(want_pred=record, mean_type=self.mean_type, logsnr_next=lvecs[(f + 1) & 1])
+                if caps.update == "sampler_step":
+                    noise = None
+                    if caps.noise == "arg":
+                        noise = ops.aligned(noises[s.i]) if noises is not None else ops.rng_normal(shape, seed, off, dev)
+                    z_s, xp, ep = ops.sampler_step(out, z_t, s.lt, s.ls, s.is_last, noise=noise, **kw)
+                else:
+                    z_s, xp, ep = ops.stochastic_step(out, z_t, s.lt, s.ls, s.sto.coef_z, s.sto.coef_x, s.sto.coef_noise, s.sto.coef_prev,
+                                                      s.is_last, seed, off, **kw)
+                c_z, c_o = dps_coefs(s.lt, self.mean_type)
+                z_t = ops.dps_correct(z_s, u, g, enorm2, c_z, c_o, zeta)
+                if record:
+                    zs.append(z_t); xs.append(xp); es.append(ep)
+                ops.throttle()
+        return (torch.stack(zs), torch.stack(xs), torch.stack(es)) if record else (z_t[None], None, None)
 
     def _inpaint_known(self, mask, shape, device):
         """The shape rules of the inpainting loop ([B, ...], a multiple of 4 values per image), then the mask -> uint8 [B, n] (`_inpaint_mask`)."""

@@ -1179,6 +1179,112 @@ def box_residual(v, z, obs, logsnr_t, cf, N, v_uncond=None, cond_w=None, mean_ty
     return r
 
 
+# ---- diffusion posterior sampling (Chung et al. 2023, Algorithm 1; an extension; gaussian_diffusion.GaussianDiffusion.posterior_sample) ----
+DPS_OPS = {"box": C["GMK_DPS_BOX"], "blur": C["GMK_DPS_BLUR"]}
+BLUR_MAX_R, BLUR_MAX_SIDE = C["GMK_BLUR_MAX_R"], C["GMK_BLUR_MAX_SIDE"]
+
+
+@functools.lru_cache(maxsize=32)
+def _device_taps(taps, device):
+    """The fp32 taps of a blur (a tuple of 2 R + 1 floats) on `device`: made once per operator, not once per sampler step."""
+    return torch.tensor(taps, dtype=torch.float32).to(device)
+
+
+def _blur_check(shape, taps):
+    """-> (B, C, H, W, R) of a blur with `taps` (2 R + 1 floats) on images of `shape`, or ValueError."""
+    if len(shape) != 4 or 0 in shape:
+        raise ValueError(f"blur operator: shape {tuple(shape)}, expected [B, C, H, W] with every dimension > 0")
+    B, C, H, W = (int(d) for d in shape)
+    R = (len(taps) - 1) // 2
+    if len(taps) != 2 * R + 1 or not 1 <= R <= BLUR_MAX_R:
+        raise ValueError(f"blur operator: {len(taps)} taps, expected 2 R + 1 with 1 <= R <= {BLUR_MAX_R}")
+    if H > BLUR_MAX_SIDE or W > BLUR_MAX_SIDE:
+        raise ValueError(f"blur operator: H = {H}, W = {W}, at most {BLUR_MAX_SIDE} (the plane is staged in LDS)")
+    return B, C, H, W, R
+
+
+def gauss_blur(x, taps):
+    """A x of the blur operator (gmk_gauss_blur; an extension): x fp32 [B, C, H, W] with H, W <= 64 -> x's shape, every channel convolved with
+    `taps` (a tuple of 2 R + 1 fp32 values, `gaussian_diffusion.blur_taps`) along its rows, then along its columns, with zero padding: each
+    value a sequential fp32 sum of fmul(tap, value) in tap order."""
+    _f32(x, "x")
+    taps = tuple(float(t) for t in taps)
+    B, C, H, W, R = _blur_check(tuple(x.shape), taps)
+    out = torch.empty_like(x)
+    with _Timed("gauss_blur_kernel", 0.0, _nbytes(x, out), fixed=True):
+        check(lib.gmk_gauss_blur(_p(x), _p(out), _p(_device_taps(taps, x.device)), R, B, C, H, W, _s()), "gauss_blur")
+    return out
+
+
+def measure(x, op):
+    """A x of a `gaussian_diffusion.MeasurementOp`: `box_mean` (kind 'box') or `gauss_blur` (kind 'blur')."""
+    if op.kind == "box":
+        return box_mean(x, op.cf, op.N)
+    if op.kind == "blur":
+        return gauss_blur(x, op.taps)
+    raise ValueError(f"measurement operator of kind {op.kind!r}: expected 'box' or 'blur'")
+
+
+def dps_backproject(v, z, obs, logsnr_t, op, mean_type="v"):
+    """The data term of one DPS step (gmk_dps_backproject): x-hat the UNCLIPPED, unguided data prediction of the network output v at
+    (z, logsnr_t), e = obs - A x-hat, -> (u, enorm2) = (A^T e, fp32 of z's shape; |e_b|^2, fp32 [B]).  v, z: fp32 [B, C, H, W]; obs: what
+    `measure(x, op)` returns for an x of z's shape; op: a `gaussian_diffusion.MeasurementOp`."""
+    if mean_type not in MEAN_TYPES:
+        raise ValueError(f"mean_type {mean_type!r}: expected one of {sorted(MEAN_TYPES)}")
+    if not math.isfinite(float(logsnr_t)):
+        raise ValueError(f"dps_backproject: non-finite time {logsnr_t}")
+    if op.kind not in DPS_OPS:
+        raise ValueError(f"measurement operator of kind {op.kind!r}: expected 'box' or 'blur'")
+    shape = tuple(z.shape)
+    if tuple(v.shape) != shape:
+        raise ValueError(f"v: shape {tuple(v.shape)}, expected z's {shape}")
+    if op.kind == "box":
+        B, C, H, W, cf, N, low = box_geometry(shape, op.cf, op.N)
+        taps, R = None, 0
+    else:
+        B, C, H, W, R = _blur_check(shape, op.taps)
+        cf, N, low = 1, 1, shape
+    if tuple(obs.shape) != tuple(low):
+        raise ValueError(f"obs: shape {tuple(obs.shape)}, expected {tuple(low)}")
+    _f32(v, "v"); _f32(z, "z"); _f32(obs, "obs")
+    if op.kind == "blur":
+        taps = _device_taps(tuple(float(t) for t in op.taps), z.device)
+    u = torch.empty_like(z)
+    enorm2 = torch.empty((B,), device=z.device, dtype=torch.float32)
+    with _Timed("dps_backproject_kernel", 0.0, _nbytes(v, z, obs, u), fixed=True):
+        check(lib.gmk_dps_backproject(_p(v), _p(z), _p(obs), float(logsnr_t), DPS_OPS[op.kind], cf, N, _p(taps), R, _p(u), _p(enorm2),
+                                      MEAN_TYPES[mean_type], B, C, H, W, _s()), "dps_backproject")
+    return u, enorm2
+
+
+def dps_correct(z, u, g, enorm2, c_z, c_o, zeta):
+    """The guidance of one DPS step, in place on z (gmk_dps_correct): z += 2 zeta / max(sqrt(enorm2[b]), FLT_MIN) (c_z u + c_o g) - u, enorm2
+    from `dps_backproject`, g the network's input VJP of u, (c_z, c_o) = d x-hat / d (z, out).  z, u, g: fp32 [B, ...] of one shape with a
+    multiple of 4 values per image; zeta finite, >= 0; zeta = 0 launches nothing.  -> z"""
+    shape = tuple(z.shape)
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f"z: bad shape {shape}, expected [B, ...] with B and every image dimension > 0")
+    B, n = shape[0], math.prod(shape[1:])
+    if n % 4:
+        raise ValueError(f"z: {n} values per image, a multiple of 4 is required")
+    for t, nm in ((u, "u"), (g, "g")):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{nm}: shape {tuple(t.shape)}, expected {shape}")
+    if tuple(enorm2.shape) != (B,):
+        raise ValueError(f"enorm2: shape {tuple(enorm2.shape)}, expected ({B},)")
+    c_z, c_o, zeta = float(c_z), float(c_o), float(zeta)
+    if not (math.isfinite(c_z) and math.isfinite(c_o)):
+        raise ValueError(f"dps_correct: non-finite coefficient c_z = {c_z}, c_o = {c_o}")
+    if not (math.isfinite(zeta) and 0.0 <= zeta < 1e38):
+        raise ValueError(f"dps_correct: zeta = {zeta}, need a finite step size >= 0")
+    _f32(z, "z"); _f32(u, "u"); _f32(g, "g"); _f32(enorm2, "enorm2")
+    if zeta == 0.0:                         # (the entry launches nothing either: a profile records no launch)
+        return z
+    with _Timed("dps_correct_kernel", 0.0, _nbytes(z, u, g, z), fixed=True):
+        check(lib.gmk_dps_correct(_p(z), _p(u), _p(g), _p(enorm2), c_z, c_o, zeta, B, n, _s()), "dps_correct")
+    return z
+
+
 def _step_forms(name, plain, dt, with_ns, head, rest, z, B, thr, ns):
     """One launch of an update that has a thresholded and a restoring form: the entry `plain`, with thr (fp32 [B], dynamic thresholding) `dt`,
     with ns ((r, cf, N), restoration) `with_ns`, never both.  The extra pointer follows `head`, the box geometry `rest`."""

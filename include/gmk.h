@@ -532,6 +532,31 @@ int gmk_dpm_solver_step_ns(const float* v, const float* v_uncond, const float* c
                            float logsnr_t, float logsnr_s, float coef_z, float coef_x, float coef_prev, int is_last, float* z_next,
                            float* x_pred, float* eps_pred, float* z_dup, float* logsnr_next, int mean_type, int B, int64_t n, int C, int H,
                            int W, int cf, int N, void* stream);
+/* Diffusion posterior sampling (DPS: Chung et al. 2023, "Diffusion Posterior Sampling for General Noisy Inverse Problems", Algorithm 1); an
+ * extension, no reference call site.  The observation is y = A x + noise, A linear on NCHW fp32 images, n = C H W:
+ *   GMK_DPS_BOX   the box mean (cf, N) above: y is [B][C / cf][H / N][W / N]; A^T e = fdiv(e[g], (float)k) replicated over the members of box g.
+ *   GMK_DPS_BLUR  a separable Gaussian blur per channel with zero padding, y of the image's shape.  taps: 2 R + 1 device floats, taps[k + R] the
+ *     weight of offset k (the host normalises them), 1 <= R <= GMK_BLUR_MAX_R, H, W <= GMK_BLUR_MAX_SIDE (a plane is staged in LDS).  Rows
+ *     first, t[y][x] = sum_k taps[k + R] x[y][x + k], then columns, out[y][x] = sum_k taps[k + R] t[y + k][x]; each sum starts from 0 and adds
+ *     fmul(tap, value) for k = -R ... R in that order, the terms outside the plane left out.  Symmetric taps make A symmetric: A^T = A.
+ *   gmk_gauss_blur: out = A x.  One workgroup per image, which loops over the channels.
+ *   gmk_dps_backproject: x_hat the UNCLIPPED, unguided data prediction of (v, z, logsnr_t, mean_type) (a clip has zero gradient where the early
+ *     steps saturate), e = fsub(obs, A x_hat), u = A^T e (B x n), enorm2[b] = |e_b|^2: per thread the sequential fp32 sum of fmul(e, e) over
+ *     its elements, then a 256-leaf binary tree in LDS - no atomics, the same call gives the same bits.  One workgroup per image; v and z are
+ *     read once.  The blur is gmk_gauss_blur's device function: its bits.  box: cf, N are read; blur: taps, R.
+ *   gmk_dps_correct: in place, z = fadd(z, fmul(s_b, fadd(fmul(c_z, u), fmul(c_o, g)))), s_b = min(fdiv(2 zeta, max(sqrt(enorm2[b]), FLT_MIN)),
+ *     FLT_MAX) - the paper's step zeta_i = zeta / |y - A x_hat| along -grad |y - A x_hat|^2 = 2 (c_z u + c_o g), g = (d out / d z)^T u the
+ *     network's input VJP and (c_z, c_o) = d x_hat / d (z, out).  n % 4 == 0, 16-byte aligned rows; zeta finite, >= 0; zeta = 0 launches
+ *     nothing (z keeps its bits).  No rows of GMK_KERNEL_TABLE. */
+#define GMK_DPS_BOX 0
+#define GMK_DPS_BLUR 1
+#define GMK_BLUR_MAX_R 15
+#define GMK_BLUR_MAX_SIDE 64
+int gmk_gauss_blur(const float* x, float* out, const float* taps, int R, int B, int C, int H, int W, void* stream);
+int gmk_dps_backproject(const float* v, const float* z, const float* obs, float logsnr_t, int op, int cf, int N, const float* taps, int R,
+                        float* u, float* enorm2, int mean_type, int B, int C, int H, int W, void* stream);
+int gmk_dps_correct(float* z, const float* u, const float* g, const float* enorm2, float c_z, float c_o, float zeta, int B, int64_t n,
+                    void* stream);
 /* RePaint inpainting merge (Lugmayr et al. 2022, Algorithm 1, jump length 1); an extension, no reference call site.  In place on z (B x n,
  * fp32), after the sampler update of a step t -> s has written it.  mask: uint8 B x n in x's element order, nonzero = known pixel; x0: the
  * known image (B x n fp32).  n % 4 == 0.
