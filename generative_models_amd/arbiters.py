@@ -1,14 +1,17 @@
-"""Stand-in feature extractors for the heavy eval (reference gms/main.py:85-90, gms/arbiters/*).
+"""Stand-in feature extractors for the heavy eval (reference gms/main.py:85-90, gms/arbiters/*): the fallback when no file
+is given.
 
-The reference embeds samples and test images with a PRETRAINED autoencoder (64-dim latents: FID, precision / recall) and scores
-class-conditional samples with a pretrained classifier; both are TorchScript blobs that are not part of its checkout
-(`.MISSING_LARGE_BLOBS`) and cannot be produced here (their training scripts and MNIST are out of reach).  When the files named by
-`--autoencoder` / `--classifier` exist they are loaded exactly as the reference does.  When they do not, these two stand-ins keep
-`--eval_heavy 1` running end to end on the HIP path's samples:
+The reference embeds samples and test images with a TRAINED autoencoder (64-dim latents: FID, precision / recall) and scores
+class-conditional samples with a trained classifier; both are TorchScript blobs that are not part of its checkout
+(`.MISSING_LARGE_BLOBS`).  The models behind them are trainable here: `--model=autoencoder` / `--model=classifier`
+(arbiter_models.py, the reference's gms/arbiters classes restated) leave a `model.jit.pt` that `--autoencoder` / `--classifier` load
+exactly as the reference loads its own files, and numbers taken with such a file are logged under the reference's keys
+(`G.arbiters` = "trained", or "reference" for a file from elsewhere).  When the named files do not exist, these two stand-ins keep
+`--eval_heavy 1` running end to end on the HIP path's samples, under keys of their own (`G.arbiters` = "stand-in"):
 
 * `RandomFeatureEncoder` - a fixed-seed, untrained convolutional encoder to 64 features (stock torch ops: evaluation only, far
   off the hot path).  Fréchet distance and k-NN precision / recall in a random-feature space are well-defined and move the right
-  way (tests/test_host_logic.py), but their VALUES are not comparable with numbers taken in the reference's autoencoder space.
+  way (tests/test_host_logic.py), but their VALUES are not comparable with numbers taken in a trained autoencoder's space.
 * `CentroidClassifier` - nearest-class-centroid logits in that feature space, fitted in closed form on labelled real batches
   (one pass over the test set): `classifier_loss` then measures whether a class-conditional sample lands nearer to its own class.
 """

@@ -71,9 +71,10 @@ class GM(nn.Module):
 
 
 _NOT_PLUGIN_FILES = ("__init__", "main", "common")          # the reference's filter on file names (gms/common.py:45)
+_ARBITER_MARK = re.compile(r"^ARBITER_PLUGINS\s*=\s*True\b", flags=re.M)      # a plugin file's own statement that its models are the evaluation's
 
 
-def _plugin_modules(package):
+def _plugin_modules(package, arbiters=False):
     """Dotted names of the package's modules that may define a plugin: file name passes the reference's filter AND the source
     contains a class deriving from something called *GM* (so that discovery does not import kernels / bindings needlessly)."""
     root = Path(importlib.import_module(package).__file__).parent
@@ -84,15 +85,19 @@ def _plugin_modules(package):
             source = path.read_text()
         except OSError:
             continue
+        if _ARBITER_MARK.search(source) and not arbiters:          # arbiters, not generative models: registered for the driver only
+            continue
         if re.search(r"^\s*class\s+\w+\(.*GM\w*\)", source, flags=re.M):
             yield ".".join(path.relative_to(root.parent).with_suffix("").parts)
 
 
-def discover_models(package="generative_models_amd"):
+def discover_models(package="generative_models_amd", arbiters=False):
     """{snake_case(class name): class} for every GM subclass defined in the package (gms/common.py:38-55).  The reference CLI
-    spelling `--model=diffusion` (run_all.sh:16) is registered as an alias of `diffusion_model`."""
+    spelling `--model=diffusion` (run_all.sh:16) is registered as an alias of `diffusion_model`.  arbiters=True (the driver's call) adds
+    the models of plugin files that declare `ARBITER_PLUGINS = True` at module level: the evaluation's own trainable models, `autoencoder`
+    and `classifier` (arbiter_models.py; the reference keeps them apart too, in gms/arbiters/)."""
     found = {}
-    for modname in _plugin_modules(package):
+    for modname in _plugin_modules(package, arbiters):
         for attr, obj in vars(importlib.import_module(modname)).items():
             if isinstance(obj, type) and obj is not GM and issubclass(obj, GM):
                 found[convert_camel_to_snake(attr)] = obj

@@ -19,6 +19,7 @@ generator, `--data mnist` reads the IDX files if they are present; the writer is
 """
 import argparse
 import os
+import re
 import time
 from collections import defaultdict
 from pathlib import Path
@@ -67,6 +68,9 @@ DG.dump_samples = 0        # N > 0: after every checkpoint, N samples as <logdir
 DG.nn_eval = 0             # Q > 0: after every checkpoint, Q samples beside their nearest training images in pixel space (neighbours.py;
                            # data_device 1 and binarize 0 only): eval/nn_dist, eval/nn_dist_test, eval/nn_closer, <logdir>/nearest_neighbours.npz
 DG.nn_k = 3                # neighbours kept per sample (1 .. 8)
+DG.eval_heavy_samples = 0  # N > 0: the heavy evaluation draws at least N samples instead of the reference's 500 and scores them without a distance
+                           # matrix (metrics.eval_heavy_at_scale: also eval/density, eval/coverage, eval/heavy_samples); this rank's shard only
+DG.eval_heavy_k = 3        # neighbours of the k-NN balls of that evaluation (1 .. 8)
 
 SyntheticMNIST = datasets.SyntheticMNIST       # kept importable from here
 
@@ -91,7 +95,7 @@ class FlagSpace:
         """-> (G, Model)"""
         typed = {key: (common.args_type(value), value) for key, value in self.base.items()}
         peek, _ = self._parser(typed).parse_known_args(argv)          # first look: which model, which checkpoint, which logdir
-        registry = common.discover_models()
+        registry = common.discover_models(arbiters=True)
         resuming = peek.resume != Path(".")
         if resuming and peek.weights_from != Path("."):
             raise ValueError(f"--resume {peek.resume} together with --weights_from {peek.weights_from}: a resumed run takes its weights from "
@@ -343,9 +347,23 @@ def _run_device(flag):
     return str(flag)
 
 
+_HPS_MODEL = re.compile(r"^model:[ \t]*['\"]?([A-Za-z0-9_]+)['\"]?[ \t]*$", flags=re.M)
+
+
+def _trained_here(path):
+    """Whether a TorchScript arbiter was saved by this driver: its directory holds the hps.yaml of an --model=autoencoder / classifier run.
+    Only the top-level `model:` line is read, as text: the file sits beside a path the user names, and nothing in it is constructed."""
+    try:
+        found = _HPS_MODEL.search((Path(path).parent / "hps.yaml").read_text())
+    except (OSError, UnicodeDecodeError):
+        return False
+    return found is not None and found.group(1) in ("autoencoder", "classifier")
+
+
 def _feature_extractors(G, device, test_ds=None):
-    """TorchScript autoencoder / classifier of the heavy eval (gms/main.py:86-91) when the files exist.  The reference's weight files
-    are not in its checkout (.MISSING_LARGE_BLOBS): without them the stand-ins of `arbiters.py` take over (a fixed random-feature
+    """TorchScript autoencoder / classifier of the heavy eval (gms/main.py:86-91) when the files exist: trained here with
+    --model=autoencoder / --model=classifier (arbiter_models.py) or brought from elsewhere.  The reference's own weight files
+    are not in its checkout (.MISSING_LARGE_BLOBS): without a file the stand-ins of `arbiters.py` take over (a fixed random-feature
     encoder; a nearest-class-centroid classifier fitted on the labelled test batches), so `--eval_heavy 1` runs end to end."""
     if not G.eval_heavy:
         return None, None
@@ -367,6 +385,8 @@ def _feature_extractors(G, device, test_ds=None):
         classifier = arbiters.CentroidClassifier(arbiters.RandomFeatureEncoder().to(device)).to(device).fit(batches)
     # recorded in hps.yaml next to the flags: which feature space the eval/* numbers of this run live in
     G.arbiters = "stand-in" if (getattr(autoencoder, "stand_in", False) or getattr(classifier, "stand_in", False)) else "reference"
+    if G.arbiters == "reference" and _trained_here(G.autoencoder) and (classifier is None or _trained_here(G.classifier)):
+        G.arbiters = "trained"          # TorchScript files of arbiter_models.py: the reference's architecture and keys, this driver's training run
     return autoencoder, classifier
 
 
@@ -430,6 +450,14 @@ def _check_nn_flags(G, n_train=None):
         raise ValueError(f"--nn_k {G.nn_k}: the training set has {n_train} images")
 
 
+def _check_heavy_flags(G):
+    """The flags of the heavy evaluation at scale, named before any model is built."""
+    if G.eval_heavy_samples < 0:
+        raise ValueError(f"--eval_heavy_samples {G.eval_heavy_samples}: 0 (the reference's 500 samples) or the number N >= 1 of samples to draw")
+    if G.eval_heavy_samples and not 1 <= G.eval_heavy_k <= 8:
+        raise ValueError(f"--eval_heavy_k {G.eval_heavy_k}: 1 .. 8 neighbours per ball")
+
+
 def _check_posthoc_flags(G):
     """The flags of the power-function averages (models that have them), named before any model is built."""
     if "ema_sigma_rel" in G or "ema_snapshot_every" in G:
@@ -468,6 +496,7 @@ def load_model_and_data(argv=None):
     _check_data_flags(G)
     _check_image_flags(G)
     _check_nn_flags(G)
+    _check_heavy_flags(G)
     _check_posthoc_flags(G)
     init_distributed()
     _check_resume_flags(G, Model)                                      # after init_distributed: the state file names its world size

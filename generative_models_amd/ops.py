@@ -1877,6 +1877,57 @@ def nn_search_u8(queries, database, k=1, db_sqnorm=None):
     return dist2, index.long()
 
 
+# ---- k-NN radii and ball counts of fp32 rows (an extension; no reference call site: metrics.manifold_metrics) -----
+KNN_TILE, KNN_SLAB, KNN_MAX_D = C["GMK_KNN_TILE"], C["GMK_KNN_SLAB"], C["GMK_KNN_MAX_D"]
+
+
+def _f32_rows(t, name):
+    """fp32 device tensor [rows, D] -> itself when contiguous (4-byte alignment is enough: a view that starts off a 16-byte boundary takes the
+    kernels' scalar staging path), else a contiguous copy; the ranges of include/gmk.h checked."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError(f"{name}: dtype {getattr(t, 'dtype', type(t))}, expected {torch.float32}")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: expected a device tensor (the HIP path has no CPU fallback)")
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[0] >= 1 << 31:
+        raise ValueError(f"{name}: shape {tuple(t.shape)} (want [rows, D] with 1 .. 2^31 - 1 rows)")
+    if not 1 <= t.shape[1] <= KNN_MAX_D:
+        raise ValueError(f"{name}: rows of D = {t.shape[1]} floats (1 .. {KNN_MAX_D})")
+    return t.contiguous()
+
+
+def knn_radius2(pts, k=3):
+    """-> fp32 [N]: per row the (k + 1)-th smallest value of {d2(pts[i], pts[j]) : all j, j = i included}, the SQUARED distance to the k-th
+    nearest other point (include/gmk.h: gmk_knn_radius_f32; d2 is the ascending fmaf chain of the direct differences)."""
+    pts = _f32_rows(pts, "knn_radius2: pts")
+    N, D = pts.shape
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= NN_MAX_K or k + 1 > N:
+        raise ValueError(f"knn_radius2: k = {k!r} with N = {N} (an integer in 1 .. {NN_MAX_K}, k + 1 at most N)")
+    need = lib.gmk_knn_radius_workspace(N, k)
+    workspace = torch.empty((need // 4,), device=pts.device, dtype=torch.float32)
+    r2 = torch.empty((N,), device=pts.device, dtype=torch.float32)
+    with _Timed("knn_tile_kernel[radius]", 3.0 * N * N * D, _nbytes(pts, r2), fixed=True):
+        check(lib.gmk_knn_radius_f32(_p(pts), N, D, k, _p(workspace), need, _p(r2), _s()), "knn_radius2")
+    return r2
+
+
+def ball_counts(balls, r2, queries, want_q=True, want_m=True):
+    """-> (q_count int32 [Q] or None, m_count int32 [M] or None): q_count[q] = #{j : d2(queries[q], balls[j]) < r2[j]}, m_count[j] = #{q : the
+    same predicate}, strict (include/gmk.h: gmk_ball_counts_f32).  balls [M, D], r2 [M], queries [Q, D]: fp32 device tensors."""
+    balls, queries = _f32_rows(balls, "ball_counts: balls"), _f32_rows(queries, "ball_counts: queries")
+    (M, D), Q = balls.shape, queries.shape[0]
+    if queries.device != balls.device or queries.shape[1] != D:
+        raise ValueError(f"ball_counts: balls {tuple(balls.shape)} on {balls.device}, queries {tuple(queries.shape)} on {queries.device}")
+    if (not isinstance(r2, torch.Tensor) or r2.dtype != torch.float32 or r2.device != balls.device or tuple(r2.shape) != (M,)
+            or not r2.is_contiguous()):
+        raise ValueError(f"ball_counts: r2 {getattr(r2, 'dtype', type(r2))} {tuple(getattr(r2, 'shape', ()))}, expected contiguous "
+                         f"{torch.float32} [{M}] on {balls.device}")
+    q_count = torch.empty((Q,), device=balls.device, dtype=torch.int32) if want_q else None
+    m_count = torch.empty((M,), device=balls.device, dtype=torch.int32) if want_m else None
+    with _Timed("knn_tile_kernel[counts]", 3.0 * M * Q * D, _nbytes(balls, queries, r2, q_count, m_count), fixed=True):
+        check(lib.gmk_ball_counts_f32(_p(balls), _p(r2), M, _p(queries), Q, D, _p(q_count), _p(m_count), _s()), "ball_counts")
+    return q_count, m_count
+
+
 # ---- self-attention core (north_star extension; no reference call site) -----------------------------------------
 def bgemm_nt(A, B, out=None, alpha=1.0, out_dtype=None):
     """C[b] = alpha * A[b] @ B[b]^T for batches of K-contiguous matrices (row / batch strides free): A [batch, M, K],

@@ -826,6 +826,30 @@ int64_t gmk_nn_search_workspace(int64_t Q, int64_t N, int k);
 int gmk_nn_search_u8(const uint8_t* queries, int64_t Q, const uint8_t* database, int64_t N, int D, const int* db_sqnorm, int k,
                      void* workspace, int64_t workspace_bytes, int* dist2_out, int* index_out, void* stream);
 
+/* ---- k-NN radii and ball counts of fp32 rows (no reference call site: metrics.manifold_metrics, the heavy evaluation at a sample count
+ * where the reference's two N x N cdist matrices no longer fit) ----
+ * Both entries use one squared distance of two rows a, b of D floats:  acc = 0;  for i = 0 .. D - 1: t = a[i] - b[i]; acc = fmaf(t, t, acc)
+ * - one fp32 chain in ascending i, a function of the two rows alone (not of the launch shape, gmk_set_cu_limit, or which row is the query):
+ * d2(a, b) == d2(b, a) bit for bit, d2(a, a) == 0, and both kernels give the same bits for the same pair.
+ *   gmk_knn_radius_f32   r2_out[i] = the (k + 1)-th smallest VALUE of the multiset {d2(pts[i], pts[j]) : j = 0 .. N - 1} (j = i, value 0,
+ *                        included): topk(cdist(a, a), k + 1, largest=False)[..., -1] squared.  1 <= k <= GMK_NN_MAX_K, k + 1 <= N < 2^31,
+ *                        1 <= D <= GMK_KNN_MAX_D.  workspace: gmk_knn_radius_workspace(N, k) bytes (-1 for arguments out of range), 4-byte
+ *                        aligned.  One workgroup per (row tile of GMK_KNN_TILE, slab of GMK_KNN_SLAB columns) leaves the k + 1 smallest
+ *                        values per row and slab in the workspace ([slab][k + 1][N] floats), one thread per row merges them.  No atomics:
+ *                        two calls give the same bytes.
+ *   gmk_ball_counts_f32  q_count[q] = #{j : d2(queries[q], balls[j]) < r2[j]} (strict), m_count[j] = #{q : the same predicate}; either
+ *                        may be null.  Both are zeroed by this entry on `stream`, then filled with int32 atomic adds (exact, commutative:
+ *                        a function of the inputs).  1 <= M, Q < 2^31.
+ * Rows are contiguous, 4-byte aligned (16-byte loads when every base is 16-byte aligned and D % 4 == 0).  csrc/knn_f32.hip.  No rows of
+ * GMK_KERNEL_TABLE. */
+#define GMK_KNN_TILE 64
+#define GMK_KNN_SLAB 1024
+#define GMK_KNN_MAX_D 4096
+int64_t gmk_knn_radius_workspace(int64_t N, int k);
+int gmk_knn_radius_f32(const float* pts, int64_t N, int D, int k, void* workspace, int64_t workspace_bytes, float* r2_out, void* stream);
+int gmk_ball_counts_f32(const float* balls, const float* r2, int64_t M, const float* queries, int64_t Q, int D,
+                        int* q_count, int* m_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
